@@ -2,6 +2,7 @@
 """bench.py -- PCM Msamples/s of the resample + ramp + format hot path on MI355X (BASELINE.json).
 
     python bench.py --gpus 1 --steps 5 --warmup 2                  # configs[2], the headline (default)
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full           # ... and everything measured and checked beside it
     python bench.py --config 4                                      # configs[3]: 2048 mixed streams (44.1/96 -> 48 kHz, 2/6/8 channels)
     python bench.py --config 5                                      # configs[4]: FLAC frames -> pack -> resample -> ramp -> S24
     python bench.py --gpus N                                        # N > 1 without a launcher: bench.py starts the N ranks itself
@@ -10,15 +11,20 @@
 
 A "step" is one pass of the hot path over the whole batch a rank owns: every launch the batch needs (one fused
 resample->ramp->pack launch per filter/layout group; config 5 also the FLAC pack), inputs and descriptors already resident in
-HBM.  Streams shard across ranks with no collective.  Rank 0 prints ONE JSON line with `roofline` (HIP events on every
-launch of the step, on the launch stream), `cpu_baseline` (the CPU oracle timed on this host's cores, and the full-size
-bit-exact check of the GPU's output against it) and `cadence` (one 5 ms message per stream per call, the live regime).
-The default line (config 3, one GPU) also carries `configs`: BASELINE configs[3] and configs[4] run in the same process at
-their full size (`--no-extra-configs` skips them), each with its own ms_per_step, roofline fraction and bit-exact check.
-`plan_ms` is the wall time of ohgpu_src_batch_create for the step's batches (the plan is made once and reused by every launch;
-median of three creations, `plan_ms_first` the process's first).
-The CPU oracle (oracle/, tests/oracle_lib.py) is used only for the `cpu_baseline` leg, never on the measured path.  A run
-whose check fails prints the line with `value` null and exits 1.
+HBM.  Streams shard across ranks with no collective.  Rank 0 prints ONE JSON line: `value` (Msamples/s over the timed steps),
+`ms_per_step` and `roofline` (HIP events on every launch of the step, on the launch stream).  A plain run does only that: it
+sets up, runs `--sustain` seconds of launches and the warm-up, times `--steps` steps, writes `--dump-outputs` and prints.
+`--full` adds what is measured or checked beside the headline: `plan_ms` (the wall time of ohgpu_src_batch_create for the
+step's batches -- the plan is made once and reused by every launch; median of three creations, `plan_ms_first` the process's
+first), the shader clock and the stored traffic profile in `roofline`, `cpu_baseline` (the CPU oracle timed on this host's
+cores, and the full-size bit-exact check of the GPU's output against it), `end_to_end` and `cadence` (one 5 ms message per
+stream per call, the live regime).  The default --full line (config 3, one GPU) also carries `configs`: BASELINE configs[3]
+and configs[4] run in the same process at their full size (`--no-extra-configs` skips them), each with its own ms_per_step,
+roofline fraction and bit-exact check.
+The CPU oracle (oracle/, tests/oracle_lib.py) is used only for the `cpu_baseline` leg, never on the measured path.  A --full
+run whose check fails prints the line with `value` null and exits 1.
+`--dump-outputs DIR` writes, after the timed steps, what the last step left in every group's destination arena as .npy files
+(dump_outputs); the inputs are seeded, so two builds given the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -152,25 +158,26 @@ class Group:
         with ThreadPoolExecutor(max(1, min(32, HOST_THREADS or len(os.sched_getaffinity(0))))) as ex:     # (numpy releases the GIL in these passes; a rank's share of the host: main())
             list(ex.map(one, range(len(self.stream_ids))))
 
-    def attach(self, ctx):
+    def attach(self, ctx, full=True):
         self.h = ctx.src_create(self.L, self.M, self.taps, self.coef)
         self.d_src = self.d_src_external if self.d_src_external is not None else ctx.upload(self.src)
         self.d_dst = ctx.malloc(self.dst_bytes)
         ctx.memset(self.d_dst, 0, self.dst_bytes)
         ctx.sync()
         # validation, plan, upload (synchronous): created three times, the median reported -- and the first beside it, which also pays
-        # for what a process pays once (the planner's thread pool starting, the allocator's first pages)
+        # for what a process pays once (the planner's thread pool starting, the allocator's first pages).  Not `full` (a plain bench
+        # run): created once, and no plan figures.
         times = []
-        for k in range(3):
+        for k in range(3 if full else 1):
             if k:
                 ctx.batch_destroy(self.batch)
             t0 = time.perf_counter()
             self.batch = ctx.src_batch(self.h, self.descs, self.src_bytes, self.dst_bytes)
             times.append((time.perf_counter() - t0) * 1e3)
         self.plan_ms_first = times[0]
-        self.plan_ms = sorted(times)[1]
+        self.plan_ms = sorted(times)[len(times) // 2]
         self.info, self.plan = ctx.batch_info(self.batch), ctx.src_plan(self.batch)
-        self.plan_ms_repeat = self._repeat_ms(ctx)
+        self.plan_ms_repeat = self._repeat_ms(ctx) if full else None
 
     def _repeat_ms(self, ctx):
         """What the NEXT period of the same streams costs a caller that keeps its batch: the group's messages one whole period (a
@@ -598,6 +605,37 @@ def end_to_end(ctx, capi, g):
     return out
 
 
+DUMP_SAMPLES = 1 << 22             # --dump-outputs: samples kept over all groups (float32 values + float64 positions: 48 MiB at most)
+
+
+def dump_outputs(capi, ctx, groups, out_dir, prefix=""):
+    """--dump-outputs DIR: what the timed launches left in each group's destination arena (the last step's output, what a caller
+    of ohgpu_src_batch_run receives), decoded to the samples' integer values.  Where a group's output holds more samples than its
+    share of DUMP_SAMPLES, a fixed sample of it: one position per stride, at a seeded offset within the stride (the same positions
+    for the same arguments).  Writes <prefix>g<i>_<rate>hz_<ch>ch.npy (the values: float32 up to 24 bits, float64 above) and
+    ..._index.npy (float64: each value's position among the group's samples, stream by stream, frame by frame, channel by channel)."""
+    os.makedirs(out_dir, exist_ok=True)
+    totals = [len(g.stream_ids) * g.out_total * g.channels for g in groups]
+    for i, (g, total) in enumerate(zip(groups, totals)):
+        keep = min(total, max(1, DUMP_SAMPLES * total // max(1, sum(totals))))
+        if keep == total:
+            idx = np.arange(total, dtype=np.int64)
+        else:
+            stride = total // keep
+            rng = np.random.default_rng(0x5EED + i)
+            idx = np.arange(keep, dtype=np.int64) * stride + rng.integers(0, stride, keep)
+        bps = g.dst_bits // 8
+        raw = ctx.download(g.d_dst, g.dst_bytes).reshape(-1, bps)[idx].astype(np.int64)
+        order = range(bps) if g.dst_endian == capi.ENDIAN_BIG else range(bps - 1, -1, -1)
+        v = np.zeros(idx.size, dtype=np.int64)
+        for b in order:
+            v = (v << 8) | raw[:, b]
+        v = np.where(v >= 1 << (g.dst_bits - 1), v - (1 << g.dst_bits), v)
+        name = f"{prefix}g{i}_{g.rate_in}hz_{g.channels}ch"
+        np.save(os.path.join(out_dir, name + ".npy"), v.astype(np.float32 if g.dst_bits <= 24 else np.float64))
+        np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+
+
 def source_fingerprint():
     """sha256 over the sources of the kernel the headline times (what a stored profile must have been taken from)."""
     import hashlib
@@ -697,7 +735,7 @@ def measure(capi, ctx, args, rank, world, dist, light=False):
     else:
         groups, scaling = build_groups(capi, args, rank, world)
     for g in groups:
-        g.attach(ctx)
+        g.attach(ctx, full=args.full)
     ctx.sync()
 
     def step(events=None):
@@ -746,6 +784,7 @@ def measure(capi, ctx, args, rank, world, dist, light=False):
         tot = torch.tensor([frames_all, subs_all], dtype=torch.float64)
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
         frames_all, subs_all = float(tot[0]), float(tot[1])
+    if dist is not None and args.full:
         # a launch waits for the slowest rank's plan, and config 5's step for the slowest rank's decode: the maxima are the job's
         plan_ms_max, plan_ms_first_max, decode_s_max = slowest_rank(dist, float(sum(g.plan_ms for g in groups)), float(sum(g.plan_ms_first for g in groups)),
                                                                     flac.decode_s if flac is not None else 0.0)
@@ -758,10 +797,14 @@ def measure(capi, ctx, args, rank, world, dist, light=False):
     # per-launch kernel time (HIP events on the launch stream), this rank; and the shader clock the chip holds right behind the
     # timed launches (a 0.2 ms probe kernel, queued before anything lets the chip idle): a slow box shows in the clock or, the clock
     # being the same, in the memory system -- either way not in the build
-    try:
-        clock_mhz = round(ctx.shader_clock_mhz(), 1)
-    except Exception:
-        clock_mhz = None
+    clock_mhz = None
+    if args.full:
+        try:
+            clock_mhz = round(ctx.shader_clock_mhz(), 1)
+        except Exception:
+            pass
+    if args.dump_outputs and not light:
+        dump_outputs(capi, ctx, groups, args.dump_outputs, f"rank{rank}_" if world > 1 else "")
     per_step = np.array([[ctx.elapsed_ms(ev[k][i][0], ev[k][i][1]) for i in range(n_ev)] for k in range(args.steps)], dtype=np.float64)
     grp_ms = [float(per_step[:, i].mean()) for i in range(n_ev)]
     step_kernel_ms = per_step[:, :len(groups)].sum(axis=1)             # per timed step: its launches' kernel time
@@ -775,7 +818,7 @@ def measure(capi, ctx, args, rank, world, dist, light=False):
     achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
     plan_ms = float(sum(g.plan_ms for g in groups))
     plan_ms_first = float(sum(g.plan_ms_first for g in groups))
-    if dist is not None:
+    if dist is not None and args.full:
         plan_ms, plan_ms_first = plan_ms_max, plan_ms_first_max       # (the slowest rank's)
 
     result = None
@@ -802,10 +845,6 @@ def measure(capi, ctx, args, rank, world, dist, light=False):
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "plan_ms": round(plan_ms, 3),                    # ohgpu_src_batch_create for the step's batches (median of three creations): once, reused by every launch
-            "plan_ms_first": round(plan_ms_first, 3),        # ... and the process's first creation of them
-            # ... and what the same batch costs for the next period of the same streams (ohgpu_src_batch_advance + _set_ramps)
-            "plan_ms_repeat": (round(float(sum(g.plan_ms_repeat for g in groups)), 3) if all(g.plan_ms_repeat is not None for g in groups) else None),
             "msubsamples_per_s": round(subs_all * args.steps / elapsed / 1e6, 3),   # frames x channels
             "higher_is_better": True,
             "scaling": scaling,
@@ -820,7 +859,7 @@ def measure(capi, ctx, args, rank, world, dist, light=False):
                        "groups": [{"rate_in": g.rate_in, "channels": g.channels, "src_bits": g.src_bits, "streams": len(g.stream_ids),
                                    "taps_per_phase": g.taps, "frames_per_stream": g.in_frames, "msgs": int(g.info["n_msgs"]),
                                    "kernel_ms": round(grp_ms[i], 4), "gbps": round(g.algorithmic_bytes / (grp_ms[i] * 1e-3) / 1e9, 1),
-                                   "plan_ms": round(g.plan_ms, 3),
+                                   **({"plan_ms": round(g.plan_ms, 3)} if args.full else {}),
                                    "block_kernel_out_frames": g.plan["block_kernel_out_frames"], "generic_pieces": g.plan["generic_pieces"]}
                                   for i, g in enumerate(groups)],
                        "sharding": f"streams over {world} rank(s), no collective"},
@@ -839,9 +878,15 @@ def measure(capi, ctx, args, rank, world, dist, light=False):
                          "fp64_tflops": round(flops / (kernel_ms * 1e-3) / 1e12, 2), "fp64_peak_tflops": 78.6,
                          "fp64_frac": round(flops / (kernel_ms * 1e-3) / 1e12 / 78.6, 4)},
         }
+        if args.full:
+            result.update({
+                "plan_ms": round(plan_ms, 3),                # ohgpu_src_batch_create for the step's batches (median of three creations): once, reused by every launch
+                "plan_ms_first": round(plan_ms_first, 3),    # ... and the process's first creation of them
+                # ... and what the same batch costs for the next period of the same streams (ohgpu_src_batch_advance + _set_ramps)
+                "plan_ms_repeat": (round(float(sum(g.plan_ms_repeat for g in groups)), 3) if all(g.plan_ms_repeat is not None for g in groups) else None)})
         if flac is not None:
             result["config"]["flac"] = flac.report(grp_ms[-1])
-            if dist is not None:
+            if dist is not None and args.full:
                 result["config"]["flac"]["host_decode"]["seconds_max_over_ranks"] = round(decode_s_max, 3)
         share = getattr(args, "host_share", None)
         if share is not None:
@@ -851,7 +896,7 @@ def measure(capi, ctx, args, rank, world, dist, light=False):
                               "pinned_to_cpus_near_gpu": (f"{len(share['cpus'])} CPUs" if (world > 1 and share["cpus"]) else None),
                               "plan_ms": "max over ranks" if world > 1 else "this rank"}
         pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")
-        if os.path.exists(pmc) and args.config == 3 and world == 1:
+        if args.full and os.path.exists(pmc) and args.config == 3 and world == 1:
             # `traffic` is a counter measurement of THIS workload taken in separate --pmc passes (tools/profile_bench.sh), not of
             # this run: it is quoted only while the kernel's sources are the ones that profile was taken from
             try:
@@ -862,7 +907,9 @@ def measure(capi, ctx, args, rank, world, dist, light=False):
                     result["roofline"]["traffic_source"] = "stored profile, not this run: " + str(p.get("source"))
             except Exception:
                 pass
-        if world == 1 and not args.no_cpu:
+        if not args.full:
+            pass                                             # (a plain run: the headline alone -- no baseline, no check, no side legs)
+        elif world == 1 and not args.no_cpu:
             got = [ctx.download(g.d_dst, g.dst_bytes) for g in groups]
             if not light:
                 try:                                         # (reported extras: never let them cost the headline line)
@@ -900,8 +947,11 @@ def main():
     ap.add_argument("--seconds", type=float, default=None, help="audio per stream (default: 10 s)")
     ap.add_argument("--streams", type=int, default=None, help="config 3/5: streams per GPU (256); config 4: streams in all (2048)")
     ap.add_argument("--variant", type=int, default=0, help="kernel variant (0 tuned, 1 generic v1, 4 round 2's lean kernel; 2 and 5 -- round 1's block kernel, round 4's unit-per-wave matrix kernel -- in a legacy build only)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline / check, end_to_end and cadence legs (profiling runs)")
-    ap.add_argument("--no-extra-configs", action="store_true", help="the default line without its `configs` object (configs[3] and configs[4] at full size)")
+    ap.add_argument("--full", action="store_true", help="beside the headline: plan timings, the shader clock, the stored traffic profile, the "
+                    "cpu_baseline leg and its bit-exact check, end_to_end, cadence and (default line) the extra configs; a plain run times the steps alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed to DIR/*.npy (a fixed sample of it)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline / check, end_to_end and cadence legs (profiling runs)")
+    ap.add_argument("--no-extra-configs", action="store_true", help="--full: the default line without its `configs` object (configs[3] and configs[4] at full size)")
     ap.add_argument("--sustain", type=float, default=1.0, help="seconds of back-to-back launches before the warm-up and the timed steps, so that they see the clock the chip holds under this load")
     ap.add_argument("--channels", type=int, default=2, help="config 3: channels per stream (the headline is stereo)")
     ap.add_argument("--rate-in", type=int, default=44100, help="config 3: input rate (the headline is 44100)")
@@ -949,16 +999,16 @@ def main():
         capi.set_plan_threads(min(16, share["threads"]))
     args.host_share = share
     result, ok = measure(capi, ctx, args, rank, world, dist)
-    # The default line (config 3, one GPU, sizes untouched) also carries BASELINE configs[3] and configs[4], at their full size
+    # The default --full line (config 3, one GPU, sizes untouched) also carries BASELINE configs[3] and configs[4], at their full size
     # (2048 streams x 10 s; 256 FLAC streams x 10 s), same process, each with its own sustain phase, steps and whole-step check.
-    if rank == 0 and world == 1 and args.config == 3 and not explicit and not args.no_extra_configs and not args.no_cpu \
+    if args.full and rank == 0 and world == 1 and args.config == 3 and not explicit and not args.no_extra_configs and not args.no_cpu \
             and args.channels == 2 and args.rate_in == 44100 and args.src_bits == BITS:
         result["configs"] = {}
         for cfg in (4, 5):
             t0 = time.perf_counter()
             try:
                 sub = argparse.Namespace(**vars(args))
-                sub.config, sub.streams, sub.sustain = cfg, (2048 if cfg == 4 else 256), 0.5
+                sub.config, sub.streams, sub.sustain, sub.dump_outputs = cfg, (2048 if cfg == 4 else 256), 0.5, None
                 r, sub_ok = measure(capi, ctx, sub, rank, world, dist, light=True)
                 ok = ok and sub_ok
                 entry = {"metric": r["metric"], "workload": r["config"]["workload"], "value": r["value"], "ms_per_step": r["ms_per_step"],

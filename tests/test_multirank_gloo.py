@@ -79,7 +79,7 @@ def test_bench_runs_under_the_launcher_with_two_ranks_on_a_gpu(config):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", str(config), "--steps", "2", "--warmup", "1",
-           "--seconds", "0.3", "--streams", "24" if config == 4 else "6", "--sustain", "0"]
+           "--seconds", "0.3", "--streams", "24" if config == 4 else "6", "--sustain", "0", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -98,7 +98,7 @@ def test_bench_starts_its_own_ranks_when_asked_for_two_gpus():
     torch.distributed.run, before this process has loaded the C ABI), relays rank 0's line and the child's exit code.  Two
     ranks share the box's one GPU here; every rank checks its first stream against the oracle."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--seconds", "0.3", "--streams", "6", "--sustain", "0"]
+           "--seconds", "0.3", "--streams", "6", "--sustain", "0", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]

@@ -10,4 +10,4 @@ $CC -x hip -c ohpipeline_amd/csrc/src_plan.cpp -o /tmp/pt_plan.o || exit 1
 TAG=$(ls -t $OBJ/ohgpu_api.hip.*.o | head -1 | sed 's/.*ohgpu_api\.hip\.\([0-9a-f]*\)\..*/\1/')
 objs=$(ls $OBJ/*.$TAG.*.o | grep -v -e ohgpu_api -e src_plan)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ohpipeline_amd/lib/libohgpu.so $objs /tmp/pt_api.o /tmp/pt_plan.o || exit 1
-python3 bench.py --steps 3 --warmup 1 --no-cpu --no-extra-configs --sustain 0.05 2>&1 | grep -o "\[plan timing\].*\|\"plan_ms\": [0-9.]*" | head -20
+python3 bench.py --full --steps 3 --warmup 1 --no-cpu --no-extra-configs --sustain 0.05 2>&1 | grep -o "\[plan timing\].*\|\"plan_ms\": [0-9.]*" | head -20

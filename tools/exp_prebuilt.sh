@@ -11,7 +11,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   for tag in "$@"; do
     if [ "$tag" = base ]; then cp /tmp/libohgpu.base.so $LIB; else cp ohpipeline_amd/lib/variants/libohgpu.$tag.so $LIB || continue; fi
     echo -n "[$tag] "
-    timeout -k 10 150 python3 bench.py --steps $STEPS --warmup 20 --no-cpu --no-extra-configs ${EXP_ARGS} 2> /tmp/exp_err.txt | python3 -c "
+    timeout -k 10 150 python3 bench.py --full --steps $STEPS --warmup 20 --no-cpu --no-extra-configs ${EXP_ARGS} 2> /tmp/exp_err.txt | python3 -c "
 import json,sys
 t=sys.stdin.read()
 try:

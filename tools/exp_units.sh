@@ -7,7 +7,7 @@ trap 'python3 ohpipeline_amd/build.py --force > /dev/null 2>&1' EXIT     # an in
 OHGPU_EXTRA_FLAGS="-DOHGPU_DIAG -DOHGPU_DIAG_ONE_KERNEL" python3 ohpipeline_amd/build.py --force > /dev/null 2>&1 || { echo "build failed"; exit 1; }
 for envs in "OHGPU_DIAG_KB_MAX=1" "OHGPU_DIAG_KB_MAX=2" "OHGPU_DIAG_KB_MAX=3" "OHGPU_DIAG_KB_MAX=8 OHGPU_DIAG_TAIL_ROUNDS=1.5" "OHGPU_DIAG_KB_MAX=8 OHGPU_DIAG_TAIL_ROUNDS=0.6" "OHGPU_DIAG_KB_MAX=1" "OHGPU_DIAG_KB_MAX=3"; do
   echo -n "$envs: "
-  env $envs timeout -k 10 120 python3 bench.py --steps 300 --warmup 20 --no-cpu | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['roofline']['kernel_avg_ms'], d['roofline']['frac'], d['plan_ms'])"
+  env $envs timeout -k 10 120 python3 bench.py --full --steps 300 --warmup 20 --no-cpu | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['roofline']['kernel_avg_ms'], d['roofline']['frac'], d['plan_ms'])"
 done
 OHGPU_EXTRA_FLAGS="-DOHGPU_DIAG -DOHGPU_DIAG_ONE_KERNEL -DOHGPU_DIAG_STAMP" python3 ohpipeline_amd/build.py --force > /dev/null 2>&1 || { echo "stamp build failed"; exit 1; }
 for envs in "OHGPU_DIAG_KB_MAX=1" "OHGPU_DIAG_KB_MAX=3" "OHGPU_DIAG_KB_MAX=8 OHGPU_DIAG_TAIL_ROUNDS=0.6"; do
