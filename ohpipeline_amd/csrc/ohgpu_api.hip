@@ -14,7 +14,6 @@
 #include <unistd.h>
 
 #include <atomic>
-#include <chrono>
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -241,10 +240,14 @@ int ohgpu_device_pci_bus_id(ohgpu_ctx* ctx, char* buf, size_t buf_bytes)
     return OHGPU_OK;
 }
 
+// Variants 2 and 5 named kernels the library no longer has (round 1's block kernel, round 4's unit-per-wave matrix kernel); they
+// are accepted as aliases of 4, and nothing past this point sees them.
+static int kernel_variant_alias(int variant) { return variant == 2 || variant == 5 ? 4 : variant; }
+
 int ohgpu_set_kernel_variant(ohgpu_ctx* ctx, int variant)
 {
     if (!ctx || variant < 0 || variant > 5) return set_error(OHGPU_ERR_INVALID, "ohgpu_set_kernel_variant: bad argument");
-    ctx->variant = variant;
+    ctx->variant = kernel_variant_alias(variant);
     return OHGPU_OK;
 }
 
@@ -913,7 +916,7 @@ bool src_describe(uint32_t L, uint32_t M, uint32_t T, const int32_t* coef_q28, o
     const uint32_t mf_L_blk = (T == 32 || s->halfband) ? src_block_outputs(L, 6) : 0;
     std::vector<uint8_t> adig;
     s->mf_halfband = false;
-    s->mf_L_blk = 0; s->mf_kb_cap = 0;
+    s->mf_L_blk = 0;
     if (mf_L_blk != 0 && s->halfband) {
         tables->made = build_mfma_halfband(coef_q28, mf_L_blk, &tables->steps, &tables->amat);
         s->mf_halfband = tables->made;
@@ -921,10 +924,7 @@ bool src_describe(uint32_t L, uint32_t M, uint32_t T, const int32_t* coef_q28, o
         build_mfma_images(adig, tables->steps, L, &tables->amat);
         tables->made = true;
     }
-    if (tables->made) {
-        s->mf_L_blk = mf_L_blk;
-        s->mf_kb_cap = s->mf_halfband ? 1 : 8;
-    }
+    if (tables->made) s->mf_L_blk = mf_L_blk;
     return true;
 }
 }  // namespace
@@ -1075,10 +1075,6 @@ int src_check_and_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_src_msg_desc*
         b->dst_bits = d0.dst_bits; b->dst_endian = d0.dst_endian;
         b->src_planar = (d0.flags & OHGPU_FLAG_SRC_PLANAR32) != 0;
     };
-#ifdef OHGPU_PLAN_TIMING
-    const auto tp0 = std::chrono::steady_clock::now();
-    auto since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
-#endif
     // A large batch is 64 bytes a message to read -- 32 MB for the headline's half a million -- and both the checks and the planner's
     // cut into segments are bound by exactly that.  So the planner is let loose on the messages FIRST, on the usual caller's terms
     // (one layout, streams one after the other in time order), and checks each message itself the first time it looks at it; a batch
@@ -1091,9 +1087,6 @@ int src_check_and_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_src_msg_desc*
         PlanFusedCheck fused;
         fused.src = src;
         const int err = plan_src_fast(ctx, b, descs, n, true, digest, &fused);
-#ifdef OHGPU_PLAN_TIMING
-        fprintf(stderr, "[plan timing] check fused with the plan: %.2f ms (checked %d, retry %d)\n", since(tp0), (int)fused.checked, (int)fused.retry);
-#endif
         if (err != OHGPU_OK) return err;
         if (fused.checked && fused.total.err != OHGPU_OK) return set_error(fused.total.err, "%s", fused.total.msg);
         if (fused.checked && !fused.retry) {
@@ -1123,15 +1116,8 @@ int src_check_and_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_src_msg_desc*
         }
         if (n > 0) layout_of_first();
     }
-#ifdef OHGPU_PLAN_TIMING
-    const auto tp1 = std::chrono::steady_clock::now();
-    fprintf(stderr, "[plan timing] validate%s %.2f ms\n", dev ? "+convert" : "", since(tp0));
-#endif
     int err = OHGPU_OK;
     if (b->uniform && n > 0) err = plan_src_fast(ctx, b, descs, n, ordered, digest);
-#ifdef OHGPU_PLAN_TIMING
-    fprintf(stderr, "[plan timing] plan_src_fast %.2f ms\n", since(tp1));
-#endif
     return err;
 }
 
@@ -1255,12 +1241,11 @@ int ohgpu_src_plan_digest(uint32_t L, uint32_t M, uint32_t taps_per_phase, const
         flt.max_sum_abs = (int64_t)1 << 28;
         flt.halfband = false;
         flt.mf_L_blk = taps_per_phase == 32 ? src_block_outputs(L, 6) : 0;
-        flt.mf_kb_cap = 8;
         tables.made = flt.mf_L_blk != 0;
     }
     flt.d_mf_amat = tables.made ? (uint8_t*)&flt : nullptr;         // (only its being there is looked at)
     ohgpu_ctx ctx{};
-    ctx.variant = kernel_variant;
+    ctx.variant = kernel_variant_alias(kernel_variant);
     ctx.num_cus = num_cus > 0 ? num_cus : 256;
     ohgpu_batch b;
     b.kind = kBatchSrc; b.n = n; b.src = &flt; b.src_arena_bytes = src_arena_bytes; b.dst_arena_bytes = dst_arena_bytes; b.uniform = true;
@@ -1295,7 +1280,7 @@ int ohgpu_src_batch_units(const ohgpu_batch* b, uint64_t* units, uint64_t* long_
 
 // Which kernel runs a (uniform) resampled batch's whole blocks: ONE decision, taken from the plan (what it serves: made under the
 // variant in force at creation) and the variant in force NOW, and used by the launch and by the name a benchmark prints alike.
-enum SrcKernel { kSrcGeneric, kSrcWg, kSrcMfma, kSrcLean, kSrcBlock };
+enum SrcKernel { kSrcGeneric, kSrcWg, kSrcLean, kSrcBlock };
 static SrcKernel src_kernel_choice(const ohgpu_ctx* ctx, const ohgpu_batch* b, bool arena_aligned = true)
 {
     const int v = ctx->variant;
@@ -1303,21 +1288,14 @@ static SrcKernel src_kernel_choice(const ohgpu_ctx* ctx, const ohgpu_batch* b, b
     // a variant that asks for another)
     if (v == 1 || !b->fast.enabled || !arena_aligned || (b->fast.wg_only && v != 0)) return kSrcGeneric;
     if (b->fast.mfma_wg && v == 0) return kSrcWg;                                         // the taps on the matrix pipe (round 4), a unit per workgroup
-#ifdef OHGPU_LEGACY_KERNELS
-    if (b->fast.mfma && (v == 0 || v == 3 || v == 5)) return kSrcMfma;                   // ... a unit per wave (variant 5, and where the workgroup kernel's block geometry does not hold)
-    if (b->fast.lean && (v != 2 || b->fast.lean_only || !b->fast.d_work)) return kSrcLean;   // round 2's, under every variant but 2 -- and under 2 where round 1's has no layout or no tables
-    if (b->fast.d_work) return kSrcBlock;                                                  // round 1's (variant 2; a filter beyond the lean kernel's rounding bound under any)
-#else
-    if (b->fast.lean) return kSrcLean;                                                     // round 2's, under every other variant (rounds 1's and 4's unit-per-wave kernels as variants: legacy builds)
+    if (b->fast.lean) return kSrcLean;                                                     // round 2's, under every other variant
     if (b->fast.d_work) return kSrcBlock;                                                  // round 1's: the fallback for a filter beyond the lean kernel's rounding bound
-#endif
     return kSrcGeneric;
 }
 static const char* src_kernel_name(SrcKernel k)
 {
     switch (k) {
     case kSrcWg: return "src_mfma_wg_kernel";
-    case kSrcMfma: return "src_mfma_kernel";
     case kSrcLean: return "src_lean_kernel";
     case kSrcBlock: return "src_block_kernel";
     default: return "src_kernel_v1";
@@ -1454,9 +1432,6 @@ static int src_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* s
             OHGPU_HIP_TRY(launch_src_mfma_wg(ctx, batch, (const uint8_t*)src_base, (uint8_t*)dst_base, s, one_launch ? &x : nullptr));
             break;
         }
-#ifdef OHGPU_LEGACY_KERNELS
-        case kSrcMfma: OHGPU_HIP_TRY(launch_src_mfma(ctx, batch, (const uint8_t*)src_base, (uint8_t*)dst_base, s)); break;
-#endif
         case kSrcBlock: OHGPU_HIP_TRY(launch_src_block(ctx, batch, (const uint8_t*)src_base, (uint8_t*)dst_base, s)); break;
         default: OHGPU_HIP_TRY(launch_src_lean(ctx, batch, (const uint8_t*)src_base, (uint8_t*)dst_base, s)); break;
         }

@@ -96,7 +96,7 @@ struct RampJob {              // ramp_plane_kernel: frames [i0, i0 + count) of o
     uint8_t  pad[3];
 };
 static_assert(sizeof(SegMsg) == 24 && sizeof(SrcWork) == 32 && sizeof(SrcSeg) == 24 && sizeof(LeanUnit) == 32 && sizeof(RampJob) == 32, "plan layouts");
-struct MfStep {               // src_mfma_kernel: one step = 16 consecutive output frames of a row (the same for every row: rows start at phase 0)
+struct MfStep {               // the matrix-pipe tables: one step = 16 consecutive output frames of a row (the same for every row: rows start at phase 0)
     uint32_t aoff[16];        // output m's A row: byte offset into a digit's table, phase * 96 + (31 + k0 - n0(m))
     uint32_t b0[16], b1[16], b2[16];   // its accumulators' initial values: bits 0..15 and (signed) bits 16.. of 32896 * sum(c[phase]) + 2^27 -- below 2^28, so
                               // that class 2's accumulator holds them beside its own 2^22 -- and zero (b2: a third read per tile until round 4's end)
@@ -132,12 +132,11 @@ struct SrcFastPlan {
     uint32_t max_waves = 0;       // waves per workgroup the LDS allows (<= 12)
     uint32_t ring_bytes = 0;      // bytes of packed output a block row's LDS ring holds
     bool     lean = false;        // the batch runs on src_lean_kernel (round 2) rather than src_block_kernel
-    bool     lean_only = false;   // ... and round 1's kernel has no instantiation for its layout (variant 2 then runs the lean kernel too)
+    bool     lean_only = false;   // ... and round 1's main list has no instantiation for its layout
     bool     lean_halfband = false;   // ... in its half-band form (the filter is one AND the layout has that instantiation): LDS sizing and dispatch agree on this
     bool     wg_only = false;     // ... or no block kernel but src_mfma_wg_kernel has one: any variant that asks for another kernel gets the generic one
     uint32_t lean_coef_lds_bytes = 0, lean_wave_lds_bytes = 0, lean_max_waves = 0;
-    bool     mfma = false;        // ... and its layout is one src_mfma_kernel (round 4) serves: same units and planes, the filter's digit tables
-    bool     mfma_wg = false;     // ... as src_mfma_wg_kernel cuts them: one unit per workgroup (rows of ONE block; the units whose input image leaves the arena -- kWorkEdge, in front of the list -- run on it too, through its checked loads)
+    bool     mfma_wg = false;     // ... and src_mfma_wg_kernel runs the lean kernel's units (the filter's digit tables) as it cuts them: one unit per workgroup (rows of ONE block; the units whose input image leaves the arena -- kWorkEdge, in front of the list -- run on it too, through its checked loads)
     bool     mfma_wg_halfband = false;   // ... in its half-band form (the filter's tables are build_mfma_halfband's)
     uint32_t wg_unit_rows = 0;    // ... and the rows its units were cut to (WgGeom::kUnitRows: the launch checks)
     const void* d_mf_amat = nullptr;   // (owned by the ohgpu_src)
@@ -358,11 +357,11 @@ struct ohgpu_src {
                                   // lean kernel's half-band instantiations multiply by the 33 taps that are not
     double*  d_coef;              // [L][T] exact integer-valued doubles (Q28)
     int32_t* d_coef_q28;          // [L][T] int32
-    // src_mfma_kernel's tables (T = 32 filters whose ratio the 16-output tiling holds; null otherwise), made for blocks of
-    // mf_L_blk outputs and rows of up to mf_kb_cap blocks
+    // the matrix-pipe tables (T = 32 filters whose ratio the 16-output tiling holds, and half-band filters; null otherwise), made for
+    // blocks of mf_L_blk outputs
     uint8_t* d_mf_amat = nullptr; // the steps' A operands, lane-linear: [step][4 digits][64 lanes][16 bytes] (build_mfma_images)
     ohgpu::MfStep* d_mf_steps = nullptr;
-    uint32_t mf_L_blk = 0, mf_kb_cap = 0;
+    uint32_t mf_L_blk = 0;
     bool     mf_halfband = false; // ... in the half-band form: one coefficient image for every step (build_mfma_halfband)
 };
 
@@ -456,7 +455,6 @@ hipError_t launch_src_v1(const ohgpu_ctx* ctx, const void* d_descs, size_t n, co
                          const uint8_t* src, uint8_t* dst, hipStream_t s);
 hipError_t launch_src_block(const ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
 hipError_t launch_src_lean(const ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
-hipError_t launch_src_mfma(const ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s, uint32_t first_unit = 0);   // csrc/src_mfma_kernel.hip, legacy builds only (units [first_unit, n_lean))
 // (`query`: nothing is launched; the instantiation the batch would run is asked what the device grants it -- ohgpu_src_batch_occupancy)
 // (`start` / `stop`: the launch itself carries the two events -- hipExtLaunchKernelGGL: its dispatch's own timestamps, no packet more
 // in the queue -- ohgpu_src_batch_run_timed)
@@ -469,7 +467,6 @@ bool build_mfma_tables(uint32_t L, uint32_t M, uint32_t T, const int32_t* coef_q
                        std::vector<uint8_t>* adig, std::vector<MfStep>* steps);
 void build_mfma_images(const std::vector<uint8_t>& adig, const std::vector<MfStep>& steps, uint32_t L, std::vector<uint8_t>* amat);
 bool src_mfma_supported(uint32_t T, uint32_t ch, uint32_t sb, uint32_t db);
-void src_mfma_geometry(uint32_t* rows, uint32_t* wave_lds_bytes, uint32_t* max_waves);
 uint32_t src_block_outputs(uint32_t L, uint32_t fb_dst);      // outputs per block (0: no block length fits): whole phase periods, >= 128, whole 64-byte lines
 hipError_t launch_ramp_planes(const ohgpu_ctx* ctx, const void* d_jobs, uint32_t n_jobs, void* d_planes, hipStream_t s);   // csrc/ramp_plane_kernel.hip
 hipError_t load_ramp_plane_kernel();
@@ -477,7 +474,7 @@ bool src_lean_geometry(uint32_t L, uint32_t T, bool halfband, uint32_t ch, uint3
                        uint32_t* rows, uint32_t* in_blocks, uint32_t* stage_frames, uint32_t* ring_bytes, uint32_t* coef_lds_bytes,
                        uint32_t* wave_lds_bytes, uint32_t* max_waves);
 bool src_block_supported(uint32_t T, uint32_t ch, uint32_t sb, uint32_t src_le, uint32_t db, uint32_t dst_le);
-bool src_block_built(uint32_t T, uint32_t ch, uint32_t sb, uint32_t src_le, uint32_t db, uint32_t dst_le);   // ... and round 1's kernel itself is in this library for the layout (the fallback list; a legacy build: the whole list)
+bool src_block_built(uint32_t T, uint32_t ch, uint32_t sb, uint32_t src_le, uint32_t db, uint32_t dst_le);   // ... and round 1's kernel itself is in this library for the layout (the fallback list)
 bool src_lean_only_supported(uint32_t T, uint32_t ch, uint32_t sb, uint32_t src_le, uint32_t db, uint32_t dst_le);
 bool src_lean_halfband_supported(uint32_t T, uint32_t ch, uint32_t sb, uint32_t src_le, uint32_t db, uint32_t dst_le);
 bool src_block_geometry(uint32_t L, uint32_t T, uint32_t ch, uint32_t sb, uint32_t db, uint32_t out_per_drain,

@@ -685,11 +685,7 @@ static hipError_t launch_line(const ohgpu_ctx* ctx, const ohgpu_batch* b, uint32
     // - / 0.150 / 0.152, the sender's S32 -> S24 pack 0.168 / - / 0.156 / 0.160 --; 512 k 0.261 / 0.262 / 0.265 / 0.279, S32 -> S24
     // 0.310 / 0.312 / 0.323 / 0.335; 1 M within the noise.  Round 5's profiles of the Songcast and sender-pack benches are what
     // showed it (6 % behind round 3's on a launch size the occupancy had not been tried on).
-#ifdef OHGPU_LINE_GROUPS_PER_CU
-    const uint32_t per_cu = OHGPU_LINE_GROUPS_PER_CU;
-#else
     const uint32_t per_cu = heavy_percent >= 30u || count < 400000u ? 6u : 4u;
-#endif
     if (grid > cus * per_cu) grid = cus * per_cu;
     hipLaunchKernelGGL((pcm_line_kernel<SB, DB>), dim3(grid), dim3(kLineWaves * 64), 0, s,
                        (const PcmChunk*)b->line.d_chunks + first, count, src, dst, ctx->d_ramp_table, (const uint8_t*)b->line.d_prefix);

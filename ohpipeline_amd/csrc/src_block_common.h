@@ -43,15 +43,13 @@ static constexpr uint32_t kRampLdsBytes = 1024;         // RampArray.h's 512 Q15
 // the bytes that are USED span at most 15 + frames * fb_src bytes.  Stereo rows drift against the banks by themselves (the
 // rows of a unit are M_blk frames apart, never a whole number of pieces for the stereo layouts); wider frames get an
 // odd count so that the rows start in different banks.
-#ifndef OHGPU_LEAN_STAGE_FRAMES
-#define OHGPU_LEAN_STAGE_FRAMES 16
-#endif
-// frames per stage: stereo rows take OHGPU_LEAN_STAGE_FRAMES at a time (each row's request then covers most of a 128-byte
+static constexpr int kLeanStageFrames = 16;
+// frames per stage: stereo rows take kLeanStageFrames at a time (each row's request then covers most of a 128-byte
 // line: with 8 frames -- 48 bytes of a 6-byte-frame row -- every line was requested by three or four stages and fetched
 // from memory 1.8 times), wider frames 8
 // (mono and the odd channel counts: 16 frames too -- a stage must advance every row by whole 16-byte pieces, and 8 frames of
 // 3, 9, 15 or 21 bytes do not)
-static constexpr int lean_stage_frames(int ch) { return (ch <= 2 || (ch & 1)) ? OHGPU_LEAN_STAGE_FRAMES : 8; }
+static constexpr int lean_stage_frames(int ch) { return (ch <= 2 || (ch & 1)) ? kLeanStageFrames : 8; }
 static constexpr int lean_in_blocks(int ch, int sb)
 {
     const int n = (lean_stage_frames(ch) * ch * sb + 14) / 16 + 1;
@@ -69,14 +67,10 @@ enum { kWorkRamped = 1u,      // a ramped message overlaps the unit's output ran
 }  // namespace ohgpu
 
 // ---- instantiations: (T, channels, source bytes, source LE, destination bytes, destination LE) ----
-// The list is compiled in parts so that the build can run them side by side (ohpipeline_amd/build.py compiles each kernel
-// file once per part with -DOHGPU_BLOCK_PART=k): part 1 also holds the host code and only DECLARES the other parts' kernels;
-// parts 2.. hold nothing but their kernels.  Without the macro (tools, tests) a file is one translation unit.
-#ifdef OHGPU_DIAG_ONE_KERNEL
-#define OHGPU_BLOCK_KERNELS_1(X) X(32, 2, 3, true, 3, false)
-#define OHGPU_BLOCK_KERNELS_2(X)
-#define OHGPU_BLOCK_KERNELS_3(X)
-#else
+// OHGPU_BLOCK_KERNELS is the lean kernel's main list and the planner's layout classification (src_block_supported).  The lean
+// kernel is compiled in parts so that the build can run them side by side (ohpipeline_amd/build.py compiles src_lean_kernel.hip
+// once per part with -DOHGPU_BLOCK_PART=k): part 1 also holds the host code and only DECLARES the other parts' kernels;
+// parts 2.. hold nothing but their kernels.  Without the macro (tools, tests) the file is one translation unit.
 #define OHGPU_BLOCK_KERNELS_1(X)    \
     X(32, 2, 3, true, 3, false)     \
     X(32, 2, 3, true, 3, true)      \
@@ -99,10 +93,8 @@ enum { kWorkRamped = 1u,      // a ramped message overlaps the unit's output ran
     X(64, 8, 3, true, 3, false)     \
     X(32, 2, 2, false, 3, false)    \
     X(32, 2, 2, false, 2, false)
-#endif
 #define OHGPU_BLOCK_KERNELS(X) OHGPU_BLOCK_KERNELS_1(X) OHGPU_BLOCK_KERNELS_2(X) OHGPU_BLOCK_KERNELS_3(X)
-// Round 1's block kernel in the SHIPPED library (round 5: retired as a selectable variant, legacy builds have the whole list above):
-// only as the fallback for a filter whose phase sums reach 2^29 -- beyond the lean kernel's rounding bias, which is what keeps its
+// Round 1's block kernel is instantiated only for these: the fallback for a filter whose phase sums reach 2^29 -- beyond the lean kernel's rounding bias, which is what keeps its
 // fp64 sums exact -- and only for the stereo layouts such a filter is likely to meet.  ohgpu_src_design's own 48 -> 44.1 kHz and
 // 32 -> 48 kHz filters are such filters (sum|c| = 2.02 and 2.40 x 2^28); without these they would run on the generic kernel.
 #define OHGPU_BLOCK_FALLBACK_KERNELS(X) \
@@ -112,29 +104,18 @@ enum { kWorkRamped = 1u,      // a ramped message overlaps the unit's output ran
     X(32, 2, 2, true, 3, false)         \
     X(32, 2, 2, false, 3, false)
 // the lean kernel's planar-source instantiations (source bytes 0 = the TInt32 planes of OHGPU_FLAG_SRC_PLANAR32), compiled with part 3
-#ifdef OHGPU_DIAG_ONE_KERNEL
-#define OHGPU_LEAN_PLANAR_KERNELS(X)
-#else
 #define OHGPU_LEAN_PLANAR_KERNELS(X) \
     X(32, 2, 0, true, 3, false)      \
     X(32, 2, 0, true, 3, true)
-#endif
 // the lean kernel's half-band instantiations (a filter with ohgpu_src::halfband: T = 64 stored, 33 products per output), part 4.
 // Each has a plain T = 64 twin in the list above, which serves every other 64-tap filter of the same layout.
-#ifdef OHGPU_DIAG_ONE_KERNEL
-#define OHGPU_LEAN_HB_KERNELS(X)
-#else
 #define OHGPU_LEAN_HB_KERNELS(X)     \
     X(64, 2, 3, true, 3, false)      \
     X(64, 6, 3, true, 3, false)      \
     X(64, 8, 3, true, 3, false)
-#endif
-// layouts only the lean kernel is instantiated for (round 1's kernel, variant 2, leaves them to the generic one): packed 32-bit
+// layouts only the lean kernel is instantiated for (round 1's list above leaves them out): packed 32-bit
 // stereo sources, mono (64 blocks per wave), wide little-endian outputs, and the channel counts that complete 1..8 for S24
 // little-endian sources (Msg.h:171 admits 1 to 8 channels): 3, 4, 5, 7.  Part 5.
-#ifdef OHGPU_DIAG_ONE_KERNEL
-#define OHGPU_LEAN_ONLY_KERNELS(X)
-#else
 #define OHGPU_LEAN_ONLY_KERNELS(X)   \
     X(32, 2, 4, true, 3, false)      \
     X(32, 2, 4, false, 3, false)     \
@@ -148,12 +129,8 @@ enum { kWorkRamped = 1u,      // a ramped message overlaps the unit's output ran
     X(32, 4, 3, true, 3, false)      \
     X(32, 5, 3, true, 3, false)      \
     X(32, 7, 3, true, 3, false)
-#endif
 // ... and (round 4, part 6) the layouts that were the generic kernel's: odd channel counts from big-endian S24, 16- and 32-bit big-endian
 // destinations for six and eight channels, 8-bit stereo sources.
-#ifdef OHGPU_DIAG_ONE_KERNEL
-#define OHGPU_LEAN_MORE_KERNELS(X)
-#else
 #define OHGPU_LEAN_MORE_KERNELS(X)   \
     X(32, 3, 3, false, 3, false)     \
     X(32, 5, 3, false, 3, false)     \
@@ -163,5 +140,4 @@ enum { kWorkRamped = 1u,      // a ramped message overlaps the unit's output ran
     X(32, 6, 3, true, 4, false)      \
     X(32, 8, 3, true, 4, false)      \
     X(32, 2, 1, false, 3, false)
-#endif
 #define OHGPU_BLOCK_PARTS 6

@@ -1,7 +1,5 @@
 // src_block_kernel.hip -- round 1's resample -> ramp -> pack kernel ("block kernel").  Since round 2 the batches run on
-// src_lean_kernel.hip, since round 4 on src_mfma_wg_kernel.hip.  RETIRED as a selectable kernel in round 5: its nineteen
-// instantiations and ohgpu_set_kernel_variant(ctx, 2) exist only in a legacy build (-DOHGPU_LEGACY_KERNELS: OHGPU_LEGACY=1 python
-// ohpipeline_amd/build.py, or tools/build_variant.sh -- the same-box A/B reference).  What the shipped library keeps of it:
+// src_lean_kernel.hip, since round 4 on src_mfma_wg_kernel.hip; no kernel variant selects this one.  What the library keeps of it:
 //   * the FALLBACK for filters whose phase sums break the lean kernel's rounding bias (sum|c| >= 2^29: this kernel rounds by
 //     add-floor-convert and is exact up to the design's own bound of 2^30) -- five stereo instantiations
 //     (OHGPU_BLOCK_FALLBACK_KERNELS), one translation unit.  ohgpu_src_design's 48 -> 44.1 kHz and 32 -> 48 kHz filters are such;
@@ -355,7 +353,7 @@ void src_block_kernel(const SrcSeg* __restrict__ segs, const SegMsg* __restrict_
                     v4.x = q[0]; v4.y = q[1]; v4.z = q[2]; v4.w = q[3];
                     u32x4* const o = (u32x4*)(dst + wave_dst + (int64_t)((uint64_t)r * L_blk) * FB_DST + drained * 64 + part * 16);
                     // written once, never read here: a non-temporal store keeps the output from pushing the input lines, which
-                    // two or three stages re-read, out of the XCD's L2 (tools/exp_traffic.sh: 2.17 -> 1.80 GB per launch, -3.6 % time)
+                    // two or three stages re-read, out of the XCD's L2 (2.17 -> 1.80 GB per launch, -3.6 % time)
                     __builtin_nontemporal_store(v4, o);
                 }
             }
@@ -550,27 +548,8 @@ void src_block_kernel(const SrcSeg* __restrict__ segs, const SegMsg* __restrict_
     }
 }
 
-// ---- instantiations: (T, channels, source bytes, source LE, destination bytes, destination LE) ----
-// The list is compiled in parts so that the build can run them side by side (ohpipeline_amd/build.py compiles this file
-// once per part with -DOHGPU_BLOCK_PART=k): part 1 also holds the host code and only DECLARES the other parts' kernels;
-// parts 2.. hold nothing but their kernels.  Without the macro (tools, tests) the file is one translation unit.
-#ifdef OHGPU_LEGACY_KERNELS
-#define OHGPU_KERNEL_ARGS const SrcSeg*, const SegMsg*, const SrcWork*, uint32_t, const double*, const uint16_t*, const uint8_t*, \
-                          uint8_t*, uint64_t, int, int, uint32_t, uint32_t, uint32_t, uint32_t*
-#define X_DEFINE(t, c, s_, sl, d, dl) template __global__ void src_block_kernel<t, c, s_, sl, d, dl>(OHGPU_KERNEL_ARGS);
-#define X_DECLARE(t, c, s_, sl, d, dl) extern template __global__ void src_block_kernel<t, c, s_, sl, d, dl>(OHGPU_KERNEL_ARGS);
-#if defined(OHGPU_BLOCK_PART) && OHGPU_BLOCK_PART == 2
-OHGPU_BLOCK_KERNELS_2(X_DEFINE)
-#elif defined(OHGPU_BLOCK_PART) && OHGPU_BLOCK_PART == 3
-OHGPU_BLOCK_KERNELS_3(X_DEFINE)
-#elif defined(OHGPU_BLOCK_PART)
-OHGPU_BLOCK_KERNELS_2(X_DECLARE)
-OHGPU_BLOCK_KERNELS_3(X_DECLARE)
-#endif
-
-#endif   // OHGPU_LEGACY_KERNELS (the shipped library: one translation unit, the fallback list's kernels instantiated by their launches below)
-
-#if !defined(OHGPU_BLOCK_PART) || OHGPU_BLOCK_PART == 1
+// ---- host code: the fallback list's kernels (T, channels, source bytes, source LE, destination bytes, destination LE) are
+// instantiated by their launches below ----
 // Launch shape: up to MAX_WAVES waves per workgroup (what the LDS left by the coefficient table allows), one
 // workgroup per CU, waves loop over the work units; a small batch is spread as one-wave workgroups instead.
 static void launch_shape(const ohgpu_ctx* ctx, const ohgpu_batch* b, uint32_t* grid, uint32_t* waves, uint32_t* lds)
@@ -631,18 +610,12 @@ bool src_block_geometry(uint32_t L, uint32_t T, uint32_t ch, uint32_t sb, uint32
     return true;
 }
 
-// the kernels THIS library has: the whole list in a legacy build, the fallback list otherwise
-#ifdef OHGPU_LEGACY_KERNELS
-#define OHGPU_BLOCK_BUILT(X) OHGPU_BLOCK_KERNELS(X)
-#else
-#define OHGPU_BLOCK_BUILT(X) OHGPU_BLOCK_FALLBACK_KERNELS(X)
-#endif
-
+// the kernels this library has: the fallback list
 bool src_block_built(uint32_t T, uint32_t ch, uint32_t sb, uint32_t src_le, uint32_t db, uint32_t dst_le)
 {
 #define X(t, c, s_, sl, d, dl) \
     if (T == t && ch == c && sb == s_ && (src_le != 0) == sl && db == d && (dst_le != 0) == dl) return true;
-    OHGPU_BLOCK_BUILT(X)
+    OHGPU_BLOCK_FALLBACK_KERNELS(X)
 #undef X
     return false;
 }
@@ -658,11 +631,9 @@ hipError_t launch_src_block(const ohgpu_ctx* ctx, const ohgpu_batch* b, const ui
 #define X(t, c, s_, sl, d, dl)                                                                                            \
     if (T == t && prm.channels == c && prm.sb == s_ && (prm.src_le != 0) == sl && prm.db == d && (prm.dst_le != 0) == dl) \
         return launch_one<t, c, s_, sl, d, dl>(ctx, b, prm, s);
-    OHGPU_BLOCK_BUILT(X)
+    OHGPU_BLOCK_FALLBACK_KERNELS(X)
 #undef X
     return hipErrorInvalidValue;
 }
-
-#endif   // host code: part 1 (or the single translation unit)
 
 }  // namespace ohgpu

@@ -157,26 +157,17 @@ __device__ __forceinline__ uint32_t lean_unpack_sel(uint32_t sh)
 // centre exactly zero).  T stays the filter's stored length -- the trip, the warm-up and the history are 64 input frames -- but
 // the window holds only the T / 2 EVEN-parity frames the T / 2 non-zero outer taps meet (an output is due on every even
 // frame), and the odd-parity frames wait, packed, in a delay line of T / 4 registers for the centre tap, T / 2 - 1 frames later.
-#ifndef OHGPU_LEAN_MAX_WAVES_T32
-#define OHGPU_LEAN_MAX_WAVES_T32 0                       // (experiments: waves per workgroup of the 32-slot-window kernels)
-#endif
-#ifndef OHGPU_LEAN_MAX_WAVES_WIDE
-#define OHGPU_LEAN_MAX_WAVES_WIDE 16                     // ... of those with six channels or more: they fit 128 registers, four waves per SIMD
-#endif
 // Waves per workgroup.  A 32-slot window: three per SIMD for stereo (134 registers; and what the LDS left by the coefficient
 // table allows with 16-frame stages, 11), FOUR for six channels and more -- those kernels have no pair exchange, fit 128
-// registers and their 8-frame stages leave the LDS room (same-box A/B on config 4, tools/exp_wide16.sh: six channels 1.75 ->
+// registers and their 8-frame stages leave the LDS room (same-box A/B on config 4: six channels 1.75 ->
 // 1.67 ms, eight 2.25 -> 2.09 ms).  A half-band kernel carries the delay line on top and stays at three: the six-channel one
 // does not fit 128 registers (it would spill), and the eight-channel one, which just does, measured 2.5 % SLOWER squeezed
-// into them (tools/exp_hb8.sh: 2.98-2.99 against 2.91 ms).  Two per SIMD when the window alone is 128 registers (T = 64).
+// into them (2.98-2.99 against 2.91 ms).  Two per SIMD when the window alone is 128 registers (T = 64).
+static constexpr int kLeanMaxWavesWide = 16;       // six channels or more: 128 registers, four waves per SIMD
 static constexpr int lean_max_waves(int tw, int ch, bool halfband)
 {
     if (tw > 32) return 8;
-    if (OHGPU_LEAN_MAX_WAVES_T32 > 0) return OHGPU_LEAN_MAX_WAVES_T32;
-#ifdef OHGPU_DIAG_HB8_WAVES
-    if (halfband && ch == 8) return OHGPU_DIAG_HB8_WAVES;      // (diagnostic: the eight-channel half-band kernel's occupancy)
-#endif
-    return (ch >= 6 && !halfband) ? OHGPU_LEAN_MAX_WAVES_WIDE : 12;
+    return (ch >= 6 && !halfband) ? kLeanMaxWavesWide : 12;
 }
 template <int T, int CH, int SB, int DB, bool HB = false>
 struct LeanGeom {
@@ -200,7 +191,7 @@ void src_lean_kernel(const LeanUnit* __restrict__ units, const uint32_t n_work,
                      const double* __restrict__ coef, const uint16_t* __restrict__ planes, const uint32_t plane_stride,
                      const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                      const uint64_t src_arena_bytes, const int L, const int M, const uint32_t L_blk1, const uint32_t M_blk1,
-                     const uint32_t ring_bytes, const uint32_t src_shift, uint32_t* __restrict__ unit_counter, uint64_t* __restrict__ dbg)
+                     const uint32_t ring_bytes, const uint32_t src_shift, uint32_t* __restrict__ unit_counter, uint64_t* __restrict__ /*unused*/)
 {
     static_assert(T % 16 == 0 && T >= 32 && T <= 64, "T / 16 coefficient registers per lane");
     constexpr bool PL = LeanGeom<T, CH, SB, DB, HB>::PL;       // planar TInt32 source (src_shift = 32 - its bit depth)
@@ -208,15 +199,6 @@ void src_lean_kernel(const LeanUnit* __restrict__ units, const uint32_t n_work,
     static_assert(!HB || (T == 64 && !PL), "the half-band kernel: 63 taps stored as 64, packed sources");
     using G = LeanGeom<T, CH, SB, DB, HB>;
     constexpr int TW = G::TW;                               // window slots (HB: the even-parity frames only)
-#ifdef OHGPU_DIAG_STAMP
-    // diagnostic build: shader-clock stamps per phase, summed per wave, written to dbg[wave][8] at the end (never read by the kernel)
-    uint64_t st_setup = 0, st_warm = 0, st_stage = 0, st_drain = 0, st_out = 0, st_units = 0, st_mark = 0;
-    const uint64_t st_begin = __builtin_amdgcn_s_memtime();
-    const uint64_t st_begin_real = __builtin_amdgcn_s_memrealtime();          // (100 MHz: the shader clock = ticks / real ticks * 100 MHz)
-#define STAMP(acc) { const uint64_t n_ = __builtin_amdgcn_s_memtime(); acc += n_ - st_mark; st_mark = n_; }
-#else
-#define STAMP(acc)
-#endif
     constexpr int NCR = TW / 16;
     constexpr int BPW = G::BPW, ROWS = G::ROWS, IN_ROWS = G::IN_ROWS;
     constexpr int FB_SRC = G::FB_SRC, FB_DST = G::FB_DST;
@@ -241,10 +223,7 @@ void src_lean_kernel(const LeanUnit* __restrict__ units, const uint32_t n_work,
     // dual-dword operation, not addresses -- and without it the stereo kernel's per-wave LDS is 10 240 bytes: twelve waves per
     // CU instead of eleven.  Same-box A/B, alternating: a wash on most boxes (0.458-0.479 against 0.468-0.489 ms), 11 % faster
     // on a box that ran the whole kernel 40 % slow (0.605 against 0.681 ms): the twelfth wave is insurance, not speed.)
-#ifndef OHGPU_LEAN_RING_PAD
-#define OHGPU_LEAN_RING_PAD 0
-#endif
-    const uint32_t row_stride = ring_bytes + OHGPU_LEAN_RING_PAD;
+    const uint32_t row_stride = ring_bytes;
     const uint32_t ring_area = (ROWS * row_stride + 15) & ~15u;
     const uint32_t dummy_bytes = G::DUMMY ? ring_bytes + 64u : 0u;    // (their store address moves with ring_pos like everyone's)
     const uint32_t wave_lds = (OFF_RING + ring_area + dummy_bytes + 127u) & ~127u;
@@ -296,9 +275,6 @@ void src_lean_kernel(const LeanUnit* __restrict__ units, const uint32_t n_work,
     // the launch ends when the slowest such pair does.
     uint32_t claim = 0;
     bool claimed = false;
-#ifdef OHGPU_DIAG_STAMP
-    st_mark = __builtin_amdgcn_s_memtime(); st_units++;
-#endif
     const uint32_t n_blocks = wk.n_blocks;
     // A row is `kb` consecutive blocks of its stream (src_plan.cpp: long units first, one-block units for the end of the launch):
     // the window stays warm from block to block, so a row pays the T warm-up advances and their history once, not per block.
@@ -342,9 +318,6 @@ void src_lean_kernel(const LeanUnit* __restrict__ units, const uint32_t n_work,
         piece_off[it] = d_r - al + a0 + 16 * part;
     }
     auto issue_stage = [&](int q) __attribute__((always_inline)) {
-#ifdef OHGPU_DIAG_NO_DMA
-        if (q >= 0) { stage_off += SF * FB_SRC; return; }
-#endif
         const uint32_t buf = OFF_IN + (uint32_t)(q & 1) * BUF_BYTES;
 #pragma unroll
         for (int it = 0; it < IN_ITERS; it++) {
@@ -353,28 +326,17 @@ void src_lean_kernel(const LeanUnit* __restrict__ units, const uint32_t n_work,
             const uint32_t m0v = wave_lds_addr + buf + (uint32_t)(it * 64) * 16;
             if (!checked) {
                 const uint64_t sbase = (uint64_t)(uintptr_t)src + (uint64_t)stage_off;
-#if defined(OHGPU_DIAG_DMA_POLICY_ID) && OHGPU_DIAG_DMA_POLICY_ID == 1     // (diagnostic builds: a cache policy on the staging loads)
-#define LEAN_DMA_POLICY " nt"
-#elif defined(OHGPU_DIAG_DMA_POLICY_ID) && OHGPU_DIAG_DMA_POLICY_ID == 2
-#define LEAN_DMA_POLICY " sc1"
-#elif defined(OHGPU_DIAG_DMA_POLICY_ID) && OHGPU_DIAG_DMA_POLICY_ID == 3
-#define LEAN_DMA_POLICY " sc0 sc1"
-#elif defined(OHGPU_DIAG_DMA_POLICY_ID) && OHGPU_DIAG_DMA_POLICY_ID == 4
-#define LEAN_DMA_POLICY " sc0"
-#else
-#define LEAN_DMA_POLICY ""
-#endif
                 if (last_partial) {
                     // (the lanes beyond the last piece are masked off for this one instruction; EXEC is saved and put back, not
                     // assumed full: the statement then holds in whatever control flow a compiler leaves around it)
                     uint64_t keep;
                     asm volatile("s_mov_b64 %[keep], exec\n\ts_and_b64 exec, %[keep], %[mask]\n\ts_mov_b32 m0, %[m0v]\n\ts_nop 0\n\t"
-                                 "global_load_lds_dwordx4 %[off], %[base]" LEAN_DMA_POLICY "\n\ts_mov_b64 exec, %[keep]"
+                                 "global_load_lds_dwordx4 %[off], %[base]\n\ts_mov_b64 exec, %[keep]"
                                  : [keep] "=&s"(keep)
                                  : [off] "v"(piece_off[it]), [base] "s"(sbase), [m0v] "s"(m0v), [mask] "s"((1ull << (kTail & 63)) - 1ull)
                                  : "memory", "m0", "scc");
                 } else {
-                    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" LEAN_DMA_POLICY
+                    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
                                  : : "v"(piece_off[it]), "s"(sbase), "s"(m0v) : "memory", "m0");
                 }
             } else {
@@ -411,9 +373,6 @@ void src_lean_kernel(const LeanUnit* __restrict__ units, const uint32_t n_work,
     uint32_t drained = 0;                                 // lines written so far (wave-uniform)
     uint32_t line_pos = 0;                                // ring position of line `drained`
     auto drain = [&](int frames_stored) __attribute__((always_inline)) {
-#ifdef OHGPU_DIAG_NO_DRAIN
-        if (frames_stored >= 0) return;
-#endif
         while (drained < (((uint32_t)frames_stored * FB_DST) >> 6)) {
             uint32_t pos = line_pos + (lane & 3) * 16 + (((lane >> 5) & 1u) ? ring_half : 0u);   // (row = it * 16 + lane / 4: its bit 3 is the lane's bit 5)
             if (pos >= ring_bytes) pos -= ring_bytes;
@@ -435,13 +394,7 @@ void src_lean_kernel(const LeanUnit* __restrict__ units, const uint32_t n_work,
             for (int it = 0; it < DRAIN_ITERS; it++) {
                 if ((uint32_t)(it * 16) + (lane >> 2) < wave_rows) {
                     uint8_t* const line = dst + wave_dst + (uint64_t)drained * 64 + (uint64_t)(it * 16) * L_blk * FB_DST;    // wave-uniform
-#if defined(OHGPU_DIAG_STORE_PLAIN)
-                    *(u32x4*)(line + drain_off) = v4[it];
-#elif !defined(OHGPU_DIAG_NO_STORE)
                     __builtin_nontemporal_store(v4[it], (u32x4*)(line + drain_off));
-#else
-                    if (v4[it].x == 0x12345678u && v4[it].y == 0x9abcdef0u) *(u32x4*)(line + drain_off) = v4[it];
-#endif
                 }
             }
             drained++;
@@ -481,9 +434,6 @@ void src_lean_kernel(const LeanUnit* __restrict__ units, const uint32_t n_work,
     uint32_t st_addr = PAIR ? ring_lane_lo : ring_lane, st_lo = 0, st_hi = 0;
     uint32_t y_even = 0, y_odd = 0;                           // frames whose bytes are in the ring or in the pending store
     auto issue_store = [&]() __attribute__((always_inline)) {
-#ifdef OHGPU_DIAG_NO_RING
-        return;
-#endif
         if constexpr (PAIR) asm volatile("ds_write2_b32 %0, %1, %2 offset1:1" : : "v"(st_addr), "v"(st_lo), "v"(st_hi) : "memory");
         else if constexpr (DB == 4) asm volatile("ds_write_b32 %0, %1" : : "v"(st_addr), "v"(st_lo) : "memory");
         else if constexpr (DB == 3) asm volatile("ds_write_b8 %0, %1\n\tds_write_b8 %0, %2 offset:1\n\tds_write_b8_d16_hi %0, %1 offset:2"
@@ -505,7 +455,6 @@ void src_lean_kernel(const LeanUnit* __restrict__ units, const uint32_t n_work,
     // from then on stage q + 1 is issued when stage q begins (into the buffer stage q - 1 was read from), here and in the loop.
     issue_stage(0);
     issue_stage(1);
-    STAMP(st_setup)
     static_for([&](auto stage) __attribute__((always_inline)) {
         constexpr int q = decltype(stage)::value;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       // stage q has landed
@@ -540,7 +489,6 @@ void src_lean_kernel(const LeanUnit* __restrict__ units, const uint32_t n_work,
             for (int s = 0; s < T / 4; s++) dly[s] = first_block ? 0u : dly[s];
         }
     }
-    STAMP(st_warm)
     // The coefficient reads above were issued before the warm-up's waits: they have landed.  From here on, in issue order:
     //   per advance:  X (raw sample; of the NEXT advance where that lies in the same stage -- see the loop)
     //   per output:   W  S  16 taps(c[NCR-1])  C'[NCR-1]   W  16 taps(c[NCR-2])  C'[NCR-2] ...
@@ -554,22 +502,17 @@ void src_lean_kernel(const LeanUnit* __restrict__ units, const uint32_t n_work,
         static_for([&](auto slot) __attribute__((always_inline)) {
             constexpr int s = decltype(slot)::value;
             if constexpr ((s & 3) == 0) {
-                STAMP(st_out)
                 if constexpr ((s % SF) == 0) {
                     const int q = (g * T + s) / SF;
-#ifndef OHGPU_DIAG_NO_STAGE_WAIT                                       // (diagnostic: wrong audio, the wait's share of the time)
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // stage q has landed (this wave issued all of it)
-#endif
                     if ((q + 1) * SF < total) issue_stage(q + 1);
                     else if (!claimed) {
                         if (lane == 0) claim = atomicAdd(unit_counter, 1u);
                         claimed = true;
                     }
-                    STAMP(st_stage)
                 }
                 issue_store();
                 drain(PAIR ? (j & ~1) : j);
-                STAMP(st_drain)
             }
             // ---- advance: this channel's sample of the next input frame enters slot s ----
             tl += L;
@@ -582,13 +525,11 @@ void src_lean_kernel(const LeanUnit* __restrict__ units, const uint32_t n_work,
             constexpr int sp = s % SF, ph = sp % PH;
             constexpr int ws = HB ? s / 2 : s;                          // the window slot of this advance's frame (HB: even frames only)
             constexpr bool had_ahead = sp != 0, look_ahead = sp != SF - 1;
-#ifndef OHGPU_DIAG_NO_X
             if constexpr (!had_ahead) lean_issue_2xu32<FB_SRC * (sp - ph) / 4>(rawp[s & 1], in_addr[(s / SF) & 1][ph]);
             if constexpr (look_ahead) {
                 constexpr int sn = sp + 1, phn = sn % PH;
                 lean_issue_2xu32<FB_SRC * (sn - phn) / 4>(rawp[(s + 1) & 1], in_addr[(s / SF) & 1][phn]);
             }
-#endif
             if constexpr (HB && (s & 1) != 0) {
                 // half-band, an odd-parity frame: no output is ever due on it and no outer tap ever meets it.  It waits, as
                 // sample x 256, for the centre tap of the output T / 4 outputs on: wait for the sample and unpack, ONE statement
@@ -597,11 +538,7 @@ void src_lean_kernel(const LeanUnit* __restrict__ units, const uint32_t n_work,
                              : [w] "=&v"(dly[(s / 2) % (T / 4)])
                              : [hi] "v"((uint32_t)(rawp[s & 1] >> 32)), [lo] "v"((uint32_t)rawp[s & 1]), [n] "i"(look_ahead ? 1 : 0),
                                [sel] "v"(in_sel[sp % PH]) : "memory");
-#ifdef OHGPU_DIAG_NO_EXPECT
-            } else if (!(t < tle)) {
-#else
             } else if (__builtin_expect(!(t < tle), 0)) {       // (unlikely: kept out of the line of the outputs, one taken branch less per output)
-#endif
                 // no output needs it yet (M > L), or the block is done: wait for the sample (everything but the look-ahead just
                 // issued) and convert, in ONE statement
                 uint32_t w;
@@ -661,18 +598,14 @@ void src_lean_kernel(const LeanUnit* __restrict__ units, const uint32_t n_work,
                         __builtin_amdgcn_sched_barrier(0);
                     }
 #define W_(k) win[(ws - (16 * r + (k)) + 2 * TW) % TW]
-#ifndef OHGPU_DIAG_NO_TAPS
                     if constexpr (r == 0)
                         lean_taps16_unpack<PL>(acc, cf[0], rawp[s & 1], in_sel[(s % SF) % PH], win[ws], W_(15), W_(14), W_(13), W_(12), W_(11), W_(10), W_(9), W_(8),
                                            W_(7), W_(6), W_(5), W_(4), W_(3), W_(2), W_(1));
                     else
                         lean_taps16(acc, cf[r], W_(15), W_(14), W_(13), W_(12), W_(11), W_(10), W_(9), W_(8),
                                     W_(7), W_(6), W_(5), W_(4), W_(3), W_(2), W_(1), W_(0));
-#else
-                    if constexpr (r == 0) win[ws] = lean_unpack<PL>(rawp[s & 1], in_sel[(s % SF) % PH]);
-#endif
 #undef W_
-                    lean_issue_f64<r * 128>(cf[r], cp);      // (no ablation switch here: the waits above count this reload)
+                    lean_issue_f64<r * 128>(cf[r], cp);      // (the waits above count this reload)
                 }, std::make_integer_sequence<int, NCR>{});
                 // ---- round, clamp, (ramp,) pack: ONE hand-written statement.  u = trunc(2^24 + 0.5 + sum) clamped to
                 // 2^24 + [-2^23, 2^23 - 1]; its low 24 bits are the S24 value.  Everything that survives the output is an in-place
@@ -787,7 +720,6 @@ void src_lean_kernel(const LeanUnit* __restrict__ units, const uint32_t n_work,
             }
         }, std::make_integer_sequence<int, T>{});
     }
-    STAMP(st_out)
     if (!claimed && lane == 0) claim = atomicAdd(unit_counter, 1u);          // (a unit too short for a stage boundary of its own)
     // the next unit's descriptor is fetched while the last lines are written back
     unit = first_claimed + (uint32_t)__builtin_amdgcn_readfirstlane((int)claim);
@@ -795,16 +727,7 @@ void src_lean_kernel(const LeanUnit* __restrict__ units, const uint32_t n_work,
     issue_store();
     drain(j);
     wk = next_wk;
-    STAMP(st_drain)
     }   // units
-#ifdef OHGPU_DIAG_STAMP
-    if (dbg != nullptr && lane == 0) {
-        uint64_t* o = dbg + (size_t)(blockIdx.x * n_waves + wave) * 10;
-        o[0] = st_setup; o[1] = st_warm; o[2] = st_stage; o[3] = st_drain; o[4] = st_out; o[5] = st_units;
-        o[6] = st_begin; o[7] = __builtin_amdgcn_s_memtime();
-        o[8] = st_begin_real; o[9] = __builtin_amdgcn_s_memrealtime();
-    }
-#endif
     // The counters reset themselves: a wave reports in after its last claim, and the last wave of the grid zeroes both.
     if (lane == 0) {
         const uint32_t waves_total = gridDim.x * n_waves;
@@ -859,16 +782,13 @@ bool src_lean_geometry(uint32_t L, uint32_t T, bool halfband, uint32_t ch, uint3
     *ring_bytes = rb;
     const uint32_t tw = halfband ? T / 2 : T;              // (LeanGeom::TW: the taps the LDS table holds)
     *coef_lds_bytes = L * tw * 8;
-    *wave_lds_bytes = (2 * ((in_rows * inb * 16 + 127u) & ~127u) + ((bpw * (rb + OHGPU_LEAN_RING_PAD) + 15) & ~15u) + ((64 % ch) ? rb + 64u : 0u) + 127u) & ~127u;
+    *wave_lds_bytes = (2 * ((in_rows * inb * 16 + 127u) & ~127u) + ((bpw * rb + 15) & ~15u) + ((64 % ch) ? rb + 64u : 0u) + 127u) & ~127u;
     const uint32_t budget = 160 * 1024;
     if (*coef_lds_bytes + *wave_lds_bytes > budget) return false;
     uint32_t w = (budget - *coef_lds_bytes) / *wave_lds_bytes;
     const uint32_t cap = (uint32_t)lean_max_waves((int)tw, (int)ch, halfband);
     if (w > cap) w = cap;
     if (w < 4) return false;
-#ifdef OHGPU_DIAG
-    if (const char* e = getenv("OHGPU_DIAG_MAX_WAVES")) { const uint32_t x = (uint32_t)atoi(e); if (x >= 4 && x < w) w = x; }   // (diagnostic builds: occupancy)
-#endif
     *max_waves = w;
     return true;
 }
@@ -887,41 +807,9 @@ static hipError_t launch_lean_one(const ohgpu_ctx* ctx, const ohgpu_batch* b, co
     const uint32_t lds = f.lean_coef_lds_bytes + w * f.lean_wave_lds_bytes;
     hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    uint64_t* dbg = nullptr;
-#ifdef OHGPU_DIAG_STAMP
-    const char* stamp_path = getenv("OHGPU_DIAG_STAMP_FILE");
-    const size_t n_dbg = (size_t)g * w * 10;
-    if (stamp_path && hipMalloc((void**)&dbg, n_dbg * 8) == hipSuccess) hipMemsetAsync(dbg, 0, n_dbg * 8, s);
-#endif
     hipLaunchKernelGGL(kernel, dim3(g), dim3(w * 64), lds, s,
                        (const LeanUnit*)f.d_lean_units, f.n_lean, p.coef, (const uint16_t*)f.d_planes, f.plane_stride, p.src, p.dst,
-                       p.src_arena_bytes, (int)p.L, (int)p.M, p.L_blk, p.M_blk, f.ring_bytes, 32u - b->src_bits, (uint32_t*)f.d_counter, dbg);
-#ifdef OHGPU_DIAG_STAMP
-    if (dbg) {      // diagnostic build only: wait, sum up, write a text report, never on the product path
-        hipStreamSynchronize(s);
-        std::vector<uint64_t> h(n_dbg);
-        hipMemcpy(h.data(), dbg, n_dbg * 8, hipMemcpyDeviceToHost);
-        hipFree(dbg);
-        if (FILE* fo = fopen(stamp_path, "w")) {
-            double sum[6] = {0, 0, 0, 0, 0, 0}, t0 = 1e300, t1 = 0, life = 0, last_min = 1e300, life_real = 0;
-            for (size_t i = 0; i < n_dbg; i += 10) {
-                for (int k = 0; k < 6; k++) sum[k] += (double)h[i + k];
-                if ((double)h[i + 6] < t0) t0 = (double)h[i + 6];
-                if ((double)h[i + 7] > t1) t1 = (double)h[i + 7];
-                if ((double)h[i + 7] < last_min) last_min = (double)h[i + 7];
-                life += (double)(h[i + 7] - h[i + 6]);
-                life_real += (double)(h[i + 9] - h[i + 8]);
-            }
-            const double nw = (double)(n_dbg / 10);
-            fprintf(fo, "shader clock over the waves' lives: %.3f GHz (s_memtime / s_memrealtime at 100 MHz)\n", life / life_real * 0.1);
-            fprintf(fo, "waves %.0f (grid %u x %u), units %.0f; kernel span %.0f ticks, first wave done at %.0f; mean wave life %.0f\n", nw, g, w, sum[5], t1 - t0, last_min - t0, life / nw);
-            fprintf(fo, "mean ticks per wave: set-up %.0f warm-up %.0f stage wait+issue %.0f drain %.0f outputs %.0f | per unit: %.0f %.0f %.0f %.0f %.0f\n",
-                    sum[0] / nw, sum[1] / nw, sum[2] / nw, sum[3] / nw, sum[4] / nw,
-                    sum[0] / sum[5], sum[1] / sum[5], sum[2] / sum[5], sum[3] / sum[5], sum[4] / sum[5]);
-            fclose(fo);
-        }
-    }
-#endif
+                       p.src_arena_bytes, (int)p.L, (int)p.M, p.L_blk, p.M_blk, f.ring_bytes, 32u - b->src_bits, (uint32_t*)f.d_counter, (uint64_t*)nullptr);
     return hipGetLastError();
 }
 

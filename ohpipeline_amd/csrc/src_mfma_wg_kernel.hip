@@ -2,11 +2,11 @@
 // v_mfma_i32_16x16x64_i8 per tile of 16 outputs x 16 columns, 32-bit recombination) with the work cut for the MEMORY system:
 // one unit per WORKGROUP, five tiles per WAVE and pass.
 //
-// Why.  With a unit per wave (src_mfma_kernel.hip) a wave reads 96 bytes of each of its 32 rows per step and writes 192 bytes of
+// Why.  With a unit per wave (round 4's first matrix kernel) a wave reads 96 bytes of each of its 32 rows per step and writes 192 bytes of
 // each per pair of steps.  Every byte is fetched once and every sector written whole (1.09 x the algorithmic traffic), and still
 // the launch is bound by exactly that access pattern: with the arithmetic compiled out it takes 0.41 ms of the 0.42, because
 // 65 000 row streams advancing a hundred bytes at a time leave no DRAM page open for its next visitor.  The same kernel moving
-// the same bytes as one contiguous 6 KB run per wave and pair of steps takes 0.30 ms (`tools/exp_mfma.sh`, MF_DIAG_IO_CONTIG).
+// the same bytes as one contiguous 6 KB run per wave and pair of steps takes 0.30 ms (round 4, same box).
 // So a unit has to arrive and leave in ONE piece.
 //
 // How.  A planner unit is 30 or 32 CONSECUTIVE blocks of a stream (src_plan.cpp: rows of one block), its input and its output each
@@ -41,11 +41,9 @@
 #include "pcm_device.h"
 #include "src_mfma_common.h"
 
-#ifndef OHGPU_WG_ROWS
-#define OHGPU_WG_ROWS 16                            // rows (blocks) a workgroup takes at a time: 16 (three workgroups per CU) or 32 (two)
-#endif
-
 namespace ohgpu {
+
+constexpr int kWgRows = 16;                         // rows (blocks) a workgroup takes at a time: 16 rows, three workgroups per CU (32: two)
 
 constexpr uint32_t kWgPlaneIn = 12 * 64;            // planar TInt32 source: bytes of one channel's frames of a row's image (two of them side by side)
 
@@ -91,13 +89,7 @@ struct WgGeom {
     // Round 5, same box, turn and turn about (gpurun_out/r5/exp_hbrun.log, ms): six channels 1.825 -> 1.752 (-4 %), stereo 0.574 -> 0.583
     // (+1.5 %: sixteen rows, and the split's sixteen lanes a row apart pay for the run's fixed row distance even with the spare bytes
     // below), eight channels 2.20-2.30 -> 2.31-2.33 (its first section is one row: 160 tasks for 256 lanes).  So: six channels.
-#if defined(MF_WG_HB_ROWS)
-    static constexpr bool kHbRun = false;               // (A/B: every row's image fetched on its own, staged in two sections cut by chunks)
-#elif defined(MF_WG_HB_RUN_ALL)
-    static constexpr bool kHbRun = HB;                  // (A/B: every channel count)
-#else
     static constexpr bool kHbRun = HB && PAIRS == 3;
-#endif
     static constexpr uint32_t kHbAdv = 256u * kFb;                                   // bytes from a row's image to the next row's
     static constexpr uint32_t kHbRunBytes = (kSR - 1u) * kHbAdv + kRowIn;            // the rows' union: 24960 (stereo), 24192, 26112
     static constexpr uint32_t kHbRunPieces = kHbRunBytes / 16u;
@@ -115,21 +107,9 @@ struct WgGeom {
     static constexpr uint32_t kChunksA = HB ? 13 : kImgChunks;        // ... and the input chunks it holds whole
     static constexpr uint32_t kRowInPitch = kPlanes ? 2 * kWgPlaneIn + 16 : (HB ? kRoundsA * kRound + 16 : kRowIn + 16);   // (sixteen stereo rows, 16 bytes each, then meet all 64 banks once)
     static constexpr uint32_t kRowOut = kOutFrames * kFb;             // bytes of a row's output
-    // ... and the distance between two rows of the OUTPUT IMAGE in LDS: the same, unless MF_WG_OUT_PAD is set.  Six channels: frames 18
-    // bytes apart put two of a row's sixteen frames of a step into every bank, and with rows 2880 bytes = 720 dwords apart (16 mod 32)
-    // the two pair-rows a 32-lane half of the epilogue's 2-byte stores serves land on the same banks again -- 5.25 LDS cycles per
-    // store by the bank model where stereo's take 4 and eight channels' 2; rows 64 bytes further apart meet them at 4
-    // (tools/micro/lds_conflicts.py).  Built and measured in round 5 (the image then is no longer the output piece for piece: phase (D)
-    // finds piece f at (f / 180) * pitch + 16 (f % 180) and the barrier between (D) and (A) is back): bit-exact, and config 4's
-    // six-channel 44.1 kHz group took 1.2965 / 1.2822 / 1.2840 ms with the pad against 1.2770 / 1.2782 / 1.2828 without, same box, turn
-    // and turn about -- a 2- to 3-way conflict on a 2-byte store costs no time (the store's four cycles are its data's way to the LDS,
-    // MI355X_MICROARCH.md), the barrier costs what it cost before.  Not the default.
-#ifdef MF_WG_OUT_PAD
-    static constexpr uint32_t kRowOutPitch = kRowOut + (PAIRS == 3 && !HB ? 64u : 0u);
-#else
-    static constexpr uint32_t kRowOutPitch = kRowOut;
-#endif
-    static constexpr bool kOutLinear = kRowOutPitch == kRowOut;
+    // (the output image's rows lie back to back.  Six channels' 2-byte stores meet 2- to 3-way bank conflicts there; a 64-byte pad
+    // between rows takes them to the stereo level but measured no faster -- config 4's six-channel group 1.28 ms either way, round 5 --
+    // and costs a barrier between (D) and (A))
     static constexpr uint32_t kCt = ROWS / 8;
     static constexpr uint32_t kWaves = 2 * kCt;
     static constexpr uint32_t kThreads = 64 * kWaves;                 // = 16 * ROWS
@@ -148,17 +128,13 @@ struct WgGeom {
     // are sixteen registers.  The buffer is the longest run the geometry admits (stereo 972 pieces, six channels 936, eight 1008); that
     // three workgroups still share a CU -- six channels: 52 KB each to the byte -- the table of initial values holds two copies of a
     // value instead of four (read as ds_read2_b64 of the same 8 bytes twice).
-#ifdef MF_WG_NO_DMA
-    static constexpr bool kDma = false;
-#else
     static constexpr bool kDma = kSpan;
-#endif
     static constexpr uint32_t kBiasSteps = HB ? 0 : kSteps;
     static constexpr uint32_t kBiasCopies = kDma ? 2 : 4;
     static constexpr uint32_t kBiasStep = 128 * kBiasCopies;          // [b0, b1][output 16][copies] dwords
     static constexpr uint32_t kBiasBytes = kBiasSteps * kBiasStep;
     static constexpr uint32_t kInBytes = kSpan ? kSpanBytes : (kHbRun ? kHbStage : kSR * kRowInPitch);   // the input image ...
-    static constexpr uint32_t kOutBytes = (ROWS + PAIRS - 1) / PAIRS * kRowOutPitch;     // ... and the output image that lies over it (six channels: the idle pair-row's stores land behind the fifth row)
+    static constexpr uint32_t kOutBytes = (ROWS + PAIRS - 1) / PAIRS * kRowOut;     // ... and the output image that lies over it (six channels: the idle pair-row's stores land behind the fifth row)
     static constexpr uint32_t kStageBytes = kDma ? kOutBytes : (kInBytes > kOutBytes ? kInBytes : kOutBytes);
     static constexpr uint32_t kDmaBytes = kDma ? (((kSR - 1) * kOutFrames * kFbIn + kRowIn + 15u) / 16u) * 16u : 0u;
     static constexpr uint32_t kLdsBytes = kPlaneBytes + kStageBytes + kBiasBytes + kDmaBytes;
@@ -175,47 +151,10 @@ struct WgGeom {
     static_assert(!HB || (kChunksA * 16 * kFb <= kRoundsA * kRound && (kChunksA * 16 * kFb) >= (kRoundsA - 1) * kRound), "the two stagings meet in chunk 13");
 };
 
-#ifdef MF_WG_SPLIT_GENERIC
-constexpr bool kDiagSplitGeneric = true;            // (timing experiments: stereo through the any-stride split)
-#else
-constexpr bool kDiagSplitGeneric = false;
-#endif
-#ifdef MF_WG_OUT_B16
-constexpr bool kWideOut = false;                    // (A/B: round 4's epilogue, six 2-byte LDS stores per tile for every layout)
-#else
-constexpr bool kWideOut = true;                     // stereo and eight channels: a lane's twelve output bytes of a tile in two LDS stores
-#endif
-#ifdef MF_WG_NO_PIPE
-constexpr bool kPipe = false;                       // (A/B: a tile's matrix instructions, then its vector instructions, tile by tile)
-#else
-constexpr bool kPipe = true;                        // a tile's last vector instructions between the next tile's matrix instructions
-#endif
-// wave priorities by phase: the tiles (C), the output's stores and the next input's staging and loads (D, A), the split (S)
-#ifndef MF_WG_PRIO_C
-#define MF_WG_PRIO_C 3
-#endif
-#ifndef MF_WG_PRIO_D
-#define MF_WG_PRIO_D 0
-#endif
-#ifndef MF_WG_PRIO_S
-#define MF_WG_PRIO_S MF_WG_PRIO_D
-#endif
-constexpr int kPrioC = MF_WG_PRIO_C, kPrioD = MF_WG_PRIO_D, kPrioS = MF_WG_PRIO_S;
-#ifdef MF_WG_LATE_LOADS
-constexpr bool kLateLoads = true;                   // (A/B: the next unit's loads issued behind the split, as in round 4)
-#else
-constexpr bool kLateLoads = false;
-#endif
-#ifndef MF_DIAG_BARRIER_MASK
-#define MF_DIAG_BARRIER_MASK 0xf
-#endif
-template <int WHICH = 0>
+// wave priorities by phase: the tiles (C), the output's stores, the next input's staging and loads and the split (D, A, S)
+constexpr int kPrioC = 3, kPrioD = 0;
 __device__ __forceinline__ void wg_barrier()
 {
-    if constexpr (((MF_DIAG_BARRIER_MASK >> WHICH) & 1) == 0) {            // (timing experiments only: a barrier left out)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        return;
-    }
     // every LDS access of this wave has completed; nothing moves across (global loads in flight stay in flight)
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
@@ -293,7 +232,7 @@ void src_mfma_wg_kernel(const LeanUnit* __restrict__ units, const uint32_t n_wor
     const v4i hb_s0 = v4i{hb0, hb0, hb0, hb0}, hb_s2 = v4i{hb1, hb1, hb1, hb1};
     // where the lane's frame of pair-row 2 g lies in the output image (+ 16 frames per step; + 8 pair-rows per column tile; the pair-row
     // 2 g + 1 is the next row (stereo) or the next pair of the same row (eight channels); six channels: out_at below)
-    uint8_t* const out_lds = stage + ((2u * g) / (uint32_t)PAIRS) * G::kRowOutPitch + 6u * ((2u * g) % (uint32_t)PAIRS) + G::kFb * n;
+    uint8_t* const out_lds = stage + ((2u * g) / (uint32_t)PAIRS) * G::kRowOut + 6u * ((2u * g) % (uint32_t)PAIRS) + G::kFb * n;
     auto pair_row_srow = [&](uint32_t ct, uint32_t q) __attribute__((always_inline)) { return (ct * 8u + 2u * g + q) / (uint32_t)PAIRS; };   // the stream row of a tile's pair-row
     // the input image row by row (planar sources and the half-band form; packed sources otherwise: the pass's one run, span_* below):
     // 16 PAIRS lanes per row; lane `sub` of a row moves its pieces sub, sub + 16 PAIRS, .. and, the first half of them, one more --
@@ -322,13 +261,13 @@ void src_mfma_wg_kernel(const LeanUnit* __restrict__ units, const uint32_t n_wor
     constexpr uint32_t kB0 = DST_LE ? 0 : 2, kB1 = 1, kB2 = DST_LE ? 2 : 0;       // byte of the 24-bit value that is memory byte 0, 1, 2
     constexpr uint32_t sel_lo = kB0 | kB1 << 8 | kB2 << 16 | (4 + kB0) << 24;     // {R, L} -> L's three bytes, R's first
     constexpr uint32_t sel_hi = (4 + kB1) | (4 + kB2) << 8 | 0x0c0c0000u;          // {R, L} -> R's other two
-    // ... and twelve bytes from FOUR values {a, b, c, d} (kWideOut): dword 0 = sel_lo of {b, a}, dword 1 = b's other two bytes and c's
+    // ... and twelve bytes from FOUR values {a, b, c, d} (stereo, eight channels): dword 0 = sel_lo of {b, a}, dword 1 = b's other two bytes and c's
     // first two, dword 2 = c's last and d's three
     constexpr uint32_t sel_mid = kB1 | kB2 << 8 | (4 + kB0) << 16 | (4 + kB1) << 24;
     constexpr uint32_t sel_top = kB2 | (4 + kB0) << 8 | (4 + kB1) << 16 | (4 + kB2) << 24;
     const bool n_odd = (n & 1u) != 0;
-    // (kWideOut, stereo: the lane's twelve bytes -- the even lane's in row 2 g from its own frame on, the odd lane's in row 2 g + 1 from its even neighbour's frame on)
-    const uint32_t wide_off = n_odd ? G::kRowOutPitch - G::kFb : 0u;
+    // (stereo: the lane's twelve bytes -- the even lane's in row 2 g from its own frame on, the odd lane's in row 2 g + 1 from its even neighbour's frame on)
+    const uint32_t wide_off = n_odd ? G::kRowOut - G::kFb : 0u;
 
     // a workgroup unit = sub-unit `u % kSubUnits` of planner unit `u / kSubUnits`
     struct Unit { int64_t src0, dst0; uint32_t n_blocks, plane, plane_stride; bool ramped, first, edge; };
@@ -350,11 +289,6 @@ void src_mfma_wg_kernel(const LeanUnit* __restrict__ units, const uint32_t n_wor
         // (scalar base + 32-bit lane offset is the load's scalar-base form, but only if the offset is widened in THIS block: hoisted out
         // of the loop as a 64-bit pair it costs eight registers for the whole launch and a 64-bit add per load -- mf_here pins it)
         const uint8_t* const base = src + w.src0;
-#ifdef MF_DIAG_NO_LOAD
-        (void)base;
-#pragma unroll
-        for (int k = 0; k < (int)G::kInRounds; k++) raw[k] = u32x4{tid, in_src, (uint32_t)w.n_blocks, (uint32_t)k};
-#else
         if (w.edge) {
             // a unit at an end of the arena (the first of the first stream, the last of the last): its pieces one by one, out of line,
             // bytes outside the arena read as zero -- they are history before a stream's first frame, rows the unit does not hold, or
@@ -402,12 +336,10 @@ void src_mfma_wg_kernel(const LeanUnit* __restrict__ units, const uint32_t n_wor
                 raw[G::kFullRounds] = *(const u32x4_u*)(base + mf_here(in_src + in_last));
             }
         }
-#endif
     };
     // kDma: the pass's run, memory -> LDS.  A wave's lanes fill a contiguous KB per instruction (LDS address = M0 + 16 lane); lanes past
     // the run's end sit out.  A unit at an end of the arena brings its pieces through registers, checked, as ever.
     auto issue_dma = [&](const Unit& w) __attribute__((always_inline)) {
-#ifndef MF_DIAG_NO_LOAD
         if (w.edge) {
 #pragma unroll
             for (int k = 0; k < (int)G::kInRounds; k++) {
@@ -427,12 +359,8 @@ void src_mfma_wg_kernel(const LeanUnit* __restrict__ units, const uint32_t n_wor
                 }
             }
         }
-#endif
     };
     auto stage_input = [&](const u32x4 (&raw)[G::kInRounds]) __attribute__((always_inline)) {
-#ifdef MF_DIAG_NO_STAGE
-        return;
-#endif
         if constexpr (G::kPlanes) {
 #pragma unroll
             for (int k = 0; k < 6; k++) *(u32x4*)(stage + in_lds + (k / 3) * kWgPlaneIn + 256 * (k % 3)) = raw[k];
@@ -444,9 +372,6 @@ void src_mfma_wg_kernel(const LeanUnit* __restrict__ units, const uint32_t n_wor
     // half-band: the image in two sections over the same LDS -- section 0 = the lanes' rounds 0..4 (bytes 0 .. 5 kRound of every row:
     // input chunks 0..12 whole), section 1 = rounds 4..7 (bytes 4 kRound .. 7.5 kRound, stored from the row's start: chunks 13..19)
     auto stage_section = [&](auto sec_c, const u32x4 (&raw)[G::kInRounds]) __attribute__((always_inline)) {
-#ifdef MF_DIAG_NO_STAGE
-        return;
-#endif
         constexpr int SEC = decltype(sec_c)::value;
         if constexpr (G::kHbRun) {
             // section SEC of the run: its pieces to where the section starts at 0 (a round wholly outside it is no code at all)
@@ -522,9 +447,6 @@ void src_mfma_wg_kernel(const LeanUnit* __restrict__ units, const uint32_t n_wor
         }
     };
     auto split_section = [&](auto sec_c, bool first) __attribute__((always_inline)) {
-#ifdef MF_DIAG_NO_SPLIT
-        return;
-#endif
         constexpr int SEC = decltype(sec_c)::value;
         if constexpr (G::kHbRun) {
             constexpr uint32_t kTasksRun = (SEC == 0 ? G::kHbRows0 : G::kSR - G::kHbRows0) * (uint32_t)PAIRS * 40u;
@@ -586,7 +508,7 @@ void src_mfma_wg_kernel(const LeanUnit* __restrict__ units, const uint32_t n_wor
                     for (int j = 0; j < 3; j++) pl[3 * c + j][q] = sb[j];
                 }
             }
-        } else if constexpr (PAIRS == 1 && !kDiagSplitGeneric) {
+        } else if constexpr (PAIRS == 1) {
             // stereo: the eight frames are 48 contiguous bytes from an even address -- the thirteen dwords around them, moved down by the
             // two bytes an odd start is off (one v_alignbyte_b32 per dword), then the same network as for twelve aligned dwords
             const uint32_t byte0 = sp_span0 + hc * 48u;
@@ -634,9 +556,6 @@ void src_mfma_wg_kernel(const LeanUnit* __restrict__ units, const uint32_t n_wor
         }
     };
     auto split_all = [&](bool first) __attribute__((always_inline)) {
-#ifdef MF_DIAG_NO_SPLIT
-        return;
-#endif
         split_task(sp_hc0, first);
         if (sp_hc0 < 8u) split_task(sp_hc0 + 16u, first);
     };
@@ -644,15 +563,15 @@ void src_mfma_wg_kernel(const LeanUnit* __restrict__ units, const uint32_t n_wor
     auto stage_and_split = [&](const u32x4 (&raw)[G::kInRounds], bool first) __attribute__((always_inline)) {
         if constexpr (HB) {
             stage_section(std::integral_constant<int, 0>{}, raw);
-            wg_barrier<2>();
+            wg_barrier();
             split_section(std::integral_constant<int, 0>{}, first);
-            wg_barrier<2>();                                 // section 0 has been read
+            wg_barrier();                                 // section 0 has been read
             stage_section(std::integral_constant<int, 1>{}, raw);
-            wg_barrier<2>();
+            wg_barrier();
             split_section(std::integral_constant<int, 1>{}, first);
         } else {
             stage_input(raw);
-            wg_barrier<2>();
+            wg_barrier();
             split_all(first);
         }
     };
@@ -703,9 +622,6 @@ void src_mfma_wg_kernel(const LeanUnit* __restrict__ units, const uint32_t n_wor
             asm volatile("ds_read_b64 %0, %6\n\tds_read_b64 %1, %6 offset:%7\n\t"
                          "ds_read_b64 %2, %6 offset:%8\n\tds_read_b64 %3, %6 offset:%9\n\t"
                          "ds_read_b64 %4, %6 offset:%10\n\tds_read_b64 %5, %6 offset:%11"
-#ifdef MF_WG_EARLY_WAIT
-                         "\n\ts_waitcnt lgkmcnt(0)"
-#endif
                          : "=&v"(h[0]), "=&v"(h[1]), "=&v"(h[2]), "=&v"(h[3]), "=&v"(h[4]), "=&v"(h[5])
                          : "v"(at), "n"(G::kHalf), "n"(G::kDigit), "n"(G::kDigit + G::kHalf), "n"(2 * G::kDigit), "n"(2 * G::kDigit + G::kHalf)
                          : "memory");
@@ -747,8 +663,8 @@ void src_mfma_wg_kernel(const LeanUnit* __restrict__ units, const uint32_t n_wor
                         y[v] = mu[v >> 1] != 0xffffu ? r : y[v];
                     }
                 }
-                uint8_t* const os = out_lds + ct * ((8u / (uint32_t)(PAIRS == 3 ? 1 : PAIRS)) * G::kRowOutPitch) + 16u * G::kFb * step;
-                if constexpr (kWideOut && PAIRS == 1) {
+                uint8_t* const os = out_lds + ct * ((8u / (uint32_t)(PAIRS == 3 ? 1 : PAIRS)) * G::kRowOut) + 16u * G::kFb * step;
+                if constexpr (PAIRS == 1) {
                     // Stereo: TWELVE contiguous bytes per lane instead of two frames of six in two rows.  Lanes n and n + 1 (n even) hold
                     // frames n and n + 1 of pair-rows 2 g and 2 g + 1; the even lane takes both frames of row 2 g, the odd lane both of row
                     // 2 g + 1 -- four selects with the neighbour's value as their DPP operand (mf_pair_gather) -- and 6 n is a multiple of four for even n: three
@@ -759,7 +675,7 @@ void src_mfma_wg_kernel(const LeanUnit* __restrict__ units, const uint32_t n_wor
                     const uint32_t w0 = mf_perm(f1, f0, sel_lo), w1 = mf_perm(f2, f1, sel_mid), w2 = mf_perm(f3, f2, sel_top);
                     const uint32_t at = (uint32_t)(uintptr_t)(lds_u8_t)(os + wide_off);
                     asm volatile("ds_write2_b32 %0, %1, %2 offset1:1\n\tds_write_b32 %0, %3 offset:8" : : "v"(at), "v"(w0), "v"(w1), "v"(w2) : "memory");
-                } else if constexpr (kWideOut && PAIRS == 4) {
+                } else if constexpr (PAIRS == 4) {
                     // Eight channels: pair-rows 2 g and 2 g + 1 are neighbouring pairs of ONE frame -- the lane's four values are twelve
                     // contiguous bytes at a multiple of four as they stand
                     const uint32_t w0 = mf_perm((uint32_t)y[1], (uint32_t)y[0], sel_lo), w1 = mf_perm((uint32_t)y[2], (uint32_t)y[1], sel_mid), w2 = mf_perm((uint32_t)y[3], (uint32_t)y[2], sel_top);
@@ -776,9 +692,9 @@ void src_mfma_wg_kernel(const LeanUnit* __restrict__ units, const uint32_t n_wor
                     uint32_t at;
                     if constexpr (PAIRS == 3) {                      // (a tile's eight pair-rows start anywhere in a row of three)
                         const uint32_t pr = ct * 8u + 2u * g + (uint32_t)q, sr = pr / 3u;
-                        at = (uint32_t)(uintptr_t)(lds_u8_t)(stage + sr * G::kRowOutPitch + 6u * (pr - 3u * sr) + G::kFb * n + 16u * G::kFb * step);
+                        at = (uint32_t)(uintptr_t)(lds_u8_t)(stage + sr * G::kRowOut + 6u * (pr - 3u * sr) + G::kFb * n + 16u * G::kFb * step);
                     } else {
-                        at = (uint32_t)(uintptr_t)(lds_u8_t)(os + q * (PAIRS == 1 ? G::kRowOutPitch : 6u));
+                        at = (uint32_t)(uintptr_t)(lds_u8_t)(os + q * (PAIRS == 1 ? G::kRowOut : 6u));
                     }
                     asm volatile("ds_write_b16 %0, %1\n\tds_write_b16_d16_hi %0, %1 offset:2\n\tds_write_b16 %0, %2 offset:4"
                                  : : "v"(at), "v"(lo), "v"(hi) : "memory");
@@ -787,120 +703,78 @@ void src_mfma_wg_kernel(const LeanUnit* __restrict__ units, const uint32_t n_wor
             };
             u32x2 h[6];
             issue_planes(kc[0], kFirst % G::kCt, h);
-            if constexpr (kPipe) {
-                // The tiles as a software pipeline of ONE wave: a tile's twelve matrix instructions in two halves -- (a) the six that
-                // make s0, s1, s2, (b) the six that make s3, s4, s5 -- with the PREVIOUS tile's last twenty-eight vector instructions
-                // (T2, W, y, clamp, pack, store: they need only U, s4, s5 of it) written between them and this tile's first twelve
-                // (T0, T1, U) behind (b): in program order every vector instruction has matrix instructions of another output's
-                // around it that it does not depend on, and the accumulators a half writes are dead by then -- no register more.
-                // (Round 5: a wave alone alternated 192 cycles of matrix pipe and 160 of vector pipe, and with three waves a SIMD the
-                // others filled a third of that: 303 cycles a tile with every global access compiled out.)
-                int u_prev[4];
-                v4i s4p, s5p;
-                static_for([&](auto ic) __attribute__((always_inline)) {
-                    constexpr uint32_t i = decltype(ic)::value;
-                    constexpr bool kHas = i < G::kTilesPerWave, kPrev = i > 0;
-                    constexpr uint32_t ii = kHas ? i : G::kTilesPerWave - 1u;
-                    constexpr uint32_t set = (kFirst + ii) / G::kCt - kFirst / G::kCt;
-                    constexpr uint32_t ip = kPrev ? i - 1u : 0u;
-                    constexpr uint32_t set_p = (kFirst + ip) / G::kCt - kFirst / G::kCt, ct_p = (kFirst + ip) % G::kCt;
-                    static_assert(set < G::kKcSets, "a wave's tiles touch kKcSets steps");
-                    v4i bd[3];
-                    v4i s0, s1 = v4i{0, 0, 0, 0}, s2, s3 = v4i{0, 0, 0, 0}, s4 = v4i{0, 0, 0, 0}, s5 = v4i{0, 0, 0, 0};
-                    const v4i (&c)[4] = a[HB ? 0 : set];
-                    if constexpr (kHas) {
-                        const uint8_t* const bi = my_bias + (step0 + set) * G::kBiasStep;
-                        if constexpr (G::kDma) read_bias2(bi, s0, s2);         // (in front of the wait in take_planes)
-                        take_planes(h, bd);
-                        if constexpr (HB) { s0 = hb_s0; s2 = hb_s2; }
-                        else if constexpr (!G::kDma) { s0 = *(const v4i*)bi; s2 = *(const v4i*)(bi + G::kBiasStep / 2); }
-                        s0 = MF_MFMA(bd[0], c[0], s0);
-                        s1 = MF_MFMA(bd[0], c[1], s1);
-                        s2 = MF_MFMA(bd[0], c[2], s2);
-                        s1 = MF_MFMA(bd[1], c[0], s1);
-                        s2 = MF_MFMA(bd[1], c[1], s2);
-                        s2 = MF_MFMA(bd[2], c[0], s2);
-                    }
-                    if constexpr (kPrev) {
-                        int y[4];
-#pragma unroll
-                        for (int v = 0; v < 4; v++) y[v] = mf_recombine_tail(u_prev[v], s4p[v], s5p[v]);
-                        finish_tile(std::integral_constant<uint32_t, set_p>{}, std::integral_constant<uint32_t, ct_p>{}, y);
-                    }
-                    if constexpr (kHas) {
-                        s3 = MF_MFMA(bd[0], c[3], s3);
-                        s3 = MF_MFMA(bd[1], c[2], s3);
-                        s3 = MF_MFMA(bd[2], c[1], s3);
-                        s4 = MF_MFMA(bd[1], c[3], s4);
-                        s4 = MF_MFMA(bd[2], c[2], s4);
-                        s5 = MF_MFMA(bd[2], c[3], s5);
-                        if constexpr (i + 1 < G::kTilesPerWave) {
-                            constexpr uint32_t set_n = (kFirst + i + 1) / G::kCt - kFirst / G::kCt, ct_n = (kFirst + i + 1) % G::kCt;
-                            issue_planes(kc[set_n], ct_n, h);
-                        }
-#pragma unroll
-                        for (int v = 0; v < 4; v++) u_prev[v] = mf_recombine_head(s0[v], s1[v], s2[v], s3[v]);
-                        s4p = s4; s5p = s5;
-                    }
-                }, std::make_integer_sequence<int, (int)G::kTilesPerWave + 1>{});
-            } else {
+            // The tiles as a software pipeline of ONE wave: a tile's twelve matrix instructions in two halves -- (a) the six that
+            // make s0, s1, s2, (b) the six that make s3, s4, s5 -- with the PREVIOUS tile's last twenty-eight vector instructions
+            // (T2, W, y, clamp, pack, store: they need only U, s4, s5 of it) written between them and this tile's first twelve
+            // (T0, T1, U) behind (b): in program order every vector instruction has matrix instructions of another output's
+            // around it that it does not depend on, and the accumulators a half writes are dead by then -- no register more.
+            // (Round 5: a wave alone alternated 192 cycles of matrix pipe and 160 of vector pipe, and with three waves a SIMD the
+            // others filled a third of that: 303 cycles a tile with every global access compiled out.)
+            int u_prev[4];
+            v4i s4p, s5p;
             static_for([&](auto ic) __attribute__((always_inline)) {
                 constexpr uint32_t i = decltype(ic)::value;
-                v4i bd[3];
-                constexpr uint32_t set = (kFirst + i) / G::kCt - kFirst / G::kCt, ct = (kFirst + i) % G::kCt;
+                constexpr bool kHas = i < G::kTilesPerWave, kPrev = i > 0;
+                constexpr uint32_t ii = kHas ? i : G::kTilesPerWave - 1u;
+                constexpr uint32_t set = (kFirst + ii) / G::kCt - kFirst / G::kCt;
+                constexpr uint32_t ip = kPrev ? i - 1u : 0u;
+                constexpr uint32_t set_p = (kFirst + ip) / G::kCt - kFirst / G::kCt, ct_p = (kFirst + ip) % G::kCt;
                 static_assert(set < G::kKcSets, "a wave's tiles touch kKcSets steps");
-                const uint32_t step = step0 + set;
-                const uint8_t* const bi = my_bias + step * G::kBiasStep;
+                v4i bd[3];
                 v4i s0, s1 = v4i{0, 0, 0, 0}, s2, s3 = v4i{0, 0, 0, 0}, s4 = v4i{0, 0, 0, 0}, s5 = v4i{0, 0, 0, 0};
-                if constexpr (G::kDma) read_bias2(bi, s0, s2);                 // (in front of the wait in take_planes)
-                take_planes(h, bd);
-                if constexpr (HB) { s0 = hb_s0; s2 = hb_s2; }
-                else if constexpr (!G::kDma) { s0 = *(const v4i*)bi; s2 = *(const v4i*)(bi + G::kBiasStep / 2); }
                 const v4i (&c)[4] = a[HB ? 0 : set];
-                s0 = MF_MFMA(bd[0], c[0], s0);
-                s1 = MF_MFMA(bd[0], c[1], s1);
-                s2 = MF_MFMA(bd[0], c[2], s2);
-                s3 = MF_MFMA(bd[0], c[3], s3);
-                s1 = MF_MFMA(bd[1], c[0], s1);
-                s2 = MF_MFMA(bd[1], c[1], s2);
-                s3 = MF_MFMA(bd[1], c[2], s3);
-                s4 = MF_MFMA(bd[1], c[3], s4);
-                s2 = MF_MFMA(bd[2], c[0], s2);
-                s3 = MF_MFMA(bd[2], c[1], s3);
-                s4 = MF_MFMA(bd[2], c[2], s4);
-                s5 = MF_MFMA(bd[2], c[3], s5);
-                if constexpr (i + 1 < G::kTilesPerWave) {
-                    // the next tile's planes, while this one's matrix instructions run
-                    constexpr uint32_t set_n = (kFirst + i + 1) / G::kCt - kFirst / G::kCt, ct_n = (kFirst + i + 1) % G::kCt;
-                    issue_planes(kc[set_n], ct_n, h);
+                if constexpr (kHas) {
+                    const uint8_t* const bi = my_bias + (step0 + set) * G::kBiasStep;
+                    if constexpr (G::kDma) read_bias2(bi, s0, s2);         // (in front of the wait in take_planes)
+                    take_planes(h, bd);
+                    if constexpr (HB) { s0 = hb_s0; s2 = hb_s2; }
+                    else if constexpr (!G::kDma) { s0 = *(const v4i*)bi; s2 = *(const v4i*)(bi + G::kBiasStep / 2); }
+                    s0 = MFMA_I8(bd[0], c[0], s0);
+                    s1 = MFMA_I8(bd[0], c[1], s1);
+                    s2 = MFMA_I8(bd[0], c[2], s2);
+                    s1 = MFMA_I8(bd[1], c[0], s1);
+                    s2 = MFMA_I8(bd[1], c[1], s2);
+                    s2 = MFMA_I8(bd[2], c[0], s2);
                 }
-                int y[4];
+                if constexpr (kPrev) {
+                    int y[4];
 #pragma unroll
-                for (int v = 0; v < 4; v++) y[v] = mf_recombine(s0[v], s1[v], s2[v], s3[v], s4[v], s5[v]);
-                finish_tile(std::integral_constant<uint32_t, set>{}, std::integral_constant<uint32_t, ct>{}, y);
-            }, std::make_integer_sequence<int, (int)G::kTilesPerWave>{});
-            }
+                    for (int v = 0; v < 4; v++) y[v] = mf_recombine_tail(u_prev[v], s4p[v], s5p[v]);
+                    finish_tile(std::integral_constant<uint32_t, set_p>{}, std::integral_constant<uint32_t, ct_p>{}, y);
+                }
+                if constexpr (kHas) {
+                    s3 = MFMA_I8(bd[0], c[3], s3);
+                    s3 = MFMA_I8(bd[1], c[2], s3);
+                    s3 = MFMA_I8(bd[2], c[1], s3);
+                    s4 = MFMA_I8(bd[1], c[3], s4);
+                    s4 = MFMA_I8(bd[2], c[2], s4);
+                    s5 = MFMA_I8(bd[2], c[3], s5);
+                    if constexpr (i + 1 < G::kTilesPerWave) {
+                        constexpr uint32_t set_n = (kFirst + i + 1) / G::kCt - kFirst / G::kCt, ct_n = (kFirst + i + 1) % G::kCt;
+                        issue_planes(kc[set_n], ct_n, h);
+                    }
+#pragma unroll
+                    for (int v = 0; v < 4; v++) u_prev[v] = mf_recombine_head(s0[v], s1[v], s2[v], s3[v]);
+                    s4p = s4; s5p = s5;
+                }
+            }, std::make_integer_sequence<int, (int)G::kTilesPerWave + 1>{});
         };
-#ifndef MF_DIAG_IO_ONLY
         static_for([&](auto pc) __attribute__((always_inline)) {
             if (wave % G::kCt == (uint32_t)decltype(pc)::value) {         // (wave-uniform)
                 if (ramped) run_tiles(pc, std::true_type{});
                 else run_tiles(pc, std::false_type{});
             }
         }, std::make_integer_sequence<int, (int)G::kCt>{});
-#endif
-#ifndef MF_WG_NO_PRIO
         __builtin_amdgcn_s_setprio(kPrioD);                  // (the tiles run at priority 3: -2 % on the headline in round 4, -4 % in round 5, same box, alternating)
-#endif
         if constexpr (G::kDma) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (this wave's pieces of the next run have landed; the last pass's stores with them, long since)
-        wg_barrier<0>();                                    // the output image is whole; the planes are free (kDma: and the next run is in its buffer)
+        wg_barrier();                                    // the output image is whole; the planes are free (kDma: and the next run is in its buffer)
 
         // ---- (D) the unit leaves as lane-contiguous pieces.  vmcnt counts loads and stores together, in issue order: the next
         // unit's input -- requested a whole phase (C) ago -- is waited for HERE, in front of the stores, not behind them ----
         // (the unit after the next: its descriptor is asked for here, a phase before its loads are issued)
         const uint32_t u_n2 = u_nxt + n_groups;
         Unit wk_n2 = wk;
-        if constexpr (G::kSpan && !kLateLoads) wk_n2 = fetch_unit(u_n2 < n_work ? u_n2 : u_cur);
+        if constexpr (G::kSpan) wk_n2 = fetch_unit(u_n2 < n_work ? u_n2 : u_cur);
         if constexpr (!G::kDma) asm volatile("" : "+v"(raw[0]), "+v"(raw[1]), "+v"(raw[2]));
         if constexpr (G::kInRounds > 3 && !G::kDma) asm volatile("" : "+v"(raw[3]));
         if constexpr (G::kInRounds > 4) asm volatile("" : "+v"(raw[4]));
@@ -916,21 +790,12 @@ void src_mfma_wg_kernel(const LeanUnit* __restrict__ units, const uint32_t n_wor
             for (int k = 0; k < (int)G::kStoreRounds; k++) {
                 uint32_t f = G::kThreads * k + tid;
                 if (f >= G::kOutPieces) f = G::kOutPieces - 1;
-                if constexpr (G::kOutLinear) {
-                    op[k] = *(const u32x4*)(stage + 16u * f);
-                } else {
-                    const uint32_t row = f / (G::kRowOut / 16u);
-                    op[k] = *(const u32x4*)(stage + row * G::kRowOutPitch + 16u * (f - row * (G::kRowOut / 16u)));
-                }
+                op[k] = *(const u32x4*)(stage + 16u * f);
             }
 #pragma unroll
             for (int k = 0; k < (int)G::kStoreRounds; k++) {
                 const uint32_t o = mf_here(16u * (G::kThreads * k + tid));
-#if defined(MF_DIAG_NO_STORE)
-                if (o < out_bytes && n_blocks > 1000000u) *(u32x4_u*)(unit_dst + o) = op[k];
-#else
                 if (o < out_bytes) __builtin_nontemporal_store(op[k], (u32x4_u*)(unit_dst + o));
-#endif
             }
         }
         // (the output image has been read.  Packed sources' input image is the pass's run piece for piece, and the output image is too:
@@ -945,27 +810,22 @@ void src_mfma_wg_kernel(const LeanUnit* __restrict__ units, const uint32_t n_wor
             wk_nxt = wk_n2;
             u_cur = u_nxt;
             u_nxt += n_groups;
-#ifndef MF_WG_NO_PRIO
             __builtin_amdgcn_s_setprio(kPrioC);
-#endif
-            wg_barrier<3>();                                // the planes are whole; the run's buffer and the output image are free
+            wg_barrier();                                // the planes are whole; the run's buffer and the output image are free
             if (u_nxt < n_work) issue_dma(wk_nxt);          // (uniform)
             continue;
         }
-        if constexpr (!G::kSpan || !G::kOutLinear) wg_barrier<1>();
+        if constexpr (!G::kSpan) wg_barrier();
         if (u_nxt >= n_work) break;                         // (uniform)
 
         // ---- (A) + (S) the next unit: registers -> input image -> planes; then its successor's input is requested ----
-        if constexpr (G::kSpan && !kLateLoads) {
+        if constexpr (G::kSpan) {
             // ... requested as soon as the registers are free -- behind the stage's writes, in front of the split -- so that it is in
             // flight for (S) and (C), not for (C) alone (round 5: 0.3011 -> 0.3001 ms on the headline, same box, three alternating pairs;
             // that this is all it gains says the launch does not wait for its loads: tools/micro/run_copy.hip)
             stage_input(raw);
             issue_input(wk_n2, raw);
-#ifndef MF_WG_NO_PRIO
-            if constexpr (kPrioS != kPrioD) __builtin_amdgcn_s_setprio(kPrioS);
-#endif
-            wg_barrier<2>();
+            wg_barrier();
             split_all(wk_nxt.first);
             wk = wk_nxt;
             wk_nxt = wk_n2;
@@ -979,10 +839,8 @@ void src_mfma_wg_kernel(const LeanUnit* __restrict__ units, const uint32_t n_wor
         wk_nxt = fetch_unit(u_nxt < n_work ? u_nxt : u_cur);
         issue_input(wk_nxt, raw);
         }
-#ifndef MF_WG_NO_PRIO
         __builtin_amdgcn_s_setprio(kPrioC);
-#endif
-        wg_barrier<3>();
+        wg_barrier();
     }
 }
 
@@ -1007,8 +865,8 @@ bool src_mfma_wg_unit_inside(int64_t src_row0, uint32_t row_src_bytes, uint64_t 
 template <int PLANAR, int PAIRS, bool HB, bool SRC_LE, bool DST_LE>
 static hipError_t launch_wg_one(const ohgpu_ctx* ctx, const ohgpu_batch* b, const SrcFastParams& p, hipStream_t s, WgOccupancy* query)
 {
-    using G = WgGeom<OHGPU_WG_ROWS, PLANAR, PAIRS, HB>;
-    auto kernel = src_mfma_wg_kernel<OHGPU_WG_ROWS, PLANAR, PAIRS, HB, SRC_LE, DST_LE>;
+    using G = WgGeom<kWgRows, PLANAR, PAIRS, HB>;
+    auto kernel = src_mfma_wg_kernel<kWgRows, PLANAR, PAIRS, HB, SRC_LE, DST_LE>;
     const SrcFastPlan& f = b->fast;
     if (f.n_lean == 0) return hipSuccess;
     if (!src_mfma_wg_supported(p.L_blk, p.M_blk, p.channels, p.sb, p.db, G::kPlanes, HB) || p.channels != 2u * PAIRS || f.wg_unit_rows != G::kUnitRows) return hipErrorInvalidValue;

@@ -5,7 +5,6 @@
 
 #include <algorithm>
 #include <functional>
-#include <chrono>
 #include <cstdio>
 #include <cmath>
 #include <cstdlib>
@@ -136,40 +135,27 @@ int plan_src_fast(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_src_msg_desc* desc
     lean = lean && lean_rows == rows && lean_ring == ring;
     if ((lean_only || wg_only) && !lean) return OHGPU_OK;
     // a block: whole phase periods (multiple of L), at least 128 outputs, and a whole number of 64-byte output lines
-    uint32_t min_blk = 128;
-#ifdef OHGPU_DIAG
-    if (const char* e = getenv("OHGPU_DIAG_MIN_BLOCK")) min_blk = (uint32_t)atoi(e);     // (diagnostic builds: longer blocks per lane)
-#endif
-    const uint32_t L_blk = src_block_outputs_for(L, fb_dst, min_blk);
+    const uint32_t L_blk = src_block_outputs_for(L, fb_dst, 128);
     if (L_blk == 0) return OHGPU_OK;
     const uint64_t M_blk64 = (uint64_t)L_blk * M / L;
     if (M_blk64 + T > 32000 || M_blk64 < T) return OHGPU_OK;    // a block is at least one filter length of input
     const uint32_t M_blk = (uint32_t)M_blk64;
 
-    // src_mfma_kernel (round 4) runs the same units for the layouts it serves, from the filter's digit tables -- made for this
-    // block length and rows of up to mf_kb_cap blocks -- with its own number of waves per CU.  src_mfma_wg_kernel (the default where
-    // it applies; ohgpu_set_kernel_variant(5) keeps the unit-per-wave kernel) takes a unit per WORKGROUP: rows of one block, so that
-    // a unit's input and output are each one contiguous run, and no unit whose 32-row input image leaves the arena.
-    uint32_t mf_rows = 0, mf_wave_lds = 0, mf_max_waves = 0;
-    src_mfma_geometry(&mf_rows, &mf_wave_lds, &mf_max_waves);
-    // (mf_layout: 24-bit stereo through the 32-tap tiling -- the layout the unit-per-wave kernel was written for and the workgroup
-    // kernel's first; `mfma`: that kernel itself is in this library, which since round 5 it is only in a legacy build)
+    // src_mfma_wg_kernel (the default where it applies) runs the lean kernel's units from the filter's digit tables -- made for this
+    // block length -- a unit per WORKGROUP: rows of one block, so that a unit's input and output are each one contiguous run.
+    // (mf_layout: 24-bit stereo through the 32-tap tiling, the workgroup kernel's first layout.  `rows == 32` is the row count of
+    // round 4's unit-per-wave kernel, whose geometry this test was written against; stereo's 64 / 2 rows are 32, so it holds)
     const bool mf_layout = lean && !planar && src_mfma_supported(T, ch, sb, db) && flt->d_mf_amat != nullptr && flt->mf_L_blk == L_blk && (L_blk >> 4) <= 16u &&      // (the kernel's bias table: one block's steps)
-                           mf_rows == rows && (M_blk + T) * fb_src < (1u << 24);
-#ifdef OHGPU_LEGACY_KERNELS
-    const bool mfma = mf_layout;
-#else
-    const bool mfma = false;
-#endif
-    // (a planar source -- the FLAC decoder's planes -- is the workgroup kernel's too: its split reads the planes; the unit-per-wave
-    // kernel has no such form, so with variants 3..5 a planar batch stays on the lean kernel)
+                           rows == 32 && (M_blk + T) * fb_src < (1u << 24);
+    // (a planar source -- the FLAC decoder's planes -- is the workgroup kernel's too: its split reads the planes; with variants 3
+    // and 4 a planar batch stays on the lean kernel)
     // (six and eight channels too: the same tiles over channel PAIRS, units of 64 / channels rows as the lean kernel's)
     // (and the half-band 2:1 decimator, from its own tables: build_mfma_halfband)
     const bool wg_hb = flt->mf_halfband && T == 64 && !planar;
     const bool wg_tables = lean && flt->d_mf_amat != nullptr && flt->mf_L_blk == L_blk && (T == 32 || wg_hb) && rows == 64u / ch;
     const bool wg_wide = !planar && (ch > 2 || wg_hb || sb == 2) && (M_blk + T) * fb_src < (1u << 24);     // (and 16-bit stereo)
     const bool mfma_wg = wg_tables && (planar || mf_layout || wg_wide) && src_mfma_wg_supported(L_blk, M_blk, ch, sb, db, planar, wg_hb) &&
-                         !(ctx && (ctx->variant == 5 || ctx->variant == 3 || ctx->variant == 4 || ctx->variant == 2));
+                         !(ctx && (ctx->variant == 3 || ctx->variant == 4));
     if (wg_only && !mfma_wg) return OHGPU_OK;
     // The workgroup kernel walks a unit in passes of 16, 5 or 4 rows (WgGeom::kSR) and does not care how many a unit holds: six- and
     // eight-channel units are cut 30 and 32 rows long instead of the lean kernel's 10 and 8 -- a third to a quarter of the units to
@@ -177,13 +163,6 @@ int plan_src_fast(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_src_msg_desc* desc
     const bool wg_long_units = mfma_wg && !planar && ch > 2;
     if (wg_long_units) rows = ch == 6 ? 30u : 32u;
 
-#ifdef OHGPU_PLAN_TIMING
-    std::vector<std::pair<const char*, std::chrono::steady_clock::time_point>> tps;
-    auto mark = [&](const char* what) { tps.emplace_back(what, std::chrono::steady_clock::now()); };
-    mark("start");
-#else
-    auto mark = [](const char*) {};
-#endif
     // order messages by (stream, output position); a stream is identified by where its absolute frame 0 lives
     // (a batch whose messages are in order already -- the usual one -- reads its "order" from a table of 0, 1, 2, .. kept from plan to
     // plan: allocating and filling one per plan was 0.09 of the headline's 1.3 ms.  Up to a million entries; a plan holds the table
@@ -224,7 +203,6 @@ int plan_src_fast(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_src_msg_desc* desc
     // validation pass has seen that: no pass of this planner's, no sort of half a million messages)
     if (!ordered) std::sort(order_own.begin(), order_own.end(), before);
 
-    mark("order");
     struct SegRun { uint32_t seg; uint64_t blk_lo, blk_hi; uint32_t work_begin; };   // a segment's whole blocks and where its units start in `work`
     // what a stretch of messages contributes (indices local to the stretch until the stretches are put together)
     struct Stretch {
@@ -329,17 +307,10 @@ int plan_src_fast(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_src_msg_desc* desc
     // first bad descriptor, or at the first that is not of the batch's layout or out of order)
     // (... a run of them at a time: one call and its set-up per 128 messages, not per message.  A bad descriptor further on in the run
     // stops the stretch before the pass reaches it -- the plan is thrown away either way, and the first bad one is still the first)
-#ifdef OHGPU_PLAN_TIMING
-    static thread_local uint64_t tsc_check, tsc_grow, tsc_units, tsc_rem;
-    tsc_check = tsc_grow = tsc_units = tsc_rem = 0;
-#define PLAN_TSC(acc, stmt) { const uint64_t t0_ = __builtin_ia32_rdtsc(); stmt; acc += __builtin_ia32_rdtsc() - t0_; }
-#else
-#define PLAN_TSC(acc, stmt) { stmt; }
-#endif
     auto looked_at = [&](Stretch& o, size_t k) -> bool {
         if (!fused || k < o.checked_upto) return true;
         const size_t upto = std::min(k + 128, o.check_end);
-        PLAN_TSC(tsc_check, src_check_range(fused->src, descs, k, upto, b->src_arena_bytes, b->dst_arena_bytes, nullptr, &o.chk));
+        src_check_range(fused->src, descs, k, upto, b->src_arena_bytes, b->dst_arena_bytes, nullptr, &o.chk);
         o.checked_upto = upto;
         return o.chk.err == OHGPU_OK && o.chk.uniform && o.chk.ordered;
     };
@@ -368,7 +339,7 @@ int plan_src_fast(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_src_msg_desc* desc
                 if (before) o.chk.ordered = false;
             }
             if (slow) {
-                PLAN_TSC(tsc_check, src_check_range(fused->src, descs, k, k + 1, b->src_arena_bytes, b->dst_arena_bytes, nullptr, &o.chk));
+                src_check_range(fused->src, descs, k, k + 1, b->src_arena_bytes, b->dst_arena_bytes, nullptr, &o.chk);
                 *sb = src_base_of(d); *db = dst_base_of(d);
             }
             if (o.chk.err != OHGPU_OK || !o.chk.uniform || !o.chk.ordered) return false;
@@ -389,9 +360,6 @@ int plan_src_fast(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_src_msg_desc* desc
             if (d0.n_frames != 0 && (d0.out_frame0 * M) / L < T - 1u) o.stream_start = true;     // (a run's first message reaches furthest back)
             uint64_t next_out = d0.out_frame0 + d0.n_frames;
             bool zero_len = d0.n_frames == 0;
-#ifdef OHGPU_PLAN_TIMING
-            const uint64_t tg0 = __builtin_ia32_rdtsc();
-#endif
             while (!zero_len && e < i_end) {
                 int64_t sb_e, db_e;
                 __builtin_prefetch(&descs[order[e + 32 < i_end ? e + 32 : e]]);
@@ -402,10 +370,6 @@ int plan_src_fast(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_src_msg_desc* desc
                 next_out += d.n_frames;
                 e++;
             }
-#ifdef OHGPU_PLAN_TIMING
-            const uint64_t tg1 = __builtin_ia32_rdtsc();
-            tsc_grow += tg1 - tg0;
-#endif
             const uint64_t m_begin = d0.out_frame0, m_end = next_out;
             uint64_t blk_lo = (m_begin + L_blk - 1) / L_blk, blk_hi = m_end / L_blk;
             // (a stream whose output does not start on a 64-byte boundary is written with unaligned 16-byte stores: they run at
@@ -453,10 +417,6 @@ int plan_src_fast(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_src_msg_desc* desc
                 blk_lo = blk_hi = 0;   // everything goes to the generic kernel
             }
             const uint64_t fast_lo = fast_ok ? blk_lo * L_blk : m_end, fast_hi = fast_ok ? blk_hi * L_blk : m_end;
-#ifdef OHGPU_PLAN_TIMING
-            const uint64_t tg2 = __builtin_ia32_rdtsc();
-            tsc_units += tg2 - tg1;
-#endif
             for (size_t k = i; k < e; k++) {
                 const ohgpu_src_msg_desc& d = descs[order[k]];
                 if (d.n_frames == 0) continue;
@@ -465,9 +425,6 @@ int plan_src_fast(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_src_msg_desc* desc
                 if (lo < fast_lo) { o.rem.push_back(make_piece(d, lo, std::min(hi, fast_lo), L, M)); o.rem_msg.push_back(order[k]); }
                 if (hi > fast_hi) { o.rem.push_back(make_piece(d, std::max(lo, fast_hi), hi, L, M)); o.rem_msg.push_back(order[k]); }
             }
-#ifdef OHGPU_PLAN_TIMING
-            tsc_rem += __builtin_ia32_rdtsc() - tg2;
-#endif
             i = e;
         }
     };
@@ -535,11 +492,6 @@ int plan_src_fast(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_src_msg_desc* desc
         parts.clear();
     }
     if (direct_units ? lean_units.empty() : work.empty()) return OHGPU_OK;
-    mark("segments");
-#ifdef OHGPU_PLAN_TIMING
-    fprintf(stderr, "[plan timing]   (this thread's cycles: check %.2f M, grow less check %.2f M, units %.2f M, remainder %.2f M)\n",
-            tsc_check * 1e-6, (tsc_grow - tsc_check) * 1e-6, tsc_units * 1e-6, tsc_rem * 1e-6);
-#endif
     // ---- the lean kernel's units.  A unit is `rows` rows; a row is `kb` CONSECUTIVE blocks of its stream.  With kb = 1 (round
     // 2) every block pays a filter length of warm-up advances and re-reads that much history (32 frames per 147), and every
     // 160 outputs a unit set-up; a row of kb blocks pays them once.  But long units make the end of the launch coarse -- round
@@ -548,28 +500,21 @@ int plan_src_fast(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_src_msg_desc* desc
     // which stay one block long because a long unit would run the ramp path for all its outputs -- as one-block units for
     // the waves to level out on.
     if (lean) {
-        const uint32_t waves = (ctx && ctx->num_cus > 0 ? (uint32_t)ctx->num_cus : 256u) * (mfma ? mf_max_waves : lean_max_waves);
-        // Same-box A/Bs on the headline workload, alternating passes, +-0.2 % within a box.  Eleven waves per CU
-        // (tools/exp_units3.sh): one block per row everywhere 0.4955 ms; one long unit of 8 blocks per wave 0.4832; 6 blocks and
+        const uint32_t waves = (ctx && ctx->num_cus > 0 ? (uint32_t)ctx->num_cus : 256u) * lean_max_waves;
+        // Same-box A/Bs on the headline workload, alternating passes, +-0.2 % within a box.  Eleven waves per CU:
+        // one block per row everywhere 0.4955 ms; one long unit of 8 blocks per wave 0.4832; 6 blocks and
         // two rounds of short units kept 0.4995; two rounds of 4-block units 0.5025; three rounds of 2-block units 0.4933.
-        // Twelve waves (tools/exp_units4.sh): one block per row 0.496; 7-block units for eleven of twelve waves 0.4475; for
+        // Twelve waves: one block per row 0.496; 7-block units for eleven of twelve waves 0.4475; for
         // EVERY wave (3072 long units for 3072 waves, 0.83 rounds of short ones left) 0.4375; 6-block units 0.50-0.51.  What a
         // long row saves by itself is small (set-up and warm-up are 7 % of a one-block unit; the history it does not re-read is
         // 18 % of the reads); what decides is how the schedule's last units fall, and "every wave exactly one long unit, as
         // long as possible" is the rule that was best at both occupancies.
-        uint32_t kb_max = 8, long_rounds = 0;
-        double tail_rounds = 0.0;                            // (diagnostic: plain work held back from the long units, in rounds of short units)
-#ifdef OHGPU_DIAG
-        if (const char* e = getenv("OHGPU_DIAG_TAIL_ROUNDS")) tail_rounds = atof(e);       // (diagnostic builds: the long/short split)
-        if (const char* e = getenv("OHGPU_DIAG_KB_MAX")) kb_max = (uint32_t)atoi(e);
-        if (const char* e = getenv("OHGPU_DIAG_LONG_ROUNDS")) long_rounds = (uint32_t)atoi(e);
-#endif
-        if (mfma && kb_max > flt->mf_kb_cap) kb_max = flt->mf_kb_cap;      // (the step table's length)
+        uint32_t kb_max = 8;
         if (mfma_wg) kb_max = 1;                                           // (a unit = consecutive blocks)
         // the plain, full one-block units (the only ones that merge), in runs between ramped or partly filled ones
         uint64_t plain_total = 0;
         for (const SrcWork& w : work) plain_total += (!(w.flags & kWorkRamped) && w.n_blocks == rows) ? 1u : 0u;
-        const double plain_avail = (double)plain_total - tail_rounds * waves;
+        const double plain_avail = (double)plain_total;
         uint32_t kb_long = 1;
         uint64_t long_target = 0;                            // long units to cut, over all segments
         if (ctx && ctx->variant == 3 && !mfma_wg) {        // ohgpu_set_kernel_variant(3): the long rows forced, for tests with small batches
@@ -577,7 +522,7 @@ int plan_src_fast(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_src_msg_desc* desc
             long_target = ~(uint64_t)0;
         } else if (plain_avail >= 2.0 * waves && kb_max >= 2) {
             // rounds of long units: one, unless even 8-block units would leave more than that for a second helping
-            const uint32_t n_rounds = long_rounds ? long_rounds : (uint32_t)std::max(1.0, std::ceil(plain_avail / ((double)waves * kb_max) - 0.25));
+            const uint32_t n_rounds = (uint32_t)std::max(1.0, std::ceil(plain_avail / ((double)waves * kb_max) - 0.25));
             kb_long = (uint32_t)(plain_avail / ((double)waves * n_rounds));
             if (kb_long > kb_max) kb_long = kb_max;
             if (kb_long < 2) kb_long = 1;
@@ -669,25 +614,19 @@ int plan_src_fast(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_src_msg_desc* desc
         // (the edge units in front: their checked loads are slow, and the launch should not end on them)
         if (mfma_wg) std::stable_partition(lean_units.begin(), lean_units.end(), [](const LeanUnit& u) { return (u.flags & kWorkEdge) != 0; });
     }
-    // (segments, messages and one-block work units are round 1's kernel's: they go to the device only for a batch planned while
-    // ohgpu_set_kernel_variant(2) is in force, or one the lean kernel cannot run -- 12 MB of the headline's plan, and most of the time its upload took)
-    // (a filter the lean kernel's rounding does not hold -- sum|c| >= 2^29 -- runs on round 1's whatever the variant, where this
-    // library has that kernel for the layout: five stereo layouts in the shipped library, the whole list in a legacy build, which
-    // also takes it under variant 2)
+    // (segments, messages and one-block work units are round 1's kernel's: they go to the device only for a batch the lean kernel
+    // cannot run -- 12 MB of the headline's plan, and most of the time its upload took.  That is a filter the lean kernel's rounding
+    // does not hold -- sum|c| >= 2^29 -- which runs on round 1's whatever the variant, where this library has that kernel for the
+    // layout: the five stereo layouts of OHGPU_BLOCK_FALLBACK_KERNELS)
     const bool round1_built = block_ok && src_block_built(T, ch, sb, src_le, db, dst_le);
-#ifdef OHGPU_LEGACY_KERNELS
-    const bool round1 = round1_built && ((ctx && ctx->variant == 2) || !lean);
-#else
     const bool round1 = round1_built && !lean;
-#endif
     if (!lean && !round1) return OHGPU_OK;                                      // (neither block kernel can take it: the generic kernel's batch)
-    // (round 1's kernel, variant 2, keeps one-block units; ramped first, partly filled units last)
+    // (round 1's kernel keeps one-block units; ramped first, partly filled units last)
     if (round1)
         std::stable_sort(work.begin(), work.end(), [](const SrcWork& x, const SrcWork& y) {
             return ((x.flags & kWorkRamped) ? 3u : 1u) * x.n_blocks > ((y.flags & kWorkRamped) ? 3u : 1u) * y.n_blocks;
         });
 
-    mark("units");
     const std::vector<RampJob> dev_jobs(ramp_jobs.begin(), ramp_jobs.end());        // (the device's records)
     if (digest) {
         // (ohgpu_src_plan_digest: what the plan consists of, hashed; nothing goes to a device)
@@ -709,11 +648,7 @@ int plan_src_fast(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_src_msg_desc* desc
         digest->units = lean ? lean_units.size() : work.size();
         digest->pieces = rem.size();
         digest->ramp_jobs = ramp_jobs.size();
-        digest->kernel = mfma_wg ? 3 : (mfma ? 2 : (lean ? 1 : 0));
-#ifdef OHGPU_PLAN_TIMING
-        for (size_t k = 1; k < tps.size(); k++)
-            fprintf(stderr, "[plan timing]   %s %.2f ms\n", tps[k].first, std::chrono::duration<double, std::milli>(tps[k].second - tps[k - 1].second).count());
-#endif
+        digest->kernel = mfma_wg ? 3 : (lean ? 1 : 0);
         return OHGPU_OK;
     }
     Slab slab;
@@ -744,10 +679,8 @@ int plan_src_fast(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_src_msg_desc* desc
     slab.add(std::vector<uint32_t>(2, 0u), &f.d_counter);            // {units claimed, waves finished}: zero between launches
     slab.add(dev_jobs, &f.d_ramp_jobs);
     slab.reserve((plane_entries ? plane_entries : 8) * sizeof(uint16_t), &f.d_planes);
-    mark("slab");
     int err = slab.upload(ctx, &f.d_slab);
     if (err != OHGPU_OK) { free_src_fast(ctx, b); return err; }
-    mark("upload");
     {   // the planes: preset to "no ramp", then RampApplicator's multiplier for every frame of a ramped message (device)
         hipStream_t s0 = ctx ? ctx->stream : nullptr;
         hipError_t e = hipMemsetAsync(f.d_planes, 0xff, (plane_entries ? plane_entries : 8) * sizeof(uint16_t), s0);
@@ -757,12 +690,6 @@ int plan_src_fast(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_src_msg_desc* desc
         if (e == hipSuccess) e = hipEventRecord(f.planes_ready, s0);
         if (e != hipSuccess) { free_src_fast(ctx, b); return set_error(OHGPU_ERR_DEVICE, "ramp planes: %s", hipGetErrorString(e)); }
     }
-    mark("planes");
-#ifdef OHGPU_PLAN_TIMING
-    for (size_t k = 1; k < tps.size(); k++)
-        fprintf(stderr, "[plan timing]   %s %.2f ms\n", tps[k].first, std::chrono::duration<double, std::milli>(tps[k].second - tps[k - 1].second).count());
-    fprintf(stderr, "[plan timing]   slab %zu bytes, %zu units, %zu ramp jobs, %zu plane entries\n", slab.host.size(), lean_units.size(), ramp_jobs.size(), plane_entries);
-#endif
     f.enabled = true;
     // (what ohgpu_src_batch_set_ramps and ohgpu_src_batch_advance go by: small next to the messages -- a job per ramped message and
     // unit, a piece per block-unaligned message end)
@@ -790,12 +717,11 @@ int plan_src_fast(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_src_msg_desc* desc
     f.lean_wave_lds_bytes = lean_wave_lds;
     f.plane_stride = 16;                                              // SrcWork::plane counts 16-byte pieces
     f.lean_max_waves = lean_max_waves;
-    f.mfma = mfma;
     f.mfma_wg = mfma_wg;
     f.mfma_wg_halfband = mfma_wg && wg_hb;
     f.wg_unit_rows = mfma_wg ? rows : 0u;
-    f.d_mf_amat = (mfma || mfma_wg) ? flt->d_mf_amat : nullptr;
-    f.d_mf_steps = (mfma || mfma_wg) ? flt->d_mf_steps : nullptr;
+    f.d_mf_amat = mfma_wg ? flt->d_mf_amat : nullptr;
+    f.d_mf_steps = mfma_wg ? flt->d_mf_steps : nullptr;
     f.fast_out_frames = fast_frames;
     SrcFastParams& p = f.params;
     memset(&p, 0, sizeof(p));

@@ -80,7 +80,7 @@ def _taps_of(name):
     return t // 2 if _halfband(name) else t
 
 
-@pytest.mark.parametrize("which", ["lean"])     # (round 1's block kernel is retired from the shipped library: OHGPU_LEGACY builds only)
+@pytest.mark.parametrize("which", ["lean"])
 def test_no_scalar_memory_traffic_between_taps(which, request):
     for name, body in request.getfixturevalue(which).items():
         taps = [i for i, l in enumerate(body) if "v_fmac_f64_dpp" in l]
@@ -89,7 +89,7 @@ def test_no_scalar_memory_traffic_between_taps(which, request):
         assert not bad, (name, bad[:3])
 
 
-@pytest.mark.parametrize("which", ["lean"])     # (round 1's block kernel is retired from the shipped library: OHGPU_LEGACY builds only)
+@pytest.mark.parametrize("which", ["lean"])
 def test_no_scratch_and_no_valu_exec_writes(which, request):
     for name, body in request.getfixturevalue(which).items():
         assert not any(re.match(r"^\s*scratch_", l) for l in body), name
@@ -136,7 +136,7 @@ def main_loop(body):
     return body[start:]
 
 
-@pytest.mark.parametrize("which", ["lean"])     # (round 1's block kernel is retired from the shipped library: OHGPU_LEGACY builds only)
+@pytest.mark.parametrize("which", ["lean"])
 def test_every_output_has_its_counted_waits(which, request):
     for name, body in request.getfixturevalue(which).items():
         T = _taps_of(name)
@@ -151,7 +151,7 @@ def test_every_output_has_its_counted_waits(which, request):
             assert set(counted) == {T // 16 - 1}, (name, set(counted))
 
 
-@pytest.mark.parametrize("which", ["lean"])     # (round 1's block kernel is retired from the shipped library: OHGPU_LEGACY builds only)
+@pytest.mark.parametrize("which", ["lean"])
 def test_lds_traffic_keeps_the_order_the_counts_assume(which, request):
     """After every counted wait: [the ring store(s), only after an output's first wait] 16 taps, then the reload of the
     coefficient register those taps used -- and no other LDS instruction in between (the counts in the waits are the
@@ -201,7 +201,7 @@ LOAD = re.compile(r"^\s*(ds_read\w*|global_load_(?:dword\w*|ushort|ubyte|sbyte|s
 ANY_WAIT = {"ds": re.compile(r"s_waitcnt.*lgkmcnt"), "gl": re.compile(r"s_waitcnt.*vmcnt")}
 
 
-@pytest.mark.parametrize("which", ["lean"])     # (round 1's block kernel is retired from the shipped library: OHGPU_LEGACY builds only)
+@pytest.mark.parametrize("which", ["lean"])
 def test_no_instruction_touches_a_load_destination_before_its_wait(which, request):
     """Between a load's issue and the next wait on its counter, no instruction of the straight-line code that follows may
     name the destination registers (the scan stops at a branch or a label: there the next block opens with the wait)."""
@@ -280,7 +280,7 @@ def _uncovered_touches(body):
     return bad
 
 
-@pytest.mark.parametrize("which", ["lean"])     # (round 1's block kernel is retired from the shipped library: OHGPU_LEGACY builds only)
+@pytest.mark.parametrize("which", ["lean"])
 def test_no_lds_read_lands_in_a_register_the_code_has_moved_on_from(which, request):
     for name, body in request.getfixturevalue(which).items():
         assert not _uncovered_touches(body), (name, _uncovered_touches(body)[:3])

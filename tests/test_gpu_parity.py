@@ -701,8 +701,7 @@ def test_a_batch_created_under_one_variant_runs_under_every_other(ctx, created_u
         ctx.src_run(b1, d_src, d_dst)
         assert np.array_equal(ctx.download(d_dst, dbytes), want)
         ctx.batch_destroy(b1)
-        # (rounds 1's block kernel and round 4's unit-per-wave matrix kernel are retired from the shipped library: variants 2 and 5,
-        # like 3 and 4, run the lean kernel on a plan the workgroup kernel does not take)
+        # (variants 2 and 5 are aliases of 4: like 3 and 4 they run the lean kernel on a plan the workgroup kernel does not take)
         if created_under == 0:
             assert names[0] == "src_mfma_wg_kernel" and all(names[v] == "src_lean_kernel" for v in (2, 3, 4, 5)), names
         else:
