@@ -370,8 +370,77 @@ int ohgpu_src_batch_set_ramps(ohgpu_ctx* ctx, ohgpu_batch* batch, const uint16_t
 int ohgpu_src_process_host(ohgpu_ctx* ctx, const ohgpu_src* src, const ohgpu_src_msg_desc* descs, size_t n,
                            const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes);
 
+/* ---- pulled resampler (own specification; DESIGN.md 4b "Pulled resampling") ----
+ * The stand-in for IPullableClock::PullClock (ClockPuller.h:17-34) when one device serves many streams against one output clock:
+ * instead of pulling a DAC, each stream's resampling ratio follows its own clock controller, message by message.  One prototype
+ * (Kaiser-windowed sinc, P = 2^phases_log2 phases per input frame, T taps per phase) serves every ratio near rate_in -> rate_out;
+ * a message carries its own position and step:
+ *   output j of a message:  u = pos_frac + j * step (64 bits),  n = pos_frame + (u >> 32),  f = u & 0xffffffff,
+ *                           p = f >> (32 - s),  w = (f >> (16 - s)) & 0xffff,
+ *                           c_k = C[p][k] + (((C[p+1][k] - C[p][k]) * w) >> 16),
+ *                           y = clamp_s24((sum_k c_k * x[n - k] + 2^27) >> 28)   (x: S24, frames before the stream start are 0)
+ * then RampApplicator's 24-bit case and the pack, as for ohgpu_src_msg_desc.  Splitting a message after k outputs gives a
+ * message at pos + k * step (the carry goes into pos_frame) whose bytes equal the tail of the unsplit one's. */
+#define OHGPU_SRC_PULL_NOMINAL     (1u << 31)            /* IPullableClock::kNominalFreq: multiplier 1.0 in fix 1.31 */
+#define OHGPU_SRC_PULL_MAX_STEP    (16ull << 32)         /* at most 16 input frames per output frame (Q32.32) */
+
+/* One OUTPUT message of a pulled stream.  80 bytes.  The fields of ohgpu_src_msg_desc, with out_frame0 replaced by the
+ * message's position (pos_frame + pos_frac / 2^32 input frames) and its step (Q32.32 input frames per output frame).  The input
+ * buffer rules are ohgpu_src_msg_desc's: ohgpu_src_pull_window gives the frames a message reads. */
+typedef struct ohgpu_src_pull_msg_desc {
+    uint64_t src_offset;    /* bytes from src_base to input frame src_frame0                        */
+    uint64_t src_frame0;    /* absolute index of the first input frame held in the buffer           */
+    uint64_t src_frames;    /* number of input frames held                                          */
+    uint64_t pos_frame;     /* integer part of output 0's input position                            */
+    uint64_t step;          /* Q32.32 input frames per output frame, 1 .. OHGPU_SRC_PULL_MAX_STEP   */
+    uint64_t dst_offset;    /* bytes from dst_base                                                  */
+    uint32_t pos_frac;      /* fractional part of output 0's input position, units of 2^-32         */
+    uint32_t n_frames;      /* output frames in this message                                        */
+    uint16_t ramp_start;
+    uint16_t ramp_end;
+    uint16_t attenuation;   /* must be 256                                                          */
+    uint8_t  channels;      /* 1..8                                                                 */
+    uint8_t  src_bits;      /* 8, 16, 24, 32 packed                                                 */
+    uint8_t  src_endian;
+    uint8_t  dst_bits;      /* 16, 24, 32                                                           */
+    uint8_t  dst_endian;
+    uint8_t  flags;         /* OHGPU_FLAG_RAMP | OHGPU_FLAG_ZERO_LSB32                              */
+    uint8_t  reserved[4];   /* zero                                                                 */
+    uint64_t src_plane_stride; /* 0 (planar sources are not supported on the pulled path)          */
+} ohgpu_src_pull_msg_desc;
+
+/* Host only.  The Q28 table of (P + 1) rows of T, P = 2^phases_log2, from the prototype h[n], n = 0 .. T*P - 1: for p < P,
+ * coef_q28[p*T + k] = round(h[p + k*P] / g_p * 2^28) with g_p = sum_k h[p + k*P] (each row scaled to DC gain 1 on its own, so it sums
+ * to 2^28 within T / 2); row P is row 0 moved on one tap (coef_q28[P*T + k] = coef_q28[k + 1], the last 0: h[T*P] = 0).  The band
+ * edges (f_stop = rate_out - f_pass, or rate_in - f_pass from 2x upsampling on; cutoff midway) hold for every input
+ * rate in rate_in * [1 - max_pull, 1 + max_pull].  OHGPU_ERR_INVALID for phases_log2 outside 1 .. 16, taps_per_phase other than 32
+ * or 64, a pass band that meets the stop band, a table beyond the exact-accumulation bound, or a capacity below (P + 1) * T. */
+int ohgpu_src_pull_design(uint32_t rate_in, uint32_t rate_out, uint32_t taps_per_phase, uint32_t phases_log2, double beta,
+                          double f_pass_hz, double max_pull, int32_t* coef_q28, size_t coef_capacity);
+/* Host only.  step = floor(2 * rate_in * multiplier / rate_out): multiplier in fix 1.31 (OHGPU_SRC_PULL_NOMINAL = 1.0); above
+ * nominal consumes input faster.  OHGPU_ERR_INVALID for a zero rate, or a step that is zero or beyond OHGPU_SRC_PULL_MAX_STEP. */
+int ohgpu_src_pull_step(uint32_t rate_in, uint32_t rate_out, uint32_t multiplier, uint64_t* step);
+/* Host only.  The input frames [first, first + frames) a message of n_frames outputs reads (first clamped at the stream start).
+ * OHGPU_ERR_INVALID for n_frames == 0, a bad step, or n_frames * step overflowing. */
+int ohgpu_src_pull_window(uint64_t pos_frame, uint32_t pos_frac, uint64_t step, uint32_t n_frames, uint32_t taps_per_phase,
+                          uint64_t* first, uint64_t* frames);
+/* The table on the device.  OHGPU_ERR_UNSUPPORTED for a table that does not fit the kernel's LDS (up to 2^8 phases, T = 32 or
+ * 64); OHGPU_ERR_INVALID as ohgpu_src_pull_design refuses.  A pulled filter is for the calls below only:
+ * ohgpu_src_batch_create refuses it, and these refuse a fixed-ratio filter (OHGPU_ERR_INVALID). */
+int ohgpu_src_pull_create(ohgpu_ctx* ctx, uint32_t taps_per_phase, uint32_t phases_log2, const int32_t* coef_q28, ohgpu_src** src);
+int ohgpu_src_pull_destroy(ohgpu_ctx* ctx, ohgpu_src* src);
+/* Validated like ohgpu_src_batch_create (OHGPU_ERR_BOUNDS / _INVALID / _UNSUPPORTED, nothing kept on a refusal); freed with
+ * ohgpu_batch_destroy; ohgpu_batch_info counts its messages.  The batch holds no per-launch device state: it may be run any
+ * number of times, on any stream. */
+int ohgpu_src_pull_batch_create(ohgpu_ctx* ctx, const ohgpu_src* src, const ohgpu_src_pull_msg_desc* descs, size_t n,
+                                uint64_t src_arena_bytes, uint64_t dst_arena_bytes, ohgpu_batch** batch);
+int ohgpu_src_pull_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* src_base, void* dst_base, void* stream);
+/* Host-buffer convenience, as ohgpu_src_process_host (the context's arenas and staging; nothing allocated in a steady state). */
+int ohgpu_src_pull_process_host(ohgpu_ctx* ctx, const ohgpu_src* src, const ohgpu_src_pull_msg_desc* descs, size_t n,
+                                const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes);
+
 /* What the *_process_host calls of this context have moved so far: their number, how many of them were ohgpu_src_process_host,
- * and the bytes copied to and from the device for audio (descriptors and plans not counted).  A driver's handle on "one call per
+ * or ohgpu_src_pull_process_host, and the bytes copied to and from the device for audio (descriptors and plans not counted).  A driver's handle on "one call per
  * filter per period, windows only" (tests/cpp/test_host.cpp, bench.py's cadence.adapter). */
 int ohgpu_host_transfer_stats(ohgpu_ctx* ctx, uint64_t* calls, uint64_t* src_calls, uint64_t* h2d_bytes, uint64_t* d2h_bytes);
 

@@ -31,6 +31,17 @@ SRC_MSG_DESC = np.dtype([
     ("channels", "u1"), ("src_bits", "u1"), ("src_endian", "u1"),
     ("dst_bits", "u1"), ("dst_endian", "u1"), ("flags", "u1"), ("src_plane_stride", "<u8")], align=False)
 
+# ohgpu_src_pull_msg_desc (80 B): the pulled resampler's message
+SRC_PULL_MSG_DESC = np.dtype([
+    ("src_offset", "<u8"), ("src_frame0", "<u8"), ("src_frames", "<u8"), ("pos_frame", "<u8"), ("step", "<u8"),
+    ("dst_offset", "<u8"), ("pos_frac", "<u4"), ("n_frames", "<u4"),
+    ("ramp_start", "<u2"), ("ramp_end", "<u2"), ("attenuation", "<u2"),
+    ("channels", "u1"), ("src_bits", "u1"), ("src_endian", "u1"),
+    ("dst_bits", "u1"), ("dst_endian", "u1"), ("flags", "u1"), ("reserved", "u1", (4,)), ("src_plane_stride", "<u8")], align=False)
+assert SRC_PULL_MSG_DESC.itemsize == 80
+SRC_PULL_NOMINAL = 1 << 31
+SRC_PULL_MAX_STEP = 16 << 32
+
 FMT_UNPACK_PLANAR, FMT_SENDER_PACK, FMT_FLAC_PACK = 1, 2, 3
 FMT_DESC = np.dtype([
     ("src_offset", "<u8"), ("dst_offset", "<u8"), ("src_plane_stride", "<u8"), ("dst_plane_stride", "<u8"),
@@ -123,6 +134,14 @@ SYMBOLS = {
     "ohgpu_src_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64]),
     "ohgpu_host_transfer_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "ohgpu_set_kernel_variant": (C.c_int, [_vp, C.c_int]),
+    "ohgpu_src_pull_design": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double, _vp, C.c_size_t]),
+    "ohgpu_src_pull_step": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _u64p]),
+    "ohgpu_src_pull_window": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _u64p, _u64p]),
+    "ohgpu_src_pull_create": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _vpp]),
+    "ohgpu_src_pull_destroy": (C.c_int, [_vp, _vp]),
+    "ohgpu_src_pull_batch_create": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
+    "ohgpu_src_pull_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "ohgpu_src_pull_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64]),
 }
 
 
@@ -224,6 +243,29 @@ def src_design(rate_in, rate_out, taps_per_phase=32, beta=9.0, f_pass=20000.0):
     check(lib().ohgpu_src_design(rate_in, rate_out, taps_per_phase, beta, f_pass, coef.ctypes.data_as(C.c_void_p),
                                  coef.size, C.byref(L_), C.byref(M_)))
     return L_.value, M_.value, coef
+
+
+def src_pull_design(rate_in, rate_out, taps_per_phase=32, phases_log2=8, beta=8.0, f_pass=20000.0, max_pull=0.001):
+    """The pulled resampler's Q28 table, shape (2^phases_log2 + 1, taps_per_phase) (ohgpu_src_pull_design; host only)."""
+    rows = (1 << phases_log2) + 1 if 0 <= phases_log2 <= 16 else 1
+    coef = np.zeros(rows * taps_per_phase, dtype=np.int32)
+    check(lib().ohgpu_src_pull_design(rate_in, rate_out, taps_per_phase, phases_log2, beta, f_pass, max_pull,
+                                      coef.ctypes.data_as(C.c_void_p), coef.size))
+    return coef.reshape(rows, taps_per_phase)
+
+
+def src_pull_step(rate_in, rate_out, multiplier=SRC_PULL_NOMINAL):
+    """floor(2 * rate_in * multiplier / rate_out): Q32.32 input frames per output frame (ohgpu_src_pull_step; host only)."""
+    st = C.c_uint64(0)
+    check(lib().ohgpu_src_pull_step(rate_in, rate_out, multiplier, C.byref(st)))
+    return int(st.value)
+
+
+def src_pull_window(pos_frame, pos_frac, step, n_frames, taps_per_phase):
+    """(first, frames): the input frames a pulled message reads (ohgpu_src_pull_window; host only)."""
+    first, frames = C.c_uint64(0), C.c_uint64(0)
+    check(lib().ohgpu_src_pull_window(pos_frame, pos_frac, step, n_frames, taps_per_phase, C.byref(first), C.byref(frames)))
+    return int(first.value), int(frames.value)
 
 
 class Context:
@@ -478,3 +520,33 @@ class Context:
             check(lib().ohgpu_src_batch_run_timed(self._h, batch, d_src, d_dst, stream, events[0], events[1]))
         else:
             check(lib().ohgpu_src_batch_run(self._h, batch, d_src, d_dst, stream))
+
+    # ---- the pulled resampler
+    def src_pull_create(self, taps_per_phase, phases_log2, coef_q28):
+        c = np.ascontiguousarray(coef_q28, dtype=np.int32)
+        s = C.c_void_p()
+        check(lib().ohgpu_src_pull_create(self._h, taps_per_phase, phases_log2, c.ctypes.data_as(C.c_void_p), C.byref(s)))
+        return s
+
+    def src_pull_destroy(self, src):
+        check(lib().ohgpu_src_pull_destroy(self._h, src))
+
+    def src_pull_batch(self, src, descs, src_arena_bytes, dst_arena_bytes):
+        d = np.ascontiguousarray(descs)
+        assert d.dtype == SRC_PULL_MSG_DESC
+        b = C.c_void_p()
+        check(lib().ohgpu_src_pull_batch_create(self._h, src, d.ctypes.data_as(C.c_void_p), d.size, src_arena_bytes,
+                                                dst_arena_bytes, C.byref(b)))
+        return b
+
+    def src_pull_run(self, batch, d_src, d_dst, stream=None):
+        check(lib().ohgpu_src_pull_batch_run(self._h, batch, d_src, d_dst, stream))
+
+    def src_pull_process_host(self, src, descs, src_bytes, dst_bytes_array):
+        """ohgpu_src_pull_process_host: host buffers in, host buffers out."""
+        d = np.ascontiguousarray(descs)
+        assert d.dtype == SRC_PULL_MSG_DESC
+        check(lib().ohgpu_src_pull_process_host(self._h, src, d.ctypes.data_as(C.c_void_p), d.size,
+                                                src_bytes.ctypes.data_as(C.c_void_p), src_bytes.nbytes,
+                                                dst_bytes_array.ctypes.data_as(C.c_void_p), dst_bytes_array.nbytes))
+        return dst_bytes_array

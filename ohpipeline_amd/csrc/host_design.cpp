@@ -1,5 +1,6 @@
 // host_design.cpp -- host-side tables the device kernels consume: the RampArray multipliers and the
 // polyphase resampler's Q28 coefficients.  Product code (never calls into oracle/).
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <vector>
@@ -101,6 +102,75 @@ int design_src(uint32_t rate_in, uint32_t rate_out, uint32_t T, double beta, dou
     // sum|c| < 2^30 and |x| <= 2^23 keep every partial sum an integer below 2^53: fp64 accumulation is then exact
     if (worst >= ((int64_t)1 << 30))
         return set_error(OHGPU_ERR_INVALID, "src design: sum|c| = %lld breaks the exact-accumulation bound", (long long)worst);
+    return OHGPU_OK;
+}
+
+
+// The pulled resampler's table.  The prototype h[n], n = 0 .. T*P - 1, is sampled at P = 2^s phases per input
+// frame; frequencies below are in cycles per input frame at an input rate pulled anywhere in rate_in * [1 - max_pull, 1 + max_pull]:
+// the pass edge at the slowest such rate, the stop edge (DESIGN.md 4's rule) at the fastest, the cutoff midway.  Rows p = 0 .. P of
+// T: coef[p*T + k] = round(h[p + k*P] / g_p * 2^28) with g_p = sum_k h[p + k*P] and h[T*P] = 0 (row P is row 0 moved on one tap).
+int design_src_pull(uint32_t rate_in, uint32_t rate_out, uint32_t T, uint32_t s, double beta, double f_pass, double max_pull,
+                    std::vector<int32_t>* coef_q28)
+{
+    if (rate_in == 0 || rate_out == 0) return set_error(OHGPU_ERR_INVALID, "src pull design: zero rate");
+    if (T != 32 && T != 64) return set_error(OHGPU_ERR_INVALID, "src pull design: %u taps per phase (32 or 64)", T);
+    if (s < 1 || s > 16) return set_error(OHGPU_ERR_INVALID, "src pull design: phases_log2 %u outside 1..16", s);
+    if (!(max_pull >= 0.0 && max_pull < 0.5) || !(f_pass > 0.0) || !(beta >= 0.0))
+        return set_error(OHGPU_ERR_INVALID, "src pull design: max_pull %g, f_pass %g, beta %g", max_pull, f_pass, beta);
+    // (from 2x upsampling on the images of the pass band, not the output's alias, set the stop edge: at exactly 2x the output's
+    // rule would put the cutoff at the input rate)
+    double f_stop = (double)rate_out - f_pass;
+    if (f_stop > (double)rate_in - f_pass && rate_out >= 2 * rate_in) f_stop = (double)rate_in - f_pass;
+    const double fp = f_pass / ((double)rate_in * (1.0 - max_pull));
+    const double fs = f_stop / ((double)rate_in * (1.0 + max_pull));
+    if (!(fs > fp)) return set_error(OHGPU_ERR_INVALID, "src pull design: stop edge %g <= pass edge %g (cycles per input frame)", fs, fp);
+    const uint32_t P = 1u << s;
+    const uint64_t N = (uint64_t)T * P;
+    const double fc = 0.5 * (fp + fs);
+    const double wc = 2.0 * fc / (double)P;
+    const double centre = 0.5 * (double)(N - 1);
+    const double i0b = bessel_i0(beta);
+    std::vector<double> h(N + 1, 0.0);
+    for (uint64_t n = 0; n < N; n++) {
+        const double d = (double)n - centre;
+        const double x = wc * d;
+        const double sinc = (std::fabs(x) < 1e-12) ? 1.0 : std::sin(M_PI * x) / (M_PI * x);
+        const double r = d / centre;
+        const double arg = 1.0 - r * r;
+        h[n] = wc * sinc * bessel_i0(beta * std::sqrt(arg > 0.0 ? arg : 0.0)) / i0b;
+    }
+    // each row p < P is scaled to DC gain 1 on its own (the sampled prototype's phases differ in gain by up to 1e-4 of it: the stop
+    // band's aliases), so that every row sums to 2^28 within T / 2; row P is row 0 moved on one tap
+    coef_q28->assign((size_t)(P + 1) * T, 0);
+    for (uint32_t p = 0; p < P; p++) {
+        double row = 0.0;
+        for (uint32_t k = 0; k < T; k++) row += h[p + (uint64_t)k * P];
+        for (uint32_t k = 0; k < T; k++)
+            (*coef_q28)[(size_t)p * T + k] = (int32_t)std::floor(h[p + (uint64_t)k * P] / row * 268435456.0 + 0.5);
+    }
+    for (uint32_t k = 0; k + 1 < T; k++) (*coef_q28)[(size_t)P * T + k] = (*coef_q28)[k + 1];
+    return check_src_pull_table(T, s, coef_q28->data(), "src pull design");
+}
+
+// Every interpolated coefficient lies between its two rows' values, so sum_k max(|C[p][k]|, |C[p+1][k]|) < 2^30 keeps |acc| < 2^53
+// for S24 input: fp64 accumulation is exact in any order.  The kernel forms the interpolation as mulhi(2 * (C[p+1] - C[p]), w << 15),
+// which needs every difference below 2^30 as well.
+int check_src_pull_table(uint32_t T, uint32_t s, const int32_t* c, const char* who)
+{
+    const uint32_t P = 1u << s;
+    for (uint32_t p = 0; p < P; p++) {
+        int64_t bound = 0;
+        for (uint32_t k = 0; k < T; k++) {
+            const int64_t a = c[(size_t)p * T + k], b = c[(size_t)(p + 1) * T + k];
+            bound += std::max(a < 0 ? -a : a, b < 0 ? -b : b);
+            if ((b - a) >= ((int64_t)1 << 30) || (a - b) >= ((int64_t)1 << 30))
+                return set_error(OHGPU_ERR_INVALID, "%s: rows %u and %u differ by 2^30 or more at tap %u", who, p, p + 1, k);
+        }
+        if (bound >= ((int64_t)1 << 30))
+            return set_error(OHGPU_ERR_INVALID, "%s: rows %u and %u have sum max|c| = %lld >= 2^30 (exact fp64 accumulation bound)", who, p,
+                             p + 1, (long long)bound);
+    }
     return OHGPU_OK;
 }
 

@@ -309,7 +309,7 @@ struct OhmPlan {
     uint32_t n_unfolded = 0, n_unfolded_generic = 0;
 };
 
-enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5 };
+enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6 };
 
 }  // namespace ohgpu
 
@@ -363,6 +363,11 @@ struct ohgpu_src {
     ohgpu::MfStep* d_mf_steps = nullptr;
     uint32_t mf_L_blk = 0;
     bool     mf_halfband = false; // ... in the half-band form: one coefficient image for every step (build_mfma_halfband)
+    // a pulled filter (ohgpu_src_pull_create): T taps, 2^phases_log2 phases, the (P + 1) x T Q28 table; L = M = 0 and no fixed-ratio
+    // tables.  The fixed-ratio calls refuse it, the pulled ones refuse anything else.
+    bool     pulled = false;
+    uint32_t phases_log2 = 0;
+    int32_t* d_pull_table = nullptr;
 };
 
 namespace ohgpu {
@@ -399,6 +404,8 @@ struct ohgpu_batch {
     ohgpu::FlywheelPlan fly;      // kBatchFlywheel only
     ohgpu::FmtLinePlan fmtline;   // kBatchFmt only
     ohgpu::OhmPlan ohm;           // kBatchOhm only
+    void*    d_pull_tiles = nullptr;   // kBatchSrcPull: PullTile[n_pull_tiles] on the device (d_descs holds the messages)
+    uint32_t n_pull_tiles = 0;
     // kBatchSrc whose messages differ in layout: one uniform batch per layout (each with its own block-kernel plan), run one
     // after the other; this batch keeps every descriptor for the generic kernel (ohgpu_set_kernel_variant(1)).
     std::vector<ohgpu_batch*> parts;
@@ -480,8 +487,28 @@ bool src_lean_halfband_supported(uint32_t T, uint32_t ch, uint32_t sb, uint32_t 
 bool src_block_geometry(uint32_t L, uint32_t T, uint32_t ch, uint32_t sb, uint32_t db, uint32_t out_per_drain,
                         uint32_t* rows, uint32_t* ring_bytes, uint32_t* coef_lds_bytes, uint32_t* wave_lds_bytes, uint32_t* max_waves);
 
+// The pulled resampler (csrc/src_pull_kernel.hip): a batch is cut on the host into tiles of up to kPullTile consecutive outputs of
+// one message whose input window fits the workgroup's LDS window; a persistent grid loops over them.
+constexpr uint32_t kPullTile = 256;
+struct PullTile {             // 32 bytes
+    uint32_t msg;             // index into the batch's descriptors
+    uint32_t j0;              // first output of the tile within its message
+    uint32_t count;           // outputs, 1 .. kPullTile
+    uint32_t win_frames;      // input frames staged: [win_first, win_first + win_frames)
+    int64_t  win_first;       // absolute input frame (negative at a stream start: those frames are zeros)
+    uint64_t reserved;
+};
+static_assert(sizeof(PullTile) == 32, "PullTile");
+static_assert(sizeof(ohgpu_src_pull_msg_desc) == 80, "ohgpu_src_pull_msg_desc layout");
+uint32_t src_pull_window_cap(uint32_t T);                     // LDS window of a tile, in subsamples
+uint32_t src_pull_lds_bytes(uint32_t T, uint32_t phases_log2);  // table + window
+hipError_t launch_src_pull(const ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
+
 // host helpers
 void build_ramp_table(uint16_t out[512]);
+int  design_src_pull(uint32_t rate_in, uint32_t rate_out, uint32_t T, uint32_t phases_log2, double beta, double f_pass,
+                     double max_pull, std::vector<int32_t>* coef_q28);
+int  check_src_pull_table(uint32_t T, uint32_t phases_log2, const int32_t* coef_q28, const char* who);
 int  design_src(uint32_t rate_in, uint32_t rate_out, uint32_t T, double beta, double f_pass,
                 std::vector<int32_t>* coef_q28, uint32_t* L, uint32_t* M);
 // floor(t / d) for a divisor fixed over many t: a 64 x 64 -> 128 multiply by floor((2^64 - 1) / d) and at most two steps up (the

@@ -7,6 +7,7 @@
 #include <map>
 
 #include "../../include/ohgpu.h"
+#include "PullableSampleRateConverter.h"
 #include "SampleRateConverter.h"
 
 namespace OpenHome {
@@ -159,6 +160,10 @@ MsgAudio* MsgAudioPcm::Allocate()
     MsgAudioPcm* msg = new MsgAudioPcm(iFactory, iAudioData, iSampleRate, iBitDepth, iNumChannels, iTrackOffset);
     msg->iResampled = iResampled;
     msg->iResampledFrame0 = iResampledFrame0;
+    msg->iPulled = iPulled;
+    msg->iPullPosFrame = iPullPosFrame;
+    msg->iPullPosFrac = iPullPosFrac;
+    msg->iPullStep = iPullStep;
     msg->iAttenuation = iAttenuation;
     return msg;
 }
@@ -205,9 +210,17 @@ MsgPlayable* MsgAudioPcm::CreatePlayable()
         work.attenuation = iAttenuation;
         work.ramp = iRamp;
         work.resampled = iResampled != nullptr;
+        work.pulled = iPulled != nullptr;
         if (work.resampled) {
             work.stream = iResampled;
             work.outFrame0 = iResampledFrame0 + firstFrame;
+        }
+        else if (work.pulled) {                                    // the split identity: output k is at pos + k * step
+            work.pullStream = iPulled;
+            work.pullStep = iPullStep;
+            work.pullPosFrame = iPullPosFrame;
+            work.pullPosFrac = iPullPosFrac;
+            PullAdvance(work.pullPosFrame, work.pullPosFrac, work.pullStep, firstFrame);
         }
         else {
             work.audio = iAudioData;
@@ -284,6 +297,7 @@ MsgPlayable* MsgPlayable::Split(TUint aBytes)
     tail.sizeBytes -= aBytes;
     tail.frames = tail.sizeBytes / frameBytes;
     tail.outFrame0 += headFrames;
+    if (tail.pulled) PullAdvance(tail.pullPosFrame, tail.pullPosFrac, tail.pullStep, headFrames);
     tail.ramp = iWork.ramp.IsEnabled() ? iWork.ramp.Split(aBytes, iWork.sizeBytes) : Media::Ramp();
     MsgPlayable* rest = new MsgPlayable(iFactory, tail, iJiffies - headJiffies);
     iWork.sizeBytes = aBytes;
@@ -302,35 +316,45 @@ void MsgPlayable::Read(IPcmProcessor& aProcessor)
 
 // ---------------------------------------------------------------- PlayableBatch
 struct PlayableBatch::WindowRun {
-    SampleRateConverterStream* stream;
+    const SampleRateConverterStream* stream;         // a fixed-ratio stream's window, or ...
     TUint64 firstFrame;              // the union window of the run's items: input frames [firstFrame, firstFrame + frames)
     TUint frames;
     TUint64 nextOut;                 // the output frame an item must start at to join the run
     TUint64 srcOffset;               // of the window, in its group's part of the source arena
+    const PullableSampleRateConverterStream* pulled = nullptr;   // ... a pulled stream's
+    TUint FrameBytes() const { return stream != nullptr ? stream->FrameBytes() : pulled->FrameBytes(); }
+    void CopyFrames(TByte* aDst) const
+    {
+        if (stream != nullptr) stream->CopyFrames(firstFrame, frames, aDst);
+        else pulled->CopyFrames(firstFrame, frames, aDst);
+    }
 };
 
 struct PlayableBatch::Group {
-    const SrcFilter* filter = nullptr;                    // nullptr: the plain audio (one ohgpu_pcm_process_host)
+    const SrcFilter* filter = nullptr;                    // nullptr: the plain audio (one ohgpu_pcm_process_host) or ...
+    const PullFilter* pullFilter = nullptr;               // ... the pulled audio of one filter (one ohgpu_src_pull_process_host)
     std::vector<size_t> items;
     std::vector<ohgpu_msg_desc> pcm;
     std::vector<ohgpu_src_msg_desc> src;
+    std::vector<ohgpu_src_pull_msg_desc> pull;
     std::vector<WindowRun> runs;
     std::vector<size_t> runOf;                            // per resampled item: its run
     TUint64 srcBase = 0, srcBytes = 0, dstBase = 0, dstBytes = 0;
-    void Clear() { items.clear(); pcm.clear(); src.clear(); runs.clear(); runOf.clear(); srcBase = srcBytes = dstBase = dstBytes = 0; }
+    void Clear() { items.clear(); pcm.clear(); src.clear(); pull.clear(); runs.clear(); runOf.clear(); srcBase = srcBytes = dstBase = dstBytes = 0; }
 };
 
 struct PlayableBatch::Scratch {
     std::deque<Group> groups;                             // [0] the plain audio, [1 + k] the k-th filter met (a deque: Take's references stay valid)
     size_t used = 0;
     std::map<const DecodedAudio*, TUint64> audioBase;
-    Group& Take(const SrcFilter* aFilter)
+    Group& Take(const SrcFilter* aFilter, const PullFilter* aPullFilter = nullptr)
     {
-        for (size_t g = 0; g < used; g++) if (groups[g].filter == aFilter) return groups[g];
+        for (size_t g = 0; g < used; g++) if (groups[g].filter == aFilter && groups[g].pullFilter == aPullFilter) return groups[g];
         if (used == groups.size()) groups.emplace_back();
         Group& g = groups[used++];
         g.Clear();
         g.filter = aFilter;
+        g.pullFilter = aPullFilter;
         return g;
     }
 };
@@ -382,9 +406,23 @@ void PlayableBatch::Run()
         if (w.frames == 0) {
             continue;
         }
-        Group& g = w.resampled ? sc.Take(&w.stream->Filter()) : plain;
+        Group& g = w.resampled ? sc.Take(&w.stream->Filter()) : (w.pulled ? sc.Take(nullptr, &w.pullStream->Filter()) : plain);
         g.items.push_back(i);
-        if (w.resampled) {
+        if (w.pulled) {
+            uint64_t first = 0, frames = 0;
+            const int err = ohgpu_src_pull_window(w.pullPosFrame, w.pullPosFrac, w.pullStep, w.frames, w.pullStream->Filter().T, &first, &frames);
+            ASSERT(err == OHGPU_OK);
+            const PullableSampleRateConverterStream* ring = w.pullStream.get();
+            WindowRun* r = g.runs.empty() ? nullptr : &g.runs.back();
+            if (r != nullptr && r->pulled == ring && first >= r->firstFrame && first <= r->firstFrame + r->frames) {
+                r->frames = (TUint)std::max<TUint64>(r->frames, first + frames - r->firstFrame);   // overlaps or follows on: one window
+            }
+            else {
+                g.runs.push_back({nullptr, first, (TUint)frames, 0, 0, ring});
+            }
+            g.runOf.push_back(g.runs.size() - 1);
+        }
+        else if (w.resampled) {
             TUint64 first = 0;
             TUint frames = 0;
             w.stream->Window(w.outFrame0, w.frames, first, frames);
@@ -408,7 +446,7 @@ void PlayableBatch::Run()
         Group& g = sc.groups[k];
         for (WindowRun& r : g.runs) {
             r.srcOffset = g.srcBytes;
-            g.srcBytes += ((TUint64)r.frames * r.stream->FrameBytes() + 15u) & ~(TUint64)15u;
+            g.srcBytes += ((TUint64)r.frames * r.FrameBytes() + 15u) & ~(TUint64)15u;
         }
         for (size_t i : g.items) {
             const PlayableWork& w = iItems[i].playable->Work();
@@ -430,12 +468,35 @@ void PlayableBatch::Run()
     for (size_t k = 0; k < sc.used; k++) {
         Group& g = sc.groups[k];
         for (const WindowRun& r : g.runs) {
-            r.stream->CopyFrames(r.firstFrame, r.frames, src + g.srcBase + r.srcOffset);
+            r.CopyFrames(src + g.srcBase + r.srcOffset);
         }
         size_t nthResampled = 0;
         for (size_t i : g.items) {
             const PlayableWork& w = iItems[i].playable->Work();
-            if (w.resampled) {
+            if (w.pulled) {
+                const WindowRun& r = g.runs[g.runOf[nthResampled++]];
+                ohgpu_src_pull_msg_desc d;
+                memset(&d, 0, sizeof(d));
+                d.src_offset = r.srcOffset;
+                d.src_frame0 = r.firstFrame;
+                d.src_frames = r.frames;
+                d.pos_frame = w.pullPosFrame;
+                d.pos_frac = w.pullPosFrac;
+                d.step = w.pullStep;
+                d.dst_offset = iItems[i].outOffset;
+                d.n_frames = w.frames;
+                d.ramp_start = (uint16_t)w.ramp.Start();
+                d.ramp_end = (uint16_t)w.ramp.End();
+                d.attenuation = OHGPU_UNITY_ATTENUATION;
+                d.channels = (uint8_t)w.channels;
+                d.src_bits = (uint8_t)w.pullStream->SourceBitDepth();
+                d.src_endian = GpuEndian(w.pullStream->SourceEndian());
+                d.dst_bits = (uint8_t)iItems[i].outBits;
+                d.dst_endian = GpuEndian(iOutEndian);
+                d.flags = w.ramp.IsEnabled() ? OHGPU_FLAG_RAMP : 0;
+                g.pull.push_back(d);
+            }
+            else if (w.resampled) {
                 const WindowRun& r = g.runs[g.runOf[nthResampled++]];
                 ohgpu_src_msg_desc d;
                 memset(&d, 0, sizeof(d));
@@ -489,6 +550,11 @@ void PlayableBatch::Run()
         if (!g.src.empty()) {
             const int err = ohgpu_src_process_host(ctx, g.filter->handle, g.src.data(), g.src.size(), src + g.srcBase, g.srcBytes,
                                                    dst + g.dstBase, g.dstBytes);
+            ASSERT(err == OHGPU_OK);
+        }
+        if (!g.pull.empty()) {
+            const int err = ohgpu_src_pull_process_host(ctx, g.pullFilter->handle, g.pull.data(), g.pull.size(), src + g.srcBase, g.srcBytes,
+                                                        dst + g.dstBase, g.dstBytes);
             ASSERT(err == OHGPU_OK);
         }
     }
@@ -547,6 +613,9 @@ MsgFactory::~MsgFactory()
         for (auto& kv : iFilters) {
             ohgpu_src_destroy(iCtx, kv.second.handle);
         }
+        for (auto& kv : iPullFilters) {
+            ohgpu_src_pull_destroy(iCtx, kv.second.handle);
+        }
         if (iArenaSrc != nullptr) ohgpu_free_host(iCtx, iArenaSrc);
         if (iArenaDst != nullptr) ohgpu_free_host(iCtx, iArenaDst);
         ohgpu_shutdown(iCtx);
@@ -579,6 +648,29 @@ const SrcFilter& MsgFactory::SharedFilter(TUint aRateIn, TUint aRateOut, TUint a
         f.M = M;
         f.T = aTapsPerPhase;
         it = iFilters.emplace(key, f).first;                               // (std::map: the reference handed out stays valid)
+    }
+    return it->second;
+}
+
+const PullFilter& MsgFactory::SharedPullFilter(TUint aRateIn, TUint aRateOut, TUint aTapsPerPhase, TUint aPhasesLog2, double aBeta,
+                                               double aPassHz, double aMaxPull)
+{
+    std::lock_guard<std::mutex> hold(iFilterLock);
+    const auto key = std::make_tuple(aRateIn, aRateOut, aTapsPerPhase, aPhasesLog2, aBeta, aPassHz, aMaxPull);
+    auto it = iPullFilters.find(key);
+    if (it == iPullFilters.end()) {
+        // designed once per design, on the host; uploaded once where there is a device
+        PullFilter f;
+        f.T = aTapsPerPhase;
+        f.phasesLog2 = aPhasesLog2;
+        f.table.resize((((size_t)1 << aPhasesLog2) + 1) * aTapsPerPhase);
+        int err = ohgpu_src_pull_design(aRateIn, aRateOut, aTapsPerPhase, aPhasesLog2, aBeta, aPassHz, aMaxPull, f.table.data(), f.table.size());
+        ASSERT(err == OHGPU_OK);
+        if (iCtx != nullptr) {
+            err = ohgpu_src_pull_create(iCtx, aTapsPerPhase, aPhasesLog2, f.table.data(), &f.handle);
+            ASSERT(err == OHGPU_OK);
+        }
+        it = iPullFilters.emplace(key, std::move(f)).first;
     }
     return it->second;
 }

@@ -47,12 +47,22 @@ class MsgAudioEncoded; class MsgMetaText; class MsgStreamInterrupted; class MsgH
 class MsgDecodedStream; class MsgAudioPcm; class MsgAudioDsd; class MsgSilence; class MsgPlayable; class MsgQuit;
 class MsgFactory;
 class SampleRateConverterStream;
+class PullableSampleRateConverterStream;
 
 /** A designed polyphase filter on the device (include/ohgpu.h: ohgpu_src), kept by the factory and shared by every stream of the
  *  same conversion: streams that share a filter can share a launch. */
 struct SrcFilter {
     ohgpu_src* handle = nullptr;
     TUint L = 0, M = 0, T = 0;
+};
+
+/** A pulled resampler's filter (include/ohgpu.h: ohgpu_src_pull_*): one table serves every ratio near its conversion.
+ *  The factory keeps one per design and shares it like SrcFilter.  The host copy of the table is kept (P + 1 rows of T); the device
+ *  handle is null on a control-plane-only factory. */
+struct PullFilter {
+    ohgpu_src* handle = nullptr;
+    TUint T = 0, phasesLog2 = 0;
+    std::vector<int32_t> table;
 };
 
 class IMsgProcessor;
@@ -275,6 +285,7 @@ protected:
 class MsgAudioPcm : public MsgAudio {                    // Msg.cpp:2109-2305
     friend class MsgFactory;
     friend class SampleRateConverter;
+    friend class PullableSampleRateConverter;
 public:
     static const TUint kUnityAttenuation = 256;
     static const TUint64 kTrackOffsetInvalid = UINT64_MAX;
@@ -294,6 +305,10 @@ private:
     std::shared_ptr<DecodedAudio> iAudioData;            // null for resampled audio
     std::shared_ptr<SampleRateConverterStream> iResampled;   // set for audio produced by SampleRateConverter
     TUint64 iResampledFrame0 = 0;                        // absolute output frame of jiffy offset 0
+    std::shared_ptr<PullableSampleRateConverterStream> iPulled;   // set for audio produced by PullableSampleRateConverter
+    TUint64 iPullPosFrame = 0;                           // ... the input position of jiffy offset 0's output,
+    TUint iPullPosFrac = 0;                              //     frame and fraction (2^-32), and the step in force for it (Q32.32):
+    TUint64 iPullStep = 0;                               //     output k of the message is at pos + k * step, however it is split
     TUint64 iTrackOffset;
     TUint iAttenuation = kUnityAttenuation;
 };
@@ -318,6 +333,10 @@ struct PlayableWork {
     std::shared_ptr<DecodedAudio> audio;
     std::shared_ptr<SampleRateConverterStream> stream;
     TUint64 outFrame0 = 0;       // resampled: absolute first output frame
+    TBool pulled = false;        // pulled: the stream, the first output's input position and the step (ohgpu_src_pull_msg_desc)
+    std::shared_ptr<PullableSampleRateConverterStream> pullStream;
+    TUint64 pullPosFrame = 0, pullStep = 0;
+    TUint pullPosFrac = 0;
     TUint offsetBytes = 0, sizeBytes = 0, frames = 0;
     TUint sampleRate = 0, bitDepth = 0, channels = 0, attenuation = 256;
     Media::Ramp ramp;
@@ -346,8 +365,8 @@ private:
 
 /** Reads many playables -- typically one per stream per driver period -- then replays each one's BeginBlock /
  *  ProcessFragment* / EndBlock sequence in the order they were added (Msg.cpp:2646-2653, 2753-2786 per message, on the driver's
- *  thread: AnimatorBasic.cpp:77-142).  One device call for all the plain audio and ONE PER FILTER for the rate-converted audio, however
- *  many streams share it: what goes to the device is each message's window of input (SampleRateConverterStream::Window), packed
+ *  thread: AnimatorBasic.cpp:77-142).  One device call for all the plain audio and ONE PER FILTER for the rate-converted audio, fixed
+ *  ratio (ohgpu_src_process_host) or pulled (ohgpu_src_pull_process_host), however many streams share it: what goes to the device is each message's window of input (SampleRateConverterStream::Window), packed
  *  back to back in the factory's pinned arena, and what comes back is the messages' output and nothing else.  Output depth/endian
  *  default to the playable's own (pass-through); SetOutputFormat asks the device for the conversion the processor would do.
  *  The fragments handed to the processors point into the factory's arena: valid until the factory's next Run (the reference
@@ -397,6 +416,10 @@ public:
     /** The filter of a conversion, designed and uploaded on first use and kept for the factory's lifetime. */
     const SrcFilter& SharedFilter(TUint aRateIn, TUint aRateOut, TUint aTapsPerPhase, double aBeta, double aPassHz);
     TUint FilterCount() const;
+    /** The pulled resampler's filter of a design (ohgpu_src_pull_design), designed on first use and kept for the factory's lifetime;
+     *  uploaded when the factory has a device. */
+    const PullFilter& SharedPullFilter(TUint aRateIn, TUint aRateOut, TUint aTapsPerPhase, TUint aPhasesLog2, double aBeta,
+                                       double aPassHz, double aMaxPull);
     /** The driver thread's pinned staging for host-buffer reads (PlayableBatch::Run): at least the sizes asked for, kept and grown
      *  with headroom.  Like the ohgpu_ctx it belongs to one thread at a time. */
     void ReserveArena(size_t aSrcBytes, size_t aDstBytes, TByte*& aSrc, TByte*& aDst);
@@ -404,6 +427,7 @@ private:
     ohgpu_ctx* iCtx;
     mutable std::mutex iFilterLock;
     std::map<std::tuple<TUint, TUint, TUint, double, double>, SrcFilter> iFilters;
+    std::map<std::tuple<TUint, TUint, TUint, TUint, double, double, double>, PullFilter> iPullFilters;
     TByte* iArenaSrc = nullptr;
     TByte* iArenaDst = nullptr;
     size_t iArenaSrcBytes = 0, iArenaDstBytes = 0;

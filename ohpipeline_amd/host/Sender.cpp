@@ -54,7 +54,7 @@ void OhmFrameBatch::Run()
         TBool endianKnown = false;
         for (auto* p : w.playables) {
             const PlayableWork& pw = p->Work();
-            ASSERT(!pw.resampled);                       // a Sender downstream of the SampleRateConverter reads its output first (not wired up)
+            ASSERT(!pw.resampled && !pw.pulled);        // a Sender downstream of a sample-rate converter reads its output first (not wired up)
             if (!pw.silence && pw.frames > 0) {
                 const TUint e = (pw.audio->Endian() == AudioDataEndian::Little) ? OHGPU_ENDIAN_LITTLE : OHGPU_ENDIAN_BIG;
                 ASSERT(!endianKnown || e == endian);

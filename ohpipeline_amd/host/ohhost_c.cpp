@@ -8,6 +8,7 @@
 
 #include "../../include/ohgpu.h"
 #include "Msg.h"
+#include "PullableSampleRateConverter.h"
 #include "Ramp.h"
 #include "SampleRateConverter.h"
 
@@ -103,9 +104,9 @@ int ohhost_stream_ramp_schedule(const uint32_t* sizes, uint32_t n, uint32_t up_j
 
 }  // extern "C"
 
-// ---- a driver thread's period over many rate-converted streams, for scripted callers (bench.py's cadence.adapter): `lanes`
-// chains of SampleRateConverter -> CreatePlayable (PreDriver.cpp:115-133's one line) behind one factory = one GPU context, read
-// with ONE PlayableBatch::Run per tick, the way AnimatorBasic.cpp:77-142 reads one.
+// ---- a driver thread's period over many rate-converted streams, for scripted callers (bench.py's cadence.adapter,
+// tools/bench_pull.py): `lanes` chains of SampleRateConverter (or PullableSampleRateConverter) -> CreatePlayable (PreDriver.cpp:115-133's
+// one line) behind one factory = one GPU context, read with ONE PlayableBatch::Run per tick, the way AnimatorBasic.cpp:77-142 reads one.
 namespace {
 
 class CopyOut : public IPcmProcessor {
@@ -127,9 +128,12 @@ private:
 };
 
 struct LiveLane : public IPipelineElementUpstream {
-    LiveLane(MsgFactory& aFactory, TUint aRateOut, TUint aTaps) : iSrc(aFactory, *this, aRateOut, aTaps) {}
+    LiveLane(MsgFactory& aFactory, TUint aRateOut, TUint aTaps) : iSrc(new SampleRateConverter(aFactory, *this, aRateOut, aTaps)), iElement(iSrc.get()) {}
+    LiveLane(MsgFactory& aFactory, TUint aRateOut) : iPulled(new PullableSampleRateConverter(aFactory, *this, aRateOut)), iElement(iPulled.get()) {}
     Msg* Pull() override { ASSERT(!iPending.empty()); Msg* m = iPending.front(); iPending.pop_front(); return m; }
-    SampleRateConverter iSrc;
+    std::unique_ptr<SampleRateConverter> iSrc;               // one of the two
+    std::unique_ptr<PullableSampleRateConverter> iPulled;
+    IPipelineElementUpstream* iElement;
     std::deque<Msg*> iPending;
     CopyOut iSink;
 };
@@ -167,6 +171,39 @@ int ohhost_live_create(int device, uint32_t lanes, uint32_t rate_in, uint32_t ra
     });
 }
 
+// The same with PullableSampleRateConverter lanes (every stream converted, 48 -> 48 kHz included), each at nominal
+// until ohhost_live_pull_clock pulls it.
+int ohhost_live_pull_create(int device, uint32_t lanes, uint32_t rate_in, uint32_t rate_out, uint32_t channels, uint32_t bits,
+                            uint32_t little_endian, uint32_t out_bits, ohhost_live** out)
+{
+    OHHOST_TRY({
+        std::unique_ptr<ohhost_live> live(new ohhost_live());
+        live->factory.reset(new MsgFactory(device));
+        live->batch.reset(new PlayableBatch(*live->factory));
+        live->batch->SetOutputFormat(out_bits, AudioDataEndian::Big);
+        live->rateIn = rate_in; live->channels = channels; live->bits = bits;
+        live->endian = little_endian ? AudioDataEndian::Little : AudioDataEndian::Big;
+        for (uint32_t l = 0; l < lanes; l++) {
+            live->lanes.emplace_back(new LiveLane(*live->factory, rate_out));
+            DecodedStreamInfo info;
+            info.iStreamId = l + 1; info.iBitDepth = bits; info.iSampleRate = rate_in; info.iNumChannels = channels;
+            live->lanes.back()->iPending.push_back(live->factory->CreateMsgDecodedStream(info));
+        }
+        *out = live.release();
+        return 0;
+    });
+}
+
+// IPullableClock::PullClock on lane `lane` of a pulled driver (-1: not a pulled lane).
+int ohhost_live_pull_clock(ohhost_live* live, uint32_t lane, uint32_t multiplier)
+{
+    OHHOST_TRY({
+        ASSERT(lane < live->lanes.size() && live->lanes[lane]->iPulled != nullptr);
+        live->lanes[lane]->iPulled->PullClock(multiplier);
+        return 0;
+    });
+}
+
 // One driver period.  Lane l is fed `frames` input frames from input + l * in_lane_stride; whatever audio that makes available on
 // every lane is read with ONE PlayableBatch::Run and lands at output + l * out_lane_stride (out_bytes[l] bytes of it).
 int ohhost_live_tick(ohhost_live* live, const uint8_t* input, uint64_t in_lane_stride, uint32_t frames, uint8_t* output,
@@ -183,7 +220,7 @@ int ohhost_live_tick(ohhost_live* live, const uint8_t* input, uint64_t in_lane_s
             lane.iSink.iBytes = 0;
             lane.iSink.iCap = (uint32_t)out_lane_stride;
             while (!lane.iPending.empty()) {
-                Msg* msg = lane.iSrc.Pull();
+                Msg* msg = lane.iElement->Pull();
                 if (KindOf(msg) == MsgKind::AudioPcm) live->batch->Add(static_cast<MsgAudioPcm*>(msg)->CreatePlayable(), lane.iSink);
                 else msg->RemoveRef();
             }

@@ -37,6 +37,10 @@ def lib():
         L.ohhost_live_create.restype = C.c_int
         L.ohhost_live_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                          C.POINTER(C.c_void_p)]
+        L.ohhost_live_pull_create.restype = C.c_int
+        L.ohhost_live_pull_create.argtypes = L.ohhost_live_create.argtypes
+        L.ohhost_live_pull_clock.restype = C.c_int
+        L.ohhost_live_pull_clock.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
         L.ohhost_live_tick.restype = C.c_int
         L.ohhost_live_tick.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
         L.ohhost_live_stats.restype = C.c_int
@@ -49,11 +53,13 @@ def lib():
 
 class LiveDriver:
     """`lanes` chains of SampleRateConverter -> CreatePlayable behind one MsgFactory (one GPU context), read with ONE
-    PlayableBatch::Run per tick: the C++ adapter's live path, as a driver thread would use it (host/ohhost_c.cpp)."""
+    PlayableBatch::Run per tick: the C++ adapter's live path, as a driver thread would use it (host/ohhost_c.cpp).  pulled=True:
+    PullableSampleRateConverter lanes instead (pull_clock)."""
 
-    def __init__(self, device, lanes, rate_in, rate_out, channels, bits, little_endian=True, out_bits=24):
+    def __init__(self, device, lanes, rate_in, rate_out, channels, bits, little_endian=True, out_bits=24, pulled=False):
         self._h = C.c_void_p()
-        rc = lib().ohhost_live_create(device, lanes, rate_in, rate_out, channels, bits, 1 if little_endian else 0, out_bits, C.byref(self._h))
+        create = lib().ohhost_live_pull_create if pulled else lib().ohhost_live_create
+        rc = create(device, lanes, rate_in, rate_out, channels, bits, 1 if little_endian else 0, out_bits, C.byref(self._h))
         if rc != 0:
             raise RuntimeError(f"ohhost_live_create failed: {rc}")
         self.lanes = lanes
@@ -68,6 +74,12 @@ class LiveDriver:
         if rc != 0:
             raise RuntimeError(f"ohhost_live_tick failed: {rc}")
         return self._out_bytes
+
+    def pull_clock(self, lane, multiplier):
+        """IPullableClock::PullClock on a pulled lane (fix 1.31; clamped to the lane's MaxPull)."""
+        rc = lib().ohhost_live_pull_clock(self._h, lane, multiplier)
+        if rc != 0:
+            raise RuntimeError(f"ohhost_live_pull_clock failed: {rc}")
 
     def stats(self):
         v = [C.c_uint64(0) for _ in range(4)]
