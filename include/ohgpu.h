@@ -355,11 +355,14 @@ int ohgpu_src_batch_run_timed(ohgpu_ctx* ctx, const ohgpu_batch* batch, const vo
  *     OHGPU_ERR_INVALID for a batch that holds a stream's first message (its window is zeros where the next period's is history),
  *     OHGPU_ERR_UNSUPPORTED for one without a block-kernel plan;
  *   - other ramp endpoints (the flags stay: which messages are ramped is the plan's shape): ohgpu_src_batch_set_ramps, one pair per
- *     message in the batch's order (those of unramped messages are not looked at).  Rewrites the ramp jobs and the generic-kernel
- *     pieces on the device and refills the multiplier planes; waits for the batch's last launch first.  Not for a batch of several
- *     layouts.
+ *     message in the batch's order (those of unramped messages are not looked at).  Every ramped message's pair is checked first:
+ *     OHGPU_ERR_INVALID for an endpoint beyond OHGPU_RAMP_MAX, and a refused call changes nothing.  Then, after the batch's last
+ *     launch, it rewrites wherever the plan keeps the endpoints -- the ramp jobs (and refills the multiplier planes), the
+ *     generic-kernel pieces, round 1's per-message records (src_block_kernel), the generic kernel's per-message descriptors (a batch
+ *     created under kernel variant 1 or without a block-kernel plan).  Not for a batch of several layouts (OHGPU_ERR_UNSUPPORTED).
  * Anything else -- another tiling, other flags, other streams -- is another batch.  tests/test_plan_threads.py holds the plan of a
- * shifted period to the digest of the period it was made for; tests/test_gpu_parity.py runs both calls against the oracle. */
+ * shifted period to the digest of the period it was made for; tests/test_gpu_parity.py runs both calls against the oracle,
+ * tests/test_gpu_src_textbook.py on every plan kind against the textbook model. */
 int ohgpu_src_batch_block(const ohgpu_batch* batch, uint32_t* block_outputs, uint32_t* block_inputs);
 int ohgpu_src_batch_advance(ohgpu_ctx* ctx, ohgpu_batch* batch, uint64_t blocks);
 int ohgpu_src_batch_set_ramps(ohgpu_ctx* ctx, ohgpu_batch* batch, const uint16_t* ramp_start, const uint16_t* ramp_end, size_t n);

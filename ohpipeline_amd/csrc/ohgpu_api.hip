@@ -1500,14 +1500,28 @@ int ohgpu_src_batch_set_ramps(ohgpu_ctx* ctx, ohgpu_batch* b, const uint16_t* ra
     if (n != b->n) return set_error(OHGPU_ERR_INVALID, "ohgpu_src_batch_set_ramps: %zu endpoints for a batch of %zu messages", n, b->n);
     if (!b->parts.empty()) return set_error(OHGPU_ERR_UNSUPPORTED, "ohgpu_src_batch_set_ramps: a batch of several layouts (create one batch per layout to re-ramp it)");
     SrcFastPlan& f = b->fast;
-    // (only the messages that carry a ramp are looked at: the flags are the plan's)
-    for (uint32_t m : f.job_msg) if (ramp_start[m] > OHGPU_RAMP_MAX || ramp_end[m] > OHGPU_RAMP_MAX) return set_error(OHGPU_ERR_INVALID, "ohgpu_src_batch_set_ramps: message %u: ramp beyond Ramp::kMax", m);
-    for (uint32_t m : f.rem_msg) if (ramp_start[m] > OHGPU_RAMP_MAX || ramp_end[m] > OHGPU_RAMP_MAX) return set_error(OHGPU_ERR_INVALID, "ohgpu_src_batch_set_ramps: message %u: ramp beyond Ramp::kMax", m);
+    // Every form the batch keeps a ramped message in is checked before anything is written: a refused call leaves the endpoints in
+    // force as they were.  (Only the messages that carry a ramp are looked at: the flags are the plan's.)
+    auto beyond = [&](uint32_t m) { return ramp_start[m] > OHGPU_RAMP_MAX || ramp_end[m] > OHGPU_RAMP_MAX; };
+    auto refuse = [&](uint32_t m) { return set_error(OHGPU_ERR_INVALID, "ohgpu_src_batch_set_ramps: message %u: ramp beyond Ramp::kMax (nothing was changed)", m); };
+    for (uint32_t m : f.job_msg) if (beyond(m)) return refuse(m);
+    for (uint32_t m : f.rem_msg) if (beyond(m)) return refuse(m);
+    for (uint32_t m : f.msgs_ramped_msg) if (beyond(m)) return refuse(m);
+    if (b->host_descs)
+        for (size_t i = 0; i < n; i++) if ((b->host_descs[i].flags & OHGPU_FLAG_RAMP) && beyond((uint32_t)i)) return refuse((uint32_t)i);
     OHGPU_HIP_TRY(batch_wait_last_launch(b));                                    // (the batch's last launch reads what is rewritten here)
     hipStream_t s0 = ctx->stream;
     if (f.enabled) {
         for (size_t k = 0; k < f.host_jobs.size(); k++) { f.host_jobs[k].ramp_start = ramp_start[f.job_msg[k]]; f.host_jobs[k].ramp_end = ramp_end[f.job_msg[k]]; }
         for (size_t k = 0; k < f.host_rem.size(); k++) { f.host_rem[k].ramp_start = ramp_start[f.rem_msg[k]]; f.host_rem[k].ramp_end = ramp_end[f.rem_msg[k]]; }
+        if (!f.msgs_ramped.empty()) {       // round 1's plan: its kernel reads the endpoints of whole-block messages from their SegMsg records
+            for (size_t k = 0; k < f.msgs_ramped.size(); k++) {
+                SegMsg& sm = f.host_msgs[f.msgs_ramped[k]];
+                sm.ramp_start = ramp_start[f.msgs_ramped_msg[k]];
+                sm.ramp_end = ramp_end[f.msgs_ramped_msg[k]];
+            }
+            OHGPU_HIP_TRY(hipMemcpyAsync(f.d_msgs, f.host_msgs.data(), f.host_msgs.size() * sizeof(SegMsg), hipMemcpyHostToDevice, s0));
+        }
         if (!f.host_jobs.empty()) {
             OHGPU_HIP_TRY(hipMemcpyAsync(f.d_ramp_jobs, f.host_jobs.data(), f.host_jobs.size() * sizeof(RampJob), hipMemcpyHostToDevice, s0));
             OHGPU_HIP_TRY(hipMemsetAsync(f.d_planes, 0xff, (f.plane_entries ? f.plane_entries : 8) * sizeof(uint16_t), s0));

@@ -161,6 +161,10 @@ struct SrcFastPlan {
     std::vector<uint32_t> job_msg;
     std::vector<DevSrcDesc> host_rem;
     std::vector<uint32_t> rem_msg;
+    // ... and round 1's plan (d_work, not lean), whose kernel reads the endpoints from the SegMsg array itself: that array, and for
+    // each ramped message its place in it and the caller's index
+    std::vector<SegMsg> host_msgs;
+    std::vector<uint32_t> msgs_ramped, msgs_ramped_msg;
     size_t   plane_entries = 0;
     bool     stream_start = false;
     uint64_t advanced_blocks = 0;       // ohgpu_src_batch_advance: blocks added to every message's position since creation

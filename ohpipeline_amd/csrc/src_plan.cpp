@@ -671,6 +671,9 @@ int plan_src_fast(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_src_msg_desc* desc
         slab.add(segs, &f.d_segs);
         slab.add(msgs, &f.d_msgs);
         slab.add(work, &f.d_work);
+        for (size_t k = 0; k < n; k++)
+            if (msgs[k].flags & OHGPU_FLAG_RAMP) { f.msgs_ramped.push_back((uint32_t)k); f.msgs_ramped_msg.push_back(order[k]); }
+        f.host_msgs.swap(msgs);
     }
     slab.host.reserve((round1 ? segs.size() * sizeof(SrcSeg) + n * sizeof(SegMsg) + work.size() * sizeof(SrcWork) : 0) + lean_units.size() * sizeof(LeanUnit) +
                       rem.size() * sizeof(DevSrcDesc) + ramp_jobs.size() * sizeof(RampJob) + 8 * 256);     // (one allocation, nothing copied twice)

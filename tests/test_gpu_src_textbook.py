@@ -1,0 +1,460 @@
+"""Every resampler plan kind on the GPU against the textbook model (tests/src_textbook.py) -- not the oracle, whose polyphase
+indexing the kernels share.  A matrix of cells, each first asserting the kernel its batch runs on (ctx.src_kernel_name), then
+comparing the GPU's bytes with the model's for four input classes: impulses (the expected outputs read straight from the table),
+rounding ties, rails, seeded noise in ragged unsorted messages; and, where the cell's filter is in tests/golden/src_textbook.json,
+the fixture's two inputs against its hashes.  Then the same batch for three periods on every plan kind (run,
+ohgpu_src_batch_advance, ohgpu_src_batch_set_ramps, a refused set_ramps), the filters' audio in the frequency domain (no model),
+and the pulled path at phase-aligned steps against the same operation."""
+import hashlib
+import json
+import os
+import zlib
+
+import numpy as np
+import pytest
+
+import src_pull_model as PM
+import src_textbook as TB
+from ohpipeline_amd import capi
+
+pytestmark = pytest.mark.gpu
+
+LE, BE = capi.ENDIAN_LITTLE, capi.ENDIAN_BIG
+kMax = capi.RAMP_MAX
+RAMPS = [(kMax, 0), (0, kMax), (kMax, 8192), (8191, 8190), (5, 5), (kMax, kMax), (0, 0), (12345, 54), (17, 16001)]   # test_gpu_parity.RAMPS
+FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "src_textbook.json")
+FILL = 0xA5
+F44, F96, F48, F32 = (44100, 48000, 32), (96000, 48000, 64), (48000, 44100, 32), (32000, 48000, 16)
+WG, LEAN, BLOCK, V1 = "src_mfma_wg_kernel", "src_lean_kernel", "src_block_kernel", "src_kernel_v1"
+
+# layouts: (channels, source bits, source byte order, destination bits, destination byte order, planar source)
+S24 = (2, 24, LE, 24, BE, False)
+WG_LAYOUTS = [(F44, S24), (F44, (6, 24, LE, 24, BE, False)), (F44, (8, 24, LE, 24, BE, False)), (F96, S24),
+              (F96, (8, 24, LE, 24, BE, False)), (F44, (2, 16, LE, 24, BE, False)), (F44, (2, 16, BE, 24, BE, True)),
+              (F44, (2, 24, BE, 24, BE, True))]
+LEAN_ONLY_LAYOUTS = [(F44, (1, 16, LE, 24, BE, False)), (F44, (2, 32, LE, 24, BE, False)), (F44, (5, 24, LE, 24, BE, False)),
+                     (F44, (2, 24, LE, 16, BE, False)), (F44, (2, 24, LE, 32, BE, False))]
+BLOCK_LAYOUTS = [(F48, (2, 24, LE, 24, BE, False)), (F48, (2, 24, LE, 24, LE, False)), (F48, (2, 24, BE, 24, BE, False)),
+                 (F48, (2, 16, LE, 24, BE, False)), (F48, (2, 16, BE, 24, BE, False))]     # OHGPU_BLOCK_FALLBACK_KERNELS
+# (kernel, the variant the batch is created and run under, filter, layout)
+CELLS = ([(WG, 0, f, lay) for f, lay in WG_LAYOUTS] + [(LEAN, 4, f, lay) for f, lay in WG_LAYOUTS + LEAN_ONLY_LAYOUTS] +
+         [(BLOCK, 0, f, lay) for f, lay in BLOCK_LAYOUTS] +
+         [(V1, 1, F44, S24), (V1, 0, F44, (2, 24, LE, 8, BE, False)), (V1, 0, F32, (8, 24, LE, 24, BE, False))])
+
+
+def layout_id(lay):
+    ch, sb, se, db, de, planar = lay
+    return f"{ch}ch-{'planar' if planar else ('le' if se == LE else 'be')}{sb}-{'le' if de == LE else 'be'}{db}"
+
+
+def cell_id(c):
+    kernel, variant, (rin, rout, T), lay = c
+    return f"{kernel[4:].replace('_kernel', '')}-v{variant}-{rin // 100}to{rout // 100}x{T}-{layout_id(lay)}"
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = capi.Context(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def ramp_table():
+    return capi.ramp_table()
+
+
+class Filter:
+    def __init__(self, ctx, rin, rout, T):
+        self.rin, self.rout, self.T = rin, rout, T
+        self.L, self.M, self.coef = capi.src_design(rin, rout, T, 9.0, 20000.0)
+        self.handle = ctx.src_create(self.L, self.M, T, self.coef)
+
+
+@pytest.fixture(scope="module")
+def filters(ctx):
+    made = {}
+
+    def get(f):
+        if f not in made:
+            made[f] = Filter(ctx, *f)
+        return made[f]
+    yield get
+    for f in made.values():
+        ctx.src_destroy(f.handle)
+
+
+class Batch:
+    """Streams of one or more layouts in one source arena (a planar stream: its planes, 5 frames apart), their messages' outputs
+    in one destination arena, each stream's contiguous, a few bytes between streams."""
+
+    def __init__(self):
+        self.src = bytearray()
+        self.rows = []
+        self.dst = 0
+        self.streams = []
+
+    def add_stream(self, y, lay, rng, first=0):
+        """y: source-unit samples of input frames first .. first + len(y) - 1 (the stream's buffer).  Returns the stream's index."""
+        ch, sb, se, db, de, planar = lay
+        stride = (y.shape[0] + 5) * 4 if planar else None
+        off = len(self.src)
+        self.src += bytes(TB.encode(y, sb, se, rng, stride))
+        self.src += bytes((-len(self.src)) % 16)
+        self.dst += 3
+        self.streams.append(dict(off=off, first=first, frames=y.shape[0], stride=stride or 0, lay=lay, dst0=self.dst, out0=None))
+        return len(self.streams) - 1
+
+    def add_msg(self, s, out0, n, flags=0, ramp=(kMax, kMax)):
+        """Message [out0, out0 + n) of stream s; a stream's messages must come in output order (their bytes are back to back)."""
+        st = self.streams[s]
+        ch, sb, se, db, de, planar = st["lay"]
+        if st["out0"] is None:
+            st["out0"] = out0
+        dst = st["dst0"] + (out0 - st["out0"]) * ch * db // 8
+        self.rows.append((st["off"], st["first"], st["frames"], out0, dst, n, ramp[0], ramp[1], 256, ch, sb, se, db, de,
+                          flags | (capi.FLAG_SRC_PLANAR32 if planar else 0), st["stride"]))
+        self.dst = max(self.dst, dst + n * ch * db // 8)
+
+    def descs(self):
+        return np.array(self.rows, dtype=capi.SRC_MSG_DESC)
+
+    def arena(self):
+        return np.frombuffer(bytes(self.src), dtype=np.uint8).copy()
+
+
+def model(flt, descs, src, dst_bytes, ramp_table):
+    return TB.batch_bytes(flt.coef, flt.L, flt.M, flt.T, descs, src, dst_bytes, ramp_table, FILL)
+
+
+def assert_same(got, want, what):
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, f"{what}: {bad.size} of {want.size} bytes differ, first at {bad[:8]}"
+
+
+def run(ctx, flt, variant, kernel, descs, src, dst_bytes):
+    """Create the batch under `variant`, assert the kernel it runs on, run it once: (bytes, plan)."""
+    ctx.set_kernel_variant(variant)
+    try:
+        b = ctx.src_batch(flt.handle, descs, src.size, dst_bytes)
+        try:
+            assert ctx.src_kernel_name(b) == kernel
+            plan = ctx.src_plan(b)
+            d_src, d_dst = ctx.upload(src), ctx.malloc(dst_bytes)
+            try:
+                ctx.memset(d_dst, FILL, dst_bytes)
+                ctx.src_run(b, d_src, d_dst)
+                got = ctx.download(d_dst, dst_bytes)
+            finally:
+                ctx.free(d_src)
+                ctx.free(d_dst)
+        finally:
+            ctx.batch_destroy(b)
+    finally:
+        ctx.set_kernel_variant(0)
+    return got, plan
+
+
+def block_of(ctx, flt, lay, variant):
+    """(outputs, inputs) of the cell's blocks (ohgpu_src_batch_block on a probe batch); a plan without blocks: the filter's period
+    times what makes some 160 outputs."""
+    probe = Batch()
+    s = probe.add_stream(np.zeros((30000, lay[0]), dtype=np.int64), lay, None)
+    end = min(TB.out_frames(flt.L, flt.M, 30000), 24000)
+    for m in range(0, end, 4000):
+        probe.add_msg(s, m, min(4000, end - m))
+    ctx.set_kernel_variant(variant)
+    try:
+        b = ctx.src_batch(flt.handle, probe.descs(), len(probe.src), probe.dst)
+        try:
+            return ctx.src_batch_block(b)
+        except capi.OhGpuError as e:
+            assert e.code == capi.ERR_UNSUPPORTED
+            k = -(-160 // flt.L)
+            return k * flt.L, k * flt.M
+        finally:
+            ctx.batch_destroy(b)
+    finally:
+        ctx.set_kernel_variant(0)
+
+
+def full_scale(bits):
+    return -(1 << (min(bits, 24) - 1)), (1 << (min(bits, 24) - 1)) - 1
+
+
+def one_stream(flt, lay, y, rng, msg=240, ramp_every=4):
+    """One stream from its start, every output the input allows, in messages of `msg` frames (the last ragged); every
+    ramp_every-th message ramped with the next of RAMPS, every fifth ZERO_LSB32."""
+    b = Batch()
+    s = b.add_stream(y, lay, rng)
+    n_out = TB.out_frames(flt.L, flt.M, y.shape[0])
+    for i, m in enumerate(range(0, n_out, msg)):
+        ramped = ramp_every and i % ramp_every == ramp_every - 1
+        b.add_msg(s, m, min(msg, n_out - m), (capi.FLAG_RAMP if ramped else 0) | (capi.FLAG_ZERO_LSB32 if i % 5 == 4 else 0),
+                  RAMPS[i % len(RAMPS)] if ramped else (kMax, kMax))
+    return b, n_out
+
+
+@pytest.mark.parametrize("cell", CELLS, ids=[cell_id(c) for c in CELLS])
+def test_every_plan_kind_equals_the_model(ctx, filters, ramp_table, cell):
+    kernel, variant, f, lay = cell
+    flt = filters(f)
+    ch, sb, se, db, de, planar = lay
+    L_blk, M_blk = block_of(ctx, flt, lay, variant)
+    rng = np.random.default_rng(zlib.crc32(cell_id(cell).encode()))
+    lo, hi = full_scale(sb)
+    msg = 220 if flt.rout == 44100 else 240
+    n_in = max(4 * M_blk, 3000)
+    block_plan = kernel != V1
+
+    # (a) impulses: input frame 0, the first and the last input frame of block 1, the newest frame of a message's first output;
+    # channel c 2c frames further in (the last frame of the block: 2c frames back), signs alternating
+    first_msg = next(m for m in range(0, 1 << 30, msg) if (m * flt.M) // flt.L >= 2 * M_blk + 3 * flt.T)
+    sites = [(0, 1), (M_blk, 1), (2 * M_blk - 1, -1), ((first_msg * flt.M) // flt.L, 1)]
+    y = np.zeros((n_in, ch), dtype=np.int64)
+    for i, (n, way) in enumerate(sites):
+        for c in range(ch):
+            y[n + way * 2 * c, c] = hi if (i + c) % 2 == 0 else lo
+    b, n_out = one_stream(flt, lay, y, rng, msg)
+    descs, src = b.descs(), b.arena()
+    s24 = np.zeros((n_out, ch), dtype=np.int64)
+    m = np.arange(n_out)
+    for i, (n, way) in enumerate(sites):
+        for c in range(ch):
+            s24[:, c] += TB.impulse_response(flt.coef, flt.L, flt.M, flt.T, int(y[n + way * 2 * c, c]) << TB.source_shift(sb), n + way * 2 * c, m)
+    want = np.full(b.dst, FILL, dtype=np.uint8)
+    for d in descs:
+        o = int(d["out_frame0"])
+        piece = TB.pack(s24[o:o + int(d["n_frames"])], d, ramp_table)
+        want[int(d["dst_offset"]):int(d["dst_offset"]) + piece.size] = piece
+    assert np.array_equal(model(flt, descs, src, b.dst, ramp_table), want)
+    got, plan = run(ctx, flt, variant, kernel, descs, src, b.dst)
+    assert_same(got, want, "impulses")
+    assert not block_plan or plan["block_kernel_out_frames"] > 0
+
+    # (b) rounding ties (windows apart), both signs, one source step either side, some past the clamp
+    y = rng.integers(lo, hi + 1, size=(n_in, ch))
+    ties = TB.plant_ties(rng, flt.coef, flt.L, flt.M, flt.T, y, sb)
+    sums = np.array([acc for acc, offset in ties.values() if offset == 0], dtype=object)
+    assert len(ties) > 20 and (sums < 0).any() and (sums > 0).any()
+    b, _ = one_stream(flt, lay, y, rng, msg)
+    descs, src = b.descs(), b.arena()
+    got, _ = run(ctx, flt, variant, kernel, descs, src, b.dst)
+    assert_same(got, model(flt, descs, src, b.dst, ramp_table), "ties")
+
+    # (c) rails: full-scale DC at each rail, then a full-scale square wave in the pass band; the outputs clamp on both sides
+    y = np.empty((n_in, ch), dtype=np.int64)
+    third = n_in // 3
+    y[:third], y[third:2 * third] = np.where(np.arange(ch) % 2 == 0, hi, lo), np.where(np.arange(ch) % 2 == 0, lo, hi)
+    y[2 * third:] = np.where((np.arange(n_in - 2 * third) // 24) % 2 == 0, hi, lo)[:, None]
+    b, n_out = one_stream(flt, lay, y, rng, msg)
+    descs, src = b.descs(), b.arena()
+    s24 = TB.resample(flt.coef, flt.L, flt.M, flt.T, y << TB.source_shift(sb), 0, 0, n_out)
+    assert (s24 == TB.S24_MAX).sum() > 10 and (s24 == TB.S24_MIN).sum() > 10
+    got, _ = run(ctx, flt, variant, kernel, descs, src, b.dst)
+    assert_same(got, model(flt, descs, src, b.dst, ramp_table), "rails")
+
+    # (d) noise in ragged messages whose ends miss the block edges, RAMPS and ZERO_LSB32, one stream from its start and one asked
+    # for from the middle (its buffer starts there), the descriptors shuffled
+    b = Batch()
+    first = 3 * M_blk + 11
+    for f0, m, end in ((0, 0, TB.out_frames(flt.L, flt.M, n_in)),
+                       (first, -(-(first + flt.T) * flt.L // flt.M) + 1, TB.out_frames(flt.L, flt.M, first + n_in))):
+        s = b.add_stream(rng.integers(lo, hi + 1, size=(n_in, ch)), lay, rng, first=f0)
+        i = 0
+        while m < end:
+            n = min((1, 5, 43, 220, 239, 241, 700)[i % 7], end - m)
+            ramp = RAMPS[i % len(RAMPS)]
+            b.add_msg(s, m, n, (capi.FLAG_RAMP if i % 3 else 0) | (capi.FLAG_ZERO_LSB32 if i % 4 == 1 else 0), ramp)
+            m += n
+            i += 1
+    descs, src = b.descs(), b.arena()
+    descs = descs[rng.permutation(descs.size)]
+    got, plan = run(ctx, flt, variant, kernel, descs, src, b.dst)
+    assert_same(got, model(flt, descs, src, b.dst, ramp_table), "ragged noise")
+    assert not block_plan or (plan["block_kernel_out_frames"] > 0 and plan["generic_pieces"] > 0), plan
+
+    # the golden fixture's inputs, where the cell's filter is there and its layout carries S24 in and out
+    fx = {(e["rate_in"], e["rate_out"], e["T"]): e for e in json.load(open(FIXTURE))["filters"]}
+    if f in fx and ch == 2 and sb in (24, 32) and db == 24:
+        for inp in fx[f]["inputs"]:
+            x = TB.fixture_input(inp["kind"], flt.coef, flt.L, flt.M, flt.T)
+            b, n_out = one_stream(flt, lay, x, rng, msg, ramp_every=0)
+            got, _ = run(ctx, flt, variant, kernel, b.descs(), b.arena(), b.dst)
+            y = PM.decode_s24(got[3:3 + n_out * 6], 2, 24, de)
+            assert y[:64].tolist() == inp["first_64"], inp["kind"]
+            assert hashlib.sha256(np.ascontiguousarray(y, dtype="<i4").tobytes()).hexdigest() == inp["s24_sha256"], inp["kind"]
+
+
+# ------------------------------------------------------------------------------------------ the same batch, three periods
+REUSE = {"wg": (WG, 0, F44, [S24]), "lean": (LEAN, 4, F44, [S24]), "round1": (BLOCK, 0, F48, [S24]),
+         "two-layouts": (WG, 0, F44, [S24, (6, 24, LE, 24, BE, False)]), "generic": (V1, 0, F44, [(2, 24, LE, 8, BE, False)])}
+
+
+@pytest.mark.parametrize("kind", list(REUSE))
+def test_the_same_batch_for_three_periods(ctx, filters, ramp_table, kind):
+    """A period of messages that starts 37 outputs into a block and ends 13 short of one (generic pieces beside the block units),
+    two ramped messages in seven: (1) run; (2) ohgpu_src_batch_advance by 5 blocks, new audio in the same arena; (3)
+    ohgpu_src_batch_set_ramps with new endpoints.  Every period against the model on that period's descriptors; then a refused
+    set_ramps (one endpoint beyond Ramp::kMax on a message inside whole blocks) and a run that must keep the old endpoints.  A
+    batch of two layouts refuses set_ramps; a batch without a block plan refuses advance and re-ramps in place."""
+    kernel, variant, f, layouts = REUSE[kind]
+    flt = filters(f)
+    L_blk, M_blk = block_of(ctx, flt, layouts[0], variant)
+    msg = 220 if flt.rout == 44100 else 240
+    period_blocks = max(3, -(-2000 // L_blk))
+    head, tail = 37, 13
+    out_frames = period_blocks * L_blk - head - tail
+    hist = M_blk + flt.T
+    win = period_blocks * M_blk + hist
+    rng = np.random.default_rng(7 + len(kind))
+    stream_layouts = layouts + layouts[:1]
+    whole = [rng.integers(full_scale(lay[1])[0], full_scale(lay[1])[1] + 1, size=((20 + 3 * period_blocks) * M_blk, lay[0]))
+             for lay in stream_layouts]
+
+    def make(first_block, pair):
+        b = Batch()
+        for y, lay in zip(whole, stream_layouts):
+            f0 = first_block * M_blk - hist
+            s = b.add_stream(y[f0:f0 + win], lay, None, first=f0)
+            m, i = first_block * L_blk + head, 0
+            while m < first_block * L_blk + head + out_frames:
+                n = min(msg, first_block * L_blk + head + out_frames - m)
+                ramped = i % 7 < 2
+                b.add_msg(s, m, n, capi.FLAG_RAMP if ramped else 0, pair if ramped else (kMax, kMax))
+                m += n
+                i += 1
+        return b.descs(), b.arena(), b.dst
+
+    at = 3
+    d1, a1, dst_bytes = make(at, (kMax, 2000))
+    b = d_src = d_dst = None
+    try:
+        ctx.set_kernel_variant(variant)
+        b = ctx.src_batch(flt.handle, d1, a1.size, dst_bytes)
+        assert ctx.src_kernel_name(b) == kernel
+        d_src, d_dst = ctx.upload(a1), ctx.malloc(dst_bytes)
+
+        def period(descs, arena, what):
+            ctx.memset(d_dst, FILL, dst_bytes)
+            ctx.src_run(b, d_src, d_dst)
+            assert_same(ctx.download(d_dst, dst_bytes), model(flt, descs, arena, dst_bytes, ramp_table), what)
+
+        period(d1, a1, "period 1")
+        last, arena = d1, a1
+        if kind == "generic":
+            with pytest.raises(capi.OhGpuError) as e:
+                ctx.src_batch_advance(b, 5)
+            assert e.value.code == capi.ERR_UNSUPPORTED
+        else:
+            assert ctx.src_plan(b)["block_kernel_out_frames"] > 0 and ctx.src_plan(b)["generic_pieces"] > 0
+            ctx.src_batch_advance(b, 5)
+            at += 5
+            last, arena, _ = make(at, (kMax, 2000))
+            ctx.copy_h2d(d_src, arena)
+            period(last, arena, "period 2: advanced")
+        new, _, _ = make(at, (100, 16000))
+        if kind == "two-layouts":
+            with pytest.raises(capi.OhGpuError) as e:
+                ctx.src_batch_set_ramps(b, new["ramp_start"], new["ramp_end"])
+            assert e.value.code == capi.ERR_UNSUPPORTED
+            return
+        ctx.src_batch_set_ramps(b, new["ramp_start"], new["ramp_end"])
+        period(new, arena, "period 3: new ramps")
+        # refused: every ramped message gets other endpoints, one of them beyond Ramp::kMax -- nothing may change
+        ramped = np.nonzero(new["flags"] & capi.FLAG_RAMP)[0]
+        lo, hi = new["out_frame0"].astype(np.int64), new["out_frame0"].astype(np.int64) + new["n_frames"]
+        mid = [k for k in ramped if kind == "generic" or ((at + 1) * L_blk <= lo[k] and hi[k] <= (at + period_blocks - 1) * L_blk)]
+        assert mid, "no ramped message inside whole blocks"
+        starts = np.where(new["flags"] & capi.FLAG_RAMP, 5000, new["ramp_start"]).astype(np.uint16)
+        starts[mid[len(mid) // 2]] = kMax + 1
+        with pytest.raises(capi.OhGpuError) as e:
+            ctx.src_batch_set_ramps(b, starts, new["ramp_end"])
+        assert e.value.code == capi.ERR_INVALID
+        period(new, arena, "after a refused set_ramps")
+    finally:
+        ctx.set_kernel_variant(0)
+        if b is not None:
+            ctx.batch_destroy(b)
+        if d_src is not None:
+            ctx.free(d_src)
+            ctx.free(d_dst)
+
+
+# ------------------------------------------------------------------------------------------ audio
+@pytest.mark.parametrize("kernel,variant,f,tone,others", [
+    (WG, 0, F44, 15000, True), (WG, 0, F44, 19500, False), (LEAN, 4, F44, 15000, True), (LEAN, 4, F44, 19500, False),
+    (WG, 0, F96, 19000, True), (LEAN, 4, F96, 19000, True), (WG, 0, F96, 30000, True), (LEAN, 4, F96, 30000, True),
+    (BLOCK, 0, F48, 15000, True)])
+def test_tones_through_the_filters(ctx, filters, ramp_table, kernel, variant, f, tone, others):
+    """2 s of a -6 dBFS tone in both channels (the second a quarter period later), S24; output frames [rate_out, 2 rate_out) through a
+    rectangular window, one bin per Hz: a tone in the pass band keeps its level within 0.01 dB; nothing else (images, aliases, a
+    stop-band tone) reaches -85 dB below the input tone.  (19.5 kHz at 44.1 -> 48 kHz: its image lies in the transition band by
+    design, the other bins are not looked at.)"""
+    flt = filters(f)
+    rin, rout = flt.rin, flt.rout
+    A = 10 ** (-6 / 20) * TB.S24_MAX
+    n = np.arange(2 * rin)
+    y = np.stack([np.round(A * np.sin(2 * np.pi * tone * n / rin + ph)) for ph in (0.0, np.pi / 2)], axis=1).astype(np.int64)
+    b, n_out = one_stream(flt, S24, y, None, 220 if rout == 44100 else 240, ramp_every=0)
+    assert n_out == 2 * rout
+    got, _ = run(ctx, flt, variant, kernel, b.descs(), b.arena(), b.dst)
+    out = PM.decode_s24(got[3:3 + n_out * 6], 2, 24, BE)[rout:2 * rout].astype(np.float64)
+    for c in range(2):
+        amp = 2 * np.abs(np.fft.rfft(out[:, c])) / rout
+        if tone < min(rin, rout) / 2:
+            gain = 20 * np.log10(amp[tone] / A)
+            assert abs(gain) <= 0.01, (c, gain)
+            amp[tone] = 0
+        if others:
+            worst = int(np.argmax(amp))
+            assert 20 * np.log10(amp[worst] / A) <= -85, (c, worst, 20 * np.log10(amp[worst] / A))
+
+
+# ------------------------------------------------------------------------------------------ the pulled path
+@pytest.mark.parametrize("s", [8, 6])
+@pytest.mark.parametrize("T", [32, 64])
+@pytest.mark.parametrize("ch", [2, 6])
+def test_pulled_phase_aligned_steps_equal_the_textbook_operation(ctx, ramp_table, s, T, ch):
+    """Steps a * 2^(32 - s) with a = P, about 0.92 P and 2 P, positions on the phase grid past T frames in: the pulled kernel's bytes
+    equal upfirdn's operation (up = 2^s, down = a, on the table's prototype) through the same pack -- tables of 2^8 and 2^6 phases,
+    the stereo and the any-channel instantiation, ramps and ZERO_LSB32 on some messages."""
+    table = capi.src_pull_design(44100, 48000, T, s, 8.0 if T == 32 else 9.0, 20000.0, 0.001)
+    flt = ctx.src_pull_create(T, s, table)
+    P, unit = 1 << s, 1 << (32 - s)
+    rng = np.random.default_rng(s * 100 + T + ch)
+    n_in = 4000
+    x = rng.integers(TB.S24_MIN, TB.S24_MAX + 1, size=(n_in, ch))
+    x[1000:1400] = TB.S24_MAX
+    x[1400:1800] = TB.S24_MIN
+    src = TB.encode(x, 24, LE)
+    descs, want, dp = [], [], 0
+    for i, a in enumerate((P, (P * 92) // 100, 2 * P)):
+        pos, frac = T + 5 + 7 * i, int(rng.integers(0, P)) * unit
+        for k, n in enumerate((240, 1, 77, 240, 300)):
+            d = np.zeros(1, dtype=capi.SRC_PULL_MSG_DESC)[0]
+            d["src_frames"], d["pos_frame"], d["pos_frac"], d["step"], d["n_frames"] = n_in, pos, frac, a * unit, n
+            d["dst_offset"], d["attenuation"] = dp, 256
+            d["channels"], d["src_bits"], d["src_endian"], d["dst_bits"], d["dst_endian"] = ch, 24, LE, 24, BE
+            d["flags"] = (capi.FLAG_RAMP if k % 2 else 0) | (capi.FLAG_ZERO_LSB32 if k == 3 else 0)
+            d["ramp_start"], d["ramp_end"] = RAMPS[(i + k) % len(RAMPS)]
+            y = TB.resample_pulled(table, s, x, 0, pos, frac, a * unit, n)
+            piece = PM.pack(y, 24, BE, int(d["flags"]), RAMPS[(i + k) % len(RAMPS)], ramp_table)
+            assert np.array_equal(piece, PM.message_bytes(table, s, d, src, ramp_table))
+            descs.append(d)
+            want.append(piece)
+            dp += piece.size
+            pos, frac = PM.advance(pos, frac, a * unit, n)
+    assert pos < n_in
+    descs = np.array(descs, dtype=capi.SRC_PULL_MSG_DESC)
+    d_src, d_dst = ctx.upload(src), ctx.malloc(dp)
+    b = ctx.src_pull_batch(flt, descs, src.size, dp)
+    try:
+        ctx.memset(d_dst, FILL, dp)
+        ctx.src_pull_run(b, d_src, d_dst)
+        assert_same(ctx.download(d_dst, dp), np.concatenate(want), f"pulled s={s} T={T} ch={ch}")
+    finally:
+        ctx.batch_destroy(b)
+        ctx.free(d_src)
+        ctx.free(d_dst)
+        ctx.src_pull_destroy(flt)
