@@ -161,6 +161,24 @@ int ohgpu_batch_destroy(ohgpu_ctx* ctx, ohgpu_batch* batch);
 /* Totals recorded at creation (for throughput accounting). */
 int ohgpu_batch_info(const ohgpu_batch* batch, uint64_t* n_msgs, uint64_t* in_frames, uint64_t* out_frames,
                      uint64_t* src_bytes_touched, uint64_t* dst_bytes_written);
+/* Which kernels a PCM batch (ohgpu_pcm_batch_create) or a Songcast frame batch (ohgpu_ohm_batch_create) was planned onto at its
+ * creation -- read-only, for tests and tools that must know that the path they mean to exercise is the one that ran.  A chunk is
+ * one wave's unit of work of the line kernel (csrc/pcm_line_kernel.hip); under ohgpu_set_kernel_variant(1) a batch runs the
+ * generic kernel message by message whatever its plan says.  OHGPU_ERR_INVALID for any other kind of batch. */
+typedef struct ohgpu_batch_paths {       /* 64 bytes */
+    uint32_t line_planned;          /* 1: the line kernel has a plan for the batch (0: only the generic kernel can run it) */
+    uint32_t launches;              /* line-kernel launches per run: one per layout present (8-bit / silence, and each 16/24/32-bit depth pair) */
+    uint32_t staged_chunks;         /* staged path: 8-bit audio on either side and silence, <= 512 subsamples each */
+    uint32_t group_chunks;          /* register path, plain: runs of a stream's consecutive plain messages, merged and re-cut */
+    uint32_t heavy_chunks;          /* register path, ramped or attenuated: one per message */
+    uint32_t prefixed_chunks;       /* chunks that write a Songcast header in front of their audio */
+    uint32_t ohm_wide_fragments;    /* Songcast: audible fragments of streams of more than two channels (the channel-selecting kernel) */
+    uint32_t ohm_staged_fragments;  /* Songcast: silent fragments of such streams (through scratch) */
+    uint32_t ohm_headers_fused;     /* Songcast: frame headers written by the audio pass itself */
+    uint32_t ohm_headers_separate;  /* Songcast: frame headers the header kernel writes (every header under kernel variant 1) */
+    uint32_t reserved[6];
+} ohgpu_batch_paths;
+int ohgpu_batch_paths_info(const ohgpu_batch* batch, ohgpu_batch_paths* out);
 
 /* Convenience for hosts that hold host buffers (a live pipeline's 5 ms cadence: the driver thread's MsgPlayable::Read of a
  * period, Msg.cpp:2646-2653, for as many playables as the caller brings): H2D, run, D2H, sync.  Of dst_host only the bytes the
@@ -284,7 +302,8 @@ typedef struct ohgpu_ohm_frame_desc {   /* 48 bytes: one OhmSenderDriver::SendAu
 /* Sizes of a frame of `samples` sample instants: the header (8 + 50 + codec_bytes) and the whole datagram. */
 int ohgpu_ohm_frame_layout(const ohgpu_ohm_stream* stream, uint32_t samples, uint32_t* header_bytes, uint32_t* frame_bytes);
 /* OHGPU_ERR_INVALID where the reference asserts: more audio than OhmMsgAudio::kMaxSampleBytes in a frame (Sender.cpp:364),
- * a codec name over 29 bytes; OHGPU_ERR_UNSUPPORTED for ramped/silent/attenuated fragments of more than 8 channels. */
+ * a codec name over 29 bytes; OHGPU_ERR_UNSUPPORTED for ramped/silent/attenuated fragments, and for any fragment of a
+ * little-endian source, of more than 8 channels (those take the message path, which carries at most 8). */
 int ohgpu_ohm_batch_create(ohgpu_ctx* ctx, const ohgpu_ohm_stream* streams, size_t n_streams,
                            const ohgpu_ohm_frame_desc* frames, size_t n_frames,
                            const ohgpu_ohm_fragment* fragments, size_t n_fragments,

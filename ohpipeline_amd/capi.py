@@ -48,6 +48,11 @@ FMT_DESC = np.dtype([
     ("n_frames", "<u4"), ("kind", "u1"), ("channels", "u1"), ("src_bits", "u1"), ("dst_bits", "u1"),
     ("reserved", "u1", (8,))], align=False)
 
+BATCH_PATHS = np.dtype([(k, "<u4") for k in ("line_planned", "launches", "staged_chunks", "group_chunks", "heavy_chunks",
+                                            "prefixed_chunks", "ohm_wide_fragments", "ohm_staged_fragments", "ohm_headers_fused",
+                                            "ohm_headers_separate")] + [("reserved", "<u4", (6,))], align=False)
+assert BATCH_PATHS.itemsize == 64
+
 FLYWHEEL_DESC = np.dtype([
     ("src_offset", "<u8"), ("channel_bytes", "<u8"), ("dst_offset", "<u8"), ("in_samples", "<u4"),
     ("out_frames", "<u4"), ("block_frames", "<u4"), ("sample_rate", "<u4"), ("channels", "<u4"),
@@ -98,6 +103,7 @@ SYMBOLS = {
     "ohgpu_pcm_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "ohgpu_batch_destroy": (C.c_int, [_vp, _vp]),
     "ohgpu_batch_info": (C.c_int, [_vp, _u64p, _u64p, _u64p, _u64p, _u64p]),
+    "ohgpu_batch_paths_info": (C.c_int, [_vp, _vp]),
     "ohgpu_pcm_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64]),
     "ohgpu_fmt_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
     "ohgpu_fmt_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
@@ -391,6 +397,12 @@ class Context:
         check(lib().ohgpu_batch_info(batch, *[C.byref(x) for x in v]))
         keys = ("n_msgs", "in_frames", "out_frames", "src_bytes_touched", "dst_bytes_written")
         return dict(zip(keys, (int(x.value) for x in v)))
+
+    def batch_paths(self, batch):
+        """Which kernels a pcm or Songcast frame batch was planned onto (ohgpu_batch_paths), as a dict of counts."""
+        v = np.zeros(1, dtype=BATCH_PATHS)
+        check(lib().ohgpu_batch_paths_info(batch, v.ctypes.data_as(C.c_void_p)))
+        return {k: int(v[k][0]) for k in BATCH_PATHS.names if k != "reserved"}
 
     def pcm_process_host(self, descs, src, dst):
         d = np.ascontiguousarray(descs)

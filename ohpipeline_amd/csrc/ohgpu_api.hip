@@ -650,6 +650,33 @@ int ohgpu_batch_info(const ohgpu_batch* b, uint64_t* n_msgs, uint64_t* in_frames
     return OHGPU_OK;
 }
 
+static void add_line_paths(const PcmLinePlan& line, ohgpu_batch_paths* out)
+{
+    if (!line.enabled) return;
+    out->line_planned = 1;
+    for (uint32_t k = 0; k < kLineLists; k++) out->launches += line.list_count[k] != 0;
+    out->staged_chunks += line.n_staged; out->group_chunks += line.n_group; out->heavy_chunks += line.n_heavy;
+    out->prefixed_chunks += line.prefixed ? line.n_prefixed : 0;
+}
+
+int ohgpu_batch_paths_info(const ohgpu_batch* b, ohgpu_batch_paths* out)
+{
+    if (!b || !out) return set_error(OHGPU_ERR_INVALID, "ohgpu_batch_paths_info: null argument");
+    memset(out, 0, sizeof(*out));
+    if (b->kind == kBatchPcm) {
+        add_line_paths(b->line, out);
+        return OHGPU_OK;
+    }
+    if (b->kind != kBatchOhm) return set_error(OHGPU_ERR_INVALID, "ohgpu_batch_paths_info: neither a pcm batch nor a Songcast frame batch");
+    const OhmPlan& p = b->ohm;
+    if (p.direct) add_line_paths(p.direct->line, out);
+    out->ohm_wide_fragments = p.n_selr;
+    out->ohm_staged_fragments = p.stage ? (uint32_t)p.stage->n : 0;
+    out->ohm_headers_fused = p.n_unfolded_generic - p.n_unfolded;
+    out->ohm_headers_separate = p.n_unfolded;
+    return OHGPU_OK;
+}
+
 int ohgpu_pcm_process_host(ohgpu_ctx* ctx, const ohgpu_msg_desc* descs, size_t n,
                            const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes)
 {

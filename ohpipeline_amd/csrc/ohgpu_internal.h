@@ -48,6 +48,7 @@ static_assert(sizeof(DevSrcDesc) == 56, "DevSrcDesc layout");
 static_assert(sizeof(ohgpu_msg_desc) == 32, "ohgpu_msg_desc layout");
 static_assert(sizeof(ohgpu_src_msg_desc) == 64, "ohgpu_src_msg_desc layout");
 static_assert(sizeof(ohgpu_fmt_desc) == 48, "ohgpu_fmt_desc layout");
+static_assert(sizeof(ohgpu_batch_paths) == 64, "ohgpu_batch_paths layout");
 
 // ---- block ("fast") resampler plan: contiguous runs of output messages cut into phase-aligned blocks ----
 struct SrcSeg {               // one contiguous run of output messages of one stream
@@ -241,6 +242,7 @@ struct PcmLinePlan {
     uint32_t n_chunks = 0;
     uint32_t list_first[kLineLists] = {}, list_count[kLineLists] = {};   // d_chunks[list_first[k], + list_count[k]): one launch each
     uint8_t  list_heavy[kLineLists] = {};   // ... and the share of each list's subsamples, in percent, that is ramped or attenuated (the launch's occupancy)
+    uint32_t n_staged = 0, n_group = 0, n_heavy = 0, n_prefixed = 0;     // chunks by path (ohgpu_batch_paths): list 0 / plain runs / ramped or attenuated messages
     void*    d_chunks = nullptr;
     void*    d_prefix = nullptr;  // the prefix blob
 };

@@ -457,7 +457,7 @@ int ohgpu_ohm_batch_create(ohgpu_ctx* ctx, const ohgpu_ohm_stream* streams, size
             } else if (!(fg.flags & OHGPU_FLAG_SILENCE)) {
                 // a wider stream's audible fragment: one pass over the two channels that go on the wire
                 if (!plain && ch > OHGPU_MAX_CHANNELS)
-                    return set_error(OHGPU_ERR_UNSUPPORTED, "ohm fragment %zu: ramp / attenuation on %u channels (MsgPlayable carries at most 8)", gi, ch);
+                    return set_error(OHGPU_ERR_UNSUPPORTED, "ohm fragment %zu: ramp / attenuation / little-endian source on %u channels (MsgPlayable carries at most 8)", gi, ch);
                 if (fg.ramp_start > OHGPU_RAMP_MAX || fg.ramp_end > OHGPU_RAMP_MAX)
                     return set_error(OHGPU_ERR_INVALID, "ohm fragment %zu: ramp [%u..%u] beyond Ramp::kMax", gi, fg.ramp_start, fg.ramp_end);
                 if ((fg.flags & OHGPU_FLAG_RAMP) && fg.n_frames > 131071u)      // i*iTotalRamp is TInt arithmetic (Msg.cpp:835)

@@ -643,7 +643,12 @@ int plan_pcm_line(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_msg_desc* descs, s
         uint64_t sub_all = 0, sub_heavy = 0;
         for (const PcmChunk& c : lists[k]) {
             sub_all += c.nq;
-            if ((c.flags & kChunkRamp) || c.attenuation != OHGPU_UNITY_ATTENUATION) sub_heavy += c.nq;
+            const bool heavy = (c.flags & kChunkRamp) || c.attenuation != OHGPU_UNITY_ATTENUATION;
+            if (heavy) sub_heavy += c.nq;
+            if (k == 0 || (c.flags & kChunkSilence)) b->line.n_staged++;     // (a silent chunk of a 16/24/32-bit layout rides in its layout's launch, staged)
+            else if (heavy) b->line.n_heavy++;
+            else b->line.n_group++;
+            if (c.prefix_bytes) b->line.n_prefixed++;
         }
         b->line.list_heavy[k] = sub_all ? (uint8_t)((sub_heavy * 100 + sub_all / 2) / sub_all) : 0;
         all.insert(all.end(), lists[k].begin(), lists[k].end());

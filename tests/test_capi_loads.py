@@ -70,6 +70,23 @@ def test_songcast_struct_layouts_match_header(tmp_path):
     assert out[7] == capi.FLYWHEEL_DESC.itemsize == 48
 
 
+def test_batch_paths_query_is_exported_and_laid_out_as_the_header_says(tmp_path):
+    """ohgpu_batch_paths_info: the read-only call that tells a test which kernel path a pcm / Songcast batch was planned onto."""
+    assert "ohgpu_batch_paths_info" in capi.SYMBOLS and hasattr(capi.lib(), "ohgpu_batch_paths_info")
+    src = tmp_path / "sz.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ohgpu.h"\n'
+                   'int main(){printf("%zu %zu %zu %zu %zu\\n", sizeof(ohgpu_batch_paths), offsetof(ohgpu_batch_paths, launches),'
+                   'offsetof(ohgpu_batch_paths, heavy_chunks), offsetof(ohgpu_batch_paths, ohm_headers_separate),'
+                   'offsetof(ohgpu_batch_paths, reserved));return 0;}\n')
+    exe = tmp_path / "sz"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    out = [int(v) for v in subprocess.check_output([str(exe)]).split()]
+    f = capi.BATCH_PATHS.fields
+    assert out == [capi.BATCH_PATHS.itemsize, f["launches"][1], f["heavy_chunks"][1], f["ohm_headers_separate"][1], f["reserved"][1]]
+    assert out[0] == 64
+    assert capi.lib().ohgpu_batch_paths_info(None, None) == capi.ERR_INVALID      # (no context, no device: a null batch is refused)
+
+
 def test_ramp_table_equals_reference_data():
     """The table the DEVICE uses (generated in host_design.cpp) equals RampArray.h:7-74 entry for entry."""
     golden = json.load(open(os.path.join(ROOT, "tests", "golden", "ramp_table_q15.json")))["values"]
