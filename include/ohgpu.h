@@ -64,7 +64,8 @@ extern "C" {
 #define OHGPU_FLAG_SRC_PLANAR32 0x08u /* resampled messages only: the source is what CodecFlac::CallbackWrite is handed (Codec/Flac.cpp:
                                          379-417) -- one plane of host-endian TInt32 per channel, sample values at src_bits depth,
                                          sign-extended -- instead of the packed bytes that callback makes of it: channel c's plane
-                                         starts at src_offset + c * src_plane_stride, a frame is 4 bytes.  a14 -> a1 -> a-R in one pass */
+                                         starts at src_offset + c * src_plane_stride, a frame is 4 bytes.  a14 -> a1 -> a-R in one pass;
+                                         as in that callback, bits above the depth are ignored */
 #define OHGPU_FLAG_ZERO_LSB32 0x04u  /* RampGenerator::ProcessFragment "case 32" (StarvationRamper.cpp:311-320):
                                         when dst_bits == 32 write a zero least-significant byte */
 
@@ -161,10 +162,14 @@ int ohgpu_batch_destroy(ohgpu_ctx* ctx, ohgpu_batch* batch);
 /* Totals recorded at creation (for throughput accounting). */
 int ohgpu_batch_info(const ohgpu_batch* batch, uint64_t* n_msgs, uint64_t* in_frames, uint64_t* out_frames,
                      uint64_t* src_bytes_touched, uint64_t* dst_bytes_written);
-/* Which kernels a PCM batch (ohgpu_pcm_batch_create) or a Songcast frame batch (ohgpu_ohm_batch_create) was planned onto at its
- * creation -- read-only, for tests and tools that must know that the path they mean to exercise is the one that ran.  A chunk is
- * one wave's unit of work of the line kernel (csrc/pcm_line_kernel.hip); under ohgpu_set_kernel_variant(1) a batch runs the
- * generic kernel message by message whatever its plan says.  OHGPU_ERR_INVALID for any other kind of batch. */
+/* Which kernels a PCM batch (ohgpu_pcm_batch_create), a Songcast frame batch (ohgpu_ohm_batch_create) or a batch of the layout-
+ * changing processors (ohgpu_fmt_batch_create) was planned onto at its creation -- read-only, for tests and tools that must know
+ * that the path they mean to exercise is the one that ran.  A chunk is one wave's unit of work of the line kernel
+ * (csrc/pcm_line_kernel.hip); under ohgpu_set_kernel_variant(1) a batch runs the generic kernel message by message whatever its
+ * plan says.  A fmt batch takes exactly one of five routes: mono / stereo Songcast packs of >= 16 bits as plain PCM messages
+ * (line_planned, group_chunks), Songcast packs of wider streams (fmt_wide_records), a uniform stereo batch on a register-only
+ * kernel (fmt_stereo_*), the staged layout kernel (fmt_staged_chunks), or, with every count zero, the generic kernel only.
+ * OHGPU_ERR_INVALID for any other kind of batch. */
 typedef struct ohgpu_batch_paths {       /* 64 bytes */
     uint32_t line_planned;          /* 1: the line kernel has a plan for the batch (0: only the generic kernel can run it) */
     uint32_t launches;              /* line-kernel launches per run: one per layout present (8-bit / silence, and each 16/24/32-bit depth pair) */
@@ -176,7 +181,12 @@ typedef struct ohgpu_batch_paths {       /* 64 bytes */
     uint32_t ohm_staged_fragments;  /* Songcast: silent fragments of such streams (through scratch) */
     uint32_t ohm_headers_fused;     /* Songcast: frame headers written by the audio pass itself */
     uint32_t ohm_headers_separate;  /* Songcast: frame headers the header kernel writes (every header under kernel variant 1) */
-    uint32_t reserved[6];
+    uint32_t fmt_wide_records;      /* fmt: Songcast packs of streams of more than two channels on the channel-selecting kernel, one per descriptor with frames */
+    uint32_t fmt_stereo_records;    /* fmt: a uniform stereo batch of UNPACK_PLANAR (16/24/32 bit) or FLAC_PACK on its register-only kernel, one per descriptor with frames */
+    uint32_t fmt_stereo_kind;       /* ... which of the two: OHGPU_FMT_UNPACK_PLANAR or OHGPU_FMT_FLAC_PACK (0 when fmt_stereo_records is 0) */
+    uint32_t fmt_stereo_bytes;      /* ... and the instantiation: source bytes per subsample 2/3/4 (UNPACK_PLANAR), destination bytes 1/2/3 (FLAC_PACK) */
+    uint32_t fmt_staged_chunks;     /* fmt: chunks of the staged layout kernel (csrc/fmt_line_kernel.hip), <= 512 destination subsamples each */
+    uint32_t reserved[1];
 } ohgpu_batch_paths;
 int ohgpu_batch_paths_info(const ohgpu_batch* batch, ohgpu_batch_paths* out);
 

@@ -50,7 +50,8 @@ FMT_DESC = np.dtype([
 
 BATCH_PATHS = np.dtype([(k, "<u4") for k in ("line_planned", "launches", "staged_chunks", "group_chunks", "heavy_chunks",
                                             "prefixed_chunks", "ohm_wide_fragments", "ohm_staged_fragments", "ohm_headers_fused",
-                                            "ohm_headers_separate")] + [("reserved", "<u4", (6,))], align=False)
+                                            "ohm_headers_separate", "fmt_wide_records", "fmt_stereo_records", "fmt_stereo_kind",
+                                            "fmt_stereo_bytes", "fmt_staged_chunks")] + [("reserved", "<u4", (1,))], align=False)
 assert BATCH_PATHS.itemsize == 64
 
 FLYWHEEL_DESC = np.dtype([
@@ -399,7 +400,7 @@ class Context:
         return dict(zip(keys, (int(x.value) for x in v)))
 
     def batch_paths(self, batch):
-        """Which kernels a pcm or Songcast frame batch was planned onto (ohgpu_batch_paths), as a dict of counts."""
+        """Which kernels a pcm, Songcast frame or fmt batch was planned onto (ohgpu_batch_paths), as a dict of counts."""
         v = np.zeros(1, dtype=BATCH_PATHS)
         check(lib().ohgpu_batch_paths_info(batch, v.ctypes.data_as(C.c_void_p)))
         return {k: int(v[k][0]) for k in BATCH_PATHS.names if k != "reserved"}

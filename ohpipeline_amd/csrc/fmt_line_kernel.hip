@@ -316,6 +316,8 @@ int plan_fmt_line(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_fmt_desc* descs, s
             sub_per_frame = ch;
             frames_per_chunk = budget / ch > 80 ? std::min<uint32_t>(kFmtChunkSub / ch, (budget / ch - 64) / 4) : 0;   // ch runs of <= 4f + 62 bytes
         }
+        // (never taken while validation keeps channels <= 10 and subsamples <= 4 bytes: budget / (ch * sb) >= 2272 / 40 = 56 > 4, and
+        // for a14 budget / ch >= 227 > 80; kept for the day a wider descriptor is admitted)
         if (frames_per_chunk == 0) return OHGPU_OK;                     // a frame does not fit the staging buffer: generic kernel
         magic_u31(c.map_a, &c.m_a, &sh); c.s_a = (uint8_t)sh;
         const uint32_t planes = d.kind == OHGPU_FMT_UNPACK_PLANAR ? ch : 1;

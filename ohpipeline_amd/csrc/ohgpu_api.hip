@@ -659,6 +659,17 @@ static void add_line_paths(const PcmLinePlan& line, ohgpu_batch_paths* out)
     out->prefixed_chunks += line.prefixed ? line.n_prefixed : 0;
 }
 
+// The route plan_fmt_line planned a fmt batch onto: what ohgpu_fmt_batch_run launches (unless kernel variant 1 sends the batch to
+// the generic kernel) and what ohgpu_batch_paths_info reports -- one function, so that the two cannot drift apart.
+enum FmtRoute { kFmtRoutePcmLine, kFmtRouteWide, kFmtRouteStereo, kFmtRouteStaged, kFmtRouteGeneric };
+static FmtRoute fmt_route(const ohgpu_batch* b)
+{
+    if (b->line.enabled) return kFmtRoutePcmLine;                       // mono / stereo Songcast packs as PCM messages
+    if (b->fmtline.n_wide) return kFmtRouteWide;                        // Songcast packs of wider streams
+    if (b->fmtline.enabled) return b->fmtline.group_kind ? kFmtRouteStereo : kFmtRouteStaged;
+    return kFmtRouteGeneric;
+}
+
 int ohgpu_batch_paths_info(const ohgpu_batch* b, ohgpu_batch_paths* out)
 {
     if (!b || !out) return set_error(OHGPU_ERR_INVALID, "ohgpu_batch_paths_info: null argument");
@@ -667,7 +678,22 @@ int ohgpu_batch_paths_info(const ohgpu_batch* b, ohgpu_batch_paths* out)
         add_line_paths(b->line, out);
         return OHGPU_OK;
     }
-    if (b->kind != kBatchOhm) return set_error(OHGPU_ERR_INVALID, "ohgpu_batch_paths_info: neither a pcm batch nor a Songcast frame batch");
+    if (b->kind == kBatchFmt) {
+        const FmtLinePlan& f = b->fmtline;
+        switch (fmt_route(b)) {
+        case kFmtRoutePcmLine: add_line_paths(b->line, out); break;
+        case kFmtRouteWide: out->fmt_wide_records = f.n_wide; break;
+        case kFmtRouteStereo:
+            out->fmt_stereo_records = f.n_chunks;
+            out->fmt_stereo_kind = f.group_kind;
+            out->fmt_stereo_bytes = f.group_bytes;
+            break;
+        case kFmtRouteStaged: out->fmt_staged_chunks = f.n_chunks; break;
+        case kFmtRouteGeneric: break;
+        }
+        return OHGPU_OK;
+    }
+    if (b->kind != kBatchOhm) return set_error(OHGPU_ERR_INVALID, "ohgpu_batch_paths_info: not a pcm, Songcast frame or fmt batch");
     const OhmPlan& p = b->ohm;
     if (p.direct) add_line_paths(p.direct->line, out);
     out->ohm_wide_fragments = p.n_selr;
@@ -767,15 +793,15 @@ int ohgpu_fmt_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* sr
     if (!batch || batch->kind != kBatchFmt) return set_error(OHGPU_ERR_INVALID, "ohgpu_fmt_batch_run: not a fmt batch");
     if (batch->n == 0) return OHGPU_OK;
     if (!src_base || !dst_base) return set_error(OHGPU_ERR_INVALID, "ohgpu_fmt_batch_run: null arena pointer");
-    if (ctx->variant != 1 && batch->line.enabled)                       // stereo Songcast packs planned onto the PCM line kernel
-        OHGPU_HIP_TRY(launch_pcm_line(ctx, batch, (const uint8_t*)src_base, (uint8_t*)dst_base, pick_stream(ctx, stream)));
-    else if (ctx->variant != 1 && batch->fmtline.n_wide)                // Songcast packs of wider streams
-        OHGPU_HIP_TRY(launch_ohm_wide(ctx, batch->fmtline.d_wide, batch->fmtline.n_wide, (const uint8_t*)src_base, (uint8_t*)dst_base, nullptr,
-                                      pick_stream(ctx, stream)));
-    else if (ctx->variant != 1 && batch->fmtline.enabled)
-        OHGPU_HIP_TRY(launch_fmt_line(ctx, batch, (const uint8_t*)src_base, (uint8_t*)dst_base, pick_stream(ctx, stream)));
-    else
-        OHGPU_HIP_TRY(launch_fmt_v1(ctx, batch, (const uint8_t*)src_base, (uint8_t*)dst_base, pick_stream(ctx, stream)));
+    const uint8_t* src = (const uint8_t*)src_base;
+    uint8_t* dst = (uint8_t*)dst_base;
+    switch (ctx->variant == 1 ? kFmtRouteGeneric : fmt_route(batch)) {
+    case kFmtRoutePcmLine: OHGPU_HIP_TRY(launch_pcm_line(ctx, batch, src, dst, pick_stream(ctx, stream))); break;
+    case kFmtRouteWide: OHGPU_HIP_TRY(launch_ohm_wide(ctx, batch->fmtline.d_wide, batch->fmtline.n_wide, src, dst, nullptr, pick_stream(ctx, stream))); break;
+    case kFmtRouteStereo:                                               // (launch_fmt_line picks the instantiation by group_kind / group_bytes)
+    case kFmtRouteStaged: OHGPU_HIP_TRY(launch_fmt_line(ctx, batch, src, dst, pick_stream(ctx, stream))); break;
+    case kFmtRouteGeneric: OHGPU_HIP_TRY(launch_fmt_v1(ctx, batch, src, dst, pick_stream(ctx, stream))); break;
+    }
     return OHGPU_OK;
 }
 

@@ -71,7 +71,7 @@ def test_songcast_struct_layouts_match_header(tmp_path):
 
 
 def test_batch_paths_query_is_exported_and_laid_out_as_the_header_says(tmp_path):
-    """ohgpu_batch_paths_info: the read-only call that tells a test which kernel path a pcm / Songcast batch was planned onto."""
+    """ohgpu_batch_paths_info: the read-only call that tells a test which kernel path a pcm / Songcast / fmt batch was planned onto."""
     assert "ohgpu_batch_paths_info" in capi.SYMBOLS and hasattr(capi.lib(), "ohgpu_batch_paths_info")
     src = tmp_path / "sz.c"
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ohgpu.h"\n'
@@ -84,6 +84,14 @@ def test_batch_paths_query_is_exported_and_laid_out_as_the_header_says(tmp_path)
     f = capi.BATCH_PATHS.fields
     assert out == [capi.BATCH_PATHS.itemsize, f["launches"][1], f["heavy_chunks"][1], f["ohm_headers_separate"][1], f["reserved"][1]]
     assert out[0] == 64
+    # the fmt routes' fields came out of `reserved`: the older fields stay where they were, the struct stays 64 bytes
+    assert (f["launches"][1], f["heavy_chunks"][1], f["ohm_headers_separate"][1]) == (4, 16, 36)
+    names = ("fmt_wide_records", "fmt_stereo_records", "fmt_stereo_kind", "fmt_stereo_bytes", "fmt_staged_chunks", "reserved")
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ohgpu.h"\nint main(){printf("' + "%zu " * len(names) + '\\n", '
+                   + ", ".join(f"offsetof(ohgpu_batch_paths, {n})" for n in names) + ");return 0;}\n")
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    out = [int(v) for v in subprocess.check_output([str(exe)]).split()]
+    assert out == [f[n][1] for n in names] == [40, 44, 48, 52, 56, 60]
     assert capi.lib().ohgpu_batch_paths_info(None, None) == capi.ERR_INVALID      # (no context, no device: a null batch is refused)
 
 

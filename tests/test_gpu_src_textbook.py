@@ -286,6 +286,41 @@ def test_every_plan_kind_equals_the_model(ctx, filters, ramp_table, cell):
             assert hashlib.sha256(np.ascontiguousarray(y, dtype="<i4").tobytes()).hexdigest() == inp["s24_sha256"], inp["kind"]
 
 
+@pytest.mark.parametrize("kernel,variant", [(WG, 0), (LEAN, 4), (V1, 1)], ids=["wg", "lean", "generic"])
+def test_planar_planes_with_bits_above_the_depth(ctx, filters, ramp_table, kernel, variant):
+    """OHGPU_FLAG_SRC_PLANAR32 is a14 -> a1 -> a-R in one pass, and a14 (CodecFlac::CallbackWrite) keeps the low src_bits bits of
+    every TInt32 and drops the rest.  16-bit stereo planes whose upper 16 bits are noise, against the model of the composition: pack
+    the planes as a14 does (tests/fmt_textbook.py), resample the packed bytes.  Bits above the depth are ignored on every kernel."""
+    import fmt_textbook as FT
+    lay = (2, 16, BE, 24, BE, True)
+    flt = filters(F44)
+    rng = np.random.default_rng(515)
+    n_in = 3000
+    y = rng.integers(-32768, 32768, size=(n_in, 2))
+    y[:6, 0], y[:6, 1] = (-32768, 32767, -1, 0, 1, -32767), (32767, -32768, 0, -1, -2, 2)
+    b, n_out = one_stream(flt, lay, y, rng, 240)
+    descs, src = b.descs(), b.arena()
+    off, stride = int(descs["src_offset"][0]), int(descs["src_plane_stride"][0])
+    dirty = src.copy()
+    for c in range(2):
+        words = dirty[off + c * stride:off + c * stride + 4 * n_in].view("<u4")
+        words[:] = (words & 0xFFFF) | (rng.integers(0, 1 << 16, size=n_in).astype(np.uint32) << 16)
+    assert (dirty != src).sum() > n_in
+    fd = {"kind": FT.FLAC_PACK, "channels": 2, "n_frames": n_in, "src_bits": 32, "dst_bits": 16, "src_offset": off, "dst_offset": 0,
+          "src_plane_stride": stride, "dst_plane_stride": 0}
+    (_, packed), = FT.flac_pack(fd, dirty.tobytes())
+    assert FT.flac_pack(fd, src.tobytes()) == [(0, packed)]             # (in range, the planes say the same)
+    packed_descs = descs.copy()
+    packed_descs["flags"] &= ~np.uint8(capi.FLAG_SRC_PLANAR32)
+    packed_descs["src_offset"], packed_descs["src_plane_stride"], packed_descs["src_endian"] = 0, 0, BE
+    want = model(flt, packed_descs, np.frombuffer(packed, dtype=np.uint8), b.dst, ramp_table)
+    assert np.array_equal(model(flt, descs, src, b.dst, ramp_table), want)
+    got, _ = run(ctx, flt, variant, kernel, descs, dirty, b.dst)
+    assert_same(got, want, "planes with noise above bit 15")
+    got, _ = run(ctx, flt, variant, kernel, descs, src, b.dst)
+    assert_same(got, want, "planes in range")
+
+
 # ------------------------------------------------------------------------------------------ the same batch, three periods
 REUSE = {"wg": (WG, 0, F44, [S24]), "lean": (LEAN, 4, F44, [S24]), "round1": (BLOCK, 0, F48, [S24]),
          "two-layouts": (WG, 0, F44, [S24, (6, 24, LE, 24, BE, False)]), "generic": (V1, 0, F44, [(2, 24, LE, 8, BE, False)])}
