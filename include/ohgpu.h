@@ -19,6 +19,12 @@
  *   IPcmProcessor::ProcessFragment doing depth conversion                dst_bits / dst_endian
  *     FlywheelInput::AppendSubsample8/16/24/32 (StarvationRamper.cpp:117-186)
  *     RampGenerator::ProcessFragment           (StarvationRamper.cpp:281-327)
+ *   CodecDsdDsf::Process (Codec/DsdDsf.cpp:169-247, ReverseBits8 :460-465)   OHGPU_DSD_DSF  } ohgpu_dsd_batch_run()
+ *   CodecDsdDff::TransferToOutputBuffer (Codec/DsdDff.cpp:305-327, 350-369)  OHGPU_DSD_DFF  }
+ *   CodecDsdRaw / DsdFiller (Codec/DsdRaw.cpp:119-134, DsdFiller.cpp:73-99)  OHGPU_DSD_RAW  }
+ *   MsgPlayableDsd::ReadBlock (Msg.cpp:2834-2839)                        OHGPU_DSD_PASS
+ *   MsgPlayableSilenceDsd::ReadBlock (Msg.cpp:2916-2932), muted DSD       OHGPU_DSD_FLAG_SILENCE
+ *       (Msg.cpp:2360-2373)
  *   "SampleRateConverter" -- NOT PRESENT in the reference  ohgpu_src_* (own spec)
  *
  * The reference binds nothing through FFI today (it is one C++ static library); INTEGRATION.md
@@ -224,6 +230,72 @@ typedef struct ohgpu_fmt_desc {     /* 48 bytes */
 int ohgpu_fmt_batch_create(ohgpu_ctx* ctx, const ohgpu_fmt_desc* descs, size_t n,
                            uint64_t src_arena_bytes, uint64_t dst_arena_bytes, ohgpu_batch** batch);
 int ohgpu_fmt_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* src_base, void* dst_base, void* stream);
+
+/* ---- DSD: the codec-side packers, the playable pass-through, silence ----
+ * The pipeline's DSD format (Pipeline/Msg.cpp:2379-2393) is a run of SAMPLE BLOCKS of W = sample_block_words 32-bit words; a block
+ * holds W * 4 / (4 + P) CHUNKS, P = pad_bytes_per_chunk, and a chunk is
+ *     [P/2 x 00] L L [P/2 x 00] R R
+ * -- sixteen one-bit samples per channel, most significant bit first, the padding in front of each channel's two bytes.  The
+ * reference asserts (W * 4) % (4 + P) == 0 and takes W - P for the chunks of a block (Codec/DsdDsf.cpp:108,196, DsdDff.cpp:92,334,
+ * Msg.cpp:2385); both hold only for P == 0 (any W >= 1) or W == P + 4 with P even -- in practice (1,0), (2,0), (6,2), (8,4).  Any
+ * other pair is OHGPU_ERR_INVALID.
+ *
+ * A descriptor turns n_chunks chunks' worth of source into ceil(n_chunks / chunks per block) * W * 4 bytes at dst_offset: the
+ * chunks, back to back, then 0x69 up to the end of the last block (every byte of that tail, pad positions included: DsdDsf.cpp:
+ * 218-237, DsdDff.cpp:350-369).  Chunk j is made of
+ *   OHGPU_DSD_DSF   bytes 2r, 2r + 1 of the left plane and of the right plane of pair q (j = 2048 q + r): a file is pairs of
+ *                   4096-byte planes, left then right, so they lie at src_offset + 8192 q + 2r and 4096 further on; every byte is
+ *                   bit-reversed (the file is LSB first).  Stereo only, as in the reference (DsdDsf.cpp:483).  The source span is
+ *                   the whole pairs the chunks touch, ceil(n_chunks / 2048) * 8192 bytes.
+ *   OHGPU_DSD_DFF   source bytes 4j .. 4j + 3 = L R L R, written s0 s2 | s1 s3
+ *   OHGPU_DSD_RAW   source bytes 4j .. 4j + 3 = L L R R, written s0 s1 | s2 s3 (only the padding is added)
+ *   OHGPU_DSD_PASS  the (4 + P) source bytes at src_offset + j * (4 + P), as they are: a playable of audio already in the format
+ * With OHGPU_DSD_FLAG_SILENCE (any kind) the source is not read (src_offset is not looked at) and every output byte is 0x69.  RAW, PASS and SILENCE take whole
+ * blocks only, as the reference does (Msg.cpp:2922; DsdFiller completes a Raw stream's last input block on the host, so its pad
+ * positions stay 00): n_chunks not a multiple of the chunks per block is OHGPU_ERR_INVALID.
+ *
+ * One deliberate difference: when a DSF or DFF stream ends on a chunk count that is not a whole number of blocks, the reference
+ * converts only the whole blocks (numBlocks = remainingChunks / numChunks) yet counts the leftover chunks' bytes, which are then
+ * whatever its buffer last held.  Here the leftover chunks ARE converted and the 0x69 fill starts behind them.  Wherever the
+ * reference's output is well defined the two agree. */
+#define OHGPU_DSD_PASS 1
+#define OHGPU_DSD_DSF  2
+#define OHGPU_DSD_DFF  3
+#define OHGPU_DSD_RAW  4
+#define OHGPU_DSD_FLAG_SILENCE 0x01u
+#define OHGPU_DSD_SILENCE_BYTE 0x69   /* MsgPlayableSilenceDsd, Msg.cpp:2916-2932 */
+
+typedef struct ohgpu_dsd_desc {     /* 32 bytes */
+    uint64_t src_offset;
+    uint64_t dst_offset;
+    uint32_t n_chunks;
+    uint8_t  kind;                  /* OHGPU_DSD_* */
+    uint8_t  flags;                 /* OHGPU_DSD_FLAG_SILENCE */
+    uint8_t  sample_block_words;    /* W */
+    uint8_t  pad_bytes_per_chunk;   /* P */
+    uint8_t  reserved[8];           /* zero */
+} ohgpu_dsd_desc;
+
+/* Host only, no device needed: validates (kind, W, P, n_chunks) by the rules above and gives the source bytes a descriptor reads
+ * from src_offset on (what OHGPU_DSD_FLAG_SILENCE makes 0) and the destination bytes it writes.  Either result may be NULL. */
+int ohgpu_dsd_layout(uint32_t kind, uint32_t sample_block_words, uint32_t pad_bytes_per_chunk, uint32_t n_chunks,
+                     uint64_t* src_bytes, uint64_t* dst_bytes);
+/* Validated like ohgpu_fmt_batch_create (OHGPU_ERR_INVALID / _BOUNDS, nothing kept on a refusal; a descriptor of no chunks is
+ * accepted wherever its offsets point); freed with ohgpu_batch_destroy; ohgpu_batch_info counts its descriptors, its chunks (as
+ * frames in and out) and its bytes.  The batch holds no per-launch device state: it may be run any number of times, on any stream.
+ * Under ohgpu_set_kernel_variant(1) the whole batch runs the plain per-byte kernel dsd_kernel_v1. */
+int ohgpu_dsd_batch_create(ohgpu_ctx* ctx, const ohgpu_dsd_desc* descs, size_t n,
+                           uint64_t src_arena_bytes, uint64_t dst_arena_bytes, ohgpu_batch** batch);
+int ohgpu_dsd_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* src_base, void* dst_base, void* stream);
+/* How the batch was planned (read-only, for tests and tools): descriptors that have a body of whole lanes on the wide path (offsets
+ * 16-byte aligned; a packer's P <= 4 and n_chunks >= 8; PASS and silence from 16 bytes on), descriptors with chunks that are left
+ * to the byte path altogether, and launches per run (1, or 0 for a batch without chunks).  The wide path also needs both arena
+ * pointers 16-byte aligned at the run (ohgpu_malloc's are).  ohgpu_batch_paths_info answers OHGPU_ERR_INVALID for a DSD batch. */
+int ohgpu_dsd_batch_paths(const ohgpu_batch* batch, uint32_t* wide_descs, uint32_t* generic_descs, uint32_t* launches);
+/* Host-buffer convenience, as ohgpu_pcm_process_host: the context's arenas, nothing allocated in a steady state, dst_host bytes
+ * that no descriptor covers preserved, counted in ohgpu_host_transfer_stats. */
+int ohgpu_dsd_process_host(ohgpu_ctx* ctx, const ohgpu_dsd_desc* descs, size_t n,
+                           const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes);
 
 /* ---- FlywheelRamper ----
  * Replaces FlywheelRamperManager::Ramp (OpenHome/Media/FlywheelRamper.cpp:44-66; per channel FlywheelRamper::Initialise

@@ -48,6 +48,15 @@ FMT_DESC = np.dtype([
     ("n_frames", "<u4"), ("kind", "u1"), ("channels", "u1"), ("src_bits", "u1"), ("dst_bits", "u1"),
     ("reserved", "u1", (8,))], align=False)
 
+# DSD: ohgpu_dsd_desc (32 B)
+DSD_PASS, DSD_DSF, DSD_DFF, DSD_RAW = 1, 2, 3, 4
+DSD_FLAG_SILENCE = 1
+DSD_SILENCE_BYTE = 0x69
+DSD_DESC = np.dtype([
+    ("src_offset", "<u8"), ("dst_offset", "<u8"), ("n_chunks", "<u4"), ("kind", "u1"), ("flags", "u1"),
+    ("sample_block_words", "u1"), ("pad_bytes_per_chunk", "u1"), ("reserved", "u1", (8,))], align=False)
+assert DSD_DESC.itemsize == 32
+
 BATCH_PATHS = np.dtype([(k, "<u4") for k in ("line_planned", "launches", "staged_chunks", "group_chunks", "heavy_chunks",
                                             "prefixed_chunks", "ohm_wide_fragments", "ohm_staged_fragments", "ohm_headers_fused",
                                             "ohm_headers_separate", "fmt_wide_records", "fmt_stereo_records", "fmt_stereo_kind",
@@ -108,6 +117,11 @@ SYMBOLS = {
     "ohgpu_pcm_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64]),
     "ohgpu_fmt_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
     "ohgpu_fmt_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "ohgpu_dsd_layout": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u64p, _u64p]),
+    "ohgpu_dsd_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
+    "ohgpu_dsd_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "ohgpu_dsd_batch_paths": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "ohgpu_dsd_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64]),
     "ohgpu_flywheel_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
     "ohgpu_flywheel_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "ohgpu_flywheel_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64]),
@@ -275,6 +289,13 @@ def src_pull_window(pos_frame, pos_frac, step, n_frames, taps_per_phase):
     return int(first.value), int(frames.value)
 
 
+def dsd_layout(kind, sample_block_words, pad_bytes_per_chunk, n_chunks):
+    """(source bytes, destination bytes) of a DSD descriptor, or OhGpuError(ERR_INVALID) (ohgpu_dsd_layout; host only)."""
+    s, d = C.c_uint64(0), C.c_uint64(0)
+    check(lib().ohgpu_dsd_layout(kind, sample_block_words, pad_bytes_per_chunk, n_chunks, C.byref(s), C.byref(d)))
+    return int(s.value), int(d.value)
+
+
 class Context:
     """One GPU context (ohgpu_ctx).  Owns device allocations made through it."""
 
@@ -423,6 +444,31 @@ class Context:
 
     def fmt_run(self, batch, d_src, d_dst, stream=None):
         check(lib().ohgpu_fmt_batch_run(self._h, batch, d_src, d_dst, stream))
+
+    def dsd_batch(self, descs, src_arena_bytes, dst_arena_bytes):
+        d = np.ascontiguousarray(descs)
+        assert d.dtype == DSD_DESC
+        b = C.c_void_p()
+        check(lib().ohgpu_dsd_batch_create(self._h, d.ctypes.data_as(C.c_void_p), d.size, src_arena_bytes,
+                                           dst_arena_bytes, C.byref(b)))
+        return b
+
+    def dsd_run(self, batch, d_src, d_dst, stream=None):
+        check(lib().ohgpu_dsd_batch_run(self._h, batch, d_src, d_dst, stream))
+
+    def dsd_batch_paths(self, batch):
+        """How a DSD batch was planned (ohgpu_dsd_batch_paths): descriptors on the wide path, on the byte path, launches."""
+        v = [C.c_uint32(0) for _ in range(3)]
+        check(lib().ohgpu_dsd_batch_paths(batch, *[C.byref(x) for x in v]))
+        return dict(zip(("wide_descs", "generic_descs", "launches"), (int(x.value) for x in v)))
+
+    def dsd_process_host(self, descs, src, dst):
+        d = np.ascontiguousarray(descs)
+        assert d.dtype == DSD_DESC
+        check(lib().ohgpu_dsd_process_host(self._h, d.ctypes.data_as(C.c_void_p), d.size,
+                                           src.ctypes.data_as(C.c_void_p), src.nbytes,
+                                           dst.ctypes.data_as(C.c_void_p), dst.nbytes))
+        return dst
 
     def flywheel_batch(self, descs, src_arena_bytes, dst_arena_bytes):
         d = np.ascontiguousarray(descs)

@@ -625,7 +625,7 @@ int ohgpu_batch_destroy(ohgpu_ctx* ctx, ohgpu_batch* batch)
     for (ohgpu_batch* part : batch->parts) ohgpu_batch_destroy(ctx, part);
     // (its blocks go back to the context's cache, for the next batch to write into: nothing of this one may still be running --
     // what hipFree used to see to by itself)
-    if (batch->d_descs || batch->kind == kBatchPcm || batch->kind == kBatchFlywheel || batch->kind == kBatchFmt) (void)hipDeviceSynchronize();
+    if (batch->d_descs || batch->kind == kBatchPcm || batch->kind == kBatchFlywheel || batch->kind == kBatchFmt || batch->kind == kBatchDsd) (void)hipDeviceSynchronize();
     if (batch->kind == kBatchSrc) free_src_fast(ctx, batch);          // (waits for the batch's last launch: before its event goes)
     if (batch->last_done) hipEventDestroy(batch->last_done);
     if (batch->d_descs) ctx_dev_free(ctx, batch->d_descs);
@@ -633,6 +633,7 @@ int ohgpu_batch_destroy(ohgpu_ctx* ctx, ohgpu_batch* batch)
     if (batch->kind == kBatchFlywheel) free_flywheel(ctx, batch);
     if (batch->kind == kBatchFmt) { free_fmt_line(ctx, batch); free_pcm_line(ctx, batch); }
     if (batch->kind == kBatchOhm) free_ohm(ctx, batch);
+    if (batch->kind == kBatchDsd) free_dsd_line(ctx, batch);
     if (batch->d_pull_tiles) ctx_dev_free(ctx, batch->d_pull_tiles);
     delete batch;
     return OHGPU_OK;
@@ -803,6 +804,112 @@ int ohgpu_fmt_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* sr
     case kFmtRouteGeneric: OHGPU_HIP_TRY(launch_fmt_v1(ctx, batch, src, dst, pick_stream(ctx, stream))); break;
     }
     return OHGPU_OK;
+}
+
+/* ---------------------------------------------------------------- DSD packers, pass-through, silence */
+// The rules of ohgpu.h's DSD section in one place: ohgpu_dsd_layout, and every descriptor of ohgpu_dsd_batch_create.
+static int dsd_check(const char* who, uint32_t kind, uint32_t flags, uint32_t W, uint32_t P, uint32_t n_chunks, uint64_t* src_bytes, uint64_t* dst_bytes)
+{
+    if (kind != OHGPU_DSD_PASS && kind != OHGPU_DSD_DSF && kind != OHGPU_DSD_DFF && kind != OHGPU_DSD_RAW)
+        return set_error(OHGPU_ERR_INVALID, "%s: unknown kind %u", who, kind);
+    if (flags & ~OHGPU_DSD_FLAG_SILENCE) return set_error(OHGPU_ERR_INVALID, "%s: unknown flags 0x%x", who, flags);
+    // ASSERT((W * 4) % (4 + P) == 0) with W - P chunks per block: DsdDsf.cpp:108,196, DsdDff.cpp:92,334, Msg.cpp:2385
+    if (W < 1 || W > 255 || !(P == 0 || (P % 2 == 0 && W == P + 4)))
+        return set_error(OHGPU_ERR_INVALID, "%s: sample block of %u words with %u pad bytes per chunk (P == 0, or W == P + 4 with P even)", who, W, P);
+    const uint64_t cs = 4 + P, per_block = W * 4 / cs, blocks = (n_chunks + per_block - 1) / per_block;
+    const bool silent = (flags & OHGPU_DSD_FLAG_SILENCE) != 0;
+    if ((silent || kind == OHGPU_DSD_RAW || kind == OHGPU_DSD_PASS) && n_chunks % per_block != 0)   // ASSERT, Msg.cpp:2922
+        return set_error(OHGPU_ERR_INVALID, "%s: %u chunks are not whole sample blocks of %llu (Raw, pass-through and silence take whole blocks)", who, n_chunks, (unsigned long long)per_block);
+    if (src_bytes) {
+        if (silent) *src_bytes = 0;
+        else if (kind == OHGPU_DSD_DSF) *src_bytes = ((uint64_t)n_chunks + 2047) / 2048 * 8192;
+        else if (kind == OHGPU_DSD_PASS) *src_bytes = n_chunks * cs;
+        else *src_bytes = (uint64_t)n_chunks * 4;
+    }
+    if (dst_bytes) *dst_bytes = blocks * W * 4;
+    return OHGPU_OK;
+}
+
+int ohgpu_dsd_layout(uint32_t kind, uint32_t sample_block_words, uint32_t pad_bytes_per_chunk, uint32_t n_chunks, uint64_t* src_bytes, uint64_t* dst_bytes)
+{
+    return dsd_check("ohgpu_dsd_layout", kind, 0, sample_block_words, pad_bytes_per_chunk, n_chunks, src_bytes, dst_bytes);
+}
+
+int ohgpu_dsd_batch_create(ohgpu_ctx* ctx, const ohgpu_dsd_desc* descs, size_t n,
+                           uint64_t src_arena_bytes, uint64_t dst_arena_bytes, ohgpu_batch** out)
+{
+    CTX_GUARD("ohgpu_dsd_batch_create");
+    if (!out || (n && !descs)) return set_error(OHGPU_ERR_INVALID, "ohgpu_dsd_batch_create: null argument");
+    *out = nullptr;
+    if (n > 0xffffffffull) return set_error(OHGPU_ERR_INVALID, "ohgpu_dsd_batch_create: too many descriptors");
+    ohgpu_batch* b = new (std::nothrow) ohgpu_batch();
+    if (!b) return set_error(OHGPU_ERR_NOMEM, "ohgpu_dsd_batch_create: out of host memory");
+    b->kind = kBatchDsd;
+    b->n = n;
+    b->src_arena_bytes = src_arena_bytes;
+    b->dst_arena_bytes = dst_arena_bytes;
+    for (size_t i = 0; i < n; i++) {
+        const ohgpu_dsd_desc& d = descs[i];
+        char who[48];
+        snprintf(who, sizeof(who), "dsd desc %zu", i);
+        uint64_t src_bytes = 0, dst_bytes = 0;
+        int err = dsd_check(who, d.kind, d.flags, d.sample_block_words, d.pad_bytes_per_chunk, d.n_chunks, &src_bytes, &dst_bytes);
+        for (size_t k = 0; k < sizeof(d.reserved) && err == OHGPU_OK; k++)
+            if (d.reserved[k]) err = set_error(OHGPU_ERR_INVALID, "%s: reserved bytes must be zero", who);
+        if (err == OHGPU_OK && src_bytes > 0 && (d.src_offset > src_arena_bytes || src_bytes > src_arena_bytes - d.src_offset))   // (a silent descriptor reads no source: its src_offset is not looked at)
+            err = set_error(OHGPU_ERR_BOUNDS, "%s: reads [%llu, +%llu) beyond the %llu-byte source arena", who, (unsigned long long)d.src_offset, (unsigned long long)src_bytes, (unsigned long long)src_arena_bytes);
+        if (err == OHGPU_OK && d.n_chunks > 0 && (d.dst_offset > dst_arena_bytes || dst_bytes > dst_arena_bytes - d.dst_offset))
+            err = set_error(OHGPU_ERR_BOUNDS, "%s: writes [%llu, +%llu) beyond the %llu-byte destination arena", who, (unsigned long long)d.dst_offset, (unsigned long long)dst_bytes, (unsigned long long)dst_arena_bytes);
+        if (err != OHGPU_OK) { delete b; return err; }
+        b->in_frames += d.n_chunks;
+        b->out_frames += d.n_chunks;
+        b->src_bytes_touched += src_bytes;
+        b->dst_bytes_written += dst_bytes;
+    }
+    int err = upload_batch(ctx, b, descs, n * sizeof(ohgpu_dsd_desc));
+    if (err == OHGPU_OK) err = plan_dsd_line(ctx, b, descs, n);
+    if (err != OHGPU_OK) { if (b->d_descs) ctx_dev_free(ctx, b->d_descs); delete b; return err; }
+    *out = b;
+    return OHGPU_OK;
+}
+
+int ohgpu_dsd_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* src_base, void* dst_base, void* stream)
+{
+    CTX_GUARD("ohgpu_dsd_batch_run");
+    if (!batch || batch->kind != kBatchDsd) return set_error(OHGPU_ERR_INVALID, "ohgpu_dsd_batch_run: not a DSD batch");
+    if (batch->dsd.n_pieces == 0) return OHGPU_OK;
+    if (!dst_base || (!src_base && batch->src_bytes_touched)) return set_error(OHGPU_ERR_INVALID, "ohgpu_dsd_batch_run: null arena pointer");
+    if (ctx->variant == 1) OHGPU_HIP_TRY(launch_dsd_v1(ctx, batch, (const uint8_t*)src_base, (uint8_t*)dst_base, pick_stream(ctx, stream)));
+    else OHGPU_HIP_TRY(launch_dsd_line(ctx, batch, (const uint8_t*)src_base, (uint8_t*)dst_base, pick_stream(ctx, stream)));
+    return OHGPU_OK;
+}
+
+int ohgpu_dsd_batch_paths(const ohgpu_batch* b, uint32_t* wide_descs, uint32_t* generic_descs, uint32_t* launches)
+{
+    if (!b || b->kind != kBatchDsd) return set_error(OHGPU_ERR_INVALID, "ohgpu_dsd_batch_paths: not a DSD batch");
+    if (wide_descs) *wide_descs = b->dsd.n_wide;
+    if (generic_descs) *generic_descs = b->dsd.n_generic;
+    if (launches) *launches = b->dsd.n_pieces ? 1u : 0u;
+    return OHGPU_OK;
+}
+
+int ohgpu_dsd_process_host(ohgpu_ctx* ctx, const ohgpu_dsd_desc* descs, size_t n,
+                           const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes)
+{
+    CTX_GUARD("ohgpu_dsd_process_host");
+    ohgpu_batch* b = nullptr;
+    int err = ohgpu_dsd_batch_create(ctx, descs, n, src_bytes, dst_bytes, &b);
+    if (err != OHGPU_OK) return err;
+    std::vector<std::pair<uint64_t, uint64_t>> out(n);
+    for (size_t i = 0; i < n; i++) {
+        uint64_t bytes = 0;
+        (void)dsd_check("dsd", descs[i].kind, descs[i].flags, descs[i].sample_block_words, descs[i].pad_bytes_per_chunk, descs[i].n_chunks, nullptr, &bytes);
+        out[i] = {descs[i].dst_offset, bytes};
+    }
+    err = host_roundtrip(ctx, src_host, src_bytes, dst_host, dst_bytes, out,
+                         [&](const void* d_src, void* d_dst) { return ohgpu_dsd_batch_run(ctx, b, d_src, d_dst, nullptr); });
+    ohgpu_batch_destroy(ctx, b);
+    return err;
 }
 
 /* ---------------------------------------------------------------- FlywheelRamper (N1) */

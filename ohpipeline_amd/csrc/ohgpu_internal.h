@@ -49,6 +49,7 @@ static_assert(sizeof(ohgpu_msg_desc) == 32, "ohgpu_msg_desc layout");
 static_assert(sizeof(ohgpu_src_msg_desc) == 64, "ohgpu_src_msg_desc layout");
 static_assert(sizeof(ohgpu_fmt_desc) == 48, "ohgpu_fmt_desc layout");
 static_assert(sizeof(ohgpu_batch_paths) == 64, "ohgpu_batch_paths layout");
+static_assert(sizeof(ohgpu_dsd_desc) == 32, "ohgpu_dsd_desc layout");
 
 // ---- block ("fast") resampler plan: contiguous runs of output messages cut into phase-aligned blocks ----
 struct SrcSeg {               // one contiguous run of output messages of one stream
@@ -273,6 +274,22 @@ struct FmtLinePlan {
     void*    d_wide = nullptr;
 };
 
+// ---- DSD (csrc/dsd_line_kernel.hip) ----
+struct DsdPiece {             // 32 bytes: one wave's share of a descriptor -- chunks [j0, j0 + n), then `fill` bytes of 0x69
+    uint64_t src_off, dst_off;    // the DESCRIPTOR's offsets (a DSF chunk's place in its plane pair follows from its index)
+    uint32_t j0, n;
+    uint32_t fill;                // bytes of 0x69 right behind chunk j0 + n - 1 (the descriptor's last piece; every piece of a silent one)
+    uint8_t  kind, pad;           // OHGPU_DSD_*, padBytesPerChunk
+    uint8_t  flags;               // kPieceWide: whole lanes of eight chunks go out in 16-byte stores; kPieceSilence
+    uint8_t  pad8;
+};
+static_assert(sizeof(DsdPiece) == 32, "DsdPiece");
+struct DsdPlan {
+    uint32_t n_pieces = 0;
+    uint32_t n_wide = 0, n_generic = 0;   // descriptors with / without a 16-byte-store body (ohgpu_dsd_batch_paths)
+    void*    d_pieces = nullptr;
+};
+
 // ---- FlywheelRamper (csrc/flywheel_kernel.hip) ----
 struct FlywheelLane { uint32_t req, channel; };      // one lane = one channel of one request
 struct FlywheelPlan {
@@ -315,7 +332,7 @@ struct OhmPlan {
     uint32_t n_unfolded = 0, n_unfolded_generic = 0;
 };
 
-enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6 };
+enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7 };
 
 }  // namespace ohgpu
 
@@ -410,6 +427,7 @@ struct ohgpu_batch {
     ohgpu::FlywheelPlan fly;      // kBatchFlywheel only
     ohgpu::FmtLinePlan fmtline;   // kBatchFmt only
     ohgpu::OhmPlan ohm;           // kBatchOhm only
+    ohgpu::DsdPlan dsd;           // kBatchDsd only
     void*    d_pull_tiles = nullptr;   // kBatchSrcPull: PullTile[n_pull_tiles] on the device (d_descs holds the messages)
     uint32_t n_pull_tiles = 0;
     // kBatchSrc whose messages differ in layout: one uniform batch per layout (each with its own block-kernel plan), run one
@@ -450,6 +468,10 @@ void free_pcm_line(ohgpu_ctx* ctx, ohgpu_batch* b);
 int plan_fmt_line(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_fmt_desc* descs, size_t n);
 void free_fmt_line(ohgpu_ctx* ctx, ohgpu_batch* b);
 hipError_t launch_fmt_line(const ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
+int plan_dsd_line(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_dsd_desc* descs, size_t n);   // csrc/dsd_line_kernel.hip
+void free_dsd_line(ohgpu_ctx* ctx, ohgpu_batch* b);
+hipError_t launch_dsd_line(const ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
+hipError_t launch_dsd_v1(const ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
 // csrc/ohm_frame_kernel.hip: the two wire channels of streams wider than stereo (Sender::DoProcessFragment), one record per fragment
 OhmSelRec wide_record(uint64_t src_off, uint64_t dst_off, uint32_t n_frames, uint32_t channels, uint32_t sb, bool little, uint64_t src_arena_bytes);
 hipError_t launch_ohm_wide(const ohgpu_ctx* ctx, const void* d_recs, uint32_t n_recs, const uint8_t* src, uint8_t* dst, const uint8_t* prefix, hipStream_t s);

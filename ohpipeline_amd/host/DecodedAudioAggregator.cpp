@@ -143,3 +143,21 @@ TUint64 CodecController::OutputAudioPcm(const Brx& aData, TUint aChannels, TUint
     }
     return jiffiesOut;
 }
+
+TUint64 CodecController::OutputAudioDsd(const Brx& aData, TUint aChannels, TUint aSampleRate, TUint aSampleBlockWords,
+                                        TUint64 aTrackOffset, TUint aPadBytesPerChunk)
+{
+    ASSERT(aChannels == iChannels && aSampleRate == iSampleRate);    // :867-868
+    ASSERT(aSampleBlockWords != 0 && aData.Bytes() % (aSampleBlockWords * 4) == 0);   // whole sample blocks
+    const TUint pieceMax = DecodedAudio::kMaxBytes - DecodedAudio::kMaxBytes % (aSampleBlockWords * 4);
+    TUint64 jiffiesOut = 0;
+    for (TUint done = 0; done < aData.Bytes(); ) {                    // (an empty buffer outputs nothing, :871-874)
+        const TUint piece = std::min(pieceMax, aData.Bytes() - done);
+        MsgAudioDsd* audio = iMsgFactory.CreateMsgAudioDsd(Brn(aData.Ptr() + done, piece), aChannels, aSampleRate, aSampleBlockWords,
+                                                           aTrackOffset + jiffiesOut, aPadBytesPerChunk);
+        jiffiesOut += audio->Jiffies();
+        iDownstreamElement.Push(audio);
+        done += piece;
+    }
+    return jiffiesOut;
+}

@@ -5,7 +5,8 @@
 //   DecodedAudioAggregator                                   OpenHome/Media/Pipeline/DecodedAudioAggregator.{h,cpp}
 //       small MsgAudioPcm are joined until 5 ms or DecodedAudio::kMaxBytes are reached
 // Neither interprets a PCM byte (the codec's endian travels in the DecodedAudio and is resolved by the device when the
-// audio is read).  DSD is out of scope: MsgAudioDsd passes through untouched.
+// audio is read).  DSD leaves the codec side through CodecController::OutputAudioDsd (host/DsdPacker.h feeds it); the
+// aggregator does not join DSD messages: MsgAudioDsd passes through untouched.
 //
 // Shape of this implementation: the aggregator holds at most one message; every message that is not PCM audio first
 // releases it (one helper serves all of them), PCM audio is absorbed by Absorb(), which keeps a running byte count next to
@@ -68,6 +69,10 @@ public:
     /** CodecController.cpp:799-826: returns the jiffies output; asserts the format is the announced one. */
     TUint64 OutputAudioPcm(const Brx& aData, TUint aChannels, TUint aSampleRate, TUint aBitDepth, AudioDataEndian aEndian,
                            TUint64 aTrackOffset);
+    /** CodecController.cpp:864-896: aData is whole sample blocks in the pipeline's DSD format; it leaves as MsgAudioDsd of at most
+     *  DecodedAudio::kMaxBytes each (DSD is not Songcast, so nothing cuts it to 5 ms).  Returns the jiffies output. */
+    TUint64 OutputAudioDsd(const Brx& aData, TUint aChannels, TUint aSampleRate, TUint aSampleBlockWords, TUint64 aTrackOffset,
+                           TUint aPadBytesPerChunk);
     TUint MaxOutputBytes() const { return iMaxOutputBytes; }
 private:
     MsgFactory& iMsgFactory;

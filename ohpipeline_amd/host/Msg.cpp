@@ -43,6 +43,13 @@ void ProcessorPcmBufTest::ProcessSilence(const Brx& aData, TUint aNumChannels, T
     ProcessFragment(aData, aNumChannels, aSubsampleBytes);
 }
 
+void ProcessorDsdBufTest::ProcessFragment(const Brx& aData, TUint /*aNumChannels*/, TUint aSampleBlockWords)
+{
+    ASSERT(aSampleBlockWords != 0 && aData.Bytes() % (aSampleBlockWords * 4) == 0);
+    iBuf.insert(iBuf.end(), aData.Ptr(), aData.Ptr() + aData.Bytes());
+    iFragments.push_back(aData.Bytes());
+}
+
 // ---------------------------------------------------------------- DecodedAudio
 DecodedAudio::DecodedAudio(const Brx& aData, TUint aBitDepth, AudioDataEndian aEndian)
     : iBitDepth(aBitDepth)
@@ -53,6 +60,14 @@ DecodedAudio::DecodedAudio(const Brx& aData, TUint aBitDepth, AudioDataEndian aE
     ASSERT(aData.Bytes() % (aBitDepth / 8) == 0);
     ASSERT(aData.Bytes() <= kMaxBytes);
     iData.assign(aData.Ptr(), aData.Ptr() + aData.Bytes());
+}
+
+DecodedAudio::DecodedAudio(const Brx& aDsd)
+    : iBitDepth(1)
+    , iEndian(AudioDataEndian::Invalid)                      // bits in time order: a byte order does not apply
+{
+    ASSERT(aDsd.Bytes() <= kMaxBytes);
+    iData.assign(aDsd.Ptr(), aDsd.Ptr() + aDsd.Bytes());
 }
 
 void DecodedAudio::Aggregate(const DecodedAudio& aOther)
@@ -231,43 +246,147 @@ MsgPlayable* MsgAudioPcm::CreatePlayable()
     return playable;
 }
 
+// ---------------------------------------------------------------- MsgAudioDsd
+// What the reference fixes (Msg.cpp:2308-2462; its suite runs against this in tests/cpp/test_dsd.cpp): a message's jiffies count
+// playable samples only, offsets and sizes reach the audio rounded DOWN to whole sample blocks, and the padded size of a window is
+// the whole blocks from the block its offset lies in to the block its end lies in, scaled by W / (W - P).
+MsgAudioDsd::MsgAudioDsd()
+    : MsgAudio(0, 1, 0)
+{
+}
+
+MsgAudioDsd::MsgAudioDsd(MsgFactory& aFactory, std::shared_ptr<DecodedAudio> aAudio, TUint aSampleRate, TUint aChannels,
+                         TUint aSampleBlockWords, TUint aBlockWordsNoPad, TUint64 aTrackOffset)
+    : MsgAudio(aSampleRate, 1, aChannels)
+    , iFactory(&aFactory)
+    , iAudioData(aAudio)
+    , iSampleBlockWords(aSampleBlockWords)
+    , iBlockWordsNoPad(aBlockWordsNoPad)
+    , iTrackOffset(aTrackOffset)
+{
+}
+
+MsgAudio* MsgAudioDsd::Allocate()
+{
+    ASSERT(iFactory != nullptr);
+    return new MsgAudioDsd(*iFactory, iAudioData, iSampleRate, iNumChannels, iSampleBlockWords, iBlockWordsNoPad, iTrackOffset);
+}
+
+MsgAudio* MsgAudioDsd::Clone()
+{
+    MsgAudioDsd* twin = static_cast<MsgAudioDsd*>(MsgAudio::Clone());
+    twin->iSizeTotalJiffies = iSizeTotalJiffies;
+    return twin;
+}
+
+TUint MsgAudioDsd::JiffiesPlayableToJiffiesTotal(TUint aJiffies, TUint aJiffiesPerSampleBlockPlayable) const
+{
+    const TUint wholeBlocks = aJiffies - aJiffies % aJiffiesPerSampleBlockPlayable;
+    ASSERT(wholeBlocks % iBlockWordsNoPad == 0);
+    return wholeBlocks / iBlockWordsNoPad * iSampleBlockWords;
+}
+
+void MsgAudioDsd::Measure()
+{
+    const TUint blockPlayable = SamplesPerBlock(iBlockWordsNoPad) * Jiffies::PerSample(iSampleRate);
+    const TUint intoBlock = iOffset % blockPlayable;               // the window starts this far into a sample block
+    iSizeTotalJiffies = JiffiesPlayableToJiffiesTotal(iSize + intoBlock, blockPlayable);
+}
+
+void MsgAudioDsd::SplitCompleted(MsgAudio& aRemaining)
+{
+    MsgAudioDsd& remaining = static_cast<MsgAudioDsd&>(aRemaining);
+    remaining.iTrackOffset = (iTrackOffset == kTrackOffsetInvalid) ? iTrackOffset : iTrackOffset + iSize;
+    Measure();
+    remaining.Measure();
+}
+
+MsgPlayable* MsgAudioDsd::CreatePlayable()
+{
+    ASSERT(iFactory != nullptr);
+    const TUint perSample = Jiffies::PerSample(iSampleRate);
+    const TUint blockSamples = SamplesPerBlock(iSampleBlockWords);
+    TUint offsetTotal = JiffiesPlayableToJiffiesTotal(iOffset, SamplesPerBlock(iBlockWordsNoPad) * perSample);
+    TUint sizeTotal = iSizeTotalJiffies;
+    PlayableWork work;
+    work.sampleRate = iSampleRate;
+    work.bitDepth = 1;
+    work.channels = iNumChannels;
+    work.sampleBlockWords = iSampleBlockWords;
+    work.sizeBytes = Jiffies::ToBytesSampleBlock(sizeTotal, perSample, iNumChannels, 1, blockSamples);
+    work.frames = work.sizeBytes * 8 / iNumChannels;
+    work.silence = iRamp.Direction() == Ramp::EMute;               // muted DSD plays 0x69 (Msg.cpp:2360-2373); nothing else is ever ramped
+    if (!work.silence) {
+        work.offsetBytes = Jiffies::ToBytesSampleBlock(offsetTotal, perSample, iNumChannels, 1, blockSamples);
+        work.audio = iAudioData;
+        work.ramp = iRamp;
+        ASSERT(work.offsetBytes + work.sizeBytes <= iAudioData->Bytes());
+    }
+    MsgPlayable* playable = new MsgPlayable(*iFactory, work, iSize);
+    RemoveRef();
+    return playable;
+}
+
 // ---------------------------------------------------------------- MsgSilence
 MsgSilence::MsgSilence(MsgFactory& aFactory, TUint& aJiffies, TUint aSampleRate, TUint aBitDepth, TUint aChannels)
     : MsgAudio(aSampleRate, aBitDepth, aChannels)
     , iFactory(aFactory)
 {
-    Jiffies::RoundDownNonZeroSampleBlock(aJiffies, Jiffies::PerSample(aSampleRate));
+    iBlockJiffiesPlayable = iBlockJiffiesTotal = Jiffies::PerSample(aSampleRate);
+    Jiffies::RoundDownNonZeroSampleBlock(aJiffies, iBlockJiffiesPlayable);
+    iSize = aJiffies;
+}
+
+MsgSilence::MsgSilence(MsgFactory& aFactory, TUint& aJiffies, TUint aSampleRate, TUint aChannels, TUint aSampleBlockWords, TUint aPadBytesPerChunk)
+    : MsgAudio(aSampleRate, 1, aChannels)
+    , iFactory(aFactory)
+    , iSampleBlockWords(aSampleBlockWords)
+{
+    ASSERT(aSampleBlockWords != 0 && aSampleBlockWords > aPadBytesPerChunk);
+    const TUint perSample = Jiffies::PerSample(aSampleRate);
+    iBlockJiffiesTotal = aSampleBlockWords * 32 / aChannels * perSample;
+    iBlockJiffiesPlayable = (aSampleBlockWords - aPadBytesPerChunk) * 32 / aChannels * perSample;
+    Jiffies::RoundDownNonZeroSampleBlock(aJiffies, iBlockJiffiesPlayable);
     iSize = aJiffies;
 }
 
 MsgAudio* MsgSilence::Allocate()
 {
-    TUint jiffies = Jiffies::PerSample(iSampleRate);
-    return new MsgSilence(iFactory, jiffies, iSampleRate, iBitDepth, iNumChannels);
+    TUint jiffies = iBlockJiffiesPlayable;
+    MsgSilence* msg = new MsgSilence(iFactory, jiffies, iSampleRate, iBitDepth, iNumChannels);
+    msg->iSampleBlockWords = iSampleBlockWords;
+    msg->iBlockJiffiesPlayable = iBlockJiffiesPlayable;
+    msg->iBlockJiffiesTotal = iBlockJiffiesTotal;
+    return msg;
 }
 
 void MsgSilence::SplitCompleted(MsgAudio& aRemaining)
 {
-    // both parts stay whole samples; what does not fit the first part moves to the second (Msg.cpp:2520-2545)
+    // both parts stay whole samples (DSD: whole sample blocks); what does not fit the first part moves to the second (Msg.cpp:2520-2545)
     MsgSilence& remaining = static_cast<MsgSilence&>(aRemaining);
-    const TUint block = Jiffies::PerSample(iSampleRate);
-    const TUint extra = iSize % block;
+    const TUint extra = iSize % iBlockJiffiesPlayable;
     iSize -= extra;
     remaining.iSize += extra;
 }
 
 MsgPlayable* MsgSilence::CreatePlayable()
 {
-    const TUint jiffiesPerSample = Jiffies::PerSample(iSampleRate);
-    TUint jiffies = iSize;
     PlayableWork work;
     work.silence = true;
     work.sampleRate = iSampleRate;
     work.bitDepth = iBitDepth;
     work.channels = iNumChannels;
-    work.sizeBytes = Jiffies::ToBytes(jiffies, jiffiesPerSample, iNumChannels, iBitDepth);
-    work.frames = work.sizeBytes / ((iBitDepth / 8) * iNumChannels);
-    work.ramp = iRamp;
+    if (iSampleBlockWords != 0) {                                  // DSD: the whole blocks of iSize, with their padding
+        work.sampleBlockWords = iSampleBlockWords;
+        work.sizeBytes = iSize / iBlockJiffiesPlayable * iSampleBlockWords * 4;
+        work.frames = work.sizeBytes * 8 / iNumChannels;
+    }
+    else {
+        TUint jiffies = iSize;
+        work.sizeBytes = Jiffies::ToBytes(jiffies, iBlockJiffiesPlayable, iNumChannels, iBitDepth);
+        work.frames = work.sizeBytes / ((iBitDepth / 8) * iNumChannels);
+        work.ramp = iRamp;
+    }
     MsgPlayable* playable = new MsgPlayable(iFactory, work, iSize);
     RemoveRef();
     return playable;
@@ -289,13 +408,15 @@ MsgPlayable* MsgPlayable::Split(TUint aBytes)
     if (aBytes == iWork.sizeBytes) {
         return nullptr;                                            // nothing behind the cut
     }
-    const TUint frameBytes = (iWork.bitDepth / 8) * iWork.channels;
-    const TUint headFrames = aBytes / frameBytes;
+    if (iWork.Dsd()) {
+        ASSERT(aBytes % (iWork.sampleBlockWords * 4) == 0);       // a DSD playable is read in whole sample blocks (Msg.cpp:2922)
+    }
+    const TUint headFrames = iWork.Dsd() ? aBytes * 8 / iWork.channels : aBytes / ((iWork.bitDepth / 8) * iWork.channels);
     const TUint headJiffies = headFrames * Jiffies::PerSample(iWork.sampleRate);
     PlayableWork tail = iWork;
     tail.offsetBytes += aBytes;
     tail.sizeBytes -= aBytes;
-    tail.frames = tail.sizeBytes / frameBytes;
+    tail.frames = iWork.frames - headFrames;
     tail.outFrame0 += headFrames;
     if (tail.pulled) PullAdvance(tail.pullPosFrame, tail.pullPosFrac, tail.pullStep, headFrames);
     tail.ramp = iWork.ramp.IsEnabled() ? iWork.ramp.Split(aBytes, iWork.sizeBytes) : Media::Ramp();
@@ -310,6 +431,14 @@ void MsgPlayable::Read(IPcmProcessor& aProcessor)
 {
     PlayableBatch batch(iFactory);
     AddRef();                        // the batch releases one reference; Read() leaves ownership with the caller
+    batch.Add(this, aProcessor);
+    batch.Run();
+}
+
+void MsgPlayable::Read(IDsdProcessor& aProcessor)
+{
+    PlayableBatch batch(iFactory);
+    AddRef();
     batch.Add(this, aProcessor);
     batch.Run();
 }
@@ -333,6 +462,8 @@ struct PlayableBatch::WindowRun {
 struct PlayableBatch::Group {
     const SrcFilter* filter = nullptr;                    // nullptr: the plain audio (one ohgpu_pcm_process_host) or ...
     const PullFilter* pullFilter = nullptr;               // ... the pulled audio of one filter (one ohgpu_src_pull_process_host)
+    TBool dsd = false;                                    // ... or the DSD playables (one ohgpu_dsd_process_host)
+    std::vector<ohgpu_dsd_desc> dsdDescs;
     std::vector<size_t> items;
     std::vector<ohgpu_msg_desc> pcm;
     std::vector<ohgpu_src_msg_desc> src;
@@ -340,21 +471,23 @@ struct PlayableBatch::Group {
     std::vector<WindowRun> runs;
     std::vector<size_t> runOf;                            // per resampled item: its run
     TUint64 srcBase = 0, srcBytes = 0, dstBase = 0, dstBytes = 0;
-    void Clear() { items.clear(); pcm.clear(); src.clear(); pull.clear(); runs.clear(); runOf.clear(); srcBase = srcBytes = dstBase = dstBytes = 0; }
+    void Clear() { items.clear(); dsdDescs.clear(); pcm.clear(); src.clear(); pull.clear(); runs.clear(); runOf.clear(); srcBase = srcBytes = dstBase = dstBytes = 0; }
 };
 
 struct PlayableBatch::Scratch {
     std::deque<Group> groups;                             // [0] the plain audio, [1 + k] the k-th filter met (a deque: Take's references stay valid)
     size_t used = 0;
     std::map<const DecodedAudio*, TUint64> audioBase;
-    Group& Take(const SrcFilter* aFilter, const PullFilter* aPullFilter = nullptr)
+    std::map<const DecodedAudio*, TUint64> dsdAudioBase;  // ... and the DSD group's
+    Group& Take(const SrcFilter* aFilter, const PullFilter* aPullFilter = nullptr, TBool aDsd = false)
     {
-        for (size_t g = 0; g < used; g++) if (groups[g].filter == aFilter && groups[g].pullFilter == aPullFilter) return groups[g];
+        for (size_t g = 0; g < used; g++) if (groups[g].filter == aFilter && groups[g].pullFilter == aPullFilter && groups[g].dsd == aDsd) return groups[g];
         if (used == groups.size()) groups.emplace_back();
         Group& g = groups[used++];
         g.Clear();
         g.filter = aFilter;
         g.pullFilter = aPullFilter;
+        g.dsd = aDsd;
         return g;
     }
 };
@@ -382,7 +515,16 @@ void PlayableBatch::SetOutputFormat(TUint aBitDepth, AudioDataEndian aEndian)
 
 void PlayableBatch::Add(MsgPlayable* aPlayable, IPcmProcessor& aProcessor)
 {
+    ASSERT(!aPlayable->Work().Dsd());                              // DSD is read through an IDsdProcessor
     iItems.push_back({aPlayable, &aProcessor, 0, 0});
+}
+
+void PlayableBatch::Add(MsgPlayable* aPlayable, IDsdProcessor& aProcessor)
+{
+    ASSERT(aPlayable->Work().Dsd());
+    Item item{aPlayable, nullptr, 0, 0};
+    item.dsdProcessor = &aProcessor;
+    iItems.push_back(item);
 }
 
 static uint8_t GpuEndian(AudioDataEndian aEndian)
@@ -396,6 +538,7 @@ void PlayableBatch::Run()
     Scratch& sc = *iScratch;
     sc.used = 0;
     sc.audioBase.clear();
+    sc.dsdAudioBase.clear();
     // ---- who goes with whom: the plain audio in one call, the rate-converted audio in one call per filter.  Within a group the
     // outputs lie back to back in the order the items came (they tile the group's span of the destination: one copy back), and
     // of the sources each distinct DecodedAudio lies there once, each run of consecutive outputs of a stream as ONE window ----
@@ -406,9 +549,16 @@ void PlayableBatch::Run()
         if (w.frames == 0) {
             continue;
         }
-        Group& g = w.resampled ? sc.Take(&w.stream->Filter()) : (w.pulled ? sc.Take(nullptr, &w.pullStream->Filter()) : plain);
+        Group& g = w.Dsd() ? sc.Take(nullptr, nullptr, true)
+                 : w.resampled ? sc.Take(&w.stream->Filter()) : (w.pulled ? sc.Take(nullptr, &w.pullStream->Filter()) : plain);
         g.items.push_back(i);
-        if (w.pulled) {
+        if (w.Dsd()) {
+            if (!w.silence && sc.dsdAudioBase.find(w.audio.get()) == sc.dsdAudioBase.end()) {
+                sc.dsdAudioBase.emplace(w.audio.get(), g.srcBytes);
+                g.srcBytes += (w.audio->Bytes() + 15u) & ~15u;
+            }
+        }
+        else if (w.pulled) {
             uint64_t first = 0, frames = 0;
             const int err = ohgpu_src_pull_window(w.pullPosFrame, w.pullPosFrac, w.pullStep, w.frames, w.pullStream->Filter().T, &first, &frames);
             ASSERT(err == OHGPU_OK);
@@ -451,7 +601,7 @@ void PlayableBatch::Run()
         for (size_t i : g.items) {
             const PlayableWork& w = iItems[i].playable->Work();
             iItems[i].outOffset = g.dstBytes;                            // (within the group, for now)
-            g.dstBytes += (TUint64)w.frames * w.channels * (iItems[i].outBits / 8);
+            g.dstBytes += w.Dsd() ? w.sizeBytes : (TUint64)w.frames * w.channels * (iItems[i].outBits / 8);
         }
         g.srcBase = srcTotal;
         g.dstBase = dstTotal;
@@ -470,10 +620,29 @@ void PlayableBatch::Run()
         for (const WindowRun& r : g.runs) {
             r.CopyFrames(src + g.srcBase + r.srcOffset);
         }
+        if (g.dsd) {
+            for (const auto& kv : sc.dsdAudioBase) {
+                memcpy(src + g.srcBase + kv.second, kv.first->Ptr(0), kv.first->Bytes());
+            }
+        }
         size_t nthResampled = 0;
         for (size_t i : g.items) {
             const PlayableWork& w = iItems[i].playable->Work();
-            if (w.pulled) {
+            if (w.Dsd()) {
+                // a playable is whole sample blocks already in the format: a copy, or 0x69.  The padding plays no part in either, so
+                // the blocks go to the device as W chunks of four bytes each (P = 0 is valid for every W)
+                ohgpu_dsd_desc d;
+                memset(&d, 0, sizeof(d));
+                ASSERT(w.sampleBlockWords <= 255 && w.sizeBytes % (w.sampleBlockWords * 4) == 0);
+                d.kind = OHGPU_DSD_PASS;
+                d.sample_block_words = (uint8_t)w.sampleBlockWords;
+                d.n_chunks = w.sizeBytes / 4;
+                d.dst_offset = iItems[i].outOffset;
+                if (w.silence) d.flags = OHGPU_DSD_FLAG_SILENCE;
+                else d.src_offset = sc.dsdAudioBase[w.audio.get()] + w.offsetBytes;
+                g.dsdDescs.push_back(d);
+            }
+            else if (w.pulled) {
                 const WindowRun& r = g.runs[g.runOf[nthResampled++]];
                 ohgpu_src_pull_msg_desc d;
                 memset(&d, 0, sizeof(d));
@@ -547,6 +716,10 @@ void PlayableBatch::Run()
             const int err = ohgpu_pcm_process_host(ctx, g.pcm.data(), g.pcm.size(), src + g.srcBase, g.srcBytes, dst + g.dstBase, g.dstBytes);
             ASSERT(err == OHGPU_OK);
         }
+        if (!g.dsdDescs.empty()) {
+            const int err = ohgpu_dsd_process_host(ctx, g.dsdDescs.data(), g.dsdDescs.size(), src + g.srcBase, g.srcBytes, dst + g.dstBase, g.dstBytes);
+            ASSERT(err == OHGPU_OK);
+        }
         if (!g.src.empty()) {
             const int err = ohgpu_src_process_host(ctx, g.filter->handle, g.src.data(), g.src.size(), src + g.srcBase, g.srcBytes,
                                                    dst + g.dstBase, g.dstBytes);
@@ -561,8 +734,26 @@ void PlayableBatch::Run()
     // ---- deliver, message by message, with the reference's callback sequence (Msg.cpp:2646-2653, 2753-2786, 2874-2893) ----
     for (size_t i = 0; i < iItems.size(); i++) {
         MsgPlayable* playable = iItems[i].playable;
-        IPcmProcessor& proc = *iItems[i].processor;
         const PlayableWork& w = playable->Work();
+        if (iItems[i].dsdProcessor != nullptr) {
+            // Msg.cpp:2655-2660, 2834-2839, 2916-2932: audible DSD is one fragment, silence comes in DecodedAudio::kMaxBytes pieces; a
+            // playable of no bytes still hands over one (empty) fragment
+            IDsdProcessor& dsd = *iItems[i].dsdProcessor;
+            dsd.BeginBlock();
+            const TByte* out = w.sizeBytes ? dst + iItems[i].outOffset : nullptr;
+            const TUint pieceBytes = w.silence ? DecodedAudio::kMaxBytes : std::max<TUint>(w.sizeBytes, 1);
+            ASSERT(!w.silence || DecodedAudio::kMaxBytes % (w.sampleBlockWords * 4) == 0);
+            TUint done = 0;
+            do {
+                const TUint n = std::min(pieceBytes, w.sizeBytes - done);
+                dsd.ProcessFragment(Brn(out + done, n), w.channels, w.sampleBlockWords);
+                done += n;
+            } while (done < w.sizeBytes);
+            dsd.EndBlock();
+            playable->RemoveRef();
+            continue;
+        }
+        IPcmProcessor& proc = *iItems[i].processor;
         const TUint subsampleBytes = iItems[i].outBits / 8;
         const TUint outFrameBytes = subsampleBytes * w.channels;
         proc.BeginBlock();
@@ -733,6 +924,28 @@ MsgAudioPcm* MsgFactory::CreateMsgAudioPcm(const Brx& aData, TUint aChannels, TU
 MsgSilence* MsgFactory::CreateMsgSilence(TUint& aSizeJiffies, TUint aSampleRate, TUint aBitDepth, TUint aChannels)
 {
     return new MsgSilence(*this, aSizeJiffies, aSampleRate, aBitDepth, aChannels);
+}
+
+MsgAudioDsd* MsgFactory::CreateMsgAudioDsd(const Brx& aData, TUint aChannels, TUint aSampleRate, TUint aSampleBlockWords,
+                                           TUint64 aTrackOffset, TUint aPadBytesPerChunk)
+{
+    // Msg.cpp:2379-2393, 2170-2183: one subsample per bit; of every W words W - P are audio
+    ASSERT(aChannels != 0 && aSampleBlockWords != 0 && aPadBytesPerChunk < aSampleBlockWords);
+    const TUint blockWordsNoPad = aSampleBlockWords - aPadBytesPerChunk;
+    const TUint playableBits = aData.Bytes() * 8 * blockWordsNoPad / aSampleBlockWords;
+    ASSERT(playableBits % aChannels == 0);
+    const TUint jiffies = playableBits / aChannels * Jiffies::PerSample(aSampleRate);
+    ASSERT(jiffies > 0);                                             // zero-length audio asserts
+    auto audio = std::make_shared<DecodedAudio>(aData);
+    MsgAudioDsd* msg = new MsgAudioDsd(*this, audio, aSampleRate, aChannels, aSampleBlockWords, blockWordsNoPad, aTrackOffset);
+    msg->iSize = jiffies;
+    msg->Measure();
+    return msg;
+}
+
+MsgSilence* MsgFactory::CreateMsgSilenceDsd(TUint& aSizeJiffies, TUint aSampleRate, TUint aChannels, TUint aSampleBlockWords, TUint aPadBytesPerChunk)
+{
+    return new MsgSilence(*this, aSizeJiffies, aSampleRate, aChannels, aSampleBlockWords, aPadBytesPerChunk);
 }
 
 MsgHalt* MsgFactory::CreateMsgHalt()

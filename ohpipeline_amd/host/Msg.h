@@ -7,6 +7,7 @@
 //   MsgAudio / MsgAudioPcm / MsgSilence   Msg.cpp:1949-2276, 2466-2560
 //   MsgPlayable (Pcm / Silence)     Msg.cpp:2591-2893
 //   IMsgProcessor, IPcmProcessor    Msg.h:1177-1240
+//   MsgAudioDsd, DSD silence and playables, IDsdProcessor   Msg.cpp:2308-2462, 2562-2586, 2816-2856, 2900-2937
 //   PipelineElement, IPipelineElementUpstream/Downstream   Msg.h:1475-1525, 1844-1856
 //   MsgFactory                      Msg.h:1987-2075
 // What differs, on purpose (MI355X-first):
@@ -131,6 +132,32 @@ private:
     std::vector<TUint> iFragments;
 };
 
+/** Used to retrieve DSD audio from a MsgPlayable (Msg.h, IDsdProcessor). */
+class IDsdProcessor {
+public:
+    virtual ~IDsdProcessor() {}
+    virtual void BeginBlock() = 0;
+    /** aData: whole sample blocks of aSampleBlockWords 32-bit words in the pipeline's DSD format */
+    virtual void ProcessFragment(const Brx& aData, TUint aNumChannels, TUint aSampleBlockWords) = 0;
+    virtual void EndBlock() = 0;
+    virtual void Flush() = 0;
+};
+
+/** Reads DSD into a growing buffer (Media/Utils/ProcessorAudioUtils.cpp, ProcessorDsdBufTest). */
+class ProcessorDsdBufTest : public IDsdProcessor {
+public:
+    Brn Buf() const { return Brn(iBuf.data(), (TUint)iBuf.size()); }
+    const std::vector<TUint>& Fragments() const { return iFragments; }
+public: // from IDsdProcessor
+    void BeginBlock() override { iBuf.clear(); iFragments.clear(); }
+    void ProcessFragment(const Brx& aData, TUint aNumChannels, TUint aSampleBlockWords) override;
+    void EndBlock() override {}
+    void Flush() override {}
+private:
+    std::vector<TByte> iBuf;
+    std::vector<TUint> iFragments;
+};
+
 /** Packed PCM as delivered by a codec; shared between the messages split from / cloned from one another. */
 class DecodedAudio {
 public:
@@ -138,6 +165,7 @@ public:
     static const TUint kMaxNumChannels = 8;
 public:
     DecodedAudio(const Brx& aData, TUint aBitDepth, AudioDataEndian aEndian);   // DecodedAudio::ConstructPcm asserts
+    explicit DecodedAudio(const Brx& aDsd);                                      // DecodedAudio::ConstructDsd: bytes in the pipeline's DSD format, depth 1
     void Aggregate(const DecodedAudio& aOther);                                  // Msg.cpp:317-323
     const TByte* Ptr(TUint aOffsetBytes) const;
     TUint Bytes() const { return (TUint)iData.size(); }
@@ -185,7 +213,6 @@ OH_TRIVIAL_MSG(MsgMetaText);
 OH_TRIVIAL_MSG(MsgStreamInterrupted);
 OH_TRIVIAL_MSG(MsgHalt);
 OH_TRIVIAL_MSG(MsgWait);
-OH_TRIVIAL_MSG(MsgAudioDsd);
 OH_TRIVIAL_MSG(MsgQuit);
 
 class MsgDelay : public Msg {                            // Msg.h:470-487
@@ -313,17 +340,57 @@ private:
     TUint iAttenuation = kUnityAttenuation;
 };
 
+/** DSD audio in the pipeline's format: sample blocks of SampleBlockWords() 32-bit words of which
+ *  PadBytesPerChunk() words' worth is padding.  Jiffies() counts the PLAYABLE samples (what a listener hears);
+ *  SizeTotalJiffies() is what the whole sample blocks under [offset, offset + size) occupy, padding included -- the figure a
+ *  driver's byte count follows -- and JiffiesNonPlayable() the difference.  Never ramped: muted, it plays 0x69. */
+class MsgAudioDsd : public MsgAudio {                    // Msg.cpp:2308-2462
+    friend class MsgFactory;
+public:
+    static const TUint64 kTrackOffsetInvalid = UINT64_MAX;
+public:
+    MsgAudioDsd();                                       // an empty message of no stream (elements that only route it need no more)
+    MsgAudio* Clone() override;
+    TUint64 TrackOffset() const { return iTrackOffset; }
+    TUint SizeTotalJiffies() const { return iSizeTotalJiffies; }
+    TUint JiffiesNonPlayable() const { return iSizeTotalJiffies - iSize; }
+    TUint SampleBlockWords() const { return iSampleBlockWords; }
+    TUint BlockWordsNoPad() const { return iBlockWordsNoPad; }
+    /** aJiffies of playable audio, rounded down to whole sample blocks (of aJiffiesPerSampleBlockPlayable), with their padding */
+    TUint JiffiesPlayableToJiffiesTotal(TUint aJiffies, TUint aJiffiesPerSampleBlockPlayable) const;
+    MsgPlayable* CreatePlayable();                       // consumes this message's reference (Msg.cpp:2340-2377)
+    Msg* Process(IMsgProcessor& aProcessor) override { return aProcessor.ProcessMsg(this); }
+private:
+    MsgAudioDsd(MsgFactory& aFactory, std::shared_ptr<DecodedAudio> aAudio, TUint aSampleRate, TUint aChannels,
+                TUint aSampleBlockWords, TUint aBlockWordsNoPad, TUint64 aTrackOffset);
+    MsgAudio* Allocate() override;
+    void SplitCompleted(MsgAudio& aRemaining) override;
+    TUint SamplesPerBlock(TUint aBlockWords) const { return aBlockWords * 32 / iNumChannels; }   // one subsample per bit
+    void Measure();                                      // iSizeTotalJiffies from iOffset / iSize
+private:
+    MsgFactory* iFactory = nullptr;
+    std::shared_ptr<DecodedAudio> iAudioData;
+    TUint iSampleBlockWords = 0, iBlockWordsNoPad = 0;
+    TUint iSizeTotalJiffies = 0;
+    TUint64 iTrackOffset = 0;
+};
+
 class MsgSilence : public MsgAudio {                     // Msg.cpp:2458-2560
     friend class MsgFactory;
 public:
+    TUint SampleBlockWords() const { return iSampleBlockWords; }   // 0: PCM silence
     MsgPlayable* CreatePlayable();
     Msg* Process(IMsgProcessor& aProcessor) override { return aProcessor.ProcessMsg(this); }
 private:
     MsgSilence(MsgFactory& aFactory, TUint& aJiffies, TUint aSampleRate, TUint aBitDepth, TUint aChannels);
+    /** DSD silence (MsgSilence::InitialiseDsd, Msg.cpp:2562-2586): whole sample blocks, jiffies counted without the padding */
+    MsgSilence(MsgFactory& aFactory, TUint& aJiffies, TUint aSampleRate, TUint aChannels, TUint aSampleBlockWords, TUint aPadBytesPerChunk);
     MsgAudio* Allocate() override;
     void SplitCompleted(MsgAudio& aRemaining) override;
 private:
     MsgFactory& iFactory;
+    TUint iSampleBlockWords = 0;                         // DSD only
+    TUint iBlockJiffiesPlayable = 0, iBlockJiffiesTotal = 0;   // a sample block without / with its padding (PCM: a sample, both)
 };
 
 /** What one MsgPlayable asks the device to do: exactly the fields of ohgpu_msg_desc / ohgpu_src_msg_desc. */
@@ -340,10 +407,13 @@ struct PlayableWork {
     TUint offsetBytes = 0, sizeBytes = 0, frames = 0;
     TUint sampleRate = 0, bitDepth = 0, channels = 0, attenuation = 256;
     Media::Ramp ramp;
+    TUint sampleBlockWords = 0;  // DSD (bitDepth == 1): `audio` holds the pipeline's DSD format, sizes are whole sample blocks, no ramp
+    TBool Dsd() const { return bitDepth == 1; }
 };
 
 class MsgPlayable : public Msg {                         // Msg.cpp:2591-2653
     friend class MsgAudioPcm;
+    friend class MsgAudioDsd;
     friend class MsgSilence;
     friend class PlayableBatch;
 public:
@@ -353,6 +423,8 @@ public:
     const Media::Ramp& Ramp() const { return iWork.ramp; }
     /** Runs this one playable on the GPU and replays the reference's callback sequence.  Prefer PlayableBatch. */
     void Read(IPcmProcessor& aProcessor);
+    /** The same for a DSD playable (Msg.cpp:2655-2660): BeginBlock, the fragments, EndBlock. */
+    void Read(IDsdProcessor& aProcessor);
     Msg* Process(IMsgProcessor& aProcessor) override { return aProcessor.ProcessMsg(this); }
     const PlayableWork& Work() const { return iWork; }
 private:
@@ -377,10 +449,13 @@ public:
     ~PlayableBatch();
     void SetOutputFormat(TUint aBitDepth, AudioDataEndian aEndian);   // 0 = keep each playable's depth
     void Add(MsgPlayable* aPlayable, IPcmProcessor& aProcessor);      // takes over the caller's reference
+    /** A DSD playable: a tick's DSD playables go out as ONE ohgpu_dsd_process_host call beside the PCM one (pass-through and 0x69
+     *  silence; SetOutputFormat does not apply); silence is replayed in DecodedAudio::kMaxBytes pieces (Msg.cpp:2925-2931). */
+    void Add(MsgPlayable* aPlayable, IDsdProcessor& aProcessor);
     void Run();                                                        // launches, waits, delivers, releases
     TUint Count() const { return (TUint)iItems.size(); }
 private:
-    struct Item { MsgPlayable* playable; IPcmProcessor* processor; TUint64 outOffset; TUint outBits; };
+    struct Item { MsgPlayable* playable; IPcmProcessor* processor; TUint64 outOffset; TUint outBits; IDsdProcessor* dsdProcessor = nullptr; };
     struct WindowRun;                                                  // consecutive items of one stream whose outputs follow on: one window
     struct Group;                                                      // the items one device call serves
     MsgFactory& iFactory;
@@ -402,6 +477,9 @@ public:
     MsgDecodedStream* CreateMsgDecodedStream(const DecodedStreamInfo& aInfo);
     MsgAudioPcm* CreateMsgAudioPcm(const Brx& aData, TUint aChannels, TUint aSampleRate, TUint aBitDepth, AudioDataEndian aEndian, TUint64 aTrackOffset);
     MsgSilence* CreateMsgSilence(TUint& aSizeJiffies, TUint aSampleRate, TUint aBitDepth, TUint aChannels);
+    /** aData: whole sample blocks in the pipeline's DSD format, as a packer's run (host/DsdPacker.h) or a DSD-native source delivers them */
+    MsgAudioDsd* CreateMsgAudioDsd(const Brx& aData, TUint aChannels, TUint aSampleRate, TUint aSampleBlockWords, TUint64 aTrackOffset, TUint aPadBytesPerChunk);
+    MsgSilence* CreateMsgSilenceDsd(TUint& aSizeJiffies, TUint aSampleRate, TUint aChannels, TUint aSampleBlockWords, TUint aPadBytesPerChunk);
     MsgHalt* CreateMsgHalt();
     MsgQuit* CreateMsgQuit();
     MsgTrack* CreateMsgTrack() { return new MsgTrack(); }

@@ -14,7 +14,7 @@
 //              3. every lane hands over its next message (rescue audio first, then the halt, then whatever the inbox holds)
 // A lane's behaviour towards ITS driver is the reference's, message for message (the reference's own suite, restated in
 // tests/cpp/test_host.cpp, runs against the one-lane facade StarvationRamper).  No PCM byte is touched on the host.
-// Left out: DSD (MsgAudioDsd passes through unramped), the observer thread (observers are called synchronously, as the
+// Left out: DSD through the flywheel (MsgAudioDsd passes through unramped: the reference does not ramp DSD either), the observer thread (observers are called synchronously, as the
 // reference's tests do with ElementObserverSync), thread priorities.
 #pragma once
 
