@@ -129,7 +129,14 @@ struct WgGeom {
     // three workgroups still share a CU -- six channels: 52 KB each to the byte -- the table of initial values holds two copies of a
     // value instead of four (read as ds_read2_b64 of the same 8 bytes twice).
     static constexpr bool kDma = kSpan;
-    static constexpr uint32_t kBiasSteps = HB ? 0 : kSteps;
+    // Stereo (24- and 16-bit) through kDma has the registers for more: a wave's tiles touch kKcSets steps, and an output's two values
+    // are the same for every pass of the launch -- they stay in 8 kKcSets registers as the matrix instructions' C operands, like the
+    // half-band form's, and there is no table to fill or to read (kBiasRegs: two ds_read2_b64 a tile less, a quarter of the tiles'
+    // LDS cycles; -2 % on the headline, -4 % on config 4's stereo group).  Six channels would spill with them (168 registers, 16 bytes
+    // of scratch); eight channels fit (159 registers) and ran 7.6 % SLOWER (config 4's group 1.415 -> 1.523 ms, same box, two
+    // alternating pairs): both keep the table.
+    static constexpr bool kBiasRegs = kDma && PAIRS == 1;
+    static constexpr uint32_t kBiasSteps = HB || kBiasRegs ? 0 : kSteps;
     static constexpr uint32_t kBiasCopies = kDma ? 2 : 4;
     static constexpr uint32_t kBiasStep = 128 * kBiasCopies;          // [b0, b1][output 16][copies] dwords
     static constexpr uint32_t kBiasBytes = kBiasSteps * kBiasStep;
@@ -216,6 +223,17 @@ void src_mfma_wg_kernel(const LeanUnit* __restrict__ units, const uint32_t n_wor
             for (int j = 0; j < 4; j++) a[q < (int)G::kASets ? q : 0][j] = *(const v4i*)(amat + ((uint64_t)image * kMfStepImage + j * 1024u + lane * 16u));
         }
         kc[q] = steps[st].kc;
+    }
+    // (kBiasRegs: ... and the initial values of its outputs in those steps)
+    v4i bq0[G::kBiasRegs ? G::kKcSets : 1], bq2[G::kBiasRegs ? G::kKcSets : 1];
+    if constexpr (G::kBiasRegs) {
+#pragma unroll
+        for (int q = 0; q < (int)G::kKcSets; q++) {
+            const uint32_t st = step0 + q < G::kSteps ? step0 + q : G::kSteps - 1u;
+            const int v0 = (int)steps[st].b0[lane & 15u], v1 = (int)steps[st].b1[lane & 15u];
+            bq0[q] = v4i{v0, v0, v0, v0};
+            bq2[q] = v4i{v1, v1, v1, v1};
+        }
     }
 
     // ---- lane roles ----
@@ -461,9 +479,9 @@ void src_mfma_wg_kernel(const LeanUnit* __restrict__ units, const uint32_t n_wor
         for (uint32_t k = 0; k * G::kThreads < kTasks; k++)
             if (k * G::kThreads + tid < kTasks) split_hb_task(k * G::kThreads + tid, kFirstChunk, kByte0, first);
     };
-    auto split_task = [&](uint32_t hc, bool first) __attribute__((always_inline)) {
-        // the stream's block 0: the frames before it (chunks 0 and 1 of row 0) read as zeros
-        const bool zero = first && sp_srow == 0 && hc < 4u;
+    auto split_task = [&](uint32_t hc, auto first) __attribute__((always_inline)) {
+        // the stream's block 0: the frames before it (chunks 0 and 1 of row 0) read as zeros (`first`: a bool, or a constant -- split_all)
+        const bool zero = (bool)first && sp_srow == 0 && hc < 4u;
         uint32_t pl[6][2];                                  // [3 * channel + byte of the 24-bit sample, least significant first... in memory order for packed][frames 0-3, 4-7]
         if constexpr (G::kS16) {
             // 16-bit stereo: a frame is one dword {L lo, L hi, R lo, R hi} (or hi first); a 4 x 4 byte transpose per four frames gives the
@@ -556,8 +574,17 @@ void src_mfma_wg_kernel(const LeanUnit* __restrict__ units, const uint32_t n_wor
         }
     };
     auto split_all = [&](bool first) __attribute__((always_inline)) {
-        split_task(sp_hc0, first);
-        if (sp_hc0 < 8u) split_task(sp_hc0 + 16u, first);
+        // (kDma: only a stream's first pass has frames to zero, and `first` is the same for the whole workgroup -- every other pass runs
+        // a copy of the first round's task without its twelve selects; the second round's half chunks, 16.., never have any.  The
+        // row-by-row forms have no registers for a second copy: the planar ones would spill)
+        if constexpr (G::kDma) {
+            if (first) split_task(sp_hc0, std::true_type{});
+            else split_task(sp_hc0, std::false_type{});
+            if (sp_hc0 < 8u) split_task(sp_hc0 + 16u, std::false_type{});
+        } else {
+            split_task(sp_hc0, first);
+            if (sp_hc0 < 8u) split_task(sp_hc0 + 16u, first);
+        }
     };
     // a pass's input, from the registers it arrived in to the planes
     auto stage_and_split = [&](const u32x4 (&raw)[G::kInRounds], bool first) __attribute__((always_inline)) {
@@ -725,9 +752,10 @@ void src_mfma_wg_kernel(const LeanUnit* __restrict__ units, const uint32_t n_wor
                 const v4i (&c)[4] = a[HB ? 0 : set];
                 if constexpr (kHas) {
                     const uint8_t* const bi = my_bias + (step0 + set) * G::kBiasStep;
-                    if constexpr (G::kDma) read_bias2(bi, s0, s2);         // (in front of the wait in take_planes)
+                    if constexpr (G::kDma && !G::kBiasRegs) read_bias2(bi, s0, s2);   // (in front of the wait in take_planes)
                     take_planes(h, bd);
                     if constexpr (HB) { s0 = hb_s0; s2 = hb_s2; }
+                    else if constexpr (G::kBiasRegs) { s0 = bq0[set]; s2 = bq2[set]; }
                     else if constexpr (!G::kDma) { s0 = *(const v4i*)bi; s2 = *(const v4i*)(bi + G::kBiasStep / 2); }
                     s0 = MFMA_I8(bd[0], c[0], s0);
                     s1 = MFMA_I8(bd[0], c[1], s1);
