@@ -25,6 +25,8 @@
  *   MsgPlayableDsd::ReadBlock (Msg.cpp:2834-2839)                        OHGPU_DSD_PASS
  *   MsgPlayableSilenceDsd::ReadBlock (Msg.cpp:2916-2932), muted DSD       OHGPU_DSD_FLAG_SILENCE
  *       (Msg.cpp:2360-2373)
+ *   CodecFlac + libFLAC: frames found, entropy-decoded, restored            ohgpu_flac_batch_run()
+ *       (Codec/Flac.cpp:355-443; thirdparty/flac-1.2.1 by its format document)   -> TInt32 planes or CallbackWrite's packed bytes
  *   "SampleRateConverter" -- NOT PRESENT in the reference  ohgpu_src_* (own spec)
  *
  * The reference binds nothing through FFI today (it is one C++ static library); INTEGRATION.md
@@ -296,6 +298,97 @@ int ohgpu_dsd_batch_paths(const ohgpu_batch* batch, uint32_t* wide_descs, uint32
  * that no descriptor covers preserved, counted in ohgpu_host_transfer_stats. */
 int ohgpu_dsd_process_host(ohgpu_ctx* ctx, const ohgpu_dsd_desc* descs, size_t n,
                            const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes);
+
+/* ---- FLAC: native frames decoded on the device ----
+ * Stands where libFLAC stands under CodecFlac (Codec/Flac.cpp): file bytes in, and out either the planar TInt32 frames
+ * CallbackWrite is handed (what OHGPU_FLAG_SRC_PLANAR32 reads) or the packed big-endian bytes that callback makes of them.
+ * A descriptor is one stream's byte range; its frames are FOUND (they carry no length): every byte position whose header is legal
+ * and whose CRC-8 matches is a candidate, every candidate is parsed to its end (CRC-16), and the chain takes the lowest candidate
+ * that parses -- with OHGPU_FLAC_FLAG_AT_FRAME the one at src_offset -- and then, each time, the candidate that starts exactly where
+ * the last frame ended, has the descriptor's channels, depth and rate, and carries the next number.  The chain stops with
+ * OHGPU_FLAC_OK where the range ends or cuts a frame short (bytes_consumed = where to resume), with OHGPU_FLAC_CORRUPT at bytes that
+ * are no such frame (CodecFlac::CallbackError, Flac.cpp:421-425), OHGPU_FLAC_UNSUPPORTED at a frame of 12 or 20 bits, and with
+ * OHGPU_FLAC_OVERFLOW at a frame that would land outside [0, max_samples): frames in front of the stop are delivered, nothing
+ * behind it is written.  A frame's place is its own first sample number (frame number x blocksize under fixed blocking) minus
+ * first_sample.  Bit depths 8, 16, 24; 1..8 channels; every subframe type, both Rice codings, escapes, wasted bits. */
+#define OHGPU_FLAC_OK          0u
+#define OHGPU_FLAC_CORRUPT     1u
+#define OHGPU_FLAC_UNSUPPORTED 2u
+#define OHGPU_FLAC_OVERFLOW    3u
+#define OHGPU_FLAC_FLAG_AT_FRAME  0x01u  /* the first frame starts at src_offset (a caller resuming at bytes_consumed) */
+#define OHGPU_FLAC_OUT_PACKED_BE  0x02u  /* interleaved big-endian at bits / 8 bytes at dst_offset, instead of the planes */
+
+typedef struct ohgpu_flac_streaminfo_t {    /* 48 bytes: the STREAMINFO block */
+    uint32_t min_blocksize, max_blocksize;
+    uint32_t sample_rate;
+    uint8_t  channels, bits, reserved[2];
+    uint64_t total_samples;
+    uint8_t  md5[16];
+    uint32_t min_framesize, max_framesize;
+} ohgpu_flac_streaminfo_t;
+
+typedef struct ohgpu_flac_stream_desc {     /* 64 bytes */
+    uint64_t src_offset;            /* the stream's bytes: [src_offset, src_offset + src_bytes) of the source arena, any alignment */
+    uint64_t src_bytes;             /* < 2^31 */
+    uint64_t dst_offset;            /* multiple of 4 */
+    uint64_t dst_plane_stride;      /* planes: bytes between the channels' planes, multiple of 4, >= max_samples * 4; packed: 0 */
+    uint64_t first_sample;          /* the stream's sample that goes to index 0 of the output */
+    uint32_t max_samples;           /* the output holds samples [first_sample, first_sample + max_samples) */
+    uint32_t sample_rate;           /* STREAMINFO's */
+    uint32_t blocksize;             /* fixed blocking: the stream's block size; 0 = the chain's first frame's */
+    uint32_t max_blocksize;         /* STREAMINFO's, 16..65535: a larger frame is no frame */
+    uint8_t  channels;              /* 1..8 */
+    uint8_t  bits;                  /* 8, 16, 24 */
+    uint8_t  flags;                 /* OHGPU_FLAC_FLAG_AT_FRAME | OHGPU_FLAC_OUT_PACKED_BE */
+    uint8_t  reserved[5];           /* zero */
+} ohgpu_flac_stream_desc;
+
+typedef struct ohgpu_flac_stream_result {   /* 48 bytes */
+    uint32_t status;                /* OHGPU_FLAC_* */
+    uint32_t frames;                /* frames delivered */
+    uint64_t samples;               /* ... and their samples (per channel) */
+    uint64_t first_sample_decoded;  /* the first delivered frame's first sample number */
+    uint64_t bytes_consumed;        /* from src_offset: what lies behind is for the next call */
+    uint32_t candidates;            /* headers with a matching CRC-8 in the range */
+    uint32_t candidates_rejected;   /* ... that did not become frames */
+    uint64_t reserved;
+} ohgpu_flac_stream_result;
+
+typedef struct ohgpu_flac_frame {           /* 24 bytes: one delivered frame */
+    uint32_t stream;                /* index of its descriptor */
+    uint32_t blocksize;
+    uint64_t first_sample;          /* its first sample number in the stream */
+    uint32_t src_pos, src_end;      /* its bytes, from the descriptor's src_offset */
+} ohgpu_flac_frame;
+
+/* Host only, no device needed: "fLaC", the metadata blocks, STREAMINFO; *audio_offset = where the first frame starts.
+ * OHGPU_ERR_INVALID: bad magic, no STREAMINFO in front, or the n bytes end inside the metadata. */
+int ohgpu_flac_streaminfo(const void* bytes, size_t n, ohgpu_flac_streaminfo_t* info, uint64_t* audio_offset);
+/* Host only, no device needed: the validation ohgpu_flac_batch_create makes, with its codes and ohgpu_last_error() texts. */
+int ohgpu_flac_batch_check(const ohgpu_flac_stream_desc* descs, size_t n, uint64_t src_arena_bytes, uint64_t dst_arena_bytes);
+/* Validated on the host (ranges against the arenas: OHGPU_ERR_BOUNDS; alignment, channels, overlapping planes: OHGPU_ERR_INVALID;
+ * a depth other than 8/16/24: OHGPU_ERR_UNSUPPORTED); freed with ohgpu_batch_destroy.  The batch owns its results and, from its
+ * first run on, its scratch: it runs on one stream at a time. */
+int ohgpu_flac_batch_create(ohgpu_ctx* ctx, const ohgpu_flac_stream_desc* descs, size_t n,
+                            uint64_t src_arena_bytes, uint64_t dst_arena_bytes, ohgpu_batch** batch);
+/* Scan, probe, chain, restore.  The number of candidates is only known after the scan, so this call SYNCHRONISES with the host
+ * between its phases (once, after the scan; the rest is queued on the stream).  Scratch -- the candidates' residuals, bounded by
+ * max_blocksize x channels each -- is kept by the batch and its small arrays come from the context's block cache: a second run of
+ * the same shape allocates nothing (ohgpu_device_allocations).  Under ohgpu_set_kernel_variant(1) the restore is the plain route:
+ * one thread per accepted frame, everything straight from the bytes. */
+int ohgpu_flac_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* src_base, void* dst_base, void* stream);
+/* The last run's per-stream results (waits for that run); n = the batch's descriptor count. */
+int ohgpu_flac_batch_results(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_flac_stream_result* results, size_t n);
+/* The last run's delivered frames, by stream and then in stream order (waits for that run): up to `capacity` of them are written,
+ * *n_frames is how many there are. */
+int ohgpu_flac_batch_frames(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_flac_frame* frames, size_t capacity, size_t* n_frames);
+/* The last run's phases in milliseconds from device events: scan, probe, chain, restore (waits for that run). */
+int ohgpu_flac_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float ms[4]);
+/* Host-buffer convenience, as ohgpu_dsd_process_host: one upload, one run.  Of dst_host only the samples that were decoded are
+ * written.  results (n of them) and frames (as ohgpu_flac_batch_frames) may be NULL. */
+int ohgpu_flac_process_host(ohgpu_ctx* ctx, const ohgpu_flac_stream_desc* descs, size_t n,
+                            const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes,
+                            ohgpu_flac_stream_result* results, ohgpu_flac_frame* frames, size_t frames_capacity, size_t* n_frames);
 
 /* ---- FlywheelRamper ----
  * Replaces FlywheelRamperManager::Ramp (OpenHome/Media/FlywheelRamper.cpp:44-66; per channel FlywheelRamper::Initialise

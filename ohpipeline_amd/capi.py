@@ -57,6 +57,23 @@ DSD_DESC = np.dtype([
     ("sample_block_words", "u1"), ("pad_bytes_per_chunk", "u1"), ("reserved", "u1", (8,))], align=False)
 assert DSD_DESC.itemsize == 32
 
+# FLAC frames: ohgpu_flac_stream_desc (64 B), ohgpu_flac_stream_result (48 B), ohgpu_flac_streaminfo_t (48 B)
+FLAC_OK, FLAC_CORRUPT, FLAC_UNSUPPORTED, FLAC_OVERFLOW = 0, 1, 2, 3
+FLAC_FLAG_AT_FRAME, FLAC_OUT_PACKED_BE = 1, 2
+FLAC_STREAM_DESC = np.dtype([
+    ("src_offset", "<u8"), ("src_bytes", "<u8"), ("dst_offset", "<u8"), ("dst_plane_stride", "<u8"), ("first_sample", "<u8"),
+    ("max_samples", "<u4"), ("sample_rate", "<u4"), ("blocksize", "<u4"), ("max_blocksize", "<u4"),
+    ("channels", "u1"), ("bits", "u1"), ("flags", "u1"), ("reserved", "u1", (5,))], align=False)
+FLAC_STREAM_RESULT = np.dtype([
+    ("status", "<u4"), ("frames", "<u4"), ("samples", "<u8"), ("first_sample_decoded", "<u8"), ("bytes_consumed", "<u8"),
+    ("candidates", "<u4"), ("candidates_rejected", "<u4"), ("reserved", "<u8")], align=False)
+FLAC_STREAMINFO = np.dtype([
+    ("min_blocksize", "<u4"), ("max_blocksize", "<u4"), ("sample_rate", "<u4"), ("channels", "u1"), ("bits", "u1"),
+    ("reserved", "u1", (2,)), ("total_samples", "<u8"), ("md5", "u1", (16,)), ("min_framesize", "<u4"), ("max_framesize", "<u4")], align=False)
+FLAC_FRAME = np.dtype([("stream", "<u4"), ("blocksize", "<u4"), ("first_sample", "<u8"), ("src_pos", "<u4"), ("src_end", "<u4")], align=False)
+assert FLAC_FRAME.itemsize == 24
+assert FLAC_STREAM_DESC.itemsize == 64 and FLAC_STREAM_RESULT.itemsize == 48 and FLAC_STREAMINFO.itemsize == 48
+
 BATCH_PATHS = np.dtype([(k, "<u4") for k in ("line_planned", "launches", "staged_chunks", "group_chunks", "heavy_chunks",
                                             "prefixed_chunks", "ohm_wide_fragments", "ohm_staged_fragments", "ohm_headers_fused",
                                             "ohm_headers_separate", "fmt_wide_records", "fmt_stereo_records", "fmt_stereo_kind",
@@ -122,6 +139,14 @@ SYMBOLS = {
     "ohgpu_dsd_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "ohgpu_dsd_batch_paths": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "ohgpu_dsd_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64]),
+    "ohgpu_flac_streaminfo": (C.c_int, [_vp, C.c_size_t, _vp, _u64p]),
+    "ohgpu_flac_batch_check": (C.c_int, [_vp, C.c_size_t, C.c_uint64, C.c_uint64]),
+    "ohgpu_flac_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
+    "ohgpu_flac_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "ohgpu_flac_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_flac_batch_frames": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ohgpu_flac_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
+    "ohgpu_flac_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "ohgpu_flywheel_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
     "ohgpu_flywheel_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "ohgpu_flywheel_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64]),
@@ -294,6 +319,24 @@ def dsd_layout(kind, sample_block_words, pad_bytes_per_chunk, n_chunks):
     s, d = C.c_uint64(0), C.c_uint64(0)
     check(lib().ohgpu_dsd_layout(kind, sample_block_words, pad_bytes_per_chunk, n_chunks, C.byref(s), C.byref(d)))
     return int(s.value), int(d.value)
+
+
+def flac_streaminfo(stream):
+    """(STREAMINFO as a dict, offset of the first frame) of a FLAC stream's first bytes (ohgpu_flac_streaminfo; host only)."""
+    buf = np.frombuffer(bytes(stream), dtype=np.uint8)
+    info = np.zeros(1, dtype=FLAC_STREAMINFO)
+    off = C.c_uint64(0)
+    check(lib().ohgpu_flac_streaminfo(buf.ctypes.data_as(C.c_void_p), buf.size, info.ctypes.data_as(C.c_void_p), C.byref(off)))
+    i = info[0]
+    return ({k: int(i[k]) for k in ("min_blocksize", "max_blocksize", "sample_rate", "channels", "bits", "total_samples",
+                                    "min_framesize", "max_framesize")} | {"md5": bytes(i["md5"])}, int(off.value))
+
+
+def flac_batch_check(descs, src_arena_bytes, dst_arena_bytes):
+    """The validation of ctx.flac_batch without a device (ohgpu_flac_batch_check): OhGpuError on a bad descriptor."""
+    d = np.ascontiguousarray(descs)
+    assert d.dtype == FLAC_STREAM_DESC
+    check(lib().ohgpu_flac_batch_check(d.ctypes.data_as(C.c_void_p), d.size, src_arena_bytes, dst_arena_bytes))
 
 
 class Context:
@@ -469,6 +512,48 @@ class Context:
                                            src.ctypes.data_as(C.c_void_p), src.nbytes,
                                            dst.ctypes.data_as(C.c_void_p), dst.nbytes))
         return dst
+
+    def flac_batch(self, descs, src_arena_bytes, dst_arena_bytes):
+        d = np.ascontiguousarray(descs)
+        assert d.dtype == FLAC_STREAM_DESC
+        b = C.c_void_p()
+        check(lib().ohgpu_flac_batch_create(self._h, d.ctypes.data_as(C.c_void_p), d.size, src_arena_bytes,
+                                            dst_arena_bytes, C.byref(b)))
+        return b
+
+    def flac_run(self, batch, d_src, d_dst, stream=None):
+        """Scan, probe, chain, restore (ohgpu_flac_batch_run): synchronises with the host once, after the scan."""
+        check(lib().ohgpu_flac_batch_run(self._h, batch, d_src, d_dst, stream))
+
+    def flac_results(self, batch, n):
+        """The last run's FLAC_STREAM_RESULT per stream (waits for the run)."""
+        res = np.zeros(n, dtype=FLAC_STREAM_RESULT)
+        check(lib().ohgpu_flac_batch_results(self._h, batch, res.ctypes.data_as(C.c_void_p), n))
+        return res
+
+    def flac_frames(self, batch):
+        """The last run's delivered frames (FLAC_FRAME), by stream and in stream order."""
+        n = C.c_size_t(0)
+        check(lib().ohgpu_flac_batch_frames(self._h, batch, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=FLAC_FRAME)
+        check(lib().ohgpu_flac_batch_frames(self._h, batch, out.ctypes.data_as(C.c_void_p), out.size, C.byref(n)))
+        return out
+
+    def flac_phase_ms(self, batch):
+        """The last run's (scan, probe, chain, restore) in milliseconds, from device events."""
+        ms = (C.c_float * 4)()
+        check(lib().ohgpu_flac_batch_phase_ms(self._h, batch, ms))
+        return tuple(float(v) for v in ms)
+
+    def flac_process_host(self, descs, src, dst):
+        """Host buffers in and out (ohgpu_flac_process_host); returns the results.  Only decoded samples are written to dst."""
+        d = np.ascontiguousarray(descs)
+        assert d.dtype == FLAC_STREAM_DESC
+        res = np.zeros(d.size, dtype=FLAC_STREAM_RESULT)
+        check(lib().ohgpu_flac_process_host(self._h, d.ctypes.data_as(C.c_void_p), d.size,
+                                            src.ctypes.data_as(C.c_void_p), src.nbytes,
+                                            dst.ctypes.data_as(C.c_void_p), dst.nbytes, res.ctypes.data_as(C.c_void_p), None, 0, None))
+        return res
 
     def flywheel_batch(self, descs, src_arena_bytes, dst_arena_bytes):
         d = np.ascontiguousarray(descs)

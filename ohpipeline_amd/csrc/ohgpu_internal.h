@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/ohgpu.h"
+#include "flac_frame_core.h"
 
 namespace ohgpu {
 
@@ -50,6 +51,8 @@ static_assert(sizeof(ohgpu_src_msg_desc) == 64, "ohgpu_src_msg_desc layout");
 static_assert(sizeof(ohgpu_fmt_desc) == 48, "ohgpu_fmt_desc layout");
 static_assert(sizeof(ohgpu_batch_paths) == 64, "ohgpu_batch_paths layout");
 static_assert(sizeof(ohgpu_dsd_desc) == 32, "ohgpu_dsd_desc layout");
+static_assert(sizeof(ohgpu_flac_stream_desc) == 64 && sizeof(ohgpu_flac_stream_result) == 48 && sizeof(ohgpu_flac_streaminfo_t) == 48 && sizeof(ohgpu_flac_frame) == 24, "FLAC layouts");
+static_assert(sizeof(flaccore::Result) == sizeof(ohgpu_flac_stream_result) && sizeof(flaccore::Stream) == 64 && sizeof(flaccore::Probe) == 56 && sizeof(flaccore::Sub) == 80, "FLAC device layouts");
 
 // ---- block ("fast") resampler plan: contiguous runs of output messages cut into phase-aligned blocks ----
 struct SrcSeg {               // one contiguous run of output messages of one stream
@@ -332,7 +335,32 @@ struct OhmPlan {
     uint32_t n_unfolded = 0, n_unfolded_generic = 0;
 };
 
-enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7 };
+// ---- FLAC frames (csrc/flac_frame_kernel.hip): what a batch keeps between runs; the batch's d_descs holds nothing ----
+struct FlacScanTile { uint32_t stream, pos0; };       // one workgroup's share of the scan: positions [pos0, pos0 + 1024) of a stream
+struct FlacState {
+    std::vector<flaccore::Stream> streams;            // the descriptors (cand_first / cand_count are each run's)
+    uint32_t n_tiles = 0, max_blocksize = 0;
+    void* d_tables = nullptr;                         // flaccore::Tables
+    void* d_tiles = nullptr;                          // FlacScanTile[n_tiles]
+    void* d_streams = nullptr;                        // flaccore::Stream[n]
+    void* d_results = nullptr;                        // flaccore::Result[n]
+    void* d_counter = nullptr;                        // uint32: candidates the scan found
+    // grown when a run needs more, kept otherwise
+    void* d_list = nullptr;   size_t list_cap = 0;    // uint2 (stream, pos), in the scan's order
+    void* d_probes = nullptr; size_t probes_cap = 0;  // flaccore::Probe, sorted
+    void* d_rowcand = nullptr; void* d_subs = nullptr; size_t rows_cap = 0;   // per row (candidate, channel): its candidate; flaccore::Sub
+    void* d_rows = nullptr;   size_t rows_words = 0;  // int32 [rows][max_blocksize]
+    bool  rows_cached = false;                        // ... from the context's block cache (else hipMalloc'ed)
+    std::vector<flaccore::Probe> host_probes;
+    std::vector<uint32_t> host_rowcand;
+    std::vector<uint32_t> host_list;
+    hipEvent_t ev[5] = {};
+    hipStream_t last_stream = nullptr;
+    bool ran = false;
+    uint32_t n_candidates = 0;
+};
+
+enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8 };
 
 }  // namespace ohgpu
 
@@ -428,6 +456,7 @@ struct ohgpu_batch {
     ohgpu::FmtLinePlan fmtline;   // kBatchFmt only
     ohgpu::OhmPlan ohm;           // kBatchOhm only
     ohgpu::DsdPlan dsd;           // kBatchDsd only
+    ohgpu::FlacState* flac = nullptr;   // kBatchFlac only (what a run changes lives behind the pointer: a run takes a const batch)
     void*    d_pull_tiles = nullptr;   // kBatchSrcPull: PullTile[n_pull_tiles] on the device (d_descs holds the messages)
     uint32_t n_pull_tiles = 0;
     // kBatchSrc whose messages differ in layout: one uniform batch per layout (each with its own block-kernel plan), run one
@@ -472,6 +501,12 @@ int plan_dsd_line(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_dsd_desc* descs, s
 void free_dsd_line(ohgpu_ctx* ctx, ohgpu_batch* b);
 hipError_t launch_dsd_line(const ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
 hipError_t launch_dsd_v1(const ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
+// csrc/flac_frame_kernel.hip
+int  flac_plan(ohgpu_ctx* ctx, ohgpu_batch* b);                       // the device side of a validated batch (b->flac->streams is filled)
+void flac_free(ohgpu_ctx* ctx, ohgpu_batch* b);
+int  flac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s, bool plain);
+int  flac_results(ohgpu_ctx* ctx, const ohgpu_batch* b, ohgpu_flac_stream_result* out);
+int  flac_frames(ohgpu_ctx* ctx, const ohgpu_batch* b, ohgpu_flac_frame* out, size_t capacity, size_t* n_frames);
 // csrc/ohm_frame_kernel.hip: the two wire channels of streams wider than stereo (Sender::DoProcessFragment), one record per fragment
 OhmSelRec wide_record(uint64_t src_off, uint64_t dst_off, uint32_t n_frames, uint32_t channels, uint32_t sb, bool little, uint64_t src_arena_bytes);
 hipError_t launch_ohm_wide(const ohgpu_ctx* ctx, const void* d_recs, uint32_t n_recs, const uint8_t* src, uint8_t* dst, const uint8_t* prefix, hipStream_t s);

@@ -19,6 +19,7 @@ namespace OpenHome {
 namespace Media {
 
 OH_EXCEPTION(CodecStreamFeatureUnsupported);
+OH_EXCEPTION(CodecStreamCorrupt);
 
 class DecodedAudioAggregator : public PipelineElement, public IPipelineElementDownstream {
 public:
