@@ -16,11 +16,10 @@
 
 #include <algorithm>
 #include <cstring>
-#include <new>
 #include <type_traits>
 #include <vector>
 
-#include "ohgpu_internal.h"
+#include "api_common.h"
 #include "pcm_device.h"
 
 namespace ohgpu {
@@ -332,8 +331,7 @@ int ohgpu_ohm_batch_create(ohgpu_ctx* ctx, const ohgpu_ohm_stream* streams, size
                            const ohgpu_ohm_fragment* fragments, size_t n_fragments,
                            uint64_t src_arena_bytes, uint64_t dst_arena_bytes, ohgpu_batch** out)
 {
-    if (!ctx) return set_error(OHGPU_ERR_INVALID, "ohgpu_ohm_batch_create: null context");
-    OHGPU_HIP_TRY(hipSetDevice(ctx->device));
+    CTX_GUARD("ohgpu_ohm_batch_create");
     if (!out || (n_streams && !streams) || (n_frames && !frames) || (n_fragments && !fragments))
         return set_error(OHGPU_ERR_INVALID, "ohgpu_ohm_batch_create: null argument");
     *out = nullptr;
@@ -497,18 +495,14 @@ int ohgpu_ohm_batch_create(ohgpu_ctx* ctx, const ohgpu_ohm_stream* streams, size
         dst_written += frame_bytes;
     }
 
-    ohgpu_batch* b = new (std::nothrow) ohgpu_batch();
-    if (!b) return set_error(OHGPU_ERR_NOMEM, "ohgpu_ohm_batch_create: out of host memory");
-    b->kind = kBatchOhm;
-    b->n = n_frames;
-    b->src_arena_bytes = src_arena_bytes;
-    b->dst_arena_bytes = dst_arena_bytes;
+    BatchPtr b;     // (the arguments and the counts' caps were checked above)
+    int err = batch_begin(ctx, "ohgpu_ohm_batch_create", kBatchOhm, true, n_frames, UINT64_MAX, src_arena_bytes, dst_arena_bytes, out, &b);
+    if (err != OHGPU_OK) return err;
     b->in_frames = b->out_frames = in_frames;
     b->src_bytes_touched = src_touched;
     b->dst_bytes_written = dst_written;
     OhmPlan& plan = b->ohm;
     plan.n_frames = (uint32_t)n_frames;
-    int err = OHGPU_OK;
     auto dev_copy = [&](void** d, const void* h, size_t bytes) -> int {
         if (bytes == 0) return OHGPU_OK;
         hipError_t e = hipMalloc(d, bytes);
@@ -544,20 +538,15 @@ int ohgpu_ohm_batch_create(ohgpu_ctx* ctx, const ohgpu_ohm_stream* streams, size
     if (err == OHGPU_OK) err = dev_copy(&plan.d_wide_prefix, wide_blob.data(), wide_blob.size());
     if (err == OHGPU_OK) err = dev_copy(&plan.d_frames, recs.data(), recs.size() * sizeof(OhmFrameRec));
     if (err == OHGPU_OK) err = dev_copy(&plan.d_streams, stream_recs.data(), stream_recs.size());
-    if (err != OHGPU_OK) { free_ohm(ctx, b); delete b; return err; }
-    *out = b;
-    return OHGPU_OK;
+    return batch_done(err, b, out);
 }
 
 int ohgpu_ohm_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* src_base, void* dst_base, void* stream)
 {
-    if (!ctx) return set_error(OHGPU_ERR_INVALID, "ohgpu_ohm_batch_run: null context");
-    OHGPU_HIP_TRY(hipSetDevice(ctx->device));
-    if (!batch || batch->kind != kBatchOhm) return set_error(OHGPU_ERR_INVALID, "ohgpu_ohm_batch_run: not a Songcast frame batch");
-    if (batch->n == 0) return OHGPU_OK;
-    if (!dst_base || (!src_base && batch->src_bytes_touched)) return set_error(OHGPU_ERR_INVALID, "ohgpu_ohm_batch_run: null arena pointer");
+    const int go = run_guard(ctx, "ohgpu_ohm_batch_run", batch, kBatchOhm, batch && batch->n == 0, true, src_base, dst_base);
+    if (go <= 0) return go;
     const OhmPlan& p = batch->ohm;
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t s = pick_stream(ctx, stream);
     int err = OHGPU_OK;
     if (p.direct) err = ohgpu_pcm_batch_run(ctx, p.direct, src_base, dst_base, s);
     if (err == OHGPU_OK && p.stage) err = ohgpu_pcm_batch_run(ctx, p.stage, src_base, p.d_scratch, s);
@@ -582,21 +571,15 @@ int ohgpu_ohm_process_host(ohgpu_ctx* ctx, const ohgpu_ohm_stream* streams, size
                            const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes)
 {
     ohgpu_batch* b = nullptr;
-    int err = ohgpu_ohm_batch_create(ctx, streams, n_streams, frames, n_frames, fragments, n_fragments, src_bytes, dst_bytes, &b);
+    const int err = ohgpu_ohm_batch_create(ctx, streams, n_streams, frames, n_frames, fragments, n_fragments, src_bytes, dst_bytes, &b);
     if (err != OHGPU_OK) return err;
     // (a frame's datagram = header + the audio of its fragments: the bytes the call hands back; bytes no frame covers stay as given)
-    std::vector<std::pair<uint64_t, uint64_t>> out(n_frames);
-    for (size_t i = 0; i < n_frames && err == OHGPU_OK; i++) {
+    return process_host(ctx, b, n_frames, src_host, src_bytes, dst_host, dst_bytes, ohgpu_ohm_batch_run, [&](size_t i) {
         uint32_t samples = 0, header = 0, total = 0;
         for (uint32_t k = 0; k < frames[i].n_fragments; k++) samples += fragments[frames[i].first_fragment + k].n_frames;
-        err = ohgpu_ohm_frame_layout(&streams[frames[i].stream], samples, &header, &total);
-        out[i] = {frames[i].dst_offset, total};
-    }
-    if (err == OHGPU_OK)
-        err = ohgpu::host_roundtrip(ctx, src_host, src_bytes, dst_host, dst_bytes, out,
-                                    [&](const void* d_src, void* d_dst) { return ohgpu_ohm_batch_run(ctx, b, d_src, d_dst, nullptr); });
-    ohgpu_batch_destroy(ctx, b);
-    return err;
+        (void)ohgpu_ohm_frame_layout(&streams[frames[i].stream], samples, &header, &total);     // (the create has checked the same)
+        return std::make_pair(frames[i].dst_offset, (uint64_t)total);
+    });
 }
 
 }  // extern "C"

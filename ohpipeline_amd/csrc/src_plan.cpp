@@ -13,8 +13,8 @@
 #include <utility>
 #include <vector>
 
-#include "ohgpu_internal.h"
 #include "src_block_common.h"
+#include "src_plan.h"
 
 namespace ohgpu {
 

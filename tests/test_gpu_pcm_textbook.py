@@ -8,7 +8,7 @@ Every test first asks ohgpu_batch_paths_info which path the planner chose (stage
 attenuated "heavy") and asserts it, then runs under both kernel variants (`vctx`: the tuned line kernel, and variant 1 = the
 generic kernel of csrc/pcm_kernels.hip, which must give the same bytes from the same batch description).
 
-The largest message: ohgpu_pcm_batch_create states no cap of its own -- validate_msg (csrc/ohgpu_api.hip) bounds a message by its
+The largest message: ohgpu_pcm_batch_create states no cap of its own -- validate_msg (csrc/api_pcm.hip) bounds a message by its
 arenas, by n_frames < 2^32 and, when ramped, by n_frames <= 131071 (the reference's TInt ramp product, Msg.cpp:835) -- so messages
 beyond the reference's 9216-byte cell are part of the contract and are tested here against the model directly
 (test_messages_beyond_the_reference_cell).  Prefixes are not reachable through ohgpu_pcm_batch_create (only the Songcast frame

@@ -1,5 +1,5 @@
 """The resampler's host planner cuts a batch's streams into work units on several threads (ohpipeline_amd/csrc/src_plan.cpp,
-ohgpu_api.hip: the per-message checks, the ordering test, the segments).  The plan must not depend on how many: this compares
+api_src.hip: the per-message checks, the ordering test, the segments).  The plan must not depend on how many: this compares
 `ohgpu_src_plan_digest` -- the unit list, ramp jobs and generic-kernel pieces hashed on the host, no device -- across thread
 counts, message orders and kernel variants.  CPU only."""
 import numpy as np
