@@ -299,6 +299,73 @@ int ohgpu_dsd_batch_paths(const ohgpu_batch* batch, uint32_t* wide_descs, uint32
 int ohgpu_dsd_process_host(ohgpu_ctx* ctx, const ohgpu_dsd_desc* descs, size_t n,
                            const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes);
 
+/* ---- DSD -> PCM: a decimating FIR over the one-bit stream (own specification) ----
+ * Input: the pipeline's DSD format above, stereo; chunk j holds bits 16j .. 16j + 15 of each channel, the most significant bit of
+ * the first byte first.  Bit n < 0 (before the stream start) is [0,1,1,0,1,0,0,1][n mod 8] with a non-negative modulo: the silence
+ * byte 0x69 repeating, aligned at n = 0.  Samples s = 2 * bit - 1.
+ * Filter: decimation D in {8, 16, 32, 64}, T taps per output (a multiple of 8 in 8 .. 64), N = D * T coefficients coef[k], int32,
+ * Q28, with sum|coef| < 2^30 (every sum then fits 32 bits with the rounding added).
+ * Output frame m >= 0, channel c:   acc = sum_{k < N} coef[k] * s_c[(m + 1) * D - 1 - k]
+ *                                   y   = clamp(-2^23, 2^23 - 1, (acc + 16) >> 5)            (arithmetic shift)
+ * -- unity DC gain is sum(coef) = 2^28 -- written S24 packed, interleaved L R, big-endian unless dst_endian says little; with
+ * OHGPU_FLAG_RAMP ramped as RampApplicator's 24-bit case over the message's n_frames, like a resampled message. */
+typedef struct ohgpu_dsd_pcm ohgpu_dsd_pcm;   /* a decimating filter on the device */
+
+/* One OUTPUT message.  64 bytes.  The buffer holds chunks [src_chunk0, src_chunk0 + src_chunks) of the stream from src_offset on,
+ * (4 + P) bytes each.  Every chunk of index >= 0 that ohgpu_dsd_pcm_window names for the message must be among them
+ * (OHGPU_ERR_INVALID otherwise); bits of negative index are the idle pattern and are never read. */
+typedef struct ohgpu_dsd_pcm_msg_desc {
+    uint64_t src_offset;            /* bytes from src_base to chunk src_chunk0                                    */
+    uint64_t src_chunk0;            /* absolute index of the first chunk held                                      */
+    uint64_t src_chunks;            /* chunks held                                                                 */
+    uint64_t out_frame0;            /* absolute index of the message's first output frame                          */
+    uint64_t dst_offset;            /* bytes from dst_base                                                         */
+    uint32_t n_frames;              /* output frames (at most 131071 when ramped)                                  */
+    uint16_t ramp_start;
+    uint16_t ramp_end;
+    uint8_t  sample_block_words;    /* W  } validated as for ohgpu_dsd_desc; only P affects addressing             */
+    uint8_t  pad_bytes_per_chunk;   /* P  }                                                                        */
+    uint8_t  dst_endian;            /* OHGPU_ENDIAN_*                                                              */
+    uint8_t  flags;                 /* OHGPU_FLAG_RAMP                                                             */
+    uint8_t  reserved[12];          /* zero */
+} ohgpu_dsd_pcm_msg_desc;
+
+/* Host only.  Kaiser-windowed sinc by the rule of ohgpu_src_design's integer decimator, over all N = D * T taps: D = dsd_rate /
+ * pcm_rate, stop edge pcm_rate - f_pass_hz, cutoff midway, scaled so that sum(coef) ~ gain * 2^28, Q28 rounding half up.
+ * OHGPU_ERR_INVALID when dsd_rate / pcm_rate is not exactly 8, 16, 32 or 64, T is not a multiple of 8 in 8 .. 64, the capacity is
+ * below N, or sum|coef| >= 2^30.  Pass coef_q28 = NULL to query D only. */
+int ohgpu_dsd_pcm_design(uint32_t dsd_rate, uint32_t pcm_rate, uint32_t taps_per_output, double beta, double f_pass_hz, double gain,
+                         int32_t* coef_q28, size_t coef_capacity, uint32_t* decimation);
+/* The caller's coefficients go to the device (and, for N <= 1024, the byte tables of the fast route made from them).
+ * OHGPU_ERR_INVALID for a (D, T) outside the specification or sum|coef| >= 2^30. */
+int ohgpu_dsd_pcm_create(ohgpu_ctx* ctx, uint32_t decimation, uint32_t taps_per_output, const int32_t* coef_q28, ohgpu_dsd_pcm** filter);
+int ohgpu_dsd_pcm_destroy(ohgpu_ctx* ctx, ohgpu_dsd_pcm* filter);
+/* Host only: the chunks [*chunk_lo, *chunk_hi) that output frames [out_frame0, out_frame0 + n_frames) read -- bits
+ * (out_frame0 + 1) * D - N .. (out_frame0 + n_frames) * D - 1, those below zero left out.  OHGPU_ERR_INVALID for n_frames == 0,
+ * a (D, T) outside the specification or an out_frame0 beyond 2^40. */
+int ohgpu_dsd_pcm_window(uint64_t out_frame0, uint32_t n_frames, uint32_t decimation, uint32_t taps_per_output,
+                         uint64_t* chunk_lo, uint64_t* chunk_hi);
+/* Validated like ohgpu_src_batch_create: OHGPU_ERR_INVALID for a bad (W, P), byte order, flag, reserved byte, ramp endpoint above
+ * OHGPU_RAMP_MAX, ramped message above 131071 frames or a window that does not hold every chunk the message reads;
+ * OHGPU_ERR_BOUNDS for a window or an output beyond its arena; nothing is kept on a refusal.  A message of no frames is accepted
+ * wherever its offsets point.  The batch keeps no per-launch state: it may run any number of times, on any stream.  The filter
+ * must outlive the batch.  ohgpu_batch_info counts the messages, the chunks read (as frames in), the frames out and the bytes.
+ * Routes: the fast kernel (byte-indexed partial sums in LDS; filters of N <= 1024) unless ohgpu_set_kernel_variant(ctx, 1) is in
+ * force at the creation or at the run, or the filter is longer -- then the plain kernel, one thread per output value straight from
+ * the specification.  No byte outside the chunks named by ohgpu_dsd_pcm_window is read. */
+int ohgpu_dsd_pcm_batch_create(ohgpu_ctx* ctx, const ohgpu_dsd_pcm* filter, const ohgpu_dsd_pcm_msg_desc* descs, size_t n,
+                               uint64_t src_arena_bytes, uint64_t dst_arena_bytes, ohgpu_batch** batch);
+int ohgpu_dsd_pcm_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* src_base, void* dst_base, void* stream);
+/* Host only, no device needed: the validation of ohgpu_dsd_pcm_batch_create for a filter of (D, T), with its codes. */
+int ohgpu_dsd_pcm_batch_check(uint32_t decimation, uint32_t taps_per_output, const ohgpu_dsd_pcm_msg_desc* descs, size_t n,
+                              uint64_t src_arena_bytes, uint64_t dst_arena_bytes);
+/* How the batch was planned (read-only, for tests and tools): messages with frames on the fast route, on the plain route, and
+ * launches per run (1, or 0 for a batch without frames). */
+int ohgpu_dsd_pcm_batch_paths(const ohgpu_batch* batch, uint32_t* fast_descs, uint32_t* plain_descs, uint32_t* launches);
+/* Host-buffer convenience, as ohgpu_src_process_host: src_host need only hold each message's window of chunks. */
+int ohgpu_dsd_pcm_process_host(ohgpu_ctx* ctx, const ohgpu_dsd_pcm* filter, const ohgpu_dsd_pcm_msg_desc* descs, size_t n,
+                               const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes);
+
 /* ---- FLAC: native frames decoded on the device ----
  * Stands where libFLAC stands under CodecFlac (Codec/Flac.cpp): file bytes in, and out either the planar TInt32 frames
  * CallbackWrite is handed (what OHGPU_FLAG_SRC_PLANAR32 reads) or the packed big-endian bytes that callback makes of them.

@@ -57,6 +57,13 @@ DSD_DESC = np.dtype([
     ("sample_block_words", "u1"), ("pad_bytes_per_chunk", "u1"), ("reserved", "u1", (8,))], align=False)
 assert DSD_DESC.itemsize == 32
 
+# DSD -> PCM: ohgpu_dsd_pcm_msg_desc (64 B)
+DSD_PCM_MSG_DESC = np.dtype([
+    ("src_offset", "<u8"), ("src_chunk0", "<u8"), ("src_chunks", "<u8"), ("out_frame0", "<u8"), ("dst_offset", "<u8"),
+    ("n_frames", "<u4"), ("ramp_start", "<u2"), ("ramp_end", "<u2"), ("sample_block_words", "u1"), ("pad_bytes_per_chunk", "u1"),
+    ("dst_endian", "u1"), ("flags", "u1"), ("reserved", "u1", (12,))], align=False)
+assert DSD_PCM_MSG_DESC.itemsize == 64
+
 # FLAC frames: ohgpu_flac_stream_desc (64 B), ohgpu_flac_stream_result (48 B), ohgpu_flac_streaminfo_t (48 B)
 FLAC_OK, FLAC_CORRUPT, FLAC_UNSUPPORTED, FLAC_OVERFLOW = 0, 1, 2, 3
 FLAC_FLAG_AT_FRAME, FLAC_OUT_PACKED_BE = 1, 2
@@ -139,6 +146,16 @@ SYMBOLS = {
     "ohgpu_dsd_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "ohgpu_dsd_batch_paths": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "ohgpu_dsd_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64]),
+    "ohgpu_dsd_pcm_design": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double, _vp, C.c_size_t,
+                                       C.POINTER(C.c_uint32)]),
+    "ohgpu_dsd_pcm_create": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _vpp]),
+    "ohgpu_dsd_pcm_destroy": (C.c_int, [_vp, _vp]),
+    "ohgpu_dsd_pcm_window": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _u64p, _u64p]),
+    "ohgpu_dsd_pcm_batch_create": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
+    "ohgpu_dsd_pcm_batch_check": (C.c_int, [C.c_uint32, C.c_uint32, _vp, C.c_size_t, C.c_uint64, C.c_uint64]),
+    "ohgpu_dsd_pcm_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "ohgpu_dsd_pcm_batch_paths": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "ohgpu_dsd_pcm_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64]),
     "ohgpu_flac_streaminfo": (C.c_int, [_vp, C.c_size_t, _vp, _u64p]),
     "ohgpu_flac_batch_check": (C.c_int, [_vp, C.c_size_t, C.c_uint64, C.c_uint64]),
     "ohgpu_flac_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
@@ -319,6 +336,30 @@ def dsd_layout(kind, sample_block_words, pad_bytes_per_chunk, n_chunks):
     s, d = C.c_uint64(0), C.c_uint64(0)
     check(lib().ohgpu_dsd_layout(kind, sample_block_words, pad_bytes_per_chunk, n_chunks, C.byref(s), C.byref(d)))
     return int(s.value), int(d.value)
+
+
+def dsd_pcm_design(dsd_rate, pcm_rate, taps_per_output=16, beta=14.0, f_pass=20000.0, gain=1.0):
+    """(D, coef_q28[D * T]) from the library's own host-side decimator design (ohgpu_dsd_pcm_design; host only)."""
+    D = C.c_uint32(0)
+    check(lib().ohgpu_dsd_pcm_design(dsd_rate, pcm_rate, taps_per_output, beta, f_pass, gain, None, 0, C.byref(D)))
+    coef = np.zeros(D.value * taps_per_output, dtype=np.int32)
+    check(lib().ohgpu_dsd_pcm_design(dsd_rate, pcm_rate, taps_per_output, beta, f_pass, gain, coef.ctypes.data_as(C.c_void_p),
+                                     coef.size, C.byref(D)))
+    return D.value, coef
+
+
+def dsd_pcm_window(out_frame0, n_frames, decimation, taps_per_output):
+    """(chunk_lo, chunk_hi): the chunks a converted message reads (ohgpu_dsd_pcm_window; host only)."""
+    lo, hi = C.c_uint64(0), C.c_uint64(0)
+    check(lib().ohgpu_dsd_pcm_window(out_frame0, n_frames, decimation, taps_per_output, C.byref(lo), C.byref(hi)))
+    return int(lo.value), int(hi.value)
+
+
+def dsd_pcm_batch_check(decimation, taps_per_output, descs, src_arena_bytes, dst_arena_bytes):
+    """The validation of ctx.dsd_pcm_batch without a device (ohgpu_dsd_pcm_batch_check): OhGpuError on a bad descriptor."""
+    d = np.ascontiguousarray(descs)
+    assert d.dtype == DSD_PCM_MSG_DESC
+    check(lib().ohgpu_dsd_pcm_batch_check(decimation, taps_per_output, d.ctypes.data_as(C.c_void_p), d.size, src_arena_bytes, dst_arena_bytes))
 
 
 def flac_streaminfo(stream):
@@ -511,6 +552,42 @@ class Context:
         check(lib().ohgpu_dsd_process_host(self._h, d.ctypes.data_as(C.c_void_p), d.size,
                                            src.ctypes.data_as(C.c_void_p), src.nbytes,
                                            dst.ctypes.data_as(C.c_void_p), dst.nbytes))
+        return dst
+
+    # ---- DSD -> PCM
+    def dsd_pcm_create(self, decimation, taps_per_output, coef_q28):
+        c = np.ascontiguousarray(coef_q28, dtype=np.int32)
+        assert c.size == decimation * taps_per_output
+        f = C.c_void_p()
+        check(lib().ohgpu_dsd_pcm_create(self._h, decimation, taps_per_output, c.ctypes.data_as(C.c_void_p), C.byref(f)))
+        return f
+
+    def dsd_pcm_destroy(self, filt):
+        check(lib().ohgpu_dsd_pcm_destroy(self._h, filt))
+
+    def dsd_pcm_batch(self, filt, descs, src_arena_bytes, dst_arena_bytes):
+        d = np.ascontiguousarray(descs)
+        assert d.dtype == DSD_PCM_MSG_DESC
+        b = C.c_void_p()
+        check(lib().ohgpu_dsd_pcm_batch_create(self._h, filt, d.ctypes.data_as(C.c_void_p), d.size, src_arena_bytes,
+                                               dst_arena_bytes, C.byref(b)))
+        return b
+
+    def dsd_pcm_run(self, batch, d_src, d_dst, stream=None):
+        check(lib().ohgpu_dsd_pcm_batch_run(self._h, batch, d_src, d_dst, stream))
+
+    def dsd_pcm_batch_paths(self, batch):
+        """How a DSD -> PCM batch was planned (ohgpu_dsd_pcm_batch_paths): messages on the fast route, on the plain route, launches."""
+        v = [C.c_uint32(0) for _ in range(3)]
+        check(lib().ohgpu_dsd_pcm_batch_paths(batch, *[C.byref(x) for x in v]))
+        return dict(zip(("fast_descs", "plain_descs", "launches"), (int(x.value) for x in v)))
+
+    def dsd_pcm_process_host(self, filt, descs, src, dst):
+        d = np.ascontiguousarray(descs)
+        assert d.dtype == DSD_PCM_MSG_DESC
+        check(lib().ohgpu_dsd_pcm_process_host(self._h, filt, d.ctypes.data_as(C.c_void_p), d.size,
+                                               src.ctypes.data_as(C.c_void_p), src.nbytes,
+                                               dst.ctypes.data_as(C.c_void_p), dst.nbytes))
         return dst
 
     def flac_batch(self, descs, src_arena_bytes, dst_arena_bytes):

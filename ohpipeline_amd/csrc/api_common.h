@@ -20,6 +20,8 @@ namespace ohgpu {
 inline hipStream_t pick_stream(const ohgpu_ctx* ctx, void* stream) { return stream ? (hipStream_t)stream : ctx->stream; }
 inline bool valid_bits(uint32_t bits) { return bits == 8 || bits == 16 || bits == 24 || bits == 32; }
 inline bool valid_endian(uint32_t e) { return e == OHGPU_ENDIAN_LITTLE || e == OHGPU_ENDIAN_BIG; }
+// The pipeline's DSD format (ohgpu.h's DSD section): ASSERT((W * 4) % (4 + P) == 0) with W - P chunks per block
+inline bool valid_dsd_format(uint32_t W, uint32_t P) { return W >= 1 && W <= 255 && (P == 0 || (P % 2 == 0 && W == P + 4)); }
 // end = off + a * b + c in 64 bits; false when any step wraps (such a descriptor is out of bounds: a wrapped end can look small)
 inline bool span_end(uint64_t off, uint64_t a, uint64_t b, uint64_t c, uint64_t* end)
 {

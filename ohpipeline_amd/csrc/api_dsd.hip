@@ -14,7 +14,7 @@ static int dsd_check(const char* who, uint32_t kind, uint32_t flags, uint32_t W,
         return set_error(OHGPU_ERR_INVALID, "%s: unknown kind %u", who, kind);
     if (flags & ~OHGPU_DSD_FLAG_SILENCE) return set_error(OHGPU_ERR_INVALID, "%s: unknown flags 0x%x", who, flags);
     // ASSERT((W * 4) % (4 + P) == 0) with W - P chunks per block: DsdDsf.cpp:108,196, DsdDff.cpp:92,334, Msg.cpp:2385
-    if (W < 1 || W > 255 || !(P == 0 || (P % 2 == 0 && W == P + 4)))
+    if (!valid_dsd_format(W, P))
         return set_error(OHGPU_ERR_INVALID, "%s: sample block of %u words with %u pad bytes per chunk (P == 0, or W == P + 4 with P even)", who, W, P);
     const uint64_t cs = 4 + P, per_block = W * 4 / cs, blocks = (n_chunks + per_block - 1) / per_block;
     const bool silent = (flags & OHGPU_DSD_FLAG_SILENCE) != 0;

@@ -105,6 +105,56 @@ int design_src(uint32_t rate_in, uint32_t rate_out, uint32_t T, double beta, dou
     return OHGPU_OK;
 }
 
+// The DSD -> PCM decimator: D = dsd_rate / pcm_rate in {8, 16, 32, 64}, T taps per output a multiple of 8 in 8 .. 64,
+// N = D * T stored coefficients.  The rule is the integer decimator's above at the DSD rate: an odd length N - 1 centred on a tap,
+// stored with coef[N - 1] = 0; stop edge pcm_rate - f_pass, cutoff midway; scaled to sum = gain, Q28 rounding half up.
+int check_dsd_pcm_filter(uint32_t D, uint32_t T, const int32_t* coef_q28, const char* who)
+{
+    if ((D != 8 && D != 16 && D != 32 && D != 64) || T < 8 || T > 64 || T % 8 != 0)
+        return set_error(OHGPU_ERR_INVALID, "%s: decimation %u (8, 16, 32 or 64) with %u taps per output (a multiple of 8 in 8 .. 64)", who, D, T);
+    if (!coef_q28) return OHGPU_OK;
+    int64_t sabs = 0;
+    for (uint32_t k = 0; k < D * T; k++) sabs += coef_q28[k] < 0 ? -(int64_t)coef_q28[k] : (int64_t)coef_q28[k];
+    // one-bit samples are +-1: sum|c| < 2^30 keeps every partial sum, and the last one with the rounding added, inside 32 bits
+    if (sabs >= ((int64_t)1 << 30)) return set_error(OHGPU_ERR_INVALID, "%s: sum|c| = %lld breaks the 32-bit accumulation bound 2^30", who, (long long)sabs);
+    return OHGPU_OK;
+}
+
+int design_dsd_pcm(uint32_t dsd_rate, uint32_t pcm_rate, uint32_t T, double beta, double f_pass, double gain,
+                   std::vector<int32_t>* coef_q28, uint32_t* D_out)
+{
+    if (dsd_rate == 0 || pcm_rate == 0 || dsd_rate % pcm_rate != 0)
+        return set_error(OHGPU_ERR_INVALID, "dsd pcm design: %u -> %u is not a whole decimation", dsd_rate, pcm_rate);
+    const uint32_t D = dsd_rate / pcm_rate;
+    int err = check_dsd_pcm_filter(D, T, nullptr, "dsd pcm design");
+    if (err != OHGPU_OK) return err;
+    *D_out = D;
+    if (coef_q28 == nullptr) return OHGPU_OK;
+    const double f_stop = (double)pcm_rate - f_pass;
+    if (!(f_pass > 0.0) || !(f_stop > f_pass) || !(beta >= 0.0) || !(gain > 0.0) || !(gain < 4.0))
+        return set_error(OHGPU_ERR_INVALID, "dsd pcm design: f_pass %g (stop edge %g), beta %g, gain %g", f_pass, f_stop, beta, gain);
+    const uint32_t N = D * T - 1;
+    const double fc = 0.5 * (f_pass + f_stop);
+    const double wc = 2.0 * fc / (double)dsd_rate;
+    const double centre = 0.5 * (double)(N - 1);
+    const double i0b = bessel_i0(beta);
+    std::vector<double> h(N);
+    double sum = 0.0;
+    for (uint32_t n = 0; n < N; n++) {
+        const double d = (double)n - centre;
+        const double x = wc * d;
+        const double sinc = (std::fabs(x) < 1e-12) ? 1.0 : std::sin(M_PI * x) / (M_PI * x);
+        const double r = d / centre;
+        const double arg = 1.0 - r * r;
+        const double w = bessel_i0(beta * std::sqrt(arg > 0.0 ? arg : 0.0)) / i0b;
+        h[n] = wc * sinc * w;
+        sum += h[n];
+    }
+    const double scale = gain / sum;
+    coef_q28->assign((size_t)D * T, 0);
+    for (uint32_t n = 0; n < N; n++) (*coef_q28)[n] = (int32_t)std::floor(h[n] * scale * 268435456.0 + 0.5);
+    return check_dsd_pcm_filter(D, T, coef_q28->data(), "dsd pcm design");
+}
 
 // The pulled resampler's table.  The prototype h[n], n = 0 .. T*P - 1, is sampled at P = 2^s phases per input
 // frame; frequencies below are in cycles per input frame at an input rate pulled anywhere in rate_in * [1 - max_pull, 1 + max_pull]:

@@ -302,8 +302,9 @@ static const struct { const char* noun; void (*release)(ohgpu_ctx*, ohgpu_batch*
     {"pulled", free_pull, false},                 // kBatchSrcPull
     {"DSD", free_dsd_line, true},                 // kBatchDsd
     {"FLAC", flac_free, false},                   // kBatchFlac
+    {"DSD to PCM", free_dsd_pcm, true},           // kBatchDsdPcm
 };
-static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchFlac + 1, "a row per BatchKind");
+static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchDsdPcm + 1, "a row per BatchKind");
 
 int run_guard(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, BatchKind kind, bool empty, bool null_src_ok,
               const void* src_base, const void* dst_base)

@@ -360,7 +360,21 @@ struct FlacState {
     uint32_t n_candidates = 0;
 };
 
-enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8 };
+// ---- DSD -> PCM (csrc/dsd_pcm_kernel.hip): a batch is cut on the host into tiles of up to kDsdPcmTile consecutive output frames of
+// one message; both kernels loop over them.  The batch's d_descs holds the messages.
+constexpr uint32_t kDsdPcmTile = 512;
+constexpr uint32_t kDsdPcmTableTaps = 1024;     // the fast route's tables (N / 8 KiB) and its staging fit the LDS up to here
+struct DsdPcmTile { uint32_t msg, f0, count, pad; };   // frames [f0, f0 + count) of message msg
+static_assert(sizeof(DsdPcmTile) == 16, "DsdPcmTile");
+struct DsdPcmPlan {
+    uint32_t n_tiles = 0;
+    uint32_t n_fast = 0, n_plain = 0;     // messages with frames, by route (ohgpu_dsd_pcm_batch_paths)
+    bool     fast = false;                // planned onto dsd_pcm_table_kernel
+    void*    d_tiles = nullptr;
+};
+static_assert(sizeof(ohgpu_dsd_pcm_msg_desc) == 64, "ohgpu_dsd_pcm_msg_desc layout");
+
+enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9 };
 
 }  // namespace ohgpu
 
@@ -421,6 +435,12 @@ struct ohgpu_src {
     int32_t* d_pull_table = nullptr;
 };
 
+struct ohgpu_dsd_pcm {
+    uint32_t D, T, N;
+    int32_t* d_coef = nullptr;    // [N] Q28
+    int32_t* d_tables = nullptr;  // [N / 8][256]: byte b of an output's window (its oldest eight bits first) -> its share of the sum; null when N > kDsdPcmTableTaps
+};
+
 namespace ohgpu {
 // Host arrays of tens of megabytes that are written once, by several threads: 2 MiB-aligned and advised to the kernel as huge-page
 // material, so that filling them costs a page fault per 2 MiB instead of one per 4 KiB (seven thousand of them for the headline's
@@ -456,6 +476,8 @@ struct ohgpu_batch {
     ohgpu::FmtLinePlan fmtline;   // kBatchFmt only
     ohgpu::OhmPlan ohm;           // kBatchOhm only
     ohgpu::DsdPlan dsd;           // kBatchDsd only
+    ohgpu::DsdPcmPlan dsdpcm;     // kBatchDsdPcm only
+    const ohgpu_dsd_pcm* dsdpcm_filter = nullptr;
     ohgpu::FlacState* flac = nullptr;   // kBatchFlac only (what a run changes lives behind the pointer: a run takes a const batch)
     void*    d_pull_tiles = nullptr;   // kBatchSrcPull: PullTile[n_pull_tiles] on the device (d_descs holds the messages)
     uint32_t n_pull_tiles = 0;
@@ -504,6 +526,12 @@ int plan_dsd_line(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_dsd_desc* descs, s
 void free_dsd_line(ohgpu_ctx* ctx, ohgpu_batch* b);
 hipError_t launch_dsd_line(const ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
 hipError_t launch_dsd_v1(const ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
+// csrc/dsd_pcm_kernel.hip
+void build_dsd_pcm_tables(const int32_t* coef_q28, uint32_t N, std::vector<int32_t>* tables);
+int  plan_dsd_pcm(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_dsd_pcm_msg_desc* descs, size_t n);
+void free_dsd_pcm(ohgpu_ctx* ctx, ohgpu_batch* b);
+hipError_t launch_dsd_pcm_table(const ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
+hipError_t launch_dsd_pcm_v1(const ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
 // csrc/flac_frame_kernel.hip
 int  flac_plan(ohgpu_ctx* ctx, ohgpu_batch* b);                       // the device side of a validated batch (b->flac->streams is filled)
 void flac_free(ohgpu_ctx* ctx, ohgpu_batch* b);
@@ -575,6 +603,9 @@ void build_ramp_table(uint16_t out[512]);
 int  design_src_pull(uint32_t rate_in, uint32_t rate_out, uint32_t T, uint32_t phases_log2, double beta, double f_pass,
                      double max_pull, std::vector<int32_t>* coef_q28);
 int  check_src_pull_table(uint32_t T, uint32_t phases_log2, const int32_t* coef_q28, const char* who);
+int  design_dsd_pcm(uint32_t dsd_rate, uint32_t pcm_rate, uint32_t T, double beta, double f_pass, double gain,
+                    std::vector<int32_t>* coef_q28, uint32_t* D);       // (coef_q28 null: D only)
+int  check_dsd_pcm_filter(uint32_t D, uint32_t T, const int32_t* coef_q28, const char* who);   // the (D, T) rule; with coefficients, sum|c| < 2^30
 int  design_src(uint32_t rate_in, uint32_t rate_out, uint32_t T, double beta, double f_pass,
                 std::vector<int32_t>* coef_q28, uint32_t* L, uint32_t* M);
 void free_src_fast(ohgpu_ctx* ctx, ohgpu_batch* b);

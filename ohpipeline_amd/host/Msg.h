@@ -491,6 +491,7 @@ public:
     MsgFlush* CreateMsgFlush(TUint aId) { return new MsgFlush(aId); }
     MsgWait* CreateMsgWait() { return new MsgWait(); }
     ohgpu_ctx* Gpu() const;
+    TBool HasGpu() const { return iCtx != nullptr; }     // false for a control-plane-only factory, whose Gpu() asserts
     /** The filter of a conversion, designed and uploaded on first use and kept for the factory's lifetime. */
     const SrcFilter& SharedFilter(TUint aRateIn, TUint aRateOut, TUint aTapsPerPhase, double aBeta, double aPassHz);
     TUint FilterCount() const;
