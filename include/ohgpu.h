@@ -27,6 +27,8 @@
  *       (Msg.cpp:2360-2373)
  *   CodecFlac + libFLAC: frames found, entropy-decoded, restored            ohgpu_flac_batch_run()
  *       (Codec/Flac.cpp:355-443; thirdparty/flac-1.2.1 by its format document)   -> TInt32 planes or CallbackWrite's packed bytes
+ *   CodecAlacApple + apple_alac: packets entropy-decoded, predicted, unmixed   ohgpu_alac_batch_run()
+ *       (Codec/AlacApple.cpp, AlacAppleBase.cpp:20-115; thirdparty/apple_alac by its behaviour)   -> TInt32 planes or the decoder's packed bytes
  *   "SampleRateConverter" -- NOT PRESENT in the reference  ohgpu_src_* (own spec)
  *
  * The reference binds nothing through FFI today (it is one C++ static library); INTEGRATION.md
@@ -177,7 +179,7 @@ int ohgpu_batch_info(const ohgpu_batch* batch, uint64_t* n_msgs, uint64_t* in_fr
  * plan says.  A fmt batch takes exactly one of five routes: mono / stereo Songcast packs of >= 16 bits as plain PCM messages
  * (line_planned, group_chunks), Songcast packs of wider streams (fmt_wide_records), a uniform stereo batch on a register-only
  * kernel (fmt_stereo_*), the staged layout kernel (fmt_staged_chunks), or, with every count zero, the generic kernel only.
- * OHGPU_ERR_INVALID for any other kind of batch. */
+ * An Apple Lossless batch (ohgpu_alac_batch_create) answers with alac_route alone.  OHGPU_ERR_INVALID for any other kind of batch. */
 typedef struct ohgpu_batch_paths {       /* 64 bytes */
     uint32_t line_planned;          /* 1: the line kernel has a plan for the batch (0: only the generic kernel can run it) */
     uint32_t launches;              /* line-kernel launches per run: one per layout present (8-bit / silence, and each 16/24/32-bit depth pair) */
@@ -194,7 +196,10 @@ typedef struct ohgpu_batch_paths {       /* 64 bytes */
     uint32_t fmt_stereo_kind;       /* ... which of the two: OHGPU_FMT_UNPACK_PLANAR or OHGPU_FMT_FLAC_PACK (0 when fmt_stereo_records is 0) */
     uint32_t fmt_stereo_bytes;      /* ... and the instantiation: source bytes per subsample 2/3/4 (UNPACK_PLANAR), destination bytes 1/2/3 (FLAC_PACK) */
     uint32_t fmt_staged_chunks;     /* fmt: chunks of the staged layout kernel (csrc/fmt_line_kernel.hip), <= 512 destination subsamples each */
-    uint32_t reserved[1];
+    union {                         /* (the last word: named for what took it, `reserved` for older callers) */
+        uint32_t reserved[1];
+        uint32_t alac_route;        /* Apple Lossless: 1 the three fused phases over the transposed scratch, 2 the plain route (created under kernel variant 1) */
+    };
 } ohgpu_batch_paths;
 int ohgpu_batch_paths_info(const ohgpu_batch* batch, ohgpu_batch_paths* out);
 
@@ -456,6 +461,95 @@ int ohgpu_flac_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float ms
 int ohgpu_flac_process_host(ohgpu_ctx* ctx, const ohgpu_flac_stream_desc* descs, size_t n,
                             const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes,
                             ohgpu_flac_stream_result* results, ohgpu_flac_frame* frames, size_t frames_capacity, size_t* n_frames);
+
+/* ---- Apple Lossless packets (the format text is csrc/alac_packet_core.h) ----
+ * CodecAlacApple (Codec/AlacApple.cpp, AlacAppleBase.cpp) hands the container's packets to thirdparty/apple_alac one at a time; here a
+ * batch of streams, each a run of packets of a packet table, is decoded in one run of three phases -- entropy (a lane per packet),
+ * predictor (a lane per channel row), matrix and store (a lane per sample) -- with no host synchronisation inside it.  Packets are
+ * independent: packet p of a stream lands at sample p * frame_length of the stream's destination.  Output is host-endian TInt32
+ * planes (channel c at dst_offset + c * dst_plane_stride; what OHGPU_FLAG_SRC_PLANAR32 consumes), or the reference decoder's own
+ * buffer byte for byte (OHGPU_ALAC_OUT_PACKED_LE: bit_depth / 8 bytes a sample, interleaved, little-endian), or what row a1 makes of
+ * that (OHGPU_ALAC_OUT_PACKED_BE).  The product links no Apple code.
+ * Where this decoder is stricter than the reference's (tests/alac_textbook.py carries the same list):
+ *   - the reference reads up to four bytes past a packet (AlacAppleBase.cpp:29-33); here bits past the packet's end read as zero and
+ *     an element that needed one is CORRUPT;
+ *   - a compressed element's sample width (bit_depth - 8 * bytes shifted, plus one for a pair) outside 1..32 is CORRUPT;
+ *   - a sample count above the stream's frame_length, or audio elements of one packet that disagree about it, is CORRUPT (the
+ *     reference overruns its buffers or leaves stale samples);
+ *   - bit_depth 20 is UNSUPPORTED (AlacAppleBase.cpp:90 counts two bytes a sample for the decoder's three), so is a kb outside 1..31;
+ *   - a rounding shift of zero rounds with nothing and a matrix shift above 31 shifts by 31 (the reference's shifts are undefined
+ *     there); an escaped element carries bit_depth bits a sample whatever its shift field says;
+ *   - a failed packet writes nothing to the destination.
+ * Limits: 1..8 channels, frame_length 1..16384, a packet of at most frame_length * channels * 5 + 64 bytes. */
+#define OHGPU_ALAC_OK          0u
+#define OHGPU_ALAC_CORRUPT     1u
+#define OHGPU_ALAC_UNSUPPORTED 2u
+#define OHGPU_ALAC_OUT_PACKED_LE  0x01u
+#define OHGPU_ALAC_OUT_PACKED_BE  0x02u
+#define OHGPU_ALAC_MAX_FRAME_LENGTH 16384u
+
+typedef struct ohgpu_alac_config {          /* 24 bytes: ALACSpecificConfig, host-endian */
+    uint32_t frame_length;
+    uint8_t  compatible_version;    /* 0 */
+    uint8_t  bit_depth;             /* 16, 24, 32 (20: every packet UNSUPPORTED) */
+    uint8_t  pb, mb, kb;
+    uint8_t  channels;
+    uint16_t max_run;
+    uint32_t max_frame_bytes, avg_bit_rate, sample_rate;
+} ohgpu_alac_config;
+
+typedef struct ohgpu_alac_packet {          /* 16 bytes: one row of the packet table */
+    uint64_t src_offset;            /* the packet's bytes: [src_offset, src_offset + bytes) of the source arena, any alignment */
+    uint32_t bytes;
+    uint32_t reserved;              /* zero */
+} ohgpu_alac_packet;
+
+typedef struct ohgpu_alac_stream_desc {     /* 64 bytes */
+    ohgpu_alac_config config;
+    uint32_t first_packet, n_packets;  /* its packets: [first_packet, first_packet + n_packets) of the table; the streams' ranges
+                                          follow each other in the table without gaps, the first at 0 */
+    uint64_t dst_offset;            /* multiple of 4 */
+    uint64_t dst_plane_stride;      /* planes: bytes between the channels' planes, multiple of 4, >= n_packets * frame_length * 4; packed: 0 */
+    uint32_t flags;                 /* 0, OHGPU_ALAC_OUT_PACKED_LE or OHGPU_ALAC_OUT_PACKED_BE */
+    uint32_t reserved[3];           /* zero */
+} ohgpu_alac_stream_desc;
+
+typedef struct ohgpu_alac_packet_result { uint32_t status, samples; } ohgpu_alac_packet_result;      /* OHGPU_ALAC_*; samples per channel (0 unless OK) */
+typedef struct ohgpu_alac_stream_result {   /* 16 bytes */
+    uint32_t packets_ok;            /* the leading packets that decoded */
+    uint32_t first_bad_status;      /* the status of the packet behind them (0 when every packet decoded) */
+    uint64_t samples;               /* the samples (per channel) of the leading packets */
+} ohgpu_alac_stream_result;
+
+/* Host only, no device needed: the 24 big-endian bytes of the configuration, behind an optional 12-byte 'frma' atom and / or 12-byte
+ * 'alac' atom header (ALACDecoder.cpp:96-168).  OHGPU_ERR_INVALID: fewer bytes than that, or a compatible version other than 0. */
+int ohgpu_alac_config_parse(const void* bytes, size_t n, ohgpu_alac_config* config);
+/* Host only, no device needed: the validation ohgpu_alac_batch_create makes, with its codes and ohgpu_last_error() texts. */
+int ohgpu_alac_batch_check(const ohgpu_alac_stream_desc* descs, size_t n, const ohgpu_alac_packet* packets, size_t n_packets,
+                           uint64_t src_arena_bytes, uint64_t dst_arena_bytes);
+/* Validated on the host (ranges against the arenas: OHGPU_ERR_BOUNDS; the limits above, alignment, overlapping planes, packet ranges:
+ * OHGPU_ERR_INVALID; a depth other than 16/20/24/32: OHGPU_ERR_UNSUPPORTED); freed with ohgpu_batch_destroy.  The batch owns its
+ * results and its scratch: it runs on one stream at a time.  Created under ohgpu_set_kernel_variant(1) the batch takes the plain
+ * route -- one thread per packet does everything, over row-major scratch --, otherwise the three fused phases over the transposed
+ * scratch (ohgpu_batch_paths_info: alac_route). */
+int ohgpu_alac_batch_create(ohgpu_ctx* ctx, const ohgpu_alac_stream_desc* descs, size_t n, const ohgpu_alac_packet* packets, size_t n_packets,
+                            uint64_t src_arena_bytes, uint64_t dst_arena_bytes, ohgpu_batch** batch);
+/* Entropy, predictor, matrix and store, queued on the stream; nothing waits for the host.  Scratch is kept by the batch and its
+ * small arrays come from the context's block cache: a second run, and a second batch of the same shape, allocate nothing
+ * (ohgpu_device_allocations). */
+int ohgpu_alac_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* src_base, void* dst_base, void* stream);
+/* The last run's results (waits for that run): per stream (n = the batch's descriptor count) and / or per packet (n_packets = the
+ * table's length); either pointer may be NULL with its count 0. */
+int ohgpu_alac_batch_results(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_alac_stream_result* streams, size_t n,
+                             ohgpu_alac_packet_result* packets, size_t n_packets);
+/* The last run's phases in milliseconds from device events: entropy, predictor, matrix and store (waits for that run).  The plain
+ * route is one phase: the other two read as 0. */
+int ohgpu_alac_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float ms[3]);
+/* Host-buffer convenience, as ohgpu_flac_process_host: one upload, one run.  Of dst_host only the samples of packets that decoded
+ * are written.  Either result pointer may be NULL. */
+int ohgpu_alac_process_host(ohgpu_ctx* ctx, const ohgpu_alac_stream_desc* descs, size_t n, const ohgpu_alac_packet* packets, size_t n_packets,
+                            const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes,
+                            ohgpu_alac_stream_result* stream_results, ohgpu_alac_packet_result* packet_results);
 
 /* ---- FlywheelRamper ----
  * Replaces FlywheelRamperManager::Ramp (OpenHome/Media/FlywheelRamper.cpp:44-66; per channel FlywheelRamper::Initialise

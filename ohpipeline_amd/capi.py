@@ -81,6 +81,20 @@ FLAC_FRAME = np.dtype([("stream", "<u4"), ("blocksize", "<u4"), ("first_sample",
 assert FLAC_FRAME.itemsize == 24
 assert FLAC_STREAM_DESC.itemsize == 64 and FLAC_STREAM_RESULT.itemsize == 48 and FLAC_STREAMINFO.itemsize == 48
 
+# Apple Lossless packets: ohgpu_alac_config (24 B), ohgpu_alac_packet (16 B), ohgpu_alac_stream_desc (64 B)
+ALAC_OK, ALAC_CORRUPT, ALAC_UNSUPPORTED = 0, 1, 2
+ALAC_OUT_PACKED_LE, ALAC_OUT_PACKED_BE = 1, 2
+ALAC_ROUTE_FUSED, ALAC_ROUTE_PLAIN = 1, 2
+_ALAC_CONFIG_FIELDS = [("frame_length", "<u4"), ("compatible_version", "u1"), ("bit_depth", "u1"), ("pb", "u1"), ("mb", "u1"), ("kb", "u1"),
+                       ("channels", "u1"), ("max_run", "<u2"), ("max_frame_bytes", "<u4"), ("avg_bit_rate", "<u4"), ("sample_rate", "<u4")]
+ALAC_CONFIG = np.dtype(_ALAC_CONFIG_FIELDS, align=False)
+ALAC_PACKET = np.dtype([("src_offset", "<u8"), ("bytes", "<u4"), ("reserved", "<u4")], align=False)
+ALAC_STREAM_DESC = np.dtype(_ALAC_CONFIG_FIELDS + [("first_packet", "<u4"), ("n_packets", "<u4"), ("dst_offset", "<u8"), ("dst_plane_stride", "<u8"),
+                                                   ("flags", "<u4"), ("reserved", "<u4", (3,))], align=False)
+ALAC_PACKET_RESULT = np.dtype([("status", "<u4"), ("samples", "<u4")], align=False)
+ALAC_STREAM_RESULT = np.dtype([("packets_ok", "<u4"), ("first_bad_status", "<u4"), ("samples", "<u8")], align=False)
+assert ALAC_CONFIG.itemsize == 24 and ALAC_PACKET.itemsize == 16 and ALAC_STREAM_DESC.itemsize == 64 and ALAC_STREAM_RESULT.itemsize == 16
+
 BATCH_PATHS = np.dtype([(k, "<u4") for k in ("line_planned", "launches", "staged_chunks", "group_chunks", "heavy_chunks",
                                             "prefixed_chunks", "ohm_wide_fragments", "ohm_staged_fragments", "ohm_headers_fused",
                                             "ohm_headers_separate", "fmt_wide_records", "fmt_stereo_records", "fmt_stereo_kind",
@@ -164,6 +178,13 @@ SYMBOLS = {
     "ohgpu_flac_batch_frames": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "ohgpu_flac_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
     "ohgpu_flac_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ohgpu_alac_config_parse": (C.c_int, [_vp, C.c_size_t, _vp]),
+    "ohgpu_alac_batch_check": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, C.c_uint64, C.c_uint64]),
+    "ohgpu_alac_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
+    "ohgpu_alac_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "ohgpu_alac_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t]),
+    "ohgpu_alac_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
+    "ohgpu_alac_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
     "ohgpu_flywheel_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
     "ohgpu_flywheel_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "ohgpu_flywheel_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64]),
@@ -373,6 +394,26 @@ def flac_streaminfo(stream):
                                     "min_framesize", "max_framesize")} | {"md5": bytes(i["md5"])}, int(off.value))
 
 
+def alac_config_parse(cookie):
+    """The stream configuration (ALAC_CONFIG, one record) of a magic cookie, atom wrappers and all (ohgpu_alac_config_parse; host only)."""
+    buf = np.frombuffer(bytes(cookie), dtype=np.uint8)
+    cfg = np.zeros(1, dtype=ALAC_CONFIG)
+    check(lib().ohgpu_alac_config_parse(buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size, cfg.ctypes.data_as(C.c_void_p)))
+    return cfg[0]
+
+
+def _alac_tables(descs, packets):
+    d, p = np.ascontiguousarray(descs), np.ascontiguousarray(packets)
+    assert d.dtype == ALAC_STREAM_DESC and p.dtype == ALAC_PACKET
+    return d, p
+
+
+def alac_batch_check(descs, packets, src_arena_bytes, dst_arena_bytes):
+    """The validation of ctx.alac_batch without a device (ohgpu_alac_batch_check): OhGpuError on a bad descriptor."""
+    d, p = _alac_tables(descs, packets)
+    check(lib().ohgpu_alac_batch_check(d.ctypes.data_as(C.c_void_p), d.size, p.ctypes.data_as(C.c_void_p), p.size, src_arena_bytes, dst_arena_bytes))
+
+
 def flac_batch_check(descs, src_arena_bytes, dst_arena_bytes):
     """The validation of ctx.flac_batch without a device (ohgpu_flac_batch_check): OhGpuError on a bad descriptor."""
     d = np.ascontiguousarray(descs)
@@ -508,7 +549,9 @@ class Context:
         """Which kernels a pcm, Songcast frame or fmt batch was planned onto (ohgpu_batch_paths), as a dict of counts."""
         v = np.zeros(1, dtype=BATCH_PATHS)
         check(lib().ohgpu_batch_paths_info(batch, v.ctypes.data_as(C.c_void_p)))
-        return {k: int(v[k][0]) for k in BATCH_PATHS.names if k != "reserved"}
+        out = {k: int(v[k][0]) for k in BATCH_PATHS.names if k != "reserved"}
+        out["alac_route"] = int(v["reserved"][0][0])        # (the header's union: the last word)
+        return out
 
     def pcm_process_host(self, descs, src, dst):
         d = np.ascontiguousarray(descs)
@@ -631,6 +674,39 @@ class Context:
                                             src.ctypes.data_as(C.c_void_p), src.nbytes,
                                             dst.ctypes.data_as(C.c_void_p), dst.nbytes, res.ctypes.data_as(C.c_void_p), None, 0, None))
         return res
+
+    def alac_batch(self, descs, packets, src_arena_bytes, dst_arena_bytes):
+        d, p = _alac_tables(descs, packets)
+        b = C.c_void_p()
+        check(lib().ohgpu_alac_batch_create(self._h, d.ctypes.data_as(C.c_void_p), d.size, p.ctypes.data_as(C.c_void_p), p.size,
+                                            src_arena_bytes, dst_arena_bytes, C.byref(b)))
+        return b
+
+    def alac_run(self, batch, d_src, d_dst, stream=None):
+        """Entropy, predictor, matrix and store (ohgpu_alac_batch_run): queued on the stream, nothing waits for the host."""
+        check(lib().ohgpu_alac_batch_run(self._h, batch, d_src, d_dst, stream))
+
+    def alac_results(self, batch, n, n_packets):
+        """The last run's (ALAC_STREAM_RESULT per stream, ALAC_PACKET_RESULT per packet); waits for the run."""
+        sres, pres = np.zeros(n, dtype=ALAC_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET_RESULT)
+        check(lib().ohgpu_alac_batch_results(self._h, batch, sres.ctypes.data_as(C.c_void_p) if n else None, n,
+                                             pres.ctypes.data_as(C.c_void_p) if n_packets else None, n_packets))
+        return sres, pres
+
+    def alac_phase_ms(self, batch):
+        """The last run's (entropy, predictor, matrix and store) in milliseconds, from device events."""
+        ms = (C.c_float * 3)()
+        check(lib().ohgpu_alac_batch_phase_ms(self._h, batch, ms))
+        return tuple(float(v) for v in ms)
+
+    def alac_process_host(self, descs, packets, src, dst):
+        """Host buffers in and out (ohgpu_alac_process_host); returns (stream results, packet results).  Only decoded samples are written to dst."""
+        d, p = _alac_tables(descs, packets)
+        sres, pres = np.zeros(d.size, dtype=ALAC_STREAM_RESULT), np.zeros(p.size, dtype=ALAC_PACKET_RESULT)
+        check(lib().ohgpu_alac_process_host(self._h, d.ctypes.data_as(C.c_void_p), d.size, p.ctypes.data_as(C.c_void_p), p.size,
+                                            src.ctypes.data_as(C.c_void_p), src.nbytes, dst.ctypes.data_as(C.c_void_p), dst.nbytes,
+                                            sres.ctypes.data_as(C.c_void_p), pres.ctypes.data_as(C.c_void_p)))
+        return sres, pres
 
     def flywheel_batch(self, descs, src_arena_bytes, dst_arena_bytes):
         d = np.ascontiguousarray(descs)

@@ -303,8 +303,9 @@ static const struct { const char* noun; void (*release)(ohgpu_ctx*, ohgpu_batch*
     {"DSD", free_dsd_line, true},                 // kBatchDsd
     {"FLAC", flac_free, false},                   // kBatchFlac
     {"DSD to PCM", free_dsd_pcm, true},           // kBatchDsdPcm
+    {"lossless-packet (ALAC)", alac_free, false}, // kBatchAlac
 };
-static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchDsdPcm + 1, "a row per BatchKind");
+static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchAlac + 1, "a row per BatchKind");
 
 int run_guard(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, BatchKind kind, bool empty, bool null_src_ok,
               const void* src_base, const void* dst_base)
@@ -607,7 +608,11 @@ int ohgpu_batch_paths_info(const ohgpu_batch* b, ohgpu_batch_paths* out)
         }
         return OHGPU_OK;
     }
-    if (b->kind != kBatchOhm) return set_error(OHGPU_ERR_INVALID, "ohgpu_batch_paths_info: not a pcm, Songcast frame or fmt batch");
+    if (b->kind == kBatchAlac) {
+        out->alac_route = b->alac && b->alac->plain ? 2u : 1u;
+        return OHGPU_OK;
+    }
+    if (b->kind != kBatchOhm) return set_error(OHGPU_ERR_INVALID, "ohgpu_batch_paths_info: not a pcm, Songcast frame, fmt or Apple Lossless batch");
     const OhmPlan& p = b->ohm;
     if (p.direct) add_line_paths(p.direct->line, out);
     out->ohm_wide_fragments = p.n_selr;

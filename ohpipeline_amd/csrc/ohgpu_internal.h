@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/ohgpu.h"
+#include "alac_packet_core.h"
 #include "flac_frame_core.h"
 
 namespace ohgpu {
@@ -360,6 +361,27 @@ struct FlacState {
     uint32_t n_candidates = 0;
 };
 
+// ---- Apple Lossless packets (csrc/alac_packet_kernel.hip): what a batch keeps between runs; the batch's d_descs holds nothing ----
+struct AlacState {
+    std::vector<alaccore::Stream> streams;            // the descriptors
+    std::vector<alaccore::Packet> packets;            // the table, by stream, with each packet's rows
+    uint32_t n_rows = 0, n_groups = 0, max_frame_length = 0;   // rows with the groups' padding
+    bool     plain = false;                           // created under kernel variant 1
+    void* d_streams = nullptr;                        // alaccore::Stream[n]
+    void* d_packets = nullptr;                        // alaccore::Packet[n_packets]
+    void* d_outs = nullptr;                           // alaccore::PacketOut[n_packets]
+    void* d_chans = nullptr;                          // alaccore::Chan[n_rows]
+    void* d_rowpacket = nullptr;                      // uint32[n_rows]: the row's packet, ~0u for padding
+    void* d_groupbase = nullptr;                      // uint64[n_groups + 1]
+    void* d_rows = nullptr; size_t rows_bytes = 0;    // int32, the groups one after the other
+    bool  rows_cached = false;                        // ... from the context's block cache (else hipMalloc'ed)
+    hipEvent_t ev[4] = {};
+    hipStream_t last_stream = nullptr;
+    bool ran = false;
+};
+static_assert(sizeof(ohgpu_alac_config) == 24 && sizeof(ohgpu_alac_packet) == 16 && sizeof(ohgpu_alac_stream_desc) == 64 && sizeof(ohgpu_alac_stream_result) == 16 && sizeof(ohgpu_alac_packet_result) == 8, "Apple Lossless layouts");
+static_assert(sizeof(alaccore::Stream) == 48 && sizeof(alaccore::Packet) == 32 && sizeof(alaccore::Chan) == 80 && sizeof(alaccore::PacketOut) == sizeof(ohgpu_alac_packet_result), "Apple Lossless device layouts");
+
 // ---- DSD -> PCM (csrc/dsd_pcm_kernel.hip): a batch is cut on the host into tiles of up to kDsdPcmTile consecutive output frames of
 // one message; both kernels loop over them.  The batch's d_descs holds the messages.
 constexpr uint32_t kDsdPcmTile = 512;
@@ -374,7 +396,7 @@ struct DsdPcmPlan {
 };
 static_assert(sizeof(ohgpu_dsd_pcm_msg_desc) == 64, "ohgpu_dsd_pcm_msg_desc layout");
 
-enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9 };
+enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10 };
 
 }  // namespace ohgpu
 
@@ -479,6 +501,7 @@ struct ohgpu_batch {
     ohgpu::DsdPcmPlan dsdpcm;     // kBatchDsdPcm only
     const ohgpu_dsd_pcm* dsdpcm_filter = nullptr;
     ohgpu::FlacState* flac = nullptr;   // kBatchFlac only (what a run changes lives behind the pointer: a run takes a const batch)
+    ohgpu::AlacState* alac = nullptr;   // kBatchAlac only (likewise)
     void*    d_pull_tiles = nullptr;   // kBatchSrcPull: PullTile[n_pull_tiles] on the device (d_descs holds the messages)
     uint32_t n_pull_tiles = 0;
     // kBatchSrc whose messages differ in layout: one uniform batch per layout (each with its own block-kernel plan), run one
@@ -505,7 +528,7 @@ int set_error(int code, const char* fmt, ...);
                                                         hipGetErrorString(e_));                     \
     } while (0)
 
-// The release functions (free_pcm_line, free_fmt_line, free_dsd_line, flac_free, free_flywheel, free_src_fast, free_ohm): what
+// The release functions (free_pcm_line, free_fmt_line, free_dsd_line, flac_free, alac_free, free_flywheel, free_src_fast, free_ohm): what
 // ohgpu_batch_destroy's table calls (csrc/ohgpu_api.hip).  Each takes a PARTLY BUILT batch -- null pointers, a plan that was never
 // made -- and leaves the plan reset: a create that fails at any point hands its batch to ohgpu_batch_destroy and returns.
 // kernels
@@ -538,6 +561,11 @@ void flac_free(ohgpu_ctx* ctx, ohgpu_batch* b);
 int  flac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s, bool plain);
 int  flac_results(ohgpu_ctx* ctx, const ohgpu_batch* b, ohgpu_flac_stream_result* out);
 int  flac_frames(ohgpu_ctx* ctx, const ohgpu_batch* b, ohgpu_flac_frame* out, size_t capacity, size_t* n_frames);
+// csrc/alac_packet_kernel.hip
+int  alac_plan(ohgpu_ctx* ctx, ohgpu_batch* b);                       // the device side of a validated batch (b->alac->streams / packets are filled)
+void alac_free(ohgpu_ctx* ctx, ohgpu_batch* b);
+int  alac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
+int  alac_results(ohgpu_ctx* ctx, const ohgpu_batch* b, ohgpu_alac_packet_result* out);     // every packet's, in the table's order
 // csrc/ohm_frame_kernel.hip: the two wire channels of streams wider than stereo (Sender::DoProcessFragment), one record per fragment
 OhmSelRec wide_record(uint64_t src_off, uint64_t dst_off, uint32_t n_frames, uint32_t channels, uint32_t sb, bool little, uint64_t src_arena_bytes);
 hipError_t launch_ohm_wide(const ohgpu_ctx* ctx, const void* d_recs, uint32_t n_recs, const uint8_t* src, uint8_t* dst, const uint8_t* prefix, hipStream_t s);
