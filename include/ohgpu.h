@@ -29,6 +29,8 @@
  *       (Codec/Flac.cpp:355-443; thirdparty/flac-1.2.1 by its format document)   -> TInt32 planes or CallbackWrite's packed bytes
  *   CodecAlacApple + apple_alac: packets entropy-decoded, predicted, unmixed   ohgpu_alac_batch_run()
  *       (Codec/AlacApple.cpp, AlacAppleBase.cpp:20-115; thirdparty/apple_alac by its behaviour)   -> TInt32 planes or the decoder's packed bytes
+ *   RaopAudioDecryptor::Decrypt + CodecRaopApple: AES-128-CBC per packet, then as above   ohgpu_raop_batch_run()
+ *       (Av/Raop/ProtocolRaop.cpp:1477-1502, Av/Raop/CodecRaopApple.cpp:61-214)          -> the same, or the plaintext alone
  *   "SampleRateConverter" -- NOT PRESENT in the reference  ohgpu_src_* (own spec)
  *
  * The reference binds nothing through FFI today (it is one C++ static library); INTEGRATION.md
@@ -179,7 +181,7 @@ int ohgpu_batch_info(const ohgpu_batch* batch, uint64_t* n_msgs, uint64_t* in_fr
  * plan says.  A fmt batch takes exactly one of five routes: mono / stereo Songcast packs of >= 16 bits as plain PCM messages
  * (line_planned, group_chunks), Songcast packs of wider streams (fmt_wide_records), a uniform stereo batch on a register-only
  * kernel (fmt_stereo_*), the staged layout kernel (fmt_staged_chunks), or, with every count zero, the generic kernel only.
- * An Apple Lossless batch (ohgpu_alac_batch_create) answers with alac_route alone.  OHGPU_ERR_INVALID for any other kind of batch. */
+ * An Apple Lossless batch (ohgpu_alac_batch_create) answers with alac_route alone, and so does a RAOP batch.  OHGPU_ERR_INVALID for any other kind of batch. */
 typedef struct ohgpu_batch_paths {       /* 64 bytes */
     uint32_t line_planned;          /* 1: the line kernel has a plan for the batch (0: only the generic kernel can run it) */
     uint32_t launches;              /* line-kernel launches per run: one per layout present (8-bit / silence, and each 16/24/32-bit depth pair) */
@@ -548,6 +550,66 @@ int ohgpu_alac_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float ms
 /* Host-buffer convenience, as ohgpu_flac_process_host: one upload, one run.  Of dst_host only the samples of packets that decoded
  * are written.  Either result pointer may be NULL. */
 int ohgpu_alac_process_host(ohgpu_ctx* ctx, const ohgpu_alac_stream_desc* descs, size_t n, const ohgpu_alac_packet* packets, size_t n_packets,
+                            const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes,
+                            ohgpu_alac_stream_result* stream_results, ohgpu_alac_packet_result* packet_results);
+
+/* ---- RAOP (AirPlay) audio: AES-128-CBC decryption in front of the Apple Lossless decoder (the cipher's text is
+ * csrc/raop_aes_core.h, written from FIPS-197) ----
+ * ProtocolRaop::OutputAudio (Av/Raop/ProtocolRaop.cpp:705-743) passes every audio packet through RaopAudioDecryptor::Decrypt
+ * (:1477-1502) before CodecRaopApple sees it: AES-128-CBC under the session key, the IV starting again with EVERY packet, the
+ * bytes % 16 tail left as sent; a packet shorter than 16 bytes is all tail and a packet of 0 bytes is nothing.  Here that is one more
+ * phase in front of ohgpu_alac_*'s three, a lane per 16-byte block (CBC decryption has no chain), into a plaintext scratch the batch
+ * owns; the host never touches a payload byte.  The packet table is ohgpu_alac_packet: src_offset and bytes name the ENCRYPTED
+ * PAYLOAD, what follows the 12 header bytes of the datagram (RtpPacketRaop: 4, RaopPacketAudio: 8).
+ * Alignment: every packet's src_offset is a multiple of 4 (OHGPU_ERR_INVALID otherwise) -- with the 12-byte header in front of a
+ * payload that costs a caller who places datagrams at multiples of 4 nothing.  All other limits are ohgpu_alac_*'s.
+ * A stream whose alac.flags is 0, OHGPU_ALAC_OUT_PACKED_LE or _BE is decoded: results, statuses and the meaning of a failed packet
+ * are exactly ohgpu_alac_*'s (a wrong key yields bytes that the decoder judges like any others).
+ * A stream whose alac.flags is OHGPU_RAOP_OUT_PLAINTEXT is decrypted only (the decryptor alone, for a caller with its own decoder):
+ * the plaintext of packet p lands at dst_offset + (src_offset of p - src_offset of the stream's first packet) -- the source layout
+ * moved, so the alignment carries over --; bytes between packets are not written; its packets must ascend without overlap
+ * (OHGPU_ERR_INVALID), dst_offset is a multiple of 4, dst_plane_stride is 0, alac.config is not read and no packet-size limit
+ * applies; every packet's result is OHGPU_ALAC_OK with samples 0.  A batch may mix both kinds.
+ * The RSA unwrap of the session key, RTSP / SDP, the control and timing ports and resend / repair stay the caller's. */
+#define OHGPU_RAOP_OUT_PLAINTEXT 0x04u   /* in alac.flags: no decode */
+
+typedef struct ohgpu_raop_stream_desc {  /* 96 bytes */
+    ohgpu_alac_stream_desc alac;         /* config, packet range, destination, output form: as for ohgpu_alac_* */
+    uint8_t aes_key[16];                 /* the session key as sent (after the RSA unwrap, which is the caller's) */
+    uint8_t aes_iv[16];
+} ohgpu_raop_stream_desc;
+
+/* Host only, no device needed: the SDP fmtp string as CodecRaopApple::ParseFmtp reads it (CodecRaopApple.cpp:173-214): twelve decimal
+ * fields separated by blanks -- field 0 is ignored, fields 1..11 are frame_length, compatible_version, bit_depth, pb, mb, kb,
+ * channels, max_run, max_frame_bytes, avg_bit_rate, sample_rate ("96 352 0 16 40 10 14 2 255 0 0 44100").  Fields behind the
+ * twelfth are ignored, as there.  OHGPU_ERR_INVALID: fewer fields, a field that is no decimal number, a compatible version other
+ * than 0, or a value that does not fit its field -- THE ONE DEVIATION: the reference truncates such a value through WriteUint8 /
+ * WriteUint16Be and goes on with the wrong configuration. */
+int ohgpu_raop_fmtp_parse(const char* fmtp, size_t n, ohgpu_alac_config* config);
+/* Host only, no device needed: the validation ohgpu_raop_batch_create makes, with its codes and ohgpu_last_error() texts. */
+int ohgpu_raop_batch_check(const ohgpu_raop_stream_desc* descs, size_t n, const ohgpu_alac_packet* packets, size_t n_packets,
+                           uint64_t src_arena_bytes, uint64_t dst_arena_bytes);
+/* As ohgpu_alac_batch_create (its codes, its two routes for the Apple Lossless part: ohgpu_batch_paths_info answers alac_route as
+ * for an Apple Lossless batch; the decrypt kernel is the same on both).  The key schedules (176 bytes a stream) are made here, on
+ * the host, and live in one device array of the batch; ohgpu_batch_destroy clears that array and its host copy before the block
+ * goes back to the context's cache.  The work table -- a record per piece of up to 64 blocks of one packet -- is made here from the
+ * validated packet table: nothing the device later reads or writes lies outside what this call checked. */
+int ohgpu_raop_batch_create(ohgpu_ctx* ctx, const ohgpu_raop_stream_desc* descs, size_t n, const ohgpu_alac_packet* packets, size_t n_packets,
+                            uint64_t src_arena_bytes, uint64_t dst_arena_bytes, ohgpu_batch** batch);
+/* src_base AND dst_base MUST BE 4-BYTE ALIGNED (the kernel loads and stores dwords): OHGPU_ERR_INVALID otherwise, before anything is
+ * queued.  Decrypt (into the batch's scratch, each packet at a 16-byte boundary; plaintext streams straight into the destination),
+ * then entropy, predictor, matrix and store over that scratch: one stream, nothing waits for the host.  A second run, and a second
+ * batch of the same shape, allocate nothing (ohgpu_device_allocations). */
+int ohgpu_raop_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* src_base, void* dst_base, void* stream);
+/* As ohgpu_alac_batch_results, over the caller's packet table. */
+int ohgpu_raop_batch_results(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_alac_stream_result* streams, size_t n,
+                             ohgpu_alac_packet_result* packets, size_t n_packets);
+/* The last run's phases in milliseconds from device events: decrypt, entropy, predictor, matrix and store (waits for that run).  On
+ * the plain route the three Apple Lossless phases are one: the other two read as 0. */
+int ohgpu_raop_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float ms[4]);
+/* Host-buffer convenience, as ohgpu_alac_process_host: one upload, one run.  Of dst_host only the samples of packets that decoded,
+ * and the plaintext streams' packets, are written.  src_host is copied to a device arena, so its own alignment is free. */
+int ohgpu_raop_process_host(ohgpu_ctx* ctx, const ohgpu_raop_stream_desc* descs, size_t n, const ohgpu_alac_packet* packets, size_t n_packets,
                             const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes,
                             ohgpu_alac_stream_result* stream_results, ohgpu_alac_packet_result* packet_results);
 

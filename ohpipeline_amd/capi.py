@@ -94,6 +94,11 @@ ALAC_STREAM_DESC = np.dtype(_ALAC_CONFIG_FIELDS + [("first_packet", "<u4"), ("n_
 ALAC_PACKET_RESULT = np.dtype([("status", "<u4"), ("samples", "<u4")], align=False)
 ALAC_STREAM_RESULT = np.dtype([("packets_ok", "<u4"), ("first_bad_status", "<u4"), ("samples", "<u8")], align=False)
 assert ALAC_CONFIG.itemsize == 24 and ALAC_PACKET.itemsize == 16 and ALAC_STREAM_DESC.itemsize == 64 and ALAC_STREAM_RESULT.itemsize == 16
+# RAOP audio: ohgpu_raop_stream_desc (96 B) = an ohgpu_alac_stream_desc, the session's AES key and IV; the packet
+# table, the results and the routes are Apple Lossless's
+RAOP_OUT_PLAINTEXT = 4
+RAOP_STREAM_DESC = np.dtype(ALAC_STREAM_DESC.descr + [("aes_key", "u1", (16,)), ("aes_iv", "u1", (16,))], align=False)
+assert RAOP_STREAM_DESC.itemsize == 96
 
 BATCH_PATHS = np.dtype([(k, "<u4") for k in ("line_planned", "launches", "staged_chunks", "group_chunks", "heavy_chunks",
                                             "prefixed_chunks", "ohm_wide_fragments", "ohm_staged_fragments", "ohm_headers_fused",
@@ -185,6 +190,13 @@ SYMBOLS = {
     "ohgpu_alac_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t]),
     "ohgpu_alac_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
     "ohgpu_alac_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
+    "ohgpu_raop_fmtp_parse": (C.c_int, [C.c_char_p, C.c_size_t, _vp]),
+    "ohgpu_raop_batch_check": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, C.c_uint64, C.c_uint64]),
+    "ohgpu_raop_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
+    "ohgpu_raop_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "ohgpu_raop_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t]),
+    "ohgpu_raop_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
+    "ohgpu_raop_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
     "ohgpu_flywheel_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
     "ohgpu_flywheel_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "ohgpu_flywheel_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64]),
@@ -412,6 +424,26 @@ def alac_batch_check(descs, packets, src_arena_bytes, dst_arena_bytes):
     """The validation of ctx.alac_batch without a device (ohgpu_alac_batch_check): OhGpuError on a bad descriptor."""
     d, p = _alac_tables(descs, packets)
     check(lib().ohgpu_alac_batch_check(d.ctypes.data_as(C.c_void_p), d.size, p.ctypes.data_as(C.c_void_p), p.size, src_arena_bytes, dst_arena_bytes))
+
+
+def raop_fmtp_parse(fmtp):
+    """The stream configuration (ALAC_CONFIG, one record) of an SDP fmtp string (ohgpu_raop_fmtp_parse; host only)."""
+    raw = fmtp.encode("ascii") if isinstance(fmtp, str) else bytes(fmtp)
+    cfg = np.zeros(1, dtype=ALAC_CONFIG)
+    check(lib().ohgpu_raop_fmtp_parse(raw, len(raw), cfg.ctypes.data_as(C.c_void_p)))
+    return cfg[0]
+
+
+def _raop_tables(descs, packets):
+    d, p = np.ascontiguousarray(descs), np.ascontiguousarray(packets)
+    assert d.dtype == RAOP_STREAM_DESC and p.dtype == ALAC_PACKET
+    return d, p
+
+
+def raop_batch_check(descs, packets, src_arena_bytes, dst_arena_bytes):
+    """The validation of ctx.raop_batch without a device (ohgpu_raop_batch_check): OhGpuError on a bad descriptor."""
+    d, p = _raop_tables(descs, packets)
+    check(lib().ohgpu_raop_batch_check(d.ctypes.data_as(C.c_void_p), d.size, p.ctypes.data_as(C.c_void_p), p.size, src_arena_bytes, dst_arena_bytes))
 
 
 def flac_batch_check(descs, src_arena_bytes, dst_arena_bytes):
@@ -704,6 +736,39 @@ class Context:
         d, p = _alac_tables(descs, packets)
         sres, pres = np.zeros(d.size, dtype=ALAC_STREAM_RESULT), np.zeros(p.size, dtype=ALAC_PACKET_RESULT)
         check(lib().ohgpu_alac_process_host(self._h, d.ctypes.data_as(C.c_void_p), d.size, p.ctypes.data_as(C.c_void_p), p.size,
+                                            src.ctypes.data_as(C.c_void_p), src.nbytes, dst.ctypes.data_as(C.c_void_p), dst.nbytes,
+                                            sres.ctypes.data_as(C.c_void_p), pres.ctypes.data_as(C.c_void_p)))
+        return sres, pres
+
+    def raop_batch(self, descs, packets, src_arena_bytes, dst_arena_bytes):
+        d, p = _raop_tables(descs, packets)
+        b = C.c_void_p()
+        check(lib().ohgpu_raop_batch_create(self._h, d.ctypes.data_as(C.c_void_p), d.size, p.ctypes.data_as(C.c_void_p), p.size,
+                                            src_arena_bytes, dst_arena_bytes, C.byref(b)))
+        return b
+
+    def raop_run(self, batch, d_src, d_dst, stream=None):
+        """Decrypt, then entropy, predictor, matrix and store (ohgpu_raop_batch_run): queued on the stream; both bases 4-byte aligned."""
+        check(lib().ohgpu_raop_batch_run(self._h, batch, d_src, d_dst, stream))
+
+    def raop_results(self, batch, n, n_packets):
+        """The last run's (ALAC_STREAM_RESULT per stream, ALAC_PACKET_RESULT per packet); waits for the run."""
+        sres, pres = np.zeros(n, dtype=ALAC_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET_RESULT)
+        check(lib().ohgpu_raop_batch_results(self._h, batch, sres.ctypes.data_as(C.c_void_p) if n else None, n,
+                                             pres.ctypes.data_as(C.c_void_p) if n_packets else None, n_packets))
+        return sres, pres
+
+    def raop_phase_ms(self, batch):
+        """The last run's (decrypt, entropy, predictor, matrix and store) in milliseconds, from device events."""
+        ms = (C.c_float * 4)()
+        check(lib().ohgpu_raop_batch_phase_ms(self._h, batch, ms))
+        return tuple(float(v) for v in ms)
+
+    def raop_process_host(self, descs, packets, src, dst):
+        """Host buffers in and out (ohgpu_raop_process_host); returns (stream results, packet results)."""
+        d, p = _raop_tables(descs, packets)
+        sres, pres = np.zeros(d.size, dtype=ALAC_STREAM_RESULT), np.zeros(p.size, dtype=ALAC_PACKET_RESULT)
+        check(lib().ohgpu_raop_process_host(self._h, d.ctypes.data_as(C.c_void_p), d.size, p.ctypes.data_as(C.c_void_p), p.size,
                                             src.ctypes.data_as(C.c_void_p), src.nbytes, dst.ctypes.data_as(C.c_void_p), dst.nbytes,
                                             sres.ctypes.data_as(C.c_void_p), pres.ctypes.data_as(C.c_void_p)))
         return sres, pres

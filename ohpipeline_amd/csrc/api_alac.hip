@@ -5,9 +5,9 @@
 
 using namespace ohgpu;
 
-extern "C" {
+namespace ohgpu {
 
-static int alac_check_desc(const ohgpu_alac_stream_desc& d, size_t i, const ohgpu_alac_packet* packets, uint64_t next_packet, size_t n_packets,
+int alac_check_desc(const ohgpu_alac_stream_desc& d, size_t i, const ohgpu_alac_packet* packets, uint64_t next_packet, size_t n_packets,
                            uint64_t src_arena_bytes, uint64_t dst_arena_bytes)
 {
     const ohgpu_alac_config& c = d.config;
@@ -42,6 +42,54 @@ static int alac_check_desc(const ohgpu_alac_stream_desc& d, size_t i, const ohgp
     }
     return arena_span("alac desc", i, "writes", d.dst_offset, span, dst_arena_bytes, "destination");
 }
+
+void alac_add_stream(AlacState& a, size_t i, const ohgpu_alac_stream_desc& d)
+{
+    alaccore::Stream& s = a.streams[i];
+    memset(&s, 0, sizeof(s));
+    s.dst_offset = d.dst_offset; s.dst_plane_stride = d.dst_plane_stride; s.first_packet = d.first_packet; s.n_packets = d.n_packets;
+    s.frame_length = d.config.frame_length; s.sample_rate = d.config.sample_rate; s.max_run = d.config.max_run;
+    s.bit_depth = d.config.bit_depth; s.pb = d.config.pb; s.mb = d.config.mb; s.kb = d.config.kb; s.channels = d.config.channels;
+    s.flags = (uint8_t)d.flags;
+}
+
+int alac_download_decoded(ohgpu_ctx* ctx, const char* who, const ohgpu_alac_stream_desc& d, const ohgpu_alac_packet_result* pres, void* dst_host)
+{
+    HostStage& st = ctx->stage;
+    const uint32_t fl = d.config.frame_length;
+    const uint64_t unit = d.flags ? (uint64_t)d.config.channels * (d.config.bit_depth / 8u) : 4u;
+    for (uint32_t k = 0; k < d.n_packets;) {
+        if (pres[k].status != OHGPU_ALAC_OK) { k++; continue; }
+        const uint32_t k0 = k;
+        uint64_t samples = 0;
+        for (;;) {
+            const uint32_t got = pres[k].samples;
+            samples = (uint64_t)(k - k0) * fl + got;
+            k++;
+            if (got != fl || k == d.n_packets || pres[k].status != OHGPU_ALAC_OK) break;
+        }
+        if (samples == 0) continue;
+        for (uint32_t c = 0; c < (d.flags ? 1u : d.config.channels); c++) {
+            const uint64_t off = d.dst_offset + c * d.dst_plane_stride + (uint64_t)k0 * fl * unit, bytes = samples * unit;
+            if (hipMemcpyAsync((uint8_t*)dst_host + off, (const uint8_t*)st.d_dst + off, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+                return set_error(OHGPU_ERR_DEVICE, "%s: download failed", who);
+            st.d2h_bytes += bytes;
+        }
+    }
+    return OHGPU_OK;
+}
+
+void alac_summarise(const ohgpu_alac_packet_result* pres, uint32_t n_packets, ohgpu_alac_stream_result* out)
+{
+    ohgpu_alac_stream_result r = {0, 0, 0};
+    while (r.packets_ok < n_packets && pres[r.packets_ok].status == OHGPU_ALAC_OK) r.samples += pres[r.packets_ok++].samples;
+    if (r.packets_ok < n_packets) r.first_bad_status = pres[r.packets_ok].status;
+    *out = r;
+}
+
+}  // namespace ohgpu
+
+extern "C" {
 
 int ohgpu_alac_config_parse(const void* bytes, size_t n, ohgpu_alac_config* config)
 {
@@ -92,12 +140,7 @@ int ohgpu_alac_batch_create(ohgpu_ctx* ctx, const ohgpu_alac_stream_desc* descs,
     a.packets.resize(n_packets);
     for (size_t i = 0; i < n; i++) {
         const ohgpu_alac_stream_desc& d = descs[i];
-        alaccore::Stream& s = a.streams[i];
-        memset(&s, 0, sizeof(s));
-        s.dst_offset = d.dst_offset; s.dst_plane_stride = d.dst_plane_stride; s.first_packet = d.first_packet; s.n_packets = d.n_packets;
-        s.frame_length = d.config.frame_length; s.sample_rate = d.config.sample_rate; s.max_run = d.config.max_run;
-        s.bit_depth = d.config.bit_depth; s.pb = d.config.pb; s.mb = d.config.mb; s.kb = d.config.kb; s.channels = d.config.channels;
-        s.flags = (uint8_t)d.flags;
+        alac_add_stream(a, i, d);
         for (uint32_t k = 0; k < d.n_packets; k++) {
             alaccore::Packet& p = a.packets[d.first_packet + k];
             memset(&p, 0, sizeof(p));
@@ -131,10 +174,7 @@ int ohgpu_alac_batch_results(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_ala
     if (packets && !all.empty()) memcpy(packets, all.data(), all.size() * sizeof(all[0]));
     for (size_t i = 0; streams && i < batch->n; i++) {
         const alaccore::Stream& s = a.streams[i];
-        ohgpu_alac_stream_result r = {0, 0, 0};
-        while (r.packets_ok < s.n_packets && all[s.first_packet + r.packets_ok].status == OHGPU_ALAC_OK) r.samples += all[s.first_packet + r.packets_ok++].samples;
-        if (r.packets_ok < s.n_packets) r.first_bad_status = all[s.first_packet + r.packets_ok].status;
-        streams[i] = r;
+        alac_summarise(all.data() + s.first_packet, s.n_packets, &streams[i]);
     }
     return OHGPU_OK;
 }
@@ -169,28 +209,7 @@ int ohgpu_alac_process_host(ohgpu_ctx* ctx, const ohgpu_alac_stream_desc* descs,
     if (err == OHGPU_OK && n_packets) err = ohgpu_alac_batch_results(ctx, b, n ? sres.data() : nullptr, n, pres.data(), n_packets);
     if (err != OHGPU_OK) { (void)hipStreamSynchronize(s); return err; }
     // only what was decoded comes back: per stream, each run of packets that decoded (whole ones, then perhaps a short one) in one copy per plane
-    for (size_t i = 0; i < n && err == OHGPU_OK; i++) {
-        const ohgpu_alac_stream_desc& d = descs[i];
-        const uint32_t fl = d.config.frame_length;
-        const uint64_t unit = d.flags ? (uint64_t)d.config.channels * (d.config.bit_depth / 8u) : 4u;
-        for (uint32_t k = 0; k < d.n_packets && err == OHGPU_OK;) {
-            if (pres[d.first_packet + k].status != OHGPU_ALAC_OK) { k++; continue; }
-            const uint32_t k0 = k;
-            uint64_t samples = 0;
-            for (;;) {
-                const uint32_t got = pres[d.first_packet + k].samples;
-                samples = (uint64_t)(k - k0) * fl + got;
-                k++;
-                if (got != fl || k == d.n_packets || pres[d.first_packet + k].status != OHGPU_ALAC_OK) break;
-            }
-            if (samples == 0) continue;
-            for (uint32_t c = 0; c < (d.flags ? 1u : d.config.channels); c++) {
-                const uint64_t off = d.dst_offset + c * d.dst_plane_stride + (uint64_t)k0 * fl * unit, bytes = samples * unit;
-                if (hipMemcpyAsync((uint8_t*)dst_host + off, (const uint8_t*)st.d_dst + off, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) { err = set_error(OHGPU_ERR_DEVICE, "ohgpu_alac_process_host: download failed"); break; }
-                st.d2h_bytes += bytes;
-            }
-        }
-    }
+    for (size_t i = 0; i < n && err == OHGPU_OK; i++) err = alac_download_decoded(ctx, "ohgpu_alac_process_host", descs[i], pres.data() + descs[i].first_packet, dst_host);
     if (hipStreamSynchronize(s) != hipSuccess && err == OHGPU_OK) err = set_error(OHGPU_ERR_DEVICE, "ohgpu_alac_process_host: hipStreamSynchronize failed");
     if (err == OHGPU_OK && stream_results && n) memcpy(stream_results, sres.data(), n * sizeof(sres[0]));
     if (err == OHGPU_OK && packet_results && n_packets) memcpy(packet_results, pres.data(), n_packets * sizeof(pres[0]));

@@ -81,5 +81,14 @@ int process_host(ohgpu_ctx* ctx, ohgpu_batch* batch, size_t n, const void* src_h
 template <typename D>
 std::pair<uint64_t, uint64_t> frames_range(const D& d) { return {d.dst_offset, (uint64_t)d.n_frames * d.channels * (d.dst_bits / 8)}; }
 
+// ---- Apple Lossless (api_alac.hip), shared with RAOP (api_raop.hip), whose decoding streams are Apple Lossless streams behind a cipher:
+// one descriptor's validation (its packets [next_packet, +n_packets) of the table), its device-side record, the summary of a stream's
+// packet results, and the download of what a stream decoded (of process_host; queued on the context's stream, not waited for).
+int  alac_check_desc(const ohgpu_alac_stream_desc& d, size_t i, const ohgpu_alac_packet* packets, uint64_t next_packet, size_t n_packets,
+                     uint64_t src_arena_bytes, uint64_t dst_arena_bytes);
+void alac_add_stream(AlacState& a, size_t i, const ohgpu_alac_stream_desc& d);
+void alac_summarise(const ohgpu_alac_packet_result* pres, uint32_t n_packets, ohgpu_alac_stream_result* out);
+int  alac_download_decoded(ohgpu_ctx* ctx, const char* who, const ohgpu_alac_stream_desc& d, const ohgpu_alac_packet_result* pres, void* dst_host);
+
 }  // namespace ohgpu
 #pragma GCC visibility pop

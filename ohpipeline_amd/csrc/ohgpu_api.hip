@@ -304,8 +304,9 @@ static const struct { const char* noun; void (*release)(ohgpu_ctx*, ohgpu_batch*
     {"FLAC", flac_free, false},                   // kBatchFlac
     {"DSD to PCM", free_dsd_pcm, true},           // kBatchDsdPcm
     {"lossless-packet (ALAC)", alac_free, false}, // kBatchAlac
+    {"RAOP", raop_free, false},                   // kBatchRaop
 };
-static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchAlac + 1, "a row per BatchKind");
+static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchRaop + 1, "a row per BatchKind");
 
 int run_guard(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, BatchKind kind, bool empty, bool null_src_ok,
               const void* src_base, const void* dst_base)
@@ -608,7 +609,7 @@ int ohgpu_batch_paths_info(const ohgpu_batch* b, ohgpu_batch_paths* out)
         }
         return OHGPU_OK;
     }
-    if (b->kind == kBatchAlac) {
+    if (b->kind == kBatchAlac || b->kind == kBatchRaop) {
         out->alac_route = b->alac && b->alac->plain ? 2u : 1u;
         return OHGPU_OK;
     }

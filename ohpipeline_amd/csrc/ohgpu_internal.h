@@ -19,6 +19,7 @@
 #include "../../include/ohgpu.h"
 #include "alac_packet_core.h"
 #include "flac_frame_core.h"
+#include "raop_aes_core.h"
 
 namespace ohgpu {
 
@@ -382,6 +383,22 @@ struct AlacState {
 static_assert(sizeof(ohgpu_alac_config) == 24 && sizeof(ohgpu_alac_packet) == 16 && sizeof(ohgpu_alac_stream_desc) == 64 && sizeof(ohgpu_alac_stream_result) == 16 && sizeof(ohgpu_alac_packet_result) == 8, "Apple Lossless layouts");
 static_assert(sizeof(alaccore::Stream) == 48 && sizeof(alaccore::Packet) == 32 && sizeof(alaccore::Chan) == 80 && sizeof(alaccore::PacketOut) == sizeof(ohgpu_alac_packet_result), "Apple Lossless device layouts");
 
+// ---- RAOP audio (csrc/raop_decrypt_kernel.hip): the decrypt phase in front of an AlacState.  The batch's AlacState
+// holds the DECODING streams only, their packets rewritten to where the decrypt phase leaves them in the plaintext scratch. ----
+struct RaopState {
+    std::vector<uint32_t> keys;                       // raopcore::kKeyWords words per stream: the schedule, the IV (cleared in raop_free)
+    std::vector<int64_t>  alac_packet;                // per packet of the caller's table: its place in the AlacState's, -1 for a plaintext stream's
+    std::vector<uint32_t> alac_first;                 // per stream: its first packet in the AlacState's table (decoding streams)
+    std::vector<uint8_t>  plaintext;                  // per stream: OHGPU_RAOP_OUT_PLAINTEXT
+    std::vector<uint32_t> first_packet, n_packets;    // per stream, in the caller's table
+    uint32_t n_pieces = 0;
+    void* d_pieces = nullptr;                         // raopcore::Piece[n_pieces]
+    void* d_keys = nullptr; size_t keys_bytes = 0;    // uint32[n * kKeyWords]
+    void* d_plain = nullptr; size_t plain_bytes = 0;  // the plaintext scratch: every decoding packet at a 16-byte boundary
+    hipEvent_t ev0 = nullptr;                         // before the decrypt phase (the AlacState's ev[0] is behind it)
+};
+static_assert(sizeof(ohgpu_raop_stream_desc) == 96 && sizeof(raopcore::Piece) == 32 && sizeof(raopcore::Job) == 32, "RAOP layouts");
+
 // ---- DSD -> PCM (csrc/dsd_pcm_kernel.hip): a batch is cut on the host into tiles of up to kDsdPcmTile consecutive output frames of
 // one message; both kernels loop over them.  The batch's d_descs holds the messages.
 constexpr uint32_t kDsdPcmTile = 512;
@@ -396,7 +413,7 @@ struct DsdPcmPlan {
 };
 static_assert(sizeof(ohgpu_dsd_pcm_msg_desc) == 64, "ohgpu_dsd_pcm_msg_desc layout");
 
-enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10 };
+enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11 };
 
 }  // namespace ohgpu
 
@@ -501,7 +518,8 @@ struct ohgpu_batch {
     ohgpu::DsdPcmPlan dsdpcm;     // kBatchDsdPcm only
     const ohgpu_dsd_pcm* dsdpcm_filter = nullptr;
     ohgpu::FlacState* flac = nullptr;   // kBatchFlac only (what a run changes lives behind the pointer: a run takes a const batch)
-    ohgpu::AlacState* alac = nullptr;   // kBatchAlac only (likewise)
+    ohgpu::AlacState* alac = nullptr;   // kBatchAlac and kBatchRaop (likewise)
+    ohgpu::RaopState* raop = nullptr;   // kBatchRaop only
     void*    d_pull_tiles = nullptr;   // kBatchSrcPull: PullTile[n_pull_tiles] on the device (d_descs holds the messages)
     uint32_t n_pull_tiles = 0;
     // kBatchSrc whose messages differ in layout: one uniform batch per layout (each with its own block-kernel plan), run one
@@ -528,7 +546,7 @@ int set_error(int code, const char* fmt, ...);
                                                         hipGetErrorString(e_));                     \
     } while (0)
 
-// The release functions (free_pcm_line, free_fmt_line, free_dsd_line, flac_free, alac_free, free_flywheel, free_src_fast, free_ohm): what
+// The release functions (free_pcm_line, free_fmt_line, free_dsd_line, flac_free, alac_free, raop_free, free_flywheel, free_src_fast, free_ohm): what
 // ohgpu_batch_destroy's table calls (csrc/ohgpu_api.hip).  Each takes a PARTLY BUILT batch -- null pointers, a plan that was never
 // made -- and leaves the plan reset: a create that fails at any point hands its batch to ohgpu_batch_destroy and returns.
 // kernels
@@ -566,6 +584,11 @@ int  alac_plan(ohgpu_ctx* ctx, ohgpu_batch* b);                       // the dev
 void alac_free(ohgpu_ctx* ctx, ohgpu_batch* b);
 int  alac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
 int  alac_results(ohgpu_ctx* ctx, const ohgpu_batch* b, ohgpu_alac_packet_result* out);     // every packet's, in the table's order
+// csrc/raop_decrypt_kernel.hip
+const raopcore::Tables& raop_tables();                                // the host's copy of the computed tables (the key schedule is made on the host)
+int  raop_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const raopcore::Job* jobs, size_t n_jobs);   // pieces, keys and scratch onto the device (b->raop is filled)
+void raop_free(ohgpu_ctx* ctx, ohgpu_batch* b);                       // clears the keys, then alac_free
+int  raop_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);   // the decrypt phase alone
 // csrc/ohm_frame_kernel.hip: the two wire channels of streams wider than stereo (Sender::DoProcessFragment), one record per fragment
 OhmSelRec wide_record(uint64_t src_off, uint64_t dst_off, uint32_t n_frames, uint32_t channels, uint32_t sb, bool little, uint64_t src_arena_bytes);
 hipError_t launch_ohm_wide(const ohgpu_ctx* ctx, const void* d_recs, uint32_t n_recs, const uint8_t* src, uint8_t* dst, const uint8_t* prefix, hipStream_t s);
