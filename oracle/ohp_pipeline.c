@@ -229,6 +229,26 @@ ohp_src* ohp_src_new(uint32_t rate_in, uint32_t rate_out, uint32_t T, double bet
     return s;
 }
 void ohp_src_delete(ohp_src* s) { if (s) { ohp_src_free(s); free(s); } }
+/* another filter of the same L, M and T: L * T Q28 coefficients, phase-major (for the integer model; coef_f64 follows) */
+int ohp_src_set_coef_q28(ohp_src* s, const int32_t* coef_q28)
+{
+    int64_t sum_abs_max = 0;
+    for (uint32_t p = 0; p < s->L; p++) {
+        int64_t sabs = 0;
+        for (uint32_t k = 0; k < s->T; k++) {
+            const int64_t q = coef_q28[(size_t)p * s->T + k];
+            sabs += q < 0 ? -q : q;
+        }
+        if (sabs > sum_abs_max) sum_abs_max = sabs;
+    }
+    if (sum_abs_max >= ((int64_t)1 << 30)) return OHP_ERR_ASSERT;      /* the bound of ohp_src_design */
+    for (size_t i = 0; i < (size_t)s->L * s->T; i++) {
+        s->coef_q28[i] = coef_q28[i];
+        s->coef_f64[i] = (double)coef_q28[i] / 268435456.0;
+    }
+    s->sum_abs_max = sum_abs_max;
+    return OHP_OK;
+}
 uint32_t ohp_src_L(const ohp_src* s) { return s->L; }
 uint32_t ohp_src_M(const ohp_src* s) { return s->M; }
 uint32_t ohp_src_T(const ohp_src* s) { return s->T; }

@@ -61,6 +61,7 @@ int ohp_src_msg_process_f64(const ohp_src* s, const ohp_src_msg_desc* d, const u
 
 ohp_src*       ohp_src_new(uint32_t rate_in, uint32_t rate_out, uint32_t T, double beta, double f_pass);
 void           ohp_src_delete(ohp_src* s);
+int            ohp_src_set_coef_q28(ohp_src* s, const int32_t* coef_q28);   /* L * T values; sum|c| < 2^30 per phase */
 uint32_t       ohp_src_L(const ohp_src* s);
 uint32_t       ohp_src_M(const ohp_src* s);
 uint32_t       ohp_src_T(const ohp_src* s);

@@ -146,6 +146,7 @@ def lib():
         "ohp_src_msg_process_f64": (C.c_int, [vp, vp, vp, vp]),
         "ohp_src_new": (vp, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double]),
         "ohp_src_delete": (None, [vp]),
+        "ohp_src_set_coef_q28": (C.c_int, [vp, vp]),
         "ohp_src_L": (C.c_uint32, [vp]), "ohp_src_M": (C.c_uint32, [vp]), "ohp_src_T": (C.c_uint32, [vp]),
         "ohp_src_coef_q28": (i32p, [vp]), "ohp_src_coef_f64": (f64p, [vp]),
         "ohp_src_sum_abs_max": (C.c_int64, [vp]), "ohp_src_f_stop": (C.c_double, [vp]),
@@ -245,6 +246,15 @@ class Src:
         self.coef_f64 = np.ctypeslib.as_array(L.ohp_src_coef_f64(self.h), shape=(n,)).copy()
         self.sum_abs_max = L.ohp_src_sum_abs_max(self.h)
         self.f_stop = L.ohp_src_f_stop(self.h)
+
+    def set_coef_q28(self, coef_q28):
+        """Another filter of the same L, M and T for the integer model (L * T values, phase-major)."""
+        coef = np.ascontiguousarray(coef_q28, dtype=np.int32)
+        assert coef.size == self.L * self.T
+        if lib().ohp_src_set_coef_q28(self.h, _ptr(coef)) != 0:
+            raise ValueError("a phase has sum|c| >= 2^30")
+        self.coef_q28, self.coef_f64 = coef.copy(), coef / 268435456.0
+        self.sum_abs_max = lib().ohp_src_sum_abs_max(self.h)
 
     def out_frames(self, in_frames):
         return int(lib().ohp_src_out_frames(self.h, in_frames))

@@ -49,18 +49,17 @@ wrong bytes inside the arenas only):
 (A mutation of a tuned kernel left every variant-1 case green, and a mutation of fmt_kernel_v1 every tuned case that the planner does
 not itself hand to fmt_kernel_v1, as it should be: each is held to the model, not to the other.)
 """
-import functools
 import hashlib
 import itertools
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 import fmt_textbook as FT
+from device_shape import compute_units
 from ohpipeline_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -89,19 +88,6 @@ def vctx(ctx, request):
     ctx.set_kernel_variant(request.param)
     yield ctx
     ctx.set_kernel_variant(0)
-
-
-@functools.lru_cache(maxsize=None)
-def compute_units():
-    """The device's CU count, from torch in a child process (torch brings a HIP runtime of its own, and a process that has loaded
-    the library first cannot use it: tests/test_gpu_torch_interop.py).  Asked once per run; the limit allows for torch's cold
-    import (some ten seconds at worst), and a failure names its cause in one line."""
-    out = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.get_device_properties(0).multi_processor_count)"],
-                         capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, "the CU count could not be read through torch: " + (out.stderr.strip().splitlines() or ["?"])[-1]
-    cus = int(out.stdout.split()[-1])
-    assert 1 <= cus <= 4096
-    return cus
 
 
 def frames_per_chunk(kind, ch, width):
