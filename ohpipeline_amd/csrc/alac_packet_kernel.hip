@@ -97,12 +97,6 @@ __global__ __launch_bounds__(kAlacLanes) void alac_plain_kernel(const Stream* __
     outs[i] = o;
 }
 
-#define ALAC_TRY(expr)                                                                                                             \
-    do {                                                                                                                           \
-        const hipError_t e_ = (expr);                                                                                              \
-        if (e_ != hipSuccess) return set_error(e_ == hipErrorOutOfMemory ? OHGPU_ERR_NOMEM : OHGPU_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 int alac_plan(ohgpu_ctx* ctx, ohgpu_batch* b)
 {
     AlacState& a = *b->alac;
@@ -112,27 +106,21 @@ int alac_plan(ohgpu_ctx* ctx, ohgpu_batch* b)
     a.n_rows = (uint32_t)row_packet.size();
     a.n_groups = (uint32_t)group_base.size() - 1u;
     for (const Stream& s : a.streams) if (s.n_packets) a.max_frame_length = std::max(a.max_frame_length, s.frame_length);
-    for (hipEvent_t& e : a.ev) ALAC_TRY(hipEventCreate(&e));
+    for (hipEvent_t& e : a.ev) OHGPU_HIP_TRY_ALLOC(hipEventCreate(&e));
     if (a.packets.empty()) return OHGPU_OK;
     const size_t np = a.packets.size();
-    ALAC_TRY(ctx_dev_alloc(ctx, &a.d_streams, a.streams.size() * sizeof(Stream)));
-    ALAC_TRY(ctx_dev_alloc(ctx, &a.d_packets, np * sizeof(Packet)));
-    ALAC_TRY(ctx_dev_alloc(ctx, &a.d_outs, np * sizeof(PacketOut)));
-    ALAC_TRY(ctx_dev_alloc(ctx, &a.d_chans, (size_t)a.n_rows * sizeof(Chan)));
-    ALAC_TRY(ctx_dev_alloc(ctx, &a.d_rowpacket, (size_t)a.n_rows * sizeof(uint32_t)));
-    ALAC_TRY(ctx_dev_alloc(ctx, &a.d_groupbase, group_base.size() * sizeof(uint64_t)));
+    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &a.d_streams, a.streams.size() * sizeof(Stream)));
+    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &a.d_packets, np * sizeof(Packet)));
+    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &a.d_outs, np * sizeof(PacketOut)));
+    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &a.d_chans, (size_t)a.n_rows * sizeof(Chan)));
+    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &a.d_rowpacket, (size_t)a.n_rows * sizeof(uint32_t)));
+    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &a.d_groupbase, group_base.size() * sizeof(uint64_t)));
     a.rows_bytes = (size_t)group_base.back() * kGroupRows * sizeof(int32_t);
-    a.rows_cached = a.rows_bytes <= ((size_t)256 << (DevCache::kClasses - 1));
-    if (a.rows_cached) ALAC_TRY(ctx_dev_alloc(ctx, &a.d_rows, a.rows_bytes));
-    else {
-        ALAC_TRY(hipMalloc(&a.d_rows, a.rows_bytes));
-        std::lock_guard<std::mutex> hold(ctx->cache.m);
-        ctx->cache.device_allocs++;
-    }
-    ALAC_TRY(hipMemcpy(a.d_streams, a.streams.data(), a.streams.size() * sizeof(Stream), hipMemcpyHostToDevice));
-    ALAC_TRY(hipMemcpy(a.d_packets, a.packets.data(), np * sizeof(Packet), hipMemcpyHostToDevice));
-    ALAC_TRY(hipMemcpy(a.d_rowpacket, row_packet.data(), row_packet.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    ALAC_TRY(hipMemcpy(a.d_groupbase, group_base.data(), group_base.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &a.d_rows, a.rows_bytes));
+    OHGPU_HIP_TRY_ALLOC(hipMemcpy(a.d_streams, a.streams.data(), a.streams.size() * sizeof(Stream), hipMemcpyHostToDevice));
+    OHGPU_HIP_TRY_ALLOC(hipMemcpy(a.d_packets, a.packets.data(), np * sizeof(Packet), hipMemcpyHostToDevice));
+    OHGPU_HIP_TRY_ALLOC(hipMemcpy(a.d_rowpacket, row_packet.data(), row_packet.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    OHGPU_HIP_TRY_ALLOC(hipMemcpy(a.d_groupbase, group_base.data(), group_base.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
     return OHGPU_OK;
 }
 
@@ -141,8 +129,7 @@ void alac_free(ohgpu_ctx* ctx, ohgpu_batch* b)
     if (!b->alac) return;
     AlacState& a = *b->alac;
     (void)hipDeviceSynchronize();
-    for (void* p : {a.d_streams, a.d_packets, a.d_outs, a.d_chans, a.d_rowpacket, a.d_groupbase}) ctx_dev_free(ctx, p);
-    if (a.d_rows) { if (a.rows_cached) ctx_dev_free(ctx, a.d_rows); else (void)hipFree(a.d_rows); }
+    for (void* p : {a.d_streams, a.d_packets, a.d_outs, a.d_chans, a.d_rowpacket, a.d_groupbase, a.d_rows}) ctx_dev_free(ctx, p);
     for (hipEvent_t e : a.ev) if (e) (void)hipEventDestroy(e);
     delete b->alac;
     b->alac = nullptr;
@@ -151,7 +138,7 @@ void alac_free(ohgpu_ctx* ctx, ohgpu_batch* b)
 int alac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s)
 {
     AlacState& a = *b->alac;
-    if (a.last_stream && a.last_stream != s) ALAC_TRY(hipStreamSynchronize(a.last_stream));
+    if (a.last_stream && a.last_stream != s) OHGPU_HIP_TRY_ALLOC(hipStreamSynchronize(a.last_stream));
     a.last_stream = s;
     a.ran = true;
     const uint32_t np = (uint32_t)a.packets.size();
@@ -163,27 +150,27 @@ int alac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
     const uint64_t* group_base = (const uint64_t*)a.d_groupbase;
     const uint32_t* row_packet = (const uint32_t*)a.d_rowpacket;
     const uint32_t packet_blocks = (np + kAlacLanes - 1) / kAlacLanes;
-    ALAC_TRY(hipEventRecord(a.ev[0], s));
+    OHGPU_HIP_TRY_ALLOC(hipEventRecord(a.ev[0], s));
     if (np && a.plain) {
         hipLaunchKernelGGL(alac_plain_kernel, dim3(packet_blocks), dim3(kAlacLanes), 0, s, streams, packets, np, src, chans, rows, group_base, dst, outs);
-        ALAC_TRY(hipGetLastError());
+        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
     } else if (np) {
         hipLaunchKernelGGL(alac_entropy_kernel, dim3(packet_blocks), dim3(kAlacLanes), 0, s, streams, packets, np, src, chans, rows, group_base, outs);
-        ALAC_TRY(hipGetLastError());
+        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
     }
-    ALAC_TRY(hipEventRecord(a.ev[1], s));
+    OHGPU_HIP_TRY_ALLOC(hipEventRecord(a.ev[1], s));
     if (np && !a.plain) {
         hipLaunchKernelGGL(alac_predict_kernel, dim3((a.n_rows + kAlacLanes - 1) / kAlacLanes), dim3(kAlacLanes), 0, s, row_packet, a.n_rows,
                            (const PacketOut*)outs, (const Chan*)chans, rows, group_base);
-        ALAC_TRY(hipGetLastError());
+        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
     }
-    ALAC_TRY(hipEventRecord(a.ev[2], s));
+    OHGPU_HIP_TRY_ALLOC(hipEventRecord(a.ev[2], s));
     if (np && !a.plain) {
         hipLaunchKernelGGL(alac_store_kernel, dim3(a.n_groups, (a.max_frame_length + kTile - 1) / kTile), dim3(256), 0, s, streams, packets, row_packet,
                            (const PacketOut*)outs, (const Chan*)chans, (const int32_t*)rows, group_base, src, dst);
-        ALAC_TRY(hipGetLastError());
+        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
     }
-    ALAC_TRY(hipEventRecord(a.ev[3], s));
+    OHGPU_HIP_TRY_ALLOC(hipEventRecord(a.ev[3], s));
     return OHGPU_OK;
 }
 
@@ -192,8 +179,8 @@ int alac_results(ohgpu_ctx* ctx, const ohgpu_batch* b, ohgpu_alac_packet_result*
     AlacState& a = *b->alac;
     if (a.packets.empty()) return OHGPU_OK;
     if (!a.ran) return set_error(OHGPU_ERR_INVALID, "ohgpu_alac_batch_results: the batch has not run");
-    ALAC_TRY(hipEventSynchronize(a.ev[3]));
-    if (!a.packets.empty()) ALAC_TRY(hipMemcpy(out, a.d_outs, a.packets.size() * sizeof(PacketOut), hipMemcpyDeviceToHost));
+    OHGPU_HIP_TRY_ALLOC(hipEventSynchronize(a.ev[3]));
+    if (!a.packets.empty()) OHGPU_HIP_TRY_ALLOC(hipMemcpy(out, a.d_outs, a.packets.size() * sizeof(PacketOut), hipMemcpyDeviceToHost));
     return OHGPU_OK;
 }
 

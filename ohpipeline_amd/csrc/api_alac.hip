@@ -28,19 +28,8 @@ int alac_check_desc(const ohgpu_alac_stream_desc& d, size_t i, const ohgpu_alac_
         const int err = arena_span("alac desc", i, "reads", p.src_offset, p.bytes, src_arena_bytes, "source");
         if (err != OHGPU_OK) return err;
     }
-    if (d.dst_offset % 4 != 0 || d.dst_plane_stride % 4 != 0) return set_error(OHGPU_ERR_INVALID, "alac desc %zu: dst_offset and dst_plane_stride must be multiples of 4", i);
-    const uint64_t samples = (uint64_t)d.n_packets * c.frame_length;
-    uint64_t span;
-    if (d.flags) {
-        if (d.dst_plane_stride != 0) return set_error(OHGPU_ERR_INVALID, "alac desc %zu: dst_plane_stride with packed output", i);
-        span = samples * c.channels * (c.bit_depth / 8u);
-    } else {
-        const uint64_t plane = samples * 4u;
-        if (c.channels > 1 && d.dst_plane_stride < plane) return set_error(OHGPU_ERR_INVALID, "alac desc %zu: planes overlap (stride %llu < %llu)", i, (unsigned long long)d.dst_plane_stride, (unsigned long long)plane);
-        if (d.dst_plane_stride > (1ull << 40)) return set_error(OHGPU_ERR_INVALID, "alac desc %zu: dst_plane_stride out of range", i);
-        span = (uint64_t)(c.channels - 1u) * d.dst_plane_stride + plane;
-    }
-    return arena_span("alac desc", i, "writes", d.dst_offset, span, dst_arena_bytes, "destination");
+    return decoded_dst_check("alac desc", i, c.channels, (uint64_t)d.n_packets * c.frame_length, d.flags ? (uint64_t)c.channels * (c.bit_depth / 8u) : 0u,
+                             d.dst_offset, d.dst_plane_stride, dst_arena_bytes);
 }
 
 void alac_add_stream(AlacState& a, size_t i, const ohgpu_alac_stream_desc& d)
@@ -55,7 +44,6 @@ void alac_add_stream(AlacState& a, size_t i, const ohgpu_alac_stream_desc& d)
 
 int alac_download_decoded(ohgpu_ctx* ctx, const char* who, const ohgpu_alac_stream_desc& d, const ohgpu_alac_packet_result* pres, void* dst_host)
 {
-    HostStage& st = ctx->stage;
     const uint32_t fl = d.config.frame_length;
     const uint64_t unit = d.flags ? (uint64_t)d.config.channels * (d.config.bit_depth / 8u) : 4u;
     for (uint32_t k = 0; k < d.n_packets;) {
@@ -69,12 +57,8 @@ int alac_download_decoded(ohgpu_ctx* ctx, const char* who, const ohgpu_alac_stre
             if (got != fl || k == d.n_packets || pres[k].status != OHGPU_ALAC_OK) break;
         }
         if (samples == 0) continue;
-        for (uint32_t c = 0; c < (d.flags ? 1u : d.config.channels); c++) {
-            const uint64_t off = d.dst_offset + c * d.dst_plane_stride + (uint64_t)k0 * fl * unit, bytes = samples * unit;
-            if (hipMemcpyAsync((uint8_t*)dst_host + off, (const uint8_t*)st.d_dst + off, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-                return set_error(OHGPU_ERR_DEVICE, "%s: download failed", who);
-            st.d2h_bytes += bytes;
-        }
+        const int err = download_planes(ctx, who, dst_host, d.dst_offset, d.dst_plane_stride, d.flags ? 1u : d.config.channels, unit, (uint64_t)k0 * fl, samples);
+        if (err != OHGPU_OK) return err;
     }
     return OHGPU_OK;
 }
@@ -183,37 +167,18 @@ int ohgpu_alac_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float ms
 {
     CTX_GUARD("ohgpu_alac_batch_phase_ms");
     if (!batch || batch->kind != kBatchAlac || !ms) return set_error(OHGPU_ERR_INVALID, "ohgpu_alac_batch_phase_ms: bad argument");
-    if (!batch->alac->ran) return set_error(OHGPU_ERR_INVALID, "ohgpu_alac_batch_phase_ms: the batch has not run");
-    OHGPU_HIP_TRY(hipEventSynchronize(batch->alac->ev[3]));
-    for (int k = 0; k < 3; k++) OHGPU_HIP_TRY(hipEventElapsedTime(&ms[k], batch->alac->ev[k], batch->alac->ev[k + 1]));
-    return OHGPU_OK;
+    return phase_ms("ohgpu_alac_batch_phase_ms", batch->alac->ran, batch->alac->ev, 3, ms);
 }
 
 int ohgpu_alac_process_host(ohgpu_ctx* ctx, const ohgpu_alac_stream_desc* descs, size_t n, const ohgpu_alac_packet* packets, size_t n_packets,
                             const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes,
                             ohgpu_alac_stream_result* stream_results, ohgpu_alac_packet_result* packet_results)
 {
-    CTX_GUARD("ohgpu_alac_process_host");
-    if ((src_bytes && !src_host) || (dst_bytes && !dst_host)) return set_error(OHGPU_ERR_INVALID, "ohgpu_alac_process_host: null buffer");
-    ohgpu_batch* b = nullptr;
-    int err = ohgpu_alac_batch_create(ctx, descs, n, packets, n_packets, src_bytes, dst_bytes, &b);
-    if (err != OHGPU_OK) return err;
-    const BatchPtr own(b, BatchDeleter{ctx});
-    HostStage& st = ctx->stage;
-    hipStream_t s = ctx->stream;
-    std::vector<ohgpu_alac_stream_result> sres(n);
-    std::vector<ohgpu_alac_packet_result> pres(n_packets);
-    err = host_stage_in(ctx, src_host, src_bytes, dst_bytes);
-    if (err != OHGPU_OK) return err;
-    if (n_packets) err = ohgpu_alac_batch_run(ctx, b, st.d_src, st.d_dst, nullptr);
-    if (err == OHGPU_OK && n_packets) err = ohgpu_alac_batch_results(ctx, b, n ? sres.data() : nullptr, n, pres.data(), n_packets);
-    if (err != OHGPU_OK) { (void)hipStreamSynchronize(s); return err; }
-    // only what was decoded comes back: per stream, each run of packets that decoded (whole ones, then perhaps a short one) in one copy per plane
-    for (size_t i = 0; i < n && err == OHGPU_OK; i++) err = alac_download_decoded(ctx, "ohgpu_alac_process_host", descs[i], pres.data() + descs[i].first_packet, dst_host);
-    if (hipStreamSynchronize(s) != hipSuccess && err == OHGPU_OK) err = set_error(OHGPU_ERR_DEVICE, "ohgpu_alac_process_host: hipStreamSynchronize failed");
-    if (err == OHGPU_OK && stream_results && n) memcpy(stream_results, sres.data(), n * sizeof(sres[0]));
-    if (err == OHGPU_OK && packet_results && n_packets) memcpy(packet_results, pres.data(), n_packets * sizeof(pres[0]));
-    return err;
+    const char* const who = "ohgpu_alac_process_host";
+    return alac_process_host(ctx, who, n, n_packets, src_host, src_bytes, dst_host, dst_bytes, stream_results, packet_results,
+        [&](ohgpu_batch** b) { return ohgpu_alac_batch_create(ctx, descs, n, packets, n_packets, src_bytes, dst_bytes, b); }, ohgpu_alac_batch_run, ohgpu_alac_batch_results,
+        // per stream, each run of packets that decoded (whole ones, then perhaps a short one) in one copy per plane
+        [&](size_t i, const ohgpu_alac_packet_result* pres) { return alac_download_decoded(ctx, who, descs[i], pres + descs[i].first_packet, dst_host); });
 }
 
 }  // extern "C"

@@ -35,6 +35,24 @@ inline int arena_span(const char* what, size_t i, const char* verb, uint64_t off
     return set_error(OHGPU_ERR_BOUNDS, "%s %zu: %s [%llu, +%llu) beyond the %llu-byte %s arena", what, i, verb, (unsigned long long)off,
                      (unsigned long long)bytes, (unsigned long long)arena, which);
 }
+// Where decoded audio goes (`what`: "flac desc", "alac desc"): `samples` samples a channel from dst_offset on, in planes of 4-byte words
+// dst_plane_stride apart that do not overlap, or (packed_frame_bytes != 0) interleaved with no stride; inside the destination arena.
+inline int decoded_dst_check(const char* what, size_t i, uint32_t channels, uint64_t samples, uint64_t packed_frame_bytes, uint64_t dst_offset,
+                             uint64_t dst_plane_stride, uint64_t dst_arena_bytes)
+{
+    if (dst_offset % 4 != 0 || dst_plane_stride % 4 != 0) return set_error(OHGPU_ERR_INVALID, "%s %zu: dst_offset and dst_plane_stride must be multiples of 4", what, i);
+    uint64_t span;
+    if (packed_frame_bytes) {
+        if (dst_plane_stride != 0) return set_error(OHGPU_ERR_INVALID, "%s %zu: dst_plane_stride with packed output", what, i);
+        span = samples * packed_frame_bytes;
+    } else {
+        const uint64_t plane = samples * 4u;
+        if (channels > 1 && dst_plane_stride < plane) return set_error(OHGPU_ERR_INVALID, "%s %zu: planes overlap (stride %llu < %llu)", what, i, (unsigned long long)dst_plane_stride, (unsigned long long)plane);
+        if (dst_plane_stride > (1ull << 40)) return set_error(OHGPU_ERR_INVALID, "%s %zu: dst_plane_stride out of range", what, i);
+        span = (uint64_t)(channels - 1u) * dst_plane_stride + plane;
+    }
+    return arena_span(what, i, "writes", dst_offset, span, dst_arena_bytes, "destination");
+}
 // Variants 2 and 5 named kernels the library no longer has (round 1's block, round 4's unit-per-wave matrix kernel): aliases of 4.
 inline int kernel_variant_alias(int variant) { return variant == 2 || variant == 5 ? 4 : variant; }
 
@@ -57,13 +75,21 @@ int run_guard(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, BatchKi
 // Batches with per-launch device state (ohgpu_batch::last_done): a launch on another stream while the last one runs is refused.
 int claim_single_launch(const ohgpu_batch* b, hipStream_t s, const char* who);
 inline void launched(const ohgpu_batch* b, hipStream_t s) { b->last_untracked = false; if (b->last_done) (void)hipEventRecord(b->last_done, s); }
+// An ohgpu_*_batch_phase_ms behind its argument check: ms[k] = the time from events[k] to events[k + 1], k < count (waits for the last)
+inline int phase_ms(const char* who, bool ran, const hipEvent_t* events, int count, float* ms)
+{
+    if (!ran) return set_error(OHGPU_ERR_INVALID, "%s: the batch has not run", who);
+    OHGPU_HIP_TRY(hipEventSynchronize(events[count]));
+    for (int k = 0; k < count; k++) OHGPU_HIP_TRY(hipEventElapsedTime(&ms[k], events[k], events[k + 1]));
+    return OHGPU_OK;
+}
 
 // The route plan_fmt_line planned a fmt batch onto (api_fmt.hip): ohgpu_fmt_batch_run and ohgpu_batch_paths_info both ask it.
 enum FmtRoute { kFmtRoutePcmLine, kFmtRouteWide, kFmtRouteStereo, kFmtRouteStaged, kFmtRouteGeneric };
 FmtRoute fmt_route(const ohgpu_batch* b);
 
-// ---- host buffers.  host_stage_in: the first half of host_roundtrip (ohgpu_internal.h) -- counts the call, reserves the context's two
-// device arenas, sends src_host on the context's stream.  process_host: the body of an ohgpu_*_process_host behind its create --
+// ---- host buffers.  host_stage_in: the first half of host_roundtrip (ohgpu_internal.h) and of decoder_process_host -- counts the call,
+// reserves the context's two device arenas, sends src_host on the context's stream.  process_host: the body of an ohgpu_*_process_host behind its create --
 // range(i) = (dst_offset, bytes) of output i, the round trip through the family's run, and the batch destroyed either way.
 int host_stage_in(ohgpu_ctx* ctx, const void* src_host, uint64_t src_bytes, uint64_t dst_bytes);
 using BatchRun = int (*)(ohgpu_ctx*, const ohgpu_batch*, const void*, void*, void*);
@@ -80,15 +106,75 @@ int process_host(ohgpu_ctx* ctx, ohgpu_batch* batch, size_t n, const void* src_h
 // (dst_offset, bytes) of a message of n_frames interleaved frames: the pcm, src and src_pull descriptors alike
 template <typename D>
 std::pair<uint64_t, uint64_t> frames_range(const D& d) { return {d.dst_offset, (uint64_t)d.n_frames * d.channels * (d.dst_bits / 8)}; }
+// decoder_process_host: the whole of a decoder's ohgpu_*_process_host (FLAC, Apple Lossless, RAOP), whose outputs are known only after
+// the run -- the null-buffer check, create(&batch), the source sent, run(batch, d_src, d_dst) = the family's run and results, then
+// download() = the copies of what was decoded, queued on the context's stream, and one wait.  The batch is destroyed either way.
+template <typename Create, typename Run, typename Download>
+int decoder_process_host(ohgpu_ctx* ctx, const char* who, const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes,
+                         Create&& create, Run&& run, Download&& download)
+{
+    CTX_GUARD(who);
+    if ((src_bytes && !src_host) || (dst_bytes && !dst_host)) return set_error(OHGPU_ERR_INVALID, "%s: null buffer", who);
+    ohgpu_batch* b = nullptr;
+    int err = create(&b);
+    if (err != OHGPU_OK) return err;
+    const BatchPtr own(b, BatchDeleter{ctx});
+    err = host_stage_in(ctx, src_host, src_bytes, dst_bytes);
+    if (err != OHGPU_OK) return err;
+    err = run(b, ctx->stage.d_src, ctx->stage.d_dst);
+    if (err != OHGPU_OK) { (void)hipStreamSynchronize(ctx->stream); return err; }
+    err = download();
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && err == OHGPU_OK) err = set_error(OHGPU_ERR_DEVICE, "%s: hipStreamSynchronize failed", who);
+    return err;
+}
+// One run of decoded samples home (queued, and counted in d2h_bytes): samples [first, first + samples) of `unit` bytes each, from each
+// of `planes` planes plane_stride apart (packed output: one plane) of the context's destination arena to the same place in dst_host.
+inline int download_planes(ohgpu_ctx* ctx, const char* who, void* dst_host, uint64_t dst_offset, uint64_t plane_stride, uint32_t planes, uint64_t unit,
+                           uint64_t first, uint64_t samples)
+{
+    for (uint32_t c = 0; c < planes; c++) {
+        const uint64_t off = dst_offset + c * plane_stride + first * unit, bytes = samples * unit;
+        if (hipMemcpyAsync((uint8_t*)dst_host + off, (const uint8_t*)ctx->stage.d_dst + off, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+            return set_error(OHGPU_ERR_DEVICE, "%s: download failed", who);
+        ctx->stage.d2h_bytes += bytes;
+    }
+    return OHGPU_OK;
+}
 
 // ---- Apple Lossless (api_alac.hip), shared with RAOP (api_raop.hip), whose decoding streams are Apple Lossless streams behind a cipher:
 // one descriptor's validation (its packets [next_packet, +n_packets) of the table), its device-side record, the summary of a stream's
-// packet results, and the download of what a stream decoded (of process_host; queued on the context's stream, not waited for).
+// packet results, the download of what a stream decoded (of process_host; queued on the context's stream, not waited for), and the
+// body of both families' process_host: create, run and results are the family's, download(i, packet results) brings stream i home.
 int  alac_check_desc(const ohgpu_alac_stream_desc& d, size_t i, const ohgpu_alac_packet* packets, uint64_t next_packet, size_t n_packets,
                      uint64_t src_arena_bytes, uint64_t dst_arena_bytes);
 void alac_add_stream(AlacState& a, size_t i, const ohgpu_alac_stream_desc& d);
 void alac_summarise(const ohgpu_alac_packet_result* pres, uint32_t n_packets, ohgpu_alac_stream_result* out);
 int  alac_download_decoded(ohgpu_ctx* ctx, const char* who, const ohgpu_alac_stream_desc& d, const ohgpu_alac_packet_result* pres, void* dst_host);
+using AlacResults = int (*)(ohgpu_ctx*, const ohgpu_batch*, ohgpu_alac_stream_result*, size_t, ohgpu_alac_packet_result*, size_t);
+template <typename Create, typename Download>
+int alac_process_host(ohgpu_ctx* ctx, const char* who, size_t n, size_t n_packets, const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes,
+                      ohgpu_alac_stream_result* stream_results, ohgpu_alac_packet_result* packet_results, Create&& create, BatchRun run, AlacResults results,
+                      Download&& download)
+{
+    std::vector<ohgpu_alac_stream_result> sres;
+    std::vector<ohgpu_alac_packet_result> pres;
+    const int err = decoder_process_host(ctx, who, src_host, src_bytes, dst_host, dst_bytes, create,
+        [&](const ohgpu_batch* b, const void* d_src, void* d_dst) {
+            sres = std::vector<ohgpu_alac_stream_result>(n);
+            pres = std::vector<ohgpu_alac_packet_result>(n_packets);
+            if (!n_packets) return (int)OHGPU_OK;
+            const int e = run(ctx, b, d_src, d_dst, nullptr);
+            return e != OHGPU_OK ? e : results(ctx, b, n ? sres.data() : nullptr, n, pres.data(), n_packets);
+        },
+        [&] {   // only what was decoded comes back
+            int e = OHGPU_OK;
+            for (size_t i = 0; i < n && e == OHGPU_OK; i++) e = download(i, pres.data());
+            return e;
+        });
+    if (err == OHGPU_OK && stream_results && n) memcpy(stream_results, sres.data(), n * sizeof(sres[0]));
+    if (err == OHGPU_OK && packet_results && n_packets) memcpy(packet_results, pres.data(), n_packets * sizeof(pres[0]));
+    return err;
+}
 
 }  // namespace ohgpu
 #pragma GCC visibility pop

@@ -101,7 +101,7 @@ int ohgpu_dsd_pcm_create(ohgpu_ctx* ctx, uint32_t D, uint32_t T, const int32_t* 
         if (f->d_coef) (void)hipFree(f->d_coef);
         if (f->d_tables) (void)hipFree(f->d_tables);
         delete f;
-        return set_error(e == hipErrorOutOfMemory ? OHGPU_ERR_NOMEM : OHGPU_ERR_DEVICE, "ohgpu_dsd_pcm_create: %s", hipGetErrorString(e));
+        return set_error(hip_code(e), "ohgpu_dsd_pcm_create: %s", hipGetErrorString(e));
     }
     *out = f;
     return OHGPU_OK;

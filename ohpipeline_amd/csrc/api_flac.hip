@@ -20,18 +20,8 @@ static int flac_check_desc(const ohgpu_flac_stream_desc& d, size_t i, uint64_t s
     if (d.first_sample >= (1ull << 62)) return set_error(OHGPU_ERR_INVALID, "flac desc %zu: first_sample out of range", i);
     const int err = arena_span("flac desc", i, "reads", d.src_offset, d.src_bytes, src_arena_bytes, "source");
     if (err != OHGPU_OK) return err;
-    if (d.dst_offset % 4 != 0 || d.dst_plane_stride % 4 != 0) return set_error(OHGPU_ERR_INVALID, "flac desc %zu: dst_offset and dst_plane_stride must be multiples of 4", i);
-    uint64_t span;
-    if (d.flags & OHGPU_FLAC_OUT_PACKED_BE) {
-        if (d.dst_plane_stride != 0) return set_error(OHGPU_ERR_INVALID, "flac desc %zu: dst_plane_stride with packed output", i);
-        span = (uint64_t)d.max_samples * d.channels * (d.bits / 8u);
-    } else {
-        const uint64_t plane = (uint64_t)d.max_samples * 4u;
-        if (d.channels > 1 && d.dst_plane_stride < plane) return set_error(OHGPU_ERR_INVALID, "flac desc %zu: planes overlap (stride %llu < %llu)", i, (unsigned long long)d.dst_plane_stride, (unsigned long long)plane);
-        if (d.dst_plane_stride > (1ull << 40)) return set_error(OHGPU_ERR_INVALID, "flac desc %zu: dst_plane_stride out of range", i);
-        span = (uint64_t)(d.channels - 1u) * d.dst_plane_stride + plane;
-    }
-    return arena_span("flac desc", i, "writes", d.dst_offset, span, dst_arena_bytes, "destination");
+    return decoded_dst_check("flac desc", i, d.channels, d.max_samples, (d.flags & OHGPU_FLAC_OUT_PACKED_BE) ? (uint64_t)d.channels * (d.bits / 8u) : 0u,
+                             d.dst_offset, d.dst_plane_stride, dst_arena_bytes);
 }
 
 int ohgpu_flac_streaminfo(const void* bytes, size_t n, ohgpu_flac_streaminfo_t* info, uint64_t* audio_offset)
@@ -133,45 +123,35 @@ int ohgpu_flac_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float ms
 {
     CTX_GUARD("ohgpu_flac_batch_phase_ms");
     if (!batch || batch->kind != kBatchFlac || !ms) return set_error(OHGPU_ERR_INVALID, "ohgpu_flac_batch_phase_ms: bad argument");
-    if (!batch->flac->ran) return set_error(OHGPU_ERR_INVALID, "ohgpu_flac_batch_phase_ms: the batch has not run");
-    OHGPU_HIP_TRY(hipEventSynchronize(batch->flac->ev[4]));
-    for (int k = 0; k < 4; k++) OHGPU_HIP_TRY(hipEventElapsedTime(&ms[k], batch->flac->ev[k], batch->flac->ev[k + 1]));
-    return OHGPU_OK;
+    return phase_ms("ohgpu_flac_batch_phase_ms", batch->flac->ran, batch->flac->ev, 4, ms);
 }
 
 int ohgpu_flac_process_host(ohgpu_ctx* ctx, const ohgpu_flac_stream_desc* descs, size_t n,
                             const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes,
                             ohgpu_flac_stream_result* results, ohgpu_flac_frame* frames, size_t frames_capacity, size_t* n_frames)
 {
-    CTX_GUARD("ohgpu_flac_process_host");
-    if ((src_bytes && !src_host) || (dst_bytes && !dst_host)) return set_error(OHGPU_ERR_INVALID, "ohgpu_flac_process_host: null buffer");
-    ohgpu_batch* b = nullptr;
-    int err = ohgpu_flac_batch_create(ctx, descs, n, src_bytes, dst_bytes, &b);
-    if (err != OHGPU_OK) return err;
-    const BatchPtr own(b, BatchDeleter{ctx});
-    HostStage& st = ctx->stage;
-    hipStream_t s = ctx->stream;
-    std::vector<ohgpu_flac_stream_result> res(n);
-    err = host_stage_in(ctx, src_host, src_bytes, dst_bytes);
-    if (err != OHGPU_OK) return err;
-    err = ohgpu_flac_batch_run(ctx, b, st.d_src, st.d_dst, nullptr);
-    if (err == OHGPU_OK) err = ohgpu_flac_batch_results(ctx, b, res.data(), n);
-    if (err == OHGPU_OK && (frames || n_frames)) err = ohgpu_flac_batch_frames(ctx, b, frames, frames ? frames_capacity : 0, n_frames);
-    if (err != OHGPU_OK) { (void)hipStreamSynchronize(s); return err; }
-    // only what was decoded comes back: a chain's frames are consecutive, so per stream one run of samples (per plane)
-    for (size_t i = 0; i < n && err == OHGPU_OK; i++) {
-        const ohgpu_flac_stream_desc& d = descs[i];
-        if (res[i].frames == 0) continue;
-        const uint64_t first = res[i].first_sample_decoded - d.first_sample;
-        const bool packed = d.flags & OHGPU_FLAC_OUT_PACKED_BE;
-        const uint64_t unit = packed ? (uint64_t)d.channels * (d.bits / 8u) : 4u;
-        for (uint32_t c = 0; c < (packed ? 1u : d.channels); c++) {
-            const uint64_t off = d.dst_offset + c * d.dst_plane_stride + first * unit, bytes = res[i].samples * unit;
-            if (hipMemcpyAsync((uint8_t*)dst_host + off, (const uint8_t*)st.d_dst + off, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) { err = set_error(OHGPU_ERR_DEVICE, "ohgpu_flac_process_host: download failed"); break; }
-            st.d2h_bytes += bytes;
-        }
-    }
-    if (hipStreamSynchronize(s) != hipSuccess && err == OHGPU_OK) err = set_error(OHGPU_ERR_DEVICE, "ohgpu_flac_process_host: hipStreamSynchronize failed");
+    const char* const who = "ohgpu_flac_process_host";
+    std::vector<ohgpu_flac_stream_result> res;
+    const int err = decoder_process_host(ctx, who, src_host, src_bytes, dst_host, dst_bytes,
+        [&](ohgpu_batch** b) { return ohgpu_flac_batch_create(ctx, descs, n, src_bytes, dst_bytes, b); },
+        [&](const ohgpu_batch* b, const void* d_src, void* d_dst) {
+            res = std::vector<ohgpu_flac_stream_result>(n);
+            int e = ohgpu_flac_batch_run(ctx, b, d_src, d_dst, nullptr);
+            if (e == OHGPU_OK) e = ohgpu_flac_batch_results(ctx, b, res.data(), n);
+            if (e == OHGPU_OK && (frames || n_frames)) e = ohgpu_flac_batch_frames(ctx, b, frames, frames ? frames_capacity : 0, n_frames);
+            return e;
+        },
+        [&] {   // only what was decoded comes back: a chain's frames are consecutive, so per stream one run of samples (per plane)
+            int e = OHGPU_OK;
+            for (size_t i = 0; i < n && e == OHGPU_OK; i++) {
+                const ohgpu_flac_stream_desc& d = descs[i];
+                if (res[i].frames == 0) continue;
+                const bool packed = d.flags & OHGPU_FLAC_OUT_PACKED_BE;
+                e = download_planes(ctx, who, dst_host, d.dst_offset, d.dst_plane_stride, packed ? 1u : d.channels, packed ? (uint64_t)d.channels * (d.bits / 8u) : 4u,
+                                    res[i].first_sample_decoded - d.first_sample, res[i].samples);
+            }
+            return e;
+        });
     if (err == OHGPU_OK && results) memcpy(results, res.data(), n * sizeof(ohgpu_flac_stream_result));
     return err;
 }

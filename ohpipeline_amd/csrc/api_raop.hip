@@ -192,50 +192,32 @@ int ohgpu_raop_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float ms
     CTX_GUARD("ohgpu_raop_batch_phase_ms");
     if (!batch || batch->kind != kBatchRaop || !ms) return set_error(OHGPU_ERR_INVALID, "ohgpu_raop_batch_phase_ms: bad argument");
     const AlacState& a = *batch->alac;
-    if (!a.ran) return set_error(OHGPU_ERR_INVALID, "ohgpu_raop_batch_phase_ms: the batch has not run");
-    OHGPU_HIP_TRY(hipEventSynchronize(a.ev[3]));
-    OHGPU_HIP_TRY(hipEventElapsedTime(&ms[0], batch->raop->ev0, a.ev[0]));
-    for (int k = 0; k < 3; k++) OHGPU_HIP_TRY(hipEventElapsedTime(&ms[k + 1], a.ev[k], a.ev[k + 1]));
-    return OHGPU_OK;
+    const hipEvent_t ev[5] = {batch->raop->ev0, a.ev[0], a.ev[1], a.ev[2], a.ev[3]};
+    return phase_ms("ohgpu_raop_batch_phase_ms", a.ran, ev, 4, ms);
 }
 
 int ohgpu_raop_process_host(ohgpu_ctx* ctx, const ohgpu_raop_stream_desc* descs, size_t n, const ohgpu_alac_packet* packets, size_t n_packets,
                             const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes,
                             ohgpu_alac_stream_result* stream_results, ohgpu_alac_packet_result* packet_results)
 {
-    CTX_GUARD("ohgpu_raop_process_host");
-    if ((src_bytes && !src_host) || (dst_bytes && !dst_host)) return set_error(OHGPU_ERR_INVALID, "ohgpu_raop_process_host: null buffer");
-    ohgpu_batch* b = nullptr;
-    int err = ohgpu_raop_batch_create(ctx, descs, n, packets, n_packets, src_bytes, dst_bytes, &b);
-    if (err != OHGPU_OK) return err;
-    const BatchPtr own(b, BatchDeleter{ctx});
-    HostStage& st = ctx->stage;
-    hipStream_t s = ctx->stream;
-    std::vector<ohgpu_alac_stream_result> sres(n);
-    std::vector<ohgpu_alac_packet_result> pres(n_packets);
-    err = host_stage_in(ctx, src_host, src_bytes, dst_bytes);
-    if (err != OHGPU_OK) return err;
-    if (n_packets) err = ohgpu_raop_batch_run(ctx, b, st.d_src, st.d_dst, nullptr);
-    if (err == OHGPU_OK && n_packets) err = ohgpu_raop_batch_results(ctx, b, n ? sres.data() : nullptr, n, pres.data(), n_packets);
-    if (err != OHGPU_OK) { (void)hipStreamSynchronize(s); return err; }
-    for (size_t i = 0; i < n && err == OHGPU_OK; i++) {
-        const ohgpu_alac_stream_desc& d = descs[i].alac;
-        if (!plaintext(descs[i])) { err = alac_download_decoded(ctx, "ohgpu_raop_process_host", d, pres.data() + d.first_packet, dst_host); continue; }
-        // a plaintext stream: its packets, runs of touching ones in one copy
-        for (uint32_t k = 0; k < d.n_packets && err == OHGPU_OK;) {
-            const uint64_t from = packets[d.first_packet + k].src_offset;
-            uint64_t to = from + packets[d.first_packet + k].bytes;
-            for (k++; k < d.n_packets && packets[d.first_packet + k].src_offset == to; k++) to += packets[d.first_packet + k].bytes;
-            if (to == from) continue;
-            const uint64_t off = d.dst_offset + (from - packets[d.first_packet].src_offset);
-            if (hipMemcpyAsync((uint8_t*)dst_host + off, (const uint8_t*)st.d_dst + off, to - from, hipMemcpyDeviceToHost, s) != hipSuccess) err = set_error(OHGPU_ERR_DEVICE, "ohgpu_raop_process_host: download failed");
-            st.d2h_bytes += to - from;
-        }
-    }
-    if (hipStreamSynchronize(s) != hipSuccess && err == OHGPU_OK) err = set_error(OHGPU_ERR_DEVICE, "ohgpu_raop_process_host: hipStreamSynchronize failed");
-    if (err == OHGPU_OK && stream_results && n) memcpy(stream_results, sres.data(), n * sizeof(sres[0]));
-    if (err == OHGPU_OK && packet_results && n_packets) memcpy(packet_results, pres.data(), n_packets * sizeof(pres[0]));
-    return err;
+    const char* const who = "ohgpu_raop_process_host";
+    return alac_process_host(ctx, who, n, n_packets, src_host, src_bytes, dst_host, dst_bytes, stream_results, packet_results,
+        [&](ohgpu_batch** b) { return ohgpu_raop_batch_create(ctx, descs, n, packets, n_packets, src_bytes, dst_bytes, b); }, ohgpu_raop_batch_run, ohgpu_raop_batch_results,
+        [&](size_t i, const ohgpu_alac_packet_result* pres) {
+            const ohgpu_alac_stream_desc& d = descs[i].alac;
+            if (!plaintext(descs[i])) return alac_download_decoded(ctx, who, d, pres + d.first_packet, dst_host);
+            // a plaintext stream: its packets, runs of touching ones in one copy
+            for (uint32_t k = 0; k < d.n_packets;) {
+                const uint64_t from = packets[d.first_packet + k].src_offset;
+                uint64_t to = from + packets[d.first_packet + k].bytes;
+                for (k++; k < d.n_packets && packets[d.first_packet + k].src_offset == to; k++) to += packets[d.first_packet + k].bytes;
+                if (to == from) continue;
+                // (as one "plane" of one-byte samples: the run's bytes from its offset in the stream's window)
+                const int err = download_planes(ctx, who, dst_host, d.dst_offset, 0, 1, 1, from - packets[d.first_packet].src_offset, to - from);
+                if (err != OHGPU_OK) return err;
+            }
+            return (int)OHGPU_OK;
+        });
 }
 
 }  // extern "C"

@@ -181,7 +181,7 @@ int ohgpu_src_pull_batch_create(ohgpu_ctx* ctx, const ohgpu_src* src, const ohgp
     if (err == OHGPU_OK && !tiles.empty()) {
         hipError_t e = ctx_dev_alloc(ctx, &b->d_pull_tiles, tiles.size() * sizeof(PullTile));
         if (e == hipSuccess) e = hipMemcpy(b->d_pull_tiles, tiles.data(), tiles.size() * sizeof(PullTile), hipMemcpyHostToDevice);
-        if (e != hipSuccess) err = set_error(e == hipErrorOutOfMemory ? OHGPU_ERR_NOMEM : OHGPU_ERR_DEVICE, "ohgpu_src_pull_batch_create: tile upload: %s", hipGetErrorString(e));
+        if (e != hipSuccess) err = set_error(hip_code(e), "ohgpu_src_pull_batch_create: tile upload: %s", hipGetErrorString(e));
     }
     b->n_pull_tiles = (uint32_t)tiles.size();
     return batch_done(err, b, out);

@@ -275,7 +275,7 @@ int plan_dsd_line(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_dsd_desc* descs, s
     if (e == hipSuccess) e = hipMemcpy(b->dsd.d_pieces, pieces.data(), pieces.size() * sizeof(DsdPiece), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         free_dsd_line(ctx, b);
-        return set_error(e == hipErrorOutOfMemory ? OHGPU_ERR_NOMEM : OHGPU_ERR_DEVICE, "piece plan upload: %s", hipGetErrorString(e));
+        return set_error(hip_code(e), "piece plan upload: %s", hipGetErrorString(e));
     }
     b->dsd.n_pieces = (uint32_t)pieces.size();
     return OHGPU_OK;

@@ -121,7 +121,7 @@ int plan_dsd_pcm(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_dsd_pcm_msg_desc* d
     if (e == hipSuccess) e = hipMemcpy(b->dsdpcm.d_tiles, tiles.data(), tiles.size() * sizeof(DsdPcmTile), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         free_dsd_pcm(ctx, b);
-        return set_error(e == hipErrorOutOfMemory ? OHGPU_ERR_NOMEM : OHGPU_ERR_DEVICE, "tile plan upload: %s", hipGetErrorString(e));
+        return set_error(hip_code(e), "tile plan upload: %s", hipGetErrorString(e));
     }
     b->dsdpcm.n_tiles = (uint32_t)tiles.size();
     return OHGPU_OK;

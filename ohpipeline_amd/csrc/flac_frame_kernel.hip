@@ -132,12 +132,6 @@ __global__ __launch_bounds__(kProbeThreads) void flac_plain_kernel(const Stream*
     }
 }
 
-#define FLAC_TRY(expr)                                                                                                             \
-    do {                                                                                                                           \
-        const hipError_t e_ = (expr);                                                                                              \
-        if (e_ != hipSuccess) return set_error(e_ == hipErrorOutOfMemory ? OHGPU_ERR_NOMEM : OHGPU_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 int flac_plan(ohgpu_ctx* ctx, ohgpu_batch* b)
 {
     FlacState& f = *b->flac;
@@ -150,25 +144,19 @@ int flac_plan(ohgpu_ctx* ctx, ohgpu_batch* b)
     f.n_tiles = (uint32_t)tiles.size();
     Tables t;
     make_tables(&t);
-    FLAC_TRY(ctx_dev_alloc(ctx, &f.d_tables, sizeof(Tables)));
-    FLAC_TRY(hipMemcpy(f.d_tables, &t, sizeof(Tables), hipMemcpyHostToDevice));
-    FLAC_TRY(ctx_dev_alloc(ctx, &f.d_counter, 256));
+    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &f.d_tables, sizeof(Tables)));
+    OHGPU_HIP_TRY_ALLOC(hipMemcpy(f.d_tables, &t, sizeof(Tables), hipMemcpyHostToDevice));
+    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &f.d_counter, 256));
     if (n) {
-        FLAC_TRY(ctx_dev_alloc(ctx, &f.d_streams, n * sizeof(Stream)));
-        FLAC_TRY(ctx_dev_alloc(ctx, &f.d_results, n * sizeof(Result)));
+        OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &f.d_streams, n * sizeof(Stream)));
+        OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &f.d_results, n * sizeof(Result)));
     }
     if (f.n_tiles) {
-        FLAC_TRY(ctx_dev_alloc(ctx, &f.d_tiles, tiles.size() * sizeof(FlacScanTile)));
-        FLAC_TRY(hipMemcpy(f.d_tiles, tiles.data(), tiles.size() * sizeof(FlacScanTile), hipMemcpyHostToDevice));
+        OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &f.d_tiles, tiles.size() * sizeof(FlacScanTile)));
+        OHGPU_HIP_TRY_ALLOC(hipMemcpy(f.d_tiles, tiles.data(), tiles.size() * sizeof(FlacScanTile), hipMemcpyHostToDevice));
     }
-    for (hipEvent_t& e : f.ev) FLAC_TRY(hipEventCreate(&e));
+    for (hipEvent_t& e : f.ev) OHGPU_HIP_TRY_ALLOC(hipEventCreate(&e));
     return OHGPU_OK;
-}
-
-static void flac_free_rows(ohgpu_ctx* ctx, FlacState& f)
-{
-    if (f.d_rows) { if (f.rows_cached) ctx_dev_free(ctx, f.d_rows); else (void)hipFree(f.d_rows); }
-    f.d_rows = nullptr; f.rows_words = 0;
 }
 
 void flac_free(ohgpu_ctx* ctx, ohgpu_batch* b)
@@ -176,8 +164,7 @@ void flac_free(ohgpu_ctx* ctx, ohgpu_batch* b)
     if (!b->flac) return;
     FlacState& f = *b->flac;
     (void)hipDeviceSynchronize();
-    for (void* p : {f.d_tables, f.d_tiles, f.d_streams, f.d_results, f.d_counter, f.d_list, f.d_probes, f.d_rowcand, f.d_subs}) ctx_dev_free(ctx, p);
-    flac_free_rows(ctx, f);
+    for (void* p : {f.d_tables, f.d_tiles, f.d_streams, f.d_results, f.d_counter, f.d_list, f.d_probes, f.d_rowcand, f.d_subs, f.d_rows}) ctx_dev_free(ctx, p);
     for (hipEvent_t e : f.ev) if (e) (void)hipEventDestroy(e);
     delete b->flac;
     b->flac = nullptr;
@@ -190,7 +177,7 @@ static int flac_reserve(ohgpu_ctx* ctx, void** p, size_t* cap, size_t bytes)
     ctx_dev_free(ctx, *p);
     *p = nullptr; *cap = 0;
     const size_t want = bytes + bytes / 2 + 256;
-    FLAC_TRY(ctx_dev_alloc(ctx, p, want));
+    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, p, want));
     *cap = want;
     return OHGPU_OK;
 }
@@ -199,7 +186,7 @@ int flac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
 {
     FlacState& f = *b->flac;
     const size_t n = f.streams.size();
-    if (f.last_stream && f.last_stream != s) FLAC_TRY(hipStreamSynchronize(f.last_stream));
+    if (f.last_stream && f.last_stream != s) OHGPU_HIP_TRY_ALLOC(hipStreamSynchronize(f.last_stream));
     f.last_stream = s;
     f.ran = true;
     f.n_candidates = 0;
@@ -215,16 +202,16 @@ int flac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
         f.list_cap = cap / sizeof(uint2);
     }
     for (int attempt = 0; attempt < 2; attempt++) {
-        FLAC_TRY(hipMemsetAsync(f.d_counter, 0, sizeof(uint32_t), s));
-        FLAC_TRY(hipMemcpyAsync(f.d_streams, f.streams.data(), n * sizeof(Stream), hipMemcpyHostToDevice, s));
-        FLAC_TRY(hipEventRecord(f.ev[0], s));
+        OHGPU_HIP_TRY_ALLOC(hipMemsetAsync(f.d_counter, 0, sizeof(uint32_t), s));
+        OHGPU_HIP_TRY_ALLOC(hipMemcpyAsync(f.d_streams, f.streams.data(), n * sizeof(Stream), hipMemcpyHostToDevice, s));
+        OHGPU_HIP_TRY_ALLOC(hipEventRecord(f.ev[0], s));
         if (f.n_tiles)
             hipLaunchKernelGGL(flac_scan_kernel, dim3(f.n_tiles), dim3(kScanThreads), 0, s, (const Stream*)f.d_streams, (const FlacScanTile*)f.d_tiles, src,
                                tables, (uint2*)f.d_list, (uint32_t)f.list_cap, (uint32_t*)f.d_counter);
-        FLAC_TRY(hipGetLastError());
-        FLAC_TRY(hipEventRecord(f.ev[1], s));
-        FLAC_TRY(hipMemcpyAsync(&found, f.d_counter, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        FLAC_TRY(hipStreamSynchronize(s));
+        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
+        OHGPU_HIP_TRY_ALLOC(hipEventRecord(f.ev[1], s));
+        OHGPU_HIP_TRY_ALLOC(hipMemcpyAsync(&found, f.d_counter, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        OHGPU_HIP_TRY_ALLOC(hipStreamSynchronize(s));
         if (found <= f.list_cap) break;
         if (attempt == 1) return set_error(OHGPU_ERR_DEVICE, "ohgpu_flac_batch_run: the scan found %u candidates, then more", (uint32_t)f.list_cap);
         size_t cap = 0;
@@ -236,7 +223,7 @@ int flac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
     }
     // ---- the host's part: sort, the streams' shares, a row of scratch per (candidate, channel) ----
     f.host_list.resize((size_t)found * 2);
-    if (found) FLAC_TRY(hipMemcpy(f.host_list.data(), f.d_list, (size_t)found * sizeof(uint2), hipMemcpyDeviceToHost));
+    if (found) OHGPU_HIP_TRY_ALLOC(hipMemcpy(f.host_list.data(), f.d_list, (size_t)found * sizeof(uint2), hipMemcpyDeviceToHost));
     std::vector<uint64_t> keys(found);
     for (uint32_t i = 0; i < found; i++) keys[i] = ((uint64_t)f.host_list[2 * i] << 32) | f.host_list[2 * i + 1];
     std::sort(keys.begin(), keys.end());
@@ -255,7 +242,7 @@ int flac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
     f.n_candidates = found;
     const size_t n_rows = f.host_rowcand.size();
     const uint32_t row_words = f.max_blocksize;
-    FLAC_TRY(hipMemcpyAsync(f.d_streams, f.streams.data(), n * sizeof(Stream), hipMemcpyHostToDevice, s));
+    OHGPU_HIP_TRY_ALLOC(hipMemcpyAsync(f.d_streams, f.streams.data(), n * sizeof(Stream), hipMemcpyHostToDevice, s));
     if (found) {
         int err = flac_reserve(ctx, &f.d_probes, &f.probes_cap, found * sizeof(Probe));
         if (err != OHGPU_OK) return err;
@@ -263,26 +250,21 @@ int flac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
             ctx_dev_free(ctx, f.d_rowcand); ctx_dev_free(ctx, f.d_subs);
             f.d_rowcand = f.d_subs = nullptr; f.rows_cap = 0;
             const size_t want = n_rows + n_rows / 2 + 16;
-            FLAC_TRY(ctx_dev_alloc(ctx, &f.d_rowcand, want * sizeof(uint32_t)));
-            FLAC_TRY(ctx_dev_alloc(ctx, &f.d_subs, want * sizeof(Sub)));
+            OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &f.d_rowcand, want * sizeof(uint32_t)));
+            OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &f.d_subs, want * sizeof(Sub)));
             f.rows_cap = want;
         }
         const size_t words = n_rows * (size_t)row_words;
         if (f.rows_words < words) {
-            flac_free_rows(ctx, f);
+            ctx_dev_free(ctx, f.d_rows);
+            f.d_rows = nullptr; f.rows_words = 0;
             const size_t want = words + words / 2;
-            f.rows_cached = want * 4 <= ((size_t)256 << (DevCache::kClasses - 1));
-            if (f.rows_cached) FLAC_TRY(ctx_dev_alloc(ctx, &f.d_rows, want * 4));
-            else {
-                FLAC_TRY(hipMalloc(&f.d_rows, want * 4));
-                std::lock_guard<std::mutex> hold(ctx->cache.m);
-                ctx->cache.device_allocs++;
-            }
+            OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &f.d_rows, want * 4));
             f.rows_words = want;
         }
-        FLAC_TRY(hipMemcpyAsync(f.d_probes, f.host_probes.data(), found * sizeof(Probe), hipMemcpyHostToDevice, s));
-        FLAC_TRY(hipMemcpyAsync(f.d_rowcand, f.host_rowcand.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        FLAC_TRY(hipStreamSynchronize(s));             // (the host vectors are pageable and change with the next run)
+        OHGPU_HIP_TRY_ALLOC(hipMemcpyAsync(f.d_probes, f.host_probes.data(), found * sizeof(Probe), hipMemcpyHostToDevice, s));
+        OHGPU_HIP_TRY_ALLOC(hipMemcpyAsync(f.d_rowcand, f.host_rowcand.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        OHGPU_HIP_TRY_ALLOC(hipStreamSynchronize(s));             // (the host vectors are pageable and change with the next run)
     }
     Probe* probes = (Probe*)f.d_probes;
     Sub* subs = (Sub*)f.d_subs;
@@ -293,15 +275,15 @@ int flac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
     if (found) {
         if (plain) hipLaunchKernelGGL(flac_probe_kernel<false>, dim3(cand_blocks), dim3(kProbeThreads), 0, s, streams, probes, found, src, tables, subs, rows, row_words);
         else hipLaunchKernelGGL(flac_probe_kernel<true>, dim3(cand_blocks), dim3(kProbeThreads), 0, s, streams, probes, found, src, tables, subs, rows, row_words);
-        FLAC_TRY(hipGetLastError());
+        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
     }
-    FLAC_TRY(hipEventRecord(f.ev[2], s));
+    OHGPU_HIP_TRY_ALLOC(hipEventRecord(f.ev[2], s));
     // ---- chain ----
     if (n) {
         hipLaunchKernelGGL(flac_chain_kernel, dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, s, streams, (uint32_t)n, probes, (Result*)f.d_results);
-        FLAC_TRY(hipGetLastError());
+        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
     }
-    FLAC_TRY(hipEventRecord(f.ev[3], s));
+    OHGPU_HIP_TRY_ALLOC(hipEventRecord(f.ev[3], s));
     // ---- restore ----
     if (found) {
         if (plain) {
@@ -311,9 +293,9 @@ int flac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
                                (const Probe*)probes, (const uint32_t*)f.d_rowcand, (uint32_t)n_rows, (const Sub*)subs, rows, row_words);
             hipLaunchKernelGGL(flac_store_kernel, dim3(found, (row_words + 255) / 256), dim3(256), 0, s, streams, (const Probe*)probes, (const int32_t*)rows, row_words, dst);
         }
-        FLAC_TRY(hipGetLastError());
+        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
     }
-    FLAC_TRY(hipEventRecord(f.ev[4], s));
+    OHGPU_HIP_TRY_ALLOC(hipEventRecord(f.ev[4], s));
     return OHGPU_OK;
 }
 
@@ -321,8 +303,8 @@ int flac_results(ohgpu_ctx* ctx, const ohgpu_batch* b, ohgpu_flac_stream_result*
 {
     FlacState& f = *b->flac;
     if (!f.ran) return set_error(OHGPU_ERR_INVALID, "ohgpu_flac_batch_results: the batch has not run");
-    FLAC_TRY(hipEventSynchronize(f.ev[4]));
-    if (!f.streams.empty()) FLAC_TRY(hipMemcpy(out, f.d_results, f.streams.size() * sizeof(Result), hipMemcpyDeviceToHost));
+    OHGPU_HIP_TRY_ALLOC(hipEventSynchronize(f.ev[4]));
+    if (!f.streams.empty()) OHGPU_HIP_TRY_ALLOC(hipMemcpy(out, f.d_results, f.streams.size() * sizeof(Result), hipMemcpyDeviceToHost));
     return OHGPU_OK;
 }
 
@@ -330,8 +312,8 @@ int flac_frames(ohgpu_ctx* ctx, const ohgpu_batch* b, ohgpu_flac_frame* out, siz
 {
     FlacState& f = *b->flac;
     if (!f.ran) return set_error(OHGPU_ERR_INVALID, "ohgpu_flac_batch_frames: the batch has not run");
-    FLAC_TRY(hipEventSynchronize(f.ev[4]));
-    if (f.n_candidates) FLAC_TRY(hipMemcpy(f.host_probes.data(), f.d_probes, (size_t)f.n_candidates * sizeof(Probe), hipMemcpyDeviceToHost));
+    OHGPU_HIP_TRY_ALLOC(hipEventSynchronize(f.ev[4]));
+    if (f.n_candidates) OHGPU_HIP_TRY_ALLOC(hipMemcpy(f.host_probes.data(), f.d_probes, (size_t)f.n_candidates * sizeof(Probe), hipMemcpyDeviceToHost));
     size_t k = 0;
     for (uint32_t i = 0; i < f.n_candidates; i++) {               // (sorted by stream, then position: stream order)
         const Probe& c = f.host_probes[i];

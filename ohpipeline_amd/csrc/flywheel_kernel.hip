@@ -157,7 +157,7 @@ int plan_flywheel(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_flywheel_desc* des
     if (e == hipSuccess) e = ctx_dev_alloc(ctx, &b->fly.d_work, (size_t)3 * max_count * padded * sizeof(int16_t));
     if (e != hipSuccess) {
         free_flywheel(ctx, b);
-        return set_error(e == hipErrorOutOfMemory ? OHGPU_ERR_NOMEM : OHGPU_ERR_DEVICE, "flywheel plan: %s", hipGetErrorString(e));
+        return set_error(hip_code(e), "flywheel plan: %s", hipGetErrorString(e));
     }
     b->fly.n_lanes = (uint32_t)lanes.size();
     b->fly.lanes_padded = padded;

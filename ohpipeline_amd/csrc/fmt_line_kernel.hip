@@ -244,7 +244,7 @@ int plan_fmt_line(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_fmt_desc* descs, s
                 if (e == hipSuccess) e = hipMemcpy(b->fmtline.d_wide, recs.data(), recs.size() * sizeof(OhmSelRec), hipMemcpyHostToDevice);
                 if (e != hipSuccess) {
                     free_fmt_line(ctx, b);
-                    return set_error(e == hipErrorOutOfMemory ? OHGPU_ERR_NOMEM : OHGPU_ERR_DEVICE, "record upload: %s", hipGetErrorString(e));
+                    return set_error(hip_code(e), "record upload: %s", hipGetErrorString(e));
                 }
                 b->fmtline.n_wide = (uint32_t)recs.size();
                 return OHGPU_OK;
@@ -276,7 +276,7 @@ int plan_fmt_line(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_fmt_desc* descs, s
             if (e == hipSuccess) e = hipMemcpy(b->fmtline.d_chunks, recs.data(), recs.size() * sizeof(FmtChunk), hipMemcpyHostToDevice);
             if (e != hipSuccess) {
                 free_fmt_line(ctx, b);
-                return set_error(e == hipErrorOutOfMemory ? OHGPU_ERR_NOMEM : OHGPU_ERR_DEVICE, "record upload: %s", hipGetErrorString(e));
+                return set_error(hip_code(e), "record upload: %s", hipGetErrorString(e));
             }
             b->fmtline.n_chunks = (uint32_t)recs.size();
             b->fmtline.group_kind = kind;
@@ -352,7 +352,7 @@ int plan_fmt_line(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_fmt_desc* descs, s
     if (e == hipSuccess) e = hipMemcpy(b->fmtline.d_chunks, chunks.data(), chunks.size() * sizeof(FmtChunk), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         free_fmt_line(ctx, b);
-        return set_error(e == hipErrorOutOfMemory ? OHGPU_ERR_NOMEM : OHGPU_ERR_DEVICE, "chunk plan upload: %s", hipGetErrorString(e));
+        return set_error(hip_code(e), "chunk plan upload: %s", hipGetErrorString(e));
     }
     b->fmtline.n_chunks = (uint32_t)chunks.size();
     b->fmtline.enabled = true;

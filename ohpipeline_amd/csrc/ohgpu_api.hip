@@ -193,7 +193,7 @@ static int stage_reserve(ohgpu_ctx* ctx, void** p, size_t* cap, size_t bytes, bo
     const hipError_t e = pinned_host ? hipHostMalloc(p, want, hipHostMallocDefault) : hipMalloc(p, want);
     if (e != hipSuccess) {
         *p = nullptr;
-        return set_error(e == hipErrorOutOfMemory ? OHGPU_ERR_NOMEM : OHGPU_ERR_DEVICE, "host-buffer staging (%zu bytes): %s", want, hipGetErrorString(e));
+        return set_error(hip_code(e), "host-buffer staging (%zu bytes): %s", want, hipGetErrorString(e));
     }
     *cap = want;
     if (!pinned_host) { std::lock_guard<std::mutex> hold(ctx->cache.m); ctx->cache.device_allocs++; }

@@ -352,7 +352,6 @@ struct FlacState {
     void* d_probes = nullptr; size_t probes_cap = 0;  // flaccore::Probe, sorted
     void* d_rowcand = nullptr; void* d_subs = nullptr; size_t rows_cap = 0;   // per row (candidate, channel): its candidate; flaccore::Sub
     void* d_rows = nullptr;   size_t rows_words = 0;  // int32 [rows][max_blocksize]
-    bool  rows_cached = false;                        // ... from the context's block cache (else hipMalloc'ed)
     std::vector<flaccore::Probe> host_probes;
     std::vector<uint32_t> host_rowcand;
     std::vector<uint32_t> host_list;
@@ -375,7 +374,6 @@ struct AlacState {
     void* d_rowpacket = nullptr;                      // uint32[n_rows]: the row's packet, ~0u for padding
     void* d_groupbase = nullptr;                      // uint64[n_groups + 1]
     void* d_rows = nullptr; size_t rows_bytes = 0;    // int32, the groups one after the other
-    bool  rows_cached = false;                        // ... from the context's block cache (else hipMalloc'ed)
     hipEvent_t ev[4] = {};
     hipStream_t last_stream = nullptr;
     bool ran = false;
@@ -544,6 +542,14 @@ int set_error(int code, const char* fmt, ...);
         hipError_t e_ = (expr);                                                                     \
         if (e_ != hipSuccess) return ::ohgpu::set_error(OHGPU_ERR_DEVICE, "%s failed: %s", #expr,  \
                                                         hipGetErrorString(e_));                     \
+    } while (0)
+// OHGPU_HIP_TRY_ALLOC: the same for the plans' calls, which allocate -- out of device memory is OHGPU_ERR_NOMEM, any other failure
+// OHGPU_ERR_DEVICE (hip_code alone where the caller has a text of its own)
+inline int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? OHGPU_ERR_NOMEM : OHGPU_ERR_DEVICE; }
+#define OHGPU_HIP_TRY_ALLOC(expr)                                                                                              \
+    do {                                                                                                                       \
+        const hipError_t e_ = (expr);                                                                                          \
+        if (e_ != hipSuccess) return ::ohgpu::set_error(::ohgpu::hip_code(e_), "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
 // The release functions (free_pcm_line, free_fmt_line, free_dsd_line, flac_free, alac_free, raop_free, free_flywheel, free_src_fast, free_ohm): what

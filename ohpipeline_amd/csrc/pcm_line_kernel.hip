@@ -659,14 +659,14 @@ int plan_pcm_line(ohgpu_ctx* ctx, ohgpu_batch* b, const ohgpu_msg_desc* descs, s
     if (e == hipSuccess) e = hipMemcpy(b->line.d_chunks, all.data(), all.size() * sizeof(PcmChunk), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         free_pcm_line(ctx, b);
-        return set_error(e == hipErrorOutOfMemory ? OHGPU_ERR_NOMEM : OHGPU_ERR_DEVICE, "chunk plan upload: %s", hipGetErrorString(e));
+        return set_error(hip_code(e), "chunk plan upload: %s", hipGetErrorString(e));
     }
     if (prefixes && blob_bytes) {
         e = ctx_dev_alloc(ctx, &b->line.d_prefix, blob_bytes);
         if (e == hipSuccess) e = hipMemcpy(b->line.d_prefix, blob, blob_bytes, hipMemcpyHostToDevice);
         if (e != hipSuccess) {
             free_pcm_line(ctx, b);
-            return set_error(e == hipErrorOutOfMemory ? OHGPU_ERR_NOMEM : OHGPU_ERR_DEVICE, "prefix blob upload: %s", hipGetErrorString(e));
+            return set_error(hip_code(e), "prefix blob upload: %s", hipGetErrorString(e));
         }
         b->line.prefixed = true;
     }

@@ -40,26 +40,20 @@ __global__ __launch_bounds__(kRaopThreads) void raop_decrypt_kernel(const Piece*
     piece_lane(pc, threadIdx.x % 64u, keys + (size_t)pc.key * kKeyWords, src, pc.to_arena ? dst : scratch, td0, isbox);
 }
 
-#define RAOP_TRY(expr)                                                                                                             \
-    do {                                                                                                                           \
-        const hipError_t e_ = (expr);                                                                                              \
-        if (e_ != hipSuccess) return set_error(e_ == hipErrorOutOfMemory ? OHGPU_ERR_NOMEM : OHGPU_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 int raop_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Job* jobs, size_t n_jobs)
 {
     RaopState& r = *b->raop;
     std::vector<Piece> pieces;
     plan_pieces(jobs, n_jobs, &pieces);
     r.n_pieces = (uint32_t)pieces.size();
-    RAOP_TRY(hipEventCreate(&r.ev0));
+    OHGPU_HIP_TRY_ALLOC(hipEventCreate(&r.ev0));
     if (pieces.empty()) return OHGPU_OK;
     r.keys_bytes = r.keys.size() * sizeof(uint32_t);
-    RAOP_TRY(ctx_dev_alloc(ctx, &r.d_pieces, pieces.size() * sizeof(Piece)));
-    RAOP_TRY(ctx_dev_alloc(ctx, &r.d_keys, r.keys_bytes));
-    if (r.plain_bytes) RAOP_TRY(ctx_dev_alloc(ctx, &r.d_plain, r.plain_bytes));
-    RAOP_TRY(hipMemcpy(r.d_pieces, pieces.data(), pieces.size() * sizeof(Piece), hipMemcpyHostToDevice));
-    RAOP_TRY(hipMemcpy(r.d_keys, r.keys.data(), r.keys_bytes, hipMemcpyHostToDevice));
+    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &r.d_pieces, pieces.size() * sizeof(Piece)));
+    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &r.d_keys, r.keys_bytes));
+    if (r.plain_bytes) OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &r.d_plain, r.plain_bytes));
+    OHGPU_HIP_TRY_ALLOC(hipMemcpy(r.d_pieces, pieces.data(), pieces.size() * sizeof(Piece), hipMemcpyHostToDevice));
+    OHGPU_HIP_TRY_ALLOC(hipMemcpy(r.d_keys, r.keys.data(), r.keys_bytes, hipMemcpyHostToDevice));
     return OHGPU_OK;
 }
 
@@ -83,12 +77,12 @@ int raop_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
 {
     const RaopState& r = *b->raop;
     AlacState& a = *b->alac;
-    if (a.last_stream && a.last_stream != s) RAOP_TRY(hipStreamSynchronize(a.last_stream));      // (the scratch serves one run at a time)
-    RAOP_TRY(hipEventRecord(r.ev0, s));
+    if (a.last_stream && a.last_stream != s) OHGPU_HIP_TRY_ALLOC(hipStreamSynchronize(a.last_stream));      // (the scratch serves one run at a time)
+    OHGPU_HIP_TRY_ALLOC(hipEventRecord(r.ev0, s));
     if (r.n_pieces) {
         hipLaunchKernelGGL(raop_decrypt_kernel, dim3((r.n_pieces + kRaopWaves - 1) / kRaopWaves), dim3(kRaopThreads), 0, s, (const Piece*)r.d_pieces, r.n_pieces,
                            (const uint32_t*)r.d_keys, src, (uint8_t*)r.d_plain, dst);
-        RAOP_TRY(hipGetLastError());
+        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
     }
     return OHGPU_OK;
 }

@@ -62,7 +62,7 @@ struct Slab {
         hipError_t e = ctx ? ctx_dev_alloc(ctx, slab, total) : hipMalloc(slab, total);
         if (e == hipSuccess && !host.empty()) e = hipMemcpy(*slab, host.data(), host.size(), hipMemcpyHostToDevice);
         if (e == hipSuccess && tail) *tail_at.first = (uint8_t*)*slab + tail_at.second;
-        if (e != hipSuccess) return set_error(e == hipErrorOutOfMemory ? OHGPU_ERR_NOMEM : OHGPU_ERR_DEVICE,
+        if (e != hipSuccess) return set_error(hip_code(e),
                                               "block plan upload: %s", hipGetErrorString(e));
         for (auto& a : at) *a.first = (uint8_t*)*slab + a.second;
         return OHGPU_OK;

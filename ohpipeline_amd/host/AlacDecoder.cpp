@@ -13,20 +13,20 @@ AlacBatchDecoder::AlacBatchDecoder()
     memset(&iConfig, 0, sizeof(iConfig));
 }
 
+void AlacCheckConfig(TBool aParsed, const ohgpu_alac_config& aConfig, TBool& aCorrupt)
+{
+    const TBool was = aCorrupt;
+    aCorrupt = true;                                                  // (while a check can throw)
+    if (!aParsed) THROW(CodecStreamCorrupt);                          // AlacApple.cpp:147-157; CodecRaopApple.cpp:80-83, 211-213
+    if (aConfig.frame_length == 0 || aConfig.frame_length > AlacBatchDecoder::kFrameLengthMost || aConfig.channels == 0
+        || aConfig.channels > AlacBatchDecoder::kChannelsMost) THROW(CodecStreamCorrupt);   // AlacAppleBase.cpp:69-76; CodecRaopApple.cpp:85-94
+    if (aConfig.bit_depth != 16 && aConfig.bit_depth != 20 && aConfig.bit_depth != 24 && aConfig.bit_depth != 32) THROW(CodecStreamFeatureUnsupported);
+    aCorrupt = was;
+}
+
 void AlacBatchDecoder::SetConfig(const Brx& aCookie, TUint aTimescale, TUint64 aDuration)
 {
-    if (ohgpu_alac_config_parse(aCookie.Ptr(), aCookie.Bytes(), &iConfig) != OHGPU_OK || aTimescale == 0) {
-        iCorrupt = true;
-        THROW(CodecStreamCorrupt);
-    }
-    if (iConfig.frame_length == 0 || iConfig.frame_length > kFrameLengthMost || iConfig.channels == 0 || iConfig.channels > kChannelsMost) {
-        iCorrupt = true;
-        THROW(CodecStreamCorrupt);                                    // AlacApple.cpp:147-157, AlacAppleBase.cpp:69-76
-    }
-    if (iConfig.bit_depth != 16 && iConfig.bit_depth != 20 && iConfig.bit_depth != 24 && iConfig.bit_depth != 32) {
-        iCorrupt = true;
-        THROW(CodecStreamFeatureUnsupported);
-    }
+    AlacCheckConfig(ohgpu_alac_config_parse(aCookie.Ptr(), aCookie.Bytes(), &iConfig) == OHGPU_OK && aTimescale != 0, iConfig, iCorrupt);
     iRate = aTimescale;                                         // AlacApple.cpp:177: the container's, not the configuration's
     iLengthJiffies = aDuration * Jiffies::kPerSecond / aTimescale;
     iConfigured = true;
@@ -44,6 +44,36 @@ void AlacBatchDecoder::SeekToPacket(TUint64 aIndex)
     iPending.clear();
     iSizes.clear();
     iNextPacket = aIndex;
+}
+
+TBool AlacDeliver(CodecController& aController, TUint64& aTrackOffset, TBool& aAnnounced, TUint aRate, TUint64 aLengthJiffies,
+                  const ohgpu_alac_stream_desc& aDesc, const ohgpu_alac_stream_result& aResult, const ohgpu_alac_packet_result* aEach, const TByte* aDst)
+{
+    static const TByte kName[] = {'A', 'L', 'A', 'C'};
+    const ohgpu_alac_config& c = aDesc.config;
+    const TUint sampleBytes = (c.bit_depth / 8u) * c.channels;
+    if (!aAnnounced) {
+        // AlacApple.cpp:175-185, CodecRaopApple.cpp:109-117: the PCM's bit rate (the stream is lossless)
+        aController.OutputDecodedStream(aRate * sampleBytes * 8, c.bit_depth, aRate, c.channels, Brn(kName, sizeof(kName)), aLengthJiffies, 0, true);
+        aAnnounced = true;
+    }
+    for (uint32_t k = 0; k < aResult.packets_ok; k++) {
+        // AlacAppleBase.cpp:94-111: a packet leaves in pieces of kMaxPieceBytes, the count restarting with every packet
+        const TByte* audio = aDst + aDesc.dst_offset + (size_t)k * c.frame_length * sampleBytes;
+        const TUint bytes = aEach[aDesc.first_packet + k].samples * sampleBytes;
+        for (TUint done = 0; done < bytes; ) {
+            const TUint n = std::min(AlacBatchDecoder::kMaxPieceBytes, bytes - done);
+            aTrackOffset += aController.OutputAudioPcm(Brn(audio + done, n), c.channels, aRate, c.bit_depth, AudioDataEndian::Little, aTrackOffset);
+            done += n;
+        }
+    }
+    return aResult.packets_ok == aDesc.n_packets;
+}
+
+void AlacThrowFirstBad(const ohgpu_alac_stream_result* aFirstBad)
+{
+    if (aFirstBad != nullptr && aFirstBad->first_bad_status == OHGPU_ALAC_UNSUPPORTED) THROW(CodecStreamFeatureUnsupported);
+    if (aFirstBad != nullptr) THROW(CodecStreamCorrupt);              // AlacAppleBase.cpp:85-88
 }
 
 void AlacBatchDecoder::Flush(MsgFactory& aFactory, Lane* aLanes, size_t aCount)
@@ -70,8 +100,8 @@ void AlacBatchDecoder::Flush(MsgFactory& aFactory, Lane* aLanes, size_t aCount)
             packets.push_back(p);
             at += bytes;
         }
-        srcTotal += (d.iPending.size() + 15u) & ~(TUint64)15u;
-        dstTotal += ((TUint64)s.n_packets * d.iConfig.frame_length * d.iConfig.channels * (d.iConfig.bit_depth / 8) + 15u) & ~(TUint64)15u;
+        srcTotal += MsgFactory::ArenaShare(d.iPending.size());
+        dstTotal += MsgFactory::ArenaShare((TUint64)s.n_packets * d.iConfig.frame_length * d.iConfig.channels * (d.iConfig.bit_depth / 8));
         descs.push_back(s);
         laneOf.push_back(k);
     }
@@ -90,43 +120,22 @@ void AlacBatchDecoder::Flush(MsgFactory& aFactory, Lane* aLanes, size_t aCount)
     const int err = ohgpu_alac_process_host(aFactory.Gpu(), descs.data(), descs.size(), packets.data(), packets.size(), src, srcTotal, dst, dstTotal,
                                             results.data(), each.data());
     ASSERT(err == OHGPU_OK);
-    static const TByte kName[] = {'A', 'L', 'A', 'C'};
-    size_t firstBad = descs.size();
+    const ohgpu_alac_stream_result* firstBad = nullptr;
     for (size_t i = 0; i < descs.size(); i++) {
         Lane& lane = aLanes[laneOf[i]];
         AlacBatchDecoder& d = *lane.decoder;
-        const ohgpu_alac_config& c = d.iConfig;
-        const TUint sampleBytes = (c.bit_depth / 8u) * c.channels;
-        if (!d.iAnnounced) {
-            // AlacApple.cpp:175-185: the PCM's bit rate (the stream is lossless), the container's rate and length
-            lane.controller->OutputDecodedStream(d.iRate * sampleBytes * 8, c.bit_depth, d.iRate, c.channels, Brn(kName, sizeof(kName)),
-                                                 d.iLengthJiffies, 0, true);
-            d.iAnnounced = true;
-        }
-        for (uint32_t k = 0; k < results[i].packets_ok; k++) {
-            // AlacAppleBase.cpp:94-111: a packet leaves in pieces of kMaxPieceBytes, the count restarting with every packet
-            const TByte* audio = dst + descs[i].dst_offset + (size_t)k * c.frame_length * sampleBytes;
-            const TUint bytes = each[descs[i].first_packet + k].samples * sampleBytes;
-            for (TUint done = 0; done < bytes; ) {
-                const TUint n = std::min(kMaxPieceBytes, bytes - done);
-                lane.trackOffset += lane.controller->OutputAudioPcm(Brn(audio + done, n), c.channels, d.iRate, c.bit_depth, AudioDataEndian::Little,
-                                                                    lane.trackOffset);
-                done += n;
-            }
-        }
+        // AlacApple.cpp:175-185: the container's rate and length are what is announced
+        const TBool ok = AlacDeliver(*lane.controller, lane.trackOffset, d.iAnnounced, d.iRate, d.iLengthJiffies, descs[i], results[i], each.data(), dst);
         d.iSamples += results[i].samples;
         d.iNextPacket += results[i].packets_ok;
         d.iPending.clear();
         d.iSizes.clear();
-        if (results[i].packets_ok != descs[i].n_packets) {
+        if (!ok) {
             d.iCorrupt = true;
-            if (firstBad == descs.size()) firstBad = i;
+            if (firstBad == nullptr) firstBad = &results[i];
         }
     }
-    if (firstBad != descs.size()) {
-        if (results[firstBad].first_bad_status == OHGPU_ALAC_UNSUPPORTED) THROW(CodecStreamFeatureUnsupported);
-        THROW(CodecStreamCorrupt);                                    // AlacAppleBase.cpp:85-88
-    }
+    AlacThrowFirstBad(firstBad);
 }
 
 } // namespace Media

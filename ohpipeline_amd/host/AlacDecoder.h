@@ -68,5 +68,16 @@ private:
     TUint64 iNextPacket, iSamples;
 };
 
+// The Apple Lossless output path, which host/RaopDecoder.h shares: RAOP's streams are Apple Lossless streams behind a cipher.
+/** What StreamInitialise asks of a configuration, in its order: aParsed, a frame length of 1..4096 and one or two channels (else
+ *  CodecStreamCorrupt), a bit depth of 16, 20, 24 or 32 (else CodecStreamFeatureUnsupported).  Sets aCorrupt before it throws. */
+void AlacCheckConfig(TBool aParsed, const ohgpu_alac_config& aConfig, TBool& aCorrupt);
+/** A stream's share of a tick's output: the stream announced once (aRate and aLengthJiffies are the caller's), then every packet in
+ *  front of the first that did not decode, in CodecAlacAppleBase::Decode's pieces.  False when there was such a packet. */
+TBool AlacDeliver(CodecController& aController, TUint64& aTrackOffset, TBool& aAnnounced, TUint aRate, TUint64 aLengthJiffies,
+                  const ohgpu_alac_stream_desc& aDesc, const ohgpu_alac_stream_result& aResult, const ohgpu_alac_packet_result* aEach, const TByte* aDst);
+/** Once every lane has been served: the first bad lane's exception (aFirstBad null: none was bad). */
+void AlacThrowFirstBad(const ohgpu_alac_stream_result* aFirstBad);
+
 } // namespace Media
 } // namespace OpenHome

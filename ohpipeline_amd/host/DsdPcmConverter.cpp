@@ -122,8 +122,8 @@ void DsdPcmConverter::Flush(MsgFactory& aFactory, Lane* aLanes, size_t aCount)
         d.sample_block_words = (uint8_t)c.iSampleBlockWords;
         d.pad_bytes_per_chunk = (uint8_t)c.iPadBytesPerChunk;
         d.dst_endian = OHGPU_ENDIAN_BIG;
-        srcTotal += (d.src_chunks * c.iChunkBytes + 15u) & ~(TUint64)15u;
-        dstTotal += ((TUint64)d.n_frames * kFrameBytes + 15u) & ~(TUint64)15u;
+        srcTotal += MsgFactory::ArenaShare(d.src_chunks * c.iChunkBytes);
+        dstTotal += MsgFactory::ArenaShare((TUint64)d.n_frames * kFrameBytes);
         descs.push_back(d);
         laneOf.push_back(k);
     }

@@ -71,8 +71,8 @@ void FlacBatchDecoder::Flush(MsgFactory& aFactory, Lane* aLanes, size_t aCount)
         s.channels = info.channels;
         s.bits = info.bits;
         s.flags = OHGPU_FLAC_FLAG_AT_FRAME | OHGPU_FLAC_OUT_PACKED_BE;
-        srcTotal += (s.src_bytes + 15u) & ~(TUint64)15u;
-        dstTotal += ((TUint64)s.max_samples * info.channels * (info.bits / 8) + 15u) & ~(TUint64)15u;
+        srcTotal += MsgFactory::ArenaShare(s.src_bytes);
+        dstTotal += MsgFactory::ArenaShare((TUint64)s.max_samples * info.channels * (info.bits / 8));
         framesMax += frames;
         descs.push_back(s);
         laneOf.push_back(k);

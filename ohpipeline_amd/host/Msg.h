@@ -499,6 +499,8 @@ public:
      *  uploaded when the factory has a device. */
     const PullFilter& SharedPullFilter(TUint aRateIn, TUint aRateOut, TUint aTapsPerPhase, TUint aPhasesLog2, double aBeta,
                                        double aPassHz, double aMaxPull);
+    /** A stream's share of an arena: every stream starts at a 16-byte boundary (the device's wide loads and stores). */
+    static TUint64 ArenaShare(TUint64 aBytes) { return (aBytes + 15u) & ~(TUint64)15u; }
     /** The driver thread's pinned staging for host-buffer reads (PlayableBatch::Run): at least the sizes asked for, kept and grown
      *  with headroom.  Like the ohgpu_ctx it belongs to one thread at a time. */
     void ReserveArena(size_t aSrcBytes, size_t aDstBytes, TByte*& aSrc, TByte*& aDst);

@@ -34,18 +34,7 @@ void RaopBatchDecoder::SetSession(const Brx& aFmtp, const Brx& aKey, const Brx& 
     ASSERT(aIv.Bytes() == kKeyBytes);
     Drop();
     iConfigured = false;
-    if (ohgpu_raop_fmtp_parse((const char*)aFmtp.Ptr(), aFmtp.Bytes(), &iConfig) != OHGPU_OK) {
-        iCorrupt = true;
-        THROW(CodecStreamCorrupt);                                    // CodecRaopApple.cpp:80-83, 211-213
-    }
-    if (iConfig.frame_length == 0 || iConfig.frame_length > kFrameLengthMost || iConfig.channels == 0 || iConfig.channels > kChannelsMost) {
-        iCorrupt = true;
-        THROW(CodecStreamCorrupt);                                    // CodecRaopApple.cpp:85-94
-    }
-    if (iConfig.bit_depth != 16 && iConfig.bit_depth != 20 && iConfig.bit_depth != 24 && iConfig.bit_depth != 32) {
-        iCorrupt = true;
-        THROW(CodecStreamFeatureUnsupported);
-    }
+    AlacCheckConfig(ohgpu_raop_fmtp_parse((const char*)aFmtp.Ptr(), aFmtp.Bytes(), &iConfig) == OHGPU_OK, iConfig, iCorrupt);
     memcpy(iKey, aKey.Ptr(), kKeyBytes);
     memcpy(iIv, aIv.Ptr(), kKeyBytes);
     iConfigured = true;
@@ -99,8 +88,8 @@ void RaopBatchDecoder::Flush(MsgFactory& aFactory, Lane* aLanes, size_t aCount)
             packets.push_back(p);
         }
         base.push_back(srcTotal);
-        srcTotal += (d.iPending.size() + 15u) & ~(TUint64)15u;
-        dstTotal += ((TUint64)s.alac.n_packets * d.iConfig.frame_length * d.iConfig.channels * (d.iConfig.bit_depth / 8) + 15u) & ~(TUint64)15u;
+        srcTotal += MsgFactory::ArenaShare(d.iPending.size());
+        dstTotal += MsgFactory::ArenaShare((TUint64)s.alac.n_packets * d.iConfig.frame_length * d.iConfig.channels * (d.iConfig.bit_depth / 8));
         descs.push_back(s);
         laneOf.push_back(k);
     }
@@ -120,41 +109,21 @@ void RaopBatchDecoder::Flush(MsgFactory& aFactory, Lane* aLanes, size_t aCount)
                                             results.data(), each.data());
     for (ohgpu_raop_stream_desc& s : descs) for (uint8_t& b : s.aes_key) *(volatile uint8_t*)&b = 0;
     ASSERT(err == OHGPU_OK);
-    static const TByte kName[] = {'A', 'L', 'A', 'C'};
-    size_t firstBad = descs.size();
+    const ohgpu_alac_stream_result* firstBad = nullptr;
     for (size_t i = 0; i < descs.size(); i++) {
         Lane& lane = aLanes[laneOf[i]];
         RaopBatchDecoder& d = *lane.decoder;
-        const ohgpu_alac_config& c = d.iConfig;
-        const TUint sampleBytes = (c.bit_depth / 8u) * c.channels;
-        if (!d.iAnnounced) {
-            // CodecRaopApple.cpp:109-117: the PCM's bit rate, the fmtp's sample rate, no track length, lossless
-            lane.controller->OutputDecodedStream(c.sample_rate * sampleBytes * 8, c.bit_depth, c.sample_rate, c.channels, Brn(kName, sizeof(kName)), 0, 0, true);
-            d.iAnnounced = true;
-        }
-        for (uint32_t k = 0; k < results[i].packets_ok; k++) {
-            // AlacAppleBase.cpp:94-111: a packet leaves in pieces of kMaxPieceBytes, the count restarting with every packet
-            const TByte* audio = dst + descs[i].alac.dst_offset + (size_t)k * c.frame_length * sampleBytes;
-            const TUint bytes = each[descs[i].alac.first_packet + k].samples * sampleBytes;
-            for (TUint done = 0; done < bytes; ) {
-                const TUint n = std::min(kMaxPieceBytes, bytes - done);
-                lane.trackOffset += lane.controller->OutputAudioPcm(Brn(audio + done, n), c.channels, c.sample_rate, c.bit_depth, AudioDataEndian::Little,
-                                                                    lane.trackOffset);
-                done += n;
-            }
-        }
+        // CodecRaopApple.cpp:109-117: the fmtp's sample rate and no track length are what is announced
+        const TBool ok = AlacDeliver(*lane.controller, lane.trackOffset, d.iAnnounced, d.iConfig.sample_rate, 0, descs[i].alac, results[i], each.data(), dst);
         d.iSamples += results[i].samples;
         d.iPackets += results[i].packets_ok;
         d.Drop();
-        if (results[i].packets_ok != descs[i].alac.n_packets) {
+        if (!ok) {
             d.iCorrupt = true;
-            if (firstBad == descs.size()) firstBad = i;
+            if (firstBad == nullptr) firstBad = &results[i];
         }
     }
-    if (firstBad != descs.size()) {
-        if (results[firstBad].first_bad_status == OHGPU_ALAC_UNSUPPORTED) THROW(CodecStreamFeatureUnsupported);
-        THROW(CodecStreamCorrupt);                                    // AlacAppleBase.cpp:85-88
-    }
+    AlacThrowFirstBad(firstBad);
 }
 
 } // namespace Media

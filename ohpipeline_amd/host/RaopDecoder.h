@@ -17,9 +17,7 @@
 
 #include <vector>
 
-#include "../../include/ohgpu.h"
-#include "DecodedAudioAggregator.h"
-#include "Msg.h"
+#include "AlacDecoder.h"
 
 namespace OpenHome {
 OH_EXCEPTION(InvalidRaopPacket);
@@ -30,6 +28,8 @@ public:
     static const TUint kMaxPieceBytes = DecodedAudio::kMaxBytes;    // AlacAppleBase.cpp:96
     static const TUint kChannelsMost = 2;                             // CodecRaopApple.cpp:85-94 (kMaxChannels, kMaxSamplesPerFrame of AlacAppleBase.h)
     static const TUint kFrameLengthMost = 4096;
+    static_assert(kMaxPieceBytes == AlacBatchDecoder::kMaxPieceBytes && kChannelsMost == AlacBatchDecoder::kChannelsMost
+                  && kFrameLengthMost == AlacBatchDecoder::kFrameLengthMost, "the Apple Lossless output path (AlacDecoder.h) applies AlacBatchDecoder's");
     static const TUint kMaxDatagramBytes = 1472;                      // RtpPacketRaop::kMaxPacketBytes
     static const TUint kRtpHeaderBytes = 4;                           // RtpHeaderRaop::kBytes
     static const TUint kAudioHeaderBytes = 8;                         // RaopPacketAudio::kAudioSpecificHeaderBytes: timestamp, ssrc
