@@ -31,6 +31,8 @@
  *       (Codec/AlacApple.cpp, AlacAppleBase.cpp:20-115; thirdparty/apple_alac by its behaviour)   -> TInt32 planes or the decoder's packed bytes
  *   RaopAudioDecryptor::Decrypt + CodecRaopApple: AES-128-CBC per packet, then as above   ohgpu_raop_batch_run()
  *       (Av/Raop/ProtocolRaop.cpp:1477-1502, Av/Raop/CodecRaopApple.cpp:61-214)          -> the same, or the plaintext alone
+ *   OhmHeader::Internalise + OhmMsgAudio::Create(IReader&) + ProtocolOhBase's frame sequencer   ohgpu_ohm_rx_batch_run()
+ *       (Av/Songcast/Ohm.cpp:22-42, OhmMsg.cpp:101-175, ProtocolOhBase.cpp:254-553)            -> CodecPcm's big-endian bytes
  *   "SampleRateConverter" -- NOT PRESENT in the reference  ohgpu_src_* (own spec)
  *
  * The reference binds nothing through FFI today (it is one C++ static library); INTEGRATION.md
@@ -712,6 +714,126 @@ int ohgpu_ohm_process_host(ohgpu_ctx* ctx, const ohgpu_ohm_stream* streams, size
                            const ohgpu_ohm_frame_desc* frames, size_t n_frames,
                            const ohgpu_ohm_fragment* fragments, size_t n_fragments,
                            const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes);
+
+/* ---- Songcast receiver: parse, reorder and unpack OHM audio (the text is csrc/ohm_rx_core.h) ----
+ * The other end of ohgpu_ohm_*: received datagrams in, big-endian interleaved PCM at the wire's depth out -- what the reference's
+ * ProtocolOhm / ProtocolOhu hand to CodecPcm.  Per datagram OhmHeader::Internalise (Av/Songcast/Ohm.cpp:22-42) and
+ * OhmMsgAudio::Create(IReader&, const OhmHeader&) (OhmMsg.cpp:101-175); per stream ProtocolOhBase::Process(OhmMsgAudio&), Repair,
+ * RepairReset and the decisions of OutputAudio (ProtocolOhBase.cpp:254-553); then OutputData(aMsg.Audio()).  Three launches on one
+ * stream -- parse (a lane per datagram), sequence (a lane per stream), gather (a wave per datagram) -- and no host synchronisation.
+ * The source arena holds the datagrams as they came off the socket, each a whole OHM message at a src_offset that is a multiple of
+ * 4; a stream's datagrams are listed in arrival order.  Messages of other types (track, metatext, join, listen, leave, slave,
+ * resend, audio blob) may be in the table: they are reported (status, msg_type), not interpreted.  Timers, sockets, join / listen,
+ * track and metatext stay the caller's; the resend request a repair timer would make at the end of the batch is in the result. */
+#define OHGPU_OHM_RX_OK          0u
+#define OHGPU_OHM_RX_NOT_OHM     1u   /* wrong magic or major version, or a type OhmHeader::Internalise throws OhmError for (Ohm.cpp:35) */
+#define OHGPU_OHM_RX_NOT_AUDIO   2u   /* a valid header of another type: msg_type says which */
+#define OHGPU_OHM_RX_TRUNCATED   3u   /* fewer than 8 bytes; the header's total is not the table's `bytes`; below 8 + 50 + codec bytes */
+#define OHGPU_OHM_RX_BAD_HEADER  4u   /* audio header length != 50, reserved byte != 0, codec name over 29 bytes (the reference ASSERTs) */
+#define OHGPU_OHM_RX_OVERSIZE    5u   /* more than OHGPU_OHM_MAX_AUDIO_BYTES audio bytes */
+/* (the checks are made in this order -- csrc/ohm_rx_core.h -- and the first that fails names the status; every status but OK is
+ * ignored by the sequencer and the stream goes on, as ProtocolOhm swallows OhmError, ProtocolOhm.cpp:209) */
+#define OHGPU_OHM_RX_OUTPUT            1u   /* its audio is in the stream's run at dst_offset; `order` is its place in the output order */
+#define OHGPU_OHM_RX_DUPLICATE         2u   /* a frame already waiting, or a resent frame at or behind the last one output */
+#define OHGPU_OHM_RX_PENDING           3u   /* still waiting at the end of the batch: `order` is its place in the replay (below) */
+#define OHGPU_OHM_RX_DROPPED_BY_RESET  4u   /* the frame that caused a RepairReset, and every frame that waited when one ran */
+#define OHGPU_OHM_RX_STALE             5u   /* a frame in the past that is no resend, outside a repair: the stream stops (ReaderError) */
+#define OHGPU_OHM_RX_NOT_REACHED       6u   /* behind the datagram the stream stopped at */
+#define OHGPU_OHM_RX_IGNORED           7u   /* status != OK */
+#define OHGPU_OHM_RX_EVENT_NEW_STREAM  1u   /* OutputAudio sends a MsgDecodedStream in front of this frame (ProtocolOhBase.cpp:464-488) */
+#define OHGPU_OHM_RX_EVENT_DELAY       2u   /* ... a delay: the rate or the media latency changed (:489-493) */
+#define OHGPU_OHM_RX_EVENT_HALT        4u   /* the wire's halt flag: wait and halt behind this frame, and the stream stops (:504-512) */
+#define OHGPU_OHM_RX_STOP_NONE   0u
+#define OHGPU_OHM_RX_STOP_STALE  1u
+#define OHGPU_OHM_RX_STOP_HALT   2u
+#define OHGPU_OHM_RX_MAX_RESEND  20u   /* ProtocolOhBase::kMaxRepairMissedFrames */
+
+typedef struct ohgpu_ohm_rx_datagram {   /* 16 bytes */
+    uint64_t src_offset;            /* a multiple of 4 */
+    uint32_t bytes;                 /* as recvfrom returned */
+    uint32_t reserved;
+} ohgpu_ohm_rx_datagram;
+
+typedef struct ohgpu_ohm_rx_state {      /* 32 bytes: what ProtocolOhBase carries from one datagram to the next */
+    uint64_t last_sample_start;     /* iLastSampleStart (UINT_MAX, 0xffffffff, in a new receiver) */
+    uint32_t frame;                 /* iFrame */
+    uint32_t sample_rate;           /* iSampleRate */
+    uint32_t latency;               /* iLatency (the wire's media latency) */
+    uint8_t  running;               /* iRunning */
+    uint8_t  stream_msg_due;        /* iStreamMsgDue (1 in a new receiver) */
+    uint8_t  bit_depth;             /* iBitDepth */
+    uint8_t  channels;              /* iNumChannels */
+    uint32_t reserved[2];
+} ohgpu_ohm_rx_state;
+
+typedef struct ohgpu_ohm_rx_stream {     /* 64 bytes */
+    uint32_t first_datagram;        /* the stream's datagrams are [first_datagram, + n_datagrams) of the table, in arrival order; */
+    uint32_t n_datagrams;           /*   the streams' ranges tile the table in the streams' order */
+    uint64_t dst_offset;            /* the output run starts here, any byte address */
+    uint64_t dst_capacity;          /* >= the sum over the stream's datagrams of max(bytes - 58, 0): no parse is needed to size it */
+    ohgpu_ohm_rx_state state_in;
+    uint32_t reserved[2];
+} ohgpu_ohm_rx_stream;
+
+typedef struct ohgpu_ohm_rx_record {     /* 104 bytes, one per datagram */
+    uint8_t  status;                /* OHGPU_OHM_RX_OK ... _OVERSIZE */
+    uint8_t  disposition;           /* OHGPU_OHM_RX_OUTPUT ... _IGNORED */
+    uint8_t  events;                /* OHGPU_OHM_RX_EVENT_*, of an OUTPUT record */
+    uint8_t  flags;                 /* the wire's: OHGPU_OHM_FLAG_* and 0x10 (timestamped2) */
+    uint8_t  msg_type;              /* OhmHeader's type, from NOT_AUDIO on (0 for NOT_OHM and a TRUNCATED header) */
+    uint8_t  bit_depth, channels, codec_bytes;      /* every field from here on is 0 unless status is OK */
+    uint16_t samples;
+    int16_t  volume_offset;
+    uint32_t frame, network_timestamp, media_latency, media_timestamp, sample_rate;
+    uint64_t sample_start, samples_total;
+    uint32_t bit_rate;
+    uint32_t audio_offset;          /* of the payload within the datagram: 58 + codec_bytes */
+    uint32_t audio_bytes;
+    uint32_t order;                 /* OUTPUT: 0, 1, ... in the stream's output order; PENDING: 0, 1, ... in replay order */
+    uint64_t dst_offset;            /* OUTPUT: where its audio_bytes lie in the destination arena */
+    uint8_t  codec[32];
+} ohgpu_ohm_rx_record;
+
+typedef struct ohgpu_ohm_rx_stream_result {   /* 136 bytes */
+    ohgpu_ohm_rx_state state_out;   /* the state to give the next batch.  After a stop it is what WaitForPipelineToEmpty's RepairReset
+                                       leaves (ProtocolOhBase.cpp:157-160): not running, stream message due, frame and format kept */
+    uint64_t out_bytes;             /* the run [dst_offset, + out_bytes) was written */
+    uint32_t n_output;
+    uint32_t n_pending;             /* PENDING records: the caller queues those datagrams, in `order`, in front of the next batch's
+                                       arrivals -- that replay rebuilds the waiting set with no event */
+    uint32_t stop_reason;           /* OHGPU_OHM_RX_STOP_* */
+    uint32_t n_resend;              /* what TimerRepairExpired would ask for now (:407-447): the first 20 missing frames below the */
+    uint32_t resend[20];            /*   highest waiting one, ascending -- with the reference's unsigned loops: a gap that spans the
+                                       2^32 wrap contributes nothing */
+} ohgpu_ohm_rx_stream_result;
+
+/* Host only, no device needed: the validation ohgpu_ohm_rx_batch_create makes.  OHGPU_ERR_INVALID: a src_offset that is no multiple
+ * of 4, stream ranges that overlap or leave part of the table out, non-zero reserved fields.  OHGPU_ERR_BOUNDS: a datagram outside
+ * the source arena, a destination run [dst_offset, + dst_capacity) that ends outside the destination arena, or a dst_capacity below
+ * the sum over the stream's datagrams of max(bytes - 58, 0) -- so the device never has to refuse for room.  Destination runs of
+ * different streams must not overlap (not checked: as for every other family, overlapping outputs are the caller's mistake). */
+int ohgpu_ohm_rx_batch_check(const ohgpu_ohm_rx_stream* streams, size_t n, const ohgpu_ohm_rx_datagram* datagrams, size_t n_datagrams,
+                             uint64_t src_arena_bytes, uint64_t dst_arena_bytes);
+/* The tables go to the device; records, results and the sequencer's rings are the batch's, from the context's block cache.  An empty
+ * batch (no streams, no datagrams) is legal.  Freed with ohgpu_batch_destroy. */
+int ohgpu_ohm_rx_batch_create(ohgpu_ctx* ctx, const ohgpu_ohm_rx_stream* streams, size_t n, const ohgpu_ohm_rx_datagram* datagrams, size_t n_datagrams,
+                              uint64_t src_arena_bytes, uint64_t dst_arena_bytes, ohgpu_batch** batch);
+/* src_base MUST BE 4-BYTE ALIGNED (the parse and the gather load dwords): OHGPU_ERR_INVALID otherwise, before anything is queued;
+ * dst_base may be any address.  Parse, sequence, gather: queued on the stream, nothing waits for the host.  The batch owns its
+ * records: it runs on one stream at a time.  A second run allocates nothing on the device (ohgpu_device_allocations).  The gathered
+ * run is what ohgpu_pcm_* / ohgpu_src_* read as their source arena: the next batch may be queued on the same stream at once. */
+int ohgpu_ohm_rx_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* src_base, void* dst_base, void* stream);
+/* The last run's results (waits for that run): per stream (n = the batch's stream count) and / or per datagram (n_datagrams = the
+ * table's length); either pointer may be NULL with its count 0. */
+int ohgpu_ohm_rx_batch_results(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_ohm_rx_stream_result* streams, size_t n,
+                               ohgpu_ohm_rx_record* records, size_t n_datagrams);
+/* The last run's phases in milliseconds from device events: parse, sequence, gather (waits for that run). */
+int ohgpu_ohm_rx_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float ms[3]);
+/* Host-buffer convenience: one upload, one run, and of dst_host the bytes [dst_offset, + out_bytes) of every stream.  Either result
+ * pointer may be NULL. */
+int ohgpu_ohm_rx_process_host(ohgpu_ctx* ctx, const ohgpu_ohm_rx_stream* streams, size_t n, const ohgpu_ohm_rx_datagram* datagrams, size_t n_datagrams,
+                              const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes,
+                              ohgpu_ohm_rx_stream_result* stream_results, ohgpu_ohm_rx_record* records);
 
 /* ---- sample-rate converter (own specification; DESIGN.md "Resampler") ---- */
 /* Host-side filter design: Kaiser-windowed sinc, Q28 coefficients, coef_q28[p*T + k] = h[p + k*L].

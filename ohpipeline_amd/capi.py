@@ -124,6 +124,26 @@ OHM_FRAME_DESC = np.dtype([
     ("media_latency", "<u4"), ("media_timestamp", "<u4"), ("first_fragment", "<u4"), ("n_fragments", "<u2"),
     ("flags", "u1"), ("reserved", "u1", (5,))], align=False)
 assert OHM_STREAM.itemsize == 64 and OHM_FRAGMENT.itemsize == 24 and OHM_FRAME_DESC.itemsize == 48
+# Songcast receiver: the datagram table, the stream table with the state carried between batches, a record per
+# datagram (status, every header field, disposition) and a result per stream
+OHM_RX_OK, OHM_RX_NOT_OHM, OHM_RX_NOT_AUDIO, OHM_RX_TRUNCATED, OHM_RX_BAD_HEADER, OHM_RX_OVERSIZE = range(6)
+(OHM_RX_OUTPUT, OHM_RX_DUPLICATE, OHM_RX_PENDING, OHM_RX_DROPPED_BY_RESET, OHM_RX_STALE, OHM_RX_NOT_REACHED, OHM_RX_IGNORED) = range(1, 8)
+OHM_RX_EVENT_NEW_STREAM, OHM_RX_EVENT_DELAY, OHM_RX_EVENT_HALT = 1, 2, 4
+OHM_RX_STOP_NONE, OHM_RX_STOP_STALE, OHM_RX_STOP_HALT = 0, 1, 2
+OHM_RX_DATAGRAM = np.dtype([("src_offset", "<u8"), ("bytes", "<u4"), ("reserved", "<u4")], align=False)
+_OHM_RX_STATE = [("last_sample_start", "<u8"), ("frame", "<u4"), ("sample_rate", "<u4"), ("latency", "<u4"), ("running", "u1"),
+                 ("stream_msg_due", "u1"), ("bit_depth", "u1"), ("channels", "u1"), ("state_reserved", "<u4", (2,))]
+OHM_RX_STATE_FIELDS = tuple(name for name, *_ in _OHM_RX_STATE[:-1])
+OHM_RX_STREAM = np.dtype([("first_datagram", "<u4"), ("n_datagrams", "<u4"), ("dst_offset", "<u8"), ("dst_capacity", "<u8")] + _OHM_RX_STATE +
+                         [("reserved", "<u4", (2,))], align=False)
+OHM_RX_RECORD = np.dtype([
+    ("status", "u1"), ("disposition", "u1"), ("events", "u1"), ("flags", "u1"), ("msg_type", "u1"), ("bit_depth", "u1"), ("channels", "u1"),
+    ("codec_bytes", "u1"), ("samples", "<u2"), ("volume_offset", "<i2"), ("frame", "<u4"), ("network_timestamp", "<u4"),
+    ("media_latency", "<u4"), ("media_timestamp", "<u4"), ("sample_rate", "<u4"), ("sample_start", "<u8"), ("samples_total", "<u8"),
+    ("bit_rate", "<u4"), ("audio_offset", "<u4"), ("audio_bytes", "<u4"), ("order", "<u4"), ("dst_offset", "<u8"), ("codec", "u1", (32,))], align=False)
+OHM_RX_STREAM_RESULT = np.dtype(_OHM_RX_STATE + [("out_bytes", "<u8"), ("n_output", "<u4"), ("n_pending", "<u4"), ("stop_reason", "<u4"),
+                                                 ("n_resend", "<u4"), ("resend", "<u4", (20,))], align=False)
+assert OHM_RX_DATAGRAM.itemsize == 16 and OHM_RX_STREAM.itemsize == 64 and OHM_RX_RECORD.itemsize == 104 and OHM_RX_STREAM_RESULT.itemsize == 136
 
 # every symbol of include/ohgpu.h: name -> (restype, argtypes)
 _vp, _vpp = C.c_void_p, C.POINTER(C.c_void_p)
@@ -197,6 +217,12 @@ SYMBOLS = {
     "ohgpu_raop_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t]),
     "ohgpu_raop_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
     "ohgpu_raop_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
+    "ohgpu_ohm_rx_batch_check": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, C.c_uint64, C.c_uint64]),
+    "ohgpu_ohm_rx_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
+    "ohgpu_ohm_rx_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "ohgpu_ohm_rx_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t]),
+    "ohgpu_ohm_rx_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
+    "ohgpu_ohm_rx_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
     "ohgpu_flywheel_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
     "ohgpu_flywheel_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "ohgpu_flywheel_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64]),
@@ -432,6 +458,22 @@ def raop_fmtp_parse(fmtp):
     cfg = np.zeros(1, dtype=ALAC_CONFIG)
     check(lib().ohgpu_raop_fmtp_parse(raw, len(raw), cfg.ctypes.data_as(C.c_void_p)))
     return cfg[0]
+
+
+def _ohm_rx_tables(streams, datagrams):
+    s, g = np.ascontiguousarray(streams), np.ascontiguousarray(datagrams)
+    assert s.dtype == OHM_RX_STREAM and g.dtype == OHM_RX_DATAGRAM
+    return s, g
+
+
+def _ptr_or_none(a):
+    return a.ctypes.data_as(C.c_void_p) if a.size else None
+
+
+def ohm_rx_batch_check(streams, datagrams, src_arena_bytes, dst_arena_bytes):
+    """The validation of ctx.ohm_rx_batch without a device (ohgpu_ohm_rx_batch_check): OhGpuError on a bad table."""
+    s, g = _ohm_rx_tables(streams, datagrams)
+    check(lib().ohgpu_ohm_rx_batch_check(_ptr_or_none(s), s.size, _ptr_or_none(g), g.size, src_arena_bytes, dst_arena_bytes))
 
 
 def _raop_tables(descs, packets):
@@ -794,6 +836,36 @@ class Context:
 
     def ohm_run(self, batch, d_src, d_dst, stream=None):
         check(lib().ohgpu_ohm_batch_run(self._h, batch, d_src, d_dst, stream))
+
+    def ohm_rx_batch(self, streams, datagrams, src_arena_bytes, dst_arena_bytes):
+        s, g = _ohm_rx_tables(streams, datagrams)
+        b = C.c_void_p()
+        check(lib().ohgpu_ohm_rx_batch_create(self._h, _ptr_or_none(s), s.size, _ptr_or_none(g), g.size, src_arena_bytes, dst_arena_bytes, C.byref(b)))
+        return b
+
+    def ohm_rx_run(self, batch, d_src, d_dst, stream=None):
+        """Parse, sequence, gather (ohgpu_ohm_rx_batch_run): queued on the stream; d_src 4-byte aligned."""
+        check(lib().ohgpu_ohm_rx_batch_run(self._h, batch, d_src, d_dst, stream))
+
+    def ohm_rx_results(self, batch, n, n_datagrams):
+        """The last run's (OHM_RX_STREAM_RESULT per stream, OHM_RX_RECORD per datagram); waits for the run."""
+        sres, recs = np.zeros(n, dtype=OHM_RX_STREAM_RESULT), np.zeros(n_datagrams, dtype=OHM_RX_RECORD)
+        check(lib().ohgpu_ohm_rx_batch_results(self._h, batch, _ptr_or_none(sres), n, _ptr_or_none(recs), n_datagrams))
+        return sres, recs
+
+    def ohm_rx_phase_ms(self, batch):
+        """The last run's (parse, sequence, gather) in milliseconds, from device events."""
+        ms = (C.c_float * 3)()
+        check(lib().ohgpu_ohm_rx_batch_phase_ms(self._h, batch, ms))
+        return tuple(float(v) for v in ms)
+
+    def ohm_rx_process_host(self, streams, datagrams, src, dst):
+        """Host buffers in and out (ohgpu_ohm_rx_process_host); returns (stream results, records)."""
+        s, g = _ohm_rx_tables(streams, datagrams)
+        sres, recs = np.zeros(s.size, dtype=OHM_RX_STREAM_RESULT), np.zeros(g.size, dtype=OHM_RX_RECORD)
+        check(lib().ohgpu_ohm_rx_process_host(self._h, _ptr_or_none(s), s.size, _ptr_or_none(g), g.size, _ptr_or_none(src), src.nbytes,
+                                              _ptr_or_none(dst), dst.nbytes, _ptr_or_none(sres), _ptr_or_none(recs)))
+        return sres, recs
 
     def src_create(self, L, M, T, coef_q28):
         c = np.ascontiguousarray(coef_q28, dtype=np.int32)

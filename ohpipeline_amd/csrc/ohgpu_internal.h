@@ -19,6 +19,7 @@
 #include "../../include/ohgpu.h"
 #include "alac_packet_core.h"
 #include "flac_frame_core.h"
+#include "ohm_rx_core.h"
 #include "raop_aes_core.h"
 
 namespace ohgpu {
@@ -411,7 +412,23 @@ struct DsdPcmPlan {
 };
 static_assert(sizeof(ohgpu_dsd_pcm_msg_desc) == 64, "ohgpu_dsd_pcm_msg_desc layout");
 
-enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11 };
+// ---- Songcast receiver (csrc/ohm_rx_kernel.hip): the tables, the records and results of the last run, the
+// sequencer's rings.  The batch's d_descs holds nothing.
+struct OhmRxState {
+    size_t n_streams = 0, n_datagrams = 0;
+    void* d_streams = nullptr;                        // ohmrx::Stream[n_streams]
+    void* d_datagrams = nullptr;                      // ohmrx::Datagram[n_datagrams]
+    void* d_records = nullptr;                        // ohmrx::Record[n_datagrams]
+    void* d_results = nullptr;                        // ohmrx::StreamResult[n_streams]
+    void* d_rings = nullptr;                          // uint32[n_streams][ohmrx::kRing]
+    hipEvent_t ev[4] = {};
+    hipStream_t last_stream = nullptr;
+    bool ran = false;
+};
+static_assert(sizeof(ohgpu_ohm_rx_datagram) == sizeof(ohmrx::Datagram) && sizeof(ohgpu_ohm_rx_state) == sizeof(ohmrx::State) && sizeof(ohgpu_ohm_rx_stream) == sizeof(ohmrx::Stream) &&
+              sizeof(ohgpu_ohm_rx_record) == sizeof(ohmrx::Record) && sizeof(ohgpu_ohm_rx_stream_result) == sizeof(ohmrx::StreamResult), "Songcast receiver layouts");
+
+enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11, kBatchOhmRx = 12 };
 
 }  // namespace ohgpu
 
@@ -518,6 +535,7 @@ struct ohgpu_batch {
     ohgpu::FlacState* flac = nullptr;   // kBatchFlac only (what a run changes lives behind the pointer: a run takes a const batch)
     ohgpu::AlacState* alac = nullptr;   // kBatchAlac and kBatchRaop (likewise)
     ohgpu::RaopState* raop = nullptr;   // kBatchRaop only
+    ohgpu::OhmRxState* ohmrx = nullptr; // kBatchOhmRx only
     void*    d_pull_tiles = nullptr;   // kBatchSrcPull: PullTile[n_pull_tiles] on the device (d_descs holds the messages)
     uint32_t n_pull_tiles = 0;
     // kBatchSrc whose messages differ in layout: one uniform batch per layout (each with its own block-kernel plan), run one
@@ -552,7 +570,7 @@ inline int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? OHGPU_ERR_
         if (e_ != hipSuccess) return ::ohgpu::set_error(::ohgpu::hip_code(e_), "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-// The release functions (free_pcm_line, free_fmt_line, free_dsd_line, flac_free, alac_free, raop_free, free_flywheel, free_src_fast, free_ohm): what
+// The release functions (free_pcm_line, free_fmt_line, free_dsd_line, flac_free, alac_free, raop_free, free_flywheel, free_src_fast, free_ohm, ohm_rx_free): what
 // ohgpu_batch_destroy's table calls (csrc/ohgpu_api.hip).  Each takes a PARTLY BUILT batch -- null pointers, a plan that was never
 // made -- and leaves the plan reset: a create that fails at any point hands its batch to ohgpu_batch_destroy and returns.
 // kernels
@@ -595,6 +613,11 @@ const raopcore::Tables& raop_tables();                                // the hos
 int  raop_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const raopcore::Job* jobs, size_t n_jobs);   // pieces, keys and scratch onto the device (b->raop is filled)
 void raop_free(ohgpu_ctx* ctx, ohgpu_batch* b);                       // clears the keys, then alac_free
 int  raop_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);   // the decrypt phase alone
+// csrc/ohm_rx_kernel.hip
+int  ohm_rx_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const ohmrx::Stream* streams, const ohmrx::Datagram* datagrams);   // tables and result arrays onto the device (b->ohmrx holds the counts)
+void ohm_rx_free(ohgpu_ctx* ctx, ohgpu_batch* b);
+int  ohm_rx_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
+uint32_t ohm_rx_gather_blocks(uint32_t n_datagrams, uint32_t cus);   // the gather launch's size: the rule tests/test_gpu_ohm_rx_many_trips.py restates
 // csrc/ohm_frame_kernel.hip: the two wire channels of streams wider than stereo (Sender::DoProcessFragment), one record per fragment
 OhmSelRec wide_record(uint64_t src_off, uint64_t dst_off, uint32_t n_frames, uint32_t channels, uint32_t sb, bool little, uint64_t src_arena_bytes);
 hipError_t launch_ohm_wide(const ohgpu_ctx* ctx, const void* d_recs, uint32_t n_recs, const uint8_t* src, uint8_t* dst, const uint8_t* prefix, hipStream_t s);

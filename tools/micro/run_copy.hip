@@ -6,6 +6,8 @@
 // contiguous stretch per workgroup.  Beside it the yardstick of MI355X_MICROARCH.md: a float4 grid-stride copy of the same bytes.
 //
 //   hipcc --offload-arch=gfx950 -O3 -o run_copy run_copy.hip && ./run_copy
+//   ./run_copy REPS BYTES    the yardstick alone for another workload's bytes: the float4 copy of BYTES bytes each way (a multiple of
+//                            16), every variant, and a last line "best <TB/s>" (tools/bench_ohm_rx.py --run-copy reads it)
 //
 // Every load of a pass is issued from ONE asm statement together with the wait for the pass that is DEPTH older and that pass's
 // stores: vmcnt counts loads and stores in issue order, so "all but the 8 (DEPTH - 1) youngest" is exactly "pass p has landed".
@@ -198,7 +200,8 @@ struct Timer {
 int main(int argc, char** argv)
 {
     const uint32_t streams = 256, blocks_per_stream = 3000, n_passes = streams * blocks_per_stream / 16;     // 48 000 passes
-    const size_t copy_pieces = (size_t)((double)streams * (441000.0 + 480000.0) * 6.0 / 2) / 16;            // the float4 copy moves this many pieces each way
+    const size_t other_bytes = argc > 2 ? (size_t)atoll(argv[2]) : 0;                                        // the yardstick alone, for these bytes each way
+    const size_t copy_pieces = other_bytes ? other_bytes / 16 : (size_t)((double)streams * (441000.0 + 480000.0) * 6.0 / 2) / 16;            // the float4 copy moves this many pieces each way
     // every kernel below stays inside [0, arena): pass p reads [p * kInStride, + 900 pieces) and writes [p * kOutStride, + 960 pieces), p < n_passes;
     // the float4 copy reads and writes [0, copy_pieces * 16)
     const size_t arena = std::max({(size_t)(n_passes - 1) * kInStride + 900 * 16, (size_t)(n_passes - 1) * kOutStride + 960 * 16, copy_pieces * 16}) + 65536;
@@ -218,6 +221,7 @@ int main(int argc, char** argv)
     const int reps = argc > 1 ? atoi(argv[1]) : 40;
     printf("# run_copy: %u passes, %.4f GB in + %.4f GB out per launch; TB/s quoted on the resampler's algorithmic %.4f GB\n", n_passes,
            (double)n_passes * kInPieces * 16 / 1e9, (double)n_passes * kOutPieces * 16 / 1e9, algo / 1e9);
+    double best = 0.0;
     // ---- yardstick
     for (int nt = 0; nt < 2; nt++)
         for (int four = 0; four < 2; four++)
@@ -230,7 +234,9 @@ int main(int argc, char** argv)
                 }, reps);
                 printf("float4 copy%s%s  %2u wg/CU                     %.4f ms  %.3f TB/s\n", four ? " x4" : "   ", nt ? " nt" : "   ", per_cu, ms, 2.0 * n * 16 / ms / 1e9);
                 fflush(stdout);
+                best = std::max(best, 2.0 * n * 16 / ms / 1e9);
             }
+    if (other_bytes) { printf("best %.3f\n", best); return 0; }
     // ---- the workgroup kernel's launch shape
     auto sweep = [&](const char* name, auto kernel, int depth, bool ntl, bool nts, size_t lds) {
         int occ = 0;
