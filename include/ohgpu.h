@@ -837,6 +837,8 @@ int ohgpu_ohm_rx_process_host(ohgpu_ctx* ctx, const ohgpu_ohm_rx_stream* streams
 
 /* ---- sample-rate converter (own specification; DESIGN.md "Resampler") ---- */
 /* Host-side filter design: Kaiser-windowed sinc, Q28 coefficients, coef_q28[p*T + k] = h[p + k*L].
+ * Stop edge f_stop = rate_out - f_pass, or rate_in - f_pass from 2x upsampling on (rate_out >= 2 * rate_in: the pass band's images,
+ * not the output's alias, set it -- at exactly 2x the output's rule would put the cutoff at the input rate); cutoff midway; DESIGN.md 4.
  * Pass coef_q28 = NULL to query L, M only.  Capacity must be >= L*T. */
 int ohgpu_src_design(uint32_t rate_in, uint32_t rate_out, uint32_t taps_per_phase, double beta, double f_pass_hz,
                      int32_t* coef_q28, size_t coef_capacity, uint32_t* L, uint32_t* M);

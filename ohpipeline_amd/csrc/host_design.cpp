@@ -68,7 +68,8 @@ int design_src(uint32_t rate_in, uint32_t rate_out, uint32_t T, double beta, dou
     if (coef_q28 == nullptr) return OHGPU_OK;
     const uint32_t N = (L == 1 && T > 1) ? T - 1 : L * T;
     double f_stop = (double)rate_out - f_pass;
-    if (f_stop > (double)rate_in - f_pass && rate_out > 2 * rate_in) f_stop = (double)rate_in - f_pass;
+    // (from 2x on, as design_src_pull: at exactly 2x the output's rule would put the cutoff at the input rate)
+    if (f_stop > (double)rate_in - f_pass && rate_out >= 2 * rate_in) f_stop = (double)rate_in - f_pass;
     const double fs_up = (double)L * (double)rate_in;
     const double fc = 0.5 * (f_pass + f_stop);
     const double wc = 2.0 * fc / fs_up;

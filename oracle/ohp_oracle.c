@@ -720,7 +720,8 @@ int ohp_src_design(ohp_src* s, uint32_t rate_in, uint32_t rate_out, uint32_t T, 
     s->L = L; s->M = M; s->T = T; s->beta = beta; s->rate_in = rate_in; s->rate_out = rate_out;
     s->f_pass = f_pass;
     s->f_stop = (double)rate_out - f_pass;
-    if (s->f_stop > (double)rate_in - f_pass && rate_out > 2 * rate_in) s->f_stop = (double)rate_in - f_pass;
+    /* from 2x up-sampling on: at exactly 2x the output's rule would put the cutoff at the input rate */
+    if (s->f_stop > (double)rate_in - f_pass && rate_out >= 2 * rate_in) s->f_stop = (double)rate_in - f_pass;
     const double fs_up = (double)L * (double)rate_in;
     const double fc = 0.5 * (s->f_pass + s->f_stop);
     const double wc = 2.0 * fc / fs_up;                 /* cutoff as a fraction of the upsampled Nyquist */

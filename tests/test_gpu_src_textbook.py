@@ -2,7 +2,8 @@
 indexing the kernels share.  A matrix of cells, each first asserting the kernel its batch runs on (ctx.src_kernel_name), then
 comparing the GPU's bytes with the model's for four input classes: impulses (the expected outputs read straight from the table),
 rounding ties, rails, seeded noise in ragged unsorted messages; and, where the cell's filter is in tests/golden/src_textbook.json,
-the fixture's two inputs against its hashes.  Then the same batch for three periods on every plan kind (run,
+the fixture's two inputs against its hashes (check_cell is the cell's body; tests/test_gpu_src_ratios.py runs it over the rate ratios,
+with tables steered to the block kernel a cell is meant for).  Then the same batch for three periods on every plan kind (run,
 ohgpu_src_batch_advance, ohgpu_src_batch_set_ramps, a refused set_ramps), the filters' audio in the frequency domain (no model),
 and the pulled path at phase-aligned steps against the same operation."""
 import hashlib
@@ -48,7 +49,7 @@ def layout_id(lay):
 
 
 def cell_id(c):
-    kernel, variant, (rin, rout, T), lay = c
+    kernel, variant, (rin, rout, T, *_), lay = c
     return f"{kernel[4:].replace('_kernel', '')}-v{variant}-{rin // 100}to{rout // 100}x{T}-{layout_id(lay)}"
 
 
@@ -64,10 +65,39 @@ def ramp_table():
     return capi.ramp_table()
 
 
+def phase_sum(coef, L, T):
+    """The largest per-phase sum |c| (ohgpu_src::max_sum_abs): which block kernel a filter gets."""
+    return int(np.abs(np.asarray(coef, dtype=np.int64).reshape(L, T)).sum(axis=1).max())
+
+
+LEAN_SUMS, ROUND1_SUMS = (0, 1 << 29), (1 << 29, 1 << 30)       # [lo, hi): the lean kernel's rounding bias; round 1's kernel, the fallback
+
+
+def steered(coef, L, T, sums):
+    """The table as it is if its sum |c| lies in `sums`, else times k/4 (floored), k from the table's own sum: 3/4 or 1/2 to go
+    down, the smallest k/4 above 1 to go up.  A scaled filter is still a filter, and the model takes the same table."""
+    lo, hi = sums
+    if lo <= phase_sum(coef, L, T) < hi:
+        return coef
+    for k in ((3, 2) if phase_sum(coef, L, T) >= hi else range(5, 9)):
+        scaled = ((coef.astype(np.int64) * k) // 4).astype(np.int32)
+        if lo <= phase_sum(scaled, L, T) < hi:
+            return scaled
+    raise AssertionError(f"no k/4 takes sum |c| = {phase_sum(coef, L, T)} into [{lo}, {hi})")
+
+
 class Filter:
-    def __init__(self, ctx, rin, rout, T):
+    """capi.src_design's table at Kaiser(9) and pass edge f_pass -- `sums` given: steered into that bracket of sum |c|."""
+
+    def __init__(self, ctx, rin, rout, T, f_pass=20000.0, sums=None):
         self.rin, self.rout, self.T = rin, rout, T
-        self.L, self.M, self.coef = capi.src_design(rin, rout, T, 9.0, 20000.0)
+        self.L, self.M, self.coef = capi.src_design(rin, rout, T, 9.0, f_pass)
+        if sums is not None:
+            self.coef = steered(self.coef, self.L, T, sums)
+            assert sums[0] <= phase_sum(self.coef, self.L, T) < sums[1]
+        # a half-band 2:1 decimator, from the table's zeros as ohgpu_src_create finds it (csrc/api_src.hip, src_describe)
+        self.halfband = (self.L, self.M, T) == (1, 2, 64) and self.coef[T - 1] == 0 and \
+            not any(self.coef[k] for k in range(1, T, 2) if k != T // 2 - 1)
         self.handle = ctx.src_create(self.L, self.M, T, self.coef)
 
 
@@ -195,22 +225,25 @@ def one_stream(flt, lay, y, rng, msg=240, ramp_every=4):
     return b, n_out
 
 
-@pytest.mark.parametrize("cell", CELLS, ids=[cell_id(c) for c in CELLS])
-def test_every_plan_kind_equals_the_model(ctx, filters, ramp_table, cell):
-    kernel, variant, f, lay = cell
-    flt = filters(f)
+def check_cell(ctx, flt, ramp_table, kernel, variant, lay, name):
+    """One cell of a matrix: the batch runs on `kernel` under `variant`, and its bytes equal the model's for the four input classes.
+    Sizes: four blocks of input (3000 frames at least) -- whole blocks, a block edge inside a message, a generic head and tail."""
     ch, sb, se, db, de, planar = lay
     L_blk, M_blk = block_of(ctx, flt, lay, variant)
-    rng = np.random.default_rng(zlib.crc32(cell_id(cell).encode()))
+    rng = np.random.default_rng(zlib.crc32(name.encode()))
     lo, hi = full_scale(sb)
     msg = 220 if flt.rout == 44100 else 240
-    n_in = max(4 * M_blk, 3000)
     block_plan = kernel != V1
+    while not block_plan and M_blk < flt.T + 4 * ch:      # (block_of's stand-in for a plan without blocks: any whole periods will do, wide
+        L_blk, M_blk = 2 * L_blk, 2 * M_blk               # enough that no output sees two of the impulses below)
+    n_in = max(4 * M_blk, 3000)
 
     # (a) impulses: input frame 0, the first and the last input frame of block 1, the newest frame of a message's first output;
     # channel c 2c frames further in (the last frame of the block: 2c frames back), signs alternating
+    # (a block shorter than a window and the channels' offsets: the last frame of block 2 instead, so that no output sees two impulses)
     first_msg = next(m for m in range(0, 1 << 30, msg) if (m * flt.M) // flt.L >= 2 * M_blk + 3 * flt.T)
-    sites = [(0, 1), (M_blk, 1), (2 * M_blk - 1, -1), ((first_msg * flt.M) // flt.L, 1)]
+    last_of = 2 if M_blk - 1 - 4 * (ch - 1) >= flt.T else 3
+    sites = [(0, 1), (M_blk, 1), (last_of * M_blk - 1, -1), ((first_msg * flt.M) // flt.L, 1)]
     y = np.zeros((n_in, ch), dtype=np.int64)
     for i, (n, way) in enumerate(sites):
         for c in range(ch):
@@ -236,7 +269,8 @@ def test_every_plan_kind_equals_the_model(ctx, filters, ramp_table, cell):
     y = rng.integers(lo, hi + 1, size=(n_in, ch))
     ties = TB.plant_ties(rng, flt.coef, flt.L, flt.M, flt.T, y, sb)
     sums = np.array([acc for acc, offset in ties.values() if offset == 0], dtype=object)
-    assert len(ties) > 20 and (sums < 0).any() and (sums > 0).any()
+    # (a table without an odd coefficient has no tie to plant: the identity, 48 -> 48 kHz -- one coefficient of 2^28 -- sums to multiples of 2^28)
+    assert (len(ties) > 20 and (sums < 0).any() and (sums > 0).any()) or not (flt.coef & 1).any()
     b, _ = one_stream(flt, lay, y, rng, msg)
     descs, src = b.descs(), b.arena()
     got, _ = run(ctx, flt, variant, kernel, descs, src, b.dst)
@@ -247,10 +281,27 @@ def test_every_plan_kind_equals_the_model(ctx, filters, ramp_table, cell):
     third = n_in // 3
     y[:third], y[third:2 * third] = np.where(np.arange(ch) % 2 == 0, hi, lo), np.where(np.arange(ch) % 2 == 0, lo, hi)
     y[2 * third:] = np.where((np.arange(n_in - 2 * third) // 24) % 2 == 0, hi, lo)[:, None]
+    if int(flt.coef.astype(np.int64).sum()) < (flt.L << 28) * 7 // 8:
+        # (a table steered down passes DC and the square wave below full scale: in the last third, windows apart, the frames of an
+        # output's window at the rails by the signs of their coefficients -- sum |c| times full scale, past the clamp, either way)
+        h = TB.prototype(flt.coef, flt.L, flt.T)
+        m = -(-(2 * third + flt.T) * flt.L // flt.M)
+        for i in range(1 << 30):
+            t = m * flt.M
+            n_lo, n_hi = TB.frames_read(h.size, flt.L, [t])
+            if n_hi >= n_in:
+                break
+            n = np.arange(n_lo, n_hi + 1)
+            for c in range(ch):
+                y[n, c] = np.where(h[t - n * flt.L] * (1 if (i + c) % 2 == 0 else -1) >= 0, hi, lo)
+            m += TB.tie_gap(flt.L, flt.M, flt.T)
     b, n_out = one_stream(flt, lay, y, rng, msg)
     descs, src = b.descs(), b.arena()
-    s24 = TB.resample(flt.coef, flt.L, flt.M, flt.T, y << TB.source_shift(sb), 0, 0, n_out)
-    assert (s24 == TB.S24_MAX).sum() > 10 and (s24 == TB.S24_MIN).sum() > 10
+    s24 = np.concatenate([TB.resample(flt.coef, flt.L, flt.M, flt.T, y << TB.source_shift(sb), 0, m, min(msg, n_out - m))
+                          for m in range(0, n_out, msg)])             # (a message at a time: the model's matrix is outputs x frames)
+    # (the rails: the clamp's -- or, below them, what sum |c| lets a full-scale source reach: an identity filter, 48 -> 48 kHz, from S16)
+    reach = [int(np.clip((phase_sum(flt.coef, flt.L, flt.T) * (v << TB.source_shift(sb)) + (1 << 27)) >> 28, TB.S24_MIN, TB.S24_MAX)) for v in (lo, hi)]
+    assert (s24 == reach[1]).sum() > 10 and (s24 == reach[0]).sum() > 10
     got, _ = run(ctx, flt, variant, kernel, descs, src, b.dst)
     assert_same(got, model(flt, descs, src, b.dst, ramp_table), "rails")
 
@@ -273,6 +324,16 @@ def test_every_plan_kind_equals_the_model(ctx, filters, ramp_table, cell):
     got, plan = run(ctx, flt, variant, kernel, descs, src, b.dst)
     assert_same(got, model(flt, descs, src, b.dst, ramp_table), "ragged noise")
     assert not block_plan or (plan["block_kernel_out_frames"] > 0 and plan["generic_pieces"] > 0), plan
+
+
+@pytest.mark.parametrize("cell", CELLS, ids=[cell_id(c) for c in CELLS])
+def test_every_plan_kind_equals_the_model(ctx, filters, ramp_table, cell):
+    kernel, variant, f, lay = cell
+    flt = filters(f)
+    ch, sb, se, db, de, planar = lay
+    check_cell(ctx, flt, ramp_table, kernel, variant, lay, cell_id(cell))
+    rng = np.random.default_rng(zlib.crc32(cell_id(cell).encode()) + 1)
+    msg = 220 if flt.rout == 44100 else 240
 
     # the golden fixture's inputs, where the cell's filter is there and its layout carries S24 in and out
     fx = {(e["rate_in"], e["rate_out"], e["T"]): e for e in json.load(open(FIXTURE))["filters"]}
@@ -322,8 +383,13 @@ def test_planar_planes_with_bits_above_the_depth(ctx, filters, ramp_table, kerne
 
 
 # ------------------------------------------------------------------------------------------ the same batch, three periods
+# (the last three: a block whose input is shorter than its output, on either block kernel -- 24 -> 48 kHz, the table as designed and
+# steered up; and one four times as long -- 192 -> 48 kHz, the plain 64-tap lean kernel)
 REUSE = {"wg": (WG, 0, F44, [S24]), "lean": (LEAN, 4, F44, [S24]), "round1": (BLOCK, 0, F48, [S24]),
-         "two-layouts": (WG, 0, F44, [S24, (6, 24, LE, 24, BE, False)]), "generic": (V1, 0, F44, [(2, 24, LE, 8, BE, False)])}
+         "two-layouts": (WG, 0, F44, [S24, (6, 24, LE, 24, BE, False)]), "generic": (V1, 0, F44, [(2, 24, LE, 8, BE, False)]),
+         "lean-24to48": (LEAN, 0, (24000, 48000, 32, 10000.0, LEAN_SUMS), [S24]),
+         "round1-24to48": (BLOCK, 0, (24000, 48000, 32, 10000.0, ROUND1_SUMS), [S24]),
+         "lean-192to48": (LEAN, 0, (192000, 48000, 64, 15300.0, None), [S24])}
 
 
 @pytest.mark.parametrize("kind", list(REUSE))

@@ -48,6 +48,28 @@ def test_pass_band_is_flat_and_the_stop_band_is_85_db_down(rate_in, taps, edge_d
     assert ref.sum_abs_max < (1 << 29)                                   # the lean kernel's rounding bias; < 2^30 keeps fp64 exact
 
 
+@pytest.mark.parametrize("rate_in,taps,f_pass", [(24000, 32, 10000.0), (48000, 32, 20000.0), (22050, 32, 9000.0), (24000, 64, 10900.0)])
+def test_exactly_two_times_up_rejects_the_pass_bands_first_image(rate_in, taps, f_pass):
+    """rate_out = 2 rate_in: the stop edge is rate_in - f_pass (the rule "from 2x on", as the pulled design's), not rate_out - f_pass,
+    which would put the cutoff AT the input rate and let the images of the pass band -- rate_in - f_pass up to the up-sampled
+    Nyquist -- through at 0 dB.  Every frequency from there on at least 60 dB below the DC gain (the figure the 64-tap decimators'
+    edge is held to above; these four measure -64.1, -64.1, -90.6 and -90.9 dB), the pass band flat within 0.01 dB, DC gain L, the
+    exact-accumulation bound.  (44.1 -> 88.2 kHz with a 20 kHz pass edge leaves 4.1 kHz between the edges, too little for 32
+    taps: DESIGN.md 4 says so, nothing here asserts it.)"""
+    ref = O.Src(rate_in, 2 * rate_in, taps, BETA, f_pass)
+    assert (ref.L, ref.M) == (2, 1)
+    h = prototype(ref)
+    fs_up = ref.L * rate_in
+    gain = 20 * np.log10(ref.L)
+    passband = response_db(h, fs_up, np.linspace(0, f_pass, 81)) - gain
+    assert np.max(np.abs(passband)) < 0.01, passband
+    images = response_db(h, fs_up, np.linspace(rate_in - f_pass, fs_up / 2, 2000)) - gain
+    assert np.max(images) <= -60.0, np.max(images)
+    assert ref.f_stop == rate_in - f_pass
+    assert abs(np.sum(h) - ref.L) < 1e-6 * ref.L
+    assert ref.sum_abs_max < (1 << 30)                                   # fp64 accumulation stays exact
+
+
 def test_the_two_to_one_decimator_is_odd_length_and_half_band():
     ref = O.Src(96000, 48000, 64, BETA, F_PASS)
     c = ref.coef_q28
