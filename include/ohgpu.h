@@ -33,6 +33,8 @@
  *       (Av/Raop/ProtocolRaop.cpp:1477-1502, Av/Raop/CodecRaopApple.cpp:61-214)          -> the same, or the plaintext alone
  *   OhmHeader::Internalise + OhmMsgAudio::Create(IReader&) + ProtocolOhBase's frame sequencer   ohgpu_ohm_rx_batch_run()
  *       (Av/Songcast/Ohm.cpp:22-42, OhmMsg.cpp:101-175, ProtocolOhBase.cpp:254-553)            -> CodecPcm's big-endian bytes
+ *   CodecFlac's Ogg FLAC streams: libogg's page reader and libFLAC's Ogg aspect in front of the frames   ohgpu_ogg_batch_run()
+ *       (Codec/Flac.cpp:155-213; thirdparty/libogg and flac-1.2.1's Ogg aspect by their behaviour)        -> the run ohgpu_flac_* reads
  *   "SampleRateConverter" -- NOT PRESENT in the reference  ohgpu_src_* (own spec)
  *
  * The reference binds nothing through FFI today (it is one C++ static library); INTEGRATION.md
@@ -834,6 +836,126 @@ int ohgpu_ohm_rx_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float 
 int ohgpu_ohm_rx_process_host(ohgpu_ctx* ctx, const ohgpu_ohm_rx_stream* streams, size_t n, const ohgpu_ohm_rx_datagram* datagrams, size_t n_datagrams,
                               const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes,
                               ohgpu_ohm_rx_stream_result* stream_results, ohgpu_ohm_rx_record* records);
+
+/* ---- Ogg pages: find, checksum, join into packets, gather (the text is csrc/ogg_page_core.h) ----
+ * What libogg's page reader and libFLAC's Ogg aspect do in front of the FLAC frame decoder (RFC 3533): the bytes of an Ogg stream
+ * in, the bytes of its completed packets out, concatenated from dst_offset on at any byte alignment -- for an Ogg FLAC stream the
+ * run ohgpu_flac_* reads -- with a record per packet and a result per stream.  Four launches on one stream: find (a lane per byte
+ * position), verify (a wave per page: its CRC-32 in 64 slices, joined with the x^(8 len) multiplication), chain (a lane per stream:
+ * the walk below), gather (a wave per piece of page body).  No host synchronisation.
+ * The walk, from src_offset, at position p:
+ *   1. fewer than 27 bytes, than the header (27 + segments) or than the whole page are left: the range ends here, status OK.
+ *   2. 27 bytes or more without "OggS" at p, or a whole page whose CRC does not match: LOST_SYNC, stop.  Nothing is skipped.
+ *   3. a whole page with a good CRC whose serial is not the stream's or whose version is not 0 is counted (pages_ignored) and passed
+ *      over.  With OHGPU_OGG_ANY_SERIAL the stream's serial is that of the first whole page.
+ *   4. an accepted page's number must be expect_seq, then one more each page (mod 2^32): HOLE otherwise, stop in front of that
+ *      page.  With OHGPU_OGG_ANY_SEQ the first accepted page may carry any number.
+ *   5. a packet is a run of lacing values 255 closed by one below 255, over any number of pages.  The "continued" flag matters in
+ *      one place: on a page that sets it while no packet is open, the leading segments up to and including the first below 255 are
+ *      dropped with their bytes (all of them, when all are 255).  On the first accepted page first_page_segment = r > 0 skips
+ *      segments [0, r) and their bytes instead, and the packet at r is a fresh one; r above that page's segment count is BAD_RESUME.
+ *   6. only completed packets are delivered.  With OHGPU_OGG_FLAC_MAPPING a completed packet whose first byte is 0x7f is the
+ *      mapping's first header: shorter than 9 bytes or without "FLAC" at 1 is NOT_FLAC, a major version (byte 5) other than 1 is
+ *      UNSUPPORTED_MAPPING, both stop; otherwise its first 9 bytes are not delivered.  Every packet is tested.
+ *   7. a packet still open where the range ends is not delivered: bytes_consumed is then the offset of the page it began on,
+ *      resume_segment its first segment there and next_seq that page's number.  With no packet open bytes_consumed is the end of the
+ *      last whole page, resume_segment 0 and next_seq the last accepted number plus 1.  On a stop status bytes_consumed is the
+ *      offset of the page the walk stopped at (for the mapping's two, the page the header packet ended on), and what completed
+ *      before it is delivered.  A later call with (src_offset + bytes_consumed, expect_seq = next_seq, first_page_segment =
+ *      resume_segment) delivers exactly what one call over the whole range would have delivered behind that point. */
+#define OHGPU_OGG_OK                   0u
+#define OHGPU_OGG_LOST_SYNC            1u
+#define OHGPU_OGG_HOLE                 2u
+#define OHGPU_OGG_NOT_FLAC             3u
+#define OHGPU_OGG_UNSUPPORTED_MAPPING  4u
+#define OHGPU_OGG_BAD_RESUME           5u
+#define OHGPU_OGG_ANY_SEQ        1u
+#define OHGPU_OGG_FLAC_MAPPING   2u
+#define OHGPU_OGG_ANY_SERIAL     4u
+#define OHGPU_OGG_PACKET_BOS             1u   /* it starts with the first segment of a page that has the "first page" flag */
+#define OHGPU_OGG_PACKET_EOS             2u   /* it contains the last segment of a page that has the "last page" flag */
+#define OHGPU_OGG_PACKET_MAPPING_HEADER  4u   /* the mapping's first header: `bytes` is what is left of it without its first 9 */
+
+typedef struct ohgpu_ogg_stream_desc {   /* 64 bytes */
+    uint64_t src_offset;            /* the stream's bytes are [src_offset, + src_bytes) of the source arena, any address */
+    uint64_t dst_offset;            /* the delivered run starts here, any address */
+    uint64_t dst_capacity;          /* >= src_bytes: delivery can never run out of room */
+    uint32_t src_bytes;             /* < 2^31 */
+    uint32_t serial;                /* the logical stream's (ignored with OHGPU_OGG_ANY_SERIAL) */
+    uint32_t expect_seq;            /* the number the first accepted page must carry (ignored with OHGPU_OGG_ANY_SEQ) */
+    uint32_t packet_first;          /* the stream's records are [packet_first, + packet_capacity) of the batch's packet table; */
+    uint32_t packet_capacity;       /*   packets beyond the capacity are counted, not recorded.  0: no records */
+    uint32_t first_page_segment;    /* rule 5's r, <= 255 */
+    uint32_t flags;                 /* OHGPU_OGG_ANY_SEQ | _FLAC_MAPPING | _ANY_SERIAL */
+    uint32_t reserved[3];
+} ohgpu_ogg_stream_desc;
+
+typedef struct ohgpu_ogg_stream_result {   /* 64 bytes */
+    uint32_t status;                /* OHGPU_OGG_OK ... _BAD_RESUME */
+    uint32_t pages;                 /* accepted */
+    uint32_t pages_ignored;         /* rule 3 */
+    uint32_t packets;               /* completed and delivered, recorded or not */
+    uint64_t bytes_delivered;       /* the run [dst_offset, + bytes_delivered) was written */
+    uint64_t bytes_consumed;        /* rule 7 */
+    uint32_t resume_segment;
+    uint32_t next_seq;
+    int64_t  last_granule;          /* the last granule position other than -1 that a delivered packet got (-1: none) */
+    uint32_t serial;                /* the stream's: the descriptor's, or the first whole page's */
+    uint8_t  bos_seen, eos_seen;    /* an accepted page had the "first page" / "last page" flag */
+    uint8_t  reserved[2];
+    uint64_t reserved2;
+} ohgpu_ogg_stream_result;
+
+typedef struct ohgpu_ogg_packet {   /* 40 bytes */
+    uint64_t run_pos;               /* its delivered bytes are [dst_offset + run_pos, + bytes) */
+    uint32_t bytes;
+    uint32_t flags;                 /* OHGPU_OGG_PACKET_* */
+    int64_t  granule;               /* the page's, for the last packet that ends on a page; -1 for the others */
+    uint64_t page_offset;           /* where it began: the page (from src_offset), ... */
+    uint32_t page_seq;              /* ... that page's number, ... */
+    uint32_t segment;               /* ... and the segment */
+} ohgpu_ogg_packet;
+
+/* Host only, no device needed: the validation ohgpu_ogg_batch_create makes.  OHGPU_ERR_INVALID: non-zero reserved words, unknown
+ * flags, src_bytes >= 2^31, first_page_segment > 255, packet ranges that overlap or run past the table of n_packets records.
+ * OHGPU_ERR_BOUNDS: a range outside its arena, dst_capacity < src_bytes.  The empty batch is legal. */
+int ohgpu_ogg_batch_check(const ohgpu_ogg_stream_desc* descs, size_t n, size_t n_packets, uint64_t src_arena_bytes, uint64_t dst_arena_bytes);
+/* The descriptors go to the device; lists, bitmap, plan, packet table and results are the batch's.  Freed with ohgpu_batch_destroy. */
+int ohgpu_ogg_batch_create(ohgpu_ctx* ctx, const ohgpu_ogg_stream_desc* descs, size_t n, size_t n_packets, uint64_t src_arena_bytes, uint64_t dst_arena_bytes,
+                           ohgpu_batch** batch);
+/* Find, verify, chain, gather: queued on the stream, nothing waits for the host.  Both bases may be any address.  The batch owns its
+ * lists: it runs on one stream at a time.  A second run allocates nothing on the device (ohgpu_device_allocations).  The delivered
+ * runs are what ohgpu_flac_* reads as its source arena: that batch may be queued on the same stream at once. */
+int ohgpu_ogg_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* src_base, void* dst_base, void* stream);
+/* The last run's results, n = the batch's stream count (waits for that run). */
+int ohgpu_ogg_batch_results(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_ogg_stream_result* results, size_t n);
+/* The last run's packet table, n_packets = the table's length; of a stream's range the first min(packets, packet_capacity) records
+ * are that run's (waits for that run). */
+int ohgpu_ogg_batch_packets(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_ogg_packet* packets, size_t n_packets);
+/* The last run's phases in milliseconds from device events: find, verify, chain, gather (waits for that run). */
+int ohgpu_ogg_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float ms[4]);
+/* Host-buffer convenience: one upload, one run, and of dst_host the bytes [dst_offset, + bytes_delivered) of every stream.  Either
+ * result pointer may be NULL. */
+int ohgpu_ogg_process_host(ohgpu_ctx* ctx, const ohgpu_ogg_stream_desc* descs, size_t n, size_t n_packets, const void* src_host, uint64_t src_bytes,
+                           void* dst_host, uint64_t dst_bytes, ohgpu_ogg_stream_result* results, ohgpu_ogg_packet* packets);
+/* Host only: the page checksum of any bytes (polynomial 0x04c11db7, start 0, no reflection, no final complement). */
+uint32_t ohgpu_ogg_crc(const void* bytes, size_t n);
+/* Host only: the head of an Ogg FLAC stream (CodecFlac::Recognise's second kind: "OggS" at 0, "fLaC" at 37).  Walks the leading
+ * pages of `bytes` (any serial, any first page number, the mapping header applied), reads "fLaC" and the metadata blocks out of the
+ * packets' bytes through ohgpu_flac_streaminfo, and answers where the first audio packet begins: the page's offset, the segment in
+ * it, that page's number -- the (src_offset, first_page_segment, expect_seq) of the stream's first ohgpu_ogg_stream_desc.
+ * OHGPU_ERR_INVALID: not Ogg FLAC, or the bytes end inside the metadata.  OHGPU_ERR_UNSUPPORTED: a metadata block that does not
+ * end with its packet. */
+int ohgpu_ogg_flac_head(const void* bytes, size_t n, ohgpu_flac_streaminfo_t* info, uint32_t* serial, uint64_t* audio_page_offset, uint32_t* audio_segment,
+                        uint32_t* audio_seq);
+/* Ogg FLAC from host buffers: one upload of the Ogg bytes, the demux into a middle arena of mid_bytes that lives on the device only,
+ * one small read of the Ogg results, a FLAC batch over the delivered runs (flac_descs[i].src_offset must be ogg_descs[i].dst_offset,
+ * an offset into the middle arena; its src_bytes is replaced by the stream's bytes_delivered), and of dst_host the samples that
+ * were decoded.  The demuxed bytes never visit the host.  Any result pointer may be NULL; frames as ohgpu_flac_batch_frames. */
+int ohgpu_ogg_flac_process_host(ohgpu_ctx* ctx, const ohgpu_ogg_stream_desc* ogg_descs, const ohgpu_flac_stream_desc* flac_descs, size_t n, size_t n_packets,
+                                const void* src_host, uint64_t src_bytes, uint64_t mid_bytes, void* dst_host, uint64_t dst_bytes,
+                                ohgpu_ogg_stream_result* ogg_results, ohgpu_ogg_packet* packets,
+                                ohgpu_flac_stream_result* flac_results, ohgpu_flac_frame* frames, size_t frames_capacity, size_t* n_frames);
 
 /* ---- sample-rate converter (own specification; DESIGN.md "Resampler") ---- */
 /* Host-side filter design: Kaiser-windowed sinc, Q28 coefficients, coef_q28[p*T + k] = h[p + k*L].

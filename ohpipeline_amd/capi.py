@@ -144,6 +144,19 @@ OHM_RX_RECORD = np.dtype([
 OHM_RX_STREAM_RESULT = np.dtype(_OHM_RX_STATE + [("out_bytes", "<u8"), ("n_output", "<u4"), ("n_pending", "<u4"), ("stop_reason", "<u4"),
                                                  ("n_resend", "<u4"), ("resend", "<u4", (20,))], align=False)
 assert OHM_RX_DATAGRAM.itemsize == 16 and OHM_RX_STREAM.itemsize == 64 and OHM_RX_RECORD.itemsize == 104 and OHM_RX_STREAM_RESULT.itemsize == 136
+# Ogg pages: a descriptor and a result per stream, a record per completed packet
+OGG_OK, OGG_LOST_SYNC, OGG_HOLE, OGG_NOT_FLAC, OGG_UNSUPPORTED_MAPPING, OGG_BAD_RESUME = range(6)
+OGG_ANY_SEQ, OGG_FLAC_MAPPING, OGG_ANY_SERIAL = 1, 2, 4
+OGG_PACKET_BOS, OGG_PACKET_EOS, OGG_PACKET_MAPPING_HEADER = 1, 2, 4
+OGG_STREAM_DESC = np.dtype([("src_offset", "<u8"), ("dst_offset", "<u8"), ("dst_capacity", "<u8"), ("src_bytes", "<u4"), ("serial", "<u4"),
+                            ("expect_seq", "<u4"), ("packet_first", "<u4"), ("packet_capacity", "<u4"), ("first_page_segment", "<u4"),
+                            ("flags", "<u4"), ("reserved", "<u4", (3,))], align=False)
+OGG_STREAM_RESULT = np.dtype([("status", "<u4"), ("pages", "<u4"), ("pages_ignored", "<u4"), ("packets", "<u4"), ("bytes_delivered", "<u8"),
+                              ("bytes_consumed", "<u8"), ("resume_segment", "<u4"), ("next_seq", "<u4"), ("last_granule", "<i8"),
+                              ("serial", "<u4"), ("bos_seen", "u1"), ("eos_seen", "u1"), ("reserved", "u1", (2,)), ("reserved2", "<u8")], align=False)
+OGG_PACKET = np.dtype([("run_pos", "<u8"), ("bytes", "<u4"), ("flags", "<u4"), ("granule", "<i8"), ("page_offset", "<u8"),
+                       ("page_seq", "<u4"), ("segment", "<u4")], align=False)
+assert OGG_STREAM_DESC.itemsize == 64 and OGG_STREAM_RESULT.itemsize == 64 and OGG_PACKET.itemsize == 40
 
 # every symbol of include/ohgpu.h: name -> (restype, argtypes)
 _vp, _vpp = C.c_void_p, C.POINTER(C.c_void_p)
@@ -223,6 +236,17 @@ SYMBOLS = {
     "ohgpu_ohm_rx_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t]),
     "ohgpu_ohm_rx_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
     "ohgpu_ohm_rx_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
+    "ohgpu_ogg_batch_check": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64]),
+    "ohgpu_ogg_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
+    "ohgpu_ogg_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "ohgpu_ogg_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_ogg_batch_packets": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_ogg_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
+    "ohgpu_ogg_process_host": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
+    "ohgpu_ogg_crc": (C.c_uint32, [_vp, C.c_size_t]),
+    "ohgpu_ogg_flac_head": (C.c_int, [_vp, C.c_size_t, _vp, C.POINTER(C.c_uint32), _u64p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "ohgpu_ogg_flac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp,
+                                              C.c_size_t, C.POINTER(C.c_size_t)]),
     "ohgpu_flywheel_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
     "ohgpu_flywheel_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "ohgpu_flywheel_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64]),
@@ -474,6 +498,34 @@ def ohm_rx_batch_check(streams, datagrams, src_arena_bytes, dst_arena_bytes):
     """The validation of ctx.ohm_rx_batch without a device (ohgpu_ohm_rx_batch_check): OhGpuError on a bad table."""
     s, g = _ohm_rx_tables(streams, datagrams)
     check(lib().ohgpu_ohm_rx_batch_check(_ptr_or_none(s), s.size, _ptr_or_none(g), g.size, src_arena_bytes, dst_arena_bytes))
+
+
+def _ogg_descs(descs):
+    d = np.ascontiguousarray(descs)
+    assert d.dtype == OGG_STREAM_DESC
+    return d
+
+
+def ogg_batch_check(descs, n_packets, src_arena_bytes, dst_arena_bytes):
+    """The validation of ctx.ogg_batch without a device (ohgpu_ogg_batch_check): OhGpuError on a bad descriptor."""
+    d = _ogg_descs(descs)
+    check(lib().ohgpu_ogg_batch_check(_ptr_or_none(d), d.size, n_packets, src_arena_bytes, dst_arena_bytes))
+
+
+def ogg_crc(data):
+    """The Ogg page checksum of any bytes (ohgpu_ogg_crc; host only)."""
+    raw = bytes(data)
+    return int(lib().ohgpu_ogg_crc(raw, len(raw)))
+
+
+def ogg_flac_head(data):
+    """The head of an Ogg FLAC stream (ohgpu_ogg_flac_head; host only): (FLAC_STREAMINFO record, serial, audio page offset, audio
+    segment, audio page number)."""
+    raw = bytes(data)
+    info = np.zeros(1, dtype=FLAC_STREAMINFO)
+    serial, seg, seq, off = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+    check(lib().ohgpu_ogg_flac_head(raw, len(raw), info.ctypes.data_as(C.c_void_p), C.byref(serial), C.byref(off), C.byref(seg), C.byref(seq)))
+    return info[0], int(serial.value), int(off.value), int(seg.value), int(seq.value)
 
 
 def _raop_tables(descs, packets):
@@ -866,6 +918,49 @@ class Context:
         check(lib().ohgpu_ohm_rx_process_host(self._h, _ptr_or_none(s), s.size, _ptr_or_none(g), g.size, _ptr_or_none(src), src.nbytes,
                                               _ptr_or_none(dst), dst.nbytes, _ptr_or_none(sres), _ptr_or_none(recs)))
         return sres, recs
+
+    def ogg_batch(self, descs, n_packets, src_arena_bytes, dst_arena_bytes):
+        d = _ogg_descs(descs)
+        b = C.c_void_p()
+        check(lib().ohgpu_ogg_batch_create(self._h, _ptr_or_none(d), d.size, n_packets, src_arena_bytes, dst_arena_bytes, C.byref(b)))
+        return b
+
+    def ogg_run(self, batch, d_src, d_dst, stream=None):
+        """Find, verify, chain, gather (ohgpu_ogg_batch_run): queued on the stream."""
+        check(lib().ohgpu_ogg_batch_run(self._h, batch, d_src, d_dst, stream))
+
+    def ogg_results(self, batch, n, n_packets):
+        """The last run's (OGG_STREAM_RESULT per stream, the packet table as OGG_PACKET); waits for the run."""
+        res, pk = np.zeros(n, dtype=OGG_STREAM_RESULT), np.zeros(n_packets, dtype=OGG_PACKET)
+        check(lib().ohgpu_ogg_batch_results(self._h, batch, _ptr_or_none(res), n))
+        check(lib().ohgpu_ogg_batch_packets(self._h, batch, _ptr_or_none(pk), n_packets))
+        return res, pk
+
+    def ogg_phase_ms(self, batch):
+        """The last run's (find, verify, chain, gather) in milliseconds, from device events."""
+        ms = (C.c_float * 4)()
+        check(lib().ohgpu_ogg_batch_phase_ms(self._h, batch, ms))
+        return tuple(float(v) for v in ms)
+
+    def ogg_process_host(self, descs, n_packets, src, dst):
+        """Host buffers in and out (ohgpu_ogg_process_host); returns (stream results, packet table)."""
+        d = _ogg_descs(descs)
+        res, pk = np.zeros(d.size, dtype=OGG_STREAM_RESULT), np.zeros(n_packets, dtype=OGG_PACKET)
+        check(lib().ohgpu_ogg_process_host(self._h, _ptr_or_none(d), d.size, n_packets, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst), dst.nbytes,
+                                           _ptr_or_none(res), _ptr_or_none(pk)))
+        return res, pk
+
+    def ogg_flac_process_host(self, ogg_descs, flac_descs, n_packets, src, mid_bytes, dst, frames_capacity=0):
+        """Ogg FLAC from host buffers (ohgpu_ogg_flac_process_host); returns (Ogg results, packet table, FLAC results, frames)."""
+        o, f = _ogg_descs(ogg_descs), np.ascontiguousarray(flac_descs)
+        assert f.dtype == FLAC_STREAM_DESC and f.size == o.size
+        ores, pk = np.zeros(o.size, dtype=OGG_STREAM_RESULT), np.zeros(n_packets, dtype=OGG_PACKET)
+        fres, frames = np.zeros(o.size, dtype=FLAC_STREAM_RESULT), np.zeros(frames_capacity, dtype=FLAC_FRAME)
+        n_frames = C.c_size_t(0)
+        check(lib().ohgpu_ogg_flac_process_host(self._h, _ptr_or_none(o), _ptr_or_none(f), o.size, n_packets, _ptr_or_none(src), src.nbytes, mid_bytes,
+                                                _ptr_or_none(dst), dst.nbytes, _ptr_or_none(ores), _ptr_or_none(pk), _ptr_or_none(fres),
+                                                _ptr_or_none(frames), frames_capacity, C.byref(n_frames)))
+        return ores, pk, fres, frames[:min(int(n_frames.value), frames_capacity)]
 
     def src_create(self, L, M, T, coef_q28):
         c = np.ascontiguousarray(coef_q28, dtype=np.int32)

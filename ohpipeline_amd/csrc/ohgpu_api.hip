@@ -306,8 +306,9 @@ static const struct { const char* noun; void (*release)(ohgpu_ctx*, ohgpu_batch*
     {"lossless-packet (ALAC)", alac_free, false}, // kBatchAlac
     {"RAOP", raop_free, false},                   // kBatchRaop
     {"Songcast receiver", ohm_rx_free, false},    // kBatchOhmRx
+    {"Ogg", ogg_free, false},                     // kBatchOgg
 };
-static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchOhmRx + 1, "a row per BatchKind");
+static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchOgg + 1, "a row per BatchKind");
 
 int run_guard(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, BatchKind kind, bool empty, bool null_src_ok,
               const void* src_base, const void* dst_base)

@@ -19,6 +19,7 @@
 #include "../../include/ohgpu.h"
 #include "alac_packet_core.h"
 #include "flac_frame_core.h"
+#include "ogg_page_core.h"
 #include "ohm_rx_core.h"
 #include "raop_aes_core.h"
 
@@ -428,7 +429,33 @@ struct OhmRxState {
 static_assert(sizeof(ohgpu_ohm_rx_datagram) == sizeof(ohmrx::Datagram) && sizeof(ohgpu_ohm_rx_state) == sizeof(ohmrx::State) && sizeof(ohgpu_ohm_rx_stream) == sizeof(ohmrx::Stream) &&
               sizeof(ohgpu_ohm_rx_record) == sizeof(ohmrx::Record) && sizeof(ohgpu_ohm_rx_stream_result) == sizeof(ohmrx::StreamResult), "Songcast receiver layouts");
 
-enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11, kBatchOhmRx = 12 };
+// ---- Ogg pages (csrc/ogg_page_kernel.hip): the descriptors, the find phase's tiles, the candidate list, the bitmap of
+// verified page starts, the gather plan and its dense work list, the packet table and results of the last run.  The batch's d_descs
+// holds nothing.
+struct OggTile { uint32_t stream, pos0; };            // one workgroup's share of the find: positions [pos0, pos0 + 1024) of a stream
+struct OggState {
+    size_t n_streams = 0, n_packets = 0;
+    uint32_t n_tiles = 0, cand_cap = 0, piece_cap = 0;
+    size_t bits_bytes = 0;
+    void* d_streams = nullptr;                        // oggpage::Stream[n_streams]
+    void* d_results = nullptr;                        // oggpage::Result[n_streams]
+    void* d_bit_base = nullptr;                       // uint64[n_streams]: the stream's first bit in d_bits
+    void* d_piece_first = nullptr;                    // uint64[n_streams]: the stream's first record in d_pieces
+    void* d_tables = nullptr;                         // oggpage::Tables
+    void* d_counters = nullptr;                       // uint32[2]: candidates found, pieces in the work list
+    void* d_list = nullptr;                           // oggpage::Candidate[cand_cap]
+    void* d_pieces = nullptr;                         // oggpage::Piece[piece_cap], a region a stream
+    void* d_work = nullptr;                           // uint32[piece_cap]: the pieces to copy, dense
+    void* d_tiles = nullptr;                          // OggTile[n_tiles]
+    void* d_bits = nullptr;                           // a bit per source byte of every stream: a verified page starts here
+    void* d_packets = nullptr;                        // oggpage::Packet[n_packets]
+    hipEvent_t ev[5] = {};
+    hipStream_t last_stream = nullptr;
+    bool ran = false;
+};
+static_assert(sizeof(ohgpu_ogg_stream_desc) == sizeof(oggpage::Stream) && sizeof(ohgpu_ogg_stream_result) == sizeof(oggpage::Result) && sizeof(ohgpu_ogg_packet) == sizeof(oggpage::Packet), "Ogg layouts");
+
+enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11, kBatchOhmRx = 12, kBatchOgg = 13 };
 
 }  // namespace ohgpu
 
@@ -536,6 +563,7 @@ struct ohgpu_batch {
     ohgpu::AlacState* alac = nullptr;   // kBatchAlac and kBatchRaop (likewise)
     ohgpu::RaopState* raop = nullptr;   // kBatchRaop only
     ohgpu::OhmRxState* ohmrx = nullptr; // kBatchOhmRx only
+    ohgpu::OggState* ogg = nullptr;     // kBatchOgg only
     void*    d_pull_tiles = nullptr;   // kBatchSrcPull: PullTile[n_pull_tiles] on the device (d_descs holds the messages)
     uint32_t n_pull_tiles = 0;
     // kBatchSrc whose messages differ in layout: one uniform batch per layout (each with its own block-kernel plan), run one
@@ -570,7 +598,7 @@ inline int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? OHGPU_ERR_
         if (e_ != hipSuccess) return ::ohgpu::set_error(::ohgpu::hip_code(e_), "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-// The release functions (free_pcm_line, free_fmt_line, free_dsd_line, flac_free, alac_free, raop_free, free_flywheel, free_src_fast, free_ohm, ohm_rx_free): what
+// The release functions (free_pcm_line, free_fmt_line, free_dsd_line, flac_free, alac_free, raop_free, free_flywheel, free_src_fast, free_ohm, ohm_rx_free, ogg_free): what
 // ohgpu_batch_destroy's table calls (csrc/ohgpu_api.hip).  Each takes a PARTLY BUILT batch -- null pointers, a plan that was never
 // made -- and leaves the plan reset: a create that fails at any point hands its batch to ohgpu_batch_destroy and returns.
 // kernels
@@ -618,6 +646,11 @@ int  ohm_rx_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const ohmrx::Stream* streams, c
 void ohm_rx_free(ohgpu_ctx* ctx, ohgpu_batch* b);
 int  ohm_rx_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
 uint32_t ohm_rx_gather_blocks(uint32_t n_datagrams, uint32_t cus);   // the gather launch's size: the rule tests/test_gpu_ohm_rx_many_trips.py restates
+// csrc/ogg_page_kernel.hip
+int  ogg_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const oggpage::Stream* streams);   // tiles, lists and result arrays onto the device (b->ogg holds the counts)
+void ogg_free(ohgpu_ctx* ctx, ohgpu_batch* b);
+int  ogg_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
+uint32_t ogg_wave_blocks(uint64_t items, uint32_t cus);   // the verify and gather launches' size: the rule tests/test_gpu_ogg_textbook.py restates
 // csrc/ohm_frame_kernel.hip: the two wire channels of streams wider than stereo (Sender::DoProcessFragment), one record per fragment
 OhmSelRec wide_record(uint64_t src_off, uint64_t dst_off, uint32_t n_frames, uint32_t channels, uint32_t sb, bool little, uint64_t src_arena_bytes);
 hipError_t launch_ohm_wide(const ohgpu_ctx* ctx, const void* d_recs, uint32_t n_recs, const uint8_t* src, uint8_t* dst, const uint8_t* prefix, hipStream_t s);
