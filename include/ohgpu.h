@@ -35,6 +35,8 @@
  *       (Av/Songcast/Ohm.cpp:22-42, OhmMsg.cpp:101-175, ProtocolOhBase.cpp:254-553)            -> CodecPcm's big-endian bytes
  *   CodecFlac's Ogg FLAC streams: libogg's page reader and libFLAC's Ogg aspect in front of the frames   ohgpu_ogg_batch_run()
  *       (Codec/Flac.cpp:155-213; thirdparty/libogg and flac-1.2.1's Ogg aspect by their behaviour)        -> the run ohgpu_flac_* reads
+ *   Mpeg4Container in front of CodecAlacApple: boxes walked, sample tables expanded into packet rows   ohgpu_mp4_batch_run()
+ *       (Codec/Mpeg4.cpp by its behaviour and ISO/IEC 14496-12; AlacApple.cpp:92-186)                 -> the table ohgpu_alac_* takes
  *   "SampleRateConverter" -- NOT PRESENT in the reference  ohgpu_src_* (own spec)
  *
  * The reference binds nothing through FFI today (it is one C++ static library); INTEGRATION.md
@@ -185,7 +187,8 @@ int ohgpu_batch_info(const ohgpu_batch* batch, uint64_t* n_msgs, uint64_t* in_fr
  * plan says.  A fmt batch takes exactly one of five routes: mono / stereo Songcast packs of >= 16 bits as plain PCM messages
  * (line_planned, group_chunks), Songcast packs of wider streams (fmt_wide_records), a uniform stereo batch on a register-only
  * kernel (fmt_stereo_*), the staged layout kernel (fmt_staged_chunks), or, with every count zero, the generic kernel only.
- * An Apple Lossless batch (ohgpu_alac_batch_create) answers with alac_route alone, and so does a RAOP batch.  OHGPU_ERR_INVALID for any other kind of batch. */
+ * An Apple Lossless batch (ohgpu_alac_batch_create) answers with alac_route alone, and so does a RAOP batch; an MPEG-4 batch
+ * (ohgpu_mp4_batch_create) answers with mp4_route alone.  OHGPU_ERR_INVALID for any other kind of batch. */
 typedef struct ohgpu_batch_paths {       /* 64 bytes */
     uint32_t line_planned;          /* 1: the line kernel has a plan for the batch (0: only the generic kernel can run it) */
     uint32_t launches;              /* line-kernel launches per run: one per layout present (8-bit / silence, and each 16/24/32-bit depth pair) */
@@ -205,6 +208,7 @@ typedef struct ohgpu_batch_paths {       /* 64 bytes */
     union {                         /* (the last word: named for what took it, `reserved` for older callers) */
         uint32_t reserved[1];
         uint32_t alac_route;        /* Apple Lossless: 1 the three fused phases over the transposed scratch, 2 the plain route (created under kernel variant 1) */
+        uint32_t mp4_route;         /* MPEG-4: 1 the four phases (walk, tile sums, carries, expand), 2 the plain route: one launch, a lane per stream (kernel variant 1) */
     };
 } ohgpu_batch_paths;
 int ohgpu_batch_paths_info(const ohgpu_batch* batch, ohgpu_batch_paths* out);
@@ -956,6 +960,135 @@ int ohgpu_ogg_flac_process_host(ohgpu_ctx* ctx, const ohgpu_ogg_stream_desc* ogg
                                 const void* src_host, uint64_t src_bytes, uint64_t mid_bytes, void* dst_host, uint64_t dst_bytes,
                                 ohgpu_ogg_stream_result* ogg_results, ohgpu_ogg_packet* packets,
                                 ohgpu_flac_stream_result* flac_results, ohgpu_flac_frame* frames, size_t frames_capacity, size_t* n_frames);
+
+/* ---- MPEG-4 container: boxes and sample tables in front of the Apple Lossless decoder (the text is csrc/mp4_box_core.h) ----
+ * What Codec/Mpeg4.cpp does in front of CodecAlacApple: the bytes of an .m4a file (ISO/IEC 14496-12), or of a prefix of one, in; one
+ * ohgpu_alac_packet row and one ohgpu_mp4_sample row per sample of the first Apple Lossless track out, with a result per stream.  The
+ * packets are decoded where they lie in `mdat`: the rows point into the source arena, nothing is copied.
+ * The walk, in file order, at most OHGPU_MP4_MAX_BOXES box headers a stream (one more: INVALID).  The first thing wrong gives the
+ * status, error_offset is the box that gave it, and every other field of a refused stream reads 0 (first_bad_sample 0xffffffff):
+ *   - a box is u32 size, fourcc; size 1: a u64 size follows; size 0: to the end of the stream, at top level only.  A size below its own
+ *     header, or a child that ends behind its parent, is INVALID.  Fewer than 8 bytes left in a parent end it.
+ *   - bytes 4..8 must be "ftyp" (Mpeg4.cpp:4692): NOT_MP4.  A stream of fewer than 8 bytes is TRUNCATED.
+ *   - top level: `moof` is UNSUPPORTED; the first `mdat` is recorded; the first `moov` is entered, before or behind `mdat`, and one
+ *     that reaches past src_bytes is TRUNCATED; any other box is skipped by its size, and one that reaches past src_bytes ends the
+ *     walk.  No `moov` by then: TRUNCATED (error_offset: where the walk stood).
+ *   - moov > trak > mdia > { mdhd, minf > stbl > { stsd, stts, stsc, stsz, stco | co64 } }.  The first box of each kind counts.
+ *     `mvex` in moov and `stz2` in stbl are UNSUPPORTED.  Everything else -- free, udta, meta, uuid, at every level -- is skipped.
+ *   - mdhd: version 0 or 1 (32- or 64-bit duration, Mpeg4.cpp:1705-1784); another version, a box too short, timescale 0: INVALID.
+ *   - the five tables are version 0 and their entry count fits the box, else INVALID.  stsz: a non-zero sample_size means N samples of
+ *     that size and no array (Mpeg4.cpp:1235-1247); N > OHGPU_MP4_MAX_SAMPLES is UNSUPPORTED.
+ *   - stsd: the first sample entry only.  Its fourcc is the trak's codec; `enca` is UNSUPPORTED.  In an `alac` entry (shorter than
+ *     28 bytes: INVALID): skip 16, channels u16, bit depth u16, skip 4, the rate's upper 16 bits (Mpeg4.cpp:2066-2105), then child
+ *     boxes; the inner `alac` box is 4 bytes of version and flags, the 24-byte configuration, perhaps more (AlacApple.cpp:101-128).
+ *     No such box, fewer than 28 bytes, a compatible version other than 0, or a configuration ohgpu_alac_batch_check refuses
+ *     (channels 1..8, frame length 1..16384, depth 16/20/24/32): UNSUPPORTED.  The configuration rules; the entry's own channels,
+ *     depth and rate are reported beside it (AlacApple.cpp:160-175).
+ *   - a trak is entered until one has been taken, and is taken at its end when its codec is `alac`.  Then: any of mdhd and the five
+ *     tables missing: INVALID (error_offset: the trak).  stsc entries (fc_k, spc_k, .), k < E: fc_0 == 1, fc strictly ascending and
+ *     <= C (the chunk count), spc_k >= 1; with run_k = (fc_{k+1}, or C + 1 for the last) - fc_k and S_k = sum_{j<k} run_j spc_j,
+ *     S_E >= N; else INVALID (the stsc).  stts entries (count_m, delta_m): the leading entries that cover N samples have count >= 1
+ *     and there are enough of them, else INVALID (the stts).  The end of moov with no trak taken: NOT_ALAC, `codec` the first
+ *     trak's entry fourcc (0: none), so that a caller can route mp4a, fLaC or Opus elsewhere.
+ * The expansion, all sums in 64 bits.  For sample s (from 0): k = the last entry with S_k <= s, r = s - S_k, chunk c = fc_k - 1 +
+ * r / spc_k, place in the chunk j = r mod spc_k, file offset = co[c] + sum_{i = s-j}^{s-1} size_i; first_frame and frames come from the
+ * stts runs in the same way.  A sample whose bytes leave [0, src_bytes), or whose size is above the Apple Lossless packet limit
+ * (frame_length x channels x 5 + 64), is refused: its packet row is {the stream's src_offset, 0 bytes}, which the Apple Lossless phases
+ * judge CORRUPT and ohgpu_alac_batch_check accepts; its sample row is written as any other.  Rows [0, min(N, packet_capacity)) of the
+ * stream's range are written, and samples_refused, first_bad_sample and samples_available speak of those rows.
+ * Where this differs from the reference (tests/mp4_textbook.py carries the same list):
+ *   - the reference streams, and fetches a `moov` behind `mdat` out of band; here the bytes are there, and the walk goes on past mdat;
+ *   - the reference refuses a file at its second stsz (Mpeg4.cpp:1222-1231); here the first `alac` trak is taken and the rest skipped;
+ *   - the reference's box header has no 64-bit size; here it has;
+ *   - the reference wants chunk offsets that do not go backwards (Mpeg4.cpp:3540) because it streams; rows are independent here;
+ *   - every sum is 64-bit, where the reference's are 32-bit with wrap checks (Mpeg4.cpp:3558);
+ *   - a seek lands on the packet that holds the frame.  The reference lands on that packet's chunk (Mpeg4.cpp:3879, its own FIXME),
+ *     compares an audio-sample count against a codec-sample total (:3991) and returns an offset within one stts entry as if it were
+ *     the track's (:4136-4138); none of the three is reproduced;
+ *   - an stts run of no samples among those that cover the track is INVALID (the reference passes over it). */
+#define OHGPU_MP4_OK           0u
+#define OHGPU_MP4_NOT_MP4      1u
+#define OHGPU_MP4_TRUNCATED    2u
+#define OHGPU_MP4_INVALID      3u
+#define OHGPU_MP4_NOT_ALAC     4u
+#define OHGPU_MP4_UNSUPPORTED  5u
+#define OHGPU_MP4_MAX_SAMPLES  (1u << 24)
+#define OHGPU_MP4_MAX_BOXES    4096u
+#define OHGPU_MP4_NO_SAMPLE    0xffffffffu
+
+typedef struct ohgpu_mp4_stream_desc {   /* 32 bytes */
+    uint64_t src_offset;            /* the file's bytes are [src_offset, + src_bytes) of the source arena, any address */
+    uint32_t src_bytes;             /* < 2^31: the whole file or a prefix of it */
+    uint32_t flags;                 /* zero */
+    uint32_t packet_first;          /* the stream's rows are [packet_first, + packet_capacity) of both tables; samples beyond the */
+    uint32_t packet_capacity;       /*   capacity are counted (`samples`), not expanded.  0: no rows */
+    uint32_t reserved[2];           /* zero */
+} ohgpu_mp4_stream_desc;
+
+typedef struct ohgpu_mp4_stream_result {   /* 112 bytes */
+    uint32_t status;                /* OHGPU_MP4_OK ... _UNSUPPORTED */
+    uint32_t codec;                 /* the taken trak's entry fourcc, first character in the top byte ('alac'); NOT_ALAC: the first trak's */
+    ohgpu_alac_config config;       /* the inner `alac` box's: what the stream's ohgpu_alac_stream_desc takes */
+    uint32_t timescale;             /* mdhd */
+    uint32_t entry_rate;            /* the sample entry's: the upper 16 bits of its 16.16 rate */
+    uint64_t duration;              /* mdhd, in timescale units */
+    uint64_t frames;                /* the sum of stts over the N samples */
+    uint32_t samples;               /* N (stsz) */
+    uint32_t chunks;                /* C (stco / co64) */
+    uint32_t samples_available;     /* the leading rows that were not refused: what a prefix of a file can play */
+    uint32_t samples_refused;       /* rows refused */
+    uint32_t first_bad_sample;      /* the lowest of them; OHGPU_MP4_NO_SAMPLE: none */
+    uint16_t entry_channels, entry_bits;   /* the sample entry's */
+    uint64_t moov_offset;           /* from src_offset */
+    uint64_t mdat_offset;           /* the first mdat box (its header), and ... */
+    uint64_t mdat_bytes;            /* ... its payload as its header states it; both 0 when the walk met none */
+    uint64_t error_offset;          /* the box that gave a status other than OK */
+} ohgpu_mp4_stream_result;
+
+typedef struct ohgpu_mp4_sample {   /* 16 bytes: one row per sample, beside its ohgpu_alac_packet row */
+    uint64_t first_frame;           /* the audio frames in front of it */
+    uint32_t frames;                /* its own (its stts run's delta) */
+    uint32_t chunk;                 /* from 0 */
+} ohgpu_mp4_sample;
+
+/* Host only, no device needed: the validation ohgpu_mp4_batch_create makes.  OHGPU_ERR_INVALID: non-zero reserved words or flags,
+ * src_bytes >= 2^31, row ranges that overlap or run past the tables of n_packets rows.  OHGPU_ERR_BOUNDS: a range outside the source
+ * arena.  The empty batch is legal. */
+int ohgpu_mp4_batch_check(const ohgpu_mp4_stream_desc* descs, size_t n, size_t n_packets, uint64_t src_arena_bytes);
+/* The descriptors go to the device; tiles, carries, both tables (every byte 0xa5 until a run writes it) and the results are the
+ * batch's.  Created under ohgpu_set_kernel_variant(1) the batch takes the plain route: one launch, a lane per stream runs the walk
+ * and the serial expansion (ohgpu_batch_paths_info: mp4_route).  Both routes write the same bytes.  Freed with ohgpu_batch_destroy. */
+int ohgpu_mp4_batch_create(ohgpu_ctx* ctx, const ohgpu_mp4_stream_desc* descs, size_t n, size_t n_packets, uint64_t src_arena_bytes, ohgpu_batch** batch);
+/* Walk, tile sums, carries, expand: queued on the stream, nothing waits for the host.  The device reads a stream as the aligned 4-byte
+ * words that hold its bytes (no load is misaligned): up to 3 bytes in front of src_offset and behind src_offset + src_bytes are loaded
+ * and never used, so src_base must be a multiple of 4 and the arena's allocation must end on a multiple of 4 (any hipMalloc block does).  The batch owns its tables: it runs on one
+ * stream at a time.  A second run, and a second batch of the same shape, allocate nothing on the device (ohgpu_device_allocations). */
+int ohgpu_mp4_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* src_base, void* stream);
+/* The last run's results, n = the batch's stream count (waits for that run). */
+int ohgpu_mp4_batch_results(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_mp4_stream_result* results, size_t n);
+/* The last run's tables, n_packets = their length; of a stream's range the first min(samples, packet_capacity) rows are that run's
+ * (waits for that run).  A packet row's src_offset is absolute in the source arena: the rows are what ohgpu_alac_batch_create takes. */
+int ohgpu_mp4_batch_packets(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_alac_packet* packets, size_t n_packets);
+int ohgpu_mp4_batch_samples(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_mp4_sample* samples, size_t n_packets);
+/* The last run's phases in milliseconds from device events: walk, tile sums, carries, expand (waits for that run).  The plain route
+ * is one phase: the other three read as 0. */
+int ohgpu_mp4_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float ms[4]);
+/* Host-buffer convenience: one upload, one run, the results and both tables home.  Any of the three pointers may be NULL. */
+int ohgpu_mp4_process_host(ohgpu_ctx* ctx, const ohgpu_mp4_stream_desc* descs, size_t n, size_t n_packets, const void* src_host, uint64_t src_bytes,
+                           ohgpu_mp4_stream_result* results, ohgpu_alac_packet* packets, ohgpu_mp4_sample* samples);
+/* Host only: the row of a downloaded sample table that holds audio frame `frame` (a binary search), and that row's first frame.
+ * OHGPU_ERR_BOUNDS: the frame lies behind the table's last row. */
+int ohgpu_mp4_seek(const ohgpu_mp4_sample* samples, size_t n, uint64_t frame, uint64_t* index, uint64_t* first_frame);
+/* .m4a files from host buffers to PCM: one upload of the files' bytes, the MPEG-4 batch, one small read of its results and packet
+ * table (16 bytes a packet), an Apple Lossless batch over the same device source arena -- stream i's config from its result, its rows
+ * [0, min(samples, packet_capacity)) as its packets, output form (flags), dst_offset and dst_plane_stride from alac_descs[i], whose
+ * other fields are ignored -- and of dst_host the samples that decoded.  A stream whose status is not OK contributes no packets; the
+ * others are served.  packet_results is indexed as the MPEG-4 tables are (rows that were not decoded read {0, 0}).  Any result
+ * pointer may be NULL. */
+int ohgpu_mp4_alac_process_host(ohgpu_ctx* ctx, const ohgpu_mp4_stream_desc* mp4_descs, const ohgpu_alac_stream_desc* alac_descs, size_t n, size_t n_packets,
+                                const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes,
+                                ohgpu_mp4_stream_result* mp4_results, ohgpu_alac_packet* packets, ohgpu_mp4_sample* samples,
+                                ohgpu_alac_stream_result* alac_results, ohgpu_alac_packet_result* packet_results);
 
 /* ---- sample-rate converter (own specification; DESIGN.md "Resampler") ---- */
 /* Host-side filter design: Kaiser-windowed sinc, Q28 coefficients, coef_q28[p*T + k] = h[p + k*L].

@@ -157,6 +157,19 @@ OGG_STREAM_RESULT = np.dtype([("status", "<u4"), ("pages", "<u4"), ("pages_ignor
 OGG_PACKET = np.dtype([("run_pos", "<u8"), ("bytes", "<u4"), ("flags", "<u4"), ("granule", "<i8"), ("page_offset", "<u8"),
                        ("page_seq", "<u4"), ("segment", "<u4")], align=False)
 assert OGG_STREAM_DESC.itemsize == 64 and OGG_STREAM_RESULT.itemsize == 64 and OGG_PACKET.itemsize == 40
+# MPEG-4 container: ohgpu_mp4_stream_desc (32 B), ohgpu_mp4_stream_result (112 B), ohgpu_mp4_sample (16 B); the packet
+# table's rows are ALAC_PACKET
+MP4_OK, MP4_NOT_MP4, MP4_TRUNCATED, MP4_INVALID, MP4_NOT_ALAC, MP4_UNSUPPORTED = range(6)
+MP4_MAX_SAMPLES, MP4_MAX_BOXES, MP4_NO_SAMPLE = 1 << 24, 4096, 0xffffffff
+MP4_ROUTE_FUSED, MP4_ROUTE_PLAIN = 1, 2
+MP4_STREAM_DESC = np.dtype([("src_offset", "<u8"), ("src_bytes", "<u4"), ("flags", "<u4"), ("packet_first", "<u4"), ("packet_capacity", "<u4"),
+                            ("reserved", "<u4", (2,))], align=False)
+MP4_STREAM_RESULT = np.dtype([("status", "<u4"), ("codec", "<u4"), ("config", ALAC_CONFIG), ("timescale", "<u4"), ("entry_rate", "<u4"), ("duration", "<u8"),
+                              ("frames", "<u8"), ("samples", "<u4"), ("chunks", "<u4"), ("samples_available", "<u4"), ("samples_refused", "<u4"),
+                              ("first_bad_sample", "<u4"), ("entry_channels", "<u2"), ("entry_bits", "<u2"), ("moov_offset", "<u8"), ("mdat_offset", "<u8"),
+                              ("mdat_bytes", "<u8"), ("error_offset", "<u8")], align=False)
+MP4_SAMPLE = np.dtype([("first_frame", "<u8"), ("frames", "<u4"), ("chunk", "<u4")], align=False)
+assert MP4_STREAM_DESC.itemsize == 32 and MP4_STREAM_RESULT.itemsize == 112 and MP4_SAMPLE.itemsize == 16
 
 # every symbol of include/ohgpu.h: name -> (restype, argtypes)
 _vp, _vpp = C.c_void_p, C.POINTER(C.c_void_p)
@@ -243,6 +256,16 @@ SYMBOLS = {
     "ohgpu_ogg_batch_packets": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
     "ohgpu_ogg_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
     "ohgpu_ogg_process_host": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
+    "ohgpu_mp4_batch_check": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_uint64]),
+    "ohgpu_mp4_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_uint64, _vpp]),
+    "ohgpu_mp4_batch_run": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "ohgpu_mp4_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_mp4_batch_packets": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_mp4_batch_samples": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_mp4_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
+    "ohgpu_mp4_process_host": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "ohgpu_mp4_seek": (C.c_int, [_vp, C.c_size_t, C.c_uint64, _u64p, _u64p]),
+    "ohgpu_mp4_alac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "ohgpu_ogg_crc": (C.c_uint32, [_vp, C.c_size_t]),
     "ohgpu_ogg_flac_head": (C.c_int, [_vp, C.c_size_t, _vp, C.POINTER(C.c_uint32), _u64p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "ohgpu_ogg_flac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp,
@@ -528,6 +551,27 @@ def ogg_flac_head(data):
     return info[0], int(serial.value), int(off.value), int(seg.value), int(seq.value)
 
 
+def _mp4_descs(descs):
+    d = np.ascontiguousarray(descs)
+    assert d.dtype == MP4_STREAM_DESC
+    return d
+
+
+def mp4_batch_check(descs, n_packets, src_arena_bytes):
+    """The validation of ctx.mp4_batch without a device (ohgpu_mp4_batch_check): OhGpuError on a bad descriptor."""
+    d = _mp4_descs(descs)
+    check(lib().ohgpu_mp4_batch_check(_ptr_or_none(d), d.size, n_packets, src_arena_bytes))
+
+
+def mp4_seek(samples, frame):
+    """The row of a sample table (MP4_SAMPLE) that holds audio frame `frame` (ohgpu_mp4_seek; host only): (index, its first frame)."""
+    t = np.ascontiguousarray(samples)
+    assert t.dtype == MP4_SAMPLE
+    index, first = C.c_uint64(0), C.c_uint64(0)
+    check(lib().ohgpu_mp4_seek(_ptr_or_none(t), t.size, frame, C.byref(index), C.byref(first)))
+    return int(index.value), int(first.value)
+
+
 def _raop_tables(descs, packets):
     d, p = np.ascontiguousarray(descs), np.ascontiguousarray(packets)
     assert d.dtype == RAOP_STREAM_DESC and p.dtype == ALAC_PACKET
@@ -677,6 +721,7 @@ class Context:
         check(lib().ohgpu_batch_paths_info(batch, v.ctypes.data_as(C.c_void_p)))
         out = {k: int(v[k][0]) for k in BATCH_PATHS.names if k != "reserved"}
         out["alac_route"] = int(v["reserved"][0][0])        # (the header's union: the last word)
+        out["mp4_route"] = out["alac_route"]                 # (the same word: a batch is of one kind)
         return out
 
     def pcm_process_host(self, descs, src, dst):
@@ -961,6 +1006,49 @@ class Context:
                                                 _ptr_or_none(dst), dst.nbytes, _ptr_or_none(ores), _ptr_or_none(pk), _ptr_or_none(fres),
                                                 _ptr_or_none(frames), frames_capacity, C.byref(n_frames)))
         return ores, pk, fres, frames[:min(int(n_frames.value), frames_capacity)]
+
+    def mp4_batch(self, descs, n_packets, src_arena_bytes):
+        d = _mp4_descs(descs)
+        b = C.c_void_p()
+        check(lib().ohgpu_mp4_batch_create(self._h, _ptr_or_none(d), d.size, n_packets, src_arena_bytes, C.byref(b)))
+        return b
+
+    def mp4_run(self, batch, d_src, stream=None):
+        """Walk, tile sums, carries, expand (ohgpu_mp4_batch_run): queued on the stream."""
+        check(lib().ohgpu_mp4_batch_run(self._h, batch, d_src, stream))
+
+    def mp4_results(self, batch, n, n_packets):
+        """The last run's (MP4_STREAM_RESULT per stream, the packet table as ALAC_PACKET, the sample table as MP4_SAMPLE); waits for the run."""
+        res, pk, sm = np.zeros(n, dtype=MP4_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
+        check(lib().ohgpu_mp4_batch_results(self._h, batch, _ptr_or_none(res), n))
+        check(lib().ohgpu_mp4_batch_packets(self._h, batch, _ptr_or_none(pk), n_packets))
+        check(lib().ohgpu_mp4_batch_samples(self._h, batch, _ptr_or_none(sm), n_packets))
+        return res, pk, sm
+
+    def mp4_phase_ms(self, batch):
+        """The last run's (walk, tile sums, carries, expand) in milliseconds, from device events; the plain route: (all of it, 0, 0, 0)."""
+        ms = (C.c_float * 4)()
+        check(lib().ohgpu_mp4_batch_phase_ms(self._h, batch, ms))
+        return tuple(float(v) for v in ms)
+
+    def mp4_process_host(self, descs, n_packets, src):
+        """Host bytes in (ohgpu_mp4_process_host); returns (stream results, packet table, sample table)."""
+        d = _mp4_descs(descs)
+        res, pk, sm = np.zeros(d.size, dtype=MP4_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
+        check(lib().ohgpu_mp4_process_host(self._h, _ptr_or_none(d), d.size, n_packets, _ptr_or_none(src), src.nbytes, _ptr_or_none(res), _ptr_or_none(pk),
+                                           _ptr_or_none(sm)))
+        return res, pk, sm
+
+    def mp4_alac_process_host(self, mp4_descs, alac_descs, n_packets, src, dst):
+        """.m4a bytes in, PCM out (ohgpu_mp4_alac_process_host); returns (MPEG-4 results, packet table, sample table, Apple Lossless stream
+        results, packet results indexed as the tables are).  Of alac_descs only flags, dst_offset and dst_plane_stride are read."""
+        m, a = _mp4_descs(mp4_descs), np.ascontiguousarray(alac_descs)
+        assert a.dtype == ALAC_STREAM_DESC and a.size == m.size
+        res, pk, sm = np.zeros(m.size, dtype=MP4_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
+        ares, pres = np.zeros(m.size, dtype=ALAC_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET_RESULT)
+        check(lib().ohgpu_mp4_alac_process_host(self._h, _ptr_or_none(m), _ptr_or_none(a), m.size, n_packets, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst), dst.nbytes,
+                                                _ptr_or_none(res), _ptr_or_none(pk), _ptr_or_none(sm), _ptr_or_none(ares), _ptr_or_none(pres)))
+        return res, pk, sm, ares, pres
 
     def src_create(self, L, M, T, coef_q28):
         c = np.ascontiguousarray(coef_q28, dtype=np.int32)

@@ -20,6 +20,7 @@
 #include "alac_packet_core.h"
 #include "flac_frame_core.h"
 #include "ogg_page_core.h"
+#include "mp4_box_core.h"
 #include "ohm_rx_core.h"
 #include "raop_aes_core.h"
 
@@ -455,7 +456,34 @@ struct OggState {
 };
 static_assert(sizeof(ohgpu_ogg_stream_desc) == sizeof(oggpage::Stream) && sizeof(ohgpu_ogg_stream_result) == sizeof(oggpage::Result) && sizeof(ohgpu_ogg_packet) == sizeof(oggpage::Packet), "Ogg layouts");
 
-enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11, kBatchOhmRx = 12, kBatchOgg = 13 };
+// ---- MPEG-4 sample tables (csrc/mp4_table_kernel.hip): the descriptors, the tiles of the sums and the expansion, the
+// carries, the record of each stream's tables, both row tables and the results of the last run.  The batch's d_descs holds nothing.
+constexpr uint32_t kMp4Tile = mp4box::kTile;          // 1024 samples: tests/test_gpu_mp4_textbook.py restates it
+struct Mp4Tile { uint32_t stream, s0; };              // one workgroup's share: samples [s0, s0 + kMp4Tile) of a stream
+struct Mp4Plan { uint32_t tile_first, n_tiles, stsc_first, stts_first; };   // a stream's tiles in the tile list, its carries in d_carry_*
+struct Mp4State {
+    size_t n_streams = 0, n_packets = 0;
+    uint32_t n_tiles = 0, n_stsc = 0, n_stts = 0;
+    bool plain = false;                               // created under kernel variant 1: one launch, a lane per stream
+    void* d_streams = nullptr;                        // mp4box::Stream[n_streams]
+    void* d_results = nullptr;                        // mp4box::Result[n_streams]
+    void* d_tables = nullptr;                         // mp4box::Tables[n_streams]
+    void* d_plan = nullptr;                           // Mp4Plan[n_streams]
+    void* d_tiles = nullptr;                          // Mp4Tile[n_tiles]
+    void* d_tile_carry = nullptr;                     // uint64[n_tiles]: the tile's sum, then the sum of the stream's tiles in front of it
+    void* d_stsc_carry = nullptr;                     // uint64[n_stsc]: S_k
+    void* d_stts_carry = nullptr;                     // uint64[2 * n_stts]: the samples, then the frames, in front of each stts run
+    void* d_packets = nullptr;                        // mp4box::Row[n_packets]
+    void* d_samples = nullptr;                        // mp4box::Sample[n_packets]
+    hipEvent_t ev[5] = {};
+    hipStream_t last_stream = nullptr;
+    bool ran = false;
+};
+static_assert(sizeof(ohgpu_mp4_stream_desc) == sizeof(mp4box::Stream) && sizeof(ohgpu_mp4_stream_result) == sizeof(mp4box::Result) && sizeof(ohgpu_mp4_sample) == sizeof(mp4box::Sample) &&
+              sizeof(ohgpu_alac_packet) == sizeof(mp4box::Row) && sizeof(ohgpu_alac_config) == sizeof(mp4box::Config) && offsetof(ohgpu_mp4_stream_result, error_offset) == offsetof(mp4box::Result, error_offset) &&
+              offsetof(ohgpu_mp4_stream_result, first_bad_sample) == offsetof(mp4box::Result, first_bad_sample), "MPEG-4 layouts");
+
+enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11, kBatchOhmRx = 12, kBatchOgg = 13, kBatchMp4 = 14 };
 
 }  // namespace ohgpu
 
@@ -564,6 +592,7 @@ struct ohgpu_batch {
     ohgpu::RaopState* raop = nullptr;   // kBatchRaop only
     ohgpu::OhmRxState* ohmrx = nullptr; // kBatchOhmRx only
     ohgpu::OggState* ogg = nullptr;     // kBatchOgg only
+    ohgpu::Mp4State* mp4 = nullptr;     // kBatchMp4 only
     void*    d_pull_tiles = nullptr;   // kBatchSrcPull: PullTile[n_pull_tiles] on the device (d_descs holds the messages)
     uint32_t n_pull_tiles = 0;
     // kBatchSrc whose messages differ in layout: one uniform batch per layout (each with its own block-kernel plan), run one
@@ -598,7 +627,7 @@ inline int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? OHGPU_ERR_
         if (e_ != hipSuccess) return ::ohgpu::set_error(::ohgpu::hip_code(e_), "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-// The release functions (free_pcm_line, free_fmt_line, free_dsd_line, flac_free, alac_free, raop_free, free_flywheel, free_src_fast, free_ohm, ohm_rx_free, ogg_free): what
+// The release functions (free_pcm_line, free_fmt_line, free_dsd_line, flac_free, alac_free, raop_free, free_flywheel, free_src_fast, free_ohm, ohm_rx_free, ogg_free, mp4_free): what
 // ohgpu_batch_destroy's table calls (csrc/ohgpu_api.hip).  Each takes a PARTLY BUILT batch -- null pointers, a plan that was never
 // made -- and leaves the plan reset: a create that fails at any point hands its batch to ohgpu_batch_destroy and returns.
 // kernels
@@ -651,6 +680,10 @@ int  ogg_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const oggpage::Stream* streams);  
 void ogg_free(ohgpu_ctx* ctx, ohgpu_batch* b);
 int  ogg_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
 uint32_t ogg_wave_blocks(uint64_t items, uint32_t cus);   // the verify and gather launches' size: the rule tests/test_gpu_ogg_textbook.py restates
+// csrc/mp4_table_kernel.hip.  No launch is persistent: a workgroup a tile (sums, expand), a wave a stream (carries), a lane a stream (walk).
+int  mp4_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const mp4box::Stream* streams);   // tiles, carries and tables onto the device (b->mp4 holds the counts)
+void mp4_free(ohgpu_ctx* ctx, ohgpu_batch* b);
+int  mp4_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, hipStream_t s);
 // csrc/ohm_frame_kernel.hip: the two wire channels of streams wider than stereo (Sender::DoProcessFragment), one record per fragment
 OhmSelRec wide_record(uint64_t src_off, uint64_t dst_off, uint32_t n_frames, uint32_t channels, uint32_t sb, bool little, uint64_t src_arena_bytes);
 hipError_t launch_ohm_wide(const ohgpu_ctx* ctx, const void* d_recs, uint32_t n_recs, const uint8_t* src, uint8_t* dst, const uint8_t* prefix, hipStream_t s);

@@ -6,8 +6,9 @@
 //                                                                                   timescale and duration -> OutputDecodedStream
 //   CodecAlacAppleBase::Decode         OpenHome/Media/Codec/AlacAppleBase.cpp:66-115  a packet -> little-endian pieces -> OutputAudioPcm
 // Shape of this implementation (host/FlacDecoder.h's): a decoder is a packet queue; nothing is decoded when packets arrive.  The
-// MPEG-4 container is not here: SetConfig takes what StreamInitialise reads out of it, PushPacket takes one sample of the 'mdat' box
-// as the sample table delimits it.  Flush() takes every lane of a tick, lays the queued packets of all of them into one arena and
+// MPEG-4 container is not in this element (on the device it is ohgpu_mp4_*, DESIGN.md 5.16, whose results and packet rows are what
+// goes in here): SetConfig takes what StreamInitialise reads out of it, PushPacket takes one sample of the 'mdat' box as the sample
+// table delimits it.  Flush() takes every lane of a tick, lays the queued packets of all of them into one arena and
 // makes ONE device call (ohgpu_alac_process_host, packed little-endian output -- the reference decoder's own buffer); each packet
 // leaves through CodecController::OutputAudioPcm in Decode's pieces.  Packets are independent, so a seek is a change of the index the
 // next packet is counted from (SeekToPacket); the sample table that turns a time into that index is the container's.
