@@ -37,6 +37,8 @@
  *       (Codec/Flac.cpp:155-213; thirdparty/libogg and flac-1.2.1's Ogg aspect by their behaviour)        -> the run ohgpu_flac_* reads
  *   Mpeg4Container in front of CodecAlacApple: boxes walked, sample tables expanded into packet rows   ohgpu_mp4_batch_run()
  *       (Codec/Mpeg4.cpp by its behaviour and ISO/IEC 14496-12; AlacApple.cpp:92-186)                 -> the table ohgpu_alac_* takes
+ *   CodecWav, CodecAiff, CodecAifc: the chunks walked, the audio run made big-endian (and 32 -> 24 bit)   ohgpu_iff_batch_run()
+ *       (Codec/Wav.cpp, AiffBase.cpp, Aiff.cpp, Aifc.cpp by their behaviour)                             -> CodecPcm's big-endian bytes
  *   "SampleRateConverter" -- NOT PRESENT in the reference  ohgpu_src_* (own spec)
  *
  * The reference binds nothing through FFI today (it is one C++ static library); INTEGRATION.md
@@ -188,7 +190,8 @@ int ohgpu_batch_info(const ohgpu_batch* batch, uint64_t* n_msgs, uint64_t* in_fr
  * (line_planned, group_chunks), Songcast packs of wider streams (fmt_wide_records), a uniform stereo batch on a register-only
  * kernel (fmt_stereo_*), the staged layout kernel (fmt_staged_chunks), or, with every count zero, the generic kernel only.
  * An Apple Lossless batch (ohgpu_alac_batch_create) answers with alac_route alone, and so does a RAOP batch; an MPEG-4 batch
- * (ohgpu_mp4_batch_create) answers with mp4_route alone.  OHGPU_ERR_INVALID for any other kind of batch. */
+ * (ohgpu_mp4_batch_create) answers with mp4_route alone, a PCM file batch (ohgpu_iff_batch_create) with iff_route alone.
+ * OHGPU_ERR_INVALID for any other kind of batch. */
 typedef struct ohgpu_batch_paths {       /* 64 bytes */
     uint32_t line_planned;          /* 1: the line kernel has a plan for the batch (0: only the generic kernel can run it) */
     uint32_t launches;              /* line-kernel launches per run: one per layout present (8-bit / silence, and each 16/24/32-bit depth pair) */
@@ -209,6 +212,7 @@ typedef struct ohgpu_batch_paths {       /* 64 bytes */
         uint32_t reserved[1];
         uint32_t alac_route;        /* Apple Lossless: 1 the three fused phases over the transposed scratch, 2 the plain route (created under kernel variant 1) */
         uint32_t mp4_route;         /* MPEG-4: 1 the four phases (walk, tile sums, carries, expand), 2 the plain route: one launch, a lane per stream (kernel variant 1) */
+        uint32_t iff_route;         /* PCM files: 1 the two launches (walk, convert by 16-byte pieces), 2 the plain route: one launch, a lane per stream (kernel variant 1) */
     };
 } ohgpu_batch_paths;
 int ohgpu_batch_paths_info(const ohgpu_batch* batch, ohgpu_batch_paths* out);
@@ -1089,6 +1093,120 @@ int ohgpu_mp4_alac_process_host(ohgpu_ctx* ctx, const ohgpu_mp4_stream_desc* mp4
                                 const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes,
                                 ohgpu_mp4_stream_result* mp4_results, ohgpu_alac_packet* packets, ohgpu_mp4_sample* samples,
                                 ohgpu_alac_stream_result* alac_results, ohgpu_alac_packet_result* packet_results);
+
+/* ---- PCM files: WAV, AIFF and AIFC chunks walked and the audio made big-endian (the text is csrc/iff_chunk_core.h) ----
+ * What CodecWav, CodecAiff and CodecAifc do: the bytes of a file, or of a prefix of one, in; the audio as the pipeline's big-endian
+ * PCM out, with a result per stream.  Two launches, nothing waits for the host between them.
+ * The first 12 bytes decide the kind: "RIFF" .... "WAVE", "FORM" .... "AIFF", "FORM" .... "AIFC"; anything else (fewer than 12 bytes
+ * too) is NOT_IFF.  Chunks follow from byte 12: a four-character id, a 32-bit size (little-endian in RIFF, big-endian in FORM), the
+ * payload, and one pad byte behind an odd size.  The walk takes the first `fmt ` and the first `data`, or the first `COMM` and the
+ * first `SSND`, in either order, and stops when it has both; every other chunk, and a second one of those, is skipped by its size.
+ * More than OHGPU_IFF_MAX_CHUNKS headers: INVALID.  The first thing wrong gives the status, error_offset is the chunk that gave it
+ * (0 for NOT_IFF), and every other field of a refused stream reads 0.  The checks of a chunk are made in the order written here:
+ *   - a chunk header (8 bytes) that the walk needs and that does not lie inside src_bytes: TRUNCATED, error_offset where it would lie.
+ *   - `fmt `: size 16, 18 or 40, else INVALID; the payload not inside src_bytes: TRUNCATED.  Format tag 1 or 0xfffe, else UNSUPPORTED;
+ *     a 0xfffe chunk of 40 bytes whose sub-format does not begin with the 16-bit word 1: UNSUPPORTED.  Channels 0: INVALID; above
+ *     OHGPU_IFF_MAX_CHANNELS: UNSUPPORTED.  Rate 0 or byte rate 0: INVALID.  Depth 0 or no multiple of 8: INVALID; above 32:
+ *     UNSUPPORTED.  A frame is channels x depth / 8 bytes (the block-align field is not read); bit_rate = byte rate x 8 (mod 2^32).
+ *   - `data`: the audio is the chunk's stated size, without its pad byte.  A RIFF size field (bytes 4..8) of 0 means a continuous
+ *     stream: the audio runs to the end of src_bytes, frames_total reads 0 ("unknown"), and a `data` in front of `fmt ` is INVALID
+ *     (nothing can be found behind audio without an end).
+ *   - `COMM`: exactly 18 bytes in AIFF, at least 22 in AIFC, else INVALID; the payload not inside src_bytes: TRUNCATED.  Channels u16
+ *     (0: INVALID, above OHGPU_IFF_MAX_CHANNELS: UNSUPPORTED), sample frames u32, depth u16, the rate as an 80-bit extended number,
+ *     in AIFC the compression's fourcc.  Depth 8, 16, 24 or 32 as is, 20 reported as 24, else UNSUPPORTED; a sample is ceil(depth / 8)
+ *     bytes.  Rate: the sign is 0 and the exponent e lies in 0x3fff..0x401e, rate = (the mantissa's upper 32 bits) >> (0x401e - e),
+ *     else INVALID; rate 0: INVALID; 22255 and 11127 (the Macintosh rates) read 22050 and 11025.  Compression "NONE" is big-endian,
+ *     "sowt" and "SOWT" little-endian, anything else UNSUPPORTED.  bit_rate = rate x frame bytes x 8 (mod 2^32).
+ *   - `SSND`: a payload of fewer than 8 bytes: INVALID; its 8-byte header (offset u32, block size u32) not inside src_bytes:
+ *     TRUNCATED; offset > size - 8: INVALID.  The audio starts 8 + offset bytes into the payload.  When both chunks are known: sample
+ *     frames x frame bytes more than the chunk holds behind that point: INVALID (error_offset: the SSND).
+ *   - audio that runs past src_bytes is no error: frames_available counts the whole frames present, so a prefix of a file plays.
+ * The conversion of an OK stream: frames [frame_first, frame_first + n) go to dst_offset as big-endian samples of out_bit_depth =
+ * min(src_bit_depth, max_bit_depth) bits, n = min(frames_available - frame_first, dst_frame_capacity, dst_bytes_capacity / the output
+ * frame's bytes), and 0 when frame_first lies behind the audio.  Each output sample is the top out_bit_depth / 8 bytes of the source
+ * sample, most significant first: a 32-bit source under a limit of 24 loses its least significant byte.  8-bit WAV is copied as it
+ * lies (the reference does); with OHGPU_IFF_FLAG_WAV8_UNSIGNED each byte is xor-ed with 0x80, which is what the format means.  No byte
+ * of the destination outside the n frames is touched.
+ * Where this differs from the reference (tests/iff_textbook.py carries the same list):
+ *   - the reference streams, and wants `fmt ` before `data` and `COMM` before `SSND` (AiffBase.cpp has a FIXME of its own on it);
+ *     here the bytes are there and either order is read;
+ *   - CodecWav's chunk search returns the padded size, so an odd `data` size counts its pad byte as audio; here the stated size counts;
+ *   - the reference does not look at an extensible format's sub-format; here one that is not PCM is UNSUPPORTED;
+ *   - the reference takes a 20-bit AIFF sample for two bytes and then calls the stream 24-bit; here such a sample has three bytes;
+ *   - the reference refuses 32-bit AIFF; here it is read as 32-bit WAV is;
+ *   - the reference ignores SSND's offset field and holds the audio's size against the chunk's size with those 8 bytes in it; here
+ *     both are honoured;
+ *   - the reference's rate for exponents from 0x4013 up shifts by e - 0x4007, which is not the number the field encodes; here one
+ *     formula serves every exponent;
+ *   - OHGPU_IFF_FLAG_WAV8_UNSIGNED has no counterpart; without it the bytes are the reference's. */
+#define OHGPU_IFF_OK           0u
+#define OHGPU_IFF_NOT_IFF      1u
+#define OHGPU_IFF_TRUNCATED    2u
+#define OHGPU_IFF_INVALID      3u
+#define OHGPU_IFF_UNSUPPORTED  4u
+#define OHGPU_IFF_KIND_WAV     1u
+#define OHGPU_IFF_KIND_AIFF    2u
+#define OHGPU_IFF_KIND_AIFC    3u
+#define OHGPU_IFF_MAX_CHUNKS   4096u
+#define OHGPU_IFF_MAX_CHANNELS 10u
+#define OHGPU_IFF_MAX_FRAME_BYTES 40u      /* OHGPU_IFF_MAX_CHANNELS x 4 */
+#define OHGPU_IFF_FLAG_WAV8_UNSIGNED 1u    /* 8-bit WAV: xor every byte with 0x80 (unsigned to signed) */
+
+typedef struct ohgpu_iff_stream_desc {   /* 64 bytes */
+    uint64_t src_offset;            /* the file's bytes are [src_offset, + src_bytes) of the source arena, any address */
+    uint32_t src_bytes;             /* < 2^31: the whole file or a prefix of it */
+    uint32_t flags;                 /* OHGPU_IFF_FLAG_* */
+    uint64_t dst_offset;            /* the PCM goes to [dst_offset, + n x the output frame's bytes) of the destination arena, any address */
+    uint64_t dst_bytes_capacity;    /* the stream's room there, <= dst_frame_capacity x OHGPU_IFF_MAX_FRAME_BYTES: the frame's size is
+                                       not known before the walk, so the caller states the room and the device keeps n inside it */
+    uint64_t frame_first;           /* the first frame to convert (a seek) */
+    uint32_t dst_frame_capacity;    /* frames at most */
+    uint32_t max_bit_depth;         /* 24 or 32: iController->MaxBitDepth() */
+    uint32_t reserved[4];           /* zero */
+} ohgpu_iff_stream_desc;
+
+typedef struct ohgpu_iff_stream_result {   /* 80 bytes */
+    uint32_t status;                /* OHGPU_IFF_OK ... _UNSUPPORTED */
+    uint32_t kind;                  /* OHGPU_IFF_KIND_* */
+    uint32_t channels;
+    uint32_t sample_rate;
+    uint32_t src_bit_depth;         /* 8, 16, 24 (20 too) or 32 */
+    uint32_t out_bit_depth;         /* min(src_bit_depth, max_bit_depth) */
+    uint32_t src_endian;            /* OHGPU_ENDIAN_*: the file's */
+    uint32_t bit_rate;
+    uint64_t frames_total;          /* as the file states them; 0: a continuous stream */
+    uint64_t frames_available;      /* whole frames inside src_bytes */
+    uint64_t frames_written;        /* n */
+    uint64_t data_offset;           /* the first audio byte, from src_offset */
+    uint64_t data_bytes;            /* the audio as the file states it (a continuous stream: what there is) */
+    uint64_t error_offset;          /* the chunk that gave a status other than OK, from src_offset */
+} ohgpu_iff_stream_result;
+
+/* Host only, no device needed: the validation ohgpu_iff_batch_create makes.  OHGPU_ERR_INVALID: non-zero reserved words, unknown flags,
+ * max_bit_depth other than 24 or 32, src_bytes >= 2^31, dst_bytes_capacity above dst_frame_capacity x OHGPU_IFF_MAX_FRAME_BYTES,
+ * destination ranges [dst_offset, + dst_bytes_capacity) that overlap.  OHGPU_ERR_BOUNDS: a range outside its arena.  The empty batch
+ * is legal. */
+int ohgpu_iff_batch_check(const ohgpu_iff_stream_desc* descs, size_t n, uint64_t src_arena_bytes, uint64_t dst_arena_bytes);
+/* The descriptors go to the device; the list of the conversion's workgroups (from dst_bytes_capacity), the walk's records and the
+ * results are the batch's.  Created under ohgpu_set_kernel_variant(1) the batch takes the plain route: one launch, a lane per stream
+ * runs the walk and a byte-wise conversion (ohgpu_batch_paths_info: iff_route).  Both routes write the same bytes.  Freed with
+ * ohgpu_batch_destroy. */
+int ohgpu_iff_batch_create(ohgpu_ctx* ctx, const ohgpu_iff_stream_desc* descs, size_t n, uint64_t src_arena_bytes, uint64_t dst_arena_bytes, ohgpu_batch** batch);
+/* Walk, convert: queued on the stream, nothing waits for the host.  The walk reads a stream as the aligned 4-byte words that hold its
+ * bytes, as ohgpu_mp4_batch_run does: src_base must be a multiple of 4 and the arena's allocation must end on a multiple of 4 (any
+ * hipMalloc block does).  The conversion loads only words that lie whole inside the stream and stores whole 16-byte lines of the
+ * destination, with byte stores at a run's two ends.  The batch owns its records: it runs on one stream at a time.  A second run,
+ * and a second batch of the same shape, allocate nothing on the device (ohgpu_device_allocations). */
+int ohgpu_iff_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* src_base, void* dst_base, void* stream);
+/* The last run's results, n = the batch's stream count (waits for that run). */
+int ohgpu_iff_batch_results(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_iff_stream_result* results, size_t n);
+/* The last run's phases in milliseconds from device events: walk, convert (waits for that run).  The plain route is one phase: the
+ * second reads 0. */
+int ohgpu_iff_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float ms[2]);
+/* Host-buffer convenience: one upload, one run, the results and, of dst_host, the frames_written frames of every OK stream home.
+ * `results` may be NULL. */
+int ohgpu_iff_process_host(ohgpu_ctx* ctx, const ohgpu_iff_stream_desc* descs, size_t n, const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes,
+                           ohgpu_iff_stream_result* results);
 
 /* ---- sample-rate converter (own specification; DESIGN.md "Resampler") ---- */
 /* Host-side filter design: Kaiser-windowed sinc, Q28 coefficients, coef_q28[p*T + k] = h[p + k*L].

@@ -170,6 +170,17 @@ MP4_STREAM_RESULT = np.dtype([("status", "<u4"), ("codec", "<u4"), ("config", AL
                               ("mdat_bytes", "<u8"), ("error_offset", "<u8")], align=False)
 MP4_SAMPLE = np.dtype([("first_frame", "<u8"), ("frames", "<u4"), ("chunk", "<u4")], align=False)
 assert MP4_STREAM_DESC.itemsize == 32 and MP4_STREAM_RESULT.itemsize == 112 and MP4_SAMPLE.itemsize == 16
+# PCM files: ohgpu_iff_stream_desc (64 B), ohgpu_iff_stream_result (80 B)
+IFF_OK, IFF_NOT_IFF, IFF_TRUNCATED, IFF_INVALID, IFF_UNSUPPORTED = range(5)
+IFF_KIND_WAV, IFF_KIND_AIFF, IFF_KIND_AIFC = 1, 2, 3
+IFF_MAX_CHUNKS, IFF_MAX_CHANNELS, IFF_MAX_FRAME_BYTES, IFF_FLAG_WAV8_UNSIGNED = 4096, 10, 40, 1
+IFF_ROUTE_FUSED, IFF_ROUTE_PLAIN = 1, 2
+IFF_STREAM_DESC = np.dtype([("src_offset", "<u8"), ("src_bytes", "<u4"), ("flags", "<u4"), ("dst_offset", "<u8"), ("dst_bytes_capacity", "<u8"),
+                            ("frame_first", "<u8"), ("dst_frame_capacity", "<u4"), ("max_bit_depth", "<u4"), ("reserved", "<u4", (4,))], align=False)
+IFF_STREAM_RESULT = np.dtype([("status", "<u4"), ("kind", "<u4"), ("channels", "<u4"), ("sample_rate", "<u4"), ("src_bit_depth", "<u4"), ("out_bit_depth", "<u4"),
+                              ("src_endian", "<u4"), ("bit_rate", "<u4"), ("frames_total", "<u8"), ("frames_available", "<u8"), ("frames_written", "<u8"),
+                              ("data_offset", "<u8"), ("data_bytes", "<u8"), ("error_offset", "<u8")], align=False)
+assert IFF_STREAM_DESC.itemsize == 64 and IFF_STREAM_RESULT.itemsize == 80
 
 # every symbol of include/ohgpu.h: name -> (restype, argtypes)
 _vp, _vpp = C.c_void_p, C.POINTER(C.c_void_p)
@@ -266,6 +277,12 @@ SYMBOLS = {
     "ohgpu_mp4_process_host": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, _vp, _vp]),
     "ohgpu_mp4_seek": (C.c_int, [_vp, C.c_size_t, C.c_uint64, _u64p, _u64p]),
     "ohgpu_mp4_alac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
+    "ohgpu_iff_batch_check": (C.c_int, [_vp, C.c_size_t, C.c_uint64, C.c_uint64]),
+    "ohgpu_iff_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
+    "ohgpu_iff_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "ohgpu_iff_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_iff_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
+    "ohgpu_iff_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),
     "ohgpu_ogg_crc": (C.c_uint32, [_vp, C.c_size_t]),
     "ohgpu_ogg_flac_head": (C.c_int, [_vp, C.c_size_t, _vp, C.POINTER(C.c_uint32), _u64p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "ohgpu_ogg_flac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp,
@@ -572,6 +589,18 @@ def mp4_seek(samples, frame):
     return int(index.value), int(first.value)
 
 
+def _iff_descs(descs):
+    d = np.ascontiguousarray(descs)
+    assert d.dtype == IFF_STREAM_DESC
+    return d
+
+
+def iff_batch_check(descs, src_arena_bytes, dst_arena_bytes):
+    """The validation of ctx.iff_batch without a device (ohgpu_iff_batch_check): OhGpuError on a bad descriptor."""
+    d = _iff_descs(descs)
+    check(lib().ohgpu_iff_batch_check(_ptr_or_none(d), d.size, src_arena_bytes, dst_arena_bytes))
+
+
 def _raop_tables(descs, packets):
     d, p = np.ascontiguousarray(descs), np.ascontiguousarray(packets)
     assert d.dtype == RAOP_STREAM_DESC and p.dtype == ALAC_PACKET
@@ -722,6 +751,7 @@ class Context:
         out = {k: int(v[k][0]) for k in BATCH_PATHS.names if k != "reserved"}
         out["alac_route"] = int(v["reserved"][0][0])        # (the header's union: the last word)
         out["mp4_route"] = out["alac_route"]                 # (the same word: a batch is of one kind)
+        out["iff_route"] = out["alac_route"]
         return out
 
     def pcm_process_host(self, descs, src, dst):
@@ -1049,6 +1079,35 @@ class Context:
         check(lib().ohgpu_mp4_alac_process_host(self._h, _ptr_or_none(m), _ptr_or_none(a), m.size, n_packets, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst), dst.nbytes,
                                                 _ptr_or_none(res), _ptr_or_none(pk), _ptr_or_none(sm), _ptr_or_none(ares), _ptr_or_none(pres)))
         return res, pk, sm, ares, pres
+
+    def iff_batch(self, descs, src_arena_bytes, dst_arena_bytes):
+        d = _iff_descs(descs)
+        b = C.c_void_p()
+        check(lib().ohgpu_iff_batch_create(self._h, _ptr_or_none(d), d.size, src_arena_bytes, dst_arena_bytes, C.byref(b)))
+        return b
+
+    def iff_run(self, batch, d_src, d_dst, stream=None):
+        """Walk, convert (ohgpu_iff_batch_run): queued on the stream."""
+        check(lib().ohgpu_iff_batch_run(self._h, batch, d_src, d_dst, stream))
+
+    def iff_results(self, batch, n):
+        """The last run's IFF_STREAM_RESULT per stream; waits for the run."""
+        res = np.zeros(n, dtype=IFF_STREAM_RESULT)
+        check(lib().ohgpu_iff_batch_results(self._h, batch, _ptr_or_none(res), n))
+        return res
+
+    def iff_phase_ms(self, batch):
+        """The last run's (walk, convert) in milliseconds, from device events; the plain route: (all of it, 0)."""
+        ms = (C.c_float * 2)()
+        check(lib().ohgpu_iff_batch_phase_ms(self._h, batch, ms))
+        return tuple(float(v) for v in ms)
+
+    def iff_process_host(self, descs, src, dst):
+        """File bytes in, big-endian PCM into dst (ohgpu_iff_process_host); returns the stream results."""
+        d = _iff_descs(descs)
+        res = np.zeros(d.size, dtype=IFF_STREAM_RESULT)
+        check(lib().ohgpu_iff_process_host(self._h, _ptr_or_none(d), d.size, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst), dst.nbytes, _ptr_or_none(res)))
+        return res
 
     def src_create(self, L, M, T, coef_q28):
         c = np.ascontiguousarray(coef_q28, dtype=np.int32)

@@ -308,8 +308,9 @@ static const struct { const char* noun; void (*release)(ohgpu_ctx*, ohgpu_batch*
     {"Songcast receiver", ohm_rx_free, false},    // kBatchOhmRx
     {"Ogg", ogg_free, false},                     // kBatchOgg
     {"MPEG-4", mp4_free, false},                  // kBatchMp4
+    {"PCM file", iff_free, false},                // kBatchIff
 };
-static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchMp4 + 1, "a row per BatchKind");
+static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchIff + 1, "a row per BatchKind");
 
 int run_guard(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, BatchKind kind, bool empty, bool null_src_ok,
               const void* src_base, const void* dst_base)
@@ -620,7 +621,11 @@ int ohgpu_batch_paths_info(const ohgpu_batch* b, ohgpu_batch_paths* out)
         out->mp4_route = b->mp4 && b->mp4->plain ? 2u : 1u;
         return OHGPU_OK;
     }
-    if (b->kind != kBatchOhm) return set_error(OHGPU_ERR_INVALID, "ohgpu_batch_paths_info: not a pcm, Songcast frame, fmt, Apple Lossless or MPEG-4 batch");
+    if (b->kind == kBatchIff) {
+        out->iff_route = b->iff && b->iff->plain ? 2u : 1u;
+        return OHGPU_OK;
+    }
+    if (b->kind != kBatchOhm) return set_error(OHGPU_ERR_INVALID, "ohgpu_batch_paths_info: not a pcm, Songcast frame, fmt, Apple Lossless, MPEG-4 or PCM file batch");
     const OhmPlan& p = b->ohm;
     if (p.direct) add_line_paths(p.direct->line, out);
     out->ohm_wide_fragments = p.n_selr;

@@ -21,6 +21,7 @@
 #include "flac_frame_core.h"
 #include "ogg_page_core.h"
 #include "mp4_box_core.h"
+#include "iff_chunk_core.h"
 #include "ohm_rx_core.h"
 #include "raop_aes_core.h"
 
@@ -483,7 +484,28 @@ static_assert(sizeof(ohgpu_mp4_stream_desc) == sizeof(mp4box::Stream) && sizeof(
               sizeof(ohgpu_alac_packet) == sizeof(mp4box::Row) && sizeof(ohgpu_alac_config) == sizeof(mp4box::Config) && offsetof(ohgpu_mp4_stream_result, error_offset) == offsetof(mp4box::Result, error_offset) &&
               offsetof(ohgpu_mp4_stream_result, first_bad_sample) == offsetof(mp4box::Result, first_bad_sample), "MPEG-4 layouts");
 
-enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11, kBatchOhmRx = 12, kBatchOgg = 13, kBatchMp4 = 14 };
+// ---- PCM files (csrc/iff_pcm_kernel.hip): the descriptors, the list of the conversion's workgroups, the walk's record
+// of each stream's run and the results of the last run.  The batch's d_descs holds nothing.
+constexpr uint32_t kIffGroupPieces = 1024;            // the pieces one workgroup of the conversion takes: tests/test_gpu_iff_textbook.py restates it
+struct IffGroup { uint32_t stream, group; };          // one workgroup's share: pieces [group x kIffGroupPieces, + kIffGroupPieces) of a stream's run
+struct IffState {
+    size_t n_streams = 0;
+    uint32_t n_groups = 0;
+    bool plain = false;                               // created under kernel variant 1: one launch, a lane per stream
+    void* d_streams = nullptr;                        // iffchunk::Stream[n_streams]
+    void* d_results = nullptr;                        // iffchunk::Result[n_streams]
+    void* d_recs = nullptr;                           // iffchunk::Rec[n_streams]
+    void* d_groups = nullptr;                         // IffGroup[n_groups]
+    hipEvent_t ev[3] = {};
+    hipStream_t last_stream = nullptr;
+    bool ran = false;
+};
+static_assert(sizeof(ohgpu_iff_stream_desc) == sizeof(iffchunk::Stream) && sizeof(ohgpu_iff_stream_result) == sizeof(iffchunk::Result) &&
+              offsetof(ohgpu_iff_stream_desc, max_bit_depth) == offsetof(iffchunk::Stream, max_bit_depth) &&
+              offsetof(ohgpu_iff_stream_result, error_offset) == offsetof(iffchunk::Result, error_offset) &&
+              offsetof(ohgpu_iff_stream_result, frames_written) == offsetof(iffchunk::Result, frames_written), "IFF layouts");
+
+enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11, kBatchOhmRx = 12, kBatchOgg = 13, kBatchMp4 = 14, kBatchIff = 15 };
 
 }  // namespace ohgpu
 
@@ -593,6 +615,7 @@ struct ohgpu_batch {
     ohgpu::OhmRxState* ohmrx = nullptr; // kBatchOhmRx only
     ohgpu::OggState* ogg = nullptr;     // kBatchOgg only
     ohgpu::Mp4State* mp4 = nullptr;     // kBatchMp4 only
+    ohgpu::IffState* iff = nullptr;     // kBatchIff only
     void*    d_pull_tiles = nullptr;   // kBatchSrcPull: PullTile[n_pull_tiles] on the device (d_descs holds the messages)
     uint32_t n_pull_tiles = 0;
     // kBatchSrc whose messages differ in layout: one uniform batch per layout (each with its own block-kernel plan), run one
@@ -627,7 +650,7 @@ inline int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? OHGPU_ERR_
         if (e_ != hipSuccess) return ::ohgpu::set_error(::ohgpu::hip_code(e_), "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-// The release functions (free_pcm_line, free_fmt_line, free_dsd_line, flac_free, alac_free, raop_free, free_flywheel, free_src_fast, free_ohm, ohm_rx_free, ogg_free, mp4_free): what
+// The release functions (free_pcm_line, free_fmt_line, free_dsd_line, flac_free, alac_free, raop_free, free_flywheel, free_src_fast, free_ohm, ohm_rx_free, ogg_free, mp4_free, iff_free): what
 // ohgpu_batch_destroy's table calls (csrc/ohgpu_api.hip).  Each takes a PARTLY BUILT batch -- null pointers, a plan that was never
 // made -- and leaves the plan reset: a create that fails at any point hands its batch to ohgpu_batch_destroy and returns.
 // kernels
@@ -684,6 +707,10 @@ uint32_t ogg_wave_blocks(uint64_t items, uint32_t cus);   // the verify and gath
 int  mp4_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const mp4box::Stream* streams);   // tiles, carries and tables onto the device (b->mp4 holds the counts)
 void mp4_free(ohgpu_ctx* ctx, ohgpu_batch* b);
 int  mp4_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, hipStream_t s);
+// csrc/iff_pcm_kernel.hip.  No launch is persistent: a lane a stream (walk), a workgroup per kIffGroupPieces pieces of a run (convert).
+int  iff_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const iffchunk::Stream* streams);   // the descriptors and the workgroup list onto the device
+void iff_free(ohgpu_ctx* ctx, ohgpu_batch* b);
+int  iff_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
 // csrc/ohm_frame_kernel.hip: the two wire channels of streams wider than stereo (Sender::DoProcessFragment), one record per fragment
 OhmSelRec wide_record(uint64_t src_off, uint64_t dst_off, uint32_t n_frames, uint32_t channels, uint32_t sb, bool little, uint64_t src_arena_bytes);
 hipError_t launch_ohm_wide(const ohgpu_ctx* ctx, const void* d_recs, uint32_t n_recs, const uint8_t* src, uint8_t* dst, const uint8_t* prefix, hipStream_t s);
