@@ -1247,7 +1247,12 @@ int ohgpu_src_batch_create(ohgpu_ctx* ctx, const ohgpu_src* src, const ohgpu_src
 /* A batch may be run any number of times, one launch at a time (it owns device-side work counters): launches of the same
  * batch on one stream queue behind each other; a launch on ANOTHER stream while the previous one has not finished returns
  * OHGPU_ERR_INVALID (nothing is launched).  Different batches are independent.  The same holds for
- * ohgpu_flywheel_batch_run (the batch owns Burg's workspace). */
+ * ohgpu_flywheel_batch_run (the batch owns Burg's workspace).
+ * The decoders' and demultiplexers' batches (ohgpu_flac_, _alac_, _raop_, _ohm_rx_, _ogg_, _mp4_ and _iff_batch_run) keep records of
+ * their own -- counters, candidate and piece lists, tables, results, scratch -- which serve ONE RUN AT A TIME too, but these runs never
+ * refuse a stream: a run on another stream than the batch's last run first WAITS ON THE HOST for that run, then proceeds.  It waits on
+ * what the batch itself recorded at that run's end, never on the earlier stream, which may have been synchronised and destroyed by
+ * then.  Runs on one stream queue behind each other without a wait; the results and tables are those of the last run. */
 int ohgpu_src_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* src_base, void* dst_base, void* stream);
 /* The same with two events of the caller's (ohgpu_event_create) that bracket the batch's device work on `stream`: a batch that is one
  * launch of the workgroup matrix kernel carries them ON ITS DISPATCH (hipExtLaunchKernelGGL: the dispatch's own start and end

@@ -17,7 +17,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "ohgpu_internal.h"
+#include "api_common.h"
 
 namespace ohgpu {
 
@@ -138,8 +138,7 @@ void alac_free(ohgpu_ctx* ctx, ohgpu_batch* b)
 int alac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s)
 {
     AlacState& a = *b->alac;
-    if (a.last_stream && a.last_stream != s) OHGPU_HIP_TRY_ALLOC(hipStreamSynchronize(a.last_stream));
-    a.last_stream = s;
+    if (const int err = run_begin(a, a.ev[3], s)) return err;
     a.ran = true;
     const uint32_t np = (uint32_t)a.packets.size();
     const Stream* streams = (const Stream*)a.d_streams;
@@ -170,8 +169,7 @@ int alac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
                            (const PacketOut*)outs, (const Chan*)chans, (const int32_t*)rows, group_base, src, dst);
         OHGPU_HIP_TRY_ALLOC(hipGetLastError());
     }
-    OHGPU_HIP_TRY_ALLOC(hipEventRecord(a.ev[3], s));
-    return OHGPU_OK;
+    return run_end(a, a.ev[3], s);
 }
 
 int alac_results(ohgpu_ctx* ctx, const ohgpu_batch* b, ohgpu_alac_packet_result* out)

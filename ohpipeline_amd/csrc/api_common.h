@@ -75,6 +75,26 @@ int run_guard(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, BatchKi
 // Batches with per-launch device state (ohgpu_batch::last_done): a launch on another stream while the last one runs is refused.
 int claim_single_launch(const ohgpu_batch* b, hipStream_t s, const char* who);
 inline void launched(const ohgpu_batch* b, hipStream_t s) { b->last_untracked = false; if (b->last_done) (void)hipEventRecord(b->last_done, s); }
+// Batches whose device records serve ONE RUN AT A TIME and whose runs never refuse a stream (FlacState, AlacState -- RAOP's too --,
+// OhmRxState, OggState, Mp4State, IffState: last_stream, ended, the end-of-run event): run_begin is the first line of the family's
+// run, run_end its last.  A run on another stream than the last one's first waits, on the host, for the last run -- on the EVENT that
+// run recorded at its end, never on its stream, which the caller may have destroyed since; a run that returned an error half way
+// recorded no end, and the whole device is waited for instead.  A run on the same stream queues behind the last one by itself.
+template <typename State>
+inline int run_begin(State& st, hipEvent_t end, hipStream_t s)
+{
+    if (st.last_stream && st.last_stream != s) OHGPU_HIP_TRY(st.ended ? hipEventSynchronize(end) : hipDeviceSynchronize());
+    st.last_stream = s;
+    st.ended = false;
+    return OHGPU_OK;
+}
+template <typename State>
+inline int run_end(State& st, hipEvent_t end, hipStream_t s)
+{
+    OHGPU_HIP_TRY(hipEventRecord(end, s));
+    st.ended = true;
+    return OHGPU_OK;
+}
 // An ohgpu_*_batch_phase_ms behind its argument check: ms[k] = the time from events[k] to events[k + 1], k < count (waits for the last)
 inline int phase_ms(const char* who, bool ran, const hipEvent_t* events, int count, float* ms)
 {

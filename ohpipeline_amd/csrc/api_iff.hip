@@ -73,7 +73,7 @@ int ohgpu_iff_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* sr
     if (err != OHGPU_OK) return err;
     if (batch->iff->n_streams == 0) return OHGPU_OK;
     if (!src_base && batch->src_bytes_touched) return set_error(OHGPU_ERR_INVALID, "ohgpu_iff_batch_run: null arena pointer");
-    if (!dst_base && batch->iff->n_groups) return set_error(OHGPU_ERR_INVALID, "ohgpu_iff_batch_run: null arena pointer");
+    if (!dst_base && batch->iff->writes) return set_error(OHGPU_ERR_INVALID, "ohgpu_iff_batch_run: null arena pointer");
     return iff_run(ctx, batch, (const uint8_t*)src_base, (uint8_t*)dst_base, pick_stream(ctx, stream));
 }
 

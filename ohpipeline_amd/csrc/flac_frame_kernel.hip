@@ -16,7 +16,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "ohgpu_internal.h"
+#include "api_common.h"
 
 namespace ohgpu {
 
@@ -186,8 +186,7 @@ int flac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
 {
     FlacState& f = *b->flac;
     const size_t n = f.streams.size();
-    if (f.last_stream && f.last_stream != s) OHGPU_HIP_TRY_ALLOC(hipStreamSynchronize(f.last_stream));
-    f.last_stream = s;
+    if (const int err = run_begin(f, f.ev[4], s)) return err;
     f.ran = true;
     f.n_candidates = 0;
     const Tables* tables = (const Tables*)f.d_tables;
@@ -295,8 +294,7 @@ int flac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
         }
         OHGPU_HIP_TRY_ALLOC(hipGetLastError());
     }
-    OHGPU_HIP_TRY_ALLOC(hipEventRecord(f.ev[4], s));
-    return OHGPU_OK;
+    return run_end(f, f.ev[4], s);
 }
 
 int flac_results(ohgpu_ctx* ctx, const ohgpu_batch* b, ohgpu_flac_stream_result* out)

@@ -13,7 +13,7 @@
 // [dst_offset, + dst_bytes_capacity), which the same check placed inside the destination arena and apart from every other stream's.
 #include <hip/hip_runtime.h>
 
-#include "ohgpu_internal.h"
+#include "api_common.h"
 
 namespace ohgpu {
 
@@ -69,6 +69,7 @@ int iff_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Stream* streams)
     for (hipEvent_t& e : g.ev) OHGPU_HIP_TRY_ALLOC(hipEventCreate(&e));
     if (!g.n_streams) return OHGPU_OK;
     std::vector<IffGroup> groups;
+    for (size_t i = 0; i < g.n_streams; i++) g.writes = g.writes || streams[i].dst_bytes_capacity != 0u;
     if (!g.plain)
         for (size_t i = 0; i < g.n_streams; i++) {
             // a run has no more than dst_bytes_capacity / 16 pieces; its first workgroup is there for the edges of a run without pieces
@@ -101,8 +102,7 @@ void iff_free(ohgpu_ctx* ctx, ohgpu_batch* b)
 int iff_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s)
 {
     IffState& g = *b->iff;
-    if (g.last_stream && g.last_stream != s) OHGPU_HIP_TRY_ALLOC(hipStreamSynchronize(g.last_stream));      // (the records serve one run at a time)
-    g.last_stream = s;
+    if (const int err = run_begin(g, g.ev[2], s)) return err;      // (the records serve one run at a time)
     g.ran = true;
     const uint32_t ns = (uint32_t)g.n_streams, lane_blocks = (ns + 63u) / 64u;
     const Stream* const streams = (const Stream*)g.d_streams;
@@ -110,8 +110,8 @@ int iff_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* d
     if (g.plain) {
         hipLaunchKernelGGL(iff_plain_kernel, dim3(lane_blocks), dim3(64), 0, s, streams, ns, src, dst, (Result*)g.d_results, (Rec*)g.d_recs);
         OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-        for (int k = 1; k < 3; k++) OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[k], s));
-        return OHGPU_OK;
+        OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[1], s));
+        return run_end(g, g.ev[2], s);
     }
     hipLaunchKernelGGL(iff_walk_kernel, dim3(lane_blocks), dim3(64), 0, s, streams, ns, src, (Result*)g.d_results, (Rec*)g.d_recs);
     OHGPU_HIP_TRY_ALLOC(hipGetLastError());
@@ -120,8 +120,7 @@ int iff_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* d
         hipLaunchKernelGGL(iff_convert_kernel, dim3(g.n_groups), dim3(kIffThreads), 0, s, streams, (const Rec*)g.d_recs, (const IffGroup*)g.d_groups, src, dst);
         OHGPU_HIP_TRY_ALLOC(hipGetLastError());
     }
-    OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[2], s));
-    return OHGPU_OK;
+    return run_end(g, g.ev[2], s);
 }
 
 }  // namespace ohgpu

@@ -18,7 +18,7 @@
 // stream's rows [packet_first, + min(N, packet_capacity)), its carries (sized at create from packet_capacity) or its own records.
 #include <hip/hip_runtime.h>
 
-#include "ohgpu_internal.h"
+#include "api_common.h"
 
 namespace ohgpu {
 
@@ -259,8 +259,7 @@ void mp4_free(ohgpu_ctx* ctx, ohgpu_batch* b)
 int mp4_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, hipStream_t s)
 {
     Mp4State& g = *b->mp4;
-    if (g.last_stream && g.last_stream != s) OHGPU_HIP_TRY_ALLOC(hipStreamSynchronize(g.last_stream));      // (the tables serve one run at a time)
-    g.last_stream = s;
+    if (const int err = run_begin(g, g.ev[4], s)) return err;      // (the tables serve one run at a time)
     g.ran = true;
     const uint32_t ns = (uint32_t)g.n_streams, lane_blocks = (ns + 63u) / 64u;
     const Stream* const streams = (const Stream*)g.d_streams;
@@ -270,8 +269,8 @@ int mp4_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, hipStream_
     if (g.plain) {
         hipLaunchKernelGGL(mp4_plain_kernel, dim3(lane_blocks), dim3(64), 0, s, streams, ns, src, results, tables, (Row*)g.d_packets, (Sample*)g.d_samples);
         OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-        for (int k = 1; k < 5; k++) OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[k], s));
-        return OHGPU_OK;
+        for (int k = 1; k < 4; k++) OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[k], s));
+        return run_end(g, g.ev[4], s);
     }
     hipLaunchKernelGGL(mp4_walk_kernel, dim3(lane_blocks), dim3(64), 0, s, streams, ns, src, results, tables);
     OHGPU_HIP_TRY_ALLOC(hipGetLastError());
@@ -295,8 +294,7 @@ int mp4_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, hipStream_
     }
     hipLaunchKernelGGL(mp4_finish_kernel, dim3(lane_blocks), dim3(64), 0, s, (const Tables*)tables, ns, results);
     OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-    OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[4], s));
-    return OHGPU_OK;
+    return run_end(g, g.ev[4], s);
 }
 
 }  // namespace ohgpu

@@ -16,7 +16,7 @@
 // aligned); every store lies inside [dst_offset, + bytes delivered), and dst_capacity >= src_bytes bounds that.
 #include <hip/hip_runtime.h>
 
-#include "ohgpu_internal.h"
+#include "api_common.h"
 
 namespace ohgpu {
 
@@ -145,6 +145,7 @@ int ogg_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Stream* streams)
     OHGPU_HIP_TRY_ALLOC(hipMemcpy(g.d_tables, &tables, sizeof(Tables), hipMemcpyHostToDevice));
     if (g.n_tiles) OHGPU_HIP_TRY_ALLOC(hipMemcpy(g.d_tiles, tiles.data(), g.n_tiles * sizeof(OggTile), hipMemcpyHostToDevice));
     if (g.n_packets) OHGPU_HIP_TRY_ALLOC(hipMemset(g.d_packets, 0, g.n_packets * sizeof(Packet)));
+    OHGPU_HIP_TRY_ALLOC(hipStreamSynchronize(nullptr));                // (the fill is queued: a run on another stream must not meet it)
     return OHGPU_OK;
 }
 
@@ -162,8 +163,7 @@ void ogg_free(ohgpu_ctx* ctx, ohgpu_batch* b)
 int ogg_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s)
 {
     OggState& g = *b->ogg;
-    if (g.last_stream && g.last_stream != s) OHGPU_HIP_TRY_ALLOC(hipStreamSynchronize(g.last_stream));      // (the lists serve one run at a time)
-    g.last_stream = s;
+    if (const int err = run_begin(g, g.ev[4], s)) return err;      // (the lists serve one run at a time)
     g.ran = true;
     const uint32_t ns = (uint32_t)g.n_streams;
     const uint32_t cus = ctx->num_cus > 0 ? (uint32_t)ctx->num_cus : 256u;
@@ -192,8 +192,7 @@ int ogg_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* d
                            (const uint32_t*)g.d_work, (const uint32_t*)g.d_counters, src, dst);
         OHGPU_HIP_TRY_ALLOC(hipGetLastError());
     }
-    OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[4], s));
-    return OHGPU_OK;
+    return run_end(g, g.ev[4], s);
 }
 
 }  // namespace ohgpu

@@ -361,7 +361,7 @@ struct FlacState {
     std::vector<uint32_t> host_list;
     hipEvent_t ev[5] = {};
     hipStream_t last_stream = nullptr;
-    bool ran = false;
+    bool ran = false, ended = false;      // (ended: the last run recorded its end -- run_begin, api_common.h)
     uint32_t n_candidates = 0;
 };
 
@@ -380,7 +380,7 @@ struct AlacState {
     void* d_rows = nullptr; size_t rows_bytes = 0;    // int32, the groups one after the other
     hipEvent_t ev[4] = {};
     hipStream_t last_stream = nullptr;
-    bool ran = false;
+    bool ran = false, ended = false;      // (ended: the last run recorded its end -- run_begin, api_common.h)
 };
 static_assert(sizeof(ohgpu_alac_config) == 24 && sizeof(ohgpu_alac_packet) == 16 && sizeof(ohgpu_alac_stream_desc) == 64 && sizeof(ohgpu_alac_stream_result) == 16 && sizeof(ohgpu_alac_packet_result) == 8, "Apple Lossless layouts");
 static_assert(sizeof(alaccore::Stream) == 48 && sizeof(alaccore::Packet) == 32 && sizeof(alaccore::Chan) == 80 && sizeof(alaccore::PacketOut) == sizeof(ohgpu_alac_packet_result), "Apple Lossless device layouts");
@@ -426,7 +426,7 @@ struct OhmRxState {
     void* d_rings = nullptr;                          // uint32[n_streams][ohmrx::kRing]
     hipEvent_t ev[4] = {};
     hipStream_t last_stream = nullptr;
-    bool ran = false;
+    bool ran = false, ended = false;      // (ended: the last run recorded its end -- run_begin, api_common.h)
 };
 static_assert(sizeof(ohgpu_ohm_rx_datagram) == sizeof(ohmrx::Datagram) && sizeof(ohgpu_ohm_rx_state) == sizeof(ohmrx::State) && sizeof(ohgpu_ohm_rx_stream) == sizeof(ohmrx::Stream) &&
               sizeof(ohgpu_ohm_rx_record) == sizeof(ohmrx::Record) && sizeof(ohgpu_ohm_rx_stream_result) == sizeof(ohmrx::StreamResult), "Songcast receiver layouts");
@@ -453,7 +453,7 @@ struct OggState {
     void* d_packets = nullptr;                        // oggpage::Packet[n_packets]
     hipEvent_t ev[5] = {};
     hipStream_t last_stream = nullptr;
-    bool ran = false;
+    bool ran = false, ended = false;      // (ended: the last run recorded its end -- run_begin, api_common.h)
 };
 static_assert(sizeof(ohgpu_ogg_stream_desc) == sizeof(oggpage::Stream) && sizeof(ohgpu_ogg_stream_result) == sizeof(oggpage::Result) && sizeof(ohgpu_ogg_packet) == sizeof(oggpage::Packet), "Ogg layouts");
 
@@ -478,7 +478,7 @@ struct Mp4State {
     void* d_samples = nullptr;                        // mp4box::Sample[n_packets]
     hipEvent_t ev[5] = {};
     hipStream_t last_stream = nullptr;
-    bool ran = false;
+    bool ran = false, ended = false;      // (ended: the last run recorded its end -- run_begin, api_common.h)
 };
 static_assert(sizeof(ohgpu_mp4_stream_desc) == sizeof(mp4box::Stream) && sizeof(ohgpu_mp4_stream_result) == sizeof(mp4box::Result) && sizeof(ohgpu_mp4_sample) == sizeof(mp4box::Sample) &&
               sizeof(ohgpu_alac_packet) == sizeof(mp4box::Row) && sizeof(ohgpu_alac_config) == sizeof(mp4box::Config) && offsetof(ohgpu_mp4_stream_result, error_offset) == offsetof(mp4box::Result, error_offset) &&
@@ -492,13 +492,14 @@ struct IffState {
     size_t n_streams = 0;
     uint32_t n_groups = 0;
     bool plain = false;                               // created under kernel variant 1: one launch, a lane per stream
+    bool writes = false;                              // some stream has room in the destination arena: either route needs the arena
     void* d_streams = nullptr;                        // iffchunk::Stream[n_streams]
     void* d_results = nullptr;                        // iffchunk::Result[n_streams]
     void* d_recs = nullptr;                           // iffchunk::Rec[n_streams]
     void* d_groups = nullptr;                         // IffGroup[n_groups]
     hipEvent_t ev[3] = {};
     hipStream_t last_stream = nullptr;
-    bool ran = false;
+    bool ran = false, ended = false;      // (ended: the last run recorded its end -- run_begin, api_common.h)
 };
 static_assert(sizeof(ohgpu_iff_stream_desc) == sizeof(iffchunk::Stream) && sizeof(ohgpu_iff_stream_result) == sizeof(iffchunk::Result) &&
               offsetof(ohgpu_iff_stream_desc, max_bit_depth) == offsetof(iffchunk::Stream, max_bit_depth) &&

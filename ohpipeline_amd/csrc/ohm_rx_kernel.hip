@@ -14,7 +14,7 @@
 // run, which the same check sized from the table alone (the sum of max(bytes - 58, 0) bounds any parse's audio).
 #include <hip/hip_runtime.h>
 
-#include "ohgpu_internal.h"
+#include "api_common.h"
 
 namespace ohgpu {
 
@@ -90,8 +90,7 @@ void ohm_rx_free(ohgpu_ctx* ctx, ohgpu_batch* b)
 int ohm_rx_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s)
 {
     OhmRxState& r = *b->ohmrx;
-    if (r.last_stream && r.last_stream != s) OHGPU_HIP_TRY_ALLOC(hipStreamSynchronize(r.last_stream));      // (the records serve one run at a time)
-    r.last_stream = s;
+    if (const int err = run_begin(r, r.ev[3], s)) return err;      // (the records serve one run at a time)
     r.ran = true;
     const uint32_t ng = (uint32_t)r.n_datagrams, ns = (uint32_t)r.n_streams;
     const uint32_t cus = ctx->num_cus > 0 ? (uint32_t)ctx->num_cus : 256u;
@@ -111,8 +110,7 @@ int ohm_rx_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t
         hipLaunchKernelGGL(ohm_rx_gather_kernel, dim3(ohm_rx_gather_blocks(ng, cus)), dim3(kRxThreads), 0, s, (const Datagram*)r.d_datagrams, (const Record*)r.d_records, ng, src, dst);
         OHGPU_HIP_TRY_ALLOC(hipGetLastError());
     }
-    OHGPU_HIP_TRY_ALLOC(hipEventRecord(r.ev[3], s));
-    return OHGPU_OK;
+    return run_end(r, r.ev[3], s);
 }
 
 }  // namespace ohgpu

@@ -12,7 +12,7 @@
 
 #include <cstring>
 
-#include "ohgpu_internal.h"
+#include "api_common.h"
 
 namespace ohgpu {
 
@@ -77,7 +77,7 @@ int raop_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
 {
     const RaopState& r = *b->raop;
     AlacState& a = *b->alac;
-    if (a.last_stream && a.last_stream != s) OHGPU_HIP_TRY_ALLOC(hipStreamSynchronize(a.last_stream));      // (the scratch serves one run at a time)
+    if (const int err = run_begin(a, a.ev[3], s)) return err;      // (the scratch serves one run at a time)
     OHGPU_HIP_TRY_ALLOC(hipEventRecord(r.ev0, s));
     if (r.n_pieces) {
         hipLaunchKernelGGL(raop_decrypt_kernel, dim3((r.n_pieces + kRaopWaves - 1) / kRaopWaves), dim3(kRaopThreads), 0, s, (const Piece*)r.d_pieces, r.n_pieces,
