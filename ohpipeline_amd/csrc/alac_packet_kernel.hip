@@ -106,31 +106,24 @@ int alac_plan(ohgpu_ctx* ctx, ohgpu_batch* b)
     a.n_rows = (uint32_t)row_packet.size();
     a.n_groups = (uint32_t)group_base.size() - 1u;
     for (const Stream& s : a.streams) if (s.n_packets) a.max_frame_length = std::max(a.max_frame_length, s.frame_length);
-    for (hipEvent_t& e : a.ev) OHGPU_HIP_TRY_ALLOC(hipEventCreate(&e));
+    OHGPU_TRY(state_events(a, 4));
     if (a.packets.empty()) return OHGPU_OK;
     const size_t np = a.packets.size();
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &a.d_streams, a.streams.size() * sizeof(Stream)));
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &a.d_packets, np * sizeof(Packet)));
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &a.d_outs, np * sizeof(PacketOut)));
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &a.d_chans, (size_t)a.n_rows * sizeof(Chan)));
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &a.d_rowpacket, (size_t)a.n_rows * sizeof(uint32_t)));
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &a.d_groupbase, group_base.size() * sizeof(uint64_t)));
+    OHGPU_TRY(dev_array(ctx, a, &a.d_streams, a.streams.size(), a.streams.data()));
+    OHGPU_TRY(dev_array(ctx, a, &a.d_packets, np, a.packets.data()));
+    OHGPU_TRY(dev_array<PacketOut>(ctx, a, &a.d_outs, np));
+    OHGPU_TRY(dev_array<Chan>(ctx, a, &a.d_chans, a.n_rows));
+    OHGPU_TRY(dev_array(ctx, a, &a.d_rowpacket, row_packet.size(), row_packet.data()));
+    OHGPU_TRY(dev_array(ctx, a, &a.d_groupbase, group_base.size(), group_base.data()));
     a.rows_bytes = (size_t)group_base.back() * kGroupRows * sizeof(int32_t);
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &a.d_rows, a.rows_bytes));
-    OHGPU_HIP_TRY_ALLOC(hipMemcpy(a.d_streams, a.streams.data(), a.streams.size() * sizeof(Stream), hipMemcpyHostToDevice));
-    OHGPU_HIP_TRY_ALLOC(hipMemcpy(a.d_packets, a.packets.data(), np * sizeof(Packet), hipMemcpyHostToDevice));
-    OHGPU_HIP_TRY_ALLOC(hipMemcpy(a.d_rowpacket, row_packet.data(), row_packet.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    OHGPU_HIP_TRY_ALLOC(hipMemcpy(a.d_groupbase, group_base.data(), group_base.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    OHGPU_TRY(dev_array<uint8_t>(ctx, a, &a.d_rows, a.rows_bytes));
     return OHGPU_OK;
 }
 
 void alac_free(ohgpu_ctx* ctx, ohgpu_batch* b)
 {
     if (!b->alac) return;
-    AlacState& a = *b->alac;
-    (void)hipDeviceSynchronize();
-    for (void* p : {a.d_streams, a.d_packets, a.d_outs, a.d_chans, a.d_rowpacket, a.d_groupbase, a.d_rows}) ctx_dev_free(ctx, p);
-    for (hipEvent_t e : a.ev) if (e) (void)hipEventDestroy(e);
+    state_release(ctx, *b->alac);
     delete b->alac;
     b->alac = nullptr;
 }
@@ -138,8 +131,7 @@ void alac_free(ohgpu_ctx* ctx, ohgpu_batch* b)
 int alac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s)
 {
     AlacState& a = *b->alac;
-    if (const int err = run_begin(a, a.ev[3], s)) return err;
-    a.ran = true;
+    OHGPU_TRY(run_begin(a, s));
     const uint32_t np = (uint32_t)a.packets.size();
     const Stream* streams = (const Stream*)a.d_streams;
     const Packet* packets = (const Packet*)a.d_packets;
@@ -169,17 +161,14 @@ int alac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
                            (const PacketOut*)outs, (const Chan*)chans, (const int32_t*)rows, group_base, src, dst);
         OHGPU_HIP_TRY_ALLOC(hipGetLastError());
     }
-    return run_end(a, a.ev[3], s);
+    return run_end(a, s);
 }
 
 int alac_results(ohgpu_ctx* ctx, const ohgpu_batch* b, ohgpu_alac_packet_result* out)
 {
     AlacState& a = *b->alac;
     if (a.packets.empty()) return OHGPU_OK;
-    if (!a.ran) return set_error(OHGPU_ERR_INVALID, "ohgpu_alac_batch_results: the batch has not run");
-    OHGPU_HIP_TRY_ALLOC(hipEventSynchronize(a.ev[3]));
-    if (!a.packets.empty()) OHGPU_HIP_TRY_ALLOC(hipMemcpy(out, a.d_outs, a.packets.size() * sizeof(PacketOut), hipMemcpyDeviceToHost));
-    return OHGPU_OK;
+    return fetch_after_run("ohgpu_alac_batch_results", a, out, a.d_outs, a.packets.size() * sizeof(PacketOut));
 }
 
 }  // namespace ohgpu

@@ -3,6 +3,7 @@
 // ohgpu_batch_destroy's table (ohgpu_api.hip) at the end.  Nothing here is exported from the library.
 #pragma once
 
+#include <algorithm>
 #include <memory>
 #include <new>
 #include <utility>
@@ -69,30 +70,76 @@ int upload_batch(ohgpu_ctx* ctx, ohgpu_batch* b, const void* host_descs, size_t 
 
 // ---- launches.  The front of every ohgpu_*_batch_run: the context, the kind ("<who>: not a <noun> batch"), and two rules that differ
 // by family on purpose and are the caller's to state: `empty` (n == 0, no pieces, no tiles; FLAC has none) -- nothing to launch, whatever
-// the arenas; `null_src_ok` -- a batch that touches no source byte runs without one.  > 0: launch; 0: empty; < 0: refused, error set.
+// the arenas; `null_src_ok` -- a batch that touches no source byte runs without one; `needs_dst` -- false where the batch writes to no
+// destination arena (MPEG-4 never does, a PCM file batch without room for a frame does not).  > 0: launch; 0: empty; < 0: refused, error set.
 int run_guard(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, BatchKind kind, bool empty, bool null_src_ok,
-              const void* src_base, const void* dst_base);
+              const void* src_base, const void* dst_base, bool needs_dst = true);
 // Batches with per-launch device state (ohgpu_batch::last_done): a launch on another stream while the last one runs is refused.
 int claim_single_launch(const ohgpu_batch* b, hipStream_t s, const char* who);
 inline void launched(const ohgpu_batch* b, hipStream_t s) { b->last_untracked = false; if (b->last_done) (void)hipEventRecord(b->last_done, s); }
-// Batches whose device records serve ONE RUN AT A TIME and whose runs never refuse a stream (FlacState, AlacState -- RAOP's too --,
-// OhmRxState, OggState, Mp4State, IffState: last_stream, ended, the end-of-run event): run_begin is the first line of the family's
-// run, run_end its last.  A run on another stream than the last one's first waits, on the host, for the last run -- on the EVENT that
-// run recorded at its end, never on its stream, which the caller may have destroyed since; a run that returned an error half way
-// recorded no end, and the whole device is waited for instead.  A run on the same stream queues behind the last one by itself.
-template <typename State>
-inline int run_begin(State& st, hipEvent_t end, hipStream_t s)
+// ---- the batch states (RunState, ohgpu_internal.h: FlacState, AlacState -- RAOP's too --, OhmRxState, OggState, Mp4State, IffState).
+// In a plan: state_events creates the n events of the family's phases (the last is the end of a run); dev_array is a device block of
+// `count` elements from the context's block cache, entered in the state's registry, and filled from `host` (synchronously) where one is
+// given -- a zero count allocates nothing and leaves the pointer null; state_own enters a block that a run allocates.
+inline int state_events(RunState& st, int n)
 {
-    if (st.last_stream && st.last_stream != s) OHGPU_HIP_TRY(st.ended ? hipEventSynchronize(end) : hipDeviceSynchronize());
-    st.last_stream = s;
-    st.ended = false;
+    st.n_events = n;
+    for (int k = 0; k < n; k++) OHGPU_HIP_TRY_ALLOC(hipEventCreate(&st.ev[k]));
     return OHGPU_OK;
 }
-template <typename State>
-inline int run_end(State& st, hipEvent_t end, hipStream_t s)
+inline void state_own(RunState& st, void** p) { st.blocks.push_back(p); }
+template <typename T>
+inline int dev_array(ohgpu_ctx* ctx, RunState& st, void** p, size_t count, const T* host = nullptr)
 {
-    OHGPU_HIP_TRY(hipEventRecord(end, s));
+    state_own(st, p);
+    if (!count) return OHGPU_OK;
+    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, p, count * sizeof(T)));
+    if (host) OHGPU_HIP_TRY_ALLOC(hipMemcpy(*p, host, count * sizeof(T), hipMemcpyHostToDevice));
+    return OHGPU_OK;
+}
+// The whole of a family's release but `delete`: the device drained, every registered block that exists freed, every event that exists
+// destroyed.  It takes a state at any point of its plan.
+inline void state_release(ohgpu_ctx* ctx, RunState& st)
+{
+    (void)hipDeviceSynchronize();
+    for (void** p : st.blocks) if (*p) { ctx_dev_free(ctx, *p); *p = nullptr; }
+    for (hipEvent_t& e : st.ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+}
+// The device records serve ONE RUN AT A TIME, and a run never refuses a stream: run_begin is the first line of the family's run, run_end
+// its last.  A run on another stream than the last one's first waits, on the host, for the last run -- on the EVENT that run recorded
+// at its end, never on its stream, which the caller may have destroyed since; a run that returned an error half way recorded no end,
+// and the whole device is waited for instead.  A run on the same stream queues behind the last one by itself.
+inline int run_begin(RunState& st, hipStream_t s)
+{
+    if (st.last_stream && st.last_stream != s) OHGPU_HIP_TRY(st.ended ? hipEventSynchronize(st.end_event()) : hipDeviceSynchronize());
+    st.last_stream = s;
+    st.ended = false;
+    st.ran = true;
+    return OHGPU_OK;
+}
+inline int run_end(RunState& st, hipStream_t s)
+{
+    OHGPU_HIP_TRY(hipEventRecord(st.end_event(), s));
     st.ended = true;
+    return OHGPU_OK;
+}
+// What the last run left in a device block, home: "<who>: the batch has not run", the wait for the run's end, the copy.  The room for
+// it and the batch with nothing to fetch are the caller's to judge first.
+inline int fetch_after_run(const char* who, const RunState& st, void* dst, const void* d_src, size_t bytes)
+{
+    if (!st.ran) return set_error(OHGPU_ERR_INVALID, "%s: the batch has not run", who);
+    OHGPU_HIP_TRY(hipEventSynchronize(st.end_event()));
+    if (bytes) OHGPU_HIP_TRY(hipMemcpy(dst, d_src, bytes, hipMemcpyDeviceToHost));
+    return OHGPU_OK;
+}
+// (first, count) ranges of a batch check that must not overlap ("<who>: the <noun> ranges [a, +b) and [c, +d) overlap"); sorts them
+inline int ranges_disjoint(const char* who, const char* noun, std::vector<std::pair<uint64_t, uint64_t>>& ranges)
+{
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t k = 1; k < ranges.size(); k++)
+        if (ranges[k - 1].first + ranges[k - 1].second > ranges[k].first)
+            return set_error(OHGPU_ERR_INVALID, "%s: the %s ranges [%llu, +%llu) and [%llu, +%llu) overlap", who, noun, (unsigned long long)ranges[k - 1].first,
+                             (unsigned long long)ranges[k - 1].second, (unsigned long long)ranges[k].first, (unsigned long long)ranges[k].second);
     return OHGPU_OK;
 }
 // An ohgpu_*_batch_phase_ms behind its argument check: ms[k] = the time from events[k] to events[k + 1], k < count (waits for the last)
@@ -170,6 +217,8 @@ int  alac_check_desc(const ohgpu_alac_stream_desc& d, size_t i, const ohgpu_alac
 void alac_add_stream(AlacState& a, size_t i, const ohgpu_alac_stream_desc& d);
 void alac_summarise(const ohgpu_alac_packet_result* pres, uint32_t n_packets, ohgpu_alac_stream_result* out);
 int  alac_download_decoded(ohgpu_ctx* ctx, const char* who, const ohgpu_alac_stream_desc& d, const ohgpu_alac_packet_result* pres, void* dst_host);
+// ... and the same for FLAC (api_flac.hip), shared with Ogg FLAC (api_ogg.hip): a chain's frames are consecutive, so one run of samples
+int  flac_download_decoded(ohgpu_ctx* ctx, const char* who, const ohgpu_flac_stream_desc& d, const ohgpu_flac_stream_result& r, void* dst_host);
 using AlacResults = int (*)(ohgpu_ctx*, const ohgpu_batch*, ohgpu_alac_stream_result*, size_t, ohgpu_alac_packet_result*, size_t);
 template <typename Create, typename Download>
 int alac_process_host(ohgpu_ctx* ctx, const char* who, size_t n, size_t n_packets, const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes,

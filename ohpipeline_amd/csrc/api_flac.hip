@@ -5,6 +5,19 @@
 
 using namespace ohgpu;
 
+namespace ohgpu {
+
+// What a stream decoded, home: a chain's frames are consecutive, so one run of samples (per plane; packed output is one plane)
+int flac_download_decoded(ohgpu_ctx* ctx, const char* who, const ohgpu_flac_stream_desc& d, const ohgpu_flac_stream_result& r, void* dst_host)
+{
+    if (r.frames == 0) return OHGPU_OK;
+    const bool packed = d.flags & OHGPU_FLAC_OUT_PACKED_BE;
+    return download_planes(ctx, who, dst_host, d.dst_offset, d.dst_plane_stride, packed ? 1u : d.channels, packed ? (uint64_t)d.channels * (d.bits / 8u) : 4u,
+                           r.first_sample_decoded - d.first_sample, r.samples);
+}
+
+}  // namespace ohgpu
+
 extern "C" {
 
 static int flac_check_desc(const ohgpu_flac_stream_desc& d, size_t i, uint64_t src_arena_bytes, uint64_t dst_arena_bytes)
@@ -141,15 +154,9 @@ int ohgpu_flac_process_host(ohgpu_ctx* ctx, const ohgpu_flac_stream_desc* descs,
             if (e == OHGPU_OK && (frames || n_frames)) e = ohgpu_flac_batch_frames(ctx, b, frames, frames ? frames_capacity : 0, n_frames);
             return e;
         },
-        [&] {   // only what was decoded comes back: a chain's frames are consecutive, so per stream one run of samples (per plane)
+        [&] {   // only what was decoded comes back
             int e = OHGPU_OK;
-            for (size_t i = 0; i < n && e == OHGPU_OK; i++) {
-                const ohgpu_flac_stream_desc& d = descs[i];
-                if (res[i].frames == 0) continue;
-                const bool packed = d.flags & OHGPU_FLAC_OUT_PACKED_BE;
-                e = download_planes(ctx, who, dst_host, d.dst_offset, d.dst_plane_stride, packed ? 1u : d.channels, packed ? (uint64_t)d.channels * (d.bits / 8u) : 4u,
-                                    res[i].first_sample_decoded - d.first_sample, res[i].samples);
-            }
+            for (size_t i = 0; i < n && e == OHGPU_OK; i++) e = flac_download_decoded(ctx, who, descs[i], res[i], dst_host);
             return e;
         });
     if (err == OHGPU_OK && results) memcpy(results, res.data(), n * sizeof(ohgpu_flac_stream_result));

@@ -43,12 +43,7 @@ int ohgpu_iff_batch_check(const ohgpu_iff_stream_desc* descs, size_t n, uint64_t
         if (err != OHGPU_OK) return err;
         if (descs[i].dst_bytes_capacity) ranges.emplace_back(descs[i].dst_offset, descs[i].dst_bytes_capacity);
     }
-    std::sort(ranges.begin(), ranges.end());
-    for (size_t k = 1; k < ranges.size(); k++)
-        if (ranges[k - 1].first + ranges[k - 1].second > ranges[k].first)
-            return set_error(OHGPU_ERR_INVALID, "ohgpu_iff_batch_check: the destination ranges [%llu, +%llu) and [%llu, +%llu) overlap", (unsigned long long)ranges[k - 1].first,
-                             (unsigned long long)ranges[k - 1].second, (unsigned long long)ranges[k].first, (unsigned long long)ranges[k].second);
-    return OHGPU_OK;
+    return ranges_disjoint("ohgpu_iff_batch_check", "destination", ranges);
 }
 
 int ohgpu_iff_batch_create(ohgpu_ctx* ctx, const ohgpu_iff_stream_desc* descs, size_t n, uint64_t src_arena_bytes, uint64_t dst_arena_bytes, ohgpu_batch** out)
@@ -69,11 +64,9 @@ int ohgpu_iff_batch_create(ohgpu_ctx* ctx, const ohgpu_iff_stream_desc* descs, s
 
 int ohgpu_iff_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* src_base, void* dst_base, void* stream)
 {
-    const int err = iff_guard(ctx, "ohgpu_iff_batch_run", batch);
-    if (err != OHGPU_OK) return err;
-    if (batch->iff->n_streams == 0) return OHGPU_OK;
-    if (!src_base && batch->src_bytes_touched) return set_error(OHGPU_ERR_INVALID, "ohgpu_iff_batch_run: null arena pointer");
-    if (!dst_base && batch->iff->writes) return set_error(OHGPU_ERR_INVALID, "ohgpu_iff_batch_run: null arena pointer");
+    const bool mine = batch && batch->kind == kBatchIff;
+    const int go = run_guard(ctx, "ohgpu_iff_batch_run", batch, kBatchIff, mine && batch->iff->n_streams == 0, true, src_base, dst_base, mine && batch->iff->writes);
+    if (go <= 0) return go;
     return iff_run(ctx, batch, (const uint8_t*)src_base, (uint8_t*)dst_base, pick_stream(ctx, stream));
 }
 
@@ -84,10 +77,7 @@ int ohgpu_iff_batch_results(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_iff_
     const IffState& g = *batch->iff;
     if (n != g.n_streams || (n && !results)) return set_error(OHGPU_ERR_INVALID, "ohgpu_iff_batch_results: room for %zu results, the batch has %zu streams", n, g.n_streams);
     if (!n) return OHGPU_OK;
-    if (!g.ran) return set_error(OHGPU_ERR_INVALID, "ohgpu_iff_batch_results: the batch has not run");
-    OHGPU_HIP_TRY(hipEventSynchronize(g.ev[2]));
-    OHGPU_HIP_TRY(hipMemcpy(results, g.d_results, n * sizeof(*results), hipMemcpyDeviceToHost));
-    return OHGPU_OK;
+    return fetch_after_run("ohgpu_iff_batch_results", g, results, g.d_results, n * sizeof(*results));
 }
 
 int ohgpu_iff_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float ms[2])

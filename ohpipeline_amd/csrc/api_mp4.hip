@@ -27,10 +27,7 @@ int mp4_fetch(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, bool sa
     const Mp4State& g = *batch->mp4;
     if (n_packets != g.n_packets || (n_packets && !out)) return set_error(OHGPU_ERR_INVALID, "%s: room for %zu rows, the batch's tables have %zu", who, n_packets, g.n_packets);
     if (!n_packets || !g.n_streams) return OHGPU_OK;
-    if (!g.ran) return set_error(OHGPU_ERR_INVALID, "%s: the batch has not run", who);
-    OHGPU_HIP_TRY(hipEventSynchronize(g.ev[4]));
-    OHGPU_HIP_TRY(hipMemcpy(out, samples ? g.d_samples : g.d_packets, n_packets * 16u, hipMemcpyDeviceToHost));
-    return OHGPU_OK;
+    return fetch_after_run(who, g, out, samples ? g.d_samples : g.d_packets, n_packets * 16u);
 }
 
 }  // namespace
@@ -41,18 +38,13 @@ int ohgpu_mp4_batch_check(const ohgpu_mp4_stream_desc* descs, size_t n, size_t n
 {
     if (n && !descs) return set_error(OHGPU_ERR_INVALID, "ohgpu_mp4_batch_check: null argument");
     if (n > 0x00ffffffull || n_packets > 0x0fffffffull) return set_error(OHGPU_ERR_INVALID, "ohgpu_mp4_batch_check: too many descriptors");
-    std::vector<std::pair<uint32_t, uint32_t>> ranges;                 // (first, capacity) of the streams that have rows
+    std::vector<std::pair<uint64_t, uint64_t>> ranges;                 // (first, capacity) of the streams that have rows
     for (size_t i = 0; i < n; i++) {
         const int err = mp4_check_desc(descs[i], i, n_packets, src_arena_bytes);
         if (err != OHGPU_OK) return err;
         if (descs[i].packet_capacity) ranges.emplace_back(descs[i].packet_first, descs[i].packet_capacity);
     }
-    std::sort(ranges.begin(), ranges.end());
-    for (size_t k = 1; k < ranges.size(); k++)
-        if ((uint64_t)ranges[k - 1].first + ranges[k - 1].second > ranges[k].first)
-            return set_error(OHGPU_ERR_INVALID, "ohgpu_mp4_batch_check: the row ranges [%u, +%u) and [%u, +%u) overlap", ranges[k - 1].first, ranges[k - 1].second,
-                             ranges[k].first, ranges[k].second);
-    return OHGPU_OK;
+    return ranges_disjoint("ohgpu_mp4_batch_check", "row", ranges);
 }
 
 int ohgpu_mp4_batch_create(ohgpu_ctx* ctx, const ohgpu_mp4_stream_desc* descs, size_t n, size_t n_packets, uint64_t src_arena_bytes, ohgpu_batch** out)
@@ -74,10 +66,9 @@ int ohgpu_mp4_batch_create(ohgpu_ctx* ctx, const ohgpu_mp4_stream_desc* descs, s
 
 int ohgpu_mp4_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* src_base, void* stream)
 {
-    CTX_GUARD("ohgpu_mp4_batch_run");
-    if (!batch || batch->kind != kBatchMp4) return set_error(OHGPU_ERR_INVALID, "ohgpu_mp4_batch_run: not an MPEG-4 batch");
-    if (batch->mp4->n_streams == 0) return OHGPU_OK;
-    if (!src_base && batch->src_bytes_touched) return set_error(OHGPU_ERR_INVALID, "ohgpu_mp4_batch_run: null arena pointer");
+    const bool empty = batch && batch->kind == kBatchMp4 && batch->mp4->n_streams == 0;
+    const int go = run_guard(ctx, "ohgpu_mp4_batch_run", batch, kBatchMp4, empty, true, src_base, nullptr, false);
+    if (go <= 0) return go;
     return mp4_run(ctx, batch, (const uint8_t*)src_base, pick_stream(ctx, stream));
 }
 
@@ -88,10 +79,7 @@ int ohgpu_mp4_batch_results(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_mp4_
     const Mp4State& g = *batch->mp4;
     if (n != g.n_streams || (n && !results)) return set_error(OHGPU_ERR_INVALID, "ohgpu_mp4_batch_results: room for %zu results, the batch has %zu streams", n, g.n_streams);
     if (!n) return OHGPU_OK;
-    if (!g.ran) return set_error(OHGPU_ERR_INVALID, "ohgpu_mp4_batch_results: the batch has not run");
-    OHGPU_HIP_TRY(hipEventSynchronize(g.ev[4]));
-    OHGPU_HIP_TRY(hipMemcpy(results, g.d_results, n * sizeof(*results), hipMemcpyDeviceToHost));
-    return OHGPU_OK;
+    return fetch_after_run("ohgpu_mp4_batch_results", g, results, g.d_results, n * sizeof(*results));
 }
 
 int ohgpu_mp4_batch_packets(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_alac_packet* packets, size_t n_packets)

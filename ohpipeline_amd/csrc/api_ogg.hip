@@ -33,18 +33,13 @@ int ohgpu_ogg_batch_check(const ohgpu_ogg_stream_desc* descs, size_t n, size_t n
 {
     if (n && !descs) return set_error(OHGPU_ERR_INVALID, "ohgpu_ogg_batch_check: null argument");
     if (n > 0x00ffffffull || n_packets > 0x0fffffffull) return set_error(OHGPU_ERR_INVALID, "ohgpu_ogg_batch_check: too many descriptors");
-    std::vector<std::pair<uint32_t, uint32_t>> ranges;                 // (first, capacity) of the streams that record packets
+    std::vector<std::pair<uint64_t, uint64_t>> ranges;                 // (first, capacity) of the streams that record packets
     for (size_t i = 0; i < n; i++) {
         const int err = ogg_check_desc(descs[i], i, n_packets, src_arena_bytes, dst_arena_bytes);
         if (err != OHGPU_OK) return err;
         if (descs[i].packet_capacity) ranges.emplace_back(descs[i].packet_first, descs[i].packet_capacity);
     }
-    std::sort(ranges.begin(), ranges.end());
-    for (size_t k = 1; k < ranges.size(); k++)
-        if ((uint64_t)ranges[k - 1].first + ranges[k - 1].second > ranges[k].first)
-            return set_error(OHGPU_ERR_INVALID, "ohgpu_ogg_batch_check: the packet ranges [%u, +%u) and [%u, +%u) overlap", ranges[k - 1].first, ranges[k - 1].second,
-                             ranges[k].first, ranges[k].second);
-    return OHGPU_OK;
+    return ranges_disjoint("ohgpu_ogg_batch_check", "packet", ranges);
 }
 
 int ohgpu_ogg_batch_create(ohgpu_ctx* ctx, const ohgpu_ogg_stream_desc* descs, size_t n, size_t n_packets, uint64_t src_arena_bytes, uint64_t dst_arena_bytes,
@@ -79,10 +74,7 @@ int ohgpu_ogg_batch_results(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_ogg_
     const OggState& g = *batch->ogg;
     if (n != g.n_streams || (n && !results)) return set_error(OHGPU_ERR_INVALID, "ohgpu_ogg_batch_results: room for %zu results, the batch has %zu streams", n, g.n_streams);
     if (!n) return OHGPU_OK;
-    if (!g.ran) return set_error(OHGPU_ERR_INVALID, "ohgpu_ogg_batch_results: the batch has not run");
-    OHGPU_HIP_TRY(hipEventSynchronize(g.ev[4]));
-    OHGPU_HIP_TRY(hipMemcpy(results, g.d_results, n * sizeof(*results), hipMemcpyDeviceToHost));
-    return OHGPU_OK;
+    return fetch_after_run("ohgpu_ogg_batch_results", g, results, g.d_results, n * sizeof(*results));
 }
 
 int ohgpu_ogg_batch_packets(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_ogg_packet* packets, size_t n_packets)
@@ -93,10 +85,7 @@ int ohgpu_ogg_batch_packets(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_ogg_
     if (n_packets != g.n_packets || (n_packets && !packets))
         return set_error(OHGPU_ERR_INVALID, "ohgpu_ogg_batch_packets: room for %zu records, the batch's table has %zu", n_packets, g.n_packets);
     if (!n_packets || !g.n_streams) return OHGPU_OK;
-    if (!g.ran) return set_error(OHGPU_ERR_INVALID, "ohgpu_ogg_batch_packets: the batch has not run");
-    OHGPU_HIP_TRY(hipEventSynchronize(g.ev[4]));
-    OHGPU_HIP_TRY(hipMemcpy(packets, g.d_packets, n_packets * sizeof(*packets), hipMemcpyDeviceToHost));
-    return OHGPU_OK;
+    return fetch_after_run("ohgpu_ogg_batch_packets", g, packets, g.d_packets, n_packets * sizeof(*packets));
 }
 
 int ohgpu_ogg_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float ms[4])
@@ -207,13 +196,7 @@ int ohgpu_ogg_flac_process_host(ohgpu_ctx* ctx, const ohgpu_ogg_stream_desc* ogg
         },
         [&] {   // only what was decoded comes back, as in ohgpu_flac_process_host
             int e = OHGPU_OK;
-            for (size_t i = 0; i < n && e == OHGPU_OK; i++) {
-                const ohgpu_flac_stream_desc& d = fdescs[i];
-                if (fres[i].frames == 0) continue;
-                const bool packed = d.flags & OHGPU_FLAC_OUT_PACKED_BE;
-                e = download_planes(ctx, who, dst_host, d.dst_offset, d.dst_plane_stride, packed ? 1u : d.channels, packed ? (uint64_t)d.channels * (d.bits / 8u) : 4u,
-                                    fres[i].first_sample_decoded - d.first_sample, fres[i].samples);
-            }
+            for (size_t i = 0; i < n && e == OHGPU_OK; i++) e = flac_download_decoded(ctx, who, fdescs[i], fres[i], dst_host);
             return e;
         });
     if (d_mid) { (void)hipStreamSynchronize(ctx->stream); ctx_dev_free(ctx, d_mid); }

@@ -88,11 +88,8 @@ int ohgpu_ohm_rx_batch_results(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_o
     if ((records || n_datagrams) && (n_datagrams != r.n_datagrams || !records))
         return set_error(OHGPU_ERR_INVALID, "ohgpu_ohm_rx_batch_results: room for %zu records, the batch has %zu datagrams", n_datagrams, r.n_datagrams);
     if (r.n_streams == 0 && r.n_datagrams == 0) return OHGPU_OK;
-    if (!r.ran) return set_error(OHGPU_ERR_INVALID, "ohgpu_ohm_rx_batch_results: the batch has not run");
-    OHGPU_HIP_TRY(hipEventSynchronize(r.ev[3]));
-    if (streams && n) OHGPU_HIP_TRY(hipMemcpy(streams, r.d_results, n * sizeof(*streams), hipMemcpyDeviceToHost));
-    if (records && n_datagrams) OHGPU_HIP_TRY(hipMemcpy(records, r.d_records, n_datagrams * sizeof(*records), hipMemcpyDeviceToHost));
-    return OHGPU_OK;
+    OHGPU_TRY(fetch_after_run("ohgpu_ohm_rx_batch_results", r, streams, r.d_results, streams ? n * sizeof(*streams) : 0));
+    return fetch_after_run("ohgpu_ohm_rx_batch_results", r, records, r.d_records, records ? n_datagrams * sizeof(*records) : 0);
 }
 
 int ohgpu_ohm_rx_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float ms[3])

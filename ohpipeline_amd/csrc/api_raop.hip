@@ -177,7 +177,7 @@ int ohgpu_raop_batch_results(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_ala
         return OHGPU_OK;
     }
     if (!a.ran) return set_error(OHGPU_ERR_INVALID, "ohgpu_raop_batch_results: the batch has not run");
-    OHGPU_HIP_TRY(hipEventSynchronize(a.ev[3]));
+    OHGPU_HIP_TRY(hipEventSynchronize(a.end_event()));
     std::vector<ohgpu_alac_packet_result> decoded(a.packets.size()), all(r.alac_packet.size());
     const int err = alac_results(ctx, batch, decoded.data());
     if (err != OHGPU_OK) return err;
@@ -192,7 +192,7 @@ int ohgpu_raop_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float ms
     CTX_GUARD("ohgpu_raop_batch_phase_ms");
     if (!batch || batch->kind != kBatchRaop || !ms) return set_error(OHGPU_ERR_INVALID, "ohgpu_raop_batch_phase_ms: bad argument");
     const AlacState& a = *batch->alac;
-    const hipEvent_t ev[5] = {batch->raop->ev0, a.ev[0], a.ev[1], a.ev[2], a.ev[3]};
+    const hipEvent_t ev[5] = {batch->raop->ev[0], a.ev[0], a.ev[1], a.ev[2], a.ev[3]};
     return phase_ms("ohgpu_raop_batch_phase_ms", a.ran, ev, 4, ms);
 }
 

@@ -144,28 +144,20 @@ int flac_plan(ohgpu_ctx* ctx, ohgpu_batch* b)
     f.n_tiles = (uint32_t)tiles.size();
     Tables t;
     make_tables(&t);
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &f.d_tables, sizeof(Tables)));
-    OHGPU_HIP_TRY_ALLOC(hipMemcpy(f.d_tables, &t, sizeof(Tables), hipMemcpyHostToDevice));
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &f.d_counter, 256));
-    if (n) {
-        OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &f.d_streams, n * sizeof(Stream)));
-        OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &f.d_results, n * sizeof(Result)));
-    }
-    if (f.n_tiles) {
-        OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &f.d_tiles, tiles.size() * sizeof(FlacScanTile)));
-        OHGPU_HIP_TRY_ALLOC(hipMemcpy(f.d_tiles, tiles.data(), tiles.size() * sizeof(FlacScanTile), hipMemcpyHostToDevice));
-    }
-    for (hipEvent_t& e : f.ev) OHGPU_HIP_TRY_ALLOC(hipEventCreate(&e));
+    OHGPU_TRY(state_events(f, 5));
+    OHGPU_TRY(dev_array(ctx, f, &f.d_tables, 1, &t));
+    OHGPU_TRY(dev_array<uint32_t>(ctx, f, &f.d_counter, 64));      // (the first word is the counter)
+    OHGPU_TRY(dev_array<Stream>(ctx, f, &f.d_streams, n));
+    OHGPU_TRY(dev_array<Result>(ctx, f, &f.d_results, n));
+    OHGPU_TRY(dev_array(ctx, f, &f.d_tiles, tiles.size(), tiles.data()));
+    for (void** p : {&f.d_list, &f.d_probes, &f.d_rowcand, &f.d_subs, &f.d_rows}) state_own(f, p);      // a run's, grown on demand
     return OHGPU_OK;
 }
 
 void flac_free(ohgpu_ctx* ctx, ohgpu_batch* b)
 {
     if (!b->flac) return;
-    FlacState& f = *b->flac;
-    (void)hipDeviceSynchronize();
-    for (void* p : {f.d_tables, f.d_tiles, f.d_streams, f.d_results, f.d_counter, f.d_list, f.d_probes, f.d_rowcand, f.d_subs, f.d_rows}) ctx_dev_free(ctx, p);
-    for (hipEvent_t e : f.ev) if (e) (void)hipEventDestroy(e);
+    state_release(ctx, *b->flac);
     delete b->flac;
     b->flac = nullptr;
 }
@@ -186,8 +178,7 @@ int flac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
 {
     FlacState& f = *b->flac;
     const size_t n = f.streams.size();
-    if (const int err = run_begin(f, f.ev[4], s)) return err;
-    f.ran = true;
+    OHGPU_TRY(run_begin(f, s));
     f.n_candidates = 0;
     const Tables* tables = (const Tables*)f.d_tables;
     // ---- scan (again, with a longer list, should the hits not fit) ----
@@ -294,24 +285,19 @@ int flac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
         }
         OHGPU_HIP_TRY_ALLOC(hipGetLastError());
     }
-    return run_end(f, f.ev[4], s);
+    return run_end(f, s);
 }
 
 int flac_results(ohgpu_ctx* ctx, const ohgpu_batch* b, ohgpu_flac_stream_result* out)
 {
     FlacState& f = *b->flac;
-    if (!f.ran) return set_error(OHGPU_ERR_INVALID, "ohgpu_flac_batch_results: the batch has not run");
-    OHGPU_HIP_TRY_ALLOC(hipEventSynchronize(f.ev[4]));
-    if (!f.streams.empty()) OHGPU_HIP_TRY_ALLOC(hipMemcpy(out, f.d_results, f.streams.size() * sizeof(Result), hipMemcpyDeviceToHost));
-    return OHGPU_OK;
+    return fetch_after_run("ohgpu_flac_batch_results", f, out, f.d_results, f.streams.size() * sizeof(Result));
 }
 
 int flac_frames(ohgpu_ctx* ctx, const ohgpu_batch* b, ohgpu_flac_frame* out, size_t capacity, size_t* n_frames)
 {
     FlacState& f = *b->flac;
-    if (!f.ran) return set_error(OHGPU_ERR_INVALID, "ohgpu_flac_batch_frames: the batch has not run");
-    OHGPU_HIP_TRY_ALLOC(hipEventSynchronize(f.ev[4]));
-    if (f.n_candidates) OHGPU_HIP_TRY_ALLOC(hipMemcpy(f.host_probes.data(), f.d_probes, (size_t)f.n_candidates * sizeof(Probe), hipMemcpyDeviceToHost));
+    OHGPU_TRY(fetch_after_run("ohgpu_flac_batch_frames", f, f.host_probes.data(), f.d_probes, (size_t)f.n_candidates * sizeof(Probe)));
     size_t k = 0;
     for (uint32_t i = 0; i < f.n_candidates; i++) {               // (sorted by stream, then position: stream order)
         const Probe& c = f.host_probes[i];

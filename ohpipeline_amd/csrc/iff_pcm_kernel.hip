@@ -66,7 +66,7 @@ __global__ __launch_bounds__(kIffThreads) void iff_convert_kernel(const Stream* 
 int iff_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Stream* streams)
 {
     IffState& g = *b->iff;
-    for (hipEvent_t& e : g.ev) OHGPU_HIP_TRY_ALLOC(hipEventCreate(&e));
+    OHGPU_TRY(state_events(g, 3));
     if (!g.n_streams) return OHGPU_OK;
     std::vector<IffGroup> groups;
     for (size_t i = 0; i < g.n_streams; i++) g.writes = g.writes || streams[i].dst_bytes_capacity != 0u;
@@ -79,22 +79,17 @@ int iff_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Stream* streams)
             if (groups.size() > 0x7fffffffull) return set_error(OHGPU_ERR_INVALID, "ohgpu_iff_batch_create: the destination ranges are more than one batch takes");
         }
     g.n_groups = (uint32_t)groups.size();
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_streams, g.n_streams * sizeof(Stream)));
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_results, g.n_streams * sizeof(Result)));
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_recs, g.n_streams * sizeof(Rec)));
-    if (g.n_groups) OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_groups, g.n_groups * sizeof(IffGroup)));
-    OHGPU_HIP_TRY_ALLOC(hipMemcpy(g.d_streams, streams, g.n_streams * sizeof(Stream), hipMemcpyHostToDevice));
-    if (g.n_groups) OHGPU_HIP_TRY_ALLOC(hipMemcpy(g.d_groups, groups.data(), g.n_groups * sizeof(IffGroup), hipMemcpyHostToDevice));
+    OHGPU_TRY(dev_array(ctx, g, &g.d_streams, g.n_streams, streams));
+    OHGPU_TRY(dev_array<Result>(ctx, g, &g.d_results, g.n_streams));
+    OHGPU_TRY(dev_array<Rec>(ctx, g, &g.d_recs, g.n_streams));
+    OHGPU_TRY(dev_array(ctx, g, &g.d_groups, g.n_groups, groups.data()));
     return OHGPU_OK;
 }
 
 void iff_free(ohgpu_ctx* ctx, ohgpu_batch* b)
 {
     if (!b->iff) return;
-    IffState& g = *b->iff;
-    (void)hipDeviceSynchronize();
-    for (void* p : {g.d_streams, g.d_results, g.d_recs, g.d_groups}) ctx_dev_free(ctx, p);
-    for (hipEvent_t e : g.ev) if (e) (void)hipEventDestroy(e);
+    state_release(ctx, *b->iff);
     delete b->iff;
     b->iff = nullptr;
 }
@@ -102,8 +97,7 @@ void iff_free(ohgpu_ctx* ctx, ohgpu_batch* b)
 int iff_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s)
 {
     IffState& g = *b->iff;
-    if (const int err = run_begin(g, g.ev[2], s)) return err;      // (the records serve one run at a time)
-    g.ran = true;
+    OHGPU_TRY(run_begin(g, s));      // (the records serve one run at a time)
     const uint32_t ns = (uint32_t)g.n_streams, lane_blocks = (ns + 63u) / 64u;
     const Stream* const streams = (const Stream*)g.d_streams;
     OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[0], s));
@@ -111,7 +105,7 @@ int iff_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* d
         hipLaunchKernelGGL(iff_plain_kernel, dim3(lane_blocks), dim3(64), 0, s, streams, ns, src, dst, (Result*)g.d_results, (Rec*)g.d_recs);
         OHGPU_HIP_TRY_ALLOC(hipGetLastError());
         OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[1], s));
-        return run_end(g, g.ev[2], s);
+        return run_end(g, s);
     }
     hipLaunchKernelGGL(iff_walk_kernel, dim3(lane_blocks), dim3(64), 0, s, streams, ns, src, (Result*)g.d_results, (Rec*)g.d_recs);
     OHGPU_HIP_TRY_ALLOC(hipGetLastError());
@@ -120,7 +114,7 @@ int iff_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* d
         hipLaunchKernelGGL(iff_convert_kernel, dim3(g.n_groups), dim3(kIffThreads), 0, s, streams, (const Rec*)g.d_recs, (const IffGroup*)g.d_groups, src, dst);
         OHGPU_HIP_TRY_ALLOC(hipGetLastError());
     }
-    return run_end(g, g.ev[2], s);
+    return run_end(g, s);
 }
 
 }  // namespace ohgpu

@@ -207,7 +207,7 @@ __global__ __launch_bounds__(64) void mp4_finish_kernel(const Tables* __restrict
 int mp4_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Stream* streams)
 {
     Mp4State& g = *b->mp4;
-    for (hipEvent_t& e : g.ev) OHGPU_HIP_TRY_ALLOC(hipEventCreate(&e));
+    OHGPU_TRY(state_events(g, 5));
     if (!g.n_streams) return OHGPU_OK;
     std::vector<Mp4Tile> tiles;
     std::vector<Mp4Plan> plan(g.n_streams);
@@ -226,19 +226,16 @@ int mp4_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Stream* streams)
     if (stsc > 0x7fffffffull || stts > 0x7fffffffull || tiles.size() > 0x7fffffffull)
         return set_error(OHGPU_ERR_INVALID, "ohgpu_mp4_batch_create: %zu rows are more than one batch takes", g.n_packets);
     g.n_tiles = (uint32_t)tiles.size(); g.n_stsc = (uint32_t)stsc; g.n_stts = (uint32_t)stts;
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_streams, g.n_streams * sizeof(Stream)));
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_results, g.n_streams * sizeof(Result)));
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_tables, g.n_streams * sizeof(Tables)));
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_plan, g.n_streams * sizeof(Mp4Plan)));
-    if (g.n_tiles) OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_tiles, g.n_tiles * sizeof(Mp4Tile)));
-    if (g.n_tiles) OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_tile_carry, g.n_tiles * sizeof(uint64_t)));
-    if (g.n_tiles) OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_stsc_carry, (g.n_stsc + 1u) * sizeof(uint64_t)));
-    if (g.n_tiles) OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_stts_carry, (2u * (size_t)g.n_stts + 1u) * sizeof(uint64_t)));
-    if (g.n_packets) OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_packets, g.n_packets * sizeof(Row)));
-    if (g.n_packets) OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_samples, g.n_packets * sizeof(Sample)));
-    OHGPU_HIP_TRY_ALLOC(hipMemcpy(g.d_streams, streams, g.n_streams * sizeof(Stream), hipMemcpyHostToDevice));
-    OHGPU_HIP_TRY_ALLOC(hipMemcpy(g.d_plan, plan.data(), g.n_streams * sizeof(Mp4Plan), hipMemcpyHostToDevice));
-    if (g.n_tiles) OHGPU_HIP_TRY_ALLOC(hipMemcpy(g.d_tiles, tiles.data(), g.n_tiles * sizeof(Mp4Tile), hipMemcpyHostToDevice));
+    OHGPU_TRY(dev_array(ctx, g, &g.d_streams, g.n_streams, streams));
+    OHGPU_TRY(dev_array<Result>(ctx, g, &g.d_results, g.n_streams));
+    OHGPU_TRY(dev_array<Tables>(ctx, g, &g.d_tables, g.n_streams));
+    OHGPU_TRY(dev_array(ctx, g, &g.d_plan, g.n_streams, plan.data()));
+    OHGPU_TRY(dev_array(ctx, g, &g.d_tiles, g.n_tiles, tiles.data()));
+    OHGPU_TRY(dev_array<uint64_t>(ctx, g, &g.d_tile_carry, g.n_tiles));
+    OHGPU_TRY(dev_array<uint64_t>(ctx, g, &g.d_stsc_carry, g.n_tiles ? g.n_stsc + 1u : 0u));               // (the carries are the tiles': a
+    OHGPU_TRY(dev_array<uint64_t>(ctx, g, &g.d_stts_carry, g.n_tiles ? 2u * (size_t)g.n_stts + 1u : 0u));   //  batch without tiles has none)
+    OHGPU_TRY(dev_array<Row>(ctx, g, &g.d_packets, g.n_packets));
+    OHGPU_TRY(dev_array<Sample>(ctx, g, &g.d_samples, g.n_packets));
     if (g.n_packets) OHGPU_HIP_TRY_ALLOC(hipMemset(g.d_packets, 0xa5, g.n_packets * sizeof(Row)));
     if (g.n_packets) OHGPU_HIP_TRY_ALLOC(hipMemset(g.d_samples, 0xa5, g.n_packets * sizeof(Sample)));
     OHGPU_HIP_TRY_ALLOC(hipStreamSynchronize(nullptr));                // (the fills are queued: a run on another stream must not meet them)
@@ -248,10 +245,7 @@ int mp4_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Stream* streams)
 void mp4_free(ohgpu_ctx* ctx, ohgpu_batch* b)
 {
     if (!b->mp4) return;
-    Mp4State& g = *b->mp4;
-    (void)hipDeviceSynchronize();
-    for (void* p : {g.d_streams, g.d_results, g.d_tables, g.d_plan, g.d_tiles, g.d_tile_carry, g.d_stsc_carry, g.d_stts_carry, g.d_packets, g.d_samples}) ctx_dev_free(ctx, p);
-    for (hipEvent_t e : g.ev) if (e) (void)hipEventDestroy(e);
+    state_release(ctx, *b->mp4);
     delete b->mp4;
     b->mp4 = nullptr;
 }
@@ -259,8 +253,7 @@ void mp4_free(ohgpu_ctx* ctx, ohgpu_batch* b)
 int mp4_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, hipStream_t s)
 {
     Mp4State& g = *b->mp4;
-    if (const int err = run_begin(g, g.ev[4], s)) return err;      // (the tables serve one run at a time)
-    g.ran = true;
+    OHGPU_TRY(run_begin(g, s));      // (the tables serve one run at a time)
     const uint32_t ns = (uint32_t)g.n_streams, lane_blocks = (ns + 63u) / 64u;
     const Stream* const streams = (const Stream*)g.d_streams;
     Tables* const tables = (Tables*)g.d_tables;
@@ -270,7 +263,7 @@ int mp4_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, hipStream_
         hipLaunchKernelGGL(mp4_plain_kernel, dim3(lane_blocks), dim3(64), 0, s, streams, ns, src, results, tables, (Row*)g.d_packets, (Sample*)g.d_samples);
         OHGPU_HIP_TRY_ALLOC(hipGetLastError());
         for (int k = 1; k < 4; k++) OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[k], s));
-        return run_end(g, g.ev[4], s);
+        return run_end(g, s);
     }
     hipLaunchKernelGGL(mp4_walk_kernel, dim3(lane_blocks), dim3(64), 0, s, streams, ns, src, results, tables);
     OHGPU_HIP_TRY_ALLOC(hipGetLastError());
@@ -294,7 +287,7 @@ int mp4_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, hipStream_
     }
     hipLaunchKernelGGL(mp4_finish_kernel, dim3(lane_blocks), dim3(64), 0, s, (const Tables*)tables, ns, results);
     OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-    return run_end(g, g.ev[4], s);
+    return run_end(g, s);
 }
 
 }  // namespace ohgpu

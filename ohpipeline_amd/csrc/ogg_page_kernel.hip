@@ -109,7 +109,7 @@ uint32_t ogg_wave_blocks(uint64_t items, uint32_t cus)
 int ogg_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Stream* streams)
 {
     OggState& g = *b->ogg;
-    for (hipEvent_t& e : g.ev) OHGPU_HIP_TRY_ALLOC(hipEventCreate(&e));
+    OHGPU_TRY(state_events(g, 5));
     if (!g.n_streams) return OHGPU_OK;
     std::vector<OggTile> tiles;
     std::vector<uint64_t> bit_base(g.n_streams), piece_first(g.n_streams);
@@ -127,23 +127,18 @@ int ogg_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Stream* streams)
     g.n_tiles = (uint32_t)tiles.size(); g.cand_cap = (uint32_t)cands; g.piece_cap = (uint32_t)pieces; g.bits_bytes = (size_t)(bits / 8u);
     Tables tables;
     make_tables(&tables);
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_streams, g.n_streams * sizeof(Stream)));
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_results, g.n_streams * sizeof(Result)));
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_bit_base, g.n_streams * sizeof(uint64_t)));
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_piece_first, g.n_streams * sizeof(uint64_t)));
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_tables, sizeof(Tables)));
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_counters, 2 * sizeof(uint32_t)));
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_list, (size_t)g.cand_cap * sizeof(Candidate)));
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_pieces, (size_t)g.piece_cap * sizeof(Piece)));
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_work, (size_t)g.piece_cap * sizeof(uint32_t)));
-    if (g.n_tiles) OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_tiles, g.n_tiles * sizeof(OggTile)));
-    if (g.bits_bytes) OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_bits, g.bits_bytes));
-    if (g.n_packets) OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &g.d_packets, g.n_packets * sizeof(Packet)));
-    OHGPU_HIP_TRY_ALLOC(hipMemcpy(g.d_streams, streams, g.n_streams * sizeof(Stream), hipMemcpyHostToDevice));
-    OHGPU_HIP_TRY_ALLOC(hipMemcpy(g.d_bit_base, bit_base.data(), g.n_streams * sizeof(uint64_t), hipMemcpyHostToDevice));
-    OHGPU_HIP_TRY_ALLOC(hipMemcpy(g.d_piece_first, piece_first.data(), g.n_streams * sizeof(uint64_t), hipMemcpyHostToDevice));
-    OHGPU_HIP_TRY_ALLOC(hipMemcpy(g.d_tables, &tables, sizeof(Tables), hipMemcpyHostToDevice));
-    if (g.n_tiles) OHGPU_HIP_TRY_ALLOC(hipMemcpy(g.d_tiles, tiles.data(), g.n_tiles * sizeof(OggTile), hipMemcpyHostToDevice));
+    OHGPU_TRY(dev_array(ctx, g, &g.d_streams, g.n_streams, streams));
+    OHGPU_TRY(dev_array<Result>(ctx, g, &g.d_results, g.n_streams));
+    OHGPU_TRY(dev_array(ctx, g, &g.d_bit_base, g.n_streams, bit_base.data()));
+    OHGPU_TRY(dev_array(ctx, g, &g.d_piece_first, g.n_streams, piece_first.data()));
+    OHGPU_TRY(dev_array(ctx, g, &g.d_tables, 1, &tables));
+    OHGPU_TRY(dev_array<uint32_t>(ctx, g, &g.d_counters, 2));
+    OHGPU_TRY(dev_array<Candidate>(ctx, g, &g.d_list, g.cand_cap));
+    OHGPU_TRY(dev_array<Piece>(ctx, g, &g.d_pieces, g.piece_cap));
+    OHGPU_TRY(dev_array<uint32_t>(ctx, g, &g.d_work, g.piece_cap));
+    OHGPU_TRY(dev_array(ctx, g, &g.d_tiles, g.n_tiles, tiles.data()));
+    OHGPU_TRY(dev_array<uint8_t>(ctx, g, &g.d_bits, g.bits_bytes));
+    OHGPU_TRY(dev_array<Packet>(ctx, g, &g.d_packets, g.n_packets));
     if (g.n_packets) OHGPU_HIP_TRY_ALLOC(hipMemset(g.d_packets, 0, g.n_packets * sizeof(Packet)));
     OHGPU_HIP_TRY_ALLOC(hipStreamSynchronize(nullptr));                // (the fill is queued: a run on another stream must not meet it)
     return OHGPU_OK;
@@ -152,10 +147,7 @@ int ogg_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Stream* streams)
 void ogg_free(ohgpu_ctx* ctx, ohgpu_batch* b)
 {
     if (!b->ogg) return;
-    OggState& g = *b->ogg;
-    (void)hipDeviceSynchronize();
-    for (void* p : {g.d_streams, g.d_results, g.d_bit_base, g.d_piece_first, g.d_tables, g.d_counters, g.d_list, g.d_pieces, g.d_work, g.d_tiles, g.d_bits, g.d_packets}) ctx_dev_free(ctx, p);
-    for (hipEvent_t e : g.ev) if (e) (void)hipEventDestroy(e);
+    state_release(ctx, *b->ogg);
     delete b->ogg;
     b->ogg = nullptr;
 }
@@ -163,8 +155,7 @@ void ogg_free(ohgpu_ctx* ctx, ohgpu_batch* b)
 int ogg_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s)
 {
     OggState& g = *b->ogg;
-    if (const int err = run_begin(g, g.ev[4], s)) return err;      // (the lists serve one run at a time)
-    g.ran = true;
+    OHGPU_TRY(run_begin(g, s));      // (the lists serve one run at a time)
     const uint32_t ns = (uint32_t)g.n_streams;
     const uint32_t cus = ctx->num_cus > 0 ? (uint32_t)ctx->num_cus : 256u;
     OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[0], s));
@@ -192,7 +183,7 @@ int ogg_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* d
                            (const uint32_t*)g.d_work, (const uint32_t*)g.d_counters, src, dst);
         OHGPU_HIP_TRY_ALLOC(hipGetLastError());
     }
-    return run_end(g, g.ev[4], s);
+    return run_end(g, s);
 }
 
 }  // namespace ohgpu

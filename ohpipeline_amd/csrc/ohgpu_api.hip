@@ -287,38 +287,40 @@ int batch_begin(ohgpu_ctx* ctx, const char* who, BatchKind kind, bool args_ok, s
     return OHGPU_OK;
 }
 
-// One row per BatchKind: the noun of "<who>: not a <noun> batch"; what gives back everything the family's plan holds (it takes a
-// partly built batch: a failed create comes through here too); whether the device is drained first even without d_descs.  A new
-// family is one row here, one api_*.hip and one release function.
+// One row per BatchKind: the noun, with its article, of "<who>: not a <noun> batch"; what gives back everything the family's plan
+// holds (it takes a partly built batch: a failed create comes through here too); whether the device is drained first even without
+// d_descs.  A new
+// family is one row here, one api_*.hip, and a state that derives from RunState: its plan names each device block once (dev_array),
+// its release function is state_release and a delete.
 static void free_fmt(ohgpu_ctx* ctx, ohgpu_batch* b) { free_fmt_line(ctx, b); free_pcm_line(ctx, b); }
 static void free_pull(ohgpu_ctx* ctx, ohgpu_batch* b) { if (b->d_pull_tiles) ctx_dev_free(ctx, b->d_pull_tiles); }
 static const struct { const char* noun; void (*release)(ohgpu_ctx*, ohgpu_batch*); bool drain; } kKinds[] = {
     {nullptr, nullptr, false},
-    {"pcm", free_pcm_line, true},                 // kBatchPcm
-    {"src", free_src_fast, false},                // kBatchSrc (waits for the batch's last launch: before its event goes)
-    {"fmt", free_fmt, true},                      // kBatchFmt
-    {"flywheel", free_flywheel, true},            // kBatchFlywheel
-    {"Songcast frame", free_ohm, false},          // kBatchOhm
-    {"pulled", free_pull, false},                 // kBatchSrcPull
-    {"DSD", free_dsd_line, true},                 // kBatchDsd
-    {"FLAC", flac_free, false},                   // kBatchFlac
-    {"DSD to PCM", free_dsd_pcm, true},           // kBatchDsdPcm
-    {"lossless-packet (ALAC)", alac_free, false}, // kBatchAlac
-    {"RAOP", raop_free, false},                   // kBatchRaop
-    {"Songcast receiver", ohm_rx_free, false},    // kBatchOhmRx
-    {"Ogg", ogg_free, false},                     // kBatchOgg
-    {"MPEG-4", mp4_free, false},                  // kBatchMp4
-    {"PCM file", iff_free, false},                // kBatchIff
+    {"a pcm", free_pcm_line, true},                 // kBatchPcm
+    {"a src", free_src_fast, false},                // kBatchSrc (waits for the batch's last launch: before its event goes)
+    {"a fmt", free_fmt, true},                      // kBatchFmt
+    {"a flywheel", free_flywheel, true},            // kBatchFlywheel
+    {"a Songcast frame", free_ohm, false},          // kBatchOhm
+    {"a pulled", free_pull, false},                 // kBatchSrcPull
+    {"a DSD", free_dsd_line, true},                 // kBatchDsd
+    {"a FLAC", flac_free, false},                   // kBatchFlac
+    {"a DSD to PCM", free_dsd_pcm, true},           // kBatchDsdPcm
+    {"a lossless-packet (ALAC)", alac_free, false}, // kBatchAlac
+    {"a RAOP", raop_free, false},                   // kBatchRaop
+    {"a Songcast receiver", ohm_rx_free, false},    // kBatchOhmRx
+    {"a Ogg", ogg_free, false},                     // kBatchOgg
+    {"an MPEG-4", mp4_free, false},                 // kBatchMp4
+    {"a PCM file", iff_free, false},                // kBatchIff
 };
 static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchIff + 1, "a row per BatchKind");
 
 int run_guard(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, BatchKind kind, bool empty, bool null_src_ok,
-              const void* src_base, const void* dst_base)
+              const void* src_base, const void* dst_base, bool needs_dst)
 {
     CTX_GUARD(who);
-    if (!batch || batch->kind != kind) return set_error(OHGPU_ERR_INVALID, "%s: not a %s batch", who, kKinds[kind].noun);
+    if (!batch || batch->kind != kind) return set_error(OHGPU_ERR_INVALID, "%s: not %s batch", who, kKinds[kind].noun);
     if (empty) return 0;
-    if (!dst_base || (!src_base && !(null_src_ok && batch->src_bytes_touched == 0))) return set_error(OHGPU_ERR_INVALID, "%s: null arena pointer", who);
+    if ((needs_dst && !dst_base) || (!src_base && !(null_src_ok && batch->src_bytes_touched == 0))) return set_error(OHGPU_ERR_INVALID, "%s: null arena pointer", who);
     return 1;
 }
 

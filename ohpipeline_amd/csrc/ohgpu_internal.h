@@ -341,9 +341,26 @@ struct OhmPlan {
     uint32_t n_unfolded = 0, n_unfolded_generic = 0;
 };
 
+// ---- what the batch states below share (FlacState, AlacState, OhmRxState, OggState, Mp4State, IffState; RaopState for its blocks and
+// its one event).  The events of a run's phases: n_events are in use, the last of them is recorded at the run's end.  The tracking of
+// run_begin / run_end (api_common.h).  The registry of the device blocks that die with the batch: WHERE each pointer member lives (a
+// state is heap-allocated and never moves), not what it holds, so a block that a run frees and replaces (FLAC's lists and rows) needs
+// nothing more.  state_events, dev_array, state_release and fetch_after_run (api_common.h) are what works on it.
+struct RunState {
+    hipEvent_t ev[5] = {};
+    int n_events = 0;
+    hipStream_t last_stream = nullptr;
+    bool ran = false, ended = false;      // (ended: the last run recorded its end -- run_begin, api_common.h)
+    std::vector<void**> blocks;
+    hipEvent_t end_event() const { return ev[n_events - 1]; }
+    RunState() = default;
+    RunState(const RunState&) = delete;   // (the registry points into the state)
+    RunState& operator=(const RunState&) = delete;
+};
+
 // ---- FLAC frames (csrc/flac_frame_kernel.hip): what a batch keeps between runs; the batch's d_descs holds nothing ----
 struct FlacScanTile { uint32_t stream, pos0; };       // one workgroup's share of the scan: positions [pos0, pos0 + 1024) of a stream
-struct FlacState {
+struct FlacState : RunState {
     std::vector<flaccore::Stream> streams;            // the descriptors (cand_first / cand_count are each run's)
     uint32_t n_tiles = 0, max_blocksize = 0;
     void* d_tables = nullptr;                         // flaccore::Tables
@@ -359,14 +376,11 @@ struct FlacState {
     std::vector<flaccore::Probe> host_probes;
     std::vector<uint32_t> host_rowcand;
     std::vector<uint32_t> host_list;
-    hipEvent_t ev[5] = {};
-    hipStream_t last_stream = nullptr;
-    bool ran = false, ended = false;      // (ended: the last run recorded its end -- run_begin, api_common.h)
     uint32_t n_candidates = 0;
 };
 
 // ---- Apple Lossless packets (csrc/alac_packet_kernel.hip): what a batch keeps between runs; the batch's d_descs holds nothing ----
-struct AlacState {
+struct AlacState : RunState {
     std::vector<alaccore::Stream> streams;            // the descriptors
     std::vector<alaccore::Packet> packets;            // the table, by stream, with each packet's rows
     uint32_t n_rows = 0, n_groups = 0, max_frame_length = 0;   // rows with the groups' padding
@@ -378,16 +392,13 @@ struct AlacState {
     void* d_rowpacket = nullptr;                      // uint32[n_rows]: the row's packet, ~0u for padding
     void* d_groupbase = nullptr;                      // uint64[n_groups + 1]
     void* d_rows = nullptr; size_t rows_bytes = 0;    // int32, the groups one after the other
-    hipEvent_t ev[4] = {};
-    hipStream_t last_stream = nullptr;
-    bool ran = false, ended = false;      // (ended: the last run recorded its end -- run_begin, api_common.h)
 };
 static_assert(sizeof(ohgpu_alac_config) == 24 && sizeof(ohgpu_alac_packet) == 16 && sizeof(ohgpu_alac_stream_desc) == 64 && sizeof(ohgpu_alac_stream_result) == 16 && sizeof(ohgpu_alac_packet_result) == 8, "Apple Lossless layouts");
 static_assert(sizeof(alaccore::Stream) == 48 && sizeof(alaccore::Packet) == 32 && sizeof(alaccore::Chan) == 80 && sizeof(alaccore::PacketOut) == sizeof(ohgpu_alac_packet_result), "Apple Lossless device layouts");
 
 // ---- RAOP audio (csrc/raop_decrypt_kernel.hip): the decrypt phase in front of an AlacState.  The batch's AlacState
 // holds the DECODING streams only, their packets rewritten to where the decrypt phase leaves them in the plaintext scratch. ----
-struct RaopState {
+struct RaopState : RunState {
     std::vector<uint32_t> keys;                       // raopcore::kKeyWords words per stream: the schedule, the IV (cleared in raop_free)
     std::vector<int64_t>  alac_packet;                // per packet of the caller's table: its place in the AlacState's, -1 for a plaintext stream's
     std::vector<uint32_t> alac_first;                 // per stream: its first packet in the AlacState's table (decoding streams)
@@ -397,7 +408,7 @@ struct RaopState {
     void* d_pieces = nullptr;                         // raopcore::Piece[n_pieces]
     void* d_keys = nullptr; size_t keys_bytes = 0;    // uint32[n * kKeyWords]
     void* d_plain = nullptr; size_t plain_bytes = 0;  // the plaintext scratch: every decoding packet at a 16-byte boundary
-    hipEvent_t ev0 = nullptr;                         // before the decrypt phase (the AlacState's ev[0] is behind it)
+    // (ev[0], its one event: before the decrypt phase -- the AlacState's ev[0] is behind it; the run tracking is the AlacState's)
 };
 static_assert(sizeof(ohgpu_raop_stream_desc) == 96 && sizeof(raopcore::Piece) == 32 && sizeof(raopcore::Job) == 32, "RAOP layouts");
 
@@ -417,16 +428,13 @@ static_assert(sizeof(ohgpu_dsd_pcm_msg_desc) == 64, "ohgpu_dsd_pcm_msg_desc layo
 
 // ---- Songcast receiver (csrc/ohm_rx_kernel.hip): the tables, the records and results of the last run, the
 // sequencer's rings.  The batch's d_descs holds nothing.
-struct OhmRxState {
+struct OhmRxState : RunState {
     size_t n_streams = 0, n_datagrams = 0;
     void* d_streams = nullptr;                        // ohmrx::Stream[n_streams]
     void* d_datagrams = nullptr;                      // ohmrx::Datagram[n_datagrams]
     void* d_records = nullptr;                        // ohmrx::Record[n_datagrams]
     void* d_results = nullptr;                        // ohmrx::StreamResult[n_streams]
     void* d_rings = nullptr;                          // uint32[n_streams][ohmrx::kRing]
-    hipEvent_t ev[4] = {};
-    hipStream_t last_stream = nullptr;
-    bool ran = false, ended = false;      // (ended: the last run recorded its end -- run_begin, api_common.h)
 };
 static_assert(sizeof(ohgpu_ohm_rx_datagram) == sizeof(ohmrx::Datagram) && sizeof(ohgpu_ohm_rx_state) == sizeof(ohmrx::State) && sizeof(ohgpu_ohm_rx_stream) == sizeof(ohmrx::Stream) &&
               sizeof(ohgpu_ohm_rx_record) == sizeof(ohmrx::Record) && sizeof(ohgpu_ohm_rx_stream_result) == sizeof(ohmrx::StreamResult), "Songcast receiver layouts");
@@ -435,7 +443,7 @@ static_assert(sizeof(ohgpu_ohm_rx_datagram) == sizeof(ohmrx::Datagram) && sizeof
 // verified page starts, the gather plan and its dense work list, the packet table and results of the last run.  The batch's d_descs
 // holds nothing.
 struct OggTile { uint32_t stream, pos0; };            // one workgroup's share of the find: positions [pos0, pos0 + 1024) of a stream
-struct OggState {
+struct OggState : RunState {
     size_t n_streams = 0, n_packets = 0;
     uint32_t n_tiles = 0, cand_cap = 0, piece_cap = 0;
     size_t bits_bytes = 0;
@@ -451,9 +459,6 @@ struct OggState {
     void* d_tiles = nullptr;                          // OggTile[n_tiles]
     void* d_bits = nullptr;                           // a bit per source byte of every stream: a verified page starts here
     void* d_packets = nullptr;                        // oggpage::Packet[n_packets]
-    hipEvent_t ev[5] = {};
-    hipStream_t last_stream = nullptr;
-    bool ran = false, ended = false;      // (ended: the last run recorded its end -- run_begin, api_common.h)
 };
 static_assert(sizeof(ohgpu_ogg_stream_desc) == sizeof(oggpage::Stream) && sizeof(ohgpu_ogg_stream_result) == sizeof(oggpage::Result) && sizeof(ohgpu_ogg_packet) == sizeof(oggpage::Packet), "Ogg layouts");
 
@@ -462,7 +467,7 @@ static_assert(sizeof(ohgpu_ogg_stream_desc) == sizeof(oggpage::Stream) && sizeof
 constexpr uint32_t kMp4Tile = mp4box::kTile;          // 1024 samples: tests/test_gpu_mp4_textbook.py restates it
 struct Mp4Tile { uint32_t stream, s0; };              // one workgroup's share: samples [s0, s0 + kMp4Tile) of a stream
 struct Mp4Plan { uint32_t tile_first, n_tiles, stsc_first, stts_first; };   // a stream's tiles in the tile list, its carries in d_carry_*
-struct Mp4State {
+struct Mp4State : RunState {
     size_t n_streams = 0, n_packets = 0;
     uint32_t n_tiles = 0, n_stsc = 0, n_stts = 0;
     bool plain = false;                               // created under kernel variant 1: one launch, a lane per stream
@@ -476,9 +481,6 @@ struct Mp4State {
     void* d_stts_carry = nullptr;                     // uint64[2 * n_stts]: the samples, then the frames, in front of each stts run
     void* d_packets = nullptr;                        // mp4box::Row[n_packets]
     void* d_samples = nullptr;                        // mp4box::Sample[n_packets]
-    hipEvent_t ev[5] = {};
-    hipStream_t last_stream = nullptr;
-    bool ran = false, ended = false;      // (ended: the last run recorded its end -- run_begin, api_common.h)
 };
 static_assert(sizeof(ohgpu_mp4_stream_desc) == sizeof(mp4box::Stream) && sizeof(ohgpu_mp4_stream_result) == sizeof(mp4box::Result) && sizeof(ohgpu_mp4_sample) == sizeof(mp4box::Sample) &&
               sizeof(ohgpu_alac_packet) == sizeof(mp4box::Row) && sizeof(ohgpu_alac_config) == sizeof(mp4box::Config) && offsetof(ohgpu_mp4_stream_result, error_offset) == offsetof(mp4box::Result, error_offset) &&
@@ -488,7 +490,7 @@ static_assert(sizeof(ohgpu_mp4_stream_desc) == sizeof(mp4box::Stream) && sizeof(
 // of each stream's run and the results of the last run.  The batch's d_descs holds nothing.
 constexpr uint32_t kIffGroupPieces = 1024;            // the pieces one workgroup of the conversion takes: tests/test_gpu_iff_textbook.py restates it
 struct IffGroup { uint32_t stream, group; };          // one workgroup's share: pieces [group x kIffGroupPieces, + kIffGroupPieces) of a stream's run
-struct IffState {
+struct IffState : RunState {
     size_t n_streams = 0;
     uint32_t n_groups = 0;
     bool plain = false;                               // created under kernel variant 1: one launch, a lane per stream
@@ -497,9 +499,6 @@ struct IffState {
     void* d_results = nullptr;                        // iffchunk::Result[n_streams]
     void* d_recs = nullptr;                           // iffchunk::Rec[n_streams]
     void* d_groups = nullptr;                         // IffGroup[n_groups]
-    hipEvent_t ev[3] = {};
-    hipStream_t last_stream = nullptr;
-    bool ran = false, ended = false;      // (ended: the last run recorded its end -- run_begin, api_common.h)
 };
 static_assert(sizeof(ohgpu_iff_stream_desc) == sizeof(iffchunk::Stream) && sizeof(ohgpu_iff_stream_result) == sizeof(iffchunk::Result) &&
               offsetof(ohgpu_iff_stream_desc, max_bit_depth) == offsetof(iffchunk::Stream, max_bit_depth) &&
@@ -651,9 +650,19 @@ inline int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? OHGPU_ERR_
         if (e_ != hipSuccess) return ::ohgpu::set_error(::ohgpu::hip_code(e_), "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// OHGPU_TRY: the same for a call of the library's own that has set the error already
+#define OHGPU_TRY(expr)                          \
+    do {                                         \
+        const int err_ = (expr);                 \
+        if (err_ != OHGPU_OK) return err_;       \
+    } while (0)
+
 // The release functions (free_pcm_line, free_fmt_line, free_dsd_line, flac_free, alac_free, raop_free, free_flywheel, free_src_fast, free_ohm, ohm_rx_free, ogg_free, mp4_free, iff_free): what
 // ohgpu_batch_destroy's table calls (csrc/ohgpu_api.hip).  Each takes a PARTLY BUILT batch -- null pointers, a plan that was never
 // made -- and leaves the plan reset: a create that fails at any point hands its batch to ohgpu_batch_destroy and returns.
+// The seven whose state is a RunState (flac_free ... iff_free) are one shape -- if the pointer is set: state_release (api_common.h), which
+// frees whatever block the state's registry names and destroys whatever event exists, then delete, then null the pointer --, raop_free
+// with its key wipe in front.  Such a family names no block twice: dev_array in its plan is the one place.
 // kernels
 hipError_t launch_fmt_v1(const ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
 hipError_t launch_pcm_v1(const ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);

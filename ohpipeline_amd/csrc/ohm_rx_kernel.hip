@@ -61,28 +61,19 @@ uint32_t ohm_rx_gather_blocks(uint32_t n_datagrams, uint32_t cus)
 int ohm_rx_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Stream* streams, const Datagram* datagrams)
 {
     OhmRxState& r = *b->ohmrx;
-    for (hipEvent_t& e : r.ev) OHGPU_HIP_TRY_ALLOC(hipEventCreate(&e));
-    if (r.n_streams) {
-        OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &r.d_streams, r.n_streams * sizeof(Stream)));
-        OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &r.d_results, r.n_streams * sizeof(StreamResult)));
-        OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &r.d_rings, r.n_streams * kRing * sizeof(uint32_t)));
-        OHGPU_HIP_TRY_ALLOC(hipMemcpy(r.d_streams, streams, r.n_streams * sizeof(Stream), hipMemcpyHostToDevice));
-    }
-    if (r.n_datagrams) {
-        OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &r.d_datagrams, r.n_datagrams * sizeof(Datagram)));
-        OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &r.d_records, r.n_datagrams * sizeof(Record)));
-        OHGPU_HIP_TRY_ALLOC(hipMemcpy(r.d_datagrams, datagrams, r.n_datagrams * sizeof(Datagram), hipMemcpyHostToDevice));
-    }
+    OHGPU_TRY(state_events(r, 4));
+    OHGPU_TRY(dev_array(ctx, r, &r.d_streams, r.n_streams, streams));
+    OHGPU_TRY(dev_array<StreamResult>(ctx, r, &r.d_results, r.n_streams));
+    OHGPU_TRY(dev_array<uint32_t>(ctx, r, &r.d_rings, r.n_streams * kRing));
+    OHGPU_TRY(dev_array(ctx, r, &r.d_datagrams, r.n_datagrams, datagrams));
+    OHGPU_TRY(dev_array<Record>(ctx, r, &r.d_records, r.n_datagrams));
     return OHGPU_OK;
 }
 
 void ohm_rx_free(ohgpu_ctx* ctx, ohgpu_batch* b)
 {
     if (!b->ohmrx) return;
-    OhmRxState& r = *b->ohmrx;
-    (void)hipDeviceSynchronize();
-    for (void* p : {r.d_streams, r.d_datagrams, r.d_records, r.d_results, r.d_rings}) ctx_dev_free(ctx, p);
-    for (hipEvent_t e : r.ev) if (e) (void)hipEventDestroy(e);
+    state_release(ctx, *b->ohmrx);
     delete b->ohmrx;
     b->ohmrx = nullptr;
 }
@@ -90,8 +81,7 @@ void ohm_rx_free(ohgpu_ctx* ctx, ohgpu_batch* b)
 int ohm_rx_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s)
 {
     OhmRxState& r = *b->ohmrx;
-    if (const int err = run_begin(r, r.ev[3], s)) return err;      // (the records serve one run at a time)
-    r.ran = true;
+    OHGPU_TRY(run_begin(r, s));      // (the records serve one run at a time)
     const uint32_t ng = (uint32_t)r.n_datagrams, ns = (uint32_t)r.n_streams;
     const uint32_t cus = ctx->num_cus > 0 ? (uint32_t)ctx->num_cus : 256u;
     OHGPU_HIP_TRY_ALLOC(hipEventRecord(r.ev[0], s));
@@ -110,7 +100,7 @@ int ohm_rx_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t
         hipLaunchKernelGGL(ohm_rx_gather_kernel, dim3(ohm_rx_gather_blocks(ng, cus)), dim3(kRxThreads), 0, s, (const Datagram*)r.d_datagrams, (const Record*)r.d_records, ng, src, dst);
         OHGPU_HIP_TRY_ALLOC(hipGetLastError());
     }
-    return run_end(r, r.ev[3], s);
+    return run_end(r, s);
 }
 
 }  // namespace ohgpu

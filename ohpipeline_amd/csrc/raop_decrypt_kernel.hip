@@ -46,14 +46,12 @@ int raop_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Job* jobs, size_t n_jobs)
     std::vector<Piece> pieces;
     plan_pieces(jobs, n_jobs, &pieces);
     r.n_pieces = (uint32_t)pieces.size();
-    OHGPU_HIP_TRY_ALLOC(hipEventCreate(&r.ev0));
+    OHGPU_TRY(state_events(r, 1));
     if (pieces.empty()) return OHGPU_OK;
     r.keys_bytes = r.keys.size() * sizeof(uint32_t);
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &r.d_pieces, pieces.size() * sizeof(Piece)));
-    OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &r.d_keys, r.keys_bytes));
-    if (r.plain_bytes) OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &r.d_plain, r.plain_bytes));
-    OHGPU_HIP_TRY_ALLOC(hipMemcpy(r.d_pieces, pieces.data(), pieces.size() * sizeof(Piece), hipMemcpyHostToDevice));
-    OHGPU_HIP_TRY_ALLOC(hipMemcpy(r.d_keys, r.keys.data(), r.keys_bytes, hipMemcpyHostToDevice));
+    OHGPU_TRY(dev_array(ctx, r, &r.d_pieces, pieces.size(), pieces.data()));
+    OHGPU_TRY(dev_array(ctx, r, &r.d_keys, r.keys.size(), r.keys.data()));
+    OHGPU_TRY(dev_array<uint8_t>(ctx, r, &r.d_plain, r.plain_bytes));
     return OHGPU_OK;
 }
 
@@ -65,8 +63,7 @@ void raop_free(ohgpu_ctx* ctx, ohgpu_batch* b)
         // the expanded keys do not outlive the batch: the device array is cleared before its block goes back to the cache, the host copy too
         if (r.d_keys) (void)hipMemset(r.d_keys, 0, r.keys_bytes);
         for (uint32_t& w : r.keys) *(volatile uint32_t*)&w = 0;
-        for (void* p : {r.d_pieces, r.d_keys, r.d_plain}) ctx_dev_free(ctx, p);
-        if (r.ev0) (void)hipEventDestroy(r.ev0);
+        state_release(ctx, r);
         delete b->raop;
         b->raop = nullptr;
     }
@@ -77,8 +74,8 @@ int raop_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
 {
     const RaopState& r = *b->raop;
     AlacState& a = *b->alac;
-    if (const int err = run_begin(a, a.ev[3], s)) return err;      // (the scratch serves one run at a time)
-    OHGPU_HIP_TRY_ALLOC(hipEventRecord(r.ev0, s));
+    OHGPU_TRY(run_begin(a, s));      // (the scratch serves one run at a time)
+    OHGPU_HIP_TRY_ALLOC(hipEventRecord(r.ev[0], s));
     if (r.n_pieces) {
         hipLaunchKernelGGL(raop_decrypt_kernel, dim3((r.n_pieces + kRaopWaves - 1) / kRaopWaves), dim3(kRaopThreads), 0, s, (const Piece*)r.d_pieces, r.n_pieces,
                            (const uint32_t*)r.d_keys, src, (uint8_t*)r.d_plain, dst);
