@@ -190,7 +190,8 @@ int ohgpu_batch_info(const ohgpu_batch* batch, uint64_t* n_msgs, uint64_t* in_fr
  * (line_planned, group_chunks), Songcast packs of wider streams (fmt_wide_records), a uniform stereo batch on a register-only
  * kernel (fmt_stereo_*), the staged layout kernel (fmt_staged_chunks), or, with every count zero, the generic kernel only.
  * An Apple Lossless batch (ohgpu_alac_batch_create) answers with alac_route alone, and so does a RAOP batch; an MPEG-4 batch
- * (ohgpu_mp4_batch_create) answers with mp4_route alone, a PCM file batch (ohgpu_iff_batch_create) with iff_route alone.
+ * (ohgpu_mp4_batch_create) answers with mp4_route alone, a PCM file batch (ohgpu_iff_batch_create) with iff_route alone, a DSD file
+ * batch (ohgpu_dsd_file_batch_create) with dsd_file_route alone.
  * OHGPU_ERR_INVALID for any other kind of batch. */
 typedef struct ohgpu_batch_paths {       /* 64 bytes */
     uint32_t line_planned;          /* 1: the line kernel has a plan for the batch (0: only the generic kernel can run it) */
@@ -213,6 +214,7 @@ typedef struct ohgpu_batch_paths {       /* 64 bytes */
         uint32_t alac_route;        /* Apple Lossless: 1 the three fused phases over the transposed scratch, 2 the plain route (created under kernel variant 1) */
         uint32_t mp4_route;         /* MPEG-4: 1 the four phases (walk, tile sums, carries, expand), 2 the plain route: one launch, a lane per stream (kernel variant 1) */
         uint32_t iff_route;         /* PCM files: 1 the two launches (walk, convert by 16-byte pieces), 2 the plain route: one launch, a lane per stream (kernel variant 1) */
+        uint32_t dsd_file_route;    /* DSD files: 1 the two launches (walk, convert by lanes of eight chunks), 2 the plain route: one launch, a lane per stream (kernel variant 1) */
     };
 } ohgpu_batch_paths;
 int ohgpu_batch_paths_info(const ohgpu_batch* batch, ohgpu_batch_paths* out);
@@ -1207,6 +1209,127 @@ int ohgpu_iff_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float ms[
  * `results` may be NULL. */
 int ohgpu_iff_process_host(ohgpu_ctx* ctx, const ohgpu_iff_stream_desc* descs, size_t n, const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes,
                            ohgpu_iff_stream_result* results);
+
+/* ---- DSD files: DSF and DFF chunks walked and the audio packed into the pipeline's DSD format (the text is csrc/dsd_file_core.h) ----
+ * What CodecDsdDsf and CodecDsdDff do in front of their packers: the bytes of a file, or of a prefix of one, in; the audio in the
+ * pipeline's DSD format (the DSD section above) out, with a result per stream.  Two launches, nothing waits for the host between them.
+ * The first 16 bytes decide the kind: bytes 0..4 "DSD " is DSF; bytes 0..4 "FRM8" with bytes 12..16 "DSD " is DFF; anything else, or
+ * fewer than 16 bytes, is NOT_DSD.  The first thing wrong gives the status, error_offset is the chunk that gave it (0 for NOT_DSD), and
+ * every other field of a refused stream reads 0.  A header the walk needs that does not lie inside src_bytes is TRUNCATED, error_offset
+ * where it would lie.  The checks are made in the order written here.
+ * DSF (little-endian; a chunk is an id, a u64 size that includes these 12 bytes, and its fields):
+ *   - `DSD ` at 0 (28 bytes: id, size, the file's total size u64, the metadata pointer u64): its 28 bytes not inside src_bytes:
+ *     TRUNCATED; size other than 28: INVALID; total file size 0: INVALID.  The metadata pointer is reported (metadata_offset) and not
+ *     followed.
+ *   - `fmt ` at 28, else INVALID; its size below 52 or 2^31 and above: INVALID; its 52 bytes not inside src_bytes: TRUNCATED.  The
+ *     fields, all u32 but one: format version (reported), format id (0, else UNSUPPORTED), channel type (reported), channel count (2,
+ *     else UNSUPPORTED), sampling rate (0: INVALID), bits per sample (1, else UNSUPPORTED: 8 means a file whose bytes are MSB first,
+ *     DESIGN.md 8), sample count per channel (u64), block size per channel (4096, else UNSUPPORTED), four reserved bytes.
+ *   - `data` at 28 + the `fmt ` size, else INVALID; a size below 12: INVALID.  The audio bytes are the size less 12: odd: INVALID;
+ *     2 x floor(sample_count / 8) above them: INVALID.  The audio is pairs of 4096-byte planes, left then right.
+ *   - chunks_total = floor(sample_count / 16) (what DsdDsf.cpp:408-414 and :203 amount to).
+ * DFF (big-endian; a chunk is an id, a u64 size, the payload, and one pad byte behind an odd size):
+ *   - chunks are walked from byte 16.  More than OHGPU_DSD_FILE_MAX_CHUNKS headers, the local ones of a `PROP` counted: INVALID.  A
+ *     size of 2^63 or more: INVALID.  The walk takes the first `PROP` whose type is `SND ` and the first `DSD ` chunk, in either
+ *     order, and stops when it has both; everything else is skipped by its size.
+ *   - `FVER`, when met: size other than 4: INVALID; its payload not inside src_bytes: TRUNCATED; first byte other than 1: UNSUPPORTED;
+ *     its four bytes are format_version.
+ *   - `DST ` met before `DSD `: UNSUPPORTED.
+ *   - `PROP`: size below 4: INVALID; its payload not inside src_bytes: TRUNCATED.  One of another type than `SND ` is skipped.  Local
+ *     chunks follow its type: one that runs past the `PROP`: INVALID.  `FS  `: size 4, the rate, else INVALID; rate 0: INVALID.
+ *     `CHNL`: at least 2 bytes, else INVALID; a u16 count: 2, else UNSUPPORTED.  `CMPR`: at least 4 bytes, else INVALID; the fourcc
+ *     `DSD `, else UNSUPPORTED.  Others are skipped.  No `FS  ` or no `CHNL`: INVALID.  error_offset is the `PROP`.
+ *   - `DSD `: the audio is its stated size, bytes L R L R; odd: INVALID.  chunks_total = floor(size / 4), sample_count = 16 x that.
+ * Audio past src_bytes is no error: chunks_available counts the chunks below chunks_total whose four source bytes all lie inside
+ * src_bytes -- for DSF chunk j = 2048 q + r those at data_offset + 8192 q + 2 r, the next one, and the same two 4096 further on -- so a
+ * prefix of a file plays.
+ * The conversion of an OK stream: chunks [chunk_first, chunk_first + n) go to dst_offset in the pipeline's format for the descriptor's
+ * (W, P), the bytes exactly those an ohgpu_dsd_desc of kind OHGPU_DSD_DSF / OHGPU_DSD_DFF defines for those chunks.  With cpb = W * 4 /
+ * (4 + P) and room = floor(dst_bytes_capacity / (W * 4)) * cpb, n = min(chunks_available - chunk_first, room), or 0 when chunk_first
+ * lies behind the available chunks.  If the n chunks reach chunks_total, a last partial block is filled with 0x69 up to its end (the
+ * DSD section's rule, and its deliberate difference from the reference: the leftover chunks are converted); if they do not, n is
+ * rounded down to whole blocks.  bytes_written counts the fill.  No destination byte outside bytes_written is touched.
+ * Where this differs from the reference (tests/dsd_file_textbook.py carries the same list):
+ *   - the reference streams and wants DFF's chunks in its own order (FVER, PROP, DSD); here the bytes are there, `PROP` and `DSD ` are
+ *     read in either order and everything else is skipped by its size;
+ *   - the reference does not skip the pad byte behind an odd DFF chunk; here it is honoured;
+ *   - the reference does not look at `CMPR`, plays a `DST ` file's frames it never finds, and ignores DSF's format id and bits per
+ *     sample; here they are looked at and refused, instead of played as noise;
+ *   - the reference refuses a DSF channel count other than 2 as corrupt and takes DFF's as it comes; here both kinds are stereo and
+ *     any other count is UNSUPPORTED;
+ *   - the reference does not hold DSF's sample count against the `data` chunk's size; here a count the chunk cannot hold is INVALID. */
+#define OHGPU_DSD_FILE_OK           0u
+#define OHGPU_DSD_FILE_NOT_DSD      1u
+#define OHGPU_DSD_FILE_TRUNCATED    2u
+#define OHGPU_DSD_FILE_INVALID      3u
+#define OHGPU_DSD_FILE_UNSUPPORTED  4u
+#define OHGPU_DSD_FILE_KIND_DSF     2u     /* = OHGPU_DSD_DSF */
+#define OHGPU_DSD_FILE_KIND_DFF     3u     /* = OHGPU_DSD_DFF */
+#define OHGPU_DSD_FILE_MAX_CHUNKS   4096u
+
+typedef struct ohgpu_dsd_file_stream_desc {   /* 64 bytes */
+    uint64_t src_offset;            /* the file's bytes are [src_offset, + src_bytes) of the source arena, any address */
+    uint32_t src_bytes;             /* < 2^31: the whole file or a prefix of it */
+    uint32_t flags;                 /* zero */
+    uint64_t dst_offset;            /* a multiple of 16: the sample blocks go to [dst_offset, + bytes_written) of the destination arena */
+    uint64_t dst_bytes_capacity;    /* the stream's room there */
+    uint64_t chunk_first;           /* the first chunk to convert (a seek) */
+    uint32_t sample_block_words;    /* W  } validated as for ohgpu_dsd_desc */
+    uint32_t pad_bytes_per_chunk;   /* P  }                                 */
+    uint32_t reserved[4];           /* zero */
+} ohgpu_dsd_file_stream_desc;
+
+typedef struct ohgpu_dsd_file_stream_result {   /* 96 bytes */
+    uint32_t status;                /* OHGPU_DSD_FILE_OK ... _UNSUPPORTED */
+    uint32_t kind;                  /* OHGPU_DSD_FILE_KIND_* */
+    uint32_t channels;              /* 2 */
+    uint32_t sample_rate;           /* one-bit samples a second and channel */
+    uint32_t format_version;        /* DSF: the `fmt ` field; DFF: FVER's four bytes, 0 when the walk met none */
+    uint32_t channel_type;          /* DSF: the `fmt ` field; DFF: 0 */
+    uint64_t sample_count;          /* a channel's one-bit samples: DSF as the file states them, DFF 16 x chunks_total */
+    uint64_t chunks_total;          /* chunks of sixteen samples a channel */
+    uint64_t chunks_available;      /* those whose source bytes lie inside src_bytes */
+    uint64_t chunks_written;        /* n */
+    uint64_t bytes_written;         /* whole sample blocks, the 0x69 fill counted */
+    uint64_t data_offset;           /* the first audio byte, from src_offset */
+    uint64_t data_bytes;            /* the audio as the file states it */
+    uint64_t metadata_offset;       /* DSF: the metadata pointer (0: none); DFF: 0 */
+    uint64_t error_offset;          /* the chunk that gave a status other than OK, from src_offset */
+} ohgpu_dsd_file_stream_result;
+
+/* Host only, no device needed: the validation ohgpu_dsd_file_batch_create makes.  OHGPU_ERR_INVALID: non-zero reserved words or flags,
+ * a (W, P) that ohgpu_dsd_desc refuses, src_bytes >= 2^31, a dst_offset that is no multiple of 16, destination ranges [dst_offset,
+ * + dst_bytes_capacity) that overlap.  OHGPU_ERR_BOUNDS: a range outside its arena.  The empty batch is legal. */
+int ohgpu_dsd_file_batch_check(const ohgpu_dsd_file_stream_desc* descs, size_t n, uint64_t src_arena_bytes, uint64_t dst_arena_bytes);
+/* The descriptors go to the device; the list of the conversion's workgroups (from dst_bytes_capacity alone), the walk's records and
+ * the results are the batch's.  Created under ohgpu_set_kernel_variant(1) the batch takes the plain route: one launch, a lane per
+ * stream runs the walk and a byte-wise conversion (ohgpu_batch_paths_info: dsd_file_route).  Both routes write the same bytes.  Freed
+ * with ohgpu_batch_destroy. */
+int ohgpu_dsd_file_batch_create(ohgpu_ctx* ctx, const ohgpu_dsd_file_stream_desc* descs, size_t n, uint64_t src_arena_bytes, uint64_t dst_arena_bytes,
+                                ohgpu_batch** batch);
+/* Walk, convert: queued on the stream, nothing waits for the host.  The walk reads a stream as the aligned 4-byte words that hold its
+ * bytes, as ohgpu_iff_batch_run does: src_base must be a multiple of 4 and the arena's allocation must end on a multiple of 4 (any
+ * hipMalloc block does).  The conversion takes the audio at any address: a lane loads the aligned 16-byte lines that cover its eight
+ * chunks, only lines that lie whole inside the stream, and stores whole 16-byte lines (dst_base a multiple of 16, as ohgpu_malloc's
+ * are; otherwise, and for P above 4, it goes byte by byte).  The batch owns its records: it runs on one stream at a time.  A second
+ * run, and a second batch of the same shape, allocate nothing on the device (ohgpu_device_allocations). */
+int ohgpu_dsd_file_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* src_base, void* dst_base, void* stream);
+/* The last run's results, n = the batch's stream count (waits for that run). */
+int ohgpu_dsd_file_batch_results(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_dsd_file_stream_result* results, size_t n);
+/* The last run's phases in milliseconds from device events: walk, convert (waits for that run).  The plain route is one phase: the
+ * second reads 0. */
+int ohgpu_dsd_file_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float ms[2]);
+/* Host-buffer convenience: one upload, one run, the results and, of dst_host, the bytes_written bytes of every OK stream home.
+ * `results` may be NULL. */
+int ohgpu_dsd_file_process_host(ohgpu_ctx* ctx, const ohgpu_dsd_file_stream_desc* descs, size_t n, const void* src_host, uint64_t src_bytes,
+                                void* dst_host, uint64_t dst_bytes, ohgpu_dsd_file_stream_result* results);
+/* Host only, no device needed: the walk over `n` bytes of a file (or of a prefix) -- the same core, and the record the device's walk
+ * gives for chunk_first 0 and unlimited room under (W, P): chunks_written = chunks_available, rounded down to whole blocks where they
+ * do not reach chunks_total.  OHGPU_ERR_INVALID for a null argument, n >= 2^31 or a (W, P) that ohgpu_dsd_desc refuses. */
+int ohgpu_dsd_file_head(const void* bytes, uint64_t n, uint32_t sample_block_words, uint32_t pad_bytes_per_chunk, ohgpu_dsd_file_stream_result* result);
+/* Host only: where a seek to `sample` lands, by the reference's rounding -- DSF: sample & ~(32768 - 1) (DsdDsf.cpp's block pairs);
+ * DFF: sample & ~(2048 - 1) --, and chunk_first = sample_rounded / 16.  OHGPU_ERR_INVALID for another kind or a null result. */
+int ohgpu_dsd_file_seek(uint32_t kind, uint64_t sample, uint64_t* chunk_first, uint64_t* sample_rounded);
 
 /* ---- sample-rate converter (own specification; DESIGN.md "Resampler") ---- */
 /* Host-side filter design: Kaiser-windowed sinc, Q28 coefficients, coef_q28[p*T + k] = h[p + k*L].

@@ -181,6 +181,16 @@ IFF_STREAM_RESULT = np.dtype([("status", "<u4"), ("kind", "<u4"), ("channels", "
                               ("src_endian", "<u4"), ("bit_rate", "<u4"), ("frames_total", "<u8"), ("frames_available", "<u8"), ("frames_written", "<u8"),
                               ("data_offset", "<u8"), ("data_bytes", "<u8"), ("error_offset", "<u8")], align=False)
 assert IFF_STREAM_DESC.itemsize == 64 and IFF_STREAM_RESULT.itemsize == 80
+# DSD files: ohgpu_dsd_file_stream_desc (64 B), ohgpu_dsd_file_stream_result (96 B)
+DSD_FILE_OK, DSD_FILE_NOT_DSD, DSD_FILE_TRUNCATED, DSD_FILE_INVALID, DSD_FILE_UNSUPPORTED = range(5)
+DSD_FILE_KIND_DSF, DSD_FILE_KIND_DFF, DSD_FILE_MAX_CHUNKS = 2, 3, 4096
+DSD_FILE_ROUTE_FUSED, DSD_FILE_ROUTE_PLAIN = 1, 2
+DSD_FILE_STREAM_DESC = np.dtype([("src_offset", "<u8"), ("src_bytes", "<u4"), ("flags", "<u4"), ("dst_offset", "<u8"), ("dst_bytes_capacity", "<u8"),
+                                 ("chunk_first", "<u8"), ("sample_block_words", "<u4"), ("pad_bytes_per_chunk", "<u4"), ("reserved", "<u4", (4,))], align=False)
+DSD_FILE_STREAM_RESULT = np.dtype([("status", "<u4"), ("kind", "<u4"), ("channels", "<u4"), ("sample_rate", "<u4"), ("format_version", "<u4"), ("channel_type", "<u4"),
+                                   ("sample_count", "<u8"), ("chunks_total", "<u8"), ("chunks_available", "<u8"), ("chunks_written", "<u8"), ("bytes_written", "<u8"),
+                                   ("data_offset", "<u8"), ("data_bytes", "<u8"), ("metadata_offset", "<u8"), ("error_offset", "<u8")], align=False)
+assert DSD_FILE_STREAM_DESC.itemsize == 64 and DSD_FILE_STREAM_RESULT.itemsize == 96
 
 # every symbol of include/ohgpu.h: name -> (restype, argtypes)
 _vp, _vpp = C.c_void_p, C.POINTER(C.c_void_p)
@@ -283,6 +293,14 @@ SYMBOLS = {
     "ohgpu_iff_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
     "ohgpu_iff_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
     "ohgpu_iff_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),
+    "ohgpu_dsd_file_batch_check": (C.c_int, [_vp, C.c_size_t, C.c_uint64, C.c_uint64]),
+    "ohgpu_dsd_file_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
+    "ohgpu_dsd_file_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "ohgpu_dsd_file_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_dsd_file_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
+    "ohgpu_dsd_file_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),
+    "ohgpu_dsd_file_head": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp]),
+    "ohgpu_dsd_file_seek": (C.c_int, [C.c_uint32, C.c_uint64, _u64p, _u64p]),
     "ohgpu_ogg_crc": (C.c_uint32, [_vp, C.c_size_t]),
     "ohgpu_ogg_flac_head": (C.c_int, [_vp, C.c_size_t, _vp, C.POINTER(C.c_uint32), _u64p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "ohgpu_ogg_flac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp,
@@ -601,6 +619,33 @@ def iff_batch_check(descs, src_arena_bytes, dst_arena_bytes):
     check(lib().ohgpu_iff_batch_check(_ptr_or_none(d), d.size, src_arena_bytes, dst_arena_bytes))
 
 
+def _dsd_file_descs(descs):
+    d = np.ascontiguousarray(descs)
+    assert d.dtype == DSD_FILE_STREAM_DESC
+    return d
+
+
+def dsd_file_batch_check(descs, src_arena_bytes, dst_arena_bytes):
+    """The validation of ctx.dsd_file_batch without a device (ohgpu_dsd_file_batch_check): OhGpuError on a bad descriptor."""
+    d = _dsd_file_descs(descs)
+    check(lib().ohgpu_dsd_file_batch_check(_ptr_or_none(d), d.size, src_arena_bytes, dst_arena_bytes))
+
+
+def dsd_file_head(data, sample_block_words, pad_bytes_per_chunk):
+    """The walk over a file's bytes on the host (ohgpu_dsd_file_head): one DSD_FILE_STREAM_RESULT record."""
+    raw = np.frombuffer(bytes(data), dtype=np.uint8)
+    res = np.zeros(1, dtype=DSD_FILE_STREAM_RESULT)
+    check(lib().ohgpu_dsd_file_head(_ptr_or_none(raw), raw.size, sample_block_words, pad_bytes_per_chunk, _ptr_or_none(res)))
+    return res[0]
+
+
+def dsd_file_seek(kind, sample):
+    """(chunk_first, sample_rounded) of a seek to `sample` (ohgpu_dsd_file_seek)."""
+    first, rounded = C.c_uint64(0), C.c_uint64(0)
+    check(lib().ohgpu_dsd_file_seek(kind, sample, C.byref(first), C.byref(rounded)))
+    return int(first.value), int(rounded.value)
+
+
 def _raop_tables(descs, packets):
     d, p = np.ascontiguousarray(descs), np.ascontiguousarray(packets)
     assert d.dtype == RAOP_STREAM_DESC and p.dtype == ALAC_PACKET
@@ -752,6 +797,7 @@ class Context:
         out["alac_route"] = int(v["reserved"][0][0])        # (the header's union: the last word)
         out["mp4_route"] = out["alac_route"]                 # (the same word: a batch is of one kind)
         out["iff_route"] = out["alac_route"]
+        out["dsd_file_route"] = out["alac_route"]
         return out
 
     def pcm_process_host(self, descs, src, dst):
@@ -1101,6 +1147,35 @@ class Context:
         ms = (C.c_float * 2)()
         check(lib().ohgpu_iff_batch_phase_ms(self._h, batch, ms))
         return tuple(float(v) for v in ms)
+
+    def dsd_file_batch(self, descs, src_arena_bytes, dst_arena_bytes):
+        d = _dsd_file_descs(descs)
+        b = C.c_void_p()
+        check(lib().ohgpu_dsd_file_batch_create(self._h, _ptr_or_none(d), d.size, src_arena_bytes, dst_arena_bytes, C.byref(b)))
+        return b
+
+    def dsd_file_run(self, batch, d_src, d_dst, stream=None):
+        """Walk, convert (ohgpu_dsd_file_batch_run): queued on the stream."""
+        check(lib().ohgpu_dsd_file_batch_run(self._h, batch, d_src, d_dst, stream))
+
+    def dsd_file_results(self, batch, n):
+        """The last run's DSD_FILE_STREAM_RESULT per stream; waits for the run."""
+        res = np.zeros(n, dtype=DSD_FILE_STREAM_RESULT)
+        check(lib().ohgpu_dsd_file_batch_results(self._h, batch, _ptr_or_none(res), n))
+        return res
+
+    def dsd_file_phase_ms(self, batch):
+        """(walk, convert) of the last run in milliseconds; waits for the run."""
+        ms = (C.c_float * 2)()
+        check(lib().ohgpu_dsd_file_batch_phase_ms(self._h, batch, ms))
+        return [float(v) for v in ms]
+
+    def dsd_file_process_host(self, descs, src, dst):
+        """File bytes in, sample blocks of the pipeline's DSD format into dst (ohgpu_dsd_file_process_host); returns the stream results."""
+        d = _dsd_file_descs(descs)
+        res = np.zeros(d.size, dtype=DSD_FILE_STREAM_RESULT)
+        check(lib().ohgpu_dsd_file_process_host(self._h, _ptr_or_none(d), d.size, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst), dst.nbytes, _ptr_or_none(res)))
+        return res
 
     def iff_process_host(self, descs, src, dst):
         """File bytes in, big-endian PCM into dst (ohgpu_iff_process_host); returns the stream results."""

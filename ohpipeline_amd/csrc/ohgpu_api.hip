@@ -311,8 +311,9 @@ static const struct { const char* noun; void (*release)(ohgpu_ctx*, ohgpu_batch*
     {"a Ogg", ogg_free, false},                     // kBatchOgg
     {"an MPEG-4", mp4_free, false},                 // kBatchMp4
     {"a PCM file", iff_free, false},                // kBatchIff
+    {"a DSD file", dsd_file_free, false},           // kBatchDsdFile
 };
-static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchIff + 1, "a row per BatchKind");
+static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchDsdFile + 1, "a row per BatchKind");
 
 int run_guard(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, BatchKind kind, bool empty, bool null_src_ok,
               const void* src_base, const void* dst_base, bool needs_dst)
@@ -627,7 +628,11 @@ int ohgpu_batch_paths_info(const ohgpu_batch* b, ohgpu_batch_paths* out)
         out->iff_route = b->iff && b->iff->plain ? 2u : 1u;
         return OHGPU_OK;
     }
-    if (b->kind != kBatchOhm) return set_error(OHGPU_ERR_INVALID, "ohgpu_batch_paths_info: not a pcm, Songcast frame, fmt, Apple Lossless, MPEG-4 or PCM file batch");
+    if (b->kind == kBatchDsdFile) {
+        out->dsd_file_route = b->dsdfile && b->dsdfile->plain ? 2u : 1u;
+        return OHGPU_OK;
+    }
+    if (b->kind != kBatchOhm) return set_error(OHGPU_ERR_INVALID, "ohgpu_batch_paths_info: not a pcm, Songcast frame, fmt, Apple Lossless, MPEG-4, PCM file or DSD file batch");
     const OhmPlan& p = b->ohm;
     if (p.direct) add_line_paths(p.direct->line, out);
     out->ohm_wide_fragments = p.n_selr;

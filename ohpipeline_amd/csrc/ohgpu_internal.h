@@ -22,6 +22,7 @@
 #include "ogg_page_core.h"
 #include "mp4_box_core.h"
 #include "iff_chunk_core.h"
+#include "dsd_file_core.h"
 #include "ohm_rx_core.h"
 #include "raop_aes_core.h"
 
@@ -341,7 +342,7 @@ struct OhmPlan {
     uint32_t n_unfolded = 0, n_unfolded_generic = 0;
 };
 
-// ---- what the batch states below share (FlacState, AlacState, OhmRxState, OggState, Mp4State, IffState; RaopState for its blocks and
+// ---- what the batch states below share (FlacState, AlacState, OhmRxState, OggState, Mp4State, IffState, DsdFileState; RaopState for its blocks and
 // its one event).  The events of a run's phases: n_events are in use, the last of them is recorded at the run's end.  The tracking of
 // run_begin / run_end (api_common.h).  The registry of the device blocks that die with the batch: WHERE each pointer member lives (a
 // state is heap-allocated and never moves), not what it holds, so a block that a run frees and replaces (FLAC's lists and rows) needs
@@ -505,7 +506,28 @@ static_assert(sizeof(ohgpu_iff_stream_desc) == sizeof(iffchunk::Stream) && sizeo
               offsetof(ohgpu_iff_stream_result, error_offset) == offsetof(iffchunk::Result, error_offset) &&
               offsetof(ohgpu_iff_stream_result, frames_written) == offsetof(iffchunk::Result, frames_written), "IFF layouts");
 
-enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11, kBatchOhmRx = 12, kBatchOgg = 13, kBatchMp4 = 14, kBatchIff = 15 };
+// ---- DSD files (csrc/dsd_file_kernel.hip): the descriptors, the list of the conversion's workgroups, the walk's record
+// of each stream's run and the results of the last run.  The batch's d_descs holds nothing.
+constexpr uint32_t kDsdFileGroupPieces = 2;           // the pieces (of dsdfile::kPieceChunks chunks, a wave each) one workgroup takes: tests/test_gpu_dsd_file_textbook.py restates both
+struct DsdFileGroup { uint32_t stream, group; };      // one workgroup's share: pieces [group x kDsdFileGroupPieces, + kDsdFileGroupPieces) of a stream's run
+struct DsdFileState : RunState {
+    size_t n_streams = 0;
+    uint32_t n_groups = 0;
+    bool plain = false;                               // created under kernel variant 1: one launch, a lane per stream
+    bool writes = false;                              // some stream has room for a sample block: either route needs the destination arena
+    void* d_streams = nullptr;                        // dsdfile::Stream[n_streams]
+    void* d_results = nullptr;                        // dsdfile::Result[n_streams]
+    void* d_recs = nullptr;                           // dsdfile::Rec[n_streams]
+    void* d_groups = nullptr;                         // DsdFileGroup[n_groups]
+};
+static_assert(sizeof(ohgpu_dsd_file_stream_desc) == sizeof(dsdfile::Stream) && sizeof(ohgpu_dsd_file_stream_result) == sizeof(dsdfile::Result) &&
+              offsetof(ohgpu_dsd_file_stream_desc, pad_bytes_per_chunk) == offsetof(dsdfile::Stream, pad_bytes_per_chunk) &&
+              offsetof(ohgpu_dsd_file_stream_result, error_offset) == offsetof(dsdfile::Result, error_offset) &&
+              offsetof(ohgpu_dsd_file_stream_result, bytes_written) == offsetof(dsdfile::Result, bytes_written) &&
+              dsdfile::kDsf == OHGPU_DSD_DSF && dsdfile::kDff == OHGPU_DSD_DFF && dsdfile::kDsf == OHGPU_DSD_FILE_KIND_DSF && dsdfile::kDff == OHGPU_DSD_FILE_KIND_DFF &&
+              dsdfile::kFillByte == OHGPU_DSD_SILENCE_BYTE && dsdfile::kMaxChunks == OHGPU_DSD_FILE_MAX_CHUNKS, "DSD file layouts");
+
+enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11, kBatchOhmRx = 12, kBatchOgg = 13, kBatchMp4 = 14, kBatchIff = 15, kBatchDsdFile = 16 };
 
 }  // namespace ohgpu
 
@@ -616,6 +638,7 @@ struct ohgpu_batch {
     ohgpu::OggState* ogg = nullptr;     // kBatchOgg only
     ohgpu::Mp4State* mp4 = nullptr;     // kBatchMp4 only
     ohgpu::IffState* iff = nullptr;     // kBatchIff only
+    ohgpu::DsdFileState* dsdfile = nullptr;   // kBatchDsdFile only
     void*    d_pull_tiles = nullptr;   // kBatchSrcPull: PullTile[n_pull_tiles] on the device (d_descs holds the messages)
     uint32_t n_pull_tiles = 0;
     // kBatchSrc whose messages differ in layout: one uniform batch per layout (each with its own block-kernel plan), run one
@@ -657,10 +680,10 @@ inline int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? OHGPU_ERR_
         if (err_ != OHGPU_OK) return err_;       \
     } while (0)
 
-// The release functions (free_pcm_line, free_fmt_line, free_dsd_line, flac_free, alac_free, raop_free, free_flywheel, free_src_fast, free_ohm, ohm_rx_free, ogg_free, mp4_free, iff_free): what
+// The release functions (free_pcm_line, free_fmt_line, free_dsd_line, flac_free, alac_free, raop_free, free_flywheel, free_src_fast, free_ohm, ohm_rx_free, ogg_free, mp4_free, iff_free, dsd_file_free): what
 // ohgpu_batch_destroy's table calls (csrc/ohgpu_api.hip).  Each takes a PARTLY BUILT batch -- null pointers, a plan that was never
 // made -- and leaves the plan reset: a create that fails at any point hands its batch to ohgpu_batch_destroy and returns.
-// The seven whose state is a RunState (flac_free ... iff_free) are one shape -- if the pointer is set: state_release (api_common.h), which
+// The eight whose state is a RunState (flac_free ... dsd_file_free) are one shape -- if the pointer is set: state_release (api_common.h), which
 // frees whatever block the state's registry names and destroys whatever event exists, then delete, then null the pointer --, raop_free
 // with its key wipe in front.  Such a family names no block twice: dev_array in its plan is the one place.
 // kernels
@@ -721,6 +744,10 @@ int  mp4_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, hipStream
 int  iff_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const iffchunk::Stream* streams);   // the descriptors and the workgroup list onto the device
 void iff_free(ohgpu_ctx* ctx, ohgpu_batch* b);
 int  iff_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
+// csrc/dsd_file_kernel.hip.  No launch is persistent: a lane a stream (walk), a wave per piece of dsdfile::kPieceChunks chunks (convert).
+int  dsd_file_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const dsdfile::Stream* streams);   // the descriptors and the workgroup list onto the device
+void dsd_file_free(ohgpu_ctx* ctx, ohgpu_batch* b);
+int  dsd_file_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
 // csrc/ohm_frame_kernel.hip: the two wire channels of streams wider than stereo (Sender::DoProcessFragment), one record per fragment
 OhmSelRec wide_record(uint64_t src_off, uint64_t dst_off, uint32_t n_frames, uint32_t channels, uint32_t sb, bool little, uint64_t src_arena_bytes);
 hipError_t launch_ohm_wide(const ohgpu_ctx* ctx, const void* d_recs, uint32_t n_recs, const uint8_t* src, uint8_t* dst, const uint8_t* prefix, hipStream_t s);

@@ -127,6 +127,11 @@ void CodecController::OutputDecodedStream(TUint aBitRate, TUint aBitDepth, TUint
     iDownstreamElement.Push(iMsgFactory.CreateMsgDecodedStream(info));
 }
 
+void CodecController::OutputDecodedStreamDsd(TUint aSampleRate, TUint aNumChannels, const Brx& aCodecName, TUint64 aTrackLength, TUint64 aSampleStart)
+{
+    OutputDecodedStream(aSampleRate * aNumChannels, 1, aSampleRate, aNumChannels, aCodecName, aTrackLength, aSampleStart, true);
+}
+
 TUint64 CodecController::OutputAudioPcm(const Brx& aData, TUint aChannels, TUint aSampleRate, TUint aBitDepth,
                                         AudioDataEndian aEndian, TUint64 aTrackOffset)
 {

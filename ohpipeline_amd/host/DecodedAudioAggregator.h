@@ -70,6 +70,8 @@ public:
     /** CodecController.cpp:799-826: returns the jiffies output; asserts the format is the announced one. */
     TUint64 OutputAudioPcm(const Brx& aData, TUint aChannels, TUint aSampleRate, TUint aBitDepth, AudioDataEndian aEndian,
                            TUint64 aTrackOffset);
+    /** The DSD form of the announcement: one bit a sample, lossless, the bit rate a channel's rate x the channels. */
+    void OutputDecodedStreamDsd(TUint aSampleRate, TUint aNumChannels, const Brx& aCodecName, TUint64 aTrackLength, TUint64 aSampleStart);
     /** CodecController.cpp:864-896: aData is whole sample blocks in the pipeline's DSD format; it leaves as MsgAudioDsd of at most
      *  DecodedAudio::kMaxBytes each (DSD is not Songcast, so nothing cuts it to 5 ms).  Returns the jiffies output. */
     TUint64 OutputAudioDsd(const Brx& aData, TUint aChannels, TUint aSampleRate, TUint aSampleBlockWords, TUint64 aTrackOffset,
