@@ -1096,6 +1096,177 @@ int ohgpu_mp4_alac_process_host(ohgpu_ctx* ctx, const ohgpu_mp4_stream_desc* mp4
                                 ohgpu_mp4_stream_result* mp4_results, ohgpu_alac_packet* packets, ohgpu_mp4_sample* samples,
                                 ohgpu_alac_stream_result* alac_results, ohgpu_alac_packet_result* packet_results);
 
+/* ---- Fragmented MPEG-4: movie fragments in front of the FLAC and Apple Lossless decoders (the text is csrc/mp4_frag_core.h) ----
+ * What Codec/Mpeg4.cpp's moof switcher does in front of CodecFlac and CodecAlacApple: the bytes of an initialisation segment and its
+ * media segments (ISO/IEC 14496-12 movie fragments, as DASH and CMAF deliver them), or of a prefix of them, in; a row a `trun`, an
+ * ohgpu_alac_packet row and an ohgpu_mp4_sample row a sample of the taken track, and -- with OHGPU_MP4F_GATHER -- the samples' bytes as
+ * one contiguous run out, with a result per stream.  ohgpu_mp4_* keeps answering such a file UNSUPPORTED; this family answers a plain
+ * .m4a NOT_FRAGMENTED.  Boxes are read as in the MPEG-4 section above.
+ * The walk, in file order, at most OHGPU_MP4F_MAX_BOXES box headers a stream (one more: INVALID; the boxes inside a sample description
+ * are counted apart, against OHGPU_MP4_MAX_BOXES).  The first thing wrong gives the status, error_offset is the box that gave it, and
+ * every other field of a refused stream reads 0 (first_bad_sample 0xffffffff; `codec` is kept by NOT_CODEC and NOT_FRAGMENTED):
+ *   - top level: "ftyp" at bytes 4..8, else NOT_MP4 (fewer than 8 bytes: TRUNCATED).  The first `moov` is entered (it reaches past
+ *     src_bytes: TRUNCATED); a `moof` in front of it is INVALID; every `moof` behind it is entered; a `moof`, or any other box, that
+ *     reaches past src_bytes ends the walk -- what stood in front of it is served.  mdat, sidx, styp, free and the rest are skipped by
+ *     their size.  No `moov`: TRUNCATED.
+ *   - moov: a `trak` is entered until one is taken; it is taken at its end when its first sample entry is in `codecs`.  tkhd gives
+ *     track_id (version 0 or 1, else INVALID), mdia/mdhd the timescale and the duration (the MPEG-4 section's rules); the first stsd
+ *     gives the entry.  `enca`: UNSUPPORTED.  An `alac` entry follows exactly the MPEG-4 section's rules.  A `fLaC` entry (read only
+ *     when `codecs` asks for it) shorter than 28 bytes is INVALID; behind the same 28-byte head come child boxes, of which `dfLa`
+ *     (FLAC-in-ISOBMFF) holds 4 bytes of version and flags -- not 0: UNSUPPORTED -- and metadata blocks of 1 byte (last flag | type)
+ *     and a 24-bit length.  Fewer than 4 bytes, no block, a block that leaves the box, a first block that is not STREAMINFO of 34
+ *     bytes: INVALID.  A depth other than 8, 16 or 24: UNSUPPORTED.  The blocks behind STREAMINFO are skipped, up to the one with the
+ *     last flag or the end of the box.  No dfLa: UNSUPPORTED.  A taken trak without tkhd, mdhd or a parsed entry: INVALID (the trak).
+ *     The end of moov with no trak taken: NOT_CODEC, `codec` the first trak's entry fourcc.
+ *   - the first `mvex` is read at moov's end, when the track is known: the first `trex` with track_id (shorter than 24 bytes: INVALID)
+ *     gives default_sample_duration and default_sample_size; the first `mehd` (version 0 or 1, else INVALID) gives the duration when
+ *     mdhd's is 0.
+ *   - a stream with no mvex and no moof whose stsz counts samples is NOT_FRAGMENTED (error_offset: the moov): a file for ohgpu_mp4_*.
+ *     Any other moov without a moof is OK with 0 samples: an initialisation segment alone.
+ *   - moof: mfhd is skipped; every `traf` holds a `tfhd` (else INVALID, the traf) in front of its tfdt and trun boxes (else INVALID,
+ *     that box).  tfhd flags: 0x1 base_data_offset (u64), 0x2 sample description index (skipped), 0x8 default duration, 0x10 default
+ *     size, 0x20 default flags (skipped), 0x10000 (ignored), 0x20000 default-base-is-moof; a box too short for its flags: INVALID.  A
+ *     traf of another track_id is skipped.  Neither 0x1 nor 0x20000 on a taken traf that is not the first traf of its moof:
+ *     UNSUPPORTED (ISO then wants the end of the other track's data).  The first `tfdt` in front of the traf's first run (version 0:
+ *     u32, 1: u64, else INVALID) gives that run's first frame.  Every `trun` with samples is one RUN: flags 0x1 data_offset (signed
+ *     32), 0x4 first-sample flags (skipped); 0x100 duration, 0x200 size, 0x400 flags, 0x800 composition offset, each 4 bytes an entry
+ *     in that order.  Entries that do not fit the box: INVALID.  A trun of 0 samples writes no row and is passed over.  A sample's
+ *     size is the entry's, else tfhd's, else trex's, else INVALID (the trun); so is its duration.  More than OHGPU_MP4F_MAX_RUN_SAMPLES
+ *     samples in a trun, or more than OHGPU_MP4F_MAX_SAMPLES in a stream: UNSUPPORTED (the trun).
+ * Where a run's bytes lie: the base is tfhd's base_data_offset (beyond 2^62 it counts as 2^62) or else the moof's first byte; the run
+ * starts at base + data_offset if the trun has one, else at the base if it is the traf's first run, else where the run in front of it
+ * ends.  Its samples are contiguous.  Where its frames start: tfdt for the traf's first run, else where the run in front of it ended
+ * (0 for the stream's first).  Frames are in mdhd's timescale, counted modulo 2^64.
+ * The expansion, all sums in 64 bits: sample rows {first_frame, frames, chunk = the run's index} and packet rows {absolute offset in
+ * the source arena, bytes}, the MPEG-4 section's types, so that ohgpu_alac_batch_create and ohgpu_mp4_seek take them unchanged.  A
+ * sample whose bytes leave [0, src_bytes), or whose size is above the codec's limit (alac: frame_length x channels x 5 + 64; fLaC:
+ * max_blocksize x channels x (bits / 8 + 1) + 64), is refused: its packet row is {the stream's src_offset, 0}.  Runs beyond
+ * run_capacity and samples beyond packet_capacity (or in runs beyond run_capacity) are counted, not expanded.
+ * The gather (OHGPU_MP4F_GATHER): the bytes of rows [gather_first_row, samples_available) go, in order and without gaps, to dst_offset
+ * of the destination arena.  bytes_gathered is their sum; it is 0, and nothing is written, when that exceeds dst_capacity.  No other
+ * destination byte is touched.
+ * Where this differs from the reference (tests/mp4f_textbook.py carries the same list):
+ *   - the reference plays a fragment only when its data begins right behind its moof (the three conditions at Mpeg4.cpp:4563-4568);
+ *     here a run lies wherever its offsets say;
+ *   - the reference ignores trex, tfdt and the entries' durations (Mpeg4BoxTrun::Process, Mpeg4.cpp:1499-1662, keeps sizes
+ *     alone; no box of its table is tfdt or trex); here they
+ *     give every sample its frames;
+ *   - the reference refuses a trun of 0 samples (Mpeg4.cpp:1565-1567); here it is passed over;
+ *   - the reference does not seek in a fragmented FLAC stream (the comment at Mpeg4.cpp:4778-4794); here the sample rows serve
+ *     ohgpu_mp4_seek, and gather_first_row starts the run at the sample found;
+ *   - the reference takes `sidx` for its seek table (Mpeg4BoxSidx::Process, Mpeg4.cpp:558-690); here sidx is skipped. */
+#define OHGPU_MP4F_OK              0u
+#define OHGPU_MP4F_NOT_MP4         1u
+#define OHGPU_MP4F_TRUNCATED       2u
+#define OHGPU_MP4F_INVALID         3u
+#define OHGPU_MP4F_NOT_CODEC       4u
+#define OHGPU_MP4F_UNSUPPORTED     5u
+#define OHGPU_MP4F_NOT_FRAGMENTED  6u
+#define OHGPU_MP4F_CODEC_ALAC      1u
+#define OHGPU_MP4F_CODEC_FLAC      2u
+#define OHGPU_MP4F_GATHER          1u
+#define OHGPU_MP4F_MAX_BOXES       65536u
+#define OHGPU_MP4F_MAX_SAMPLES     (1u << 24)
+#define OHGPU_MP4F_MAX_RUN_SAMPLES (1u << 16)   /* 100 minutes of 4096-sample frames in one trun */
+#define OHGPU_MP4F_ROUTE_PHASES    1u
+#define OHGPU_MP4F_ROUTE_PLAIN     2u
+
+typedef struct ohgpu_mp4f_stream_desc {   /* 64 bytes */
+    uint64_t src_offset;            /* the stream's bytes are [src_offset, + src_bytes) of the source arena, any address */
+    uint32_t src_bytes;             /* < 2^31: the initialisation segment and the media segments so far */
+    uint32_t codecs;                /* OHGPU_MP4F_CODEC_ALAC | OHGPU_MP4F_CODEC_FLAC: the sample entries a trak is taken for */
+    uint32_t flags;                 /* OHGPU_MP4F_GATHER */
+    uint32_t packet_first;          /* the stream's rows are [packet_first, + packet_capacity) of both sample tables */
+    uint32_t packet_capacity;
+    uint32_t run_first;             /* ... and [run_first, + run_capacity) of the run table */
+    uint32_t run_capacity;
+    uint32_t gather_first_row;      /* GATHER: the first row whose bytes are gathered (a seek's row; 0: from the start) */
+    uint64_t dst_offset;            /* GATHER: where the run goes in the destination arena, any address */
+    uint64_t dst_capacity;          /* GATHER: the room there */
+    uint32_t reserved[2];           /* zero */
+} ohgpu_mp4f_stream_desc;
+
+typedef struct ohgpu_mp4f_run {   /* 32 bytes: one row per trun that has samples */
+    uint64_t data_offset;           /* its first byte, absolute in the source arena (src_offset + its place, modulo 2^64: a place may be negative) */
+    uint64_t first_frame;
+    uint32_t first_sample;          /* the stream's samples in front of it: its first row */
+    uint32_t samples;
+    uint64_t bytes;                 /* the sum of its samples' sizes */
+} ohgpu_mp4f_run;
+
+typedef struct ohgpu_mp4f_stream_result {   /* 168 bytes */
+    uint32_t status;                /* OHGPU_MP4F_OK ... _NOT_FRAGMENTED */
+    uint32_t codec;                 /* the taken trak's entry fourcc ('alac', 'fLaC'); NOT_CODEC: the first trak's */
+    uint32_t track_id;              /* tkhd */
+    uint32_t timescale;             /* mdhd */
+    ohgpu_alac_config config;       /* 'alac': the inner box's; else 0 */
+    ohgpu_flac_streaminfo_t flac;   /* 'fLaC': dfLa's STREAMINFO; else 0 */
+    uint64_t duration;              /* mdhd's, or mehd's when that is 0; in timescale units */
+    uint64_t frames;                /* the sum of every sample's duration */
+    uint64_t samples;               /* of every run */
+    uint32_t runs;                  /* truns with samples */
+    uint32_t samples_available;     /* the leading rows that were not refused: what a prefix of a stream can play */
+    uint32_t samples_refused;       /* rows refused */
+    uint32_t first_bad_sample;      /* the lowest of them; OHGPU_MP4_NO_SAMPLE: none */
+    uint32_t entry_rate;            /* the sample entry's: the upper 16 bits of its 16.16 rate */
+    uint16_t entry_channels, entry_bits;
+    uint64_t bytes_gathered;
+    uint64_t moov_offset;           /* from src_offset */
+    uint64_t first_moof_offset;     /* 0: none */
+    uint64_t error_offset;          /* the box that gave a status other than OK */
+} ohgpu_mp4f_stream_result;
+
+/* Host only, no device needed: the validation ohgpu_mp4f_batch_create makes.  OHGPU_ERR_INVALID: non-zero reserved words, unknown
+ * flags, a codecs mask of 0 or with unknown bits, src_bytes >= 2^31, row, run or gather ranges that overlap or (rows, runs) run past
+ * their tables.  OHGPU_ERR_BOUNDS: a range outside its arena.  The empty batch is legal. */
+int ohgpu_mp4f_batch_check(const ohgpu_mp4f_stream_desc* descs, size_t n, size_t n_packets, size_t n_runs, uint64_t src_arena_bytes, uint64_t dst_arena_bytes);
+/* The descriptors go to the device; the tiles, the records, the three tables (every byte 0xa5 until a run writes it) and the results
+ * are the batch's.  Created under ohgpu_set_kernel_variant(1) the batch takes the plain route: one launch, a lane per stream does
+ * everything serially, the gather included (ohgpu_mp4f_batch_paths).  Both routes write the same bytes.  Freed with ohgpu_batch_destroy. */
+int ohgpu_mp4f_batch_create(ohgpu_ctx* ctx, const ohgpu_mp4f_stream_desc* descs, size_t n, size_t n_packets, size_t n_runs, uint64_t src_arena_bytes,
+                            uint64_t dst_arena_bytes, ohgpu_batch** batch);
+/* Walk, run sums, carries, expand, finish, gather: queued on the stream, nothing waits for the host.  The source arena's rule is
+ * ohgpu_mp4_batch_run's (src_base a multiple of 4, the allocation ends on one); dst_base may be NULL when no stream gathers.  The
+ * batch owns its tables: it runs on one stream at a time.  A second run, and a second batch of the same shape, allocate nothing on
+ * the device (ohgpu_device_allocations). */
+int ohgpu_mp4f_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* src_base, void* dst_base, void* stream);
+/* The last run's results and tables (each waits for that run): n = the batch's stream count, n_runs / n_packets = the tables' length.
+ * Of a stream's ranges the first min(runs, run_capacity) run rows and the first min(samples of those runs, packet_capacity) sample
+ * and packet rows are that run's. */
+int ohgpu_mp4f_batch_results(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_mp4f_stream_result* results, size_t n);
+int ohgpu_mp4f_batch_runs(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_mp4f_run* runs, size_t n_runs);
+int ohgpu_mp4f_batch_packets(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_alac_packet* packets, size_t n_packets);
+int ohgpu_mp4f_batch_samples(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_mp4_sample* samples, size_t n_packets);
+/* The last run's phases in milliseconds from device events: walk, run sums, carries, expand, finish, gather (waits for that run).
+ * The plain route is one phase: the other five read as 0. */
+int ohgpu_mp4f_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float ms[6]);
+/* The route a batch was created onto (OHGPU_MP4F_ROUTE_*), the expansion's tiles and the workgroups of the two persistent launches
+ * (0 on the plain route); the last two may be NULL. */
+int ohgpu_mp4f_batch_paths(const ohgpu_batch* batch, uint32_t* route, uint32_t* tiles, uint32_t* wave_blocks);
+/* Host only, no device needed: the walk up to the end of `moov`, as if the stream ended there, with both codecs asked for -- what a
+ * caller needs to route a stream and to fill its decoder's descriptor.  The result's status tells; the call itself fails only on a
+ * null argument or n >= 2^31. */
+int ohgpu_mp4f_head(const void* bytes, size_t n, ohgpu_mp4f_stream_result* result);
+/* Host-buffer convenience: one upload, one run, the results and the tables home, and of dst_host the bytes that were gathered.  Any
+ * of the four result pointers may be NULL; dst_host may be NULL when dst_bytes is 0. */
+int ohgpu_mp4f_process_host(ohgpu_ctx* ctx, const ohgpu_mp4f_stream_desc* descs, size_t n, size_t n_packets, size_t n_runs, const void* src_host, uint64_t src_bytes,
+                            void* dst_host, uint64_t dst_bytes, ohgpu_mp4f_stream_result* results, ohgpu_mp4f_run* runs, ohgpu_alac_packet* packets, ohgpu_mp4_sample* samples);
+/* Fragmented fLaC from host buffers to PCM: one upload, the demultiplexer gathering into a middle arena of mid_bytes that lives on the
+ * device only, one small read of its results, a FLAC batch over the gathered runs (flac_descs[i].src_offset must be
+ * mp4f_descs[i].dst_offset, an offset into the middle arena; its src_bytes is replaced by the stream's bytes_gathered -- 0 for a stream
+ * that is not fLaC; OHGPU_FLAC_FLAG_AT_FRAME is the caller's to set), and of dst_host the samples that were decoded.  Any result
+ * pointer may be NULL; frames as ohgpu_flac_batch_frames. */
+int ohgpu_mp4f_flac_process_host(ohgpu_ctx* ctx, const ohgpu_mp4f_stream_desc* mp4f_descs, const ohgpu_flac_stream_desc* flac_descs, size_t n, size_t n_packets, size_t n_runs,
+                                 const void* src_host, uint64_t src_bytes, uint64_t mid_bytes, void* dst_host, uint64_t dst_bytes,
+                                 ohgpu_mp4f_stream_result* mp4f_results, ohgpu_mp4f_run* runs, ohgpu_alac_packet* packets, ohgpu_mp4_sample* samples,
+                                 ohgpu_flac_stream_result* flac_results, ohgpu_flac_frame* frames, size_t frames_capacity, size_t* n_frames);
+/* Fragmented alac from host buffers to PCM, as ohgpu_mp4_alac_process_host: the packets are decoded where they lie (no stream may
+ * gather); stream i's packets are its rows [0, samples_available), none for a stream that is not OK or not alac. */
+int ohgpu_mp4f_alac_process_host(ohgpu_ctx* ctx, const ohgpu_mp4f_stream_desc* mp4f_descs, const ohgpu_alac_stream_desc* alac_descs, size_t n, size_t n_packets, size_t n_runs,
+                                 const void* src_host, uint64_t src_bytes, void* dst_host, uint64_t dst_bytes,
+                                 ohgpu_mp4f_stream_result* mp4f_results, ohgpu_mp4f_run* runs, ohgpu_alac_packet* packets, ohgpu_mp4_sample* samples,
+                                 ohgpu_alac_stream_result* alac_results, ohgpu_alac_packet_result* packet_results);
+
 /* ---- PCM files: WAV, AIFF and AIFC chunks walked and the audio made big-endian (the text is csrc/iff_chunk_core.h) ----
  * What CodecWav, CodecAiff and CodecAifc do: the bytes of a file, or of a prefix of one, in; the audio as the pipeline's big-endian
  * PCM out, with a result per stream.  Two launches, nothing waits for the host between them.

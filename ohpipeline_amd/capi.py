@@ -170,6 +170,21 @@ MP4_STREAM_RESULT = np.dtype([("status", "<u4"), ("codec", "<u4"), ("config", AL
                               ("mdat_bytes", "<u8"), ("error_offset", "<u8")], align=False)
 MP4_SAMPLE = np.dtype([("first_frame", "<u8"), ("frames", "<u4"), ("chunk", "<u4")], align=False)
 assert MP4_STREAM_DESC.itemsize == 32 and MP4_STREAM_RESULT.itemsize == 112 and MP4_SAMPLE.itemsize == 16
+# fragmented MPEG-4: ohgpu_mp4f_stream_desc (64 B), ohgpu_mp4f_run (32 B), ohgpu_mp4f_stream_result (168 B); the sample and
+# packet rows are MP4_SAMPLE and ALAC_PACKET
+MP4F_OK, MP4F_NOT_MP4, MP4F_TRUNCATED, MP4F_INVALID, MP4F_NOT_CODEC, MP4F_UNSUPPORTED, MP4F_NOT_FRAGMENTED = range(7)
+MP4F_CODEC_ALAC, MP4F_CODEC_FLAC, MP4F_GATHER = 1, 2, 1
+MP4F_MAX_BOXES, MP4F_MAX_SAMPLES, MP4F_MAX_RUN_SAMPLES = 65536, 1 << 24, 1 << 16
+MP4F_ROUTE_PHASES, MP4F_ROUTE_PLAIN = 1, 2
+MP4F_STREAM_DESC = np.dtype([("src_offset", "<u8"), ("src_bytes", "<u4"), ("codecs", "<u4"), ("flags", "<u4"), ("packet_first", "<u4"), ("packet_capacity", "<u4"),
+                             ("run_first", "<u4"), ("run_capacity", "<u4"), ("gather_first_row", "<u4"), ("dst_offset", "<u8"), ("dst_capacity", "<u8"),
+                             ("reserved", "<u4", (2,))], align=False)
+MP4F_RUN = np.dtype([("data_offset", "<u8"), ("first_frame", "<u8"), ("first_sample", "<u4"), ("samples", "<u4"), ("bytes", "<u8")], align=False)
+MP4F_STREAM_RESULT = np.dtype([("status", "<u4"), ("codec", "<u4"), ("track_id", "<u4"), ("timescale", "<u4"), ("config", ALAC_CONFIG), ("flac", FLAC_STREAMINFO),
+                               ("duration", "<u8"), ("frames", "<u8"), ("samples", "<u8"), ("runs", "<u4"), ("samples_available", "<u4"), ("samples_refused", "<u4"),
+                               ("first_bad_sample", "<u4"), ("entry_rate", "<u4"), ("entry_channels", "<u2"), ("entry_bits", "<u2"), ("bytes_gathered", "<u8"),
+                               ("moov_offset", "<u8"), ("first_moof_offset", "<u8"), ("error_offset", "<u8")], align=False)
+assert MP4F_STREAM_DESC.itemsize == 64 and MP4F_RUN.itemsize == 32 and MP4F_STREAM_RESULT.itemsize == 168
 # PCM files: ohgpu_iff_stream_desc (64 B), ohgpu_iff_stream_result (80 B)
 IFF_OK, IFF_NOT_IFF, IFF_TRUNCATED, IFF_INVALID, IFF_UNSUPPORTED = range(5)
 IFF_KIND_WAV, IFF_KIND_AIFF, IFF_KIND_AIFC = 1, 2, 3
@@ -287,6 +302,20 @@ SYMBOLS = {
     "ohgpu_mp4_process_host": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, _vp, _vp]),
     "ohgpu_mp4_seek": (C.c_int, [_vp, C.c_size_t, C.c_uint64, _u64p, _u64p]),
     "ohgpu_mp4_alac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
+    "ohgpu_mp4f_batch_check": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64]),
+    "ohgpu_mp4f_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
+    "ohgpu_mp4f_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "ohgpu_mp4f_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_mp4f_batch_runs": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_mp4f_batch_packets": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_mp4f_batch_samples": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_mp4f_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
+    "ohgpu_mp4f_batch_paths": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "ohgpu_mp4f_head": (C.c_int, [_vp, C.c_size_t, _vp]),
+    "ohgpu_mp4f_process_host": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "ohgpu_mp4f_flac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ohgpu_mp4f_alac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ohgpu_iff_batch_check": (C.c_int, [_vp, C.c_size_t, C.c_uint64, C.c_uint64]),
     "ohgpu_iff_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
     "ohgpu_iff_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
@@ -611,6 +640,26 @@ def _iff_descs(descs):
     d = np.ascontiguousarray(descs)
     assert d.dtype == IFF_STREAM_DESC
     return d
+
+
+def _mp4f_descs(descs):
+    d = np.ascontiguousarray(descs)
+    assert d.dtype == MP4F_STREAM_DESC
+    return d
+
+
+def mp4f_batch_check(descs, n_packets, n_runs, src_arena_bytes, dst_arena_bytes):
+    """The validation of ctx.mp4f_batch without a device (ohgpu_mp4f_batch_check): OhGpuError on a bad descriptor."""
+    d = _mp4f_descs(descs)
+    check(lib().ohgpu_mp4f_batch_check(_ptr_or_none(d), d.size, n_packets, n_runs, src_arena_bytes, dst_arena_bytes))
+
+
+def mp4f_head(data):
+    """The walk of a fragmented stream up to the end of moov (ohgpu_mp4f_head; host only): an MP4F_STREAM_RESULT record."""
+    raw = bytes(data)
+    res = np.zeros(1, dtype=MP4F_STREAM_RESULT)
+    check(lib().ohgpu_mp4f_head(raw, len(raw), res.ctypes.data_as(C.c_void_p)))
+    return res[0]
 
 
 def iff_batch_check(descs, src_arena_bytes, dst_arena_bytes):
@@ -1125,6 +1174,73 @@ class Context:
         check(lib().ohgpu_mp4_alac_process_host(self._h, _ptr_or_none(m), _ptr_or_none(a), m.size, n_packets, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst), dst.nbytes,
                                                 _ptr_or_none(res), _ptr_or_none(pk), _ptr_or_none(sm), _ptr_or_none(ares), _ptr_or_none(pres)))
         return res, pk, sm, ares, pres
+
+    def mp4f_batch(self, descs, n_packets, n_runs, src_arena_bytes, dst_arena_bytes):
+        d = _mp4f_descs(descs)
+        b = C.c_void_p()
+        check(lib().ohgpu_mp4f_batch_create(self._h, _ptr_or_none(d), d.size, n_packets, n_runs, src_arena_bytes, dst_arena_bytes, C.byref(b)))
+        return b
+
+    def mp4f_run(self, batch, d_src, d_dst, stream=None):
+        """Walk, run sums, carries, expand, finish, gather (ohgpu_mp4f_batch_run): queued on the stream."""
+        check(lib().ohgpu_mp4f_batch_run(self._h, batch, d_src, d_dst, stream))
+
+    def mp4f_results(self, batch, n, n_packets, n_runs):
+        """The last run's (MP4F_STREAM_RESULT per stream, the run table, the packet table, the sample table); waits for the run."""
+        res, runs = np.zeros(n, dtype=MP4F_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
+        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
+        check(lib().ohgpu_mp4f_batch_results(self._h, batch, _ptr_or_none(res), n))
+        check(lib().ohgpu_mp4f_batch_runs(self._h, batch, _ptr_or_none(runs), n_runs))
+        check(lib().ohgpu_mp4f_batch_packets(self._h, batch, _ptr_or_none(pk), n_packets))
+        check(lib().ohgpu_mp4f_batch_samples(self._h, batch, _ptr_or_none(sm), n_packets))
+        return res, runs, pk, sm
+
+    def mp4f_phase_ms(self, batch):
+        """(walk, run sums, carries, expand, finish, gather) of the last run in milliseconds."""
+        ms = (C.c_float * 6)()
+        check(lib().ohgpu_mp4f_batch_phase_ms(self._h, batch, ms))
+        return tuple(float(v) for v in ms)
+
+    def mp4f_paths(self, batch):
+        """{route, tiles, wave_blocks} of a fragmented MPEG-4 batch (ohgpu_mp4f_batch_paths)."""
+        route, tiles, blocks = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        check(lib().ohgpu_mp4f_batch_paths(batch, C.byref(route), C.byref(tiles), C.byref(blocks)))
+        return dict(route=int(route.value), tiles=int(tiles.value), wave_blocks=int(blocks.value))
+
+    def mp4f_process_host(self, descs, n_packets, n_runs, src, dst):
+        """Host bytes in (ohgpu_mp4f_process_host), the gathered runs into dst; returns (results, run table, packet table, sample table)."""
+        d = _mp4f_descs(descs)
+        res, runs = np.zeros(d.size, dtype=MP4F_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
+        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
+        check(lib().ohgpu_mp4f_process_host(self._h, _ptr_or_none(d), d.size, n_packets, n_runs, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst), dst.nbytes,
+                                            _ptr_or_none(res), _ptr_or_none(runs), _ptr_or_none(pk), _ptr_or_none(sm)))
+        return res, runs, pk, sm
+
+    def mp4f_flac_process_host(self, mp4f_descs, flac_descs, n_packets, n_runs, src, mid_bytes, dst, frames_capacity=0):
+        """Fragmented fLaC from host buffers to PCM (ohgpu_mp4f_flac_process_host); returns (results, run table, packet table, sample table,
+        FLAC results, frames)."""
+        m, f = _mp4f_descs(mp4f_descs), np.ascontiguousarray(flac_descs)
+        assert f.dtype == FLAC_STREAM_DESC and f.size == m.size
+        res, runs = np.zeros(m.size, dtype=MP4F_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
+        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
+        fres, frames = np.zeros(m.size, dtype=FLAC_STREAM_RESULT), np.zeros(frames_capacity, dtype=FLAC_FRAME)
+        n_frames = C.c_size_t(0)
+        check(lib().ohgpu_mp4f_flac_process_host(self._h, _ptr_or_none(m), _ptr_or_none(f), m.size, n_packets, n_runs, _ptr_or_none(src), src.nbytes, mid_bytes,
+                                                 _ptr_or_none(dst), dst.nbytes, _ptr_or_none(res), _ptr_or_none(runs), _ptr_or_none(pk), _ptr_or_none(sm),
+                                                 _ptr_or_none(fres), _ptr_or_none(frames), frames_capacity, C.byref(n_frames)))
+        return res, runs, pk, sm, fres, frames[:min(int(n_frames.value), frames_capacity)]
+
+    def mp4f_alac_process_host(self, mp4f_descs, alac_descs, n_packets, n_runs, src, dst):
+        """Fragmented alac from host buffers to PCM (ohgpu_mp4f_alac_process_host); returns (results, run table, packet table, sample table,
+        Apple Lossless stream results, packet results indexed as the tables are)."""
+        m, a = _mp4f_descs(mp4f_descs), np.ascontiguousarray(alac_descs)
+        assert a.dtype == ALAC_STREAM_DESC and a.size == m.size
+        res, runs = np.zeros(m.size, dtype=MP4F_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
+        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
+        ares, pres = np.zeros(m.size, dtype=ALAC_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET_RESULT)
+        check(lib().ohgpu_mp4f_alac_process_host(self._h, _ptr_or_none(m), _ptr_or_none(a), m.size, n_packets, n_runs, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst),
+                                                 dst.nbytes, _ptr_or_none(res), _ptr_or_none(runs), _ptr_or_none(pk), _ptr_or_none(sm), _ptr_or_none(ares), _ptr_or_none(pres)))
+        return res, runs, pk, sm, ares, pres
 
     def iff_batch(self, descs, src_arena_bytes, dst_arena_bytes):
         d = _iff_descs(descs)

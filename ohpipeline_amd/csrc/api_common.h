@@ -77,12 +77,13 @@ int run_guard(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, BatchKi
 // Batches with per-launch device state (ohgpu_batch::last_done): a launch on another stream while the last one runs is refused.
 int claim_single_launch(const ohgpu_batch* b, hipStream_t s, const char* who);
 inline void launched(const ohgpu_batch* b, hipStream_t s) { b->last_untracked = false; if (b->last_done) (void)hipEventRecord(b->last_done, s); }
-// ---- the batch states (RunState, ohgpu_internal.h: FlacState, AlacState -- RAOP's too --, OhmRxState, OggState, Mp4State, IffState, DsdFileState).
+// ---- the batch states (RunState, ohgpu_internal.h: FlacState, AlacState -- RAOP's too --, OhmRxState, OggState, Mp4State, Mp4fState, IffState, DsdFileState).
 // In a plan: state_events creates the n events of the family's phases (the last is the end of a run); dev_array is a device block of
 // `count` elements from the context's block cache, entered in the state's registry, and filled from `host` (synchronously) where one is
 // given -- a zero count allocates nothing and leaves the pointer null; state_own enters a block that a run allocates.
 inline int state_events(RunState& st, int n)
 {
+    if (n < 1 || n > RunState::kMaxEvents) return set_error(OHGPU_ERR_INVALID, "state_events: %d events where a state holds %d", n, RunState::kMaxEvents);
     st.n_events = n;
     for (int k = 0; k < n; k++) OHGPU_HIP_TRY_ALLOC(hipEventCreate(&st.ev[k]));
     return OHGPU_OK;

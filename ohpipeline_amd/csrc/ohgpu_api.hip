@@ -312,8 +312,9 @@ static const struct { const char* noun; void (*release)(ohgpu_ctx*, ohgpu_batch*
     {"an MPEG-4", mp4_free, false},                 // kBatchMp4
     {"a PCM file", iff_free, false},                // kBatchIff
     {"a DSD file", dsd_file_free, false},           // kBatchDsdFile
+    {"a fragmented MPEG-4", mp4f_free, false},      // kBatchMp4f
 };
-static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchDsdFile + 1, "a row per BatchKind");
+static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchMp4f + 1, "a row per BatchKind");
 
 int run_guard(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, BatchKind kind, bool empty, bool null_src_ok,
               const void* src_base, const void* dst_base, bool needs_dst)

@@ -21,6 +21,7 @@
 #include "flac_frame_core.h"
 #include "ogg_page_core.h"
 #include "mp4_box_core.h"
+#include "mp4_frag_core.h"
 #include "iff_chunk_core.h"
 #include "dsd_file_core.h"
 #include "ohm_rx_core.h"
@@ -342,13 +343,14 @@ struct OhmPlan {
     uint32_t n_unfolded = 0, n_unfolded_generic = 0;
 };
 
-// ---- what the batch states below share (FlacState, AlacState, OhmRxState, OggState, Mp4State, IffState, DsdFileState; RaopState for its blocks and
+// ---- what the batch states below share (FlacState, AlacState, OhmRxState, OggState, Mp4State, Mp4fState, IffState, DsdFileState; RaopState for its blocks and
 // its one event).  The events of a run's phases: n_events are in use, the last of them is recorded at the run's end.  The tracking of
 // run_begin / run_end (api_common.h).  The registry of the device blocks that die with the batch: WHERE each pointer member lives (a
 // state is heap-allocated and never moves), not what it holds, so a block that a run frees and replaces (FLAC's lists and rows) needs
 // nothing more.  state_events, dev_array, state_release and fetch_after_run (api_common.h) are what works on it.
 struct RunState {
-    hipEvent_t ev[5] = {};
+    static constexpr int kMaxEvents = 7;  // (the family with the most phases has six and the end of a run: fragmented MPEG-4)
+    hipEvent_t ev[kMaxEvents] = {};
     int n_events = 0;
     hipStream_t last_stream = nullptr;
     bool ran = false, ended = false;      // (ended: the last run recorded its end -- run_begin, api_common.h)
@@ -487,6 +489,32 @@ static_assert(sizeof(ohgpu_mp4_stream_desc) == sizeof(mp4box::Stream) && sizeof(
               sizeof(ohgpu_alac_packet) == sizeof(mp4box::Row) && sizeof(ohgpu_alac_config) == sizeof(mp4box::Config) && offsetof(ohgpu_mp4_stream_result, error_offset) == offsetof(mp4box::Result, error_offset) &&
               offsetof(ohgpu_mp4_stream_result, first_bad_sample) == offsetof(mp4box::Result, first_bad_sample), "MPEG-4 layouts");
 
+// ---- fragmented MPEG-4 (csrc/mp4_frag_kernel.hip): the descriptors, the map of the run slots and the tiles of the
+// expansion (both made at create, from the capacities), the walk's records of streams and runs, the three tables and the results of the
+// last run.  The batch's d_descs holds nothing.
+struct Mp4fTile { uint32_t stream, s0; };             // one workgroup's share: samples [s0, s0 + mp4frag::kTile) of a stream
+struct Mp4fState : RunState {
+    size_t n_streams = 0, n_packets = 0, n_runs = 0;
+    uint32_t n_tiles = 0, wave_blocks = 0;            // (wave_blocks: the size of the two persistent launches, a wave a run slot)
+    bool plain = false;                               // created under kernel variant 1: one launch, a lane per stream
+    bool gathers = false;                             // some stream gathers: either route needs the destination arena
+    void* d_streams = nullptr;                        // mp4frag::Stream[n_streams]
+    void* d_results = nullptr;                        // mp4frag::Result[n_streams]
+    void* d_recs = nullptr;                           // mp4frag::Rec[n_streams]
+    void* d_runrecs = nullptr;                        // mp4frag::RunRec[n_runs], indexed as the run table is
+    void* d_slot_stream = nullptr;                    // uint32[n_runs]: the stream whose range the run slot lies in, kNone for a guard row
+    void* d_tiles = nullptr;                          // Mp4fTile[n_tiles]
+    void* d_runs = nullptr;                           // mp4frag::Run[n_runs]
+    void* d_packets = nullptr;                        // mp4box::Row[n_packets]
+    void* d_samples = nullptr;                        // mp4box::Sample[n_packets]
+};
+static_assert(sizeof(ohgpu_mp4f_stream_desc) == sizeof(mp4frag::Stream) && sizeof(ohgpu_mp4f_stream_result) == sizeof(mp4frag::Result) && sizeof(ohgpu_mp4f_run) == sizeof(mp4frag::Run) &&
+              sizeof(ohgpu_flac_streaminfo_t) == sizeof(mp4frag::FlacInfo) && offsetof(ohgpu_mp4f_stream_desc, dst_offset) == offsetof(mp4frag::Stream, dst_offset) &&
+              offsetof(ohgpu_mp4f_stream_result, flac) == offsetof(mp4frag::Result, flac) && offsetof(ohgpu_mp4f_stream_result, error_offset) == offsetof(mp4frag::Result, error_offset) &&
+              offsetof(ohgpu_mp4f_stream_result, first_bad_sample) == offsetof(mp4frag::Result, first_bad_sample) && offsetof(ohgpu_mp4f_run, bytes) == offsetof(mp4frag::Run, bytes) &&
+              offsetof(ohgpu_flac_streaminfo_t, md5) == offsetof(mp4frag::FlacInfo, md5) && mp4frag::kMaxBoxes == OHGPU_MP4F_MAX_BOXES && mp4frag::kMaxSamples == OHGPU_MP4F_MAX_SAMPLES && mp4frag::kMaxRunSamples == OHGPU_MP4F_MAX_RUN_SAMPLES &&
+              mp4frag::kNotFragmented == OHGPU_MP4F_NOT_FRAGMENTED && mp4frag::kGather == OHGPU_MP4F_GATHER, "fragmented MPEG-4 layouts");
+
 // ---- PCM files (csrc/iff_pcm_kernel.hip): the descriptors, the list of the conversion's workgroups, the walk's record
 // of each stream's run and the results of the last run.  The batch's d_descs holds nothing.
 constexpr uint32_t kIffGroupPieces = 1024;            // the pieces one workgroup of the conversion takes: tests/test_gpu_iff_textbook.py restates it
@@ -527,7 +555,7 @@ static_assert(sizeof(ohgpu_dsd_file_stream_desc) == sizeof(dsdfile::Stream) && s
               dsdfile::kDsf == OHGPU_DSD_DSF && dsdfile::kDff == OHGPU_DSD_DFF && dsdfile::kDsf == OHGPU_DSD_FILE_KIND_DSF && dsdfile::kDff == OHGPU_DSD_FILE_KIND_DFF &&
               dsdfile::kFillByte == OHGPU_DSD_SILENCE_BYTE && dsdfile::kMaxChunks == OHGPU_DSD_FILE_MAX_CHUNKS, "DSD file layouts");
 
-enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11, kBatchOhmRx = 12, kBatchOgg = 13, kBatchMp4 = 14, kBatchIff = 15, kBatchDsdFile = 16 };
+enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11, kBatchOhmRx = 12, kBatchOgg = 13, kBatchMp4 = 14, kBatchIff = 15, kBatchDsdFile = 16, kBatchMp4f = 17 };
 
 }  // namespace ohgpu
 
@@ -639,6 +667,7 @@ struct ohgpu_batch {
     ohgpu::Mp4State* mp4 = nullptr;     // kBatchMp4 only
     ohgpu::IffState* iff = nullptr;     // kBatchIff only
     ohgpu::DsdFileState* dsdfile = nullptr;   // kBatchDsdFile only
+    ohgpu::Mp4fState* mp4f = nullptr;   // kBatchMp4f only
     void*    d_pull_tiles = nullptr;   // kBatchSrcPull: PullTile[n_pull_tiles] on the device (d_descs holds the messages)
     uint32_t n_pull_tiles = 0;
     // kBatchSrc whose messages differ in layout: one uniform batch per layout (each with its own block-kernel plan), run one
@@ -680,7 +709,7 @@ inline int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? OHGPU_ERR_
         if (err_ != OHGPU_OK) return err_;       \
     } while (0)
 
-// The release functions (free_pcm_line, free_fmt_line, free_dsd_line, flac_free, alac_free, raop_free, free_flywheel, free_src_fast, free_ohm, ohm_rx_free, ogg_free, mp4_free, iff_free, dsd_file_free): what
+// The release functions (free_pcm_line, free_fmt_line, free_dsd_line, flac_free, alac_free, raop_free, free_flywheel, free_src_fast, free_ohm, ohm_rx_free, ogg_free, mp4_free, iff_free, dsd_file_free, mp4f_free): what
 // ohgpu_batch_destroy's table calls (csrc/ohgpu_api.hip).  Each takes a PARTLY BUILT batch -- null pointers, a plan that was never
 // made -- and leaves the plan reset: a create that fails at any point hands its batch to ohgpu_batch_destroy and returns.
 // The eight whose state is a RunState (flac_free ... dsd_file_free) are one shape -- if the pointer is set: state_release (api_common.h), which
@@ -740,6 +769,12 @@ uint32_t ogg_wave_blocks(uint64_t items, uint32_t cus);   // the verify and gath
 int  mp4_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const mp4box::Stream* streams);   // tiles, carries and tables onto the device (b->mp4 holds the counts)
 void mp4_free(ohgpu_ctx* ctx, ohgpu_batch* b);
 int  mp4_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, hipStream_t s);
+// csrc/mp4_frag_kernel.hip.  The run sums and the gather are persistent (a wave a run slot, mp4f_wave_blocks workgroups); the rest is a
+// lane a stream (walk, carries, finish) or a workgroup a tile (expand).
+int  mp4f_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const mp4frag::Stream* streams);   // the slot map, the tiles and the tables onto the device (b->mp4f holds the counts)
+void mp4f_free(ohgpu_ctx* ctx, ohgpu_batch* b);
+int  mp4f_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
+uint32_t mp4f_wave_blocks(uint64_t slots, uint32_t cus);   // the persistent launches' size: the rule tests/test_gpu_mp4f_textbook.py restates
 // csrc/iff_pcm_kernel.hip.  No launch is persistent: a lane a stream (walk), a workgroup per kIffGroupPieces pieces of a run (convert).
 int  iff_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const iffchunk::Stream* streams);   // the descriptors and the workgroup list onto the device
 void iff_free(ohgpu_ctx* ctx, ohgpu_batch* b);
