@@ -120,14 +120,6 @@ int alac_plan(ohgpu_ctx* ctx, ohgpu_batch* b)
     return OHGPU_OK;
 }
 
-void alac_free(ohgpu_ctx* ctx, ohgpu_batch* b)
-{
-    if (!b->alac) return;
-    state_release(ctx, *b->alac);
-    delete b->alac;
-    b->alac = nullptr;
-}
-
 int alac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s)
 {
     AlacState& a = *b->alac;

@@ -77,7 +77,8 @@ int run_guard(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, BatchKi
 // Batches with per-launch device state (ohgpu_batch::last_done): a launch on another stream while the last one runs is refused.
 int claim_single_launch(const ohgpu_batch* b, hipStream_t s, const char* who);
 inline void launched(const ohgpu_batch* b, hipStream_t s) { b->last_untracked = false; if (b->last_done) (void)hipEventRecord(b->last_done, s); }
-// ---- the batch states (RunState, ohgpu_internal.h: FlacState, AlacState -- RAOP's too --, OhmRxState, OggState, Mp4State, Mp4fState, IffState, DsdFileState).
+// ---- the batch states (RunState, ohgpu_internal.h: FlacState, AlacState -- RAOP's too --, OhmRxState, OggState, Mp4State, Mp4fState, and
+// FileState of the two file layers, whose whole shell is api_file.h).
 // In a plan: state_events creates the n events of the family's phases (the last is the end of a run); dev_array is a device block of
 // `count` elements from the context's block cache, entered in the state's registry, and filled from `host` (synchronously) where one is
 // given -- a zero count allocates nothing and leaves the pointer null; state_own enters a block that a run allocates.
@@ -106,6 +107,24 @@ inline void state_release(ohgpu_ctx* ctx, RunState& st)
     for (void** p : st.blocks) if (*p) { ctx_dev_free(ctx, *p); *p = nullptr; }
     for (hipEvent_t& e : st.ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
 }
+// A family's whole release (ohgpu_batch_destroy's table, csrc/ohgpu_api.hip, calls it on the batch's pointer): nothing for a null
+// pointer -- a batch that never got its state, or one released before --, else state_release, delete, and the pointer nulled.
+template <class S>
+void state_free(ohgpu_ctx* ctx, S*& p)
+{
+    if (!p) return;
+    state_release(ctx, *p);
+    delete p;
+    p = nullptr;
+}
+// The front of a results, table or phase call: the context, then "<who>: not <noun> batch" (the noun with its article: "an Ogg") unless
+// the batch is of `kind`.
+inline int state_guard(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, BatchKind kind, const char* noun)
+{
+    CTX_GUARD(who);
+    if (!batch || batch->kind != kind) return set_error(OHGPU_ERR_INVALID, "%s: not %s batch", who, noun);
+    return OHGPU_OK;
+}
 // The device records serve ONE RUN AT A TIME, and a run never refuses a stream: run_begin is the first line of the family's run, run_end
 // its last.  A run on another stream than the last one's first waits, on the host, for the last run -- on the EVENT that run recorded
 // at its end, never on its stream, which the caller may have destroyed since; a run that returned an error half way recorded no end,
@@ -132,6 +151,21 @@ inline int fetch_after_run(const char* who, const RunState& st, void* dst, const
     OHGPU_HIP_TRY(hipEventSynchronize(st.end_event()));
     if (bytes) OHGPU_HIP_TRY(hipMemcpy(dst, d_src, bytes, hipMemcpyDeviceToHost));
     return OHGPU_OK;
+}
+// A table of the last run, home, behind state_guard: "<who>: room for <n> <wording> <have><tail>" unless n is what the batch has and
+// there is somewhere to put it (the families word it differently: `wording` is "rows, the batch's tables have", "records, the batch's
+// table has", ...); nothing to fetch from an empty table or for a batch of no streams; then fetch_after_run of n rows of row_bytes.
+inline int fetch_table(const char* who, const RunState& st, const char* wording, const char* tail, size_t n, size_t have, size_t n_streams, void* out,
+                       const void* d_src, size_t row_bytes)
+{
+    if (n != have || (n && !out)) return set_error(OHGPU_ERR_INVALID, "%s: room for %zu %s %zu%s", who, n, wording, have, tail);
+    if (!n || !n_streams) return OHGPU_OK;
+    return fetch_after_run(who, st, out, d_src, n * row_bytes);
+}
+// ... the stream results: "<who>: room for <n> results, the batch has <n_streams> streams"
+inline int fetch_results(const char* who, const RunState& st, size_t n, size_t n_streams, void* out, const void* d_results, size_t row_bytes)
+{
+    return fetch_table(who, st, "results, the batch has", " streams", n, n_streams, n_streams, out, d_results, row_bytes);
 }
 // (first, count) ranges of a batch check that must not overlap ("<who>: the <noun> ranges [a, +b) and [c, +d) overlap"); sorts them
 inline int ranges_disjoint(const char* who, const char* noun, std::vector<std::pair<uint64_t, uint64_t>>& ranges)

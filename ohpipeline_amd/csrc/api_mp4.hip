@@ -22,12 +22,9 @@ int mp4_check_desc(const ohgpu_mp4_stream_desc& d, size_t i, size_t n_packets, u
 
 int mp4_fetch(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, bool samples, void* out, size_t n_packets)
 {
-    CTX_GUARD(who);
-    if (!batch || batch->kind != kBatchMp4) return set_error(OHGPU_ERR_INVALID, "%s: not an MPEG-4 batch", who);
+    OHGPU_TRY(state_guard(ctx, who, batch, kBatchMp4, "an MPEG-4"));
     const Mp4State& g = *batch->mp4;
-    if (n_packets != g.n_packets || (n_packets && !out)) return set_error(OHGPU_ERR_INVALID, "%s: room for %zu rows, the batch's tables have %zu", who, n_packets, g.n_packets);
-    if (!n_packets || !g.n_streams) return OHGPU_OK;
-    return fetch_after_run(who, g, out, samples ? g.d_samples : g.d_packets, n_packets * 16u);
+    return fetch_table(who, g, "rows, the batch's tables have", "", n_packets, g.n_packets, g.n_streams, out, samples ? g.d_samples : g.d_packets, 16u);
 }
 
 }  // namespace
@@ -74,12 +71,9 @@ int ohgpu_mp4_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* sr
 
 int ohgpu_mp4_batch_results(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_mp4_stream_result* results, size_t n)
 {
-    CTX_GUARD("ohgpu_mp4_batch_results");
-    if (!batch || batch->kind != kBatchMp4) return set_error(OHGPU_ERR_INVALID, "ohgpu_mp4_batch_results: not an MPEG-4 batch");
+    OHGPU_TRY(state_guard(ctx, "ohgpu_mp4_batch_results", batch, kBatchMp4, "an MPEG-4"));
     const Mp4State& g = *batch->mp4;
-    if (n != g.n_streams || (n && !results)) return set_error(OHGPU_ERR_INVALID, "ohgpu_mp4_batch_results: room for %zu results, the batch has %zu streams", n, g.n_streams);
-    if (!n) return OHGPU_OK;
-    return fetch_after_run("ohgpu_mp4_batch_results", g, results, g.d_results, n * sizeof(*results));
+    return fetch_results("ohgpu_mp4_batch_results", g, n, g.n_streams, results, g.d_results, sizeof(*results));
 }
 
 int ohgpu_mp4_batch_packets(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_alac_packet* packets, size_t n_packets)

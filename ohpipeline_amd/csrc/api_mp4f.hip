@@ -25,22 +25,12 @@ int mp4f_check_desc(const ohgpu_mp4f_stream_desc& d, size_t i, size_t n_packets,
     return arena_span("mp4f desc", i, "gathers into", d.dst_offset, d.dst_capacity, dst_arena_bytes, "destination");
 }
 
-int mp4f_state(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, const Mp4fState** g)
-{
-    CTX_GUARD(who);
-    if (!batch || batch->kind != kBatchMp4f) return set_error(OHGPU_ERR_INVALID, "%s: not a fragmented MPEG-4 batch", who);
-    *g = batch->mp4f;
-    return OHGPU_OK;
-}
-
 int mp4f_fetch(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, int table, void* out, size_t n_rows)
 {
-    const Mp4fState* g = nullptr;
-    OHGPU_TRY(mp4f_state(ctx, who, batch, &g));
-    const size_t have = table == 0 ? g->n_runs : g->n_packets;
-    if (n_rows != have || (n_rows && !out)) return set_error(OHGPU_ERR_INVALID, "%s: room for %zu rows, the batch's table has %zu", who, n_rows, have);
-    if (!n_rows || !g->n_streams) return OHGPU_OK;
-    return fetch_after_run(who, *g, out, table == 0 ? g->d_runs : table == 1 ? g->d_packets : g->d_samples, n_rows * (table == 0 ? sizeof(ohgpu_mp4f_run) : 16u));
+    OHGPU_TRY(state_guard(ctx, who, batch, kBatchMp4f, "a fragmented MPEG-4"));
+    const Mp4fState& g = *batch->mp4f;
+    return fetch_table(who, g, "rows, the batch's table has", "", n_rows, table == 0 ? g.n_runs : g.n_packets, g.n_streams, out,
+                       table == 0 ? g.d_runs : table == 1 ? g.d_packets : g.d_samples, table == 0 ? sizeof(ohgpu_mp4f_run) : 16u);
 }
 
 // what ohgpu_mp4f_process_host and the two decoder calls fetch after a run; any pointer may be null
@@ -108,11 +98,9 @@ int ohgpu_mp4f_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* s
 
 int ohgpu_mp4f_batch_results(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_mp4f_stream_result* results, size_t n)
 {
-    const Mp4fState* g = nullptr;
-    OHGPU_TRY(mp4f_state(ctx, "ohgpu_mp4f_batch_results", batch, &g));
-    if (n != g->n_streams || (n && !results)) return set_error(OHGPU_ERR_INVALID, "ohgpu_mp4f_batch_results: room for %zu results, the batch has %zu streams", n, g->n_streams);
-    if (!n) return OHGPU_OK;
-    return fetch_after_run("ohgpu_mp4f_batch_results", *g, results, g->d_results, n * sizeof(*results));
+    OHGPU_TRY(state_guard(ctx, "ohgpu_mp4f_batch_results", batch, kBatchMp4f, "a fragmented MPEG-4"));
+    const Mp4fState& g = *batch->mp4f;
+    return fetch_results("ohgpu_mp4f_batch_results", g, n, g.n_streams, results, g.d_results, sizeof(*results));
 }
 
 int ohgpu_mp4f_batch_runs(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_mp4f_run* runs, size_t n_runs)
@@ -132,11 +120,11 @@ int ohgpu_mp4f_batch_samples(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_mp4
 
 int ohgpu_mp4f_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float ms[6])
 {
-    const Mp4fState* g = nullptr;
-    OHGPU_TRY(mp4f_state(ctx, "ohgpu_mp4f_batch_phase_ms", batch, &g));
+    OHGPU_TRY(state_guard(ctx, "ohgpu_mp4f_batch_phase_ms", batch, kBatchMp4f, "a fragmented MPEG-4"));
     if (!ms) return set_error(OHGPU_ERR_INVALID, "ohgpu_mp4f_batch_phase_ms: bad argument");
-    const int err = phase_ms("ohgpu_mp4f_batch_phase_ms", g->ran, g->ev, 6, ms);
-    if (err == OHGPU_OK && g->plain) ms[1] = ms[2] = ms[3] = ms[4] = ms[5] = 0.0f;      // (one launch: what lies between the later events is no phase)
+    const Mp4fState& g = *batch->mp4f;
+    const int err = phase_ms("ohgpu_mp4f_batch_phase_ms", g.ran, g.ev, 6, ms);
+    if (err == OHGPU_OK && g.plain) ms[1] = ms[2] = ms[3] = ms[4] = ms[5] = 0.0f;      // (one launch: what lies between the later events is no phase)
     return err;
 }
 

@@ -69,23 +69,16 @@ int ohgpu_ogg_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* sr
 
 int ohgpu_ogg_batch_results(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_ogg_stream_result* results, size_t n)
 {
-    CTX_GUARD("ohgpu_ogg_batch_results");
-    if (!batch || batch->kind != kBatchOgg) return set_error(OHGPU_ERR_INVALID, "ohgpu_ogg_batch_results: not an Ogg batch");
+    OHGPU_TRY(state_guard(ctx, "ohgpu_ogg_batch_results", batch, kBatchOgg, "an Ogg"));
     const OggState& g = *batch->ogg;
-    if (n != g.n_streams || (n && !results)) return set_error(OHGPU_ERR_INVALID, "ohgpu_ogg_batch_results: room for %zu results, the batch has %zu streams", n, g.n_streams);
-    if (!n) return OHGPU_OK;
-    return fetch_after_run("ohgpu_ogg_batch_results", g, results, g.d_results, n * sizeof(*results));
+    return fetch_results("ohgpu_ogg_batch_results", g, n, g.n_streams, results, g.d_results, sizeof(*results));
 }
 
 int ohgpu_ogg_batch_packets(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_ogg_packet* packets, size_t n_packets)
 {
-    CTX_GUARD("ohgpu_ogg_batch_packets");
-    if (!batch || batch->kind != kBatchOgg) return set_error(OHGPU_ERR_INVALID, "ohgpu_ogg_batch_packets: not an Ogg batch");
+    OHGPU_TRY(state_guard(ctx, "ohgpu_ogg_batch_packets", batch, kBatchOgg, "an Ogg"));
     const OggState& g = *batch->ogg;
-    if (n_packets != g.n_packets || (n_packets && !packets))
-        return set_error(OHGPU_ERR_INVALID, "ohgpu_ogg_batch_packets: room for %zu records, the batch's table has %zu", n_packets, g.n_packets);
-    if (!n_packets || !g.n_streams) return OHGPU_OK;
-    return fetch_after_run("ohgpu_ogg_batch_packets", g, packets, g.d_packets, n_packets * sizeof(*packets));
+    return fetch_table("ohgpu_ogg_batch_packets", g, "records, the batch's table has", "", n_packets, g.n_packets, g.n_streams, packets, g.d_packets, sizeof(*packets));
 }
 
 int ohgpu_ogg_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float ms[4])

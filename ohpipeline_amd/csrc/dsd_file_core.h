@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "dsd_perm.h"
+#include "field_bytes.h"
 
 #if defined(__HIPCC__)
 #define DSDF_HD __host__ __device__ __forceinline__
@@ -39,7 +40,7 @@ enum Status : uint32_t { kOk = 0, kNotDsd = 1, kTruncated = 2, kInvalid = 3, kUn
 enum Kind : uint32_t { kNoKind = 0, kDsf = 2, kDff = 3 };            // OHGPU_DSD_DSF, OHGPU_DSD_DFF: the packers' kinds
 constexpr uint32_t kMaxChunks = 4096, kPieceChunks = 2048, kUnitChunks = 8, kFillByte = 0x69;
 constexpr uint32_t kPlane = 4096, kPair = 2 * kPlane, kPairChunks = kPlane / 2;
-constexpr uint32_t fourcc(char a, char b, char c, char d) { return ((uint32_t)(uint8_t)a << 24) | ((uint32_t)(uint8_t)b << 16) | ((uint32_t)(uint8_t)c << 8) | (uint8_t)d; }
+using fieldbytes::fourcc;
 
 struct Stream {               // 64 bytes = ohgpu_dsd_file_stream_desc
     uint64_t src_offset;
@@ -63,31 +64,13 @@ struct Rec {                  // 48 bytes: the walk's record for the conversion
 };
 static_assert(sizeof(Stream) == 64 && sizeof(Result) == 96 && sizeof(Rec) == 48, "DSD file layouts");
 
-// ---- bytes.  The caller has made sure that [pos, pos + width) lies inside the stream.  On the device a field is read as the aligned
-// dword(s) that hold it, joined by shifts (csrc/mp4_box_core.h has the reasons); the CPU driver builds both readers.
-#if defined(__HIP_DEVICE_COMPILE__) || defined(DSDF_ALIGNED_READS)
-DSDF_HD uint32_t le32(const uint8_t* p, uint64_t pos)
-{
-    const uintptr_t a = (uintptr_t)(p + pos);
-    const uint32_t* w = (const uint32_t*)(a & ~(uintptr_t)3);
-    const uint32_t shift = (uint32_t)(a & 3u) * 8u;
-    uint32_t v = w[0];
-    if (shift) v = (v >> shift) | (w[1] << (32u - shift));
-    return v;
-}
-DSDF_HD uint32_t u8(const uint8_t* p, uint64_t pos)
-{
-    const uintptr_t a = (uintptr_t)(p + pos);
-    return (*(const uint32_t*)(a & ~(uintptr_t)3) >> ((uint32_t)(a & 3u) * 8u)) & 0xffu;
-}
-#else
-DSDF_HD uint32_t le32(const uint8_t* p, uint64_t pos) { return (uint32_t)p[pos] | ((uint32_t)p[pos + 1] << 8) | ((uint32_t)p[pos + 2] << 16) | ((uint32_t)p[pos + 3] << 24); }
-DSDF_HD uint32_t u8(const uint8_t* p, uint64_t pos) { return p[pos]; }
-#endif
-DSDF_HD uint32_t be32(const uint8_t* p, uint64_t pos) { return __builtin_bswap32(le32(p, pos)); }
-DSDF_HD uint32_t be16(const uint8_t* p, uint64_t pos) { return (u8(p, pos) << 8) | u8(p, pos + 1); }
-DSDF_HD uint64_t le64(const uint8_t* p, uint64_t pos) { return (uint64_t)le32(p, pos) | ((uint64_t)le32(p, pos + 4) << 32); }
-DSDF_HD uint64_t be64(const uint8_t* p, uint64_t pos) { return ((uint64_t)be32(p, pos) << 32) | be32(p, pos + 4); }
+// ---- bytes: csrc/field_bytes.h's reader, aligned dwords on the device
+using fieldbytes::u8;
+using fieldbytes::le32;
+using fieldbytes::le64;
+using fieldbytes::be16;
+using fieldbytes::be32;
+using fieldbytes::be64;
 
 struct Found { uint32_t kind, rate, version, channel_type; uint64_t sample_count, chunks_total, data_offset, data_bytes, metadata; };
 

@@ -16,7 +16,7 @@
 // [dst_offset, + dst_bytes_capacity), which the same check placed inside the destination arena and apart from every other stream's.
 #include <hip/hip_runtime.h>
 
-#include "api_common.h"
+#include "api_file.h"
 
 namespace ohgpu {
 
@@ -49,10 +49,10 @@ __global__ __launch_bounds__(64) void dsd_file_plain_kernel(const Stream* __rest
 }
 
 __global__ __launch_bounds__(kDsdFileGroupPieces * 64) void dsd_file_convert_kernel(const Stream* __restrict__ streams, const Rec* __restrict__ recs,
-                                                                                   const DsdFileGroup* __restrict__ groups, const uint8_t* __restrict__ src,
+                                                                                   const PieceGroup* __restrict__ groups, const uint8_t* __restrict__ src,
                                                                                    uint8_t* __restrict__ dst)
 {
-    const DsdFileGroup g = groups[blockIdx.x];
+    const PieceGroup g = groups[blockIdx.x];
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
     const Rec c = recs[g.stream];
     const uint32_t piece = g.group * kDsdFileGroupPieces + wave;
@@ -65,55 +65,14 @@ __global__ __launch_bounds__(kDsdFileGroupPieces * 64) void dsd_file_convert_ker
 
 int dsd_file_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Stream* streams)
 {
-    DsdFileState& g = *b->dsdfile;
-    OHGPU_TRY(state_events(g, 3));
-    if (!g.n_streams) return OHGPU_OK;
-    std::vector<DsdFileGroup> groups;
-    for (size_t i = 0; i < g.n_streams; i++) {
-        // a run has no more than room_pieces pieces, whatever the walk finds
-        const uint64_t pieces = room_pieces(streams[i]), want = (pieces + kDsdFileGroupPieces - 1u) / kDsdFileGroupPieces;
-        g.writes = g.writes || pieces != 0u;
-        if (g.plain) continue;
-        if (groups.size() + want > 0x7fffffffull) return set_error(OHGPU_ERR_INVALID, "ohgpu_dsd_file_batch_create: the destination ranges are more than one batch takes");
-        for (uint64_t k = 0; k < want; k++) groups.push_back(DsdFileGroup{(uint32_t)i, (uint32_t)k});
-    }
-    g.n_groups = (uint32_t)groups.size();
-    OHGPU_TRY(dev_array(ctx, g, &g.d_streams, g.n_streams, streams));
-    OHGPU_TRY(dev_array<Result>(ctx, g, &g.d_results, g.n_streams));
-    OHGPU_TRY(dev_array<Rec>(ctx, g, &g.d_recs, g.n_streams));
-    OHGPU_TRY(dev_array(ctx, g, &g.d_groups, g.n_groups, groups.data()));
-    return OHGPU_OK;
+    // a run has no more than room_pieces pieces, whatever the walk finds
+    return file_plan(ctx, *b->file, "ohgpu_dsd_file_batch_create", streams, sizeof(Result), sizeof(Rec),
+                     [](const Stream& st) -> uint64_t { return (room_pieces(st) + kDsdFileGroupPieces - 1u) / kDsdFileGroupPieces; });
 }
 
-void dsd_file_free(ohgpu_ctx* ctx, ohgpu_batch* b)
+int dsd_file_run(ohgpu_ctx*, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s)
 {
-    if (!b->dsdfile) return;
-    state_release(ctx, *b->dsdfile);
-    delete b->dsdfile;
-    b->dsdfile = nullptr;
-}
-
-int dsd_file_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s)
-{
-    DsdFileState& g = *b->dsdfile;
-    OHGPU_TRY(run_begin(g, s));      // (the records serve one run at a time)
-    const uint32_t ns = (uint32_t)g.n_streams, lane_blocks = (ns + 63u) / 64u;
-    const Stream* const streams = (const Stream*)g.d_streams;
-    OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[0], s));
-    if (g.plain) {
-        hipLaunchKernelGGL(dsd_file_plain_kernel, dim3(lane_blocks), dim3(64), 0, s, streams, ns, src, dst, (Result*)g.d_results, (Rec*)g.d_recs);
-        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-        OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[1], s));
-        return run_end(g, s);
-    }
-    hipLaunchKernelGGL(dsd_file_walk_kernel, dim3(lane_blocks), dim3(64), 0, s, streams, ns, src, (Result*)g.d_results, (Rec*)g.d_recs);
-    OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-    OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[1], s));
-    if (g.n_groups) {
-        hipLaunchKernelGGL(dsd_file_convert_kernel, dim3(g.n_groups), dim3(kDsdFileGroupPieces * 64), 0, s, streams, (const Rec*)g.d_recs, (const DsdFileGroup*)g.d_groups, src, dst);
-        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-    }
-    return run_end(g, s);
+    return file_run(*b->file, src, dst, s, dsd_file_plain_kernel, dsd_file_walk_kernel, dsd_file_convert_kernel, kDsdFileGroupPieces * 64u);
 }
 
 }  // namespace ohgpu

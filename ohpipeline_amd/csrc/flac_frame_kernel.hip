@@ -154,14 +154,6 @@ int flac_plan(ohgpu_ctx* ctx, ohgpu_batch* b)
     return OHGPU_OK;
 }
 
-void flac_free(ohgpu_ctx* ctx, ohgpu_batch* b)
-{
-    if (!b->flac) return;
-    state_release(ctx, *b->flac);
-    delete b->flac;
-    b->flac = nullptr;
-}
-
 // p holds at least `bytes`: kept when it does, replaced (half as large again) when it does not
 static int flac_reserve(ohgpu_ctx* ctx, void** p, size_t* cap, size_t bytes)
 {

@@ -19,6 +19,8 @@
 
 #include <stdint.h>
 
+#include "field_bytes.h"
+
 #if defined(__HIPCC__)
 #define IFFC_HD __host__ __device__ __forceinline__
 #else
@@ -36,7 +38,7 @@ enum Kind : uint32_t { kNoKind = 0, kWav = 1, kAiff = 2, kAifc = 3 };
 enum : uint32_t { kLittle = 1, kBig = 2 };                            // OHGPU_ENDIAN_*
 enum : uint32_t { kFlagWav8Unsigned = 1 };
 constexpr uint32_t kMaxChunks = 4096, kMaxChannels = 10;
-constexpr uint32_t fourcc(char a, char b, char c, char d) { return ((uint32_t)(uint8_t)a << 24) | ((uint32_t)(uint8_t)b << 16) | ((uint32_t)(uint8_t)c << 8) | (uint8_t)d; }
+using fieldbytes::fourcc;
 
 struct Stream {               // 64 bytes = ohgpu_iff_stream_desc
     uint64_t src_offset;
@@ -60,33 +62,11 @@ struct Rec {                  // 40 bytes: the walk's record for the conversion
 };
 static_assert(sizeof(Stream) == 64 && sizeof(Result) == 80 && sizeof(Rec) == 40, "IFF layouts");
 
-// ---- bytes.  The caller has made sure that [pos, pos + width) lies inside the stream.  On the device a field is read as the aligned
-// dword(s) that hold it, joined by shifts (csrc/mp4_box_core.h has the reasons); the CPU driver builds both readers.
-#if defined(__HIP_DEVICE_COMPILE__) || defined(IFFC_ALIGNED_READS)
-IFFC_HD uint32_t le32(const uint8_t* p, uint64_t pos)
-{
-    const uintptr_t a = (uintptr_t)(p + pos);
-    const uint32_t* w = (const uint32_t*)(a & ~(uintptr_t)3);
-    const uint32_t shift = (uint32_t)(a & 3u) * 8u;
-    uint32_t v = w[0];
-    if (shift) v = (v >> shift) | (w[1] << (32u - shift));
-    return v;
-}
-IFFC_HD uint32_t le16(const uint8_t* p, uint64_t pos)
-{
-    const uintptr_t a = (uintptr_t)(p + pos);
-    const uint32_t* w = (const uint32_t*)(a & ~(uintptr_t)3);
-    const uint32_t shift = (uint32_t)(a & 3u) * 8u;
-    uint32_t v = w[0] >> shift;
-    if (shift == 24u) v |= w[1] << 8;
-    return v & 0xffffu;
-}
-#else
-IFFC_HD uint32_t le16(const uint8_t* p, uint64_t pos) { return (uint32_t)p[pos] | ((uint32_t)p[pos + 1] << 8); }
-IFFC_HD uint32_t le32(const uint8_t* p, uint64_t pos) { return (uint32_t)p[pos] | ((uint32_t)p[pos + 1] << 8) | ((uint32_t)p[pos + 2] << 16) | ((uint32_t)p[pos + 3] << 24); }
-#endif
-IFFC_HD uint32_t be32(const uint8_t* p, uint64_t pos) { return __builtin_bswap32(le32(p, pos)); }
-IFFC_HD uint32_t be16(const uint8_t* p, uint64_t pos) { const uint32_t v = le16(p, pos); return ((v & 0xffu) << 8) | (v >> 8); }
+// ---- bytes: csrc/field_bytes.h's reader, aligned dwords on the device
+using fieldbytes::le16;
+using fieldbytes::le32;
+using fieldbytes::be16;
+using fieldbytes::be32;
 
 struct Format { uint32_t channels, rate, depth, sample_bytes, little, bit_rate; };
 

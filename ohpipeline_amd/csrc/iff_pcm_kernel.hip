@@ -13,7 +13,7 @@
 // [dst_offset, + dst_bytes_capacity), which the same check placed inside the destination arena and apart from every other stream's.
 #include <hip/hip_runtime.h>
 
-#include "api_common.h"
+#include "api_file.h"
 
 namespace ohgpu {
 
@@ -44,10 +44,10 @@ __global__ __launch_bounds__(64) void iff_plain_kernel(const Stream* __restrict_
     recs[i] = c;
 }
 
-__global__ __launch_bounds__(kIffThreads) void iff_convert_kernel(const Stream* __restrict__ streams, const Rec* __restrict__ recs, const IffGroup* __restrict__ groups,
+__global__ __launch_bounds__(kIffThreads) void iff_convert_kernel(const Stream* __restrict__ streams, const Rec* __restrict__ recs, const PieceGroup* __restrict__ groups,
                                                                   const uint8_t* __restrict__ src, uint8_t* __restrict__ dst)
 {
-    const IffGroup g = groups[blockIdx.x];
+    const PieceGroup g = groups[blockIdx.x];
     const Rec c = recs[g.stream];
     if (c.out_bytes == 0u) return;
     const uint8_t* const run = src + streams[g.stream].src_offset + c.src_pos;
@@ -65,56 +65,16 @@ __global__ __launch_bounds__(kIffThreads) void iff_convert_kernel(const Stream* 
 
 int iff_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Stream* streams)
 {
-    IffState& g = *b->iff;
-    OHGPU_TRY(state_events(g, 3));
-    if (!g.n_streams) return OHGPU_OK;
-    std::vector<IffGroup> groups;
-    for (size_t i = 0; i < g.n_streams; i++) g.writes = g.writes || streams[i].dst_bytes_capacity != 0u;
-    if (!g.plain)
-        for (size_t i = 0; i < g.n_streams; i++) {
-            // a run has no more than dst_bytes_capacity / 16 pieces; its first workgroup is there for the edges of a run without pieces
-            const uint64_t pieces = streams[i].dst_bytes_capacity / 16u, whole = (pieces + kIffGroupPieces - 1u) / kIffGroupPieces;
-            const uint64_t want = streams[i].dst_bytes_capacity == 0u ? 0u : whole ? whole : 1u;
-            for (uint64_t k = 0; k < want; k++) groups.push_back(IffGroup{(uint32_t)i, (uint32_t)k});
-            if (groups.size() > 0x7fffffffull) return set_error(OHGPU_ERR_INVALID, "ohgpu_iff_batch_create: the destination ranges are more than one batch takes");
-        }
-    g.n_groups = (uint32_t)groups.size();
-    OHGPU_TRY(dev_array(ctx, g, &g.d_streams, g.n_streams, streams));
-    OHGPU_TRY(dev_array<Result>(ctx, g, &g.d_results, g.n_streams));
-    OHGPU_TRY(dev_array<Rec>(ctx, g, &g.d_recs, g.n_streams));
-    OHGPU_TRY(dev_array(ctx, g, &g.d_groups, g.n_groups, groups.data()));
-    return OHGPU_OK;
+    return file_plan(ctx, *b->file, "ohgpu_iff_batch_create", streams, sizeof(Result), sizeof(Rec), [](const Stream& st) -> uint64_t {
+        // a run has no more than dst_bytes_capacity / 16 pieces; its first workgroup is there for the edges of a run without pieces
+        const uint64_t pieces = st.dst_bytes_capacity / 16u, whole = (pieces + kIffGroupPieces - 1u) / kIffGroupPieces;
+        return st.dst_bytes_capacity == 0u ? 0u : whole ? whole : 1u;
+    });
 }
 
-void iff_free(ohgpu_ctx* ctx, ohgpu_batch* b)
+int iff_run(ohgpu_ctx*, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s)
 {
-    if (!b->iff) return;
-    state_release(ctx, *b->iff);
-    delete b->iff;
-    b->iff = nullptr;
-}
-
-int iff_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s)
-{
-    IffState& g = *b->iff;
-    OHGPU_TRY(run_begin(g, s));      // (the records serve one run at a time)
-    const uint32_t ns = (uint32_t)g.n_streams, lane_blocks = (ns + 63u) / 64u;
-    const Stream* const streams = (const Stream*)g.d_streams;
-    OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[0], s));
-    if (g.plain) {
-        hipLaunchKernelGGL(iff_plain_kernel, dim3(lane_blocks), dim3(64), 0, s, streams, ns, src, dst, (Result*)g.d_results, (Rec*)g.d_recs);
-        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-        OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[1], s));
-        return run_end(g, s);
-    }
-    hipLaunchKernelGGL(iff_walk_kernel, dim3(lane_blocks), dim3(64), 0, s, streams, ns, src, (Result*)g.d_results, (Rec*)g.d_recs);
-    OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-    OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[1], s));
-    if (g.n_groups) {
-        hipLaunchKernelGGL(iff_convert_kernel, dim3(g.n_groups), dim3(kIffThreads), 0, s, streams, (const Rec*)g.d_recs, (const IffGroup*)g.d_groups, src, dst);
-        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-    }
-    return run_end(g, s);
+    return file_run(*b->file, src, dst, s, iff_plain_kernel, iff_walk_kernel, iff_convert_kernel, kIffThreads);
 }
 
 }  // namespace ohgpu

@@ -2,7 +2,7 @@
 // what stands between the bytes of an .m4a file and the packet table ohgpu_alac_* takes.  Every function is __host__ __device__:
 // csrc/mp4_table_kernel.hip runs this text on the device, tests/cpp/mp4_core_driver.cpp runs the same text on the CPU under the
 // sanitizers, csrc/api_mp4.hip runs it for ohgpu_mp4_seek.  Everything in the file is big-endian and lies at any address: the host reads
-// it byte by byte, the device as aligned dwords (be32 below).
+// it byte by byte, the device as aligned dwords (csrc/field_bytes.h).
 //
 //   a box      u32 size | fourcc | (size == 1: u64 size) | payload.  Size 0: to the end of the stream, at top level only.  A size below
 //              its own header (8 or 16) is INVALID; so is a child that ends behind its parent.  Fewer than 8 bytes left in a parent are
@@ -23,6 +23,8 @@
 
 #include <stdint.h>
 
+#include "field_bytes.h"
+
 #if defined(__HIPCC__)
 #define MP4B_HD __host__ __device__ __forceinline__
 #else
@@ -38,7 +40,7 @@ namespace mp4box {
 enum Status : uint32_t { kOk = 0, kNotMp4 = 1, kTruncated = 2, kInvalid = 3, kNotAlac = 4, kUnsupported = 5 };
 constexpr uint32_t kMaxSamples = 1u << 24, kMaxBoxes = 4096, kNone = 0xffffffffu;
 constexpr uint32_t kTile = 1024;                      // samples a tile: one workgroup's share of the sums and of the expansion
-constexpr uint32_t fourcc(char a, char b, char c, char d) { return ((uint32_t)(uint8_t)a << 24) | ((uint32_t)(uint8_t)b << 16) | ((uint32_t)(uint8_t)c << 8) | (uint8_t)d; }
+using fieldbytes::fourcc;
 
 struct Stream {               // 32 bytes = ohgpu_mp4_stream_desc
     uint64_t src_offset;
@@ -73,34 +75,10 @@ struct Tables {
 };
 static_assert(sizeof(Stream) == 32 && sizeof(Config) == 24 && sizeof(Result) == 112 && sizeof(Sample) == 16 && sizeof(Row) == 16 && sizeof(Tables) == 64, "MPEG-4 layouts");
 
-// ---- bytes.  The caller has made sure that [pos, pos + width) lies inside the stream.  On the device a field is read as the aligned
-// dword(s) that hold it, joined by shifts, so that every dword load is aligned whatever the field's address (four byte loads in a row
-// are merged by the compiler into one dword load at the field's own address).  The dwords that hold a stream's first and last bytes
-// reach up to three bytes beyond it: include/ohgpu.h states that as the source arena's requirement.
-#if defined(__HIP_DEVICE_COMPILE__) || defined(MP4B_ALIGNED_READS)      // (the CPU driver builds this reader too: tests/test_mp4_core_cpu.py)
-MP4B_HD uint32_t be32(const uint8_t* p, uint64_t pos)
-{
-    const uintptr_t a = (uintptr_t)(p + pos);
-    const uint32_t* w = (const uint32_t*)(a & ~(uintptr_t)3);
-    const uint32_t shift = (uint32_t)(a & 3u) * 8u;
-    uint32_t v = w[0];
-    if (shift) v = (v >> shift) | (w[1] << (32u - shift));
-    return __builtin_bswap32(v);
-}
-MP4B_HD uint32_t be16(const uint8_t* p, uint64_t pos)
-{
-    const uintptr_t a = (uintptr_t)(p + pos);
-    const uint32_t* w = (const uint32_t*)(a & ~(uintptr_t)3);
-    const uint32_t shift = (uint32_t)(a & 3u) * 8u;
-    uint32_t v = w[0] >> shift;
-    if (shift == 24u) v |= w[1] << 8;
-    return ((v & 0xffu) << 8) | ((v >> 8) & 0xffu);
-}
-#else
-MP4B_HD uint32_t be16(const uint8_t* p, uint64_t pos) { return ((uint32_t)p[pos] << 8) | p[pos + 1]; }
-MP4B_HD uint32_t be32(const uint8_t* p, uint64_t pos) { return ((uint32_t)p[pos] << 24) | ((uint32_t)p[pos + 1] << 16) | ((uint32_t)p[pos + 2] << 8) | p[pos + 3]; }
-#endif
-MP4B_HD uint64_t be64(const uint8_t* p, uint64_t pos) { return ((uint64_t)be32(p, pos) << 32) | be32(p, pos + 4); }
+// ---- bytes: csrc/field_bytes.h's reader, aligned dwords on the device
+using fieldbytes::be16;
+using fieldbytes::be32;
+using fieldbytes::be64;
 
 struct Box { uint64_t size; uint32_t type, header; };
 // The header at pos of [pos, limit).  1: read; 0: fewer than 8 bytes are left; 2: a 64-bit size is announced and fewer than 16 are;

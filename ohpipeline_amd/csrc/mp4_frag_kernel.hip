@@ -273,14 +273,6 @@ int mp4f_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Stream* streams)
     return OHGPU_OK;
 }
 
-void mp4f_free(ohgpu_ctx* ctx, ohgpu_batch* b)
-{
-    if (!b->mp4f) return;
-    state_release(ctx, *b->mp4f);
-    delete b->mp4f;
-    b->mp4f = nullptr;
-}
-
 int mp4f_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s)
 {
     Mp4fState& g = *b->mp4f;

@@ -242,14 +242,6 @@ int mp4_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Stream* streams)
     return OHGPU_OK;
 }
 
-void mp4_free(ohgpu_ctx* ctx, ohgpu_batch* b)
-{
-    if (!b->mp4) return;
-    state_release(ctx, *b->mp4);
-    delete b->mp4;
-    b->mp4 = nullptr;
-}
-
 int mp4_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, hipStream_t s)
 {
     Mp4State& g = *b->mp4;

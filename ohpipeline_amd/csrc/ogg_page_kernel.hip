@@ -144,14 +144,6 @@ int ogg_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Stream* streams)
     return OHGPU_OK;
 }
 
-void ogg_free(ohgpu_ctx* ctx, ohgpu_batch* b)
-{
-    if (!b->ogg) return;
-    state_release(ctx, *b->ogg);
-    delete b->ogg;
-    b->ogg = nullptr;
-}
-
 int ogg_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s)
 {
     OggState& g = *b->ogg;

@@ -291,7 +291,8 @@ int batch_begin(ohgpu_ctx* ctx, const char* who, BatchKind kind, bool args_ok, s
 // holds (it takes a partly built batch: a failed create comes through here too); whether the device is drained first even without
 // d_descs.  A new
 // family is one row here, one api_*.hip, and a state that derives from RunState: its plan names each device block once (dev_array),
-// its release function is state_release and a delete.
+// its release is free_state of the batch's pointer to it (state_free, api_common.h: state_release and a delete).
+template <auto State> static void free_state(ohgpu_ctx* ctx, ohgpu_batch* b) { state_free(ctx, b->*State); }
 static void free_fmt(ohgpu_ctx* ctx, ohgpu_batch* b) { free_fmt_line(ctx, b); free_pcm_line(ctx, b); }
 static void free_pull(ohgpu_ctx* ctx, ohgpu_batch* b) { if (b->d_pull_tiles) ctx_dev_free(ctx, b->d_pull_tiles); }
 static const struct { const char* noun; void (*release)(ohgpu_ctx*, ohgpu_batch*); bool drain; } kKinds[] = {
@@ -303,16 +304,16 @@ static const struct { const char* noun; void (*release)(ohgpu_ctx*, ohgpu_batch*
     {"a Songcast frame", free_ohm, false},          // kBatchOhm
     {"a pulled", free_pull, false},                 // kBatchSrcPull
     {"a DSD", free_dsd_line, true},                 // kBatchDsd
-    {"a FLAC", flac_free, false},                   // kBatchFlac
+    {"a FLAC", free_state<&ohgpu_batch::flac>, false},   // kBatchFlac
     {"a DSD to PCM", free_dsd_pcm, true},           // kBatchDsdPcm
-    {"a lossless-packet (ALAC)", alac_free, false}, // kBatchAlac
+    {"a lossless-packet (ALAC)", free_state<&ohgpu_batch::alac>, false},   // kBatchAlac
     {"a RAOP", raop_free, false},                   // kBatchRaop
-    {"a Songcast receiver", ohm_rx_free, false},    // kBatchOhmRx
-    {"a Ogg", ogg_free, false},                     // kBatchOgg
-    {"an MPEG-4", mp4_free, false},                 // kBatchMp4
-    {"a PCM file", iff_free, false},                // kBatchIff
-    {"a DSD file", dsd_file_free, false},           // kBatchDsdFile
-    {"a fragmented MPEG-4", mp4f_free, false},      // kBatchMp4f
+    {"a Songcast receiver", free_state<&ohgpu_batch::ohmrx>, false},   // kBatchOhmRx
+    {"a Ogg", free_state<&ohgpu_batch::ogg>, false},   // kBatchOgg
+    {"an MPEG-4", free_state<&ohgpu_batch::mp4>, false},   // kBatchMp4
+    {"a PCM file", free_state<&ohgpu_batch::file>, false},   // kBatchIff
+    {"a DSD file", free_state<&ohgpu_batch::file>, false},   // kBatchDsdFile
+    {"a fragmented MPEG-4", free_state<&ohgpu_batch::mp4f>, false},   // kBatchMp4f
 };
 static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchMp4f + 1, "a row per BatchKind");
 
@@ -626,11 +627,11 @@ int ohgpu_batch_paths_info(const ohgpu_batch* b, ohgpu_batch_paths* out)
         return OHGPU_OK;
     }
     if (b->kind == kBatchIff) {
-        out->iff_route = b->iff && b->iff->plain ? 2u : 1u;
+        out->iff_route = b->file && b->file->plain ? 2u : 1u;
         return OHGPU_OK;
     }
     if (b->kind == kBatchDsdFile) {
-        out->dsd_file_route = b->dsdfile && b->dsdfile->plain ? 2u : 1u;
+        out->dsd_file_route = b->file && b->file->plain ? 2u : 1u;
         return OHGPU_OK;
     }
     if (b->kind != kBatchOhm) return set_error(OHGPU_ERR_INVALID, "ohgpu_batch_paths_info: not a pcm, Songcast frame, fmt, Apple Lossless, MPEG-4, PCM file or DSD file batch");

@@ -343,7 +343,7 @@ struct OhmPlan {
     uint32_t n_unfolded = 0, n_unfolded_generic = 0;
 };
 
-// ---- what the batch states below share (FlacState, AlacState, OhmRxState, OggState, Mp4State, Mp4fState, IffState, DsdFileState; RaopState for its blocks and
+// ---- what the batch states below share (FlacState, AlacState, OhmRxState, OggState, Mp4State, Mp4fState, FileState; RaopState for its blocks and
 // its one event).  The events of a run's phases: n_events are in use, the last of them is recorded at the run's end.  The tracking of
 // run_begin / run_end (api_common.h).  The registry of the device blocks that die with the batch: WHERE each pointer member lives (a
 // state is heap-allocated and never moves), not what it holds, so a block that a run frees and replaces (FLAC's lists and rows) needs
@@ -515,39 +515,27 @@ static_assert(sizeof(ohgpu_mp4f_stream_desc) == sizeof(mp4frag::Stream) && sizeo
               offsetof(ohgpu_flac_streaminfo_t, md5) == offsetof(mp4frag::FlacInfo, md5) && mp4frag::kMaxBoxes == OHGPU_MP4F_MAX_BOXES && mp4frag::kMaxSamples == OHGPU_MP4F_MAX_SAMPLES && mp4frag::kMaxRunSamples == OHGPU_MP4F_MAX_RUN_SAMPLES &&
               mp4frag::kNotFragmented == OHGPU_MP4F_NOT_FRAGMENTED && mp4frag::kGather == OHGPU_MP4F_GATHER, "fragmented MPEG-4 layouts");
 
-// ---- PCM files (csrc/iff_pcm_kernel.hip): the descriptors, the list of the conversion's workgroups, the walk's record
-// of each stream's run and the results of the last run.  The batch's d_descs holds nothing.
-constexpr uint32_t kIffGroupPieces = 1024;            // the pieces one workgroup of the conversion takes: tests/test_gpu_iff_textbook.py restates it
-struct IffGroup { uint32_t stream, group; };          // one workgroup's share: pieces [group x kIffGroupPieces, + kIffGroupPieces) of a stream's run
-struct IffState : RunState {
+// ---- the two file layers: PCM files (csrc/iff_pcm_kernel.hip) and DSD files (csrc/dsd_file_kernel.hip, DESIGN.md
+// 5.18).  One state for both (api_file.h has the plan, the run and the C ABI's bodies over it): the descriptors, the list of the
+// conversion's workgroups, the walk's record of each stream's run and the results of the last run, each in the family's own layout
+// (iffchunk:: or dsdfile:: Stream / Result / Rec).  The batch's d_descs holds nothing.
+constexpr uint32_t kIffGroupPieces = 1024;            // the pieces one workgroup of the PCM conversion takes: tests/test_gpu_iff_textbook.py restates it
+constexpr uint32_t kDsdFileGroupPieces = 2;           // the pieces (of dsdfile::kPieceChunks chunks, a wave each) one workgroup of the DSD conversion takes: tests/test_gpu_dsd_file_textbook.py restates both
+struct PieceGroup { uint32_t stream, group; };        // one workgroup's share: pieces [group x k*GroupPieces, + k*GroupPieces) of a stream's run
+struct FileState : RunState {
     size_t n_streams = 0;
     uint32_t n_groups = 0;
     bool plain = false;                               // created under kernel variant 1: one launch, a lane per stream
-    bool writes = false;                              // some stream has room in the destination arena: either route needs the arena
-    void* d_streams = nullptr;                        // iffchunk::Stream[n_streams]
-    void* d_results = nullptr;                        // iffchunk::Result[n_streams]
-    void* d_recs = nullptr;                           // iffchunk::Rec[n_streams]
-    void* d_groups = nullptr;                         // IffGroup[n_groups]
+    bool writes = false;                              // some stream has room in the destination arena (PCM: a byte; DSD: a sample block): either route needs the arena
+    void* d_streams = nullptr;                        // Stream[n_streams]
+    void* d_results = nullptr;                        // Result[n_streams]
+    void* d_recs = nullptr;                           // Rec[n_streams]
+    void* d_groups = nullptr;                         // PieceGroup[n_groups]
 };
 static_assert(sizeof(ohgpu_iff_stream_desc) == sizeof(iffchunk::Stream) && sizeof(ohgpu_iff_stream_result) == sizeof(iffchunk::Result) &&
               offsetof(ohgpu_iff_stream_desc, max_bit_depth) == offsetof(iffchunk::Stream, max_bit_depth) &&
               offsetof(ohgpu_iff_stream_result, error_offset) == offsetof(iffchunk::Result, error_offset) &&
               offsetof(ohgpu_iff_stream_result, frames_written) == offsetof(iffchunk::Result, frames_written), "IFF layouts");
-
-// ---- DSD files (csrc/dsd_file_kernel.hip): the descriptors, the list of the conversion's workgroups, the walk's record
-// of each stream's run and the results of the last run.  The batch's d_descs holds nothing.
-constexpr uint32_t kDsdFileGroupPieces = 2;           // the pieces (of dsdfile::kPieceChunks chunks, a wave each) one workgroup takes: tests/test_gpu_dsd_file_textbook.py restates both
-struct DsdFileGroup { uint32_t stream, group; };      // one workgroup's share: pieces [group x kDsdFileGroupPieces, + kDsdFileGroupPieces) of a stream's run
-struct DsdFileState : RunState {
-    size_t n_streams = 0;
-    uint32_t n_groups = 0;
-    bool plain = false;                               // created under kernel variant 1: one launch, a lane per stream
-    bool writes = false;                              // some stream has room for a sample block: either route needs the destination arena
-    void* d_streams = nullptr;                        // dsdfile::Stream[n_streams]
-    void* d_results = nullptr;                        // dsdfile::Result[n_streams]
-    void* d_recs = nullptr;                           // dsdfile::Rec[n_streams]
-    void* d_groups = nullptr;                         // DsdFileGroup[n_groups]
-};
 static_assert(sizeof(ohgpu_dsd_file_stream_desc) == sizeof(dsdfile::Stream) && sizeof(ohgpu_dsd_file_stream_result) == sizeof(dsdfile::Result) &&
               offsetof(ohgpu_dsd_file_stream_desc, pad_bytes_per_chunk) == offsetof(dsdfile::Stream, pad_bytes_per_chunk) &&
               offsetof(ohgpu_dsd_file_stream_result, error_offset) == offsetof(dsdfile::Result, error_offset) &&
@@ -665,8 +653,7 @@ struct ohgpu_batch {
     ohgpu::OhmRxState* ohmrx = nullptr; // kBatchOhmRx only
     ohgpu::OggState* ogg = nullptr;     // kBatchOgg only
     ohgpu::Mp4State* mp4 = nullptr;     // kBatchMp4 only
-    ohgpu::IffState* iff = nullptr;     // kBatchIff only
-    ohgpu::DsdFileState* dsdfile = nullptr;   // kBatchDsdFile only
+    ohgpu::FileState* file = nullptr;   // kBatchIff and kBatchDsdFile
     ohgpu::Mp4fState* mp4f = nullptr;   // kBatchMp4f only
     void*    d_pull_tiles = nullptr;   // kBatchSrcPull: PullTile[n_pull_tiles] on the device (d_descs holds the messages)
     uint32_t n_pull_tiles = 0;
@@ -709,12 +696,13 @@ inline int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? OHGPU_ERR_
         if (err_ != OHGPU_OK) return err_;       \
     } while (0)
 
-// The release functions (free_pcm_line, free_fmt_line, free_dsd_line, flac_free, alac_free, raop_free, free_flywheel, free_src_fast, free_ohm, ohm_rx_free, ogg_free, mp4_free, iff_free, dsd_file_free, mp4f_free): what
+// The release functions (free_pcm_line, free_fmt_line, free_dsd_line, free_dsd_pcm, raop_free, free_flywheel, free_src_fast, free_ohm): what
 // ohgpu_batch_destroy's table calls (csrc/ohgpu_api.hip).  Each takes a PARTLY BUILT batch -- null pointers, a plan that was never
 // made -- and leaves the plan reset: a create that fails at any point hands its batch to ohgpu_batch_destroy and returns.
-// The eight whose state is a RunState (flac_free ... dsd_file_free) are one shape -- if the pointer is set: state_release (api_common.h), which
-// frees whatever block the state's registry names and destroys whatever event exists, then delete, then null the pointer --, raop_free
-// with its key wipe in front.  Such a family names no block twice: dev_array in its plan is the one place.
+// The families whose state is a RunState (flac, alac, ohmrx, ogg, mp4, mp4f, file) have no function of their own: the table calls
+// state_free (api_common.h) on the batch's pointer -- if it is set: state_release, which frees whatever block the state's registry
+// names and destroys whatever event exists, then delete, then null the pointer --, and raop_free calls it twice with its key wipe in
+// front.  Such a family names no block twice: dev_array in its plan is the one place.
 // kernels
 hipError_t launch_fmt_v1(const ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
 hipError_t launch_pcm_v1(const ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
@@ -741,47 +729,39 @@ hipError_t launch_dsd_pcm_table(const ohgpu_ctx* ctx, const ohgpu_batch* b, cons
 hipError_t launch_dsd_pcm_v1(const ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
 // csrc/flac_frame_kernel.hip
 int  flac_plan(ohgpu_ctx* ctx, ohgpu_batch* b);                       // the device side of a validated batch (b->flac->streams is filled)
-void flac_free(ohgpu_ctx* ctx, ohgpu_batch* b);
 int  flac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s, bool plain);
 int  flac_results(ohgpu_ctx* ctx, const ohgpu_batch* b, ohgpu_flac_stream_result* out);
 int  flac_frames(ohgpu_ctx* ctx, const ohgpu_batch* b, ohgpu_flac_frame* out, size_t capacity, size_t* n_frames);
 // csrc/alac_packet_kernel.hip
 int  alac_plan(ohgpu_ctx* ctx, ohgpu_batch* b);                       // the device side of a validated batch (b->alac->streams / packets are filled)
-void alac_free(ohgpu_ctx* ctx, ohgpu_batch* b);
 int  alac_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
 int  alac_results(ohgpu_ctx* ctx, const ohgpu_batch* b, ohgpu_alac_packet_result* out);     // every packet's, in the table's order
 // csrc/raop_decrypt_kernel.hip
 const raopcore::Tables& raop_tables();                                // the host's copy of the computed tables (the key schedule is made on the host)
 int  raop_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const raopcore::Job* jobs, size_t n_jobs);   // pieces, keys and scratch onto the device (b->raop is filled)
-void raop_free(ohgpu_ctx* ctx, ohgpu_batch* b);                       // clears the keys, then alac_free
+void raop_free(ohgpu_ctx* ctx, ohgpu_batch* b);                       // clears the keys, then state_free of its own state and of the AlacState
 int  raop_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);   // the decrypt phase alone
 // csrc/ohm_rx_kernel.hip
 int  ohm_rx_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const ohmrx::Stream* streams, const ohmrx::Datagram* datagrams);   // tables and result arrays onto the device (b->ohmrx holds the counts)
-void ohm_rx_free(ohgpu_ctx* ctx, ohgpu_batch* b);
 int  ohm_rx_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
 uint32_t ohm_rx_gather_blocks(uint32_t n_datagrams, uint32_t cus);   // the gather launch's size: the rule tests/test_gpu_ohm_rx_many_trips.py restates
 // csrc/ogg_page_kernel.hip
 int  ogg_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const oggpage::Stream* streams);   // tiles, lists and result arrays onto the device (b->ogg holds the counts)
-void ogg_free(ohgpu_ctx* ctx, ohgpu_batch* b);
 int  ogg_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
 uint32_t ogg_wave_blocks(uint64_t items, uint32_t cus);   // the verify and gather launches' size: the rule tests/test_gpu_ogg_textbook.py restates
 // csrc/mp4_table_kernel.hip.  No launch is persistent: a workgroup a tile (sums, expand), a wave a stream (carries), a lane a stream (walk).
 int  mp4_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const mp4box::Stream* streams);   // tiles, carries and tables onto the device (b->mp4 holds the counts)
-void mp4_free(ohgpu_ctx* ctx, ohgpu_batch* b);
 int  mp4_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, hipStream_t s);
 // csrc/mp4_frag_kernel.hip.  The run sums and the gather are persistent (a wave a run slot, mp4f_wave_blocks workgroups); the rest is a
 // lane a stream (walk, carries, finish) or a workgroup a tile (expand).
 int  mp4f_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const mp4frag::Stream* streams);   // the slot map, the tiles and the tables onto the device (b->mp4f holds the counts)
-void mp4f_free(ohgpu_ctx* ctx, ohgpu_batch* b);
 int  mp4f_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
 uint32_t mp4f_wave_blocks(uint64_t slots, uint32_t cus);   // the persistent launches' size: the rule tests/test_gpu_mp4f_textbook.py restates
 // csrc/iff_pcm_kernel.hip.  No launch is persistent: a lane a stream (walk), a workgroup per kIffGroupPieces pieces of a run (convert).
 int  iff_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const iffchunk::Stream* streams);   // the descriptors and the workgroup list onto the device
-void iff_free(ohgpu_ctx* ctx, ohgpu_batch* b);
 int  iff_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
 // csrc/dsd_file_kernel.hip.  No launch is persistent: a lane a stream (walk), a wave per piece of dsdfile::kPieceChunks chunks (convert).
 int  dsd_file_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const dsdfile::Stream* streams);   // the descriptors and the workgroup list onto the device
-void dsd_file_free(ohgpu_ctx* ctx, ohgpu_batch* b);
 int  dsd_file_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
 // csrc/ohm_frame_kernel.hip: the two wire channels of streams wider than stereo (Sender::DoProcessFragment), one record per fragment
 OhmSelRec wide_record(uint64_t src_off, uint64_t dst_off, uint32_t n_frames, uint32_t channels, uint32_t sb, bool little, uint64_t src_arena_bytes);

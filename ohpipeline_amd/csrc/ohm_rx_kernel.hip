@@ -70,14 +70,6 @@ int ohm_rx_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Stream* streams, const Dat
     return OHGPU_OK;
 }
 
-void ohm_rx_free(ohgpu_ctx* ctx, ohgpu_batch* b)
-{
-    if (!b->ohmrx) return;
-    state_release(ctx, *b->ohmrx);
-    delete b->ohmrx;
-    b->ohmrx = nullptr;
-}
-
 int ohm_rx_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s)
 {
     OhmRxState& r = *b->ohmrx;

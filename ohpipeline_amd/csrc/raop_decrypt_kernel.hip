@@ -63,11 +63,9 @@ void raop_free(ohgpu_ctx* ctx, ohgpu_batch* b)
         // the expanded keys do not outlive the batch: the device array is cleared before its block goes back to the cache, the host copy too
         if (r.d_keys) (void)hipMemset(r.d_keys, 0, r.keys_bytes);
         for (uint32_t& w : r.keys) *(volatile uint32_t*)&w = 0;
-        state_release(ctx, r);
-        delete b->raop;
-        b->raop = nullptr;
     }
-    alac_free(ctx, b);
+    state_free(ctx, b->raop);
+    state_free(ctx, b->alac);
 }
 
 int raop_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s)

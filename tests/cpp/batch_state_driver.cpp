@@ -1,4 +1,4 @@
-// batch_state_driver.cpp -- the batch states' registry and release (csrc/api_common.h: state_events, dev_array, state_own, state_release
+// batch_state_driver.cpp -- the batch states' registry and release (csrc/api_common.h: state_events, dev_array, state_own, state_release, state_free
 // over csrc/ohgpu_internal.h's RunState) on the CPU, for tests/test_batch_state_cpu.py (built with -fsanitize=address,undefined
 // -fno-sanitize-recover=all).  The device is stubbed: ctx_dev_alloc / ctx_dev_free are malloc / free over a set of the live blocks, an
 // event is a heap byte, so a block or an event that nobody gives back is LeakSanitizer's to report and one given back twice is a
@@ -75,7 +75,7 @@ const char* hipGetErrorString(hipError_t) { return "stub"; }
 
 namespace {
 
-// A family's state and its release function, in the shape of flac_free ... iff_free
+// A family's state and the batch that holds it by a pointer, released through state_free as ohgpu_batch_destroy's table does
 struct DemoState : RunState {
     size_t n = 0;
     void* d_table = nullptr;
@@ -84,13 +84,7 @@ struct DemoState : RunState {
     void* d_list = nullptr; size_t list_cap = 0;      // a run's, grown on demand (FlacState::d_list)
 };
 struct Holder { DemoState* demo = nullptr; };
-void demo_free(ohgpu_ctx* ctx, Holder* b)
-{
-    if (!b->demo) return;
-    state_release(ctx, *b->demo);
-    delete b->demo;
-    b->demo = nullptr;
-}
+void demo_free(ohgpu_ctx* ctx, Holder* b) { state_free(ctx, b->demo); }
 int demo_plan(ohgpu_ctx* ctx, DemoState& d, size_t n, size_t n_tiles)
 {
     static const uint32_t table[8] = {1, 2, 3, 4, 5, 6, 7, 8};
@@ -161,7 +155,7 @@ int main()
     CHECK(g_frees - c0.frees == 6);
     nothing_left();
 
-    // 4. released twice through the family's release function: the second call finds the pointer null
+    // 4. released twice through state_free: the second call finds the pointer null
     c0 = counts();
     b.demo = new DemoState();
     CHECK(demo_plan(&ctx, *b.demo, 1, 1) == OHGPU_OK);
@@ -201,6 +195,13 @@ int main()
     c0 = counts();
     state_release(&ctx, d);
     CHECK(g_frees == c0.frees && g_destroyed == c0.destroyed && !d.d_table && !d.ev[0]);
+    nothing_left();
+
+    // 7. state_free on a pointer that was never set: nothing is touched, the device is not drained
+    c0 = counts();
+    DemoState* none = nullptr;
+    state_free(&ctx, none);
+    CHECK(!none && g_frees == c0.frees && g_destroyed == c0.destroyed && g_drains == c0.drains);
     nothing_left();
 
     printf("ok\n");

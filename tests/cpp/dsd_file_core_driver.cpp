@@ -6,7 +6,7 @@
 //       where nothing was written.
 // The fused route in the device's order: every stream walked; then per stream the workgroups the plan gives it (from
 // dst_bytes_capacity alone), each wave taking its piece lane by lane.  The plain route: the walk, the byte-wise conversion and the
-// fill.  Every stream's bytes are copied into a heap block of their own that ends where they end (built with -DDSDF_ALIGNED_READS the
+// fill.  Every stream's bytes are copied into a heap block of their own that ends where they end (built with -DOHGPU_ALIGNED_READS the
 // core reads as the device does, in aligned words, and the block is rounded up to a whole word) and begins src_offset mod 16 bytes in
 // front of them, so that the audio lies at the address mod 16 it has in the arena and a 16-byte line that does not lie whole inside
 // the stream is the sanitizer's to report; the destination arena is one heap block of exactly dst_bytes.  A step counter holds the
@@ -43,7 +43,7 @@ int main(int argc, char** argv)
     for (size_t i = 0; i < ns; i++) {
         const size_t lead = streams[i].src_offset % 16u;
         size_t size = lead + streams[i].src_bytes;
-#if defined(DSDF_ALIGNED_READS)
+#if defined(OHGPU_ALIGNED_READS)
         size = (size + 3u) & ~(size_t)3u;
 #endif
         if (posix_memalign((void**)&blocks[i], 16, size ? size : 1)) return 1;       // (16-aligned, and exactly `size` bytes to the sanitizer)

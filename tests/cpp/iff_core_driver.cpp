@@ -7,7 +7,7 @@
 // The fused route in the device's order: every stream walked; then per stream the workgroups the plan gives it (from
 // dst_bytes_capacity), each taking its pieces lane by lane and the first also the run's head and tail.  The plain route: the walk and
 // the byte-wise conversion.  Every stream's bytes are copied into a heap block of their own that ends where they end (built with
-// -DIFFC_ALIGNED_READS the core reads as the device does, in aligned words, and the block is rounded up to a whole word) and begins
+// -DOHGPU_ALIGNED_READS the core reads as the device does, in aligned words, and the block is rounded up to a whole word) and begins
 // src_offset mod 16 bytes in front of them, so that the source lies at the address mod 16 it has in the arena; the destination arena is
 // one heap block of exactly dst_bytes.  A stray index is the sanitizer's to report.  A step counter holds the walk to its bound.
 #include <cstdio>
@@ -42,7 +42,7 @@ int main(int argc, char** argv)
     for (size_t i = 0; i < ns; i++) {
         const size_t lead = streams[i].src_offset % 16u;
         size_t size = lead + streams[i].src_bytes;
-#if defined(IFFC_ALIGNED_READS)
+#if defined(OHGPU_ALIGNED_READS)
         size = (size + 3u) & ~(size_t)3u;
 #endif
         if (posix_memalign((void**)&blocks[i], 16, size ? size : 1)) return 1;       // (16-aligned, and exactly `size` bytes to the sanitizer)

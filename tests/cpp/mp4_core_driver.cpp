@@ -7,7 +7,7 @@
 // The fused route in the device's order: every stream walked; every tile's sum; per stream the four carries; every tile expanded --
 // its in-tile prefix, the head of the chunk its first sample lies in, a row a sample through the searches; the refusals counted.  The
 // plain route: the walk and expand_serial.  Every stream's bytes are copied into a heap block of exactly src_bytes, the carries and
-// the prefix are heap blocks exactly as large as the plan says (built with -DMP4B_ALIGNED_READS the core reads as the device does, in
+// the prefix are heap blocks exactly as large as the plan says (built with -DOHGPU_ALIGNED_READS the core reads as the device does, in
 // aligned words, and a stream's block is rounded up to a whole word), so that a stray index is the sanitizer's to report.  A step counter
 // holds every loop to the bound the format's text names: box headers by kMaxBoxes, entry loops by the entry counts, sample loops by N.
 #include <cstdio>
@@ -53,7 +53,7 @@ int main(int argc, char** argv)
     // (the rows' src_offset is absolute: the stream's own block stands for [src_offset, + src_bytes) of the arena)
     std::vector<uint8_t*> bytes(ns);
     for (size_t i = 0; i < ns; i++) {
-#if defined(MP4B_ALIGNED_READS)
+#if defined(OHGPU_ALIGNED_READS)
         bytes[i] = block<uint8_t>((streams[i].src_bytes + 3u) & ~(size_t)3u, 0);     // (the device's reader: whole aligned words, see mp4_box_core.h)
 #else
         bytes[i] = block<uint8_t>(streams[i].src_bytes, 0);

@@ -8,7 +8,7 @@
 // The phases' route in the device's order: every stream walked; every run's totals, 64 lanes striding its entries; per stream the
 // carries; every tile expanded -- the in-tile prefixes, the head run's entries in front of the tile, a row a sample through run_of(); per
 // stream finish(); every run's piece through ohmrx::gather_lane, a lane at a time.  The plain route: the serial text.  Every stream's
-// bytes are copied into a heap block of exactly src_bytes (built with -DMP4B_ALIGNED_READS the core reads as the device does, in aligned
+// bytes are copied into a heap block of exactly src_bytes (built with -DOHGPU_ALIGNED_READS the core reads as the device does, in aligned
 // words, and the block is rounded up to a whole word), its run records are a heap block of exactly run_capacity, the prefixes one of
 // exactly kTile + 1, so that a stray index is the sanitizer's to report.  A step counter holds every loop to its bound: box headers by
 // kMaxBoxes (and mp4box::kMaxBoxes inside a sample description), entry loops by the stream's bytes, sample loops by the rows, searches by
@@ -87,7 +87,7 @@ int main(int argc, char** argv)
     fclose(f);
     std::vector<uint8_t*> bytes(ns);
     for (size_t i = 0; i < ns; i++) {
-#if defined(MP4B_ALIGNED_READS)
+#if defined(OHGPU_ALIGNED_READS)
         bytes[i] = block<uint8_t>((streams[i].src_bytes + 3u) & ~(size_t)3u, 0);     // (the device's reader: whole aligned words, see mp4_box_core.h)
 #else
         bytes[i] = block<uint8_t>(streams[i].src_bytes, 0);

@@ -1,5 +1,6 @@
 """The batches of tests/test_gpu_stream_switch.py (on the device) and tests/test_stream_switch_cases.py (the tables and the models
-alone, on the CPU): for each of the seven families whose batch keeps per-run device records (flac, alac, raop, ohm_rx, ogg, mp4, iff)
+alone, on the CPU): for each of the eight families whose batch keeps per-run device records (flac, alac, raop, ohm_rx, ogg, mp4, iff,
+dsd_file)
 ONE set of tables and TWO source arenas of equal size, X and Y, with what the family's textbook model says a run over each must leave:
 the whole destination arena (pre-filled, with guards), the results, the packet or sample tables.  A run of the batch over X and a run
 over Y on another stream share the batch's records; every stream's output differs between X and Y, so that a mix-up of the two runs
@@ -15,7 +16,7 @@ import numpy as np
 
 from ohpipeline_amd import capi
 
-FAMILIES = ("flac", "alac", "raop", "ohm_rx", "ogg", "mp4", "iff")
+FAMILIES = ("flac", "alac", "raop", "ohm_rx", "ogg", "mp4", "iff", "dsd_file")
 
 
 class Pair:
@@ -330,7 +331,39 @@ def _iff():
                 run=lambda ctx, b, s, d, stream: ctx.iff_run(b, s, d, stream), verify=verify)
 
 
-_BUILDERS = {"flac": _flac, "alac": _alac, "raop": _raop, "ohm_rx": _ohm_rx, "ogg": _ogg, "mp4": _mp4, "iff": _iff}
+# ---------------------------------------------------------------- DSD files (dsd_file_cases)
+def _dsd_file():
+    """Four files, Y's with other audio: a DSF file of 100 chunks into (W, P) = (2, 0), a DFF file behind junk chunks into (6, 2) (Y:
+    another rate in the same four bytes), a DSF file of two plane pairs and 2100 chunks -- more than a piece of the conversion -- into
+    (8, 4) from chunk 3 on, and a DFF file into (1, 0) (Y: its compression type is DST -- unsupported, no audio)."""
+    import dsd_file_cases as DC
+    import dsd_file_textbook as FX
+    p = DC.planes
+    between = [DC.junk(b"DIIN", 11), DC.junk(b"COMT", 1)]
+    files = {"X": [FX.dsf(*p(100, 1)), FX.dff(*p(64, 2), between=between), FX.dsf(*p(2100, 3)), FX.dff(*p(33, 4))],
+             "Y": [FX.dsf(*p(100, 101)), FX.dff(*p(64, 102), between=between, rate=5644800), FX.dsf(*p(2100, 103)), FX.dff(*p(33, 104), cmpr=b"DST ")]}
+    formats = [dict(W=2, P=0), dict(W=6, P=2), dict(W=8, P=4, chunk_first=3), dict(W=1, P=0)]
+    streams = {w: [DC.stream(f, **kw) for f, kw in zip(files[w], formats)] for w in "XY"}
+    jobs = {w: DC.Job(streams[w]) for w in "XY"}
+    x, y = jobs["X"], jobs["Y"]
+    assert x.dst_bytes == y.dst_bytes
+    _same_tables((x.descs, y.descs))
+    assert [m["status"] for m in x.models] == [FX.OK] * 4 and [m["status"] for m in y.models] == [FX.OK] * 3 + [FX.UNSUPPORTED]
+    dst0 = np.full(x.dst_bytes, DC.FILL, dtype=np.uint8)
+    summary = {w: [{k: m[k] for k in FX.FIELDS} for m in jobs[w].models] for w in "XY"}
+
+    def verify(ctx, b, which):
+        job = jobs[which]
+        DC.assert_same(ctx.dsd_file_results(b, len(job.streams)), job.want_dst, job, what=which)   # (the arena is the caller's to compare)
+
+    return Pair("dsd_file", {w: jobs[w].src.copy() for w in "XY"}, dst0, {w: jobs[w].want_dst.copy() for w in "XY"},
+                [(int(d["dst_offset"]), int(d["dst_bytes_capacity"])) for d in x.descs], summary,
+                check=lambda: capi.dsd_file_batch_check(x.descs, x.src.size, dst0.size),
+                create=lambda ctx: ctx.dsd_file_batch(x.descs, x.src.size, dst0.size),
+                run=lambda ctx, b, s, d, stream: ctx.dsd_file_run(b, s, d, stream), verify=verify)
+
+
+_BUILDERS = {"flac": _flac, "alac": _alac, "raop": _raop, "ohm_rx": _ohm_rx, "ogg": _ogg, "mp4": _mp4, "iff": _iff, "dsd_file": _dsd_file}
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,5 +1,5 @@
 """The batch states' registry and release -- csrc/api_common.h's state_events, dev_array, state_own and state_release over RunState
-(csrc/ohgpu_internal.h), what FlacState ... IffState and RaopState share -- built for the CPU with AddressSanitizer and UBSan by
+(csrc/ohgpu_internal.h), what FlacState ... FileState and RaopState share -- built for the CPU with AddressSanitizer and UBSan by
 tests/cpp/batch_state_driver.cpp, a stand-alone program.  The two calls under them, ctx_dev_alloc and ctx_dev_free, are malloc and
 free over a set of the live blocks there, an event is a heap byte: a block or an event that is never given back is LeakSanitizer's
 to report, one given back twice fails a check of the driver's.  The cases: a state released fully built; with blocks that stayed

@@ -17,7 +17,7 @@ import dsd_file_textbook as FX
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture(scope="module", params=[[], ["-DDSDF_ALIGNED_READS"]], ids=["byte_reads", "the_devices_aligned_reads"])
+@pytest.fixture(scope="module", params=[[], ["-DOHGPU_ALIGNED_READS"]], ids=["byte_reads", "the_devices_aligned_reads"])
 def driver(tmp_path_factory, request):
     exe = tmp_path_factory.mktemp("dsd_file_core") / "dsd_file_core_driver"
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra", *request.param,

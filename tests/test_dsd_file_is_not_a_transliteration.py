@@ -17,7 +17,7 @@ THEIRS = ["OpenHome/Media/Codec/DsdDsf.cpp", "OpenHome/Media/Codec/DsdDff.cpp"]
 MINE = ["ohpipeline_amd/csrc/dsd_file_core.h", "ohpipeline_amd/csrc/dsd_perm.h", "ohpipeline_amd/csrc/dsd_file_kernel.hip", "ohpipeline_amd/csrc/api_dsd_file.hip",
         "ohpipeline_amd/host/DsdFileDecoder.h", "ohpipeline_amd/host/DsdFileDecoder.cpp", "tests/cpp/dsd_file_core_driver.cpp", "tests/cpp/test_dsd_file_decoder.cpp",
         "tests/dsd_file_textbook.py", "tests/dsd_file_cases.py", "tests/test_dsd_file_textbook.py", "tests/test_dsd_file_core_cpu.py", "tests/test_dsd_file_abi_host.py",
-        "tests/test_dsd_file_host_cpp.py", "tests/test_gpu_dsd_file_textbook.py", "tools/bench_dsd_file.py"]
+        "tests/test_dsd_file_host_cpp.py", "tests/test_gpu_dsd_file_textbook.py", "tools/bench_dsd_file.py", "ohpipeline_amd/csrc/field_bytes.h", "ohpipeline_amd/csrc/api_file.h"]
 
 
 @pytest.mark.parametrize("mine", MINE)

@@ -1,6 +1,6 @@
 """The shell every batch family of the C ABI shares (tests/test_gpu_batch_lifecycle.py), for the families whose signatures do not fit
 that file's Case: DSD -> PCM (a filter in front of the descriptors), RAOP and the Songcast receiver (two tables), Ogg and MPEG-4 (a
-packet table's size; MPEG-4 without a destination arena) and PCM files.  The same five things: what a failed create leaves behind,
+packet table's size; MPEG-4 without a destination arena), PCM files and DSD files.  The same five things: what a failed create leaves behind,
 what a run refuses (another family's batch, no batch, null arenas) and accepts (an empty batch), and that the host-buffer call equals
 create + run on device arenas, keeps its hands off every byte no output covers, and moves exactly what the MODEL says was delivered.
 
@@ -14,6 +14,8 @@ The batches are the smallest valid ones of each family, two outputs each:
     ogg        two streams of one page of one packet (10 and 11 bytes); the room is the stream's length, as the ABI asks
     mp4        two files of three and four packets; the "outputs" are their rows of the two tables, the hole is four rows
     iff        two 16-bit stereo WAV files of 4 and 5 frames
+    dsd_file   a DSF file of 8 chunks and a DFF file of 4, into (W, P) = (2, 0): 32 and 16 bytes, so that every dst_offset is the
+               multiple of 16 the family asks for
 
 Every table passes the library's own check before it reaches a launch; the refusals are refused before anything is queued."""
 import ctypes as C
@@ -23,6 +25,8 @@ import pytest
 
 import alac_cases as AC
 import alac_textbook as T
+import dsd_file_cases as FC
+import dsd_file_textbook as FX
 import dsd_pcm_cases as DC
 import iff_cases as IC
 import iff_textbook as IX
@@ -40,13 +44,13 @@ pytestmark = pytest.mark.gpu
 HOLE, HOLE_ROWS = 64, 4
 DEV_FILL, HOST_FILL = 0xA5, 0x5A
 ZERO_INFO = {"n_msgs": 0, "in_frames": 0, "out_frames": 0, "src_bytes_touched": 0, "dst_bytes_written": 0}
-FAMILIES = ("dsd_pcm", "raop", "ohm_rx", "ogg", "mp4", "iff")
+FAMILIES = ("dsd_pcm", "raop", "ohm_rx", "ogg", "mp4", "iff", "dsd_file")
 # the text of run_guard's "<who>: not a <noun> batch" (csrc/ohgpu_api.hip: kKinds' nouns); MPEG-4 and PCM files word their own
 NOT_MINE = {"dsd_pcm": "not a DSD to PCM batch", "raop": "not a RAOP batch", "ohm_rx": "not a Songcast receiver batch", "ogg": "not a Ogg batch",
-            "mp4": "not an MPEG-4 batch", "iff": "not a PCM file batch"}
+            "mp4": "not an MPEG-4 batch", "iff": "not a PCM file batch", "dsd_file": "not a DSD file batch"}
 # what last_error says of the last descriptor when its output lies past its arena (MPEG-4: its rows past the tables, its file past the arena)
 BOUNDS_TEXT = {"dsd_pcm": "dsd pcm desc 1: writes [", "raop": "alac desc 1: writes [", "ohm_rx": "ohm rx stream 1: writes [", "ogg": "ogg desc 1: writes [",
-               "iff": "iff desc 1: writes ["}
+               "iff": "iff desc 1: writes [", "dsd_file": "dsd file desc 1: writes ["}
 
 
 def _ptr(a):
@@ -211,6 +215,21 @@ class Fixtures:
         if bad:
             descs["dst_offset"][-1] = dst_bytes
         return Case("iff", (_ptr(descs), n), [descs], _u8(src), dst_bytes, pieces, sum(len(r) for _, r in pieces), (None,))
+
+    def _dsd_file(self, n, hole, bad):
+        files = [FC.make(kind, chunks, 50 + i) for i, (kind, chunks) in enumerate(((FX.DSF, 8), (FX.DFF, 4))[:n])]
+        offs, dst_bytes = _offsets([w.chunks_total // 2 * 8 for w in files], hole)         # (W, P) = (2, 0): two chunks to a block of 8 bytes
+        descs, src, pieces = np.zeros(n, dtype=capi.DSD_FILE_STREAM_DESC), bytearray(), []
+        for i, w in enumerate(files):
+            d, room = descs[i], w.chunks_total // 2 * 8
+            d["src_offset"], d["src_bytes"], d["dst_offset"], d["dst_bytes_capacity"], d["sample_block_words"], d["pad_bytes_per_chunk"] = len(src), len(w.data), offs[i], room, 2, 0
+            src += w.data
+            m = FX.read(w.data, 2, 0, dst_bytes_capacity=room)
+            assert m["status"] == FX.OK and m["chunks_written"] == w.chunks_total and m["bytes_written"] == len(m["blocks"]) == room
+            pieces.append((offs[i], bytes(m["blocks"])))
+        if bad:
+            descs["dst_offset"][-1] = dst_bytes
+        return Case("dsd_file", (_ptr(descs), n), [descs], _u8(src), dst_bytes, pieces, sum(len(r) for _, r in pieces), (None,))
 
     # ---- the calls, by family, returning the library's code
     def check(self, case):

@@ -16,7 +16,7 @@ import iff_textbook as IX
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture(scope="module", params=[[], ["-DIFFC_ALIGNED_READS"]], ids=["byte_reads", "the_devices_aligned_reads"])
+@pytest.fixture(scope="module", params=[[], ["-DOHGPU_ALIGNED_READS"]], ids=["byte_reads", "the_devices_aligned_reads"])
 def driver(tmp_path_factory, request):
     exe = tmp_path_factory.mktemp("iff_core") / "iff_core_driver"
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra", *request.param,

@@ -18,7 +18,7 @@ THEIRS = ["OpenHome/Media/Codec/Wav.cpp", "OpenHome/Media/Codec/AiffBase.h", "Op
 MINE = ["ohpipeline_amd/csrc/iff_chunk_core.h", "ohpipeline_amd/csrc/iff_pcm_kernel.hip", "ohpipeline_amd/csrc/api_iff.hip", "tests/cpp/iff_core_driver.cpp",
         "tests/iff_textbook.py", "tests/iff_cases.py", "tests/test_iff_textbook.py", "tests/test_iff_core_cpu.py", "tests/test_iff_abi_host.py",
         "tests/test_gpu_iff_textbook.py", "tests/test_gpu_iff_to_pcm.py", "tools/bench_iff.py", "ohpipeline_amd/host/PcmFileDecoder.h", "ohpipeline_amd/host/PcmFileDecoder.cpp",
-        "tests/cpp/test_pcm_file_decoder.cpp", "tests/test_iff_host_cpp.py"]
+        "tests/cpp/test_pcm_file_decoder.cpp", "tests/test_iff_host_cpp.py", "ohpipeline_amd/csrc/field_bytes.h", "ohpipeline_amd/csrc/api_file.h"]
 
 
 @pytest.mark.parametrize("mine", MINE)

@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TILE = 1024                          # kMp4Tile (csrc/ohgpu_internal.h)
 
 
-@pytest.fixture(scope="module", params=[[], ["-DMP4B_ALIGNED_READS"]], ids=["byte_reads", "the_devices_aligned_reads"])
+@pytest.fixture(scope="module", params=[[], ["-DOHGPU_ALIGNED_READS"]], ids=["byte_reads", "the_devices_aligned_reads"])
 def driver(tmp_path_factory, request):
     exe = tmp_path_factory.mktemp("mp4_core") / "mp4_core_driver"
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra", *request.param,

@@ -17,7 +17,7 @@ THEIRS = ["OpenHome/Media/Codec/Mpeg4.cpp", "OpenHome/Media/Codec/Mpeg4.h", "Ope
 MINE = ["ohpipeline_amd/csrc/mp4_box_core.h", "ohpipeline_amd/csrc/mp4_table_kernel.hip", "ohpipeline_amd/csrc/api_mp4.hip", "tests/cpp/mp4_core_driver.cpp",
         "tests/mp4_textbook.py", "tests/mp4_cases.py", "tests/test_mp4_textbook.py", "tests/test_mp4_core_cpu.py", "tests/test_mp4_abi_host.py",
         "tests/test_gpu_mp4_textbook.py", "tests/test_gpu_mp4_alac_to_pcm.py", "tools/bench_mp4_alac.py", "ohpipeline_amd/host/Mpeg4AlacDecoder.h", "ohpipeline_amd/host/Mpeg4AlacDecoder.cpp",
-        "tests/cpp/test_mpeg4_alac_decoder.cpp", "tests/test_mp4_host_cpp.py"]
+        "tests/cpp/test_mpeg4_alac_decoder.cpp", "tests/test_mp4_host_cpp.py", "ohpipeline_amd/csrc/field_bytes.h"]
 
 
 @pytest.mark.parametrize("mine", MINE)

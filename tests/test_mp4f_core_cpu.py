@@ -16,7 +16,7 @@ import mp4f_textbook as FX
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture(scope="module", params=[[], ["-DMP4B_ALIGNED_READS"]], ids=["byte_reads", "the_devices_aligned_reads"])
+@pytest.fixture(scope="module", params=[[], ["-DOHGPU_ALIGNED_READS"]], ids=["byte_reads", "the_devices_aligned_reads"])
 def driver(tmp_path_factory, request):
     exe = tmp_path_factory.mktemp("mp4f_core") / "mp4f_core_driver"
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra", *request.param,

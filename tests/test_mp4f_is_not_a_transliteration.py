@@ -17,7 +17,7 @@ THEIRS = ["OpenHome/Media/Codec/Mpeg4.cpp", "OpenHome/Media/Codec/Mpeg4.h", "Ope
 MINE = ["ohpipeline_amd/csrc/mp4_frag_core.h", "ohpipeline_amd/csrc/mp4_frag_kernel.hip", "ohpipeline_amd/csrc/api_mp4f.hip", "tests/cpp/mp4f_core_driver.cpp",
         "tests/mp4f_textbook.py", "tests/mp4f_cases.py", "tests/test_mp4f_textbook.py", "tests/test_mp4f_core_cpu.py", "tests/test_mp4f_abi_host.py",
         "tests/test_gpu_mp4f_textbook.py", "tests/test_gpu_mp4f_to_pcm.py", "tools/bench_mp4f.py", "tools/mp4f_serial.cpp", "ohpipeline_amd/host/Mpeg4FragmentDecoder.h", "ohpipeline_amd/host/Mpeg4FragmentDecoder.cpp",
-        "tests/cpp/test_mpeg4_fragment_decoder.cpp", "tests/test_mp4f_host_cpp.py"]
+        "tests/cpp/test_mpeg4_fragment_decoder.cpp", "tests/test_mp4f_host_cpp.py", "ohpipeline_amd/csrc/field_bytes.h"]
 
 
 @pytest.mark.parametrize("mine", MINE)

@@ -1,4 +1,4 @@
-"""What makes tests/test_gpu_stream_switch.py able to fail, checked without a device: for each of the seven families whose batch keeps
+"""What makes tests/test_gpu_stream_switch.py able to fail, checked without a device: for each of the eight families whose batch keeps
 per-run device records, the one set of tables of tests/stream_switch_cases.py passes the library's own validation, and the models'
 answers for its two source arenas X and Y differ -- inside EVERY stream's output range of the destination arena, in the results of at
 least one stream, and for MPEG-4 (which has no destination arena) in both tables.  A run that met the other run's records, or bytes of
