@@ -127,5 +127,38 @@ def mixed(key=(32, 16)):
     return _CASES[("mixed", key)]
 
 
+FAR_NEAR0 = 64          # where the near twin of a far message starts (plus the far position's parity): past every filter's history
+
+
+def far_positions(key):
+    """label -> (out_frame0, n_frames): the stream's bit index out_frame0 * D passes 2^32 at the message's frame 9, inside a tile,
+    and so do its byte index (bits / 8: what the fast kernel counts in) and its chunk index (bits / 16); out_frame0 itself passes
+    2^31 inside the first tile and 2^32 inside the second; the message whose last frame is the last below 2^40; and the one frame
+    at out_frame0 = 2^40, the last value the creation admits (2^40 + 1 is refused)."""
+    D = key[0]
+    return {"bit_2p32": ((1 << 32) // D - 9, 513), "byte_2p32": ((1 << 35) // D - 9, 513), "chunk_2p32": ((1 << 36) // D - 9, 17),
+            "frame_2p31": ((1 << 31) - 9, 513), "frame_2p32": ((1 << 32) - 521, 1025),
+            "below_2p40": ((1 << 40) - 513, 513), "at_2p40": (1 << 40, 1), "bit_2p32_short": ((1 << 32) // D - 9, 17)}
+
+
+def positions(key, far):
+    """The messages of far_positions(key) (far) or their near twins: the same frames of the same streams, moved down by an even
+    number of frames to FAR_NEAR0, so that only out_frame0 and src_chunk0 differ between the two batches -- the source bytes, the
+    layout and, the conversion being translation invariant (an even shift keeps the chunks' and the idle pattern's phase), the
+    expected destination bytes are the same."""
+    if ("positions", key, far) not in _CASES:
+        b = Batch(key, 9600 + key[0] + key[1], src_lead=1, dst_lead=3)
+        for k, (label, (out0, n)) in enumerate(far_positions(key).items()):
+            ramp = RAMPS[k % len(RAMPS)] if k % 2 else None
+            b.add(out0 if far else FAR_NEAR0 + out0 % 2, n, FORMATS[k % 3], "noise", ramp, capi.ENDIAN_LITTLE if k % 3 == 1 else capi.ENDIAN_BIG,
+                  before=k % 3, after=k % 2, src_gap=k % 2, dst_gap=1 + k % 3)
+        _CASES[("positions", key, far)] = b.finish(f"{'far' if far else 'near'} positions D={key[0]} T={key[1]}", dst_tail=5)
+    return _CASES[("positions", key, far)]
+
+
 def every_case():
     return [f(key) for key in DESIGNS for f in (shapes, inputs)] + [mixed()]
+
+
+def every_far_case():
+    return [positions(key, far) for key in DESIGNS for far in (False, True)]

@@ -1,9 +1,10 @@
 """What the FLAC decoder's tests share: the fixtures (encoder-made under golden/flac, handmade under golden/flac_decode), a Case =
 one stream descriptor over a byte buffer, the model's answer for a case (tests/flac_textbook.py: results and the whole destination
-arena), and the handful of malformed cases that also run on the device -- each of which tests/test_flac_core_cpu.py first takes
-through the sanitised CPU build.  TEST INFRASTRUCTURE ONLY."""
+arena), the handful of malformed cases that also run on the device -- each of which tests/test_flac_core_cpu.py first takes
+through the sanitised CPU build -- and the layout of cases into the device's two arenas.  TEST INFRASTRUCTURE ONLY."""
 import collections
 import functools
+import hashlib
 import json
 import os
 import random
@@ -11,6 +12,7 @@ import random
 import numpy as np
 
 import flac_textbook as T
+from ohpipeline_amd import capi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OLD_DIR = os.path.join(HERE, "golden", "flac")
@@ -129,7 +131,7 @@ def mixed_cases():
     while len(out) < 64:
         for fx in fixtures():
             packed = bool((k + len(out)) % 2)
-            if fx.name in big or fx.name.startswith("variable") or k % 3 == 0:
+            if fx.name in big or fx.first_sample or k % 3 == 0:       # (a stream that does not start at sample 0: whole, at its own first_sample)
                 out.append(whole(fx, packed))
             else:
                 # from frame j on: another first_sample, the range starting at that frame
@@ -187,3 +189,72 @@ def mutations(seed=20240611):
             b = audio[:lo] + ins + audio[lo:]
         case("splice:%d" % k, tiny, b, max_samples=rnd.choice((96, 96, 200, 40)), first_sample=rnd.choice((0, 0, 16)))
     return out
+
+
+# ---------------------------------------------------------------- on the device
+class Layout:
+    """Cases laid into one source arena (ragged offsets, junk between the ranges) and one destination arena (each case's share
+    starts as pattern from its own index 0, so that the expected arena is the model's arenas side by side)."""
+
+    def __init__(self, cases, seed=1):
+        rng = np.random.default_rng(seed)
+        src, dst0, want = bytearray(), [], []
+        self.descs = np.zeros(len(cases), dtype=capi.FLAC_STREAM_DESC)
+        self.cases = cases
+        at = 0
+        for i, c in enumerate(cases):
+            junk = bytes(rng.integers(0, 256, (i * 7 + 1) % 13, dtype=np.uint8)) + (b"\xff\xf8" if i % 3 == 0 else b"")
+            src += junk
+            d = self.descs[i]
+            d["src_offset"], d["src_bytes"] = len(src), c.src_bytes
+            src += c.data[c.offset:c.offset + c.src_bytes]
+            d["dst_offset"] = at
+            d["dst_plane_stride"] = 0 if c.flags & PACKED_BE else c.max_samples * 4
+            d["first_sample"], d["max_samples"], d["sample_rate"] = c.first_sample, c.max_samples, c.rate
+            d["blocksize"], d["max_blocksize"], d["channels"], d["bits"], d["flags"] = c.blocksize, c.max_blocksize, c.channels, c.bits, c.flags
+            n = arena_bytes(c)
+            pad = -n % 4 + 4 * (i % 2)
+            dst0 += [pattern(n), np.full(pad, 0xEE, dtype=np.uint8)]
+            want += [model(c)[1], np.full(pad, 0xEE, dtype=np.uint8)]
+            at += n + pad
+        src += b"\xff"
+        self.src = np.frombuffer(bytes(src), dtype=np.uint8)
+        self.dst0 = np.concatenate(dst0) if dst0 else np.zeros(0, dtype=np.uint8)
+        self.want = np.concatenate(want) if want else np.zeros(0, dtype=np.uint8)
+
+    def run(self, ctx, times=1):
+        d_src, d_dst = ctx.upload(self.src), ctx.upload(self.dst0)
+        b = ctx.flac_batch(self.descs, self.src.size, self.dst0.size)
+        allocs = []
+        for _ in range(times):
+            ctx.flac_run(b, d_src, d_dst)
+            res = ctx.flac_results(b, len(self.cases))
+            allocs.append(ctx.device_allocations())
+        got = ctx.download(d_dst, self.dst0.size)
+        ctx.batch_destroy(b)
+        ctx.free(d_src)
+        ctx.free(d_dst)
+        self.allocs = allocs
+        return res, got
+
+    def check(self, ctx, times=1):
+        res, got = self.run(ctx, times)
+        for i, c in enumerate(self.cases):
+            r = res[i]
+            mine = (int(r["status"]), int(r["frames"]), int(r["samples"]), int(r["first_sample_decoded"]), int(r["bytes_consumed"]),
+                    int(r["candidates"]), int(r["candidates_rejected"]))
+            assert mine == result_tuple(model(c)[0]), (c.label, mine, result_tuple(model(c)[0]))
+        bad = np.flatnonzero(got != self.want)
+        assert bad.size == 0, f"{bad.size} bytes differ, the first at {bad[0]}"
+        return res, got
+
+
+def device_md5(arena, case):
+    """The MD5 STREAMINFO carries, of what the device wrote for a whole stream."""
+    nb = case.bits // 8
+    if case.flags & PACKED_BE:
+        le = arena.reshape(-1, nb)[:, ::-1]
+    else:
+        planes = arena.view("<i4").reshape(case.channels, case.max_samples)
+        le = np.ascontiguousarray(planes.T).view(np.uint8).reshape(-1, 4)[:, :nb]
+    return hashlib.md5(np.ascontiguousarray(le).tobytes()).digest()

@@ -1,6 +1,7 @@
 """Writes tests/golden/flac_decode/*.flac + index.json: handmade FLAC streams (tests/flac_frames.py's writer) that, together with
 the five encoder-made streams under tests/golden/flac/, cover every form the device decoder reads -- the census
-tests/test_flac_textbook.py asserts.  Each stream's STREAMINFO carries the MD5 of the PCM that went in; index.json records what each
+tests/test_flac_textbook.py asserts -- and, with eight short streams entered far into their audio, every length of coded number and
+first samples up to 2^36 - 48.  Each stream's STREAMINFO carries the MD5 of the PCM that went in; index.json records what each
 holds and the model's census of it.  Where oracle/_ref exists (the reference's own libFLAC 1.2.1, tests/flac_ref.py) every stream is
 decoded with it before it is written -- frames equal, MD5 accepted -- and the padding question of flac_textbook's docstring is put to
 it.  Run from the repository root:  python tests/golden/make_flac_decode_fixtures.py"""
@@ -133,7 +134,27 @@ def build():
     pcm = tone(16 * 6, 16, 8, 2, scale=0.02, noise=1)
     frames = [W.frame(p, 16, 44100, k, [dict(type="fixed", order=1)] * 2, stereo="mid_side") for k, (_, p) in enumerate(cut(pcm, [16] * 6))]
     out["tiny_s16_stereo_44k1_b16"] = dict(data=W.stream(frames, pcm, 16, 44100, 2, min_blocksize=16, max_blocksize=16), blocksize=16)
+
+    # 9. far stream positions: three stereo frames of 16 samples each, entered where the coded number changes its length.  Variable
+    #    blocking from sample 2^31 - 32 (six bytes, then seven at 2^31) and from 2^36 - 48 (the last 36-bit numbers); fixed blocking
+    #    from the frame numbers at which the number grows from 1 to 2, 2 to 3 ... 5 to 6 bytes, and from 2^31 - 3 (the last 31-bit
+    #    numbers): first_sample = number * 16 up to about 2^35.  Totals unknown, as for the variable stream above.
+    for k, first in enumerate(FAR_VARIABLE):
+        pcm = tone(16 * 3, 16, 10 + k, 2, scale=0.02, noise=1)
+        frames = [W.frame(p, 16, 48000, first + at, [dict(type="fixed", order=1), FIXED2], variable=True, stereo="mid_side") for at, p in cut(pcm, [16] * 3)]
+        out["variable_from_%s_s16_stereo_48k_b16" % FAR_VARIABLE[first]] = dict(
+            data=W.stream(frames, pcm, 16, 48000, 2, min_blocksize=16, max_blocksize=16, total_samples=0), blocksize=0, first_sample=first, samples=48)
+    for k, number in enumerate(FAR_FIXED):
+        pcm = tone(16 * 3, 16, 20 + k, 2, scale=0.02, noise=1)
+        frames = [W.frame(p, 16, 44100, number + j, [FIXED2, dict(type="fixed", order=1)], stereo="left_side" if k % 2 else None)
+                  for j, (_, p) in enumerate(cut(pcm, [16] * 3))]
+        out["fixed_from_frame_%s_s16_stereo_44k1_b16" % FAR_FIXED[number]] = dict(
+            data=W.stream(frames, pcm, 16, 44100, 2, min_blocksize=16, max_blocksize=16, total_samples=0), blocksize=16, first_sample=number * 16, samples=48)
     return out
+
+
+FAR_VARIABLE = {(1 << 31) - 32: "2p31m32", (1 << 36) - 48: "2p36m48"}
+FAR_FIXED = {127: "127", 2047: "2047", 65535: "65535", (1 << 21) - 1: "2p21m1", (1 << 26) - 1: "2p26m1", (1 << 31) - 3: "2p31m3"}
 
 
 def ask_the_reference_about_padding():

@@ -52,6 +52,18 @@ def test_every_case_that_goes_to_the_device(driver, tmp_path):
         assert bad.size == 0, f"{c.label}: {bad.size} differing bytes, first at {bad[:6].tolist()}"
 
 
+def test_far_positions_and_their_near_twins(driver, tmp_path):
+    """tests/dsd_pcm_cases.positions: out_frame0 up to 2^40, the stream's bit, byte and chunk index past 2^32 -- and the same frames
+    entered near the stream's start.  The core gives the model's bytes for both, and the two are the same bytes."""
+    cases = DC.every_far_case()
+    assert len(cases) == 8 and max(int(c.descs["out_frame0"].max()) for c in cases) == 1 << 40
+    for c, got in zip(cases, run_cases(driver, cases, tmp_path)):
+        bad = np.nonzero(got != c.want())[0]
+        assert bad.size == 0, f"{c.label}: {bad.size} differing bytes, first at {bad[:6].tolist()}"
+    for key in DC.DESIGNS:
+        assert np.array_equal(DC.positions(key, True).want(), DC.positions(key, False).want()), key
+
+
 def test_the_cases_reach_what_they_are_there_for():
     """All ones clamp to 2^23 - 1, all zeros give -2^23, a stream start reads the idle pattern (it differs from the same bits read
     mid-stream), and the fill between the messages is there to be compared."""

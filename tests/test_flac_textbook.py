@@ -46,8 +46,35 @@ CENSUS = [
     "blocksize:16", "blocksize:192", "blocksize:576", "blocksize:4096", "blocksize:4608",
     "blocksize_code:6", "blocksize_code:7",            # the 8- and the 16-bit trailer
     "rate_code:0", "rate_code:12", "rate_code:13", "rate_code:14",   # STREAMINFO's, kHz, Hz, tens of Hz
-    "blocking:fixed", "blocking:variable", "number_bytes:5",
+    "blocking:fixed", "blocking:variable",
+    "number_bytes:1", "number_bytes:2", "number_bytes:3", "number_bytes:4", "number_bytes:5", "number_bytes:6", "number_bytes:7",
 ]
+
+
+FAR = {   # fixture -> (the first frame's coded number, the coded numbers' lengths); three frames of 16 samples each
+    "variable_from_2p31m32_s16_stereo_48k_b16": ((1 << 31) - 32, [6, 6, 7]),
+    "variable_from_2p36m48_s16_stereo_48k_b16": ((1 << 36) - 48, [7, 7, 7]),
+    "fixed_from_frame_127_s16_stereo_44k1_b16": (127, [1, 2, 2]),
+    "fixed_from_frame_2047_s16_stereo_44k1_b16": (2047, [2, 3, 3]),
+    "fixed_from_frame_65535_s16_stereo_44k1_b16": (65535, [3, 4, 4]),
+    "fixed_from_frame_2p21m1_s16_stereo_44k1_b16": ((1 << 21) - 1, [4, 5, 5]),
+    "fixed_from_frame_2p26m1_s16_stereo_44k1_b16": ((1 << 26) - 1, [5, 6, 6]),
+    "fixed_from_frame_2p31m3_s16_stereo_44k1_b16": ((1 << 31) - 3, [6, 6, 6]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(FAR))
+def test_far_fixtures_sit_where_their_names_say(name):
+    """The streams of far positions: every length of coded number at its transition, first samples past 2^31, 2^32 and up to 2^36."""
+    number, lengths = FAR[name]
+    fx = FC.fixture(name)
+    res, _ = FC.model(FC.whole(fx))
+    variable = name.startswith("variable")
+    assert fx.first_sample == (number if variable else number * 16) and fx.info["total_samples"] == 0 and fx.samples == 48
+    assert [f.header.number for f in res.frames] == [number + (16 * j if variable else j) for j in range(3)]
+    assert [f.header.number_bytes for f in res.frames] == lengths
+    assert res.first_sample_decoded == fx.first_sample and res.places == [0, 16, 32]
+    assert max(FC.fixture(n).first_sample for n in FAR) == (1 << 36) - 48 and sum(FC.fixture(n).first_sample >= 1 << 32 for n in FAR) >= 2
 
 
 def test_census_of_the_committed_fixtures():

@@ -7,12 +7,11 @@ destination arena compared with the model's, the results (status, frames, sample
 rejected) compared field by field, and for whole streams the MD5 of the device's samples compared with the stream's own STREAMINFO.
 Malformed input on the device is the handful of tests/flac_cases.device_cases, every one of which tests/test_flac_core_cpu.py has
 already taken through the sanitised CPU build of the same core; nothing here is random."""
-import hashlib
-
 import numpy as np
 import pytest
 
 import flac_cases as FC
+from flac_cases import Layout, device_md5        # (shared with the far-offset and far-position tests)
 from ohpipeline_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -30,74 +29,6 @@ def vctx(ctx, request):
     ctx.set_kernel_variant(request.param)
     yield ctx
     ctx.set_kernel_variant(0)
-
-
-class Layout:
-    """Cases laid into one source arena (ragged offsets, junk between the ranges) and one destination arena (each case's share
-    starts as FC.pattern from its own index 0, so that the expected arena is the model's arenas side by side)."""
-
-    def __init__(self, cases, seed=1):
-        rng = np.random.default_rng(seed)
-        src, dst0, want = bytearray(), [], []
-        self.descs = np.zeros(len(cases), dtype=capi.FLAC_STREAM_DESC)
-        self.cases = cases
-        at = 0
-        for i, c in enumerate(cases):
-            junk = bytes(rng.integers(0, 256, (i * 7 + 1) % 13, dtype=np.uint8)) + (b"\xff\xf8" if i % 3 == 0 else b"")
-            src += junk
-            d = self.descs[i]
-            d["src_offset"], d["src_bytes"] = len(src), c.src_bytes
-            src += c.data[c.offset:c.offset + c.src_bytes]
-            d["dst_offset"] = at
-            d["dst_plane_stride"] = 0 if c.flags & FC.PACKED_BE else c.max_samples * 4
-            d["first_sample"], d["max_samples"], d["sample_rate"] = c.first_sample, c.max_samples, c.rate
-            d["blocksize"], d["max_blocksize"], d["channels"], d["bits"], d["flags"] = c.blocksize, c.max_blocksize, c.channels, c.bits, c.flags
-            n = FC.arena_bytes(c)
-            pad = -n % 4 + 4 * (i % 2)
-            dst0 += [FC.pattern(n), np.full(pad, 0xEE, dtype=np.uint8)]
-            want += [FC.model(c)[1], np.full(pad, 0xEE, dtype=np.uint8)]
-            at += n + pad
-        src += b"\xff"
-        self.src = np.frombuffer(bytes(src), dtype=np.uint8)
-        self.dst0 = np.concatenate(dst0) if dst0 else np.zeros(0, dtype=np.uint8)
-        self.want = np.concatenate(want) if want else np.zeros(0, dtype=np.uint8)
-
-    def run(self, ctx, times=1):
-        d_src, d_dst = ctx.upload(self.src), ctx.upload(self.dst0)
-        b = ctx.flac_batch(self.descs, self.src.size, self.dst0.size)
-        allocs = []
-        for _ in range(times):
-            ctx.flac_run(b, d_src, d_dst)
-            res = ctx.flac_results(b, len(self.cases))
-            allocs.append(ctx.device_allocations())
-        got = ctx.download(d_dst, self.dst0.size)
-        ctx.batch_destroy(b)
-        ctx.free(d_src)
-        ctx.free(d_dst)
-        self.allocs = allocs
-        return res, got
-
-    def check(self, ctx, times=1):
-        res, got = self.run(ctx, times)
-        for i, c in enumerate(self.cases):
-            r = res[i]
-            mine = (int(r["status"]), int(r["frames"]), int(r["samples"]), int(r["first_sample_decoded"]), int(r["bytes_consumed"]),
-                    int(r["candidates"]), int(r["candidates_rejected"]))
-            assert mine == FC.result_tuple(FC.model(c)[0]), (c.label, mine, FC.result_tuple(FC.model(c)[0]))
-        bad = np.flatnonzero(got != self.want)
-        assert bad.size == 0, f"{bad.size} bytes differ, the first at {bad[0]}"
-        return res, got
-
-
-def device_md5(arena, case):
-    """The MD5 STREAMINFO carries, of what the device wrote for a whole stream."""
-    nb = case.bits // 8
-    if case.flags & FC.PACKED_BE:
-        le = arena.reshape(-1, nb)[:, ::-1]
-    else:
-        planes = arena.view("<i4").reshape(case.channels, case.max_samples)
-        le = np.ascontiguousarray(planes.T).view(np.uint8).reshape(-1, 4)[:, :nb]
-    return hashlib.md5(np.ascontiguousarray(le).tobytes()).digest()
 
 
 @pytest.mark.parametrize("packed", [False, True], ids=["planes", "packed_be"])

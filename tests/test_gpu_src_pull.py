@@ -6,10 +6,9 @@ import pytest
 
 import src_pull_model as PM
 from ohpipeline_amd import capi
+from src_pull_cases import S, Arena, expected, stream       # (the builders: shared with the far-offset and far-position tests)
 
 pytestmark = pytest.mark.gpu
-
-S = 8
 
 
 @pytest.fixture(scope="module")
@@ -35,42 +34,6 @@ def pulled_filter(ctx, rate_in, rate_out, T, max_pull=0.001):
     return _filters[key]
 
 
-class Arena:
-    """Streams' input laid out in one source arena, their messages' outputs back to back in one destination arena."""
-
-    def __init__(self):
-        self.src = bytearray()
-        self.descs = []
-        self.dst_bytes = 0
-
-    def add_input(self, data):
-        off = len(self.src)
-        self.src += bytes(data)
-        self.src += bytes((-len(self.src)) % 16)
-        return off
-
-    def add_msg(self, src_offset, src_frame0, src_frames, pos, frac, step, n, ch, sb, se, db, de, flags=0, ramp=(0, 0)):
-        d = np.zeros(1, dtype=capi.SRC_PULL_MSG_DESC)[0]
-        d["src_offset"], d["src_frame0"], d["src_frames"] = src_offset, src_frame0, src_frames
-        d["pos_frame"], d["pos_frac"], d["step"], d["n_frames"] = pos, frac, step, n
-        d["dst_offset"] = self.dst_bytes
-        d["ramp_start"], d["ramp_end"], d["attenuation"] = ramp[0], ramp[1], capi.UNITY_ATTENUATION
-        d["channels"], d["src_bits"], d["src_endian"], d["dst_bits"], d["dst_endian"], d["flags"] = ch, sb, se, db, de, flags
-        self.descs.append(d)
-        self.dst_bytes += n * ch * db // 8
-
-    def arrays(self):
-        return np.frombuffer(bytes(self.src) or b"\0", dtype=np.uint8).copy(), np.array(self.descs, dtype=capi.SRC_PULL_MSG_DESC)
-
-
-def expected(table, descs, src, dst_bytes, ramp_table):
-    want = np.zeros(dst_bytes, dtype=np.uint8)
-    for d in descs:
-        b = PM.message_bytes(table, S, d, src, ramp_table)
-        want[int(d["dst_offset"]):int(d["dst_offset"]) + b.size] = b
-    return want
-
-
 def run(ctx, flt, descs, src, dst_bytes, times=1):
     d_src, d_dst = ctx.upload(src), ctx.malloc(max(dst_bytes, 1))
     ctx.memset(d_dst, 0, max(dst_bytes, 1))
@@ -84,19 +47,6 @@ def run(ctx, flt, descs, src, dst_bytes, times=1):
     ctx.free(d_src)
     ctx.free(d_dst)
     return outs, info
-
-
-def stream(arena, rng, ch, sb, se, db, de, T, steps, sizes, in_frames, flags_of=lambda m: 0, ramps_of=lambda m: (0, 0), pos0=(0, 0)):
-    """One stream of random packed input whose messages take the given sizes and steps in turn, each reading the whole input."""
-    data = rng.integers(0, 256, size=in_frames * ch * sb // 8, dtype=np.uint8)
-    off = arena.add_input(data)
-    pos, frac = pos0
-    for m, (st, n) in enumerate(zip(steps, sizes)):
-        first, frames = PM.window(pos, frac, st, n, T)
-        if first + frames > in_frames:
-            break
-        arena.add_msg(off, 0, in_frames, pos, frac, st, n, ch, sb, se, db, de, flags_of(m), ramps_of(m))
-        pos, frac = PM.advance(pos, frac, st, n)
 
 
 @pytest.mark.parametrize("T", [32, 64])
