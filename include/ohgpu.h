@@ -1731,4 +1731,8 @@ int ohgpu_set_kernel_variant(ohgpu_ctx* ctx, int variant);
 #ifdef __cplusplus
 }
 #endif
+
+/* Protected fragmented MPEG-4 (ohgpu_cenc_*) has a header of its own beside this one; it comes with this one. */
+#include "ohgpu_cenc.h"
+
 #endif /* OHGPU_H */

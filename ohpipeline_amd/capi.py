@@ -185,6 +185,12 @@ MP4F_STREAM_RESULT = np.dtype([("status", "<u4"), ("codec", "<u4"), ("track_id",
                                ("first_bad_sample", "<u4"), ("entry_rate", "<u4"), ("entry_channels", "<u2"), ("entry_bits", "<u2"), ("bytes_gathered", "<u8"),
                                ("moov_offset", "<u8"), ("first_moof_offset", "<u8"), ("error_offset", "<u8")], align=False)
 assert MP4F_STREAM_DESC.itemsize == 64 and MP4F_RUN.itemsize == 32 and MP4F_STREAM_RESULT.itemsize == 168
+# protected fragmented MPEG-4: ohgpu_cenc_stream_desc (112 B), ohgpu_cenc_stream_result (208 B); statuses 0..6 are MP4F_*
+CENC_NO_KEY, CENC_HAVE_KEY, CENC_SCHEME = 7, 1, 0x63656e63
+CENC_STREAM_DESC = np.dtype(MP4F_STREAM_DESC.descr + [("key_flags", "<u4"), ("reserved2", "<u4", (3,)), ("kid", "u1", (16,)), ("key", "u1", (16,))], align=False)
+CENC_STREAM_RESULT = np.dtype([("mp4f", MP4F_STREAM_RESULT), ("entry", "<u4"), ("scheme", "<u4"), ("is_protected", "u1"), ("iv_size", "u1"), ("pad", "u1", (2,)),
+                               ("reserved", "<u4"), ("kid", "u1", (16,)), ("blocks", "<u8")], align=False)
+assert CENC_STREAM_DESC.itemsize == 112 and CENC_STREAM_RESULT.itemsize == 208
 # PCM files: ohgpu_iff_stream_desc (64 B), ohgpu_iff_stream_result (80 B)
 IFF_OK, IFF_NOT_IFF, IFF_TRUNCATED, IFF_INVALID, IFF_UNSUPPORTED = range(5)
 IFF_KIND_WAV, IFF_KIND_AIFF, IFF_KIND_AIFC = 1, 2, 3
@@ -376,6 +382,23 @@ SYMBOLS = {
     "ohgpu_src_pull_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "ohgpu_src_pull_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64]),
 }
+# include/ohgpu_cenc.h's, the part of the ABI that has a header of its own
+CENC_SYMBOLS = {
+    "ohgpu_cenc_batch_check": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64]),
+    "ohgpu_cenc_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
+    "ohgpu_cenc_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "ohgpu_cenc_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_cenc_batch_runs": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_cenc_batch_packets": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_cenc_batch_samples": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_cenc_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
+    "ohgpu_cenc_batch_paths": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "ohgpu_cenc_head": (C.c_int, [_vp, C.c_size_t, _vp]),
+    "ohgpu_cenc_process_host": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "ohgpu_cenc_flac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ohgpu_cenc_alac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
 
 
 class OhGpuError(RuntimeError):
@@ -396,7 +419,7 @@ def lib():
         raise ImportError(f"{LIB_PATH} is missing: build the HIP extension first (python ohpipeline_amd/build.py); "
                           "there is no CPU fallback for the product path")
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(CENC_SYMBOLS.items()):
         fn = getattr(L, name)          # AttributeError here = the library does not export what ohgpu.h declares
         fn.restype = res
         fn.argtypes = args
@@ -659,6 +682,27 @@ def mp4f_head(data):
     raw = bytes(data)
     res = np.zeros(1, dtype=MP4F_STREAM_RESULT)
     check(lib().ohgpu_mp4f_head(raw, len(raw), res.ctypes.data_as(C.c_void_p)))
+    return res[0]
+
+
+def _cenc_descs(descs):
+    d = np.ascontiguousarray(descs)
+    assert d.dtype == CENC_STREAM_DESC
+    return d
+
+
+def cenc_batch_check(descs, n_packets, n_runs, src_arena_bytes, dst_arena_bytes):
+    """The validation of ctx.cenc_batch without a device (ohgpu_cenc_batch_check): OhGpuError on a bad descriptor."""
+    d = _cenc_descs(descs)
+    check(lib().ohgpu_cenc_batch_check(_ptr_or_none(d), d.size, n_packets, n_runs, src_arena_bytes, dst_arena_bytes))
+
+
+def cenc_head(data):
+    """The walk of a protected or clear fragmented stream up to the end of moov (ohgpu_cenc_head; host only, no key): a CENC_STREAM_RESULT
+    record whose is_protected and kid say which key to ask for."""
+    raw = bytes(data)
+    res = np.zeros(1, dtype=CENC_STREAM_RESULT)
+    check(lib().ohgpu_cenc_head(raw, len(raw), res.ctypes.data_as(C.c_void_p)))
     return res[0]
 
 
@@ -1240,6 +1284,74 @@ class Context:
         ares, pres = np.zeros(m.size, dtype=ALAC_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET_RESULT)
         check(lib().ohgpu_mp4f_alac_process_host(self._h, _ptr_or_none(m), _ptr_or_none(a), m.size, n_packets, n_runs, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst),
                                                  dst.nbytes, _ptr_or_none(res), _ptr_or_none(runs), _ptr_or_none(pk), _ptr_or_none(sm), _ptr_or_none(ares), _ptr_or_none(pres)))
+        return res, runs, pk, sm, ares, pres
+
+    def cenc_batch(self, descs, n_packets, n_runs, src_arena_bytes, dst_arena_bytes):
+        d = _cenc_descs(descs)
+        b = C.c_void_p()
+        check(lib().ohgpu_cenc_batch_create(self._h, _ptr_or_none(d), d.size, n_packets, n_runs, src_arena_bytes, dst_arena_bytes, C.byref(b)))
+        return b
+
+    def cenc_run(self, batch, d_src, d_dst, stream=None):
+        """Walk, run sums, carries, expand, finish, decrypt-gather (ohgpu_cenc_batch_run): queued on the stream."""
+        check(lib().ohgpu_cenc_batch_run(self._h, batch, d_src, d_dst, stream))
+
+    def cenc_results(self, batch, n, n_packets, n_runs):
+        """The last run's (CENC_STREAM_RESULT per stream, the run table, the packet table, the sample table); waits for the run."""
+        res, runs = np.zeros(n, dtype=CENC_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
+        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
+        check(lib().ohgpu_cenc_batch_results(self._h, batch, _ptr_or_none(res), n))
+        check(lib().ohgpu_cenc_batch_runs(self._h, batch, _ptr_or_none(runs), n_runs))
+        check(lib().ohgpu_cenc_batch_packets(self._h, batch, _ptr_or_none(pk), n_packets))
+        check(lib().ohgpu_cenc_batch_samples(self._h, batch, _ptr_or_none(sm), n_packets))
+        return res, runs, pk, sm
+
+    def cenc_phase_ms(self, batch):
+        """(walk, run sums, carries, expand, finish, decrypt-gather) of the last run in milliseconds."""
+        ms = (C.c_float * 6)()
+        check(lib().ohgpu_cenc_batch_phase_ms(self._h, batch, ms))
+        return tuple(float(v) for v in ms)
+
+    def cenc_paths(self, batch):
+        """{route, tiles, wave_blocks: the persistent decrypt-gather launch's workgroups} of a protected MPEG-4 batch (ohgpu_cenc_batch_paths)."""
+        route, tiles, blocks = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        check(lib().ohgpu_cenc_batch_paths(batch, C.byref(route), C.byref(tiles), C.byref(blocks)))
+        return dict(route=int(route.value), tiles=int(tiles.value), wave_blocks=int(blocks.value))
+
+    def cenc_process_host(self, descs, n_packets, n_runs, src, dst):
+        """Host bytes in (ohgpu_cenc_process_host), the clear runs into dst; returns (results, run table, packet table, sample table)."""
+        d = _cenc_descs(descs)
+        res, runs = np.zeros(d.size, dtype=CENC_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
+        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
+        check(lib().ohgpu_cenc_process_host(self._h, _ptr_or_none(d), d.size, n_packets, n_runs, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst), dst.nbytes,
+                                            _ptr_or_none(res), _ptr_or_none(runs), _ptr_or_none(pk), _ptr_or_none(sm)))
+        return res, runs, pk, sm
+
+    def cenc_flac_process_host(self, cenc_descs, flac_descs, n_packets, n_runs, src, mid_bytes, dst, frames_capacity=0):
+        """Protected fLaC from host buffers to PCM (ohgpu_cenc_flac_process_host); returns (results, run table, packet table, sample table,
+        FLAC results, frames)."""
+        m, f = _cenc_descs(cenc_descs), np.ascontiguousarray(flac_descs)
+        assert f.dtype == FLAC_STREAM_DESC and f.size == m.size
+        res, runs = np.zeros(m.size, dtype=CENC_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
+        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
+        fres, frames = np.zeros(m.size, dtype=FLAC_STREAM_RESULT), np.zeros(frames_capacity, dtype=FLAC_FRAME)
+        n_frames = C.c_size_t(0)
+        check(lib().ohgpu_cenc_flac_process_host(self._h, _ptr_or_none(m), _ptr_or_none(f), m.size, n_packets, n_runs, _ptr_or_none(src), src.nbytes, mid_bytes,
+                                                 _ptr_or_none(dst), dst.nbytes, _ptr_or_none(res), _ptr_or_none(runs), _ptr_or_none(pk), _ptr_or_none(sm),
+                                                 _ptr_or_none(fres), _ptr_or_none(frames), frames_capacity, C.byref(n_frames)))
+        return res, runs, pk, sm, fres, frames[:min(int(n_frames.value), frames_capacity)]
+
+    def cenc_alac_process_host(self, cenc_descs, alac_descs, n_packets, n_runs, src, mid_bytes, dst):
+        """Protected alac from host buffers to PCM (ohgpu_cenc_alac_process_host); returns (results, run table, packet table, sample table,
+        Apple Lossless stream results, packet results indexed as the tables are)."""
+        m, a = _cenc_descs(cenc_descs), np.ascontiguousarray(alac_descs)
+        assert a.dtype == ALAC_STREAM_DESC and a.size == m.size
+        res, runs = np.zeros(m.size, dtype=CENC_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
+        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
+        ares, pres = np.zeros(m.size, dtype=ALAC_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET_RESULT)
+        check(lib().ohgpu_cenc_alac_process_host(self._h, _ptr_or_none(m), _ptr_or_none(a), m.size, n_packets, n_runs, _ptr_or_none(src), src.nbytes, mid_bytes,
+                                                 _ptr_or_none(dst), dst.nbytes, _ptr_or_none(res), _ptr_or_none(runs), _ptr_or_none(pk), _ptr_or_none(sm), _ptr_or_none(ares),
+                                                 _ptr_or_none(pres)))
         return res, runs, pk, sm, ares, pres
 
     def iff_batch(self, descs, src_arena_bytes, dst_arena_bytes):

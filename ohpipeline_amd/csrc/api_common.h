@@ -4,6 +4,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cstring>
 #include <memory>
 #include <new>
 #include <utility>
@@ -277,6 +278,53 @@ int alac_process_host(ohgpu_ctx* ctx, const char* who, size_t n, size_t n_packet
         });
     if (err == OHGPU_OK && stream_results && n) memcpy(stream_results, sres.data(), n * sizeof(sres[0]));
     if (err == OHGPU_OK && packet_results && n_packets) memcpy(packet_results, pres.data(), n_packets * sizeof(pres[0]));
+    return err;
+}
+
+// The whole of a fragmented family's fused call to the FLAC decoder (ohgpu_mp4f_flac_process_host, ohgpu_cenc_flac_process_host): one
+// upload, create(&batch) = the family's batch over a middle arena of mid_bytes that lives on the device only, run_fetch(batch, d_src,
+// d_mid, results) = the family's run and its results and tables home, a FLAC batch over the runs the family wrote (a stream's src_bytes is
+// its bytes_gathered, 0 for a stream that is not fLaC), and of dst_host the samples that were decoded.  head(result) -> the result's
+// ohgpu_mp4f_stream_result.  flac_descs[i].src_offset must be descs[i].dst_offset.
+template <typename Desc, typename Res, typename Create, typename RunFetch, typename Head>
+int frag_flac_process_host(ohgpu_ctx* ctx, const char* who, const Desc* descs, const ohgpu_flac_stream_desc* flac_descs, size_t n, const void* src_host, uint64_t src_bytes,
+                           uint64_t mid_bytes, void* dst_host, uint64_t dst_bytes, Res* results, ohgpu_flac_stream_result* flac_results, ohgpu_flac_frame* frames,
+                           size_t frames_capacity, size_t* n_frames, Create&& create, RunFetch&& run_fetch, Head&& head)
+{
+    if (n && (!descs || !flac_descs)) return set_error(OHGPU_ERR_INVALID, "%s: null argument", who);
+    for (size_t i = 0; i < n; i++)
+        if (flac_descs[i].src_offset != descs[i].dst_offset)
+            return set_error(OHGPU_ERR_INVALID, "%s: stream %zu: the FLAC descriptor reads at %llu where the demultiplexer gathers at %llu", who, i,
+                             (unsigned long long)flac_descs[i].src_offset, (unsigned long long)descs[i].dst_offset);
+    if (n_frames) *n_frames = 0;
+    std::vector<Res> mres(n);
+    std::vector<ohgpu_flac_stream_result> fres(n);
+    std::vector<ohgpu_flac_stream_desc> fdescs(flac_descs, flac_descs + n);
+    void* d_mid = nullptr;
+    const int err = decoder_process_host(ctx, who, src_host, src_bytes, dst_host, dst_bytes, create,
+        [&](const ohgpu_batch* b, const void* d_src, void* d_dst) {
+            if (!n) return (int)OHGPU_OK;
+            OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &d_mid, mid_bytes ? mid_bytes : 1));      // the middle arena: the gathered bytes never leave the device
+            int e = run_fetch(b, d_src, d_mid, mres.data());
+            if (e != OHGPU_OK) return e;
+            for (size_t i = 0; i < n; i++) fdescs[i].src_bytes = head(mres[i]).codec == mp4box::fourcc('f', 'L', 'a', 'C') ? head(mres[i]).bytes_gathered : 0u;
+            ohgpu_batch* fb = nullptr;
+            e = ohgpu_flac_batch_create(ctx, fdescs.data(), n, mid_bytes, dst_bytes, &fb);
+            if (e != OHGPU_OK) return e;
+            const BatchPtr own(fb, BatchDeleter{ctx});
+            e = ohgpu_flac_batch_run(ctx, fb, d_mid, d_dst, nullptr);
+            if (e == OHGPU_OK) e = ohgpu_flac_batch_results(ctx, fb, fres.data(), n);
+            if (e == OHGPU_OK && (frames || n_frames)) e = ohgpu_flac_batch_frames(ctx, fb, frames, frames ? frames_capacity : 0, n_frames);
+            return e;
+        },
+        [&] {   // only what was decoded comes back, as in ohgpu_flac_process_host
+            int e = OHGPU_OK;
+            for (size_t i = 0; i < n && e == OHGPU_OK; i++) e = flac_download_decoded(ctx, who, fdescs[i], fres[i], dst_host);
+            return e;
+        });
+    if (d_mid) { (void)hipStreamSynchronize(ctx->stream); ctx_dev_free(ctx, d_mid); }
+    if (err == OHGPU_OK && results && n) memcpy(results, mres.data(), n * sizeof(mres[0]));
+    if (err == OHGPU_OK && flac_results && n) memcpy(flac_results, fres.data(), n * sizeof(fres[0]));
     return err;
 }
 

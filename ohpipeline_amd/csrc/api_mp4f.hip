@@ -84,7 +84,7 @@ int ohgpu_mp4f_batch_create(ohgpu_ctx* ctx, const ohgpu_mp4f_stream_desc* descs,
         b->src_bytes_touched += descs[i].src_bytes;
         if ((descs[i].flags & OHGPU_MP4F_GATHER) && descs[i].dst_capacity) g.gathers = true;
     }
-    err = mp4f_plan(ctx, b.get(), (const mp4frag::Stream*)descs);
+    err = mp4f_plan(ctx, g, (const mp4frag::Stream*)descs, "ohgpu_mp4f_batch_create");
     return batch_done(err, b, out);
 }
 
@@ -177,44 +177,14 @@ int ohgpu_mp4f_flac_process_host(ohgpu_ctx* ctx, const ohgpu_mp4f_stream_desc* m
                                  ohgpu_mp4f_stream_result* mp4f_results, ohgpu_mp4f_run* runs, ohgpu_alac_packet* packets, ohgpu_mp4_sample* samples,
                                  ohgpu_flac_stream_result* flac_results, ohgpu_flac_frame* frames, size_t frames_capacity, size_t* n_frames)
 {
-    const char* const who = "ohgpu_mp4f_flac_process_host";
-    if (n && (!mp4f_descs || !flac_descs)) return set_error(OHGPU_ERR_INVALID, "%s: null argument", who);
-    for (size_t i = 0; i < n; i++)
-        if (flac_descs[i].src_offset != mp4f_descs[i].dst_offset)
-            return set_error(OHGPU_ERR_INVALID, "%s: stream %zu: the FLAC descriptor reads at %llu where the demultiplexer gathers at %llu", who, i,
-                             (unsigned long long)flac_descs[i].src_offset, (unsigned long long)mp4f_descs[i].dst_offset);
-    if (n_frames) *n_frames = 0;
-    std::vector<ohgpu_mp4f_stream_result> mres(n);
-    std::vector<ohgpu_flac_stream_result> fres(n);
-    std::vector<ohgpu_flac_stream_desc> fdescs(flac_descs, flac_descs + n);
-    void* d_mid = nullptr;
-    const int err = decoder_process_host(ctx, who, src_host, src_bytes, dst_host, dst_bytes,
+    return frag_flac_process_host(ctx, "ohgpu_mp4f_flac_process_host", mp4f_descs, flac_descs, n, src_host, src_bytes, mid_bytes, dst_host, dst_bytes, mp4f_results, flac_results,
+        frames, frames_capacity, n_frames,
         [&](ohgpu_batch** b) { return ohgpu_mp4f_batch_create(ctx, mp4f_descs, n, n_packets, n_runs, src_bytes, mid_bytes, b); },
-        [&](const ohgpu_batch* b, const void* d_src, void* d_dst) {
-            if (!n) return (int)OHGPU_OK;
-            OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &d_mid, mid_bytes ? mid_bytes : 1));      // the middle arena: the gathered bytes never leave the device
-            int e = ohgpu_mp4f_batch_run(ctx, b, d_src, d_mid, nullptr);
-            if (e == OHGPU_OK) e = mp4f_fetch_all(ctx, b, n, n_packets, n_runs, mres.data(), runs, packets, samples);   // (the results: the one small read between the layers)
-            if (e != OHGPU_OK) return e;
-            for (size_t i = 0; i < n; i++) fdescs[i].src_bytes = mres[i].codec == mp4box::fourcc('f', 'L', 'a', 'C') ? mres[i].bytes_gathered : 0u;
-            ohgpu_batch* fb = nullptr;
-            e = ohgpu_flac_batch_create(ctx, fdescs.data(), n, mid_bytes, dst_bytes, &fb);
-            if (e != OHGPU_OK) return e;
-            const BatchPtr own(fb, BatchDeleter{ctx});
-            e = ohgpu_flac_batch_run(ctx, fb, d_mid, d_dst, nullptr);
-            if (e == OHGPU_OK) e = ohgpu_flac_batch_results(ctx, fb, fres.data(), n);
-            if (e == OHGPU_OK && (frames || n_frames)) e = ohgpu_flac_batch_frames(ctx, fb, frames, frames ? frames_capacity : 0, n_frames);
-            return e;
+        [&](const ohgpu_batch* b, const void* d_src, void* d_mid, ohgpu_mp4f_stream_result* res) {
+            const int e = ohgpu_mp4f_batch_run(ctx, b, d_src, d_mid, nullptr);
+            return e != OHGPU_OK ? e : mp4f_fetch_all(ctx, b, n, n_packets, n_runs, res, runs, packets, samples);   // (the results: the one small read between the layers)
         },
-        [&] {   // only what was decoded comes back, as in ohgpu_flac_process_host
-            int e = OHGPU_OK;
-            for (size_t i = 0; i < n && e == OHGPU_OK; i++) e = flac_download_decoded(ctx, who, fdescs[i], fres[i], dst_host);
-            return e;
-        });
-    if (d_mid) { (void)hipStreamSynchronize(ctx->stream); ctx_dev_free(ctx, d_mid); }
-    if (err == OHGPU_OK && mp4f_results && n) memcpy(mp4f_results, mres.data(), n * sizeof(mres[0]));
-    if (err == OHGPU_OK && flac_results && n) memcpy(flac_results, fres.data(), n * sizeof(fres[0]));
-    return err;
+        [](const ohgpu_mp4f_stream_result& r) -> const ohgpu_mp4f_stream_result& { return r; });
 }
 
 int ohgpu_mp4f_alac_process_host(ohgpu_ctx* ctx, const ohgpu_mp4f_stream_desc* mp4f_descs, const ohgpu_alac_stream_desc* alac_descs, size_t n, size_t n_packets, size_t n_runs,

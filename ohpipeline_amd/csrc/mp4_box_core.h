@@ -146,6 +146,26 @@ struct Walk {
         return kOk;
     }
 
+    // The inner `alac` box of a sample entry (at c, its header read into k): the configuration and the packet limit.
+    MP4B_HD uint32_t alac_box(uint64_t c, const Box& k)
+    {
+        const uint64_t a = c + k.header;
+        if (k.size - k.header < 28u) return fail(kUnsupported, c);
+        const uint32_t w8 = be32(p, a + 8), w12 = be32(p, a + 12);   // (the six one-byte fields and max_run, as two words)
+        if (w8 >> 24) return fail(kUnsupported, c);
+        Config& g = tr.cfg;
+        g.frame_length = be32(p, a + 4);
+        g.compatible_version = (uint8_t)(w8 >> 24); g.bit_depth = (uint8_t)(w8 >> 16); g.pb = (uint8_t)(w8 >> 8); g.mb = (uint8_t)w8;
+        g.kb = (uint8_t)(w12 >> 24); g.channels = (uint8_t)(w12 >> 16);
+        g.max_run = (uint16_t)w12;
+        g.max_frame_bytes = be32(p, a + 16); g.avg_bit_rate = be32(p, a + 20); g.sample_rate = be32(p, a + 24);
+        // what ohgpu_alac_batch_check would refuse is refused here, where it costs one stream and not the batch
+        const bool depth_ok = g.bit_depth == 16 || g.bit_depth == 20 || g.bit_depth == 24 || g.bit_depth == 32;
+        if (g.channels < 1 || g.channels > 8 || g.frame_length < 1 || g.frame_length > 16384u || !depth_ok) return fail(kUnsupported, c);
+        tr.t.packet_limit = (uint64_t)g.frame_length * g.channels * 5u + 64u;
+        return kOk;
+    }
+
     MP4B_HD uint32_t stsd(uint64_t box, uint64_t pay, uint64_t len)
     {
         uint32_t count;
@@ -166,21 +186,7 @@ struct Walk {
             if (!visit()) return fail(kInvalid, c);
             if (read_box(p, c, entry_end, false, &k) != 1 || k.size > entry_end - c) return fail(kInvalid, c);
             if (k.type != fourcc('a', 'l', 'a', 'c')) { c += k.size; continue; }
-            const uint64_t a = c + k.header;
-            if (k.size - k.header < 28u) return fail(kUnsupported, c);
-            const uint32_t w8 = be32(p, a + 8), w12 = be32(p, a + 12);   // (the six one-byte fields and max_run, as two words)
-            if (w8 >> 24) return fail(kUnsupported, c);
-            Config& g = tr.cfg;
-            g.frame_length = be32(p, a + 4);
-            g.compatible_version = (uint8_t)(w8 >> 24); g.bit_depth = (uint8_t)(w8 >> 16); g.pb = (uint8_t)(w8 >> 8); g.mb = (uint8_t)w8;
-            g.kb = (uint8_t)(w12 >> 24); g.channels = (uint8_t)(w12 >> 16);
-            g.max_run = (uint16_t)w12;
-            g.max_frame_bytes = be32(p, a + 16); g.avg_bit_rate = be32(p, a + 20); g.sample_rate = be32(p, a + 24);
-            // what ohgpu_alac_batch_check would refuse is refused here, where it costs one stream and not the batch
-            const bool depth_ok = g.bit_depth == 16 || g.bit_depth == 20 || g.bit_depth == 24 || g.bit_depth == 32;
-            if (g.channels < 1 || g.channels > 8 || g.frame_length < 1 || g.frame_length > 16384u || !depth_ok) return fail(kUnsupported, c);
-            tr.t.packet_limit = (uint64_t)g.frame_length * g.channels * 5u + 64u;
-            return kOk;
+            return alac_box(c, k);
         }
         return fail(kUnsupported, entry);
     }

@@ -14,6 +14,8 @@
 //   expansion   sample i of run r lies at place_r + the sizes of the run's samples in front of it, and begins at frame_r + their
 //               durations.  emit() writes both rows and judges the refusal.
 //   the gather  a piece is the part of a run's bytes that belongs to rows [gather_first_row, samples_available): piece_of().
+// The walk takes a policy (WalkT<P>): Clear, this layer's, admits clear tracks only; csrc/cenc_core.h's reads the protection boxes where
+// the hooks stand (an `enca` entry, moov's end, a traf's other boxes and its end) and shares everything else with this walk.
 // A run has at most kMaxRunSamples samples: that bounds what one workgroup of the expansion sums in front of its tile, and what the walk's
 // lane sums for a run beyond run_capacity.
 // Places are signed 64-bit (a data_offset may be negative), a base_data_offset beyond kFar counts as kFar, and a stream has at most
@@ -34,7 +36,8 @@ using mp4box::read_box;
 using mp4box::Row;
 using mp4box::Sample;
 
-enum Status : uint32_t { kOk = 0, kNotMp4 = 1, kTruncated = 2, kInvalid = 3, kNotCodec = 4, kUnsupported = 5, kNotFragmented = 6 };
+enum Status : uint32_t { kOk = 0, kNotMp4 = 1, kTruncated = 2, kInvalid = 3, kNotCodec = 4, kUnsupported = 5, kNotFragmented = 6,
+                         kNoKey = 7 };     // (kNoKey: the protected family's alone, csrc/cenc_core.h -- this walk never gives it)
 constexpr uint32_t kMaxSamples = 1u << 24, kMaxRunSamples = 1u << 16, kMaxBoxes = 65536, kNone = 0xffffffffu;
 constexpr uint32_t kTile = 1024;                      // samples a tile: one workgroup's share of the expansion
 constexpr uint32_t kCodecAlac = 1, kCodecFlac = 2, kGather = 1;
@@ -78,7 +81,8 @@ struct RunRec {
     uint64_t time;                        // kTimed: the run's first frame; the carries set it otherwise
     uint64_t bytes, frames;               // the totals
     uint64_t gathered;                    // the bytes of the stream's runs in front of it (the carries)
-    uint32_t first_sample, pad;
+    uint32_t first_sample;
+    uint32_t iv_pos;                      // a protected track's: its first sample's IV, from the stream's first byte (the traf's end sets it); else 0
 };
 enum { kPlaced = 1, kTimed = 2 };
 // What the walk and the later phases keep of one stream.
@@ -103,7 +107,21 @@ MP4B_HD void totals_serial(const uint8_t* p, const RunRec& r, uint32_t count, ui
     *bytes = b; *frames = f;
 }
 
-struct Walk {
+// What a walk admits besides clear tracks.  Clear admits nothing: an `enca` entry stays UNSUPPORTED and a traf's other boxes are passed
+// over.  csrc/cenc_core.h has the policy that reads the protection boxes; its hooks are called where these are, with the walk itself.
+struct Clear {
+    static constexpr bool kAdmits = false;
+    template <class W> MP4B_HD uint32_t entry(W&, uint64_t, uint64_t, uint64_t, bool*) { return kOk; }       // an `enca` sample entry
+    template <class W> MP4B_HD uint32_t after_moov(W&) { return kOk; }
+    MP4B_HD void trak_begin() {}
+    MP4B_HD void traf_begin() {}
+    template <class W> MP4B_HD void traf_box(W&, uint32_t, uint64_t, uint64_t, uint64_t) {}                   // a traf's child that is no tfhd, tfdt or trun
+    template <class W> MP4B_HD uint32_t traf_end(W&, uint64_t, uint32_t, uint32_t) { return kOk; }           // (the traf, its first run, its samples)
+};
+
+template <class P>
+struct WalkT {
+    P prot;
     const uint8_t* p;         // the stream's first byte
     uint32_t n;               // its bytes
     uint32_t visited;
@@ -184,6 +202,11 @@ struct Walk {
         mp4box::Track fresh = {};
         w.tr = fresh;
         const uint32_t st = w.stsd(box, pay, len);
+        if (P::kAdmits && st == kUnsupported && w.tr.codec == fourcc('e', 'n', 'c', 'a')) {      // (the entry's box was read and held to its parent)
+            Box e;
+            (void)read_box(p, pay + 8u, pay + len, false, &e);
+            return prot.entry(*this, pay + 8u, pay + 8u + e.header, pay + 8u + e.size, parsed);
+        }
         if (st != kOk) return fail(st, w.err_at);
         codec = w.tr.codec;
         if (codec == fourcc('a', 'l', 'a', 'c')) {
@@ -213,6 +236,7 @@ struct Walk {
     {
         bool have_tkhd = false, have_mdhd = false, have_stsd = false, have_stsz = false, parsed = false;
         codec = 0; stsz_samples = 0;
+        prot.trak_begin();
         const uint32_t st = children(pay, pay + len, [&](uint32_t type, uint64_t at, uint64_t q, uint64_t m) -> uint32_t {
             if (type == fourcc('t', 'k', 'h', 'd') && !have_tkhd) {
                 have_tkhd = true;
@@ -281,6 +305,9 @@ struct Walk {
         bool have_tfhd = false, mine = false, have_size = false, have_dur = false, first_run = true, timed = false;
         uint32_t def_size = 0, def_dur = 0;
         uint64_t base = moof, time = 0;
+        const uint32_t run0 = n_runs;
+        const uint64_t samples0 = samples;
+        prot.traf_begin();
         const uint32_t st = children(pay, pay + len, [&](uint32_t type, uint64_t at, uint64_t q, uint64_t m) -> uint32_t {
             const bool tfhd = type == fourcc('t', 'f', 'h', 'd'), tfdt = type == fourcc('t', 'f', 'd', 't'), trun = type == fourcc('t', 'r', 'u', 'n');
             if (tfhd && !have_tfhd) {
@@ -300,7 +327,7 @@ struct Walk {
                 if (fl & 0x10u) { have_size = true; def_size = be32(p, f); f += 4u; }
                 return kOk;
             }
-            if (!tfdt && !trun) return kOk;
+            if (!tfdt && !trun) { prot.traf_box(*this, type, at, q, m); return kOk; }
             if (!have_tfhd) return fail(kInvalid, at);
             if (!mine) return kOk;
             if (tfdt) {
@@ -339,7 +366,8 @@ struct Walk {
             return kOk;
         });
         if (st != kOk) return st;
-        return have_tfhd ? (uint32_t)kOk : fail(kInvalid, box);
+        if (!have_tfhd) return fail(kInvalid, box);
+        return mine ? prot.traf_end(*this, box, run0, (uint32_t)(samples - samples0)) : (uint32_t)kOk;
     }
 
     // head_only: the walk ends behind moov, as if the stream did
@@ -361,6 +389,8 @@ struct Walk {
                 const uint32_t st = moov(pos, pos + b.header, b.size - b.header, &have_mvex);
                 if (st != kOk) return st;
                 if (head_only) break;
+                const uint32_t key = prot.after_moov(*this);
+                if (key != kOk) return key;
             } else if (b.type == fourcc('m', 'o', 'o', 'f')) {
                 if (!moov_seen) return fail(kInvalid, pos);
                 if (!fits) break;
@@ -379,23 +409,25 @@ struct Walk {
         return kOk;
     }
 };
+using Walk = WalkT<Clear>;
 
 // One stream: the result record (whole: every field is written), the stream's record and the records of its runs
-// [0, min(runs, run_capacity)).  `base`: the stream's first byte.
-MP4B_HD void walk(const Stream& s, const uint8_t* base, bool head_only, Result* out, Rec* rec, RunRec* runs)
+// [0, min(runs, run_capacity)).  `base`: the stream's first byte.  `w`: a fresh walk (all zero but what its policy was given).
+template <class P>
+MP4B_HD void walk_into(WalkT<P>& w, const Stream& s, const uint8_t* base, bool head_only, Result* out, Rec* rec, RunRec* runs)
 {
     Result r = {};
     Rec c = {};
-    Walk w = {};
     w.p = base; w.n = s.src_bytes; w.mask = s.codecs; w.runs = runs; w.run_capacity = s.run_capacity;
     const uint32_t status = w.run(head_only, &r);
-    if (status != kOk) {
+    if (status != kOk && status != kNoKey) {
         Result none = {};
         r = none;
         r.status = status; r.error_offset = w.err_at;
         if (status == kNotCodec) r.codec = w.first_codec;
         if (status == kNotFragmented) r.codec = w.codec;
-    } else {
+    } else {                  // (kNoKey: the walk ended behind moov -- what moov gave is kept, every count of a moof is 0)
+        if (status == kNoKey) { r.status = status; r.error_offset = w.err_at; }
         r.codec = w.codec; r.track_id = w.track_id; r.timescale = w.timescale;
         if (w.codec == fourcc('a', 'l', 'a', 'c')) r.config = w.cfg; else r.flac = w.flac;
         r.duration = w.duration == 0u && w.have_mehd ? w.mehd_duration : w.duration;
@@ -408,6 +440,11 @@ MP4B_HD void walk(const Stream& s, const uint8_t* base, bool head_only, Result* 
     r.first_bad_sample = kNone;
     *out = r;
     *rec = c;
+}
+MP4B_HD void walk(const Stream& s, const uint8_t* base, bool head_only, Result* out, Rec* rec, RunRec* runs)
+{
+    Walk w = {};
+    walk_into(w, s, base, head_only, out, rec, runs);
 }
 
 // The carries of one stream, serial over its runs (their totals are there): the public rows, the result's frames, the record's rows.

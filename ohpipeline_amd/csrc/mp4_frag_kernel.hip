@@ -241,9 +241,8 @@ uint32_t mp4f_wave_blocks(uint64_t slots, uint32_t cus)
     return (uint32_t)(want < cap ? want : cap);
 }
 
-int mp4f_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Stream* streams)
+int mp4f_plan(ohgpu_ctx* ctx, Mp4fState& g, const Stream* streams, const char* who)
 {
-    Mp4fState& g = *b->mp4f;
     OHGPU_TRY(state_events(g, 7));
     if (!g.n_streams) return OHGPU_OK;
     std::vector<Mp4fTile> tiles;
@@ -254,7 +253,7 @@ int mp4f_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Stream* streams)
             for (uint64_t s0 = 0; s0 < s.packet_capacity; s0 += kTile) tiles.push_back(Mp4fTile{(uint32_t)i, (uint32_t)s0});
         for (uint32_t k = 0; k < s.run_capacity; k++) slot_stream[s.run_first + k] = (uint32_t)i;
     }
-    if (tiles.size() > 0x7fffffffull) return set_error(OHGPU_ERR_INVALID, "ohgpu_mp4f_batch_create: %zu rows are more than one batch takes", g.n_packets);
+    if (tiles.size() > 0x7fffffffull) return set_error(OHGPU_ERR_INVALID, "%s: %zu rows are more than one batch takes", who, g.n_packets);
     g.n_tiles = (uint32_t)tiles.size();
     g.wave_blocks = mp4f_wave_blocks(g.n_runs, ctx->num_cus > 0 ? (uint32_t)ctx->num_cus : 256u);
     OHGPU_TRY(dev_array(ctx, g, &g.d_streams, g.n_streams, streams));
@@ -270,6 +269,37 @@ int mp4f_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Stream* streams)
     if (g.n_packets) OHGPU_HIP_TRY_ALLOC(hipMemset(g.d_packets, 0xa5, g.n_packets * sizeof(Row)));
     if (g.n_packets) OHGPU_HIP_TRY_ALLOC(hipMemset(g.d_samples, 0xa5, g.n_packets * sizeof(Sample)));
     OHGPU_HIP_TRY_ALLOC(hipStreamSynchronize(nullptr));                // (the fills are queued: a run on another stream must not meet them)
+    return OHGPU_OK;
+}
+
+// What stands between a walk and the gather, with the events of the phases: the family of csrc/cenc_kernel.hip runs it behind a walk of
+// its own.
+int mp4f_tables(const Mp4fState& g, const uint8_t* src, hipStream_t s)
+{
+    const uint32_t ns = (uint32_t)g.n_streams, lane_blocks = (ns + 63u) / 64u, n_slots = (uint32_t)g.n_runs;
+    const Stream* const streams = (const Stream*)g.d_streams;
+    Result* const results = (Result*)g.d_results;
+    Rec* const recs = (Rec*)g.d_recs;
+    RunRec* const runrecs = (RunRec*)g.d_runrecs;
+    const uint32_t* const slot_stream = (const uint32_t*)g.d_slot_stream;
+    OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[1], s));
+    if (g.wave_blocks) {
+        hipLaunchKernelGGL(mp4f_sums_kernel, dim3(g.wave_blocks), dim3(kMp4fThreads), 0, s, streams, (const Rec*)recs, slot_stream, n_slots, src, runrecs);
+        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
+    }
+    OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[2], s));
+    hipLaunchKernelGGL(mp4f_carries_kernel, dim3(lane_blocks), dim3(64), 0, s, streams, ns, recs, runrecs, (Run*)g.d_runs, results);
+    OHGPU_HIP_TRY_ALLOC(hipGetLastError());
+    OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[3], s));
+    if (g.n_tiles) {
+        hipLaunchKernelGGL(mp4f_expand_kernel, dim3(g.n_tiles), dim3(kMp4fThreads), 0, s, streams, (const Rec*)recs, (const RunRec*)runrecs, (const Mp4fTile*)g.d_tiles, src,
+                           (Row*)g.d_packets, (Sample*)g.d_samples, results);
+        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
+    }
+    OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[4], s));
+    hipLaunchKernelGGL(mp4f_finish_kernel, dim3(lane_blocks), dim3(64), 0, s, streams, ns, recs, (const RunRec*)runrecs, (const Row*)g.d_packets, results);
+    OHGPU_HIP_TRY_ALLOC(hipGetLastError());
+    OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[5], s));
     return OHGPU_OK;
 }
 
@@ -292,24 +322,7 @@ int mp4f_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
     }
     hipLaunchKernelGGL(mp4f_walk_kernel, dim3(lane_blocks), dim3(64), 0, s, streams, ns, src, results, recs, runrecs);
     OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-    OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[1], s));
-    if (g.wave_blocks) {
-        hipLaunchKernelGGL(mp4f_sums_kernel, dim3(g.wave_blocks), dim3(kMp4fThreads), 0, s, streams, (const Rec*)recs, slot_stream, n_slots, src, runrecs);
-        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-    }
-    OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[2], s));
-    hipLaunchKernelGGL(mp4f_carries_kernel, dim3(lane_blocks), dim3(64), 0, s, streams, ns, recs, runrecs, (Run*)g.d_runs, results);
-    OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-    OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[3], s));
-    if (g.n_tiles) {
-        hipLaunchKernelGGL(mp4f_expand_kernel, dim3(g.n_tiles), dim3(kMp4fThreads), 0, s, streams, (const Rec*)recs, (const RunRec*)runrecs, (const Mp4fTile*)g.d_tiles, src,
-                           (Row*)g.d_packets, (Sample*)g.d_samples, results);
-        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-    }
-    OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[4], s));
-    hipLaunchKernelGGL(mp4f_finish_kernel, dim3(lane_blocks), dim3(64), 0, s, streams, ns, recs, (const RunRec*)runrecs, (const Row*)g.d_packets, results);
-    OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-    OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[5], s));
+    OHGPU_TRY(mp4f_tables(g, src, s));
     if (g.gathers && g.wave_blocks) {
         hipLaunchKernelGGL(mp4f_gather_kernel, dim3(g.wave_blocks), dim3(kMp4fThreads), 0, s, streams, (const Rec*)recs, (const RunRec*)runrecs, slot_stream, n_slots,
                            (const Row*)g.d_packets, (const Result*)results, src, dst);

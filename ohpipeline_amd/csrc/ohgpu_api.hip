@@ -314,8 +314,9 @@ static const struct { const char* noun; void (*release)(ohgpu_ctx*, ohgpu_batch*
     {"a PCM file", free_state<&ohgpu_batch::file>, false},   // kBatchIff
     {"a DSD file", free_state<&ohgpu_batch::file>, false},   // kBatchDsdFile
     {"a fragmented MPEG-4", free_state<&ohgpu_batch::mp4f>, false},   // kBatchMp4f
+    {"a protected MPEG-4", cenc_free, false},   // kBatchCenc
 };
-static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchMp4f + 1, "a row per BatchKind");
+static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchCenc + 1, "a row per BatchKind");
 
 int run_guard(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, BatchKind kind, bool empty, bool null_src_ok,
               const void* src_base, const void* dst_base, bool needs_dst)

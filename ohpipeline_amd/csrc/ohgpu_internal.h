@@ -26,6 +26,7 @@
 #include "dsd_file_core.h"
 #include "ohm_rx_core.h"
 #include "raop_aes_core.h"
+#include "cenc_core.h"
 
 namespace ohgpu {
 
@@ -515,6 +516,31 @@ static_assert(sizeof(ohgpu_mp4f_stream_desc) == sizeof(mp4frag::Stream) && sizeo
               offsetof(ohgpu_flac_streaminfo_t, md5) == offsetof(mp4frag::FlacInfo, md5) && mp4frag::kMaxBoxes == OHGPU_MP4F_MAX_BOXES && mp4frag::kMaxSamples == OHGPU_MP4F_MAX_SAMPLES && mp4frag::kMaxRunSamples == OHGPU_MP4F_MAX_RUN_SAMPLES &&
               mp4frag::kNotFragmented == OHGPU_MP4F_NOT_FRAGMENTED && mp4frag::kGather == OHGPU_MP4F_GATHER, "fragmented MPEG-4 layouts");
 
+// ---- protected fragmented MPEG-4 (csrc/cenc_kernel.hip): an Mp4fState whose packet table is the expansion's own (places
+// in the source arena), and what stands behind it -- the descriptors without their keys, the expanded keys, what the protection boxes gave,
+// the public packet table (places in the destination arena), and the block prefixes of the decrypt-gather.
+struct CencState : Mp4fState {
+    std::vector<uint32_t> keys;                       // cenc::kScheduleWords words per stream (cleared in cenc_free)
+    std::vector<uint32_t> tile_first;                 // per stream: its first tile; n_streams + 1 entries
+    uint32_t crypt_blocks = 0;                        // the size of the persistent decrypt-gather launch
+    uint64_t n_chunks = 0;                            // its slots: chunks of cenc::kLaneBlocks keystream blocks, from the capacities
+    void* d_cstreams = nullptr;                       // cenc::Stream[n_streams], the keys zero
+    void* d_keys = nullptr; size_t keys_bytes = 0;    // uint32[n_streams * kScheduleWords]
+    void* d_extras = nullptr;                         // cenc::Extra[n_streams]
+    void* d_rows = nullptr;                           // mp4box::Row[n_packets]: the public packet table
+    void* d_rowrecs = nullptr;                        // cenc::RowRec[n_packets]
+    void* d_tile_first = nullptr;                     // uint32[n_streams + 1]
+    void* d_tile_blocks = nullptr;                    // uint64[n_tiles]: a tile's keystream blocks, then (the tile scan) those in front of it
+    void* d_chunk_first = nullptr;                    // uint64[n_streams + 1]: the stream's first chunk slot
+    void* d_nblocks = nullptr;                        // uint64[n_streams]: the stream's keystream blocks
+};
+static_assert(sizeof(ohgpu_cenc_stream_desc) == 112 && sizeof(ohgpu_cenc_stream_result) == 208 && sizeof(ohgpu_cenc_stream_desc) == sizeof(cenc::Stream) &&
+              sizeof(ohgpu_cenc_stream_result) == sizeof(cenc::Result) && offsetof(ohgpu_cenc_stream_desc, key_flags) == offsetof(cenc::Stream, key_flags) &&
+              offsetof(ohgpu_cenc_stream_desc, kid) == offsetof(cenc::Stream, kid) && offsetof(ohgpu_cenc_stream_desc, key) == offsetof(cenc::Stream, key) &&
+              offsetof(ohgpu_cenc_stream_result, entry) == offsetof(cenc::Result, x) && offsetof(ohgpu_cenc_stream_result, kid) == offsetof(cenc::Result, x) + offsetof(cenc::Extra, kid) &&
+              offsetof(ohgpu_cenc_stream_result, blocks) == offsetof(cenc::Result, x) + offsetof(cenc::Extra, blocks) && mp4frag::kNoKey == OHGPU_CENC_NO_KEY &&
+              cenc::kHaveKey == OHGPU_CENC_HAVE_KEY && mp4box::kMaxBoxes == OHGPU_MP4_MAX_BOXES, "protected MPEG-4 layouts");
+
 // ---- the two file layers: PCM files (csrc/iff_pcm_kernel.hip) and DSD files (csrc/dsd_file_kernel.hip, DESIGN.md
 // 5.18).  One state for both (api_file.h has the plan, the run and the C ABI's bodies over it): the descriptors, the list of the
 // conversion's workgroups, the walk's record of each stream's run and the results of the last run, each in the family's own layout
@@ -543,7 +569,7 @@ static_assert(sizeof(ohgpu_dsd_file_stream_desc) == sizeof(dsdfile::Stream) && s
               dsdfile::kDsf == OHGPU_DSD_DSF && dsdfile::kDff == OHGPU_DSD_DFF && dsdfile::kDsf == OHGPU_DSD_FILE_KIND_DSF && dsdfile::kDff == OHGPU_DSD_FILE_KIND_DFF &&
               dsdfile::kFillByte == OHGPU_DSD_SILENCE_BYTE && dsdfile::kMaxChunks == OHGPU_DSD_FILE_MAX_CHUNKS, "DSD file layouts");
 
-enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11, kBatchOhmRx = 12, kBatchOgg = 13, kBatchMp4 = 14, kBatchIff = 15, kBatchDsdFile = 16, kBatchMp4f = 17 };
+enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11, kBatchOhmRx = 12, kBatchOgg = 13, kBatchMp4 = 14, kBatchIff = 15, kBatchDsdFile = 16, kBatchMp4f = 17, kBatchCenc = 18 };
 
 }  // namespace ohgpu
 
@@ -655,6 +681,7 @@ struct ohgpu_batch {
     ohgpu::Mp4State* mp4 = nullptr;     // kBatchMp4 only
     ohgpu::FileState* file = nullptr;   // kBatchIff and kBatchDsdFile
     ohgpu::Mp4fState* mp4f = nullptr;   // kBatchMp4f only
+    ohgpu::CencState* cenc = nullptr;   // kBatchCenc only
     void*    d_pull_tiles = nullptr;   // kBatchSrcPull: PullTile[n_pull_tiles] on the device (d_descs holds the messages)
     uint32_t n_pull_tiles = 0;
     // kBatchSrc whose messages differ in layout: one uniform batch per layout (each with its own block-kernel plan), run one
@@ -754,9 +781,15 @@ int  mp4_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const mp4box::Stream* streams);   
 int  mp4_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, hipStream_t s);
 // csrc/mp4_frag_kernel.hip.  The run sums and the gather are persistent (a wave a run slot, mp4f_wave_blocks workgroups); the rest is a
 // lane a stream (walk, carries, finish) or a workgroup a tile (expand).
-int  mp4f_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const mp4frag::Stream* streams);   // the slot map, the tiles and the tables onto the device (b->mp4f holds the counts)
+int  mp4f_plan(ohgpu_ctx* ctx, Mp4fState& g, const mp4frag::Stream* streams, const char* who);   // the slot map, the tiles and the tables onto the device (g holds the counts)
 int  mp4f_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
+int  mp4f_tables(const Mp4fState& g, const uint8_t* src, hipStream_t s);   // behind a walk: ev[1], run sums, ev[2], carries, ev[3], expand, ev[4], finish, ev[5]
 uint32_t mp4f_wave_blocks(uint64_t slots, uint32_t cus);   // the persistent launches' size: the rule tests/test_gpu_mp4f_textbook.py restates
+// csrc/cenc_kernel.hip.  The walk under cenc::Protection, mp4f_tables, then the decrypt-gather: a workgroup a tile (the rows and their
+// block prefixes), a lane a stream (the tiles' prefixes), and the persistent launch (a wave per chunk of 64 keystream blocks of a stream).
+int  cenc_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const cenc::Stream* streams);
+int  cenc_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
+void cenc_free(ohgpu_ctx* ctx, ohgpu_batch* b);                       // clears the schedules, on the device and here, then state_free
 // csrc/iff_pcm_kernel.hip.  No launch is persistent: a lane a stream (walk), a workgroup per kIffGroupPieces pieces of a run (convert).
 int  iff_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const iffchunk::Stream* streams);   // the descriptors and the workgroup list onto the device
 int  iff_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);

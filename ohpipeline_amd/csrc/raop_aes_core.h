@@ -2,6 +2,7 @@
 // only, under RAOP's packet rule.  Written from FIPS-197; the tables are computed here, at compile time, from the
 // field's arithmetic.  Everything is __host__ __device__: csrc/raop_decrypt_kernel.hip runs this text on the device,
 // tests/cpp/raop_core_driver.cpp runs the same text on the CPU under the sanitizers.
+// (csrc/cenc_core.h builds its forward table from this file's S-box and field arithmetic and takes expand_encrypt_key as it is.)
 //
 // Reading of the standard:
 //   field      GF(2^8) modulo x^8 + x^4 + x^3 + x + 1; the S-box is the field inverse (0 -> 0) through the affine map
@@ -110,11 +111,10 @@ RAOP_HD void decrypt_block(const uint32_t rk[44], const uint32_t c[4], uint32_t 
     p[3] = inv_last_column(s3, s2, s1, s0, isbox) ^ rk[43];
 }
 
-// The 11 round keys of the equivalent inverse cipher from the 16 key bytes as sent: FIPS-197 5.2's expansion (words little-endian,
-// so RotWord is a rotation right by 8 and Rcon lands in the low byte), the keys taken in reverse, InvMixColumns on keys 1..9.
-inline void expand_decrypt_key(const uint8_t key[16], uint32_t rk[44], const Tables& t)
+// FIPS-197 5.2's expansion of the 16 key bytes as sent: the 11 round keys of the cipher itself (words little-endian, so RotWord is a
+// rotation right by 8 and Rcon lands in the low byte).  csrc/cenc_core.h's counter mode takes this schedule as it is.
+inline void expand_encrypt_key(const uint8_t key[16], uint32_t w[44], const Tables& t)
 {
-    uint32_t w[44];
     for (int i = 0; i < 4; i++) w[i] = (uint32_t)key[4 * i] | ((uint32_t)key[4 * i + 1] << 8) | ((uint32_t)key[4 * i + 2] << 16) | ((uint32_t)key[4 * i + 3] << 24);
     uint8_t rcon = 1;
     for (int i = 4; i < 44; i++) {
@@ -127,6 +127,13 @@ inline void expand_decrypt_key(const uint8_t key[16], uint32_t rk[44], const Tab
         }
         w[i] = w[i - 4] ^ v;
     }
+}
+
+// The 11 round keys of the equivalent inverse cipher: the expansion above, the keys taken in reverse, InvMixColumns on keys 1..9.
+inline void expand_decrypt_key(const uint8_t key[16], uint32_t rk[44], const Tables& t)
+{
+    uint32_t w[44];
+    expand_encrypt_key(key, w, t);
     for (int r = 0; r <= 10; r++)
         for (int c = 0; c < 4; c++) {
             const uint32_t v = w[4 * (10 - r) + c];

@@ -59,4 +59,15 @@ protected:
 };
 typedef Brx Brn;
 
+// A buffer its receiver fills (ohNet's Bwx): room for MaxBytes(), Bytes() of them written.
+class Bwx : public Brx {
+public:
+    Bwx(TByte* aPtr, TUint aMaxBytes) : Brx(aPtr, 0), iRoom(aPtr), iMaxBytes(aMaxBytes) {}
+    TUint MaxBytes() const { return iMaxBytes; }
+    void Replace(const Brx& aBuf) { ASSERT(aBuf.Bytes() <= iMaxBytes); for (TUint k = 0; k < aBuf.Bytes(); k++) iRoom[k] = aBuf.Ptr()[k]; iBytes = aBuf.Bytes(); }
+private:
+    TByte* iRoom;
+    TUint iMaxBytes;
+};
+
 }  // namespace OpenHome

@@ -1,0 +1,138 @@
+"""The protected MPEG-4 layer on the device (ohgpu_cenc_*, csrc/cenc_kernel.hip) against the independent model (tests/cenc_textbook.py),
+byte for byte and on both routes (the phases, and the plain one a batch created under kernel variant 1 takes, each first asserted through
+ohgpu_cenc_batch_paths): every result, the three whole tables -- pre-filled with 0xA5 by the batch, with guard rows round the streams'
+ranges -- and the whole destination arena, 0xA5 before the run and with guard bytes round every stream's room.  Samples of 0, 1, 15, 16,
+17 and 33 bytes; samples of 63, 64, 65, 128 and 129 keystream blocks; four source and four destination alignments; IVs of 8 and 16
+bytes; the low half's wrap inside a three-block sample; senc in front of and behind the truns, two truns under one senc; a
+gather_first_row in the middle of a traf; a prefix of a stream; capacities below the counts; five keys interleaved with a clear stream
+and a NO_KEY stream between good ones; a 64-stream batch run twice and a second batch that allocates nothing; the host-buffer call."""
+import numpy as np
+import pytest
+
+import cenc_cases as CC
+import cenc_textbook as CX
+from device_shape import compute_units
+from ohpipeline_amd import capi
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = capi.Context(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module", params=[0, 1], ids=["phases", "plain"])
+def vctx(ctx, request):
+    ctx.set_kernel_variant(request.param)
+    ctx.cenc_route = capi.MP4F_ROUTE_PLAIN if request.param else capi.MP4F_ROUTE_PHASES
+    yield ctx
+    ctx.set_kernel_variant(0)
+
+
+@pytest.fixture(scope="module")
+def good():
+    return CC.named_good()
+
+
+def run(ctx, job, runs=2):
+    capi.cenc_batch_check(job.descs, job.n_packets, job.n_runs, job.src.size, job.dst_bytes)
+    d_src, d_dst = ctx.upload(job.src), ctx.malloc(max(job.dst_bytes, 4))
+    b = ctx.cenc_batch(job.descs, job.n_packets, job.n_runs, job.src.size, job.dst_bytes)
+    try:
+        paths = ctx.cenc_paths(b)
+        assert paths["route"] == ctx.cenc_route
+        # the persistent decrypt-gather launch, restated: a wave per chunk slot of 64 keystream blocks, a stream has room for
+        # dst_capacity / 16 + packet_capacity blocks, four waves a workgroup, at most 8 workgroups a CU
+        chunks = sum((int(d["dst_capacity"]) // 16 + int(d["packet_capacity"]) + 63) // 64 for d in job.descs if d["dst_capacity"] and d["packet_capacity"])
+        assert paths["wave_blocks"] == (0 if ctx.cenc_route == capi.MP4F_ROUTE_PLAIN else min((chunks + 3) // 4, 8 * compute_units()))
+        allocs = []
+        for _ in range(runs):
+            ctx.memset(d_dst, CC.FILL, max(job.dst_bytes, 4))
+            ctx.cenc_run(b, d_src, d_dst)
+            results, run_rows, packets, samples = ctx.cenc_results(b, len(job.streams), job.n_packets, job.n_runs)
+            dst = ctx.download(d_dst, max(job.dst_bytes, 4))[:job.dst_bytes]
+            CC.assert_same(results, run_rows, packets, samples, dst, job)
+            allocs.append(ctx.device_allocations())
+        assert len(set(allocs)) == 1                                   # a second run allocates nothing on the device
+        ms = ctx.cenc_phase_ms(b)
+        assert all(v >= 0 for v in ms) and (ctx.cenc_route == capi.MP4F_ROUTE_PHASES or ms[1:] == (0.0,) * 5)
+    finally:
+        ctx.batch_destroy(b)
+        ctx.free(d_src)
+        ctx.free(d_dst)
+    return results
+
+
+def test_every_named_file(vctx, good):
+    bad = CC.named_malformed()
+    streams = [CC.stream(m, gather_first_row=k % 3) for k, m in enumerate(good.values())]
+    streams += [CC.stream(data, codecs=codecs, have_key=have_key, kid=kid) for data, _, _, codecs, have_key, kid in bad.values()]
+    job = CC.Job(streams)
+    results = run(vctx, job)
+    assert [(int(r["mp4f"]["status"]), int(r["mp4f"]["error_offset"])) for r in results[len(good):]] == [(status, at) for _, status, at, _, _, _ in bad.values()]
+    assert {int(r["iv_size"]) for r in results} == {0, 8, 16} and sum(1 for r in results if int(r["blocks"])) >= 12
+
+
+def test_sample_sizes_and_piece_edges_at_four_by_four_alignments(vctx, good):
+    files = [good["sizes_0_1_15_16_17_33"], good["piece_edges"]]
+    job = CC.Job([CC.stream(files[i % 2]) for i in range(32)], align=lambda i: (0, 1, 7, 14)[i // 2 % 4], dst_align=lambda i: (0, 3, 8, 15)[i // 8])
+    assert {(int(d["src_offset"]) % 16, int(d["dst_offset"]) % 16) for d in job.descs} == {(a, b) for a in (0, 1, 7, 14) for b in (0, 3, 8, 15)}
+    assert all(m["samples_available"] == len(f.sizes) for m, f in zip(job.models, files * 16))
+    run(vctx, job, runs=1)
+
+
+def test_the_wrap_both_iv_sizes_and_senc_on_either_side(vctx, good):
+    wrap, two = good["wrap_inside_three_blocks"], good["two_truns_under_one_senc_behind"]
+    streams = [CC.stream(wrap), CC.stream(good["flac_iv8"]), CC.stream(good["alac_iv16"]), CC.stream(good["senc_in_front_of_the_truns"]), CC.stream(good["senc_behind_the_truns"]),
+               CC.stream(good["two_truns_under_one_senc_front"])]
+    streams += [CC.stream(two, gather_first_row=row) for row in (3, 5, 40, 71, 100, 141, 142)]        # (a traf holds rows 0..70: 5 and 66 samples)
+    streams += [CC.stream(two, capacity=40, run_capacity=2), CC.stream(two, capacity=100, run_capacity=3, gather_first_row=72), CC.stream(two, dst_capacity=sum(two.sizes) - 1),
+                CC.stream(two, dst_capacity=0), CC.stream(two, capacity=0, run_capacity=0)]
+    streams += [CC.stream(two.data[:cut], capacity=two.n, run_capacity=len(two.runs), key=two.key, kid=two.kid) for cut in (two.segment_ends[0] + 30, two.segment_ends[0] - 9)]
+    job = CC.Job(streams)
+    assert job.models[0]["gathered"][:48] == wrap.clear[0] and job.models[0]["blocks"] == 3 + 1 + 3
+    assert job.models[-1]["samples_refused"] and job.models[-1]["bytes_gathered"] and job.models[8]["clear_rows"][40] == (0, two.sizes[40])
+    run(vctx, job)
+
+
+def test_five_keys_a_clear_stream_and_a_stream_without_its_key(vctx, good):
+    files = [CC.simple([7, 5], seed=20 + k, key=CC.key_of(k), kid=CC.kid_of(k), iv_size=(8, 16)[k % 2]) for k in range(5)]
+    streams = []
+    for k, m in enumerate(files):
+        streams += [CC.stream(m), CC.stream(good["clear_plain_flac"]) if k % 2 else CC.stream(files[(k + 1) % 5], have_key=False)]
+    streams.append(CC.stream(files[0], key=CC.key_of(3)))                                             # a wrong key under the right kid: other bytes, no refusal
+    job = CC.Job(streams)
+    assert [m["status"] for m in job.models] == [CX.OK, CX.NO_KEY, CX.OK, CX.OK, CX.OK, CX.NO_KEY, CX.OK, CX.OK, CX.OK, CX.NO_KEY, CX.OK]
+    assert job.models[-1]["gathered"] != job.models[0]["gathered"] and job.models[-1]["bytes_gathered"] == job.models[0]["bytes_gathered"]
+    results = run(vctx, job)
+    no_key = results[1]
+    assert bytes(no_key["kid"]) == CC.kid_of(1) and int(no_key["iv_size"]) == 16 and int(no_key["mp4f"]["codec"]) == CX.code(b"fLaC") and int(no_key["mp4f"]["samples"]) == 0
+
+
+def test_sixty_four_streams_twice_and_a_second_batch_that_allocates_nothing(vctx, good):
+    names = ["flac_iv8", "alac_iv16", "clear_plain_alac", "senc_behind_the_truns", "sizes_0_1_15_16_17_33", "enca_not_protected", "second_senc_skipped", "saiz_and_saio_skipped"]
+    job = CC.Job([CC.stream(good[names[i % 8]], gather_first_row=i // 8 % 3) for i in range(64)])
+    run(vctx, job, runs=2)
+    before = vctx.device_allocations()
+    again = vctx.cenc_batch(job.descs, job.n_packets, job.n_runs, job.src.size, job.dst_bytes)
+    try:
+        assert vctx.device_allocations() == before
+    finally:
+        vctx.batch_destroy(again)
+
+
+def test_an_empty_stream_an_empty_batch_and_the_host_buffer_call(vctx, good):
+    run(vctx, CC.Job([CC.stream(b""), CC.stream(good["flac_iv16"]), CC.stream(b"", capacity=0, run_capacity=0), CC.stream(good["init_segment_alone"], capacity=4, run_capacity=2)]))
+    b = vctx.cenc_batch(np.zeros(0, dtype=capi.CENC_STREAM_DESC), 0, 0, 0, 0)
+    try:
+        vctx.cenc_run(b, None, None)
+        assert all(t.size == 0 for t in vctx.cenc_results(b, 0, 0, 0))
+    finally:
+        vctx.batch_destroy(b)
+    job = CC.Job([CC.stream(good["alac_iv8"]), CC.stream(CC.named_malformed()["senc_subsamples"][0]), CC.stream(good["two_truns_under_one_senc_front"], capacity=60, gather_first_row=2)])
+    dst = np.full(job.dst_bytes, CC.FILL, dtype=np.uint8)
+    results, run_rows, packets, samples = vctx.cenc_process_host(job.descs, job.n_packets, job.n_runs, job.src, dst)
+    CC.assert_same(results, run_rows, packets, samples, dst, job)
