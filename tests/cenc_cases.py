@@ -2,6 +2,7 @@
 tests/mp4f_cases.py's builders, which are imported and not edited; the muxer's OWN RECORD of every clear sample, IV and key -- the truth
 the model (tests/cenc_textbook.py) and the product are held to --; the named good and malformed files; the fixed-seed damage; and the
 batches: the arenas, the descriptors, and what the model says every output must be."""
+import functools
 import struct
 
 import numpy as np
@@ -385,3 +386,323 @@ def fill_result(r, m):
 
 
 assert_same = FC.assert_same
+
+
+# ---- streams of more than one tile (cenc_rows_kernel's wave prefix, cenc_tiles_kernel's loop, cenc_crypt_kernel's two searches)
+TILE = 1024                 # mp4box::kTile: the samples a workgroup of cenc_rows_kernel takes, four a thread, 256 a wave
+WAVE_ROWS = 256
+RARE_SIZES = (63 * 16, 65 * 16)
+TILE_COUNTS = (255, 256, 257, 1023, 1024, 1025, 2049, 3 * TILE + 5)
+
+
+def tile_sizes(n, seed, hollow=False):
+    """the sizes of n samples: by a fixed-seed generator from EDGE_SIZES; a few of 63 and 65 keystream blocks, of which one each
+    lies behind row 1024 where there is one; nothing at rows 1023 and 1024; hollow: nothing in the whole of tile 1"""
+    rng = Lcg(4100 + seed)
+    sizes = [EDGE_SIZES[rng.next() % len(EDGE_SIZES)] for _ in range(n)]
+    for _ in range(2 + n // 600):
+        sizes[rng.next() % n] = RARE_SIZES[rng.next() % 2]
+    if n > TILE + 2:
+        a, b = (TILE + 1 + rng.next() % (n - TILE - 1) for _ in range(2))
+        sizes[a], sizes[b if b != a else TILE + 1 + (a - TILE) % (n - TILE - 1)] = RARE_SIZES
+    for row in (TILE - 1, TILE):
+        if row < n:
+            sizes[row] = 0
+    if hollow:
+        sizes[TILE:2 * TILE] = [0] * len(sizes[TILE:2 * TILE])
+    return sizes
+
+
+def tiled(n, *, seed, fragments=None, iv_size=8, k=0, codec=FLAC, hollow=False, protection="cenc", senc="behind"):
+    """a file of n samples of tile_sizes(); fragments: [[samples of a run, ...] a fragment], one senc a fragment; protection: "cenc"
+    under key k, "enca_clear" (an enca entry whose tenc says isProtected 0) or "plain" (the sibling's own fLaC / alac entry)"""
+    sizes = tile_sizes(n, seed, hollow)
+    fragments = fragments or [[n]]
+    assert sum(sum(f) for f in fragments) == n
+    made, at = [], 0
+    for q, counts in enumerate(fragments):
+        runs = []
+        for j, count in enumerate(counts):
+            samples = [bytes((7 * b + 3 * i + seed) & 0xff for b in range(sizes[i])) for i in range(at, at + count)]
+            runs.append(FC.run(samples, [1 + (5 * i + q) % 7 for i in range(at, at + count)], gap=5 if j else 0))
+            at += count
+        made.append(FC.fragment(runs, sequence=q + 1))
+    if protection == "plain":
+        m = FC.mux(FC.init_segment(codec), made, codec=codec)
+        m.clear, m.ivs, m.key, m.kid, m.protected = [m.data[o:o + s] for o, s in zip(m.offsets, m.sizes)], [], KEY, KID, False
+    elif protection == "enca_clear":
+        m = mux(protected_init(codec, sinf_options=dict(is_protected=0, iv_size=0, kid=kid_of(k))), made, codec=codec, protect=False, key=key_of(k), kid=kid_of(k), senc=senc)
+    else:
+        m = mux(protected_init(codec, sinf_options=dict(iv_size=iv_size, kid=kid_of(k))), made, codec=codec, iv_size=iv_size, key=key_of(k), kid=kid_of(k), senc=senc)
+    assert m.sizes == sizes
+    return m
+
+
+@functools.lru_cache(maxsize=None)
+def multi_tile_files():
+    """-> {name: Fragmented}, made once: a file a count of TILE_COUNTS (255 to 257 cross a wave's edge inside a tile, the larger ones
+    a tile's), under three keys and both IV sizes; 2049 samples in two truns under one senc, the second from row 1019 on, so that the
+    senc's IVs and the second run cross row 1024; 3077 samples in fragments of about 700, so that tiles 1 and 2 hold the end of one
+    run and the start of the next; 3077 samples of which tile 1 holds no byte; and two clear files of 2049 samples."""
+    out = {}
+    for q, n in enumerate(TILE_COUNTS[:6]):
+        out[f"samples_{n}"] = tiled(n, seed=n, iv_size=(8, 16)[q % 2], k=1 + q % 3, codec=(FLAC, ALAC)[q // 2 % 2])
+    out["samples_2049_two_truns_under_one_senc"] = tiled(2049, seed=31, fragments=[[1019, 1030]], iv_size=16, k=1, senc="front")
+    out["samples_3077_fragments_of_700"] = tiled(3077, seed=32, fragments=[[703], [689], [711], [697], [277]], iv_size=8, k=2)
+    out["samples_3077_tile_1_empty"] = tiled(3077, seed=33, fragments=[[1500], [1577]], iv_size=16, k=3, hollow=True)
+    out["samples_2049_plain_flac"] = tiled(2049, seed=34, fragments=[[700], [700, 649]], protection="plain")
+    out["samples_2049_enca_not_protected"] = tiled(2049, seed=35, fragments=[[1030], [1019]], k=2, protection="enca_clear")
+    return out
+
+
+def tile_blocks_of(model):
+    """the keystream blocks (for a clear stream: the 16-byte pieces) of every tile of the stream's rows, from the model's clear_rows"""
+    rows = model["clear_rows"]
+    return [sum((size + 15) // 16 for _, size in rows[t:t + TILE]) for t in range(0, len(rows), TILE)]
+
+
+def tile_claims(models):
+    """what a multi-tile job is for, counted from the models: the streams in which
+      waves      a tile with s0 >= 1024 has rows with blocks in each of waves 1, 2 and 3 of cenc_rows_kernel (256 rows a wave);
+      three      three or more tiles hold blocks;
+      hole       a tile without blocks lies between two that hold some;
+      late_run   a gathered row of some bytes lies in a run behind the first and in a tile behind the first."""
+    out = dict(waves=0, three=0, hole=0, late_run=0)
+    for m in models:
+        rows, per_tile = m["clear_rows"], tile_blocks_of(m)
+        out["waves"] += any(all(any(size for _, size in rows[t + w * WAVE_ROWS:t + (w + 1) * WAVE_ROWS]) for w in (1, 2, 3)) for t in range(TILE, len(rows), TILE))
+        out["three"] += sum(1 for b in per_tile if b) >= 3
+        filled = [t for t, b in enumerate(per_tile) if b]
+        out["hole"] += bool(filled) and any(not per_tile[t] for t in range(filled[0], filled[-1]))
+        out["late_run"] += any(size and m["samples_rows"][row][2] > 0 for row, (_, size) in enumerate(rows) if row >= TILE)
+    return out
+
+
+def _between_short(big, align=(0, 1, 7, 14), dst_align=(0, 3, 8, 15)):
+    """a job of the big streams with a short named stream in front of, between and behind them; big stream j lies at source
+    alignment align[j % 4] and destination alignment dst_align[(j + j // 4) % 4]"""
+    good = named_good()
+    short = [good[name] for name in ("flac_iv8", "sizes_0_1_15_16_17_33", "clear_plain_alac", "alac_iv16", "enca_not_protected")]
+    rng = Lcg(4200 + len(big))
+    streams = [stream(short[rng.next() % len(short)])]
+    for s in big:
+        streams += [s, stream(short[rng.next() % len(short)])]
+    job = Job(streams, align=lambda i: align[i // 2 % 4] if i % 2 else (5 * i + 1) % 16, dst_align=lambda i: dst_align[(i // 2 + i // 8) % 4] if i % 2 else (7 * i + 3) % 16)
+    job.big = list(range(1, len(streams), 2))
+    return job
+
+
+@functools.lru_cache(maxsize=None)
+def multi_tile_jobs():
+    """-> {name: Job}, made once.  "every_count": every file of multi_tile_files(), whole.  "descriptors": the 2049- and 3077-sample
+    files under gather_first_row 0, 255, 256, 1023, 1024, 1025 and 2048 (from 1024 on tile 0 has rows and no blocks); packet_capacity
+    TILE + 1 with room for exactly those rows' bytes; the same capacity over a prefix of the file that ends inside row 1000, whose
+    later rows are refused; dst_capacity ending in the middle of tile 1 and exactly where tile 1's first byte would go (the gather is
+    all or nothing: such a stream gathers nothing and has no blocks); and dst_capacity 0."""
+    files = multi_tile_files()
+    jobs = {"every_count": _between_short([stream(m) for m in files.values()])}
+    big = []
+    for name in ("samples_2049_two_truns_under_one_senc", "samples_3077_fragments_of_700", "samples_3077_tile_1_empty", "samples_2049_plain_flac"):
+        m = files[name]
+        rows = (0, 255, 256, 1023, 1024, 1025, 2048) if "plain" not in name and "empty" not in name else (1024, 2048)
+        big += [stream(m, gather_first_row=row) for row in rows if row]
+        if "plain" in name or "empty" in name:
+            continue
+        upto = [sum(m.sizes[:row]) for row in range(m.n + 1)]
+        big += [stream(m, capacity=TILE + 1, dst_capacity=upto[TILE + 1]), stream(m, dst_capacity=(upto[TILE] + upto[2 * TILE]) // 2), stream(m, dst_capacity=upto[TILE]),
+                stream(m, dst_capacity=0)]
+        cut = next(row for row in range(1000, m.n) if m.sizes[row])
+        big.append(stream(m.data[:m.offsets[cut] + 1], capacity=TILE + 1, run_capacity=len(m.runs), dst_capacity=upto[TILE], key=m.key, kid=m.kid))
+    jobs["descriptors"] = _between_short(big)
+    return jobs
+
+
+def assert_reaches(name, job):
+    """a job of multi_tile_jobs() reaches what it is for, by its models -- asserted before the job goes anywhere, so that a fixture
+    that shrinks fails here and does not quietly stop testing the paths"""
+    models = [job.models[i] for i in job.big]
+    claims = tile_claims(models)
+    assert all(m["status"] == CX.OK for m in job.models)
+    assert len({int(job.descs[i]["src_offset"]) % 16 for i in job.big}) == 4 == len({int(job.descs[i]["dst_offset"]) % 16 for i in job.big})
+    assert claims["waves"] >= 1 and claims["three"] >= 1 and claims["late_run"] >= 1, claims
+    assert {m["iv_size"] for m in models} == {0, 8, 16} and len({m["kid"] for m in models if m["is_protected"]}) >= 2
+    per_tile = [tile_blocks_of(m) for m in models]
+    if name == "every_count":
+        assert claims["hole"] >= 1 and [m["samples"] for m in models[:len(TILE_COUNTS)]] == list(TILE_COUNTS)
+        assert all(m["samples_available"] == m["samples"] == len(m["clear_rows"]) and m["bytes_gathered"] for m in models)
+        assert sum(1 for m in models if not m["is_protected"] and len(tile_blocks_of(m)) >= 3) >= 2            # the clear streams of several tiles
+        assert all(m["clear_rows"][row][1] == 0 for m in models for row in (TILE - 1, TILE) if row < m["samples"])
+        # a sample of 63 or 65 blocks behind row 1024 in front of further rows of the tile: a prefix that crosses a slot's edge there
+        assert sum(1 for m in models if any(size in RARE_SIZES for _, size in m["clear_rows"][TILE:])) >= 4
+    else:
+        firsts = {int(job.descs[i]["gather_first_row"]) for i in job.big}
+        assert firsts == {0, 255, 256, 1023, 1024, 1025, 2048}
+        assert sum(1 for t in per_tile if len(t) >= 2 and t[0] == 0 and any(t[1:])) >= 6                       # tile 0: rows and no blocks
+        assert sum(1 for t in per_tile if len(t) >= 3 and t[0] == t[1] == 0 and t[2]) >= 2                     # ... and tile 1 as well
+        cut = [m for m in models if len(m["clear_rows"]) == TILE + 1]
+        assert len(cut) == 4 and sum(1 for m in cut if m["samples_refused"] and m["samples_available"] < TILE and m["bytes_gathered"]) == 2
+        assert sum(1 for m in cut if m["samples"] > TILE + 1 and m["samples_available"] == TILE + 1 and m["bytes_gathered"]) == 2
+        nothing = [i for i in job.big if not job.models[i]["bytes_gathered"]]
+        assert len(nothing) == 6 and sorted(int(job.descs[i]["dst_capacity"]) > 0 for i in nothing) == [False] * 2 + [True] * 4
+    return claims
+
+
+# ---- more chunk slots than the persistent decrypt-gather launch has waves (cenc_crypt_kernel's loop over `g`)
+SLOT_BLOCKS = 64            # cenc::kLaneBlocks: the keystream blocks of a chunk slot, a lane each
+CRYPT_WAVES, CRYPT_GROUPS_PER_CU = 4, 8          # kCencWaves, kCencGroupsPerCu: the launch's cap today
+TRIP_SEED = 20264
+TRIPS = 5                   # the builder's target: 5 W + 67 slots (the condition is 3 W + 67; see trip_claims on why more)
+
+
+def trip_waves(cus):
+    """W: the waves a launch holds -- the larger of today's cap (8 workgroups of 4 waves a CU) and what the CUs keep resident"""
+    from device_shape import MAX_WAVES_PER_CU
+    return max(CRYPT_GROUPS_PER_CU * CRYPT_WAVES, MAX_WAVES_PER_CU) * cus
+
+
+def slots_of(dst_capacity, packet_capacity):
+    """the documented rule: a stream has room for dst_capacity / 16 + packet_capacity blocks, and none if either is 0"""
+    return (dst_capacity // 16 + packet_capacity + SLOT_BLOCKS - 1) // SLOT_BLOCKS if dst_capacity and packet_capacity else 0
+
+
+@functools.lru_cache(maxsize=None)
+def trip_pool():
+    """-> (small, medium, big): sixteen files of one to four short samples -- twelve protected, each under a key and kid of its own,
+    both IV sizes and both codecs, and four clear ones --; two of 70 to 100 blocks (two working slots); three of 130 to 200 blocks, of
+    which the last fills four slots; a clear one in each of the two"""
+    rng = Lcg(4300)
+    small = []
+    for k in range(16):
+        n = 1 + rng.next() % 4
+        sizes = [(1, 15, 16, 17, 33, 48, 100)[rng.next() % 7] for _ in range(n)]
+        codec = (FLAC, ALAC)[rng.next() % 2]
+        if k % 4 != 3:
+            small.append(simple([n], sizes=sizes, codec=codec, seed=40 + k, iv_size=(8, 16)[k % 2], key=key_of(20 + k), kid=kid_of(20 + k)))
+        elif k % 8 == 3:
+            small.append(simple([n], sizes=sizes, codec=codec, seed=40 + k, sinf_options=dict(is_protected=0, iv_size=0), protect=False))
+        else:
+            m = FC.simple([n], codec=codec, seed=40 + k)
+            m.clear, m.ivs, m.key, m.kid, m.protected = [m.data[o:o + s] for o, s in zip(m.offsets, m.sizes)], [], KEY, KID, False
+            small.append(m)
+
+    def filled(k, blocks, n, protect=True):
+        sizes = [16 * (blocks // n) - rng.next() % 16 for _ in range(n - 1)]
+        sizes.append(16 * (blocks - sum((s + 15) // 16 for s in sizes)) - 3)
+        m = simple([n], sizes=sizes, seed=60 + k, iv_size=(8, 16)[k % 2], key=key_of(40 + k), kid=kid_of(40 + k),
+                   **({} if protect else dict(sinf_options=dict(is_protected=0, iv_size=0), protect=False)))
+        assert sum((s + 15) // 16 for s in m.sizes) == blocks
+        return m
+
+    return small, [filled(0, 71, 5), filled(1, 97, 4, protect=False)], [filled(2, 131, 6), filled(3, 170, 5, protect=False), filled(4, 199, 7)]
+
+
+@functools.lru_cache(maxsize=None)
+def many_trip_job(cus, seed=TRIP_SEED):
+    """-> (Job, slots, [(stream, working, key) a slot]): a work list of TRIPS x W + 67 chunk slots and more for a device of `cus`
+    CUs, W = trip_waves(cus).  key: the index of the stream's file in the pool's files, which all have keys of their own, or -1 for
+    a clear stream.  Slot k of a stream is working when 64 k < B, B the stream's blocks by the model's clear_rows.  By one seeded
+    generator: mostly one-slot streams over the sixteen small files, under one of three pairs of capacities; one stream in thirty has
+    capacities for 3 to 39 slots (never a count that divides W or that W divides) of which one works, or two with a medium file: the
+    waves that come to its other slots jump; one in sixty is a big file that fills three or four slots in a row.  (One-slot streams
+    are the list's stuff, and 1 divides everything: what keeps the list from lining up with the grid is that the others fall among
+    them at seeded places.)  One rule binds the generator: a wave -- a residue of the slot index mod W -- that has not yet had
+    working slots of protected streams under two keys, and has only as many slots to come as it lacks, gets a one-slot protected
+    stream under a key it has not had.  Chance alone would leave some of W waves short after any affordable number of trips.
+    The model runs once per distinct (file, capacities)."""
+    small, medium, big = trip_pool()
+    files = small + medium + big
+    W = trip_waves(cus)
+    need = TRIPS * W + 67
+    counts = [c for c in range(3, 40) if W % c and c % W]
+    few = len([c for c in counts if c < 10])
+    protected_small = [f for f, m in enumerate(small) if m.protected]
+    rng = np.random.default_rng(seed)
+    streams, models, per_slot, cache, slots = [], [], [], {}, 0
+    had = [set() for _ in range(W)]                                # the keys of the protected working slots a residue has had
+
+    def short(g):
+        """residue g % W lacks as many keys as it has slots to come, slot g included"""
+        return g < need and 0 < 2 - len(had[g % W]) >= (need - g + W - 1) // W
+
+    def one_slot(f):
+        extra_rows, extra_bytes = ((0, 0), (1, 5), (0, 48))[int(rng.integers(3))]
+        return f, files[f].n + extra_rows, max(sum(files[f].sizes), 1) + extra_bytes, 1
+
+    while slots < need:
+        u = rng.random()
+        if short(slots):
+            f, capacity, dst_capacity, want = one_slot([f for f in protected_small if f not in had[slots % W]][int(rng.integers(len(protected_small) - 1))])
+        elif u < 1 / 30:
+            f = len(small) + int(rng.integers(len(medium))) if rng.random() < 0.3 else int(rng.integers(len(small)))
+            want = counts[int(rng.integers(few))] if rng.random() < 0.85 else counts[int(rng.integers(len(counts)))]
+            capacity = files[f].n
+            dst_capacity = 16 * (SLOT_BLOCKS * (want - 1) + 1 - capacity) + 7
+        elif u < 1 / 30 + 1 / 60:
+            f = len(small) + len(medium) + int(rng.integers(len(big)))
+            capacity, dst_capacity = files[f].n, sum(files[f].sizes)
+            want = slots_of(dst_capacity, capacity)
+            if W % want == 0:                                      # (four slots: room for a fifth, which does not work)
+                dst_capacity, want = 16 * (SLOT_BLOCKS * want + 1 - capacity), want + 1
+        else:
+            f, capacity, dst_capacity, want = one_slot(int(rng.integers(len(small))))
+        if any(short(slots + k) for k in range(1, want)):          # (a stream of several slots does not lie over a residue that is short)
+            f, capacity, dst_capacity, want = one_slot(int(rng.integers(len(small))))
+        assert slots_of(dst_capacity, capacity) == want, (f, capacity, dst_capacity, want)
+        m = files[f]
+        if (f, capacity, dst_capacity) not in cache:
+            cache[(f, capacity, dst_capacity)] = CX.demux(m.data, 3, capacity, len(m.runs), 0, dst_capacity, kid=m.kid, key=m.key)
+        model = cache[(f, capacity, dst_capacity)]
+        blocks = sum((size + 15) // 16 for _, size in model["clear_rows"])
+        for k in range(want):
+            per_slot.append((len(streams), SLOT_BLOCKS * k < blocks, f if m.protected else -1))
+            if m.protected and SLOT_BLOCKS * k < blocks:
+                had[(slots + k) % W].add(f)
+        streams.append(stream(m, capacity=capacity, dst_capacity=dst_capacity))
+        models.append(model)
+        slots += want
+    return Job(streams, models=models), slots, per_slot
+
+
+def trip_claims(cus, job, slots, per_slot):
+    """What the work list of many_trip_job holds, for the tests to assert.  A wave of residue r takes slots r, r + W, r + 2 W, ...
+    (W is a whole number of workgroups, so slots 4 m .. 4 m + 3 are one workgroup's four waves in one trip).
+      slots_by_rule     the slot count by the documented rule over the job's descriptors
+      launch_groups     min(ceil(slots / 4), 8 cus): the launch's workgroups by the cap as csrc/cenc_kernel.hip states it
+      chunk_first       the running sums
+      two_working       the residues with two working slots or more
+      two_keys          ... of which two belong to protected streams under different keys
+      clear_between     the residues where a clear working slot lies between two protected working ones.  Three trips cannot give a
+                        quarter of the residues that: with p protected and c clear the best of p p c is 4 / 27, which is why the
+                        list is TRIPS = 5 trips long
+      jumps             the residues that meet a slot that does not work and a working one later on
+      mixed_groups      the workgroup trips (four consecutive slots from a multiple of 4) whose working slots lie in two streams or
+                        more under different keys, and those of them where a clear stream is among them"""
+    W = trip_waves(cus)
+    d = job.descs
+    by_rule = [slots_of(int(x["dst_capacity"]), int(x["packet_capacity"])) for x in d]
+    out = dict(W=W, slots_by_rule=sum(by_rule), launch_groups=min((slots + CRYPT_WAVES - 1) // CRYPT_WAVES, CRYPT_GROUPS_PER_CU * cus),
+               chunk_first=np.concatenate([[0], np.cumsum(by_rule)]), two_working=0, two_keys=0, clear_between=0, jumps=0, mixed_groups=0, mixed_with_clear=0)
+    for r in range(W):
+        mine = per_slot[r::W]
+        working = [key for _, works, key in mine if works]
+        protected = [n for n, key in enumerate(working) if key >= 0]
+        out["two_working"] += len(working) >= 2
+        out["two_keys"] += len({working[n] for n in protected}) >= 2
+        out["clear_between"] += len(protected) >= 2 and any(key < 0 for key in working[protected[0]:protected[-1]])
+        idle = [n for n, (_, works, _) in enumerate(mine) if not works]
+        out["jumps"] += bool(idle) and any(works for _, works, _ in mine[idle[0]:])
+    for g in range(0, len(per_slot), CRYPT_WAVES):
+        working = {(i, key) for i, works, key in per_slot[g:g + CRYPT_WAVES] if works}
+        if len({key for _, key in working}) >= 2:
+            out["mixed_groups"] += 1
+            out["mixed_with_clear"] += any(key < 0 for _, key in working)
+    return out
+
+
+def assert_trips(cus, job, slots, per_slot):
+    """items 1 and 2 of the conditions (tests/test_cenc_cases.py holds all of them at four CU counts) -> trip_claims()"""
+    c = trip_claims(cus, job, slots, per_slot)
+    W = c["W"]
+    assert c["slots_by_rule"] == slots == len(per_slot) >= 3 * W + 67 and 4 * c["launch_groups"] < slots and c["launch_groups"] == CRYPT_GROUPS_PER_CU * cus, c
+    assert c["two_working"] == W and c["two_keys"] == W and 4 * c["clear_between"] >= W, c
+    return c

@@ -3,7 +3,15 @@ AddressSanitizer and UBSan into tests/cpp/cenc_core_driver.cpp, a stand-alone pr
 and taken through the phases in the device's order and through the serial text.  Every stream's bytes lie in a heap block of their own
 size, its room in the destination in one of exactly dst_capacity, its records and rows in blocks of exactly their capacities; the whole
 destination arena and all four tables must be the model's (tests/cenc_textbook.py) on both routes, with no sanitizer report.  The driver
-is built twice: with the host's byte reads, and with the reader the device compiles."""
+is built twice: with the host's byte reads, and with the reader the device compiles.
+
+Every job of more than one tile (tests/cenc_cases.py's multi_tile_jobs) and the one-CU build of the job with more chunk slots than a
+launch has waves (many_trip_job) pass here, in both builds, before tests/test_gpu_cenc_textbook.py takes them to the device.  The
+driver's phases route is a serial restatement -- it has the tiles' prefixes and both searches, and no waves and no stride -- so what
+it shows is that the model, the serial text and the per-tile arithmetic agree on these shapes and that no index leaves a stream's
+blocks.  With `s0 = ta * kTile` replaced by `s0 = 0` in the driver's restatement (a scratch copy, never committed) both multi-tile
+jobs fail here ("stream 13: block 3048 found row 1023, which does not hold it"), while the named files, the seek rows of the
+142-sample file and the one-CU work list, whose streams all fit one tile, still pass."""
 import os
 import subprocess
 
@@ -90,4 +98,21 @@ def test_fixed_seed_damage_and_a_cut_at_every_byte_of_the_protection_boxes(drive
     job = CC.Job(streams)
     statuses = [model["status"] for model in job.models]
     assert statuses.count(CX.OK) >= 100 and sum(1 for s in statuses if s not in (CX.OK, CX.TRUNCATED)) >= 50 and CX.TRUNCATED in statuses
+    check(driver, job, tmp_path)
+
+
+@pytest.mark.parametrize("name", ["every_count", "descriptors"])
+def test_streams_of_more_than_one_tile(driver, tmp_path, name):
+    """255 to 3077 samples; a tile without blocks between two that hold some; runs that end and begin inside tiles 1 and 2; two truns
+    under one senc across row 1024; gather_first_row up to 2048; capacities that cut the rows at TILE + 1 and rooms too small"""
+    job = CC.multi_tile_jobs()[name]
+    CC.assert_reaches(name, job)
+    check(driver, job, tmp_path)
+
+
+def test_more_chunk_slots_than_one_cu_has_waves(driver, tmp_path):
+    """the one-CU build of the job whose work list is longer than the persistent launch (the full-size one is the device's alone: here
+    every stream has heap blocks of its own)"""
+    job, slots, per_slot = CC.many_trip_job(1)
+    CC.assert_trips(1, job, slots, per_slot)
     check(driver, job, tmp_path)

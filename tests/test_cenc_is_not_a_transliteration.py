@@ -15,7 +15,7 @@ pytestmark = pytest.mark.skipif(not os.path.isfile(os.path.join(REF, "OpenHome",
 
 THEIRS = ["OpenHome/Media/Codec/Mpeg4.cpp", "OpenHome/Media/Codec/Mpeg4.h"]
 MINE = ["ohpipeline_amd/csrc/cenc_core.h", "ohpipeline_amd/csrc/cenc_kernel.hip", "ohpipeline_amd/csrc/api_cenc.hip", "tests/cpp/cenc_core_driver.cpp",
-        "tests/cenc_textbook.py", "tests/cenc_cases.py", "tests/far_cenc_cases.py", "tests/test_far_cenc_cases.py", "tests/test_cenc_textbook.py", "tests/test_cenc_core_cpu.py", "tests/test_cenc_abi_host.py",
+        "tests/cenc_textbook.py", "tests/cenc_cases.py", "tests/far_cenc_cases.py", "tests/test_far_cenc_cases.py", "tests/test_cenc_textbook.py", "tests/test_cenc_cases.py", "tests/test_cenc_core_cpu.py", "tests/test_cenc_abi_host.py",
         "tests/test_gpu_cenc_textbook.py", "tests/test_gpu_cenc_to_pcm.py", "tests/test_gpu_cenc_far_offsets.py", "tests/golden/make_cenc_fixtures.py", "tools/bench_cenc.py", "ohpipeline_amd/host/Mpeg4CencDecoder.h", "ohpipeline_amd/host/Mpeg4CencDecoder.cpp",
         "tests/cpp/test_mpeg4_cenc_decoder.cpp", "tests/test_cenc_host_cpp.py"]
 

@@ -5,7 +5,18 @@ ranges -- and the whole destination arena, 0xA5 before the run and with guard by
 17 and 33 bytes; samples of 63, 64, 65, 128 and 129 keystream blocks; four source and four destination alignments; IVs of 8 and 16
 bytes; the low half's wrap inside a three-block sample; senc in front of and behind the truns, two truns under one senc; a
 gather_first_row in the middle of a traf; a prefix of a stream; capacities below the counts; five keys interleaved with a clear stream
-and a NO_KEY stream between good ones; a 64-stream batch run twice and a second batch that allocates nothing; the host-buffer call."""
+and a NO_KEY stream between good ones; a 64-stream batch run twice and a second batch that allocates nothing; the host-buffer call.
+
+Streams of more than one tile (tests/cenc_cases.py's multi_tile_jobs: 255, 256, 257, 1023, 1024, 1025, 2049 and 3077 samples): rows
+with blocks in every wave of a tile behind the first, so that cenc_rows_kernel's prefix across the waves and a tile's s0 count;
+three tiles and more with blocks, and a tile without any between two that hold some, for cenc_tiles_kernel's loop and the tile
+search's tie; runs that end and begin inside tiles 1 and 2 and two truns under one senc across row 1024, for the IV's place; samples
+of 63 and 65 blocks behind row 1024; nothing at rows 1023 and 1024; clear streams of three tiles; gather_first_row at 255, 256, 1023,
+1024, 1025 and 2048; rows cut at TILE + 1; rooms that end inside tile 1, at its first byte, and of no bytes.  And a work list of five
+times as many chunk slots as the capped decrypt-gather launch has waves (many_trip_job, for this device's CU count): every wave goes
+round its loop again and again, into another stream's key schedule, from a protected stream into a clear one and back, and over the
+slots behind a stream's last block.  Each such job asserts from its models that it reaches these places before it runs, and has
+passed tests/test_cenc_core_cpu.py's sanitised driver first (the work list in its one-CU build)."""
 import numpy as np
 import pytest
 
@@ -37,7 +48,7 @@ def good():
     return CC.named_good()
 
 
-def run(ctx, job, runs=2):
+def run(ctx, job, runs=2, slots=None):
     capi.cenc_batch_check(job.descs, job.n_packets, job.n_runs, job.src.size, job.dst_bytes)
     d_src, d_dst = ctx.upload(job.src), ctx.malloc(max(job.dst_bytes, 4))
     b = ctx.cenc_batch(job.descs, job.n_packets, job.n_runs, job.src.size, job.dst_bytes)
@@ -45,9 +56,12 @@ def run(ctx, job, runs=2):
         paths = ctx.cenc_paths(b)
         assert paths["route"] == ctx.cenc_route
         # the persistent decrypt-gather launch, restated: a wave per chunk slot of 64 keystream blocks, a stream has room for
-        # dst_capacity / 16 + packet_capacity blocks, four waves a workgroup, at most 8 workgroups a CU
+        # dst_capacity / 16 + packet_capacity blocks, four waves a workgroup, at most 8 workgroups a CU.  (The other constants, as
+        # tests/cenc_cases.py restates them: TILE = 1024 samples a workgroup of the rows launch, 256 threads of four samples,
+        # SLOT_BLOCKS = 64, CRYPT_WAVES = 4 and CRYPT_GROUPS_PER_CU = 8.)
         chunks = sum((int(d["dst_capacity"]) // 16 + int(d["packet_capacity"]) + 63) // 64 for d in job.descs if d["dst_capacity"] and d["packet_capacity"])
         assert paths["wave_blocks"] == (0 if ctx.cenc_route == capi.MP4F_ROUTE_PLAIN else min((chunks + 3) // 4, 8 * compute_units()))
+        assert slots is None or (chunks == slots and (ctx.cenc_route == capi.MP4F_ROUTE_PLAIN or paths["wave_blocks"] * 4 < slots))    # the launch is capped: its waves go round
         allocs = []
         for _ in range(runs):
             ctx.memset(d_dst, CC.FILL, max(job.dst_bytes, 4))
@@ -136,3 +150,19 @@ def test_an_empty_stream_an_empty_batch_and_the_host_buffer_call(vctx, good):
     dst = np.full(job.dst_bytes, CC.FILL, dtype=np.uint8)
     results, run_rows, packets, samples = vctx.cenc_process_host(job.descs, job.n_packets, job.n_runs, job.src, dst)
     CC.assert_same(results, run_rows, packets, samples, dst, job)
+
+
+@pytest.mark.parametrize("name", ["every_count", "descriptors"])
+def test_streams_of_more_than_one_tile(vctx, name):
+    job = CC.multi_tile_jobs()[name]
+    CC.assert_reaches(name, job)
+    run(vctx, job, runs=1)
+
+
+def test_more_chunk_slots_than_the_launch_has_waves(vctx):
+    """W = max(8 x 4, 32 resident) x CUs waves; 5 W + 67 slots and more, so every wave makes five trips and some a sixth.  The plain
+    route makes no trips: it is here because both routes must write the same bytes and tables for this job too."""
+    cus = compute_units()
+    job, slots, per_slot = CC.many_trip_job(cus)
+    CC.assert_trips(cus, job, slots, per_slot)
+    run(vctx, job, runs=2, slots=slots)

@@ -10,6 +10,9 @@ included, with the reference: zero differing bytes.
 floor(32 / waves per workgroup) workgroups), so that retuning a per-CU constant does not take a test out of the regime.  The
 formula is in each test's docstring; tests/test_many_trips_cases.py holds the same conditions at 256 and 304 CUs on the CPU.
 
+Families whose trip tests live with their own suites: the protected MPEG-4 layer's persistent decrypt-gather launch (cenc_crypt_kernel)
+in tests/test_gpu_cenc_textbook.py::test_more_chunk_slots_than_the_launch_has_waves, its builder's claims in tests/test_cenc_cases.py.
+
 Mutations of the library (the convention of tests/test_gpu_pcm_textbook.py's docstring): each built once, run once against this
 file on an MI355X of 256 CUs right after a run of the unchanged library that passed all of it, never committed.
   * pcm_line_kernel, staged loop: `buf ^= 1` dropped (every later chunk of a wave is converted from the first buffer's stale bytes):
