@@ -401,6 +401,48 @@ def mutations():
     return out
 
 
+def packet_limit(cfg):
+    """the longest packet the library takes for a stream of this configuration (ohgpu_alac_batch_check)"""
+    return cfg["frame_length"] * cfg["channels"] * 5 + 64
+
+
+_device = {}
+
+
+def device_mutations():
+    """-> [(kind, cfg, packet)], kind of "cut", "flip", "splice": the part of mutations() that also runs on the device -- every 16th
+    of the cuts, every bit flip, and the splices that are no longer than packet_limit() of their stream (a longer one the library
+    refuses before anything runs).  The whole of mutations() stays with tests/test_alac_core_cpu.py: its model time is most of a
+    minute."""
+    if "picked" not in _device:
+        cases = mutations()
+        n_cuts = len(cases) - 900 - 300
+        kinds = ["cut"] * n_cuts + ["flip"] * 900 + ["splice"] * 300
+        picked = [(kind, cfg, packets[0]) for k, (kind, (cfg, packets)) in enumerate(zip(kinds, cases))
+                  if (kind != "cut" or k % 16 == 0) and (kind != "splice" or len(packets[0]) <= packet_limit(cfg))]
+        assert all(len(p) <= packet_limit(cfg) for _, cfg, p in picked)
+        _device["picked"] = picked
+    return _device["picked"]
+
+
+def damage_job():
+    """device_mutations() as one Job, a packet a stream, the forms in turn as tests/test_alac_core_cpu.py lays out mutations()"""
+    if "job" not in _device:
+        _device["job"] = Job([(cfg, [packet], FORMS[k % 3]) for k, (_, cfg, packet) in enumerate(device_mutations())])
+    return _device["job"]
+
+
+def damage_job_by_configuration():
+    """the same packets as one stream per configuration, in the same order: damaged and good packets of one stream side by side in
+    a group of rows and in one destination span"""
+    if "grouped" not in _device:
+        streams = {}
+        for _, cfg, packet in device_mutations():
+            streams.setdefault(tuple(sorted(cfg.items())), (cfg, []))[1].append(packet)
+        _device["grouped"] = Job([(cfg, packets, FORMS[k % 3]) for k, (cfg, packets) in enumerate(streams.values())])
+    return _device["grouped"]
+
+
 def capi_tables(job):
     """a Job as ohpipeline_amd.capi's (ALAC_STREAM_DESC array, ALAC_PACKET array)"""
     import numpy as np

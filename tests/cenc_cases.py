@@ -388,6 +388,18 @@ def fill_result(r, m):
 assert_same = FC.assert_same
 
 
+@functools.lru_cache(maxsize=None)
+def damage_job():
+    """-> Job, made once: a cut at every byte of the protection boxes of the small 16-byte-IV file (308 streams) and 300 files of
+    fixed-seed damage, a stream each.  tests/test_cenc_core_cpu.py takes it through the sanitised driver in both builds before
+    tests/test_gpu_cenc_textbook.py takes it to the device."""
+    m = named_good()["two_truns_under_one_senc_front"]
+    small = named_good()["flac_iv16"]
+    streams = [stream(data, capacity=m.n, run_capacity=len(m.runs), dst_capacity=len(m.data), key=m.key, kid=m.kid) for data in protection_cuts(small)]
+    streams += [stream(data, capacity=150, run_capacity=4, dst_capacity=len(data), key=f.key, kid=f.kid) for data, f in damaged(300)]
+    return Job(streams)
+
+
 # ---- streams of more than one tile (cenc_rows_kernel's wave prefix, cenc_tiles_kernel's loop, cenc_crypt_kernel's two searches)
 TILE = 1024                 # mp4box::kTile: the samples a workgroup of cenc_rows_kernel takes, four a thread, 256 a wave
 WAVE_ROWS = 256

@@ -1,7 +1,8 @@
 """What the FLAC decoder's tests share: the fixtures (encoder-made under golden/flac, handmade under golden/flac_decode), a Case =
 one stream descriptor over a byte buffer, the model's answer for a case (tests/flac_textbook.py: results and the whole destination
-arena), the handful of malformed cases that also run on the device -- each of which tests/test_flac_core_cpu.py first takes
-through the sanitised CPU build -- and the layout of cases into the device's two arenas.  TEST INFRASTRUCTURE ONLY."""
+arena), the named malformed cases and the fixed-seed mutations that also run on the device -- each of which
+tests/test_flac_core_cpu.py first takes through the sanitised CPU build -- and the layout of cases into the device's two arenas.
+TEST INFRASTRUCTURE ONLY."""
 import collections
 import functools
 import hashlib
@@ -189,6 +190,25 @@ def mutations(seed=20240611):
             b = audio[:lo] + ins + audio[lo:]
         case("splice:%d" % k, tiny, b, max_samples=rnd.choice((96, 96, 200, 40)), first_sample=rnd.choice((0, 0, 16)))
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def device_mutations():
+    """The damaged streams that also run on the device: all of mutations().  tests/test_flac_core_cpu.py takes every one of them
+    through the sanitised CPU build of the core first."""
+    return tuple(mutations())
+
+
+@functools.lru_cache(maxsize=None)
+def damage_layout():
+    """One Layout of device_mutations(), built once: every damaged stream in one source arena, one descriptor each."""
+    return Layout(list(device_mutations()), seed=13)
+
+
+def first_list(src_bytes):
+    """The entries of the scan's first candidate list: csrc/flac_frame_kernel.hip's flac_run asks for S / 512 + 256, and its
+    allocator hands out half as much again plus 32 (tests/many_trips_cases.flac_first_list restates the same sizing)."""
+    return 1.5 * (src_bytes / 512 + 256) + 32
 
 
 # ---------------------------------------------------------------- on the device

@@ -49,6 +49,25 @@ def session_stream(s, form, key=None):
     return stream(key or s["key"], s["iv"], s["payloads"], form, s["cfg"])
 
 
+def wrong_key_streams(form_of):
+    """-> nine streams that decrypt to bytes no encoder made: every committed session under its key with bit 0x10, then bit 0x01,
+    of the first byte flipped, and the last session's packets encrypted under the first session's key and offered under its own.
+    form_of(k): the output form of stream k of the nine."""
+    out = []
+    for s in sessions():
+        for bit in (0x10, 0x01):
+            wrong = bytes([s["key"][0] ^ bit]) + s["key"][1:]
+            out.append(session_stream(s, form_of(len(out)), wrong))
+    s, other = sessions()[3], sessions()[0]["key"]
+    out.append(stream(s["key"], s["iv"], [R.encrypt_packet(other, s["iv"], p) for p in s["fx"]["packets"]], form_of(len(out)), s["cfg"]))
+    return out
+
+
+def clear_packets(s):
+    """what the cipher layer hands the Apple Lossless phases for a stream: its payloads decrypted under the stream's key"""
+    return [decrypt_cached(s["key"], s["iv"], p) for p in s["payloads"]]
+
+
 _clear = {}
 
 

@@ -2,7 +2,10 @@
 the three phases over the transposed scratch and through the plain route by tests/cpp/alac_core_driver.cpp: over every fixture and
 handmade packet in every output form, over the named malformed packets, and over a fixed-seed set of more than 2 000 damaged packets.
 Every packet must end in the model's (tests/alac_textbook.py) status and sample count, and the whole destination arena must be the
-model's, with no sanitizer report.  This is where malformed input is explored; the device sees only the named handful."""
+model's, with no sanitizer report.  This is where malformed input is explored first.  The device takes the named handful
+(tests/test_gpu_alac_textbook.py) and a fixed selection of the damage (tests/alac_cases.device_mutations: every 16th cut, every bit
+flip, the splices within the library's packet limit; tests/test_gpu_alac_damage.py), whose exact jobs pass here on both routes
+before; the full set of more than 7 000 packets, most of a minute of model time, runs only here."""
 import os
 import struct
 import subprocess
@@ -69,3 +72,21 @@ def test_mutations_end_in_the_models_status(driver, tmp_path, route):
     statuses = check(driver, job, tmp_path, route, within_limits=False)      # (a spliced packet can be longer than its stream allows)
     assert {T.OK, T.CORRUPT} <= statuses                   # the set reaches the outcomes it is there for
     assert sum(1 for st, _ in job.want_packets if st == T.OK) > 50       # ... and some damage still decodes, to other samples
+
+
+def test_the_selection_that_goes_to_the_device_drops_no_cut_no_flip_and_few_splices():
+    picked = AC.device_mutations()
+    kinds = [kind for kind, _, _ in picked]
+    n_cuts = len(AC.mutations()) - 900 - 300
+    assert kinds.count("cut") == (n_cuts + 15) // 16 and kinds.count("flip") == 900 and 270 <= kinds.count("splice") <= 300
+    assert kinds == sorted(kinds)                                     # (cuts, flips, splices: the order of mutations())
+    assert all(len(packet) <= AC.packet_limit(cfg) for _, cfg, packet in picked)
+
+
+@pytest.mark.parametrize("route", ROUTES)
+@pytest.mark.parametrize("job", ["a_packet_a_stream", "a_stream_a_configuration"])
+def test_the_damage_that_goes_to_the_device(driver, tmp_path, route, job):
+    """the exact jobs of tests/test_gpu_alac_damage.py, which pass the library's own validation"""
+    job = AC.damage_job() if job == "a_packet_a_stream" else AC.damage_job_by_configuration()
+    assert len(job.table) == len(AC.device_mutations())
+    assert {T.OK, T.CORRUPT} <= check(driver, job, tmp_path, route, within_limits=True)

@@ -91,11 +91,9 @@ def test_both_iv_sizes_the_wrap_and_a_seek_row(driver, tmp_path):
 
 
 def test_fixed_seed_damage_and_a_cut_at_every_byte_of_the_protection_boxes(driver, tmp_path):
-    m = CC.named_good()["two_truns_under_one_senc_front"]
-    small = CC.named_good()["flac_iv16"]
-    streams = [CC.stream(data, capacity=m.n, run_capacity=len(m.runs), dst_capacity=len(m.data), key=m.key, kid=m.kid) for data in CC.protection_cuts(small)]
-    streams += [CC.stream(data, capacity=150, run_capacity=4, dst_capacity=len(data), key=f.key, kid=f.kid) for data, f in CC.damaged(300)]
-    job = CC.Job(streams)
+    """tests/cenc_cases.damage_job, the job tests/test_gpu_cenc_textbook.py later gives the device"""
+    job = CC.damage_job()
+    assert len(job.streams) == 608
     statuses = [model["status"] for model in job.models]
     assert statuses.count(CX.OK) >= 100 and sum(1 for s in statuses if s not in (CX.OK, CX.TRUNCATED)) >= 50 and CX.TRUNCATED in statuses
     check(driver, job, tmp_path)

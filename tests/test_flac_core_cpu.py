@@ -2,7 +2,9 @@
 scan, probe, chain and restore (both routes) by tests/cpp/flac_core_driver.cpp: over every fixture, over the malformed cases that
 later run on the device (tests/flac_cases.device_cases), and over a fixed-seed set of more than 2 000 mutated streams.  Every case must
 end in a status -- the model's (tests/flac_textbook.py) status, counts and whole destination arena -- with no sanitizer report.
-This is where malformed input is explored; the device sees only the named handful."""
+This is where malformed input is explored first: the device takes the named handful (tests/test_gpu_flac_textbook.py) and then the
+whole mutation set in one batch (tests/flac_cases.device_mutations, tests/test_gpu_flac_damage.py), and nothing that has not
+passed here."""
 import os
 import struct
 import subprocess
@@ -90,3 +92,12 @@ def test_mutations_end_in_the_models_status(driver, tmp_path):
     assert {0, 1, 3} <= statuses                   # the set reaches the outcomes it is there for
     # and is not a set of streams that all die at their first byte: a good share still delivers frames
     assert sum(1 for c in cases if len(FC.model(c)[0].frames) > 0) > len(cases) // 3
+
+
+def test_what_goes_to_the_device_of_them_is_all_of_them_and_outgrows_the_first_list():
+    """the device's set is the set above case for case (this driver takes cases one by one, so that test has covered them), and by
+    the model alone its candidates do not fit the list the device's scan sizes first: the device run scans twice"""
+    cases = FC.device_mutations()
+    assert list(cases) == FC.mutations() and len(cases) == 2142
+    candidates = sum(FC.model(c)[0].candidates for c in cases)
+    assert candidates > FC.first_list(FC.damage_layout().src.size), (candidates, FC.damage_layout().src.size)

@@ -5,9 +5,10 @@ ohgpu_batch_paths_info.
 
 Conventions, as the other textbook tests: arenas allocated to the byte (the last packet ends where the source arena ends), the
 destination pre-filled with a pattern and guard bytes around every plane, the WHOLE destination arena compared with the model's,
-every packet's status and sample count and every stream's result compared too.  Malformed input on the device is the named handful
-of tests/alac_cases.malformed, every one of which tests/test_alac_core_cpu.py has already taken through the sanitised CPU build of
-the same core; nothing here is random."""
+every packet's status and sample count and every stream's result compared too.  Malformed input here is the named handful of
+tests/alac_cases.malformed; a fixed selection of the fixed-seed damage goes to the device in tests/test_gpu_alac_damage.py, and the
+full set runs only on the CPU.  Every packet of either tests/test_alac_core_cpu.py has already taken through the sanitised CPU
+build of the same core; nothing here is random."""
 import numpy as np
 import pytest
 

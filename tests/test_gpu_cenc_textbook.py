@@ -16,7 +16,9 @@ of 63 and 65 blocks behind row 1024; nothing at rows 1023 and 1024; clear stream
 times as many chunk slots as the capped decrypt-gather launch has waves (many_trip_job, for this device's CU count): every wave goes
 round its loop again and again, into another stream's key schedule, from a protected stream into a clear one and back, and over the
 slots behind a stream's last block.  Each such job asserts from its models that it reaches these places before it runs, and has
-passed tests/test_cenc_core_cpu.py's sanitised driver first (the work list in its one-CU build)."""
+passed tests/test_cenc_core_cpu.py's sanitised driver first (the work list in its one-CU build).  So has the damage job
+(tests/cenc_cases.damage_job): a cut at every byte of the protection boxes and 300 files of fixed-seed damage, 608 streams that end
+in every status beside one another."""
 import numpy as np
 import pytest
 
@@ -150,6 +152,17 @@ def test_an_empty_stream_an_empty_batch_and_the_host_buffer_call(vctx, good):
     dst = np.full(job.dst_bytes, CC.FILL, dtype=np.uint8)
     results, run_rows, packets, samples = vctx.cenc_process_host(job.descs, job.n_packets, job.n_runs, job.src, dst)
     CC.assert_same(results, run_rows, packets, samples, dst, job)
+
+
+def test_the_damage_and_the_protection_cuts(vctx):
+    """tests/cenc_cases.damage_job: 308 cuts in the protection boxes and 300 damaged files in one batch, so that the persistent
+    decrypt-gather launch goes over the chunk slots of streams that ended INVALID, TRUNCATED, UNSUPPORTED or NO_KEY part-way through,
+    beside streams that gather.  The job has passed tests/test_cenc_core_cpu.py's sanitised driver, in both builds, first."""
+    job = CC.damage_job()
+    assert len(job.streams) == 608
+    statuses = [model["status"] for model in job.models]
+    assert statuses.count(CX.OK) >= 100 and sum(1 for s in statuses if s not in (CX.OK, CX.TRUNCATED)) >= 50 and CX.TRUNCATED in statuses
+    run(vctx, job, runs=1)
 
 
 @pytest.mark.parametrize("name", ["every_count", "descriptors"])

@@ -5,8 +5,9 @@ variant 1, the plain one (a thread per accepted frame, straight from the bytes).
 Conventions, as the other textbook tests: arenas allocated to the byte, the destination pre-filled with a pattern, the WHOLE
 destination arena compared with the model's, the results (status, frames, samples, first sample, bytes consumed, candidates,
 rejected) compared field by field, and for whole streams the MD5 of the device's samples compared with the stream's own STREAMINFO.
-Malformed input on the device is the handful of tests/flac_cases.device_cases, every one of which tests/test_flac_core_cpu.py has
-already taken through the sanitised CPU build of the same core; nothing here is random."""
+Malformed input here is the named handful of tests/flac_cases.device_cases; the fixed-seed mutations go to the device as one batch
+in tests/test_gpu_flac_damage.py.  Every one of either tests/test_flac_core_cpu.py has already taken through the sanitised CPU
+build of the same core; nothing here is random."""
 import numpy as np
 import pytest
 

@@ -136,6 +136,23 @@ def test_a_wrong_key_between_two_good_streams(vctx):
     check(vctx, job, route=vctx.alac_route)
 
 
+def test_every_wrong_key_stream(vctx):
+    """the nine streams of tests/raop_cases.wrong_key_streams -- which tests/test_raop_core_cpu.py has taken through the sanitised
+    Apple Lossless core as decrypted bytes -- each between two good sessions, in every output form: the wrong streams' packets end
+    as the model chain says, some of them CORRUPT, and the good sessions' share of the arena is exact"""
+    good = RC.sessions()
+    wrong = RC.wrong_key_streams(lambda k: FORMS[k % 3])
+    assert len(wrong) == 9
+    streams = [RC.session_stream(good[0], T.PLANAR)]
+    for k, w in enumerate(wrong):
+        streams += [w, RC.session_stream(good[(k + 1) % 4], FORMS[(k + 1) % 3])]
+    job = RC.Job(streams)
+    theirs = [st for s in job.streams[1::2] for st, _ in job.want_packets[s["first_packet"]:s["first_packet"] + s["n_packets"]]]
+    ours = [st for s in job.streams[0::2] for st, _ in job.want_packets[s["first_packet"]:s["first_packet"] + s["n_packets"]]]
+    assert T.CORRUPT in theirs and all(st == T.OK for st in ours)
+    check(vctx, job, route=vctx.alac_route)
+
+
 def test_plaintext_and_decoding_streams_in_one_batch(vctx):
     rng = AC.Lcg(52)
     s = RC.sessions()

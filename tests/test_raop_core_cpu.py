@@ -94,21 +94,16 @@ def test_the_committed_sessions_mixed_with_plaintext_streams(driver, tmp_path):
 
 def test_wrong_key_bytes_go_through_the_sanitised_apple_lossless_core(tmp_path):
     """what tests/test_gpu_raop_textbook.py later gives the device under a wrong key: the committed sessions decrypted under keys with
-    one bit flipped, through the CPU build of csrc/alac_packet_core.h on both routes, ending as the model says"""
-    import raop_textbook as R
+    one bit flipped, through the CPU build of csrc/alac_packet_core.h on both routes, ending as the model says -- the nine streams of
+    tests/raop_cases.wrong_key_streams, of which the last holds datagrams that were encrypted under another session's key
+    (tests/test_raop_host_cpp.py)"""
     import test_alac_core_cpu as AlacCpu
     exe = tmp_path / "alac_core_driver"
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra",
                            os.path.join(ROOT, "tests", "cpp", "alac_core_driver.cpp"), "-o", str(exe)])
-    streams = []
-    for k, s in enumerate(RC.sessions()):
-        for bit in (0x10, 0x01):
-            wrong = bytes([s["key"][0] ^ bit]) + s["key"][1:]
-            streams.append((s["cfg"], [R.decrypt_packet(wrong, s["iv"], p) for p in s["payloads"]], AC.FORMS[k % 3]))
-    # ... and a datagram that was encrypted under another session's key (tests/test_raop_host_cpp.py)
-    s, other = RC.sessions()[3], RC.sessions()[0]["key"]
-    streams.append((s["cfg"], [R.decrypt_packet(s["key"], s["iv"], R.encrypt_packet(other, s["iv"], p)) for p in s["fx"]["packets"]], T.PACKED_LE))
-    job = AC.Job(streams)
+    wrong = RC.wrong_key_streams(lambda k: AC.FORMS[k // 2 % 3] if k < 8 else T.PACKED_LE)
+    assert len(wrong) == 9
+    job = AC.Job([(s["cfg"], RC.clear_packets(s), s["form"]) for s in wrong])
     assert T.CORRUPT in {st for st, _ in job.want_packets}
     for route in AlacCpu.ROUTES:
         AlacCpu.check(exe, job, tmp_path, route)
