@@ -31,6 +31,8 @@
  *       (Codec/AlacApple.cpp, AlacAppleBase.cpp:20-115; thirdparty/apple_alac by its behaviour)   -> TInt32 planes or the decoder's packed bytes
  *   RaopAudioDecryptor::Decrypt + CodecRaopApple: AES-128-CBC per packet, then as above   ohgpu_raop_batch_run()
  *       (Av/Raop/ProtocolRaop.cpp:1477-1502, Av/Raop/CodecRaopApple.cpp:61-214)          -> the same, or the plaintext alone
+ *   RaopAudioServer, RaopControlServer, ProtocolRaop::ProcessPacket + Repairer<MaxFrames>   ohgpu_raop_rx_batch_run() (ohgpu_raop_rx.h)
+ *       (Av/Raop/ProtocolRaop.cpp:285-378, 662-926, 1145-1466, ProtocolRaop.h:466-789)       -> the packet table ohgpu_raop_* takes, in playing order
  *   OhmHeader::Internalise + OhmMsgAudio::Create(IReader&) + ProtocolOhBase's frame sequencer   ohgpu_ohm_rx_batch_run()
  *       (Av/Songcast/Ohm.cpp:22-42, OhmMsg.cpp:101-175, ProtocolOhBase.cpp:254-553)            -> CodecPcm's big-endian bytes
  *   CodecFlac's Ogg FLAC streams: libogg's page reader and libFLAC's Ogg aspect in front of the frames   ohgpu_ogg_batch_run()
@@ -214,6 +216,7 @@ typedef struct ohgpu_batch_paths {       /* 64 bytes */
         uint32_t alac_route;        /* Apple Lossless: 1 the three fused phases over the transposed scratch, 2 the plain route (created under kernel variant 1) */
         uint32_t mp4_route;         /* MPEG-4: 1 the four phases (walk, tile sums, carries, expand), 2 the plain route: one launch, a lane per stream (kernel variant 1) */
         uint32_t iff_route;         /* PCM files: 1 the two launches (walk, convert by 16-byte pieces), 2 the plain route: one launch, a lane per stream (kernel variant 1) */
+        uint32_t raop_rx_route;     /* RAOP receiver: 1 the sequencer is a wave per stream, 2 the plain route: a lane per stream runs the serial text (kernel variant 1) */
         uint32_t dsd_file_route;    /* DSD files: 1 the two launches (walk, convert by lanes of eight chunks), 2 the plain route: one launch, a lane per stream (kernel variant 1) */
     };
 } ohgpu_batch_paths;
@@ -584,7 +587,9 @@ int ohgpu_alac_process_host(ohgpu_ctx* ctx, const ohgpu_alac_stream_desc* descs,
  * moved, so the alignment carries over --; bytes between packets are not written; its packets must ascend without overlap
  * (OHGPU_ERR_INVALID), dst_offset is a multiple of 4, dst_plane_stride is 0, alac.config is not read and no packet-size limit
  * applies; every packet's result is OHGPU_ALAC_OK with samples 0.  A batch may mix both kinds.
- * The RSA unwrap of the session key, RTSP / SDP, the control and timing ports and resend / repair stay the caller's. */
+ * Datagrams arrive lost, doubled and out of order: ohgpu_raop_rx_* (ohgpu_raop_rx.h) is the receiver in front of this
+ * family -- the control port's sync and resend packets, repair, the flush window and the latency -- and hands over this packet table.
+ * The RSA unwrap of the session key, RTSP / SDP and the timing port stay the caller's. */
 #define OHGPU_RAOP_OUT_PLAINTEXT 0x04u   /* in alac.flags: no decode */
 
 typedef struct ohgpu_raop_stream_desc {  /* 96 bytes */
@@ -1734,5 +1739,6 @@ int ohgpu_set_kernel_variant(ohgpu_ctx* ctx, int variant);
 
 /* Protected fragmented MPEG-4 (ohgpu_cenc_*) has a header of its own beside this one; it comes with this one. */
 #include "ohgpu_cenc.h"
+#include "ohgpu_raop_rx.h"
 
 #endif /* OHGPU_H */

@@ -399,6 +399,37 @@ CENC_SYMBOLS = {
                                                C.c_size_t, C.POINTER(C.c_size_t)]),
     "ohgpu_cenc_alac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
+# include/ohgpu_raop_rx.h's: the RAOP receiver -- the datagram table, the stream table with the state carried between
+# batches, a record per datagram, a result per stream with the resend ranges
+RAOP_RX_SYMBOLS = {
+    "ohgpu_raop_rx_batch_check": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, C.c_uint64]),
+    "ohgpu_raop_rx_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_uint64, _vpp]),
+    "ohgpu_raop_rx_batch_run": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "ohgpu_raop_rx_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t]),
+    "ohgpu_raop_rx_batch_packets": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_raop_rx_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
+    "ohgpu_raop_rx_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "ohgpu_raop_rx_alac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
+}
+RAOP_RX_MAX_PACKET_BYTES, RAOP_RX_MAX_FRAMES, RAOP_RX_MAX_RANGES = 1472, 63, 31
+RAOP_RX_PORT_AUDIO, RAOP_RX_PORT_CONTROL = 0, 1
+RAOP_RX_OK, RAOP_RX_TRUNCATED, RAOP_RX_OVERSIZE, RAOP_RX_OTHER_TYPE = range(4)
+(RAOP_RX_OUTPUT, RAOP_RX_DUPLICATE, RAOP_RX_PENDING, RAOP_RX_DROPPED_BY_RESET, RAOP_RX_FLUSHED, RAOP_RX_WRONG_SESSION, RAOP_RX_SYNC, RAOP_RX_IGNORED,
+ RAOP_RX_NOT_REACHED) = range(1, 10)
+RAOP_RX_EVENT_NEW_STREAM, RAOP_RX_EVENT_DELAY = 1, 2
+RAOP_RX_STOP_NONE, RAOP_RX_STOP_BUFFER_FULL, RAOP_RX_STOP_RESTARTED = 0, 1, 2
+RAOP_RX_DATAGRAM = np.dtype([("src_offset", "<u8"), ("bytes", "<u4"), ("port", "u1"), ("reserved", "u1", (3,))], align=False)
+_RAOP_RX_STATE = [("flush_seq", "<u4"), ("flush_time", "<u4"), ("session_id", "<u4"), ("latency", "<u4"), ("control_latency", "<u4"), ("frame", "<u2"),
+                  ("running", "u1"), ("started", "u1"), ("resume_pending", "u1"), ("state_reserved", "u1", (7,))]
+RAOP_RX_STATE_FIELDS = tuple(name for name, *_ in _RAOP_RX_STATE[:-1])
+RAOP_RX_STREAM = np.dtype([("first_datagram", "<u4"), ("n_datagrams", "<u4"), ("max_frames", "<u4"), ("reserved", "<u4")] + _RAOP_RX_STATE, align=False)
+RAOP_RX_RECORD = np.dtype([
+    ("status", "u1"), ("disposition", "u1"), ("events", "u1"), ("resend", "u1"), ("marker", "u1"), ("extension", "u1"), ("type", "u1"), ("port", "u1"),
+    ("seq", "<u2"), ("payload_offset", "<u2"), ("payload_bytes", "<u4"), ("timestamp", "<u4"), ("ssrc", "<u4"), ("sync", "<u4", (4,)), ("order", "<u4"),
+    ("reserved", "<u4")], align=False)
+RAOP_RX_STREAM_RESULT = np.dtype(_RAOP_RX_STATE + [("n_output", "<u4"), ("n_pending", "<u4"), ("stop_reason", "<u4"), ("n_ranges", "<u4"),
+                                                  ("ranges", "<u4", (31, 2))], align=False)
+assert RAOP_RX_DATAGRAM.itemsize == 16 and RAOP_RX_STREAM.itemsize == 48 and RAOP_RX_RECORD.itemsize == 48 and RAOP_RX_STREAM_RESULT.itemsize == 296
 
 
 class OhGpuError(RuntimeError):
@@ -419,7 +450,7 @@ def lib():
         raise ImportError(f"{LIB_PATH} is missing: build the HIP extension first (python ohpipeline_amd/build.py); "
                           "there is no CPU fallback for the product path")
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(CENC_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(CENC_SYMBOLS.items()) + list(RAOP_RX_SYMBOLS.items()):
         fn = getattr(L, name)          # AttributeError here = the library does not export what ohgpu.h declares
         fn.restype = res
         fn.argtypes = args
@@ -608,6 +639,18 @@ def ohm_rx_batch_check(streams, datagrams, src_arena_bytes, dst_arena_bytes):
     """The validation of ctx.ohm_rx_batch without a device (ohgpu_ohm_rx_batch_check): OhGpuError on a bad table."""
     s, g = _ohm_rx_tables(streams, datagrams)
     check(lib().ohgpu_ohm_rx_batch_check(_ptr_or_none(s), s.size, _ptr_or_none(g), g.size, src_arena_bytes, dst_arena_bytes))
+
+
+def _raop_rx_tables(streams, datagrams):
+    s, g = np.ascontiguousarray(streams), np.ascontiguousarray(datagrams)
+    assert s.dtype == RAOP_RX_STREAM and g.dtype == RAOP_RX_DATAGRAM
+    return s, g
+
+
+def raop_rx_batch_check(streams, datagrams, src_arena_bytes):
+    """The validation of ctx.raop_rx_batch without a device (ohgpu_raop_rx_batch_check): OhGpuError on a bad table."""
+    s, g = _raop_rx_tables(streams, datagrams)
+    check(lib().ohgpu_raop_rx_batch_check(_ptr_or_none(s), s.size, _ptr_or_none(g), g.size, src_arena_bytes))
 
 
 def _ogg_descs(descs):
@@ -891,6 +934,7 @@ class Context:
         out["mp4_route"] = out["alac_route"]                 # (the same word: a batch is of one kind)
         out["iff_route"] = out["alac_route"]
         out["dsd_file_route"] = out["alac_route"]
+        out["raop_rx_route"] = out["alac_route"]
         return out
 
     def pcm_process_host(self, descs, src, dst):
@@ -1132,6 +1176,55 @@ class Context:
         check(lib().ohgpu_ohm_rx_process_host(self._h, _ptr_or_none(s), s.size, _ptr_or_none(g), g.size, _ptr_or_none(src), src.nbytes,
                                               _ptr_or_none(dst), dst.nbytes, _ptr_or_none(sres), _ptr_or_none(recs)))
         return sres, recs
+
+    def raop_rx_batch(self, streams, datagrams, src_arena_bytes):
+        s, g = _raop_rx_tables(streams, datagrams)
+        b = C.c_void_p()
+        check(lib().ohgpu_raop_rx_batch_create(self._h, _ptr_or_none(s), s.size, _ptr_or_none(g), g.size, src_arena_bytes, C.byref(b)))
+        return b
+
+    def raop_rx_run(self, batch, d_src, stream=None):
+        """Parse, sequence, table (ohgpu_raop_rx_batch_run): queued on the stream; d_src 4-byte aligned."""
+        check(lib().ohgpu_raop_rx_batch_run(self._h, batch, d_src, stream))
+
+    def raop_rx_results(self, batch, n, n_datagrams):
+        """The last run's (RAOP_RX_STREAM_RESULT per stream, RAOP_RX_RECORD per datagram); waits for the run."""
+        sres, recs = np.zeros(n, dtype=RAOP_RX_STREAM_RESULT), np.zeros(n_datagrams, dtype=RAOP_RX_RECORD)
+        check(lib().ohgpu_raop_rx_batch_results(self._h, batch, _ptr_or_none(sres), n, _ptr_or_none(recs), n_datagrams))
+        return sres, recs
+
+    def raop_rx_packets(self, batch, n_datagrams):
+        """The last run's packet table (ALAC_PACKET per datagram row); waits for the run."""
+        rows = np.zeros(n_datagrams, dtype=ALAC_PACKET)
+        check(lib().ohgpu_raop_rx_batch_packets(self._h, batch, _ptr_or_none(rows), n_datagrams))
+        return rows
+
+    def raop_rx_phase_ms(self, batch):
+        """The last run's (parse, sequence, table) in milliseconds, from device events."""
+        ms = (C.c_float * 3)()
+        check(lib().ohgpu_raop_rx_batch_phase_ms(self._h, batch, ms))
+        return tuple(float(v) for v in ms)
+
+    def raop_rx_process_host(self, streams, datagrams, src):
+        """Host buffer in (ohgpu_raop_rx_process_host); returns (stream results, records, packet rows)."""
+        s, g = _raop_rx_tables(streams, datagrams)
+        sres, recs, rows = np.zeros(s.size, dtype=RAOP_RX_STREAM_RESULT), np.zeros(g.size, dtype=RAOP_RX_RECORD), np.zeros(g.size, dtype=ALAC_PACKET)
+        check(lib().ohgpu_raop_rx_process_host(self._h, _ptr_or_none(s), s.size, _ptr_or_none(g), g.size, _ptr_or_none(src), src.nbytes,
+                                               _ptr_or_none(sres), _ptr_or_none(recs), _ptr_or_none(rows)))
+        return sres, recs, rows
+
+    def raop_rx_alac_process_host(self, streams, descs, datagrams, src, dst):
+        """Datagrams to PCM or plaintext (ohgpu_raop_rx_alac_process_host); returns (stream results, records, packet rows, Apple
+        Lossless stream results, packet results by datagram row)."""
+        s, g = _raop_rx_tables(streams, datagrams)
+        d = np.ascontiguousarray(descs)
+        assert d.dtype == RAOP_STREAM_DESC and d.size == s.size
+        sres, recs, rows = np.zeros(s.size, dtype=RAOP_RX_STREAM_RESULT), np.zeros(g.size, dtype=RAOP_RX_RECORD), np.zeros(g.size, dtype=ALAC_PACKET)
+        ares, pres = np.zeros(s.size, dtype=ALAC_STREAM_RESULT), np.zeros(g.size, dtype=ALAC_PACKET_RESULT)
+        check(lib().ohgpu_raop_rx_alac_process_host(self._h, _ptr_or_none(s), _ptr_or_none(d), s.size, _ptr_or_none(g), g.size, _ptr_or_none(src), src.nbytes,
+                                                    _ptr_or_none(dst), dst.nbytes, _ptr_or_none(sres), _ptr_or_none(recs), _ptr_or_none(rows),
+                                                    _ptr_or_none(ares), _ptr_or_none(pres)))
+        return sres, recs, rows, ares, pres
 
     def ogg_batch(self, descs, n_packets, src_arena_bytes, dst_arena_bytes):
         d = _ogg_descs(descs)

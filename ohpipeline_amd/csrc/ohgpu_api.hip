@@ -315,8 +315,9 @@ static const struct { const char* noun; void (*release)(ohgpu_ctx*, ohgpu_batch*
     {"a DSD file", free_state<&ohgpu_batch::file>, false},   // kBatchDsdFile
     {"a fragmented MPEG-4", free_state<&ohgpu_batch::mp4f>, false},   // kBatchMp4f
     {"a protected MPEG-4", cenc_free, false},   // kBatchCenc
+    {"a RAOP receiver", free_state<&ohgpu_batch::raoprx>, false},   // kBatchRaopRx
 };
-static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchCenc + 1, "a row per BatchKind");
+static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchRaopRx + 1, "a row per BatchKind");
 
 int run_guard(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, BatchKind kind, bool empty, bool null_src_ok,
               const void* src_base, const void* dst_base, bool needs_dst)
@@ -633,6 +634,10 @@ int ohgpu_batch_paths_info(const ohgpu_batch* b, ohgpu_batch_paths* out)
     }
     if (b->kind == kBatchDsdFile) {
         out->dsd_file_route = b->file && b->file->plain ? 2u : 1u;
+        return OHGPU_OK;
+    }
+    if (b->kind == kBatchRaopRx) {
+        out->raop_rx_route = b->raoprx && b->raoprx->plain ? 2u : 1u;
         return OHGPU_OK;
     }
     if (b->kind != kBatchOhm) return set_error(OHGPU_ERR_INVALID, "ohgpu_batch_paths_info: not a pcm, Songcast frame, fmt, Apple Lossless, MPEG-4, PCM file or DSD file batch");

@@ -25,6 +25,7 @@
 #include "iff_chunk_core.h"
 #include "dsd_file_core.h"
 #include "ohm_rx_core.h"
+#include "raop_rx_core.h"
 #include "raop_aes_core.h"
 #include "cenc_core.h"
 
@@ -443,6 +444,25 @@ struct OhmRxState : RunState {
 static_assert(sizeof(ohgpu_ohm_rx_datagram) == sizeof(ohmrx::Datagram) && sizeof(ohgpu_ohm_rx_state) == sizeof(ohmrx::State) && sizeof(ohgpu_ohm_rx_stream) == sizeof(ohmrx::Stream) &&
               sizeof(ohgpu_ohm_rx_record) == sizeof(ohmrx::Record) && sizeof(ohgpu_ohm_rx_stream_result) == sizeof(ohmrx::StreamResult), "Songcast receiver layouts");
 
+// ---- RAOP receiver (csrc/raop_rx_kernel.hip): the tables, each datagram's stream, the records, keys, rows and results of
+// the last run, and the plain route's waiting lists.  The batch's d_descs holds nothing.
+struct RaopRxState : RunState {
+    size_t n_streams = 0, n_datagrams = 0;
+    bool   plain = false;                             // created under kernel variant 1
+    void* d_streams = nullptr;                        // raoprx::Stream[n_streams]
+    void* d_datagrams = nullptr;                      // raoprx::Datagram[n_datagrams]
+    void* d_owner = nullptr;                          // uint32[n_datagrams]: the datagram's stream
+    void* d_records = nullptr;                        // raoprx::Record[n_datagrams]
+    void* d_keys = nullptr;                           // raoprx::Key[n_datagrams]
+    void* d_rows = nullptr;                           // raoprx::PacketRow[n_datagrams]
+    void* d_results = nullptr;                        // raoprx::StreamResult[n_streams]
+    void* d_slots = nullptr;                          // uint64[n_streams][raoprx::kSlots], the plain route only
+};
+static_assert(sizeof(ohgpu_raop_rx_datagram) == sizeof(raoprx::Datagram) && sizeof(ohgpu_raop_rx_state) == sizeof(raoprx::State) && sizeof(ohgpu_raop_rx_stream) == sizeof(raoprx::Stream) &&
+              sizeof(ohgpu_raop_rx_record) == sizeof(raoprx::Record) && sizeof(ohgpu_raop_rx_stream_result) == sizeof(raoprx::StreamResult) &&
+              sizeof(ohgpu_alac_packet) == sizeof(raoprx::PacketRow) && offsetof(ohgpu_raop_rx_record, order) == offsetof(raoprx::Record, order) &&
+              offsetof(ohgpu_raop_rx_state, frame) == offsetof(raoprx::State, frame), "RAOP receiver layouts");
+
 // ---- Ogg pages (csrc/ogg_page_kernel.hip): the descriptors, the find phase's tiles, the candidate list, the bitmap of
 // verified page starts, the gather plan and its dense work list, the packet table and results of the last run.  The batch's d_descs
 // holds nothing.
@@ -569,7 +589,7 @@ static_assert(sizeof(ohgpu_dsd_file_stream_desc) == sizeof(dsdfile::Stream) && s
               dsdfile::kDsf == OHGPU_DSD_DSF && dsdfile::kDff == OHGPU_DSD_DFF && dsdfile::kDsf == OHGPU_DSD_FILE_KIND_DSF && dsdfile::kDff == OHGPU_DSD_FILE_KIND_DFF &&
               dsdfile::kFillByte == OHGPU_DSD_SILENCE_BYTE && dsdfile::kMaxChunks == OHGPU_DSD_FILE_MAX_CHUNKS, "DSD file layouts");
 
-enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11, kBatchOhmRx = 12, kBatchOgg = 13, kBatchMp4 = 14, kBatchIff = 15, kBatchDsdFile = 16, kBatchMp4f = 17, kBatchCenc = 18 };
+enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11, kBatchOhmRx = 12, kBatchOgg = 13, kBatchMp4 = 14, kBatchIff = 15, kBatchDsdFile = 16, kBatchMp4f = 17, kBatchCenc = 18, kBatchRaopRx = 19 };
 
 }  // namespace ohgpu
 
@@ -682,6 +702,7 @@ struct ohgpu_batch {
     ohgpu::FileState* file = nullptr;   // kBatchIff and kBatchDsdFile
     ohgpu::Mp4fState* mp4f = nullptr;   // kBatchMp4f only
     ohgpu::CencState* cenc = nullptr;   // kBatchCenc only
+    ohgpu::RaopRxState* raoprx = nullptr;   // kBatchRaopRx only
     void*    d_pull_tiles = nullptr;   // kBatchSrcPull: PullTile[n_pull_tiles] on the device (d_descs holds the messages)
     uint32_t n_pull_tiles = 0;
     // kBatchSrc whose messages differ in layout: one uniform batch per layout (each with its own block-kernel plan), run one
@@ -772,6 +793,9 @@ int  raop_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t*
 int  ohm_rx_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const ohmrx::Stream* streams, const ohmrx::Datagram* datagrams);   // tables and result arrays onto the device (b->ohmrx holds the counts)
 int  ohm_rx_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
 uint32_t ohm_rx_gather_blocks(uint32_t n_datagrams, uint32_t cus);   // the gather launch's size: the rule tests/test_gpu_ohm_rx_many_trips.py restates
+// csrc/raop_rx_kernel.hip
+int  raop_rx_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const raoprx::Stream* streams, const raoprx::Datagram* datagrams);   // tables and result arrays onto the device (b->raoprx holds the counts and the route)
+int  raop_rx_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, hipStream_t s);
 // csrc/ogg_page_kernel.hip
 int  ogg_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const oggpage::Stream* streams);   // tiles, lists and result arrays onto the device (b->ogg holds the counts)
 int  ogg_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);

@@ -10,8 +10,9 @@
 // when datagrams arrive.  Flush() takes every lane of a tick, lays the queued payloads of all of them into one arena and makes ONE
 // device call (ohgpu_raop_process_host, packed little-endian output); each packet leaves through CodecController::OutputAudioPcm in
 // CodecAlacAppleBase::Decode's pieces.  The host never touches a sample, nor a plaintext byte.
-// Packets are expected in playing order: the resend / repair machinery in front (ProtocolRaop's Repairer), the RSA unwrap of the
-// session key, RTSP / SDP and the control and timing ports stay the host's.  This codec cannot seek (CodecRaopApple::TrySeek returns
+// Packets are expected in playing order: the resend / repair machinery in front (ProtocolRaop's Repairer) and the control port are
+// host/RaopReceiver.h's, which takes the datagrams as they arrive; the RSA unwrap of the session key, RTSP / SDP and the timing port
+// stay the host's.  This codec cannot seek (CodecRaopApple::TrySeek returns
 // false): there is no counterpart.
 #pragma once
 
