@@ -32,6 +32,7 @@
  *   RaopAudioDecryptor::Decrypt + CodecRaopApple: AES-128-CBC per packet, then as above   ohgpu_raop_batch_run()
  *       (Av/Raop/ProtocolRaop.cpp:1477-1502, Av/Raop/CodecRaopApple.cpp:61-214)          -> the same, or the plaintext alone
  *   RaopAudioServer, RaopControlServer, ProtocolRaop::ProcessPacket + Repairer<MaxFrames>   ohgpu_raop_rx_batch_run() (ohgpu_raop_rx.h)
+ *   MpegTsContainer (MpegTs, MpegPes), the framing of CodecAacFdkAdts, Id3v2   ohgpu_ts_batch_run(), ohgpu_adts_batch_run() (ohgpu_ts.h)
  *       (Av/Raop/ProtocolRaop.cpp:285-378, 662-926, 1145-1466, ProtocolRaop.h:466-789)       -> the packet table ohgpu_raop_* takes, in playing order
  *   OhmHeader::Internalise + OhmMsgAudio::Create(IReader&) + ProtocolOhBase's frame sequencer   ohgpu_ohm_rx_batch_run()
  *       (Av/Songcast/Ohm.cpp:22-42, OhmMsg.cpp:101-175, ProtocolOhBase.cpp:254-553)            -> CodecPcm's big-endian bytes
@@ -1740,5 +1741,6 @@ int ohgpu_set_kernel_variant(ohgpu_ctx* ctx, int variant);
 /* Protected fragmented MPEG-4 (ohgpu_cenc_*) has a header of its own beside this one; it comes with this one. */
 #include "ohgpu_cenc.h"
 #include "ohgpu_raop_rx.h"
+#include "ohgpu_ts.h"
 
 #endif /* OHGPU_H */

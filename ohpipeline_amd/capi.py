@@ -430,6 +430,54 @@ RAOP_RX_RECORD = np.dtype([
 RAOP_RX_STREAM_RESULT = np.dtype(_RAOP_RX_STATE + [("n_output", "<u4"), ("n_pending", "<u4"), ("stop_reason", "<u4"), ("n_ranges", "<u4"),
                                                   ("ranges", "<u4", (31, 2))], align=False)
 assert RAOP_RX_DATAGRAM.itemsize == 16 and RAOP_RX_STREAM.itemsize == 48 and RAOP_RX_RECORD.itemsize == 48 and RAOP_RX_STREAM_RESULT.itemsize == 296
+# include/ohgpu_ts.h's: the MPEG transport stream demultiplexer and the ADTS frame table -- a descriptor and a result per
+# stream in both layers, a record per PES packet, a record per ADTS frame
+_u32p = C.POINTER(C.c_uint32)
+TS_SYMBOLS = {
+    "ohgpu_ts_batch_check": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64]),
+    "ohgpu_ts_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
+    "ohgpu_ts_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "ohgpu_ts_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_ts_batch_pes": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_ts_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
+    "ohgpu_ts_batch_paths": (C.c_int, [_vp, _u32p, _u32p, _u32p]),
+    "ohgpu_ts_process_host": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
+    "ohgpu_ts_crc": (C.c_uint32, [_vp, C.c_size_t]),
+    "ohgpu_adts_batch_check": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_uint64]),
+    "ohgpu_adts_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_uint64, _vpp]),
+    "ohgpu_adts_batch_run": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "ohgpu_adts_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_adts_batch_frames": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_adts_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
+    "ohgpu_adts_batch_paths": (C.c_int, [_vp, _u32p, _u32p]),
+    "ohgpu_adts_process_host": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, _vp]),
+    "ohgpu_adts_header": (C.c_int, [_vp, C.c_size_t, _vp]),
+    "ohgpu_id3v2_skip": (C.c_uint64, [_vp, C.c_size_t]),
+    "ohgpu_ts_adts_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
+}
+TS_PACKET_BYTES, TS_NONE, TS_NO_PTS = 188, 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
+TS_OK, TS_NO_PAT, TS_NO_PMT, TS_NO_AUDIO, TS_CORRUPT = range(5)
+TS_PES_OPEN = 1
+TS_PES_CONTINUATION, TS_PES_EXCESS, TS_PES_TRUNCATED, TS_PES_CC_JUMP = 1, 2, 4, 8
+ADTS_OK, ADTS_NOT_ADTS = 0, 1
+ADTS_RECOGNISE, ADTS_INTERRUPTED = 1, 1
+ADTS_RECOGNISE_LAST_START, ADTS_RECOGNISE_FRAMES = 1001, 5
+TS_STREAM_DESC = np.dtype([("src_offset", "<u8"), ("dst_offset", "<u8"), ("dst_capacity", "<u8"), ("src_bytes", "<u4"), ("flags", "<u4"), ("pmt_pid", "<u4"),
+                           ("audio_pid", "<u4"), ("pes_open_bytes", "<u4"), ("pes_first", "<u4"), ("pes_capacity", "<u4"), ("reserved", "<u4", (3,))], align=False)
+TS_STREAM_RESULT = np.dtype([("status", "u1"), ("trailing_bytes", "u1"), ("reserved", "<u2"), ("pmt_pid", "<u2"), ("audio_pid", "<u2"), ("packets", "<u4"),
+                             ("bad_sync", "<u4"), ("tei_packets", "<u4"), ("scrambled_packets", "<u4"), ("pat_packet", "<u4"), ("pmt_packet", "<u4"),
+                             ("audio_packets", "<u4"), ("pes_packets", "<u4"), ("bad_pes_starts", "<u4"), ("bytes_delivered", "<u4"), ("dropped_bytes", "<u4"),
+                             ("cc_jumps", "<u4"), ("pes_open_bytes", "<u4"), ("corrupt_packet", "<u4")], align=False)
+TS_PES = np.dtype([("es_offset", "<u8"), ("pts", "<u8"), ("bytes", "<u4"), ("packet", "<u4"), ("flags", "<u4"), ("stream_id", "u1"), ("reserved", "u1", (3,))], align=False)
+ADTS_STREAM_DESC = np.dtype([("src_offset", "<u8"), ("src_bytes", "<u4"), ("flags", "<u4"), ("frame_first", "<u4"), ("frame_capacity", "<u4"),
+                             ("reserved", "<u4", (2,))], align=False)
+ADTS_STREAM_RESULT = np.dtype([("status", "<u4"), ("frames", "<u4"), ("bytes_consumed", "<u4"), ("first_frame_offset", "<u4"), ("interruptions", "<u4"),
+                               ("skipped_bytes", "<u4"), ("mean_payload_bytes", "<u4"), ("profile", "u1"), ("sf_index", "u1"), ("channel_config", "u1"),
+                               ("reserved", "u1"), ("reserved2", "<u4", (8,))], align=False)
+ADTS_FRAME = np.dtype([("offset", "<u8"), ("bytes", "<u4"), ("flags", "<u4"), ("header_bytes", "u1"), ("profile", "u1"), ("sf_index", "u1"), ("channel_config", "u1"),
+                       ("reserved", "<u4", (3,))], align=False)
+assert TS_STREAM_DESC.itemsize == 64 and TS_STREAM_RESULT.itemsize == 64 and TS_PES.itemsize == 32
+assert ADTS_STREAM_DESC.itemsize == 32 and ADTS_STREAM_RESULT.itemsize == 64 and ADTS_FRAME.itemsize == 32
 
 
 class OhGpuError(RuntimeError):
@@ -450,7 +498,7 @@ def lib():
         raise ImportError(f"{LIB_PATH} is missing: build the HIP extension first (python ohpipeline_amd/build.py); "
                           "there is no CPU fallback for the product path")
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(CENC_SYMBOLS.items()) + list(RAOP_RX_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(CENC_SYMBOLS.items()) + list(RAOP_RX_SYMBOLS.items()) + list(TS_SYMBOLS.items()):
         fn = getattr(L, name)          # AttributeError here = the library does not export what ohgpu.h declares
         fn.restype = res
         fn.argtypes = args
@@ -651,6 +699,42 @@ def raop_rx_batch_check(streams, datagrams, src_arena_bytes):
     """The validation of ctx.raop_rx_batch without a device (ohgpu_raop_rx_batch_check): OhGpuError on a bad table."""
     s, g = _raop_rx_tables(streams, datagrams)
     check(lib().ohgpu_raop_rx_batch_check(_ptr_or_none(s), s.size, _ptr_or_none(g), g.size, src_arena_bytes))
+
+
+def _typed(descs, dtype):
+    d = np.ascontiguousarray(descs)
+    assert d.dtype == dtype
+    return d
+
+
+def ts_batch_check(descs, n_pes, src_arena_bytes, dst_arena_bytes):
+    """The validation of ctx.ts_batch without a device (ohgpu_ts_batch_check): OhGpuError on a bad descriptor."""
+    d = _typed(descs, TS_STREAM_DESC)
+    check(lib().ohgpu_ts_batch_check(_ptr_or_none(d), d.size, n_pes, src_arena_bytes, dst_arena_bytes))
+
+
+def adts_batch_check(descs, n_frames, src_arena_bytes):
+    """The validation of ctx.adts_batch without a device (ohgpu_adts_batch_check)."""
+    d = _typed(descs, ADTS_STREAM_DESC)
+    check(lib().ohgpu_adts_batch_check(_ptr_or_none(d), d.size, n_frames, src_arena_bytes))
+
+
+def ts_crc(data):
+    """The section CRC-32 of any bytes (ohgpu_ts_crc; host only)."""
+    raw = bytes(data)
+    return int(lib().ohgpu_ts_crc(raw, len(raw)))
+
+
+def adts_header(data):
+    """One ADTS header (ohgpu_adts_header; host only): an ADTS_FRAME record, or None where the bytes begin with no valid header."""
+    raw, out = bytes(data), np.zeros(1, dtype=ADTS_FRAME)
+    return out[0] if lib().ohgpu_adts_header(raw, len(raw), out.ctypes.data_as(C.c_void_p)) == OK else None
+
+
+def id3v2_skip(data):
+    """The bytes of the ID3v2 tags at the head of a buffer (ohgpu_id3v2_skip; host only); 0: no tag."""
+    raw = bytes(data)
+    return int(lib().ohgpu_id3v2_skip(raw, len(raw)))
 
 
 def _ogg_descs(descs):
@@ -1225,6 +1309,90 @@ class Context:
                                                     _ptr_or_none(dst), dst.nbytes, _ptr_or_none(sres), _ptr_or_none(recs), _ptr_or_none(rows),
                                                     _ptr_or_none(ares), _ptr_or_none(pres)))
         return sres, recs, rows, ares, pres
+
+    def ts_batch(self, descs, n_pes, src_arena_bytes, dst_arena_bytes):
+        d = _typed(descs, TS_STREAM_DESC)
+        b = C.c_void_p()
+        check(lib().ohgpu_ts_batch_create(self._h, _ptr_or_none(d), d.size, n_pes, src_arena_bytes, dst_arena_bytes, C.byref(b)))
+        return b
+
+    def ts_run(self, batch, d_src, d_dst, stream=None):
+        """Parse, tables and sums, gather (ohgpu_ts_batch_run): queued on the stream."""
+        check(lib().ohgpu_ts_batch_run(self._h, batch, d_src, d_dst, stream))
+
+    def ts_results(self, batch, n, n_pes):
+        """The last run's (TS_STREAM_RESULT per stream, the PES table as TS_PES); waits for the run."""
+        res, pes = np.zeros(n, dtype=TS_STREAM_RESULT), np.zeros(n_pes, dtype=TS_PES)
+        check(lib().ohgpu_ts_batch_results(self._h, batch, _ptr_or_none(res), n))
+        check(lib().ohgpu_ts_batch_pes(self._h, batch, _ptr_or_none(pes), n_pes))
+        return res, pes
+
+    def ts_phase_ms(self, batch):
+        """(parse, tables and sums, gather) of the last run in milliseconds."""
+        ms = (C.c_float * 3)()
+        check(lib().ohgpu_ts_batch_phase_ms(self._h, batch, ms))
+        return tuple(float(v) for v in ms)
+
+    def ts_paths(self, batch):
+        """{route, tiles, wave_blocks} of a transport stream batch (ohgpu_ts_batch_paths)."""
+        route, tiles, blocks = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        check(lib().ohgpu_ts_batch_paths(batch, C.byref(route), C.byref(tiles), C.byref(blocks)))
+        return dict(route=int(route.value), tiles=int(tiles.value), wave_blocks=int(blocks.value))
+
+    def ts_process_host(self, descs, n_pes, src, dst):
+        """Host buffers in and out (ohgpu_ts_process_host); returns (stream results, PES table)."""
+        d = _typed(descs, TS_STREAM_DESC)
+        res, pes = np.zeros(d.size, dtype=TS_STREAM_RESULT), np.zeros(n_pes, dtype=TS_PES)
+        check(lib().ohgpu_ts_process_host(self._h, _ptr_or_none(d), d.size, n_pes, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst), dst.nbytes,
+                                          _ptr_or_none(res), _ptr_or_none(pes)))
+        return res, pes
+
+    def adts_batch(self, descs, n_frames, src_arena_bytes):
+        d = _typed(descs, ADTS_STREAM_DESC)
+        b = C.c_void_p()
+        check(lib().ohgpu_adts_batch_create(self._h, _ptr_or_none(d), d.size, n_frames, src_arena_bytes, C.byref(b)))
+        return b
+
+    def adts_run(self, batch, d_src, stream=None):
+        """Map, chain (ohgpu_adts_batch_run): queued on the stream."""
+        check(lib().ohgpu_adts_batch_run(self._h, batch, d_src, stream))
+
+    def adts_results(self, batch, n, n_frames):
+        """The last run's (ADTS_STREAM_RESULT per stream, the frame table as ADTS_FRAME); waits for the run."""
+        res, frames = np.zeros(n, dtype=ADTS_STREAM_RESULT), np.zeros(n_frames, dtype=ADTS_FRAME)
+        check(lib().ohgpu_adts_batch_results(self._h, batch, _ptr_or_none(res), n))
+        check(lib().ohgpu_adts_batch_frames(self._h, batch, _ptr_or_none(frames), n_frames))
+        return res, frames
+
+    def adts_phase_ms(self, batch):
+        """(map, chain) of the last run in milliseconds."""
+        ms = (C.c_float * 2)()
+        check(lib().ohgpu_adts_batch_phase_ms(self._h, batch, ms))
+        return tuple(float(v) for v in ms)
+
+    def adts_paths(self, batch):
+        """{route, tiles} of an ADTS batch (ohgpu_adts_batch_paths)."""
+        route, tiles = C.c_uint32(0), C.c_uint32(0)
+        check(lib().ohgpu_adts_batch_paths(batch, C.byref(route), C.byref(tiles)))
+        return dict(route=int(route.value), tiles=int(tiles.value))
+
+    def adts_process_host(self, descs, n_frames, src):
+        """Host bytes in (ohgpu_adts_process_host); returns (stream results, frame table)."""
+        d = _typed(descs, ADTS_STREAM_DESC)
+        res, frames = np.zeros(d.size, dtype=ADTS_STREAM_RESULT), np.zeros(n_frames, dtype=ADTS_FRAME)
+        check(lib().ohgpu_adts_process_host(self._h, _ptr_or_none(d), d.size, n_frames, _ptr_or_none(src), src.nbytes, _ptr_or_none(res), _ptr_or_none(frames)))
+        return res, frames
+
+    def ts_adts_process_host(self, ts_descs, adts_descs, n_pes, n_frames, src, dst):
+        """Transport bytes to the elementary run, the PES table and the frame table (ohgpu_ts_adts_process_host); returns (TS results, PES
+        table, ADTS results, frame table)."""
+        t, a = _typed(ts_descs, TS_STREAM_DESC), _typed(adts_descs, ADTS_STREAM_DESC)
+        assert t.size == a.size
+        tres, pes = np.zeros(t.size, dtype=TS_STREAM_RESULT), np.zeros(n_pes, dtype=TS_PES)
+        ares, frames = np.zeros(t.size, dtype=ADTS_STREAM_RESULT), np.zeros(n_frames, dtype=ADTS_FRAME)
+        check(lib().ohgpu_ts_adts_process_host(self._h, _ptr_or_none(t), _ptr_or_none(a), t.size, n_pes, n_frames, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst),
+                                               dst.nbytes, _ptr_or_none(tres), _ptr_or_none(pes), _ptr_or_none(ares), _ptr_or_none(frames)))
+        return tres, pes, ares, frames
 
     def ogg_batch(self, descs, n_packets, src_arena_bytes, dst_arena_bytes):
         d = _ogg_descs(descs)

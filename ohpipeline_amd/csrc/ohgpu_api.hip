@@ -316,8 +316,10 @@ static const struct { const char* noun; void (*release)(ohgpu_ctx*, ohgpu_batch*
     {"a fragmented MPEG-4", free_state<&ohgpu_batch::mp4f>, false},   // kBatchMp4f
     {"a protected MPEG-4", cenc_free, false},   // kBatchCenc
     {"a RAOP receiver", free_state<&ohgpu_batch::raoprx>, false},   // kBatchRaopRx
+    {"a transport stream", free_state<&ohgpu_batch::ts>, false},   // kBatchTs
+    {"an ADTS", free_state<&ohgpu_batch::adts>, false},   // kBatchAdts
 };
-static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchRaopRx + 1, "a row per BatchKind");
+static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchAdts + 1, "a row per BatchKind");
 
 int run_guard(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, BatchKind kind, bool empty, bool null_src_ok,
               const void* src_base, const void* dst_base, bool needs_dst)

@@ -28,6 +28,7 @@
 #include "raop_rx_core.h"
 #include "raop_aes_core.h"
 #include "cenc_core.h"
+#include "ts_packet_core.h"
 
 namespace ohgpu {
 
@@ -463,6 +464,45 @@ static_assert(sizeof(ohgpu_raop_rx_datagram) == sizeof(raoprx::Datagram) && size
               sizeof(ohgpu_alac_packet) == sizeof(raoprx::PacketRow) && offsetof(ohgpu_raop_rx_record, order) == offsetof(raoprx::Record, order) &&
               offsetof(ohgpu_raop_rx_state, frame) == offsetof(raoprx::State, frame), "RAOP receiver layouts");
 
+// ---- MPEG transport stream and ADTS (csrc/ts_packet_kernel.hip): the descriptors, each stream's first row of the
+// per-packet lists, the gather's tiles, the PES table and results of the last run; the map's tiles, the bitmap of valid headers, the
+// frame table.  The batch's d_descs holds nothing.
+struct TsTile { uint32_t stream, piece0; };           // one wave's share of the gather: destination pieces [piece0, piece0 + 64) of a stream
+struct TsState : RunState {
+    size_t n_streams = 0, n_pes = 0;
+    bool   plain = false;                             // created under kernel variant 1
+    uint64_t n_grid = 0;                              // grid packets of all streams
+    uint32_t n_tiles = 0, wave_blocks = 0;
+    void* d_streams = nullptr;                        // tspkt::Stream[n_streams]
+    void* d_results = nullptr;                        // tspkt::Result[n_streams]
+    void* d_first = nullptr;                          // uint64[n_streams + 1]: the stream's first row of the three lists below
+    void* d_pkt = nullptr;                            // tspkt::Pkt[n_grid]
+    void* d_run_end = nullptr;                        // uint32[n_grid]
+    void* d_src_at = nullptr;                         // uint32[n_grid]
+    void* d_tiles = nullptr;                          // TsTile[n_tiles]
+    void* d_pes = nullptr;                            // tspkt::Pes[n_pes]
+};
+struct AdtsTile { uint32_t stream, pos0; };           // one workgroup's share of the map: positions [pos0, pos0 + 1024) of a stream
+struct AdtsState : RunState {
+    size_t n_streams = 0, n_frames = 0;
+    bool   plain = false;
+    uint32_t n_tiles = 0;
+    size_t bits_bytes = 0;
+    void* d_streams = nullptr;                        // adts::Stream[n_streams]
+    void* d_results = nullptr;                        // adts::Result[n_streams]
+    void* d_bit_base = nullptr;                       // uint64[n_streams]: the stream's first bit in d_bits (a multiple of 1024)
+    void* d_tiles = nullptr;                          // AdtsTile[n_tiles]
+    void* d_bits = nullptr;                           // a bit per source byte: a valid header starts here
+    void* d_frames = nullptr;                         // adts::Frame[n_frames]
+};
+static_assert(sizeof(ohgpu_ts_stream_desc) == sizeof(tspkt::Stream) && sizeof(ohgpu_ts_stream_result) == sizeof(tspkt::Result) && sizeof(ohgpu_ts_pes) == sizeof(tspkt::Pes) &&
+              offsetof(ohgpu_ts_stream_desc, pes_first) == offsetof(tspkt::Stream, pes_first) && offsetof(ohgpu_ts_stream_result, corrupt_packet) == offsetof(tspkt::Result, corrupt_packet) &&
+              offsetof(ohgpu_ts_pes, stream_id) == offsetof(tspkt::Pes, stream_id) && sizeof(ohgpu_adts_stream_desc) == sizeof(adts::Stream) &&
+              sizeof(ohgpu_adts_stream_result) == sizeof(adts::Result) && sizeof(ohgpu_adts_frame) == sizeof(adts::Frame) &&
+              offsetof(ohgpu_adts_stream_result, profile) == offsetof(adts::Result, profile) && offsetof(ohgpu_adts_frame, header_bytes) == offsetof(adts::Frame, header_bytes) &&
+              tspkt::kNone == OHGPU_TS_NONE && tspkt::kNoPts == OHGPU_TS_NO_PTS && tspkt::kCorrupt == OHGPU_TS_CORRUPT && tspkt::kCcJump == OHGPU_TS_PES_CC_JUMP &&
+              adts::kLastStart == OHGPU_ADTS_RECOGNISE_LAST_START && adts::kRecogniseFrames == OHGPU_ADTS_RECOGNISE_FRAMES, "transport stream and ADTS layouts");
+
 // ---- Ogg pages (csrc/ogg_page_kernel.hip): the descriptors, the find phase's tiles, the candidate list, the bitmap of
 // verified page starts, the gather plan and its dense work list, the packet table and results of the last run.  The batch's d_descs
 // holds nothing.
@@ -589,7 +629,7 @@ static_assert(sizeof(ohgpu_dsd_file_stream_desc) == sizeof(dsdfile::Stream) && s
               dsdfile::kDsf == OHGPU_DSD_DSF && dsdfile::kDff == OHGPU_DSD_DFF && dsdfile::kDsf == OHGPU_DSD_FILE_KIND_DSF && dsdfile::kDff == OHGPU_DSD_FILE_KIND_DFF &&
               dsdfile::kFillByte == OHGPU_DSD_SILENCE_BYTE && dsdfile::kMaxChunks == OHGPU_DSD_FILE_MAX_CHUNKS, "DSD file layouts");
 
-enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11, kBatchOhmRx = 12, kBatchOgg = 13, kBatchMp4 = 14, kBatchIff = 15, kBatchDsdFile = 16, kBatchMp4f = 17, kBatchCenc = 18, kBatchRaopRx = 19 };
+enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11, kBatchOhmRx = 12, kBatchOgg = 13, kBatchMp4 = 14, kBatchIff = 15, kBatchDsdFile = 16, kBatchMp4f = 17, kBatchCenc = 18, kBatchRaopRx = 19, kBatchTs = 20, kBatchAdts = 21 };
 
 }  // namespace ohgpu
 
@@ -703,6 +743,8 @@ struct ohgpu_batch {
     ohgpu::Mp4fState* mp4f = nullptr;   // kBatchMp4f only
     ohgpu::CencState* cenc = nullptr;   // kBatchCenc only
     ohgpu::RaopRxState* raoprx = nullptr;   // kBatchRaopRx only
+    ohgpu::TsState* ts = nullptr;       // kBatchTs only
+    ohgpu::AdtsState* adts = nullptr;   // kBatchAdts only
     void*    d_pull_tiles = nullptr;   // kBatchSrcPull: PullTile[n_pull_tiles] on the device (d_descs holds the messages)
     uint32_t n_pull_tiles = 0;
     // kBatchSrc whose messages differ in layout: one uniform batch per layout (each with its own block-kernel plan), run one
@@ -747,7 +789,7 @@ inline int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? OHGPU_ERR_
 // The release functions (free_pcm_line, free_fmt_line, free_dsd_line, free_dsd_pcm, raop_free, free_flywheel, free_src_fast, free_ohm): what
 // ohgpu_batch_destroy's table calls (csrc/ohgpu_api.hip).  Each takes a PARTLY BUILT batch -- null pointers, a plan that was never
 // made -- and leaves the plan reset: a create that fails at any point hands its batch to ohgpu_batch_destroy and returns.
-// The families whose state is a RunState (flac, alac, ohmrx, ogg, mp4, mp4f, file) have no function of their own: the table calls
+// The families whose state is a RunState (flac, alac, ohmrx, ogg, mp4, mp4f, file, ts, adts) have no function of their own: the table calls
 // state_free (api_common.h) on the batch's pointer -- if it is set: state_release, which frees whatever block the state's registry
 // names and destroys whatever event exists, then delete, then null the pointer --, and raop_free calls it twice with its key wipe in
 // front.  Such a family names no block twice: dev_array in its plan is the one place.
@@ -796,6 +838,13 @@ uint32_t ohm_rx_gather_blocks(uint32_t n_datagrams, uint32_t cus);   // the gath
 // csrc/raop_rx_kernel.hip
 int  raop_rx_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const raoprx::Stream* streams, const raoprx::Datagram* datagrams);   // tables and result arrays onto the device (b->raoprx holds the counts and the route)
 int  raop_rx_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, hipStream_t s);
+// csrc/ts_packet_kernel.hip.  The gather is persistent (a wave a tile of 64 destination pieces, ts_wave_blocks workgroups); parse is a lane
+// a grid packet, tables and sums a workgroup a stream; the ADTS map a workgroup a tile, its chain a wave a stream.  The plain routes: a lane a stream.
+int  ts_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const tspkt::Stream* streams);
+int  ts_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
+uint32_t ts_wave_blocks(uint64_t tiles, uint32_t cus);   // the gather launch's size: the rule tests/test_gpu_ts_textbook.py restates
+int  adts_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const adts::Stream* streams);
+int  adts_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, hipStream_t s);
 // csrc/ogg_page_kernel.hip
 int  ogg_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const oggpage::Stream* streams);   // tiles, lists and result arrays onto the device (b->ogg holds the counts)
 int  ogg_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
