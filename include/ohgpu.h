@@ -33,6 +33,7 @@
  *       (Av/Raop/ProtocolRaop.cpp:1477-1502, Av/Raop/CodecRaopApple.cpp:61-214)          -> the same, or the plaintext alone
  *   RaopAudioServer, RaopControlServer, ProtocolRaop::ProcessPacket + Repairer<MaxFrames>   ohgpu_raop_rx_batch_run() (ohgpu_raop_rx.h)
  *   MpegTsContainer (MpegTs, MpegPes), the framing of CodecAacFdkAdts, Id3v2   ohgpu_ts_batch_run(), ohgpu_adts_batch_run() (ohgpu_ts.h)
+ *   CodecVorbis + Tremor: Vorbis I packets to 16-bit PCM (Codec/Vorbis.cpp; by the specification)   ohgpu_vorbis_batch_run() (ohgpu_vorbis.h)
  *       (Av/Raop/ProtocolRaop.cpp:285-378, 662-926, 1145-1466, ProtocolRaop.h:466-789)       -> the packet table ohgpu_raop_* takes, in playing order
  *   OhmHeader::Internalise + OhmMsgAudio::Create(IReader&) + ProtocolOhBase's frame sequencer   ohgpu_ohm_rx_batch_run()
  *       (Av/Songcast/Ohm.cpp:22-42, OhmMsg.cpp:101-175, ProtocolOhBase.cpp:254-553)            -> CodecPcm's big-endian bytes
@@ -194,7 +195,7 @@ int ohgpu_batch_info(const ohgpu_batch* batch, uint64_t* n_msgs, uint64_t* in_fr
  * kernel (fmt_stereo_*), the staged layout kernel (fmt_staged_chunks), or, with every count zero, the generic kernel only.
  * An Apple Lossless batch (ohgpu_alac_batch_create) answers with alac_route alone, and so does a RAOP batch; an MPEG-4 batch
  * (ohgpu_mp4_batch_create) answers with mp4_route alone, a PCM file batch (ohgpu_iff_batch_create) with iff_route alone, a DSD file
- * batch (ohgpu_dsd_file_batch_create) with dsd_file_route alone.
+ * batch (ohgpu_dsd_file_batch_create) with dsd_file_route alone, a Vorbis batch (ohgpu_vorbis_batch_create) with vorbis_route alone.
  * OHGPU_ERR_INVALID for any other kind of batch. */
 typedef struct ohgpu_batch_paths {       /* 64 bytes */
     uint32_t line_planned;          /* 1: the line kernel has a plan for the batch (0: only the generic kernel can run it) */
@@ -218,6 +219,7 @@ typedef struct ohgpu_batch_paths {       /* 64 bytes */
         uint32_t mp4_route;         /* MPEG-4: 1 the four phases (walk, tile sums, carries, expand), 2 the plain route: one launch, a lane per stream (kernel variant 1) */
         uint32_t iff_route;         /* PCM files: 1 the two launches (walk, convert by 16-byte pieces), 2 the plain route: one launch, a lane per stream (kernel variant 1) */
         uint32_t raop_rx_route;     /* RAOP receiver: 1 the sequencer is a wave per stream, 2 the plain route: a lane per stream runs the serial text (kernel variant 1) */
+        uint32_t vorbis_route;      /* Vorbis: 1 the transform through the FFT in the LDS, 2 the plain route: the direct-form transform (kernel variant 1) */
         uint32_t dsd_file_route;    /* DSD files: 1 the two launches (walk, convert by lanes of eight chunks), 2 the plain route: one launch, a lane per stream (kernel variant 1) */
     };
 } ohgpu_batch_paths;
@@ -1742,5 +1744,6 @@ int ohgpu_set_kernel_variant(ohgpu_ctx* ctx, int variant);
 #include "ohgpu_cenc.h"
 #include "ohgpu_raop_rx.h"
 #include "ohgpu_ts.h"
+#include "ohgpu_vorbis.h"
 
 #endif /* OHGPU_H */

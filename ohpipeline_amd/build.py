@@ -13,7 +13,8 @@ LIB_PATH = os.path.join(LIB_DIR, "libohgpu.so")
 HIP_SOURCES = ["ohgpu_api.hip", "pcm_kernels.hip", "pcm_line_kernel.hip", "flywheel_kernel.hip", "fmt_line_kernel.hip", "ohm_frame_kernel.hip", "ramp_plane_kernel.hip", "host_design.cpp", "src_plan.cpp", "src_block_kernel.hip", "src_lean_kernel.hip", "src_mfma_kernel.hip", "src_mfma_wg_kernel.hip"]
 PARTED = ("src_lean_kernel.hip",)     # compiled once per part of the instantiation list (csrc/src_block_common.h)
 HEADERS = ["ohgpu_internal.h", "pcm_device.h", os.path.join(ROOT, "include", "ohgpu.h"), os.path.join(ROOT, "include", "ohgpu_cenc.h"),
-           os.path.join(ROOT, "include", "ohgpu_raop_rx.h"), os.path.join(ROOT, "include", "ohgpu_ts.h")]
+           os.path.join(ROOT, "include", "ohgpu_raop_rx.h"), os.path.join(ROOT, "include", "ohgpu_ts.h"),
+           os.path.join(ROOT, "include", "ohgpu_vorbis.h")]
 # Per-source flags.  The lean kernel's per-frame control flow is wave-uniform (scalar compares); LLVM's structurizer
 # rewrites uniform diamonds into flag-and-test chains unless told to leave uniform regions alone (3-4 scalar instructions
 # per input frame in a loop the scalar unit co-limits).
@@ -122,6 +123,7 @@ def build_host(force=False, verbose=False):
     hdrs.append(os.path.join(ROOT, "include", "ohgpu_cenc.h"))
     hdrs.append(os.path.join(ROOT, "include", "ohgpu_raop_rx.h"))
     hdrs.append(os.path.join(ROOT, "include", "ohgpu_ts.h"))
+    hdrs.append(os.path.join(ROOT, "include", "ohgpu_vorbis.h"))
     if not force and os.path.exists(HOST_LIB_PATH):
         t = os.path.getmtime(HOST_LIB_PATH)
         if all(os.path.getmtime(f) <= t for f in srcs + hdrs) and os.path.getmtime(LIB_PATH) <= t:

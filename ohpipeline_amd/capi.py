@@ -480,6 +480,32 @@ assert TS_STREAM_DESC.itemsize == 64 and TS_STREAM_RESULT.itemsize == 64 and TS_
 assert ADTS_STREAM_DESC.itemsize == 32 and ADTS_STREAM_RESULT.itemsize == 64 and ADTS_FRAME.itemsize == 32
 
 
+# include/ohgpu_vorbis.h's: the Vorbis I decoder -- the setup image's parse, a descriptor per stream over rows of ALAC_PACKET
+VORBIS_SYMBOLS = {
+    "ohgpu_vorbis_setup_parse": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
+    "ohgpu_vorbis_codewords": (C.c_int, [_vp, C.c_size_t, _vp]),
+    "ohgpu_vorbis_batch_check": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint64, C.c_uint64, C.c_uint64]),
+    "ohgpu_vorbis_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vpp]),
+    "ohgpu_vorbis_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "ohgpu_vorbis_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t]),
+    "ohgpu_vorbis_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
+    "ohgpu_vorbis_batch_paths": (C.c_int, [_vp, _u32p, _u32p]),
+    "ohgpu_vorbis_batch_spectrum": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, _vp, C.c_size_t]),
+    "ohgpu_vorbis_head": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, _vp, _u32p, C.POINTER(C.c_uint64), _u32p, _u32p]),
+    "ohgpu_ogg_vorbis_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "ohgpu_vorbis_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
+}
+VORBIS_OK, VORBIS_HEADER, VORBIS_CORRUPT = 0, 1, 2
+VORBIS_OUT_PLANAR32 = 1
+VORBIS_INFO = np.dtype([("channels", "<u4"), ("sample_rate", "<u4"), ("blocksize_short", "<u4"), ("blocksize_long", "<u4"), ("image_bytes", "<u4"),
+                        ("codebooks", "<u4"), ("modes", "<u4"), ("reserved", "<u4")], align=False)
+VORBIS_STREAM_DESC = np.dtype([("image_offset", "<u8"), ("dst_offset", "<u8"), ("dst_plane_stride", "<u8"), ("max_samples", "<u8"), ("image_bytes", "<u4"),
+                               ("first_packet", "<u4"), ("n_packets", "<u4"), ("flags", "<u4"), ("reserved", "<u4", (4,))], align=False)
+VORBIS_PACKET_RESULT = np.dtype([("status", "u1"), ("mode", "u1"), ("blocksize", "<u2"), ("samples", "<u4"), ("position", "<u8"), ("reserved", "<u8")], align=False)
+VORBIS_STREAM_RESULT = np.dtype([("packets_ok", "<u4"), ("first_bad_status", "<u4"), ("samples", "<u8"), ("reserved", "<u8")], align=False)
+assert VORBIS_INFO.itemsize == 32 and VORBIS_STREAM_DESC.itemsize == 64 and VORBIS_PACKET_RESULT.itemsize == 24 and VORBIS_STREAM_RESULT.itemsize == 24
+
+
 class OhGpuError(RuntimeError):
     def __init__(self, code, message):
         super().__init__(f"ohgpu error {code}: {message}")
@@ -498,7 +524,7 @@ def lib():
         raise ImportError(f"{LIB_PATH} is missing: build the HIP extension first (python ohpipeline_amd/build.py); "
                           "there is no CPU fallback for the product path")
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(CENC_SYMBOLS.items()) + list(RAOP_RX_SYMBOLS.items()) + list(TS_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(CENC_SYMBOLS.items()) + list(RAOP_RX_SYMBOLS.items()) + list(TS_SYMBOLS.items()) + list(VORBIS_SYMBOLS.items()):
         fn = getattr(L, name)          # AttributeError here = the library does not export what ohgpu.h declares
         fn.restype = res
         fn.argtypes = args
@@ -705,6 +731,48 @@ def _typed(descs, dtype):
     d = np.ascontiguousarray(descs)
     assert d.dtype == dtype
     return d
+
+
+def vorbis_setup_parse(id_packet, setup_packet):
+    """The setup image of a stream's identification and setup header packets (ohgpu_vorbis_setup_parse; host only): (image as uint8, info)."""
+    a, b = bytes(id_packet), bytes(setup_packet)
+    info = np.zeros(1, dtype=VORBIS_INFO)
+    check(lib().ohgpu_vorbis_setup_parse(a, len(a), b, len(b), None, 0, info.ctypes.data))
+    image = np.zeros(int(info["image_bytes"][0]), dtype=np.uint8)
+    check(lib().ohgpu_vorbis_setup_parse(a, len(a), b, len(b), image.ctypes.data, image.size, info.ctypes.data))
+    return image, info[0]
+
+
+def vorbis_head(data):
+    """The head of an Ogg Vorbis stream (ohgpu_vorbis_head; host only): dict(image, info, serial, page_offset, segment, seq) -- where the
+    first audio packet begins."""
+    raw = bytes(data)
+    info = np.zeros(1, dtype=VORBIS_INFO)
+    serial, seg, seq, off = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+    check(lib().ohgpu_vorbis_head(raw, len(raw), None, 0, info.ctypes.data, C.byref(serial), C.byref(off), C.byref(seg), C.byref(seq)))
+    image = np.zeros(int(info["image_bytes"][0]), dtype=np.uint8)
+    check(lib().ohgpu_vorbis_head(raw, len(raw), image.ctypes.data, image.size, info.ctypes.data, C.byref(serial), C.byref(off), C.byref(seg), C.byref(seq)))
+    return dict(image=image, info=info[0], serial=int(serial.value), page_offset=int(off.value), segment=int(seg.value), seq=int(seq.value))
+
+
+def vorbis_codewords(lengths):
+    """The codewords of a list of lengths, 0 for an unused entry (ohgpu_vorbis_codewords; host only)."""
+    l = np.ascontiguousarray(lengths, dtype=np.uint8)
+    out = np.zeros(l.size, dtype=np.uint32)
+    check(lib().ohgpu_vorbis_codewords(_ptr_or_none(l), l.size, _ptr_or_none(out)))
+    return out
+
+
+def _vorbis_tables(descs, packets, images):
+    d, p, im = np.ascontiguousarray(descs), np.ascontiguousarray(packets), np.ascontiguousarray(images)
+    assert d.dtype == VORBIS_STREAM_DESC and p.dtype == ALAC_PACKET and im.dtype == np.uint8
+    return d, p, im
+
+
+def vorbis_batch_check(descs, packets, images, src_arena_bytes, dst_arena_bytes):
+    """The validation of ctx.vorbis_batch without a device (ohgpu_vorbis_batch_check): OhGpuError on a bad descriptor."""
+    d, p, im = _vorbis_tables(descs, packets, images)
+    check(lib().ohgpu_vorbis_batch_check(_ptr_or_none(d), d.size, _ptr_or_none(p), p.size, _ptr_or_none(im), im.size, src_arena_bytes, dst_arena_bytes))
 
 
 def ts_batch_check(descs, n_pes, src_arena_bytes, dst_arena_bytes):
@@ -1019,6 +1087,7 @@ class Context:
         out["iff_route"] = out["alac_route"]
         out["dsd_file_route"] = out["alac_route"]
         out["raop_rx_route"] = out["alac_route"]
+        out["vorbis_route"] = out["alac_route"]
         return out
 
     def pcm_process_host(self, descs, src, dst):
@@ -1309,6 +1378,60 @@ class Context:
                                                     _ptr_or_none(dst), dst.nbytes, _ptr_or_none(sres), _ptr_or_none(recs), _ptr_or_none(rows),
                                                     _ptr_or_none(ares), _ptr_or_none(pres)))
         return sres, recs, rows, ares, pres
+
+    def vorbis_batch(self, descs, packets, images, src_arena_bytes, dst_arena_bytes):
+        d, p, im = _vorbis_tables(descs, packets, images)
+        b = C.c_void_p()
+        check(lib().ohgpu_vorbis_batch_create(self._h, _ptr_or_none(d), d.size, _ptr_or_none(p), p.size, _ptr_or_none(im), im.size, src_arena_bytes, dst_arena_bytes, C.byref(b)))
+        return b
+
+    def vorbis_run(self, batch, d_src, d_dst, stream=None):
+        """Head, entropy, synthesis, store (ohgpu_vorbis_batch_run): queued on the stream."""
+        check(lib().ohgpu_vorbis_batch_run(self._h, batch, d_src, d_dst, stream))
+
+    def vorbis_results(self, batch, n, n_packets):
+        """The last run's (VORBIS_STREAM_RESULT per stream, VORBIS_PACKET_RESULT per packet); waits for the run."""
+        res, pres = np.zeros(n, dtype=VORBIS_STREAM_RESULT), np.zeros(n_packets, dtype=VORBIS_PACKET_RESULT)
+        check(lib().ohgpu_vorbis_batch_results(self._h, batch, _ptr_or_none(res), n, _ptr_or_none(pres), n_packets))
+        return res, pres
+
+    def vorbis_phase_ms(self, batch):
+        """(head, entropy, synthesis, store) of the last run in milliseconds."""
+        ms = (C.c_float * 4)()
+        check(lib().ohgpu_vorbis_batch_phase_ms(self._h, batch, ms))
+        return tuple(float(v) for v in ms)
+
+    def vorbis_paths(self, batch):
+        """{route, blocks} of a Vorbis batch (ohgpu_vorbis_batch_paths)."""
+        route, blocks = C.c_uint32(0), C.c_uint32(0)
+        check(lib().ohgpu_vorbis_batch_paths(batch, C.byref(route), C.byref(blocks)))
+        return dict(route=int(route.value), blocks=int(blocks.value))
+
+    def vorbis_spectrum(self, batch, packet, channel, n_values):
+        """The float32 spectrum the last run transformed for one packet and channel (ohgpu_vorbis_batch_spectrum)."""
+        out = np.zeros(n_values, dtype=np.float32)
+        check(lib().ohgpu_vorbis_batch_spectrum(self._h, batch, packet, channel, _ptr_or_none(out), n_values))
+        return out
+
+    def vorbis_process_host(self, descs, packets, images, src, dst):
+        """Host buffers in and out (ohgpu_vorbis_process_host); returns (stream results, packet results)."""
+        d, p, im = _vorbis_tables(descs, packets, images)
+        res, pres = np.zeros(d.size, dtype=VORBIS_STREAM_RESULT), np.zeros(p.size, dtype=VORBIS_PACKET_RESULT)
+        check(lib().ohgpu_vorbis_process_host(self._h, _ptr_or_none(d), d.size, _ptr_or_none(p), p.size, _ptr_or_none(im), im.size, _ptr_or_none(src), src.nbytes,
+                                              _ptr_or_none(dst), dst.nbytes, _ptr_or_none(res), _ptr_or_none(pres)))
+        return res, pres
+
+    def ogg_vorbis_process_host(self, ogg_descs, vorbis_descs, n_packets, images, src, mid_bytes, dst):
+        """Ogg bytes to PCM (ohgpu_ogg_vorbis_process_host); returns (Ogg results, Ogg packet table, Vorbis stream results, packet results
+        indexed as the Ogg table)."""
+        o = _ogg_descs(ogg_descs)
+        v, im = np.ascontiguousarray(vorbis_descs), np.ascontiguousarray(images)
+        assert v.dtype == VORBIS_STREAM_DESC and v.size == o.size and im.dtype == np.uint8
+        ores, orecs = np.zeros(o.size, dtype=OGG_STREAM_RESULT), np.zeros(n_packets, dtype=OGG_PACKET)
+        sres, pres = np.zeros(o.size, dtype=VORBIS_STREAM_RESULT), np.zeros(n_packets, dtype=VORBIS_PACKET_RESULT)
+        check(lib().ohgpu_ogg_vorbis_process_host(self._h, _ptr_or_none(o), _ptr_or_none(v), o.size, n_packets, _ptr_or_none(im), im.size, _ptr_or_none(src), src.nbytes,
+                                                  mid_bytes, _ptr_or_none(dst), dst.nbytes, _ptr_or_none(ores), _ptr_or_none(orecs), _ptr_or_none(sres), _ptr_or_none(pres)))
+        return ores, orecs, sres, pres
 
     def ts_batch(self, descs, n_pes, src_arena_bytes, dst_arena_bytes):
         d = _typed(descs, TS_STREAM_DESC)

@@ -318,8 +318,9 @@ static const struct { const char* noun; void (*release)(ohgpu_ctx*, ohgpu_batch*
     {"a RAOP receiver", free_state<&ohgpu_batch::raoprx>, false},   // kBatchRaopRx
     {"a transport stream", free_state<&ohgpu_batch::ts>, false},   // kBatchTs
     {"an ADTS", free_state<&ohgpu_batch::adts>, false},   // kBatchAdts
+    {"a Vorbis", free_state<&ohgpu_batch::vorbis>, false},   // kBatchVorbis
 };
-static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchAdts + 1, "a row per BatchKind");
+static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchVorbis + 1, "a row per BatchKind");
 
 int run_guard(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, BatchKind kind, bool empty, bool null_src_ok,
               const void* src_base, const void* dst_base, bool needs_dst)
@@ -636,6 +637,10 @@ int ohgpu_batch_paths_info(const ohgpu_batch* b, ohgpu_batch_paths* out)
     }
     if (b->kind == kBatchDsdFile) {
         out->dsd_file_route = b->file && b->file->plain ? 2u : 1u;
+        return OHGPU_OK;
+    }
+    if (b->kind == kBatchVorbis) {
+        out->vorbis_route = b->vorbis && b->vorbis->plain ? 2u : 1u;
         return OHGPU_OK;
     }
     if (b->kind == kBatchRaopRx) {

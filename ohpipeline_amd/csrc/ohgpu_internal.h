@@ -29,6 +29,7 @@
 #include "raop_aes_core.h"
 #include "cenc_core.h"
 #include "ts_packet_core.h"
+#include "vorbis_core.h"
 
 namespace ohgpu {
 
@@ -629,7 +630,32 @@ static_assert(sizeof(ohgpu_dsd_file_stream_desc) == sizeof(dsdfile::Stream) && s
               dsdfile::kDsf == OHGPU_DSD_DSF && dsdfile::kDff == OHGPU_DSD_DFF && dsdfile::kDsf == OHGPU_DSD_FILE_KIND_DSF && dsdfile::kDff == OHGPU_DSD_FILE_KIND_DFF &&
               dsdfile::kFillByte == OHGPU_DSD_SILENCE_BYTE && dsdfile::kMaxChunks == OHGPU_DSD_FILE_MAX_CHUNKS, "DSD file layouts");
 
-enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11, kBatchOhmRx = 12, kBatchOgg = 13, kBatchMp4 = 14, kBatchIff = 15, kBatchDsdFile = 16, kBatchMp4f = 17, kBatchCenc = 18, kBatchRaopRx = 19, kBatchTs = 20, kBatchAdts = 21 };
+// ---- Vorbis packets (csrc/vorbis_kernel.hip): the descriptors and the table, the setup images as the caller gave them,
+// the transform's tables by block size, the records and floors of the last run, and the scratch: a spectrum row and a windowed block per
+// packet and channel, and the entropy phase's classification bytes.  The batch's d_descs holds nothing.
+struct VorbisTab { uint32_t a, b, w, slope, cos8; };  // where the tables of one block size begin in d_tables, in floats (cos8: the plain route's)
+struct VorbisState : RunState {
+    std::vector<vorbiscore::Stream> streams;
+    std::vector<vorbiscore::Packet> packets;
+    bool     plain = false;                           // created under kernel variant 1: the direct-form transform
+    uint32_t max_channels = 0, max_block = 0;
+    VorbisTab tabs[14] = {};                          // by log2 of the block size
+    void* d_images = nullptr;                         // uint32: the images' blob
+    void* d_streams = nullptr;                        // vorbiscore::Stream[n]
+    void* d_packets = nullptr;                        // vorbiscore::Packet[n_packets]
+    void* d_recs = nullptr;                           // vorbiscore::Rec[n_packets]
+    void* d_floors = nullptr;                         // vorbiscore::FloorOut[n_packets][kMaxChannels]
+    void* d_rows = nullptr; size_t rows_bytes = 0;    // float: per stream, packet and channel a row of bs1 / 2
+    void* d_blocks = nullptr;                         // float: ... and a block of bs1
+    void* d_cls = nullptr;                            // uint8: per packet its stream's class_bytes
+    void* d_tables = nullptr;                         // float: the dB table (256), then the sizes' tables
+};
+static_assert(sizeof(ohgpu_vorbis_stream_desc) == 64 && sizeof(ohgpu_vorbis_packet_result) == sizeof(vorbiscore::Rec) && sizeof(ohgpu_vorbis_stream_result) == 24 &&
+              sizeof(ohgpu_vorbis_info) == 32 && offsetof(ohgpu_vorbis_packet_result, position) == offsetof(vorbiscore::Rec, position) &&
+              offsetof(ohgpu_vorbis_packet_result, reserved) == offsetof(vorbiscore::Rec, prev_block) && vorbiscore::kMaxCoupling == OHGPU_VORBIS_MAX_COUPLING_STEPS &&
+              vorbiscore::kMaxImageBytes == OHGPU_VORBIS_MAX_IMAGE_BYTES && vorbiscore::kMaxClassBytes == OHGPU_VORBIS_MAX_CLASS_BYTES, "Vorbis layouts");
+
+enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11, kBatchOhmRx = 12, kBatchOgg = 13, kBatchMp4 = 14, kBatchIff = 15, kBatchDsdFile = 16, kBatchMp4f = 17, kBatchCenc = 18, kBatchRaopRx = 19, kBatchTs = 20, kBatchAdts = 21, kBatchVorbis = 22 };
 
 }  // namespace ohgpu
 
@@ -745,6 +771,7 @@ struct ohgpu_batch {
     ohgpu::RaopRxState* raoprx = nullptr;   // kBatchRaopRx only
     ohgpu::TsState* ts = nullptr;       // kBatchTs only
     ohgpu::AdtsState* adts = nullptr;   // kBatchAdts only
+    ohgpu::VorbisState* vorbis = nullptr;   // kBatchVorbis only
     void*    d_pull_tiles = nullptr;   // kBatchSrcPull: PullTile[n_pull_tiles] on the device (d_descs holds the messages)
     uint32_t n_pull_tiles = 0;
     // kBatchSrc whose messages differ in layout: one uniform batch per layout (each with its own block-kernel plan), run one
@@ -845,6 +872,10 @@ int  ts_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* d
 uint32_t ts_wave_blocks(uint64_t tiles, uint32_t cus);   // the gather launch's size: the rule tests/test_gpu_ts_textbook.py restates
 int  adts_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const adts::Stream* streams);
 int  adts_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, hipStream_t s);
+// csrc/vorbis_kernel.hip.  No launch is persistent: a lane a packet (head, entropy), a lane a stream (the positions), a workgroup a packet
+// and channel (synthesis), a workgroup 256 samples of a packet (store).
+int  vorbis_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const void* images, uint64_t images_bytes);   // b->vorbis->streams / packets are filled
+int  vorbis_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
 // csrc/ogg_page_kernel.hip
 int  ogg_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const oggpage::Stream* streams);   // tiles, lists and result arrays onto the device (b->ogg holds the counts)
 int  ogg_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
