@@ -880,7 +880,29 @@ int ohgpu_ohm_rx_process_host(ohgpu_ctx* ctx, const ohgpu_ohm_rx_stream* streams
  *      last whole page, resume_segment 0 and next_seq the last accepted number plus 1.  On a stop status bytes_consumed is the
  *      offset of the page the walk stopped at (for the mapping's two, the page the header packet ended on), and what completed
  *      before it is delivered.  A later call with (src_offset + bytes_consumed, expect_seq = next_seq, first_page_segment =
- *      resume_segment) delivers exactly what one call over the whole range would have delivered behind that point. */
+ *      resume_segment) delivers exactly what one call over the whole range would have delivered behind that point.
+ * Chained streams (an Icecast mount: every track a new logical stream with its own serial, headers and granule positions).  With
+ * OHGPU_OGG_FOLLOW_LINKS the descriptor's `link` holds a magic of 0 ... 8 bytes ("\x01vorbis", "\x7fFLAC"; length 0 matches any
+ * body), rules 1-7 stand, and rule 3 has one exception:
+ *   L1. a whole page with a good CRC and version 0 begins a link when its serial is not the followed one, it has the "first page"
+ *       flag, its body begins with the magic, and the followed serial's last accepted page of this call, if there is one, did not
+ *       have the "first page" flag (so the opening group of a multiplexed stream, BOS A, BOS B, ..., is no chain).  The link before
+ *       it needs no "last page" flag.  A foreign first page that fails any of these is counted and passed over by rule 3.
+ *   L2. at a link a packet still open is dropped, neither delivered nor counted; the followed serial becomes the page's; the page
+ *       may carry any number and every later page one more (rule 4); rule 5's first_page_segment no longer applies; the first
+ *       packet that begins in the new link gets OHGPU_OGG_PACKET_LINK, and OHGPU_OGG_PACKET_BOS by its own rule; with
+ *       OHGPU_OGG_FLAC_MAPPING the new link's mapping header is stripped by rule 6 as any other.
+ *   L3. the result's `serial` is the serial followed at the end and `links` counts the links taken, whether or not their packets
+ *       were recorded.  last_granule, bos_seen and eos_seen are over every link.
+ *   L4. rule 7 holds: a later call with serial = the result's serial, the flag and the same magic delivers what one call would
+ *       have.  For that, a link none of whose packets has completed where the range ends (status OK) is left for the later call
+ *       to take: the result is that of a range which ends in front of the link's first page (bytes_consumed that page's offset,
+ *       resume_segment 0, next_seq, serial, pages, pages_ignored, bos_seen, eos_seen and links as they were there).  The known
+ *       exception: a range that ends exactly between two first pages of one opening group that both match the magic -- the later
+ *       call has not seen the first of them and takes the second for a link.
+ *   L5. a link that reuses the serial being followed is not a link: its first page is a page of that serial and fails rule 4 with
+ *       HOLE (or, with the number that happens to follow, is accepted as the stream's next page).
+ * Without the flag nothing above applies and the reserved words must be zero. */
 #define OHGPU_OGG_OK                   0u
 #define OHGPU_OGG_LOST_SYNC            1u
 #define OHGPU_OGG_HOLE                 2u
@@ -890,9 +912,16 @@ int ohgpu_ohm_rx_process_host(ohgpu_ctx* ctx, const ohgpu_ohm_rx_stream* streams
 #define OHGPU_OGG_ANY_SEQ        1u
 #define OHGPU_OGG_FLAC_MAPPING   2u
 #define OHGPU_OGG_ANY_SERIAL     4u
+#define OHGPU_OGG_FOLLOW_LINKS   16u  /* rules L1-L5 (8 is not a flag) */
 #define OHGPU_OGG_PACKET_BOS             1u   /* it starts with the first segment of a page that has the "first page" flag */
 #define OHGPU_OGG_PACKET_EOS             2u   /* it contains the last segment of a page that has the "last page" flag */
 #define OHGPU_OGG_PACKET_MAPPING_HEADER  4u   /* the mapping's first header: `bytes` is what is left of it without its first 9 */
+#define OHGPU_OGG_PACKET_LINK            8u   /* the first packet that begins in a link taken by rule L1 */
+
+typedef struct ohgpu_ogg_link_magic {   /* 12 bytes */
+    uint32_t bytes;                 /* 0 ... 8; 0 matches any body */
+    uint8_t  magic[8];              /* zero beyond `bytes` */
+} ohgpu_ogg_link_magic;
 
 typedef struct ohgpu_ogg_stream_desc {   /* 64 bytes */
     uint64_t src_offset;            /* the stream's bytes are [src_offset, + src_bytes) of the source arena, any address */
@@ -904,8 +933,11 @@ typedef struct ohgpu_ogg_stream_desc {   /* 64 bytes */
     uint32_t packet_first;          /* the stream's records are [packet_first, + packet_capacity) of the batch's packet table; */
     uint32_t packet_capacity;       /*   packets beyond the capacity are counted, not recorded.  0: no records */
     uint32_t first_page_segment;    /* rule 5's r, <= 255 */
-    uint32_t flags;                 /* OHGPU_OGG_ANY_SEQ | _FLAC_MAPPING | _ANY_SERIAL */
-    uint32_t reserved[3];
+    uint32_t flags;                 /* OHGPU_OGG_ANY_SEQ | _FLAC_MAPPING | _ANY_SERIAL | _FOLLOW_LINKS */
+    union {
+        uint32_t reserved[3];       /* without OHGPU_OGG_FOLLOW_LINKS: zero */
+        ohgpu_ogg_link_magic link;  /* with it: what the body of a link's first page begins with */
+    };
 } ohgpu_ogg_stream_desc;
 
 typedef struct ohgpu_ogg_stream_result {   /* 64 bytes */
@@ -918,10 +950,13 @@ typedef struct ohgpu_ogg_stream_result {   /* 64 bytes */
     uint32_t resume_segment;
     uint32_t next_seq;
     int64_t  last_granule;          /* the last granule position other than -1 that a delivered packet got (-1: none) */
-    uint32_t serial;                /* the stream's: the descriptor's, or the first whole page's */
+    uint32_t serial;                /* the stream's: the descriptor's, or the first whole page's; with links, the one followed at the end */
     uint8_t  bos_seen, eos_seen;    /* an accepted page had the "first page" / "last page" flag */
     uint8_t  reserved[2];
-    uint64_t reserved2;
+    union {
+        uint64_t reserved2;         /* the high half is zero */
+        uint32_t links;             /* its low half: rule L3 (0 without OHGPU_OGG_FOLLOW_LINKS) */
+    };
 } ohgpu_ogg_stream_result;
 
 typedef struct ohgpu_ogg_packet {   /* 40 bytes */
@@ -934,8 +969,8 @@ typedef struct ohgpu_ogg_packet {   /* 40 bytes */
     uint32_t segment;               /* ... and the segment */
 } ohgpu_ogg_packet;
 
-/* Host only, no device needed: the validation ohgpu_ogg_batch_create makes.  OHGPU_ERR_INVALID: non-zero reserved words, unknown
- * flags, src_bytes >= 2^31, first_page_segment > 255, packet ranges that overlap or run past the table of n_packets records.
+/* Host only, no device needed: the validation ohgpu_ogg_batch_create makes.  OHGPU_ERR_INVALID: non-zero reserved words without
+ * OHGPU_OGG_FOLLOW_LINKS, with it a magic longer than 8 bytes or non-zero bytes beyond its length, unknown flags, src_bytes >= 2^31, first_page_segment > 255, packet ranges that overlap or run past the table of n_packets records.
  * OHGPU_ERR_BOUNDS: a range outside its arena, dst_capacity < src_bytes.  The empty batch is legal. */
 int ohgpu_ogg_batch_check(const ohgpu_ogg_stream_desc* descs, size_t n, size_t n_packets, uint64_t src_arena_bytes, uint64_t dst_arena_bytes);
 /* The descriptors go to the device; lists, bitmap, plan, packet table and results are the batch's.  Freed with ohgpu_batch_destroy. */

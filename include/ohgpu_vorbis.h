@@ -128,6 +128,46 @@ int ohgpu_ogg_vorbis_process_host(ohgpu_ctx* ctx, const ohgpu_ogg_stream_desc* o
                                   void* dst_host, uint64_t dst_bytes, ohgpu_ogg_stream_result* ogg_results, ohgpu_ogg_packet* packets,
                                   ohgpu_vorbis_stream_result* stream_results, ohgpu_vorbis_packet_result* packet_results);
 
+/* ---- chained Ogg Vorbis (an Icecast mount: every track a link with its own serial, headers, channel count, rate and granule positions).
+ * One row per link of a stream that ohgpu_ogg_vorbis_links_process_host met, in stream order and then link order. */
+#define OHGPU_VORBIS_LINK_CONTINUED  0xffffffffffffffffull   /* page_offset of the link the call began in */
+#define OHGPU_VORBIS_LINK_HEAD_OPEN  1                        /* head: the range ends inside the link's three header packets */
+typedef struct ohgpu_vorbis_link {          /* 64 bytes */
+    uint32_t stream;                        /* the descriptor's index */
+    uint32_t serial;                        /* the link's (the continued link's: of the page its first packet began on, else the descriptor's) */
+    uint64_t page_offset;                   /* of the link's first page, from the stream's src_offset; OHGPU_VORBIS_LINK_CONTINUED */
+    uint32_t first_packet, n_packets;       /* the link's rows in the Ogg packet table, its header packets included */
+    int32_t  head;                          /* OHGPU_OK; ohgpu_vorbis_head's error code; OHGPU_VORBIS_LINK_HEAD_OPEN.  Not OK: nothing of the link is decoded */
+    uint32_t channels, sample_rate;         /* what the link's identification header says (the continued link's: its image) */
+    uint32_t blocksize_short, blocksize_long;
+    uint32_t reserved;
+    uint64_t dst_offset;                    /* where the link's samples lie */
+    uint64_t samples;                       /* a channel, written */
+} ohgpu_vorbis_link;
+/* Chained Ogg Vorbis from host buffers, shaped as ohgpu_ogg_vorbis_process_host: one upload, the Ogg batch with OHGPU_OGG_FOLLOW_LINKS
+ * and the magic "\x01vorbis" (set here on a copy of ogg_descs[i] unless the descriptor has the flag already), the one small read.  Then,
+ * on the host, a stream's packet records are cut at OHGPU_OGG_PACKET_LINK; each new link's head is parsed from the source bytes
+ * (ohgpu_vorbis_head at the record's page_offset) into an image in the call's own blob; every link becomes one Vorbis descriptor, and ONE
+ * Vorbis batch runs over all of them.
+ *   vorbis_descs[i] describes the link the call begins in (its image, dst_offset, flags, and max_samples as a further bound on that link);
+ *   first_packet, n_packets and dst_plane_stride are replaced.  dst_capacity_bytes[i] bounds the stream's whole region
+ *   [dst_offset, + dst_capacity_bytes[i]), which lies inside the destination.
+ *   Links lie in link order in the region, without overlap, each at a multiple of 4.  A link is sized before the run as n_packets x
+ *   blocksize_long / 2 samples a channel; one that no longer fits gets what is left, in whole frames, as its max_samples, and every later
+ *   link 0 -- the rows' samples say so.  With OHGPU_VORBIS_OUT_PLANAR32 a link's plane stride is its bound x 4.
+ *   By V3 the first OK packet of each link primes and delivers nothing: nothing overlaps across links, which is the specification's rule.
+ *   A link whose range ends inside its headers (fewer than three packets, the stream's status OK, no link behind it) has head
+ *   OHGPU_VORBIS_LINK_HEAD_OPEN: the caller sends it again from its page_offset when more bytes are there.  Give a stream a packet_capacity
+ *   for all its packets: a link is seen by its record.  A link NONE of whose packets is whole -- its first page has come, or a part of
+ *   it, and the identification packet does not end in the range -- has no row at all, by the Ogg layer's rule L4: the stream's
+ *   bytes_consumed stops at that page, its serial and links are those in front of it, and the later call finds the link.
+ * links has room for links_capacity rows; *n_links is the true count (n rows at least: every stream has its continued link, with no
+ * packets when the range begins at a link's first page).  packet_results as ohgpu_ogg_vorbis_process_host's.  Any result pointer may be NULL. */
+int ohgpu_ogg_vorbis_links_process_host(ohgpu_ctx* ctx, const ohgpu_ogg_stream_desc* ogg_descs, const ohgpu_vorbis_stream_desc* vorbis_descs, const uint64_t* dst_capacity_bytes,
+                                        size_t n, size_t n_packets, const void* images, uint64_t images_bytes, const void* src_host, uint64_t src_bytes, uint64_t mid_bytes,
+                                        void* dst_host, uint64_t dst_bytes, ohgpu_ogg_stream_result* ogg_results, ohgpu_ogg_packet* packets,
+                                        ohgpu_vorbis_link* links, size_t links_capacity, size_t* n_links, ohgpu_vorbis_packet_result* packet_results);
+
 #ifdef __cplusplus
 }
 #endif

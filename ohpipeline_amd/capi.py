@@ -146,14 +146,18 @@ OHM_RX_STREAM_RESULT = np.dtype(_OHM_RX_STATE + [("out_bytes", "<u8"), ("n_outpu
 assert OHM_RX_DATAGRAM.itemsize == 16 and OHM_RX_STREAM.itemsize == 64 and OHM_RX_RECORD.itemsize == 104 and OHM_RX_STREAM_RESULT.itemsize == 136
 # Ogg pages: a descriptor and a result per stream, a record per completed packet
 OGG_OK, OGG_LOST_SYNC, OGG_HOLE, OGG_NOT_FLAC, OGG_UNSUPPORTED_MAPPING, OGG_BAD_RESUME = range(6)
-OGG_ANY_SEQ, OGG_FLAC_MAPPING, OGG_ANY_SERIAL = 1, 2, 4
-OGG_PACKET_BOS, OGG_PACKET_EOS, OGG_PACKET_MAPPING_HEADER = 1, 2, 4
+OGG_ANY_SEQ, OGG_FLAC_MAPPING, OGG_ANY_SERIAL, OGG_FOLLOW_LINKS = 1, 2, 4, 16
+OGG_PACKET_BOS, OGG_PACKET_EOS, OGG_PACKET_MAPPING_HEADER, OGG_PACKET_LINK = 1, 2, 4, 8
 OGG_STREAM_DESC = np.dtype([("src_offset", "<u8"), ("dst_offset", "<u8"), ("dst_capacity", "<u8"), ("src_bytes", "<u4"), ("serial", "<u4"),
                             ("expect_seq", "<u4"), ("packet_first", "<u4"), ("packet_capacity", "<u4"), ("first_page_segment", "<u4"),
                             ("flags", "<u4"), ("reserved", "<u4", (3,))], align=False)
 OGG_STREAM_RESULT = np.dtype([("status", "<u4"), ("pages", "<u4"), ("pages_ignored", "<u4"), ("packets", "<u4"), ("bytes_delivered", "<u8"),
                               ("bytes_consumed", "<u8"), ("resume_segment", "<u4"), ("next_seq", "<u4"), ("last_granule", "<i8"),
                               ("serial", "<u4"), ("bos_seen", "u1"), ("eos_seen", "u1"), ("reserved", "u1", (2,)), ("reserved2", "<u8")], align=False)
+# The other members of the two structs' unions, for .view(): the link magic where `reserved` is, `links` in the low half of `reserved2`
+OGG_STREAM_DESC_LINKS = np.dtype(OGG_STREAM_DESC.descr[:-1] + [("link_magic_bytes", "<u4"), ("link_magic", "u1", (8,))], align=False)
+OGG_STREAM_RESULT_LINKS = np.dtype(OGG_STREAM_RESULT.descr[:-1] + [("links", "<u4"), ("reserved2_high", "<u4")], align=False)
+assert OGG_STREAM_DESC_LINKS.itemsize == 64 and OGG_STREAM_RESULT_LINKS.itemsize == 64
 OGG_PACKET = np.dtype([("run_pos", "<u8"), ("bytes", "<u4"), ("flags", "<u4"), ("granule", "<i8"), ("page_offset", "<u8"),
                        ("page_seq", "<u4"), ("segment", "<u4")], align=False)
 assert OGG_STREAM_DESC.itemsize == 64 and OGG_STREAM_RESULT.itemsize == 64 and OGG_PACKET.itemsize == 40
@@ -494,6 +498,8 @@ VORBIS_SYMBOLS = {
     "ohgpu_vorbis_head": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, _vp, _u32p, C.POINTER(C.c_uint64), _u32p, _u32p]),
     "ohgpu_ogg_vorbis_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
     "ohgpu_vorbis_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
+    "ohgpu_ogg_vorbis_links_process_host": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp,
+                                                      _vp, C.c_size_t, C.POINTER(C.c_size_t), _vp]),
 }
 VORBIS_OK, VORBIS_HEADER, VORBIS_CORRUPT = 0, 1, 2
 VORBIS_OUT_PLANAR32 = 1
@@ -504,6 +510,12 @@ VORBIS_STREAM_DESC = np.dtype([("image_offset", "<u8"), ("dst_offset", "<u8"), (
 VORBIS_PACKET_RESULT = np.dtype([("status", "u1"), ("mode", "u1"), ("blocksize", "<u2"), ("samples", "<u4"), ("position", "<u8"), ("reserved", "<u8")], align=False)
 VORBIS_STREAM_RESULT = np.dtype([("packets_ok", "<u4"), ("first_bad_status", "<u4"), ("samples", "<u8"), ("reserved", "<u8")], align=False)
 assert VORBIS_INFO.itemsize == 32 and VORBIS_STREAM_DESC.itemsize == 64 and VORBIS_PACKET_RESULT.itemsize == 24 and VORBIS_STREAM_RESULT.itemsize == 24
+# a link of a chained Ogg Vorbis stream (ohgpu_vorbis_link)
+VORBIS_LINK_CONTINUED, VORBIS_LINK_HEAD_OPEN = 0xFFFFFFFFFFFFFFFF, 1
+VORBIS_LINK = np.dtype([("stream", "<u4"), ("serial", "<u4"), ("page_offset", "<u8"), ("first_packet", "<u4"), ("n_packets", "<u4"), ("head", "<i4"),
+                        ("channels", "<u4"), ("sample_rate", "<u4"), ("blocksize_short", "<u4"), ("blocksize_long", "<u4"), ("reserved", "<u4"),
+                        ("dst_offset", "<u8"), ("samples", "<u8")], align=False)
+assert VORBIS_LINK.itemsize == 64
 
 
 class OhGpuError(RuntimeError):
@@ -1432,6 +1444,24 @@ class Context:
         check(lib().ohgpu_ogg_vorbis_process_host(self._h, _ptr_or_none(o), _ptr_or_none(v), o.size, n_packets, _ptr_or_none(im), im.size, _ptr_or_none(src), src.nbytes,
                                                   mid_bytes, _ptr_or_none(dst), dst.nbytes, _ptr_or_none(ores), _ptr_or_none(orecs), _ptr_or_none(sres), _ptr_or_none(pres)))
         return ores, orecs, sres, pres
+
+    def ogg_vorbis_links_process_host(self, ogg_descs, vorbis_descs, dst_capacity_bytes, n_packets, images, src, mid_bytes, dst, links_capacity=None):
+        """Chained Ogg bytes to PCM (ohgpu_ogg_vorbis_links_process_host); returns (Ogg results, Ogg packet table, the link rows -- all of
+        them unless links_capacity says how many there is room for, then (rows, true count) --, packet results indexed as the Ogg table)."""
+        o = _ogg_descs(ogg_descs)
+        v, im = np.ascontiguousarray(vorbis_descs), np.ascontiguousarray(images)
+        caps = np.ascontiguousarray(dst_capacity_bytes, dtype="<u8")
+        assert v.dtype == VORBIS_STREAM_DESC and v.size == o.size == caps.size and im.dtype == np.uint8
+        ores, orecs = np.zeros(o.size, dtype=OGG_STREAM_RESULT), np.zeros(n_packets, dtype=OGG_PACKET)
+        pres = np.zeros(n_packets, dtype=VORBIS_PACKET_RESULT)
+        room = o.size + n_packets if links_capacity is None else links_capacity
+        links, count = np.zeros(room, dtype=VORBIS_LINK), C.c_size_t(0)
+        check(lib().ohgpu_ogg_vorbis_links_process_host(self._h, _ptr_or_none(o), _ptr_or_none(v), _ptr_or_none(caps), o.size, n_packets, _ptr_or_none(im), im.size,
+                                                        _ptr_or_none(src), src.nbytes, mid_bytes, _ptr_or_none(dst), dst.nbytes, _ptr_or_none(ores), _ptr_or_none(orecs),
+                                                        _ptr_or_none(links), room, C.byref(count), _ptr_or_none(pres)))
+        if links_capacity is None:
+            return ores, orecs, links[:count.value].copy(), pres
+        return ores, orecs, (links, count.value), pres
 
     def ts_batch(self, descs, n_pes, src_arena_bytes, dst_arena_bytes):
         d = _typed(descs, TS_STREAM_DESC)

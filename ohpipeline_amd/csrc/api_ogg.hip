@@ -11,8 +11,13 @@ namespace {
 
 int ogg_check_desc(const ohgpu_ogg_stream_desc& d, size_t i, size_t n_packets, uint64_t src_arena_bytes, uint64_t dst_arena_bytes)
 {
-    for (uint32_t r : d.reserved) if (r) return set_error(OHGPU_ERR_INVALID, "ogg desc %zu: reserved words must be zero", i);
     if (d.flags & ~(uint32_t)oggpage::kKnownFlags) return set_error(OHGPU_ERR_INVALID, "ogg desc %zu: unknown flags 0x%x", i, d.flags);
+    if (d.flags & OHGPU_OGG_FOLLOW_LINKS) {
+        if (d.link.bytes > (uint32_t)oggpage::kMaxMagicBytes) return set_error(OHGPU_ERR_INVALID, "ogg desc %zu: a link magic of %u bytes where 8 is the most", i, d.link.bytes);
+        for (uint32_t k = d.link.bytes; k < (uint32_t)oggpage::kMaxMagicBytes; k++)
+            if (d.link.magic[k]) return set_error(OHGPU_ERR_INVALID, "ogg desc %zu: the link magic has a non-zero byte beyond its %u bytes", i, d.link.bytes);
+    } else
+        for (uint32_t r : d.reserved) if (r) return set_error(OHGPU_ERR_INVALID, "ogg desc %zu: reserved words must be zero", i);
     if (d.src_bytes >= 0x80000000u) return set_error(OHGPU_ERR_INVALID, "ogg desc %zu: src_bytes %u is 2^31 or more", i, d.src_bytes);
     if (d.first_page_segment > 255u) return set_error(OHGPU_ERR_INVALID, "ogg desc %zu: first_page_segment %u where a page has at most 255 segments", i, d.first_page_segment);
     if (d.packet_capacity && (d.packet_first > n_packets || d.packet_capacity > n_packets - d.packet_first))

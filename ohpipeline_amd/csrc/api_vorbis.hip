@@ -296,4 +296,153 @@ int ohgpu_ogg_vorbis_process_host(ohgpu_ctx* ctx, const ohgpu_ogg_stream_desc* o
     return OHGPU_OK;
 }
 
+int ohgpu_ogg_vorbis_links_process_host(ohgpu_ctx* ctx, const ohgpu_ogg_stream_desc* ogg_descs, const ohgpu_vorbis_stream_desc* vorbis_descs, const uint64_t* dst_capacity_bytes,
+                                        size_t n, size_t n_packets, const void* images, uint64_t images_bytes, const void* src_host, uint64_t src_bytes, uint64_t mid_bytes,
+                                        void* dst_host, uint64_t dst_bytes, ohgpu_ogg_stream_result* ogg_results, ohgpu_ogg_packet* packets,
+                                        ohgpu_vorbis_link* links, size_t links_capacity, size_t* n_links, ohgpu_vorbis_packet_result* packet_results)
+{
+    const char* const who = "ohgpu_ogg_vorbis_links_process_host";
+    if (n_links) *n_links = 0;
+    if (n && (!ogg_descs || !vorbis_descs || !dst_capacity_bytes || !images)) return set_error(OHGPU_ERR_INVALID, "%s: null argument", who);
+    if (links_capacity && !links) return set_error(OHGPU_ERR_INVALID, "%s: null argument", who);
+    if (images_bytes % 4 != 0) return set_error(OHGPU_ERR_INVALID, "%s: %llu bytes of images (whole words)", who, (unsigned long long)images_bytes);
+    std::vector<ohgpu_ogg_stream_desc> odescs(ogg_descs, ogg_descs + n);
+    for (size_t i = 0; i < n; i++) {
+        ohgpu_ogg_stream_desc& o = odescs[i];
+        if (o.flags & OHGPU_OGG_FLAC_MAPPING) return set_error(OHGPU_ERR_INVALID, "%s: stream %zu: the Ogg FLAC mapping in front of the Vorbis decoder", who, i);
+        if (!(o.flags & OHGPU_OGG_FOLLOW_LINKS)) {                      // (a caller's own magic stays; without the flag the words were to be zero)
+            for (uint32_t r : o.reserved) if (r) return set_error(OHGPU_ERR_INVALID, "%s: stream %zu: reserved words must be zero", who, i);
+            o.flags |= OHGPU_OGG_FOLLOW_LINKS;
+            o.link.bytes = 7;
+            memcpy(o.link.magic, "\x01vorbis", 7);
+        }
+        const vorbiscore::Image* im = nullptr;
+        OHGPU_TRY(vorbis_check_image(i, vorbis_descs[i], images, images_bytes, &im));
+        if (vorbis_descs[i].dst_offset % 4 != 0) return set_error(OHGPU_ERR_INVALID, "%s: stream %zu: dst_offset must be a multiple of 4", who, i);
+        OHGPU_TRY(arena_span("vorbis links stream", i, "writes", vorbis_descs[i].dst_offset, dst_capacity_bytes[i], dst_bytes, "destination"));
+    }
+    std::vector<ohgpu_ogg_stream_result> ores(n);
+    std::vector<ohgpu_ogg_packet> orecs(n_packets);
+    std::vector<ohgpu_vorbis_link> rows_out;                          // the link rows, stream by stream
+    std::vector<size_t> link_desc;                                     // per link row: its descriptor in vdescs, or SIZE_MAX (not decoded)
+    std::vector<ohgpu_vorbis_stream_desc> vdescs;
+    std::vector<uint8_t> blob((const uint8_t*)images, (const uint8_t*)images + (n ? images_bytes : 0));   // the caller's images, then the links'
+    std::vector<ohgpu_alac_packet> rows;
+    std::vector<size_t> row_record;
+    std::vector<ohgpu_vorbis_stream_result> sres;
+    std::vector<ohgpu_vorbis_packet_result> pres;
+    void* d_mid = nullptr;
+    const int err = decoder_process_host(ctx, who, src_host, src_bytes, dst_host, dst_bytes,
+        [&](ohgpu_batch** b) { return ohgpu_ogg_batch_create(ctx, odescs.data(), n, n_packets, src_bytes, mid_bytes, b); },
+        [&](const ohgpu_batch* b, const void* d_src, void* d_dst) {
+            if (!n) return (int)OHGPU_OK;
+            OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &d_mid, mid_bytes ? mid_bytes : 1));
+            int e = ohgpu_ogg_batch_run(ctx, b, d_src, d_mid, nullptr);
+            if (e == OHGPU_OK) e = ohgpu_ogg_batch_results(ctx, b, ores.data(), n);             // the one small read between the layers
+            if (e == OHGPU_OK) e = ohgpu_ogg_batch_packets(ctx, b, n_packets ? orecs.data() : nullptr, n_packets);
+            if (e != OHGPU_OK) return e;
+            for (size_t i = 0; i < n; i++) {
+                const ohgpu_ogg_stream_desc& o = odescs[i];
+                const ohgpu_vorbis_stream_desc& v0 = vorbis_descs[i];
+                const uint8_t* const bytes = (const uint8_t*)src_host + o.src_offset;
+                const uint32_t count = std::min(ores[i].packets, o.packet_capacity);
+                const ohgpu_ogg_packet* recs = orecs.data() + o.packet_first;
+                const bool planes = (v0.flags & OHGPU_VORBIS_OUT_PLANAR32) != 0;
+                uint64_t cursor = v0.dst_offset;
+                const uint64_t region_end = v0.dst_offset + dst_capacity_bytes[i];
+                bool full = false;
+                std::vector<uint32_t> cut{0u};                         // link j's records are [cut[j], cut[j + 1]); the continued link may have none
+                for (uint32_t k = 0; k < count; k++) {
+                    if (recs[k].page_offset > o.src_bytes || o.src_bytes - recs[k].page_offset < (uint64_t)oggpage::kHeaderBytes)
+                        return set_error(OHGPU_ERR_DEVICE, "%s: stream %zu: packet record %u begins outside the stream", who, i, k);
+                    if (recs[k].flags & OHGPU_OGG_PACKET_LINK) cut.push_back(k);
+                }
+                cut.push_back(count);
+                for (size_t link = 0; link + 1 < cut.size(); link++) {
+                    const uint32_t k0 = cut[link], k1 = cut[link + 1], link_packets = k1 - k0;
+                    ohgpu_vorbis_link row;
+                    memset(&row, 0, sizeof(row));
+                    row.stream = (uint32_t)i; row.first_packet = o.packet_first + k0; row.n_packets = link_packets;
+                    ohgpu_vorbis_stream_desc d = v0;
+                    if (link == 0) {
+                        const vorbiscore::Image& im = *(const vorbiscore::Image*)((const uint8_t*)images + v0.image_offset);
+                        row.serial = link_packets ? oggpage::le32(bytes + recs[k0].page_offset + 14) : o.serial;
+                        row.page_offset = OHGPU_VORBIS_LINK_CONTINUED; row.head = OHGPU_OK;
+                        row.channels = im.channels; row.sample_rate = im.rate; row.blocksize_short = im.bs0; row.blocksize_long = im.bs1;
+                    } else {
+                        row.page_offset = recs[k0].page_offset;
+                        row.serial = oggpage::le32(bytes + row.page_offset + 14);
+                        // the link's bytes end where the next link's first page begins; its head, on the page its fourth packet begins on
+                        uint64_t end = k1 < count ? recs[k1].page_offset : o.src_bytes;
+                        if (link_packets > 3) {
+                            oggpage::Page pg;
+                            const uint64_t at = recs[k0 + 3].page_offset;
+                            if (oggpage::parse_page(bytes + at, (uint32_t)(o.src_bytes - at), &pg) == 1) end = at + pg.bytes;
+                        }
+                        ohgpu_vorbis_info info;
+                        uint32_t serial = 0, seg = 0, seq = 0;
+                        uint64_t audio = 0;
+                        const bool open = link_packets < 3 && k1 == count && ores[i].status == OHGPU_OGG_OK;
+                        int head = open ? (int)OHGPU_VORBIS_LINK_HEAD_OPEN : ohgpu_vorbis_head(bytes + row.page_offset, end - row.page_offset, nullptr, 0, &info, &serial, &audio, &seg, &seq);
+                        if (head == OHGPU_OK) {
+                            const size_t at = blob.size();
+                            blob.resize(at + info.image_bytes);
+                            head = ohgpu_vorbis_head(bytes + row.page_offset, end - row.page_offset, blob.data() + at, info.image_bytes, &info, &serial, &audio, &seg, &seq);
+                            d.image_offset = at; d.image_bytes = info.image_bytes;
+                            row.channels = info.channels; row.sample_rate = info.sample_rate; row.blocksize_short = info.blocksize_short; row.blocksize_long = info.blocksize_long;
+                        }
+                        row.head = head;
+                    }
+                    // the link's place in the stream's region: sized before the run, cut to what is left, nothing behind a link that was cut
+                    row.dst_offset = cursor;
+                    size_t mine = SIZE_MAX;
+                    if (row.head == OHGPU_OK) {
+                        const uint64_t frame = (uint64_t)row.channels * (planes ? 4u : 2u);
+                        uint64_t bound = (uint64_t)link_packets * (row.blocksize_long / 2u);
+                        if (link == 0) bound = std::min<uint64_t>(bound, v0.max_samples);
+                        const uint64_t left = full || cursor >= region_end ? 0 : (region_end - cursor) / frame;
+                        if (bound > left) { bound = left; full = true; }
+                        if (bound && link_packets) {
+                            d.dst_offset = cursor; d.max_samples = bound; d.dst_plane_stride = planes ? bound * 4u : 0u;
+                            d.first_packet = (uint32_t)rows.size(); d.n_packets = link_packets;
+                            for (uint32_t k = k0; k < k1; k++) {
+                                rows.push_back(ohgpu_alac_packet{o.dst_offset + recs[k].run_pos, recs[k].bytes, 0u});
+                                row_record.push_back(o.packet_first + k);
+                            }
+                            mine = vdescs.size();
+                            vdescs.push_back(d);
+                            cursor += (bound * frame + 3u) & ~(uint64_t)3u;
+                        }
+                    }
+                    rows_out.push_back(row);
+                    link_desc.push_back(mine);
+                }
+            }
+            pres.resize(rows.size());
+            sres.resize(vdescs.size());
+            if (vdescs.empty()) return (int)OHGPU_OK;
+            ohgpu_batch* vb = nullptr;
+            e = ohgpu_vorbis_batch_create(ctx, vdescs.data(), vdescs.size(), rows.data(), rows.size(), blob.data(), blob.size(), mid_bytes, dst_bytes, &vb);
+            if (e != OHGPU_OK) return e;
+            const BatchPtr own(vb, BatchDeleter{ctx});
+            e = ohgpu_vorbis_batch_run(ctx, vb, d_mid, d_dst, nullptr);                       // one batch over every link of every stream
+            if (e == OHGPU_OK) e = ohgpu_vorbis_batch_results(ctx, vb, sres.data(), sres.size(), pres.data(), pres.size());
+            return e;
+        },
+        [&] { return vorbis_download_written(ctx, who, vdescs.data(), vdescs.size(), blob.data(), sres.data(), dst_host); });
+    if (d_mid) { (void)hipStreamSynchronize(ctx->stream); ctx_dev_free(ctx, d_mid); }
+    if (err != OHGPU_OK) return err;
+    for (size_t k = 0; k < rows_out.size(); k++)
+        if (link_desc[k] != SIZE_MAX) rows_out[k].samples = sres[link_desc[k]].samples;
+    if (n_links) *n_links = rows_out.size();
+    if (links) memcpy(links, rows_out.data(), std::min(rows_out.size(), links_capacity) * sizeof(rows_out[0]));
+    if (ogg_results && n) memcpy(ogg_results, ores.data(), n * sizeof(ores[0]));
+    if (packets && n_packets) memcpy(packets, orecs.data(), n_packets * sizeof(orecs[0]));
+    if (packet_results && n_packets) {
+        memset(packet_results, 0, n_packets * sizeof(*packet_results));
+        for (size_t k = 0; k < pres.size(); k++) packet_results[row_record[k]] = pres[k];
+    }
+    return OHGPU_OK;
+}
+
 }  // extern "C"

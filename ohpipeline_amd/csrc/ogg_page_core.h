@@ -21,6 +21,9 @@
 //              the packet records, the result, and the gather plan: pieces, each a run of body bytes that goes to the delivered run
 //              as it lies.  A page gives one piece, and one more for every mapping header in it.  Only completed packets are
 //              delivered: when the walk ends inside a packet, the pieces are cut back to where that packet began (truncate()).
+//              With kFollowLinks it also follows a chained stream from one logical stream into the next (rules L1 ... L5 there): a
+//              first page of another serial whose body begins with the descriptor's magic makes that serial the followed one, the
+//              packet still open is cut away as at the end of a range, and the link's first packet is flagged.
 //   gather     a piece is copied by csrc/ohm_rx_core.h's gather_lane: both ends at any byte address.
 #pragma once
 
@@ -36,16 +39,17 @@ namespace oggpage {
 
 enum { kHeaderBytes = 27, kMaxPageBytes = 27 + 255 + 255 * 255, kMappingHeaderBytes = 9 };
 enum Status : uint32_t { kOk = 0, kLostSync = 1, kHole = 2, kNotFlac = 3, kUnsupportedMapping = 4, kBadResume = 5 };
-enum { kAnySeq = 1, kFlacMapping = 2, kAnySerial = 4, kKnownFlags = 7 };
+enum { kAnySeq = 1, kFlacMapping = 2, kAnySerial = 4, kFollowLinks = 16, kKnownFlags = 23 };
 enum { kPageContinued = 1, kPageBos = 2, kPageEos = 4 };
-enum { kPacketBos = 1, kPacketEos = 2, kPacketMappingHeader = 4 };
+enum { kPacketBos = 1, kPacketEos = 2, kPacketMappingHeader = 4, kPacketLink = 8 };
+enum { kMaxMagicBytes = 8 };
 constexpr uint32_t kPoly = 0x04c11db7u;
 constexpr uint32_t kLanes = 64, kSliceMin = 16;       // a page's slices: one a lane, none shorter than kSliceMin but the last
 
 struct Stream {               // 64 bytes = ohgpu_ogg_stream_desc
     uint64_t src_offset, dst_offset, dst_capacity;
     uint32_t src_bytes, serial, expect_seq, packet_first, packet_capacity, first_page_segment, flags;
-    uint32_t reserved[3];
+    uint32_t reserved[3];     // with kFollowLinks the link magic: [0] its length (0 ... 8), the eight bytes of [1] and [2] as they lie the magic
 };
 struct Result {               // 64 bytes = ohgpu_ogg_stream_result
     uint32_t status, pages, pages_ignored, packets;
@@ -54,7 +58,7 @@ struct Result {               // 64 bytes = ohgpu_ogg_stream_result
     int64_t  last_granule;
     uint32_t serial;
     uint8_t  bos_seen, eos_seen, reserved[2];
-    uint64_t reserved2;
+    uint32_t links, reserved2;
 };
 struct Packet {               // 40 bytes = ohgpu_ogg_packet
     uint64_t run_pos;         // of its first delivered byte, from the stream's dst_offset
@@ -180,6 +184,15 @@ OGGP_HD bool page_good(const uint32_t* bits, uint64_t bit_base, uint32_t pos, bo
     return overflowed && crc_run(t->byte, page, 0, bytes) == stored_crc(page);
 }
 
+// The link magic: `len` bytes, byte k the k-th byte in memory of the two words (lo first)
+OGGP_HD bool begins_with(const uint8_t* body, uint32_t body_bytes, uint32_t len, uint32_t lo, uint32_t hi)
+{
+    if (body_bytes < len) return false;
+    for (uint32_t k = 0; k < len; k++)
+        if (body[k] != (((k < 4u ? lo >> (8u * k) : hi >> (8u * (k - 4u)))) & 0xffu)) return false;
+    return true;
+}
+
 // ---- the walk over one stream.
 struct Walker {
     const uint8_t* base;      // the stream's first byte
@@ -189,6 +202,7 @@ struct Walker {
     uint32_t n_packets, n_pieces, delivered;
     uint32_t cur_src, cur_run, cur_len;                               // the piece being made
     bool     open;                                                    // a packet has begun and not ended
+    bool     link_pending;                                            // a link began and none of its packets has
     uint32_t pk_page, pk_seq, pk_seg, pk_run, pk_bytes, pk_flags, pk_verdict, pk_piece, pk_cut;
 
     OGGP_HD void flush()
@@ -219,7 +233,8 @@ struct Walker {
         if (!open) {
             open = true;
             pk_page = page_pos; pk_seq = page_seq; pk_seg = seg; pk_run = delivered; pk_bytes = 0;
-            pk_flags = first_of_bos_page ? (uint32_t)kPacketBos : 0u;
+            pk_flags = (first_of_bos_page ? (uint32_t)kPacketBos : 0u) | (link_pending ? (uint32_t)kPacketLink : 0u);
+            link_pending = false;
             pk_verdict = kOk;
             if ((flags & kFlacMapping) && v > 0 && base[at] == 0x7f) {
                 const uint8_t* h = base + at;
@@ -255,7 +270,8 @@ OGGP_HD uint32_t piece_capacity(const Stream& s)
     // 27 bytes a page and 10 a mapping header (its nine bytes and a lacing value): a page gives a piece and every header one more
     return s.src_bytes / 27u + 1u + ((s.flags & kFlacMapping) ? s.src_bytes / 10u + 1u : 0u);
 }
-template <typename Good>
+// Links = false is the walk without rules L1 ... L5 in its text: what a batch none of whose streams has kFollowLinks runs.
+template <bool Links = true, typename Good>
 OGGP_HD void walk(const Stream& s, uint32_t stream_index, const uint8_t* src, Packet* packet_table, Piece* pieces, Good& good, Result* out, uint32_t* n_pieces)
 {
     Walker w;
@@ -265,13 +281,19 @@ OGGP_HD void walk(const Stream& s, uint32_t stream_index, const uint8_t* src, Pa
     w.stream_index = stream_index; w.packet_cap = s.packet_capacity; w.piece_cap = piece_capacity(s); w.flags = s.flags;
     w.n_packets = w.n_pieces = w.delivered = 0;
     w.cur_src = w.cur_run = w.cur_len = 0;
-    w.open = false;
+    w.open = w.link_pending = false;
     w.pk_page = w.pk_seq = w.pk_seg = w.pk_run = w.pk_bytes = w.pk_flags = w.pk_verdict = w.pk_piece = w.pk_cut = 0;
 
     uint32_t p = 0, status = kOk, serial = s.serial, expect = s.expect_seq, pages = 0, ignored = 0;
     bool serial_known = !(s.flags & kAnySerial), seq_known = !(s.flags & kAnySeq), first = true;
     uint8_t bos_seen = 0, eos_seen = 0;
     int64_t last_granule = -1;
+    // the links (rules L1 ... L5): how many, and whether the followed serial's last accepted page had the "first page" flag.  What
+    // the result was in front of the last link is kept in *out, where nothing else is written before the end: a link is rare, and
+    // the walk without one should not carry that in registers.
+    const bool follow = Links && (s.flags & kFollowLinks) != 0;
+    uint32_t links = 0;
+    bool last_bos = false;
     for (;;) {
         Page pg;
         const uint8_t* page = w.base + p;
@@ -279,7 +301,17 @@ OGGP_HD void walk(const Stream& s, uint32_t stream_index, const uint8_t* src, Pa
         if (whole == 0) break;
         if (whole < 0 || !good(p, page, pg.bytes)) { status = kLostSync; break; }
         if (!serial_known) { serial = pg.serial; serial_known = true; }
-        if (pg.serial != serial || pg.version != 0) { ignored++; p += pg.bytes; continue; }
+        if (pg.serial != serial || pg.version != 0) {
+            const bool link = follow && pg.version == 0 && pg.serial != serial && (pg.flags & kPageBos) && !last_bos &&
+                              begins_with(page + pg.header_bytes, pg.bytes - pg.header_bytes, s.reserved[0], s.reserved[1], s.reserved[2]);
+            if (!link) { ignored++; p += pg.bytes; continue; }
+            if (w.open) w.truncate();                                 // L2: the packet still open is dropped
+            out->bytes_consumed = p; out->serial = serial; out->next_seq = expect; out->pages = pages; out->pages_ignored = ignored;
+            out->packets = w.n_packets; out->bos_seen = bos_seen; out->eos_seen = eos_seen;
+            serial = pg.serial; seq_known = false; first = false;
+            links++;
+            w.link_pending = true;
+        }
         if (seq_known && pg.seq != expect) { status = kHole; break; }
         const uint8_t* lace = page + kHeaderBytes;
         uint32_t seg = 0, at = p + pg.header_bytes;
@@ -297,6 +329,7 @@ OGGP_HD void walk(const Stream& s, uint32_t stream_index, const uint8_t* src, Pa
             }
         }
         first = false; seq_known = true; expect = pg.seq + 1u; pages++;
+        last_bos = (pg.flags & kPageBos) != 0;
         if (pg.flags & kPageBos) bos_seen = 1;
         if (pg.flags & kPageEos) eos_seen = 1;
         const bool eos = (pg.flags & kPageEos) != 0;
@@ -321,6 +354,12 @@ OGGP_HD void walk(const Stream& s, uint32_t stream_index, const uint8_t* src, Pa
         if (status == kOk) { consumed = w.pk_page; resume = w.pk_seg; next_seq = w.pk_seq; }
         w.truncate();
     }
+    if (links && status == kOk && w.n_packets == out->packets) {      // L4: the last link is the next call's to find
+        consumed = (uint32_t)out->bytes_consumed; resume = 0; next_seq = out->next_seq;
+        serial = out->serial; pages = out->pages; ignored = out->pages_ignored;
+        bos_seen = out->bos_seen; eos_seen = out->eos_seen;
+        links--;
+    }
     w.flush();
     out->status = status; out->pages = pages; out->pages_ignored = ignored; out->packets = w.n_packets;
     out->bytes_delivered = w.delivered; out->bytes_consumed = consumed;
@@ -328,7 +367,7 @@ OGGP_HD void walk(const Stream& s, uint32_t stream_index, const uint8_t* src, Pa
     out->last_granule = last_granule;
     out->serial = serial;
     out->bos_seen = bos_seen; out->eos_seen = eos_seen; out->reserved[0] = out->reserved[1] = 0;
-    out->reserved2 = 0;
+    out->links = links; out->reserved2 = 0;
     *n_pieces = w.n_pieces;
 }
 

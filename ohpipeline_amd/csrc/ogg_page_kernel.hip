@@ -8,7 +8,8 @@
 //            copied to LDS once a workgroup.  A lane runs its slice of the page through the byte table, shifts it to the page's end
 //            with two multiplications, the wave xors the 64 terms (crc_lane), and lane 0 sets the position's bit when the sum is
 //            the stored checksum.  Pages of one stream are verified side by side: nothing here knows which page follows which.
-//   chain    a lane per stream: the walk.  Latency-bound by construction; it is there so that the gather needs no host in front of
+//   chain    a lane per stream: the walk (two instances: with the chained-stream rules for a batch that has a stream asking for them,
+//            and without them in its text for every other batch, which so runs what it ran before those rules were written).  Latency-bound by construction; it is there so that the gather needs no host in front of
 //            it.  At its end the lane takes its pieces' places in the dense work list with one atomic add.
 //   gather   a wave per piece of the work list, persistent like verify, the count read from the device: ohmrx::gather_lane.
 // Every load lies inside a stream's range, which ohgpu_ogg_batch_check placed inside the source arena (gather_lane may read back to
@@ -68,6 +69,7 @@ __global__ __launch_bounds__(kOggThreads) void ogg_verify_kernel(const Stream* _
     }
 }
 
+template <bool Links>
 __global__ __launch_bounds__(64) void ogg_chain_kernel(const Stream* __restrict__ streams, uint32_t n, const uint64_t* __restrict__ bit_base, const uint64_t* __restrict__ piece_first,
                                                        const uint8_t* __restrict__ src, const uint32_t* __restrict__ bits, uint32_t cap, uint32_t* __restrict__ counters,
                                                        const Tables* __restrict__ tables, Packet* __restrict__ packets, Piece* __restrict__ pieces, uint32_t* __restrict__ work,
@@ -80,7 +82,7 @@ __global__ __launch_bounds__(64) void ogg_chain_kernel(const Stream* __restrict_
     const uint64_t my_bits = bit_base[i], my_pieces = piece_first[i];
     auto good = [&](uint32_t pos, const uint8_t* page, uint32_t bytes) { return page_good(bits, my_bits, pos, overflowed, tables, page, bytes); };
     uint32_t n_pieces = 0;
-    walk(s, i, src, packets, pieces + my_pieces, good, &results[i], &n_pieces);
+    walk<Links>(s, i, src, packets, pieces + my_pieces, good, &results[i], &n_pieces);
     if (!n_pieces) return;
     const uint32_t at = atomicAdd(&counters[1], n_pieces);
     for (uint32_t k = 0; k < n_pieces; k++) work[at + k] = (uint32_t)my_pieces + k;
@@ -119,6 +121,7 @@ int ogg_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Stream* streams)
         for (uint32_t pos = 0; pos + kHeaderBytes <= s.src_bytes; pos += kFindTile) tiles.push_back(OggTile{(uint32_t)i, pos});
         bit_base[i] = bits;
         piece_first[i] = pieces;
+        g.follow_links = g.follow_links || (s.flags & kFollowLinks) != 0;
         bits += ((uint64_t)s.src_bytes + 31u) & ~(uint64_t)31u;
         pieces += piece_capacity(s);
         cands += s.src_bytes / 27u + 1u;
@@ -165,7 +168,7 @@ int ogg_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* d
         OHGPU_HIP_TRY_ALLOC(hipGetLastError());
     }
     OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[2], s));
-    hipLaunchKernelGGL(ogg_chain_kernel, dim3((ns + 63u) / 64u), dim3(64), 0, s, (const Stream*)g.d_streams, ns, (const uint64_t*)g.d_bit_base, (const uint64_t*)g.d_piece_first, src,
+    hipLaunchKernelGGL(g.follow_links ? ogg_chain_kernel<true> : ogg_chain_kernel<false>, dim3((ns + 63u) / 64u), dim3(64), 0, s, (const Stream*)g.d_streams, ns, (const uint64_t*)g.d_bit_base, (const uint64_t*)g.d_piece_first, src,
                        (const uint32_t*)g.d_bits, g.cand_cap, (uint32_t*)g.d_counters, (const Tables*)g.d_tables, (Packet*)g.d_packets, (Piece*)g.d_pieces, (uint32_t*)g.d_work,
                        (Result*)g.d_results);
     OHGPU_HIP_TRY_ALLOC(hipGetLastError());

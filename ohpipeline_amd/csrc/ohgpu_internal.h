@@ -512,6 +512,7 @@ struct OggState : RunState {
     size_t n_streams = 0, n_packets = 0;
     uint32_t n_tiles = 0, cand_cap = 0, piece_cap = 0;
     size_t bits_bytes = 0;
+    bool follow_links = false;                        // a stream has OHGPU_OGG_FOLLOW_LINKS: the chain launch is the instance that follows them
     void* d_streams = nullptr;                        // oggpage::Stream[n_streams]
     void* d_results = nullptr;                        // oggpage::Result[n_streams]
     void* d_bit_base = nullptr;                       // uint64[n_streams]: the stream's first bit in d_bits

@@ -9,7 +9,8 @@ the run written once -- as a fraction of the copy ceiling for the same bytes in 
 tools/micro/run_copy as a child process before this process opens the device; `--copy-tbps` takes a figure by hand); the verify
 phase's source bytes per second on its own.  Every stream's run is checked against the packets' bytes.  `--host-leg`:
 tools/ogg_host_cpu.cpp, this project's own core on `--host-threads` CPU threads (walk, serial checksums, memcpy) -- a host pass a
-caller no longer makes, not the reference's library.
+caller no longer makes, not the reference's library.  `--links`: every stream is that input twice, the second copy under a serial of
+its own -- a chain of two links --, walked with OHGPU_OGG_FOLLOW_LINKS and the magic "\x7fFLAC".
 Fused leg: `--lanes` lanes, each one fixture once as Ogg FLAC from its first audio page, through ohgpu_ogg_flac_process_host, beside
 ohgpu_flac_process_host over the same frames in native framing, alternating, host clock round each call (both end in a wait); the
 PCM of both must be equal (`--lanes 0` leaves the leg out, for a counter run).  One JSON line.
@@ -54,19 +55,22 @@ def host_leg(one, n_streams, threads):
     return int(delivered), float(ms)
 
 
-def one_stream(fixture, repeat, segments):
+def one_stream(fixture, repeat, segments, links=False):
     import flac_cases as FC
     import ogg_cases as GC
     fx = FC.fixture(fixture)
     packets, _, n_meta = GC.flac_packets(fx)
     audio = packets[n_meta:] * repeat
-    pages = GC.mux(packets[:1], 0x464C, 0, eos=False) + GC.mux(packets[1:n_meta] + audio, 0x464C, 1, max_segments=segments, bos=False)
-    return b"".join(pages), b"fLaC" + b"".join(packets[:n_meta])[13:] + b"".join(audio)
+    pages, run = [], b""
+    for serial in (0x464C, 0x464D)[:2 if links else 1]:
+        pages += GC.mux(packets[:1], serial, 0, eos=False) + GC.mux(packets[1:n_meta] + audio, serial, 1, max_segments=segments, bos=False)
+        run += b"fLaC" + b"".join(packets[:n_meta])[13:] + b"".join(audio)
+    return b"".join(pages), run
 
 
 def demux_leg(ctx, args):
     from ohpipeline_amd import capi
-    one, run = one_stream(args.fixture, args.repeat, args.segments)
+    one, run = one_stream(args.fixture, args.repeat, args.segments, args.links)
     n, size = args.streams, len(one)
     slot = (size + 255) // 256 * 256 + 48                             # (streams at different alignments mod 16 and mod 256)
     src = np.zeros(n * slot, dtype=np.uint8)
@@ -76,6 +80,10 @@ def demux_leg(ctx, args):
         src[a:a + size] = np.frombuffer(one, dtype=np.uint8)
         descs[i]["src_offset"], descs[i]["src_bytes"], descs[i]["dst_offset"], descs[i]["dst_capacity"] = a, size, i * slot + (i * 5) % 16, size
         descs[i]["serial"], descs[i]["flags"] = 0x464C, capi.OGG_FLAC_MAPPING
+        if args.links:
+            descs[i]["flags"] |= capi.OGG_FOLLOW_LINKS
+            magic = descs[i:i + 1].view(capi.OGG_STREAM_DESC_LINKS)
+            magic["link_magic_bytes"], magic["link_magic"][0, :5] = 5, np.frombuffer(b"\x7fFLAC", dtype=np.uint8)
     capi.ogg_batch_check(descs, 0, src.size, src.size)
     d_src, d_dst = ctx.upload(src), ctx.malloc(src.size)
     b = ctx.ogg_batch(descs, 0, src.size, src.size)
@@ -98,13 +106,14 @@ def demux_leg(ctx, args):
         ctx.free(d_dst)
     want = np.frombuffer(run, dtype=np.uint8)
     ok = bool(np.all(res["status"] == capi.OGG_OK) and np.all(res["bytes_delivered"] == want.size))
+    ok = ok and bool(np.all(res.view(capi.OGG_STREAM_RESULT_LINKS)["links"] == (1 if args.links else 0)))
     for i in range(n):
         o = int(descs[i]["dst_offset"])
         ok = ok and np.array_equal(got[o:o + want.size], want)
     ms = np.median(np.array(phases[args.warmup:]), axis=0)
     moved = n * (size + want.size)
     tbps = moved / (float(ms.sum()) * 1e-3) / 1e12
-    out = dict(streams=n, stream_bytes=size, source_mb=round(n * size / 1e6, 1), pages=int(res["pages"].sum()), packets=int(res["packets"].sum()),
+    out = dict(streams=n, links_followed=bool(args.links), stream_bytes=size, source_mb=round(n * size / 1e6, 1), pages=int(res["pages"].sum()), packets=int(res["packets"].sum()),
                find_ms=round(float(ms[0]), 4), verify_ms=round(float(ms[1]), 4), chain_ms=round(float(ms[2]), 4), gather_ms=round(float(ms[3]), 4),
                run_and_results_ms=round(float(np.median(walls[args.warmup:])), 4), algorithmic_tbps=round(tbps, 4),
                frac_of_copy=round(tbps / args.copy_tbps, 4) if args.copy_tbps else None,
@@ -160,12 +169,13 @@ def main():
     ap.add_argument("--copy-tbps", type=float, default=0.0)
     ap.add_argument("--run-copy", action="store_true")
     ap.add_argument("--host-leg", action="store_true")
+    ap.add_argument("--links", action="store_true")
     ap.add_argument("--host-threads", type=int, default=16)
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     from ohpipeline_amd import capi
     if args.run_copy:
-        one, run = one_stream(args.fixture, args.repeat, args.segments)
+        one, run = one_stream(args.fixture, args.repeat, args.segments, args.links)
         args.copy_tbps = copy_ceiling(args.streams * (len(one) + len(run)) // 2)
     with capi.Context(0) as ctx:
         result = dict(bench="ogg", device=ctx.name(), copy_ceiling_tbps=args.copy_tbps or None, demux=demux_leg(ctx, args), ogg_flac=fused_leg(ctx, args) if args.lanes else None)

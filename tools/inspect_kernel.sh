@@ -2,12 +2,20 @@
 # Compiles csrc/src_block_kernel.hip to assembly, prints register/spill/instruction statistics of the
 # S24LE->S24BE stereo instantiation (the headline kernel) and checks the invariant its hand-counted LDS waits
 # rely on: no scalar memory instruction between the first and the last tap of the main loop (scalar loads share
-# lgkmcnt with LDS operations and complete out of order).  Usage: bash tools/inspect_kernel.sh
+# lgkmcnt with LDS operations and complete out of order).  Usage: bash tools/inspect_kernel.sh [ogg]
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 B=$R/ohpipeline_amd/build
 mkdir -p "$B"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -I $R/include"
+# `bash tools/inspect_kernel.sh ogg`: the register and scratch figures of csrc/ogg_page_kernel.hip's kernels instead (find, verify, both
+# instances of chain, gather), from the compiler's metadata.
+if [ "$1" = ogg ]; then
+  /opt/rocm/bin/hipcc $FLAGS -S --cuda-device-only "$R/ohpipeline_amd/csrc/ogg_page_kernel.hip" -o "$B/ogg.s" 2>/dev/null
+  grep -E "^ +\.(name|sgpr_count|sgpr_spill_count|vgpr_count|vgpr_spill_count|private_segment_fixed_size):" "$B/ogg.s" | paste - - - - - - | \
+    sed -E 's/ +/ /g; s/\.name: _ZN5ohgpu[0-9]+(ogg_[a-z]+_kernel)(ILb([01])E)?[A-Za-z0-9_]*/\1<\3>/'
+  exit 0
+fi
 /opt/rocm/bin/hipcc $FLAGS -S --cuda-device-only "$R/ohpipeline_amd/csrc/src_block_kernel.hip" -o "$B/sbk.s" 2>&1 | grep -E "error|warning: loop" || true
 K=_ZN5ohgpu16src_block_kernelILi32ELi2ELi3ELb1ELi3ELb0ELb0EE
 awk -v k="$K" 'index($0, k) == 1 {f=1} f{print} /s_endpgm/{if(f)exit}' "$B/sbk.s" > "$B/k.s"
