@@ -1780,5 +1780,6 @@ int ohgpu_set_kernel_variant(ohgpu_ctx* ctx, int variant);
 #include "ohgpu_raop_rx.h"
 #include "ohgpu_ts.h"
 #include "ohgpu_vorbis.h"
+#include "ohgpu_cbcs.h"
 
 #endif /* OHGPU_H */

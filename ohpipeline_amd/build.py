@@ -14,7 +14,7 @@ HIP_SOURCES = ["ohgpu_api.hip", "pcm_kernels.hip", "pcm_line_kernel.hip", "flywh
 PARTED = ("src_lean_kernel.hip",)     # compiled once per part of the instantiation list (csrc/src_block_common.h)
 HEADERS = ["ohgpu_internal.h", "pcm_device.h", os.path.join(ROOT, "include", "ohgpu.h"), os.path.join(ROOT, "include", "ohgpu_cenc.h"),
            os.path.join(ROOT, "include", "ohgpu_raop_rx.h"), os.path.join(ROOT, "include", "ohgpu_ts.h"),
-           os.path.join(ROOT, "include", "ohgpu_vorbis.h")]
+           os.path.join(ROOT, "include", "ohgpu_vorbis.h"), os.path.join(ROOT, "include", "ohgpu_cbcs.h")]
 # Per-source flags.  The lean kernel's per-frame control flow is wave-uniform (scalar compares); LLVM's structurizer
 # rewrites uniform diamonds into flag-and-test chains unless told to leave uniform regions alone (3-4 scalar instructions
 # per input frame in a loop the scalar unit co-limits).
@@ -124,6 +124,7 @@ def build_host(force=False, verbose=False):
     hdrs.append(os.path.join(ROOT, "include", "ohgpu_raop_rx.h"))
     hdrs.append(os.path.join(ROOT, "include", "ohgpu_ts.h"))
     hdrs.append(os.path.join(ROOT, "include", "ohgpu_vorbis.h"))
+    hdrs.append(os.path.join(ROOT, "include", "ohgpu_cbcs.h"))
     if not force and os.path.exists(HOST_LIB_PATH):
         t = os.path.getmtime(HOST_LIB_PATH)
         if all(os.path.getmtime(f) <= t for f in srcs + hdrs) and os.path.getmtime(LIB_PATH) <= t:

@@ -195,6 +195,12 @@ CENC_STREAM_DESC = np.dtype(MP4F_STREAM_DESC.descr + [("key_flags", "<u4"), ("re
 CENC_STREAM_RESULT = np.dtype([("mp4f", MP4F_STREAM_RESULT), ("entry", "<u4"), ("scheme", "<u4"), ("is_protected", "u1"), ("iv_size", "u1"), ("pad", "u1", (2,)),
                                ("reserved", "<u4"), ("kid", "u1", (16,)), ("blocks", "<u8")], align=False)
 assert CENC_STREAM_DESC.itemsize == 112 and CENC_STREAM_RESULT.itemsize == 208
+# protected fragmented MPEG-4, the second family: ohgpu_cbcs_stream_desc (120 B), ohgpu_cbcs_stream_result (232 B); the statuses are CENC's
+CBCS_SCHEME_CENC, CBCS_SCHEME_CBCS = 0x63656e63, 0x63626373
+CBCS_STREAM_DESC = np.dtype(CENC_STREAM_DESC.descr + [("subsample_first", "<u4"), ("subsample_capacity", "<u4")], align=False)
+CBCS_STREAM_RESULT = np.dtype([("cenc", CENC_STREAM_RESULT), ("crypt_blocks", "u1"), ("skip_blocks", "u1"), ("constant_iv_size", "u1"), ("pad", "u1"),
+                               ("subsamples", "<u4"), ("constant_iv", "u1", (16,))], align=False)
+assert CBCS_STREAM_DESC.itemsize == 120 and CBCS_STREAM_RESULT.itemsize == 232
 # PCM files: ohgpu_iff_stream_desc (64 B), ohgpu_iff_stream_result (80 B)
 IFF_OK, IFF_NOT_IFF, IFF_TRUNCATED, IFF_INVALID, IFF_UNSUPPORTED = range(5)
 IFF_KIND_WAV, IFF_KIND_AIFF, IFF_KIND_AIFC = 1, 2, 3
@@ -484,6 +490,24 @@ assert TS_STREAM_DESC.itemsize == 64 and TS_STREAM_RESULT.itemsize == 64 and TS_
 assert ADTS_STREAM_DESC.itemsize == 32 and ADTS_STREAM_RESULT.itemsize == 64 and ADTS_FRAME.itemsize == 32
 
 
+# include/ohgpu_cbcs.h's: ohgpu_cenc_*'s calls with a batch-wide n_subsamples behind n_runs
+CBCS_SYMBOLS = {
+    "ohgpu_cbcs_batch_check": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64]),
+    "ohgpu_cbcs_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
+    "ohgpu_cbcs_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "ohgpu_cbcs_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_cbcs_batch_runs": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_cbcs_batch_packets": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_cbcs_batch_samples": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    "ohgpu_cbcs_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
+    "ohgpu_cbcs_batch_paths": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "ohgpu_cbcs_head": (C.c_int, [_vp, C.c_size_t, _vp]),
+    "ohgpu_cbcs_process_host": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "ohgpu_cbcs_flac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp,
+                                               _vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ohgpu_cbcs_alac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp,
+                                               _vp, _vp, _vp]),
+}
 # include/ohgpu_vorbis.h's: the Vorbis I decoder -- the setup image's parse, a descriptor per stream over rows of ALAC_PACKET
 VORBIS_SYMBOLS = {
     "ohgpu_vorbis_setup_parse": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
@@ -536,7 +560,7 @@ def lib():
         raise ImportError(f"{LIB_PATH} is missing: build the HIP extension first (python ohpipeline_amd/build.py); "
                           "there is no CPU fallback for the product path")
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(CENC_SYMBOLS.items()) + list(RAOP_RX_SYMBOLS.items()) + list(TS_SYMBOLS.items()) + list(VORBIS_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(CENC_SYMBOLS.items()) + list(RAOP_RX_SYMBOLS.items()) + list(TS_SYMBOLS.items()) + list(VORBIS_SYMBOLS.items()) + list(CBCS_SYMBOLS.items()):
         fn = getattr(L, name)          # AttributeError here = the library does not export what ohgpu.h declares
         fn.restype = res
         fn.argtypes = args
@@ -910,6 +934,27 @@ def cenc_head(data):
     raw = bytes(data)
     res = np.zeros(1, dtype=CENC_STREAM_RESULT)
     check(lib().ohgpu_cenc_head(raw, len(raw), res.ctypes.data_as(C.c_void_p)))
+    return res[0]
+
+
+def _cbcs_descs(descs):
+    d = np.ascontiguousarray(descs)
+    assert d.dtype == CBCS_STREAM_DESC
+    return d
+
+
+def cbcs_batch_check(descs, n_packets, n_runs, n_subsamples, src_arena_bytes, dst_arena_bytes):
+    """The validation of ctx.cbcs_batch without a device (ohgpu_cbcs_batch_check): OhGpuError on a bad descriptor."""
+    d = _cbcs_descs(descs)
+    check(lib().ohgpu_cbcs_batch_check(_ptr_or_none(d), d.size, n_packets, n_runs, n_subsamples, src_arena_bytes, dst_arena_bytes))
+
+
+def cbcs_head(data):
+    """The walk of a `cenc`- or `cbcs`-protected or clear fragmented stream up to the end of moov (ohgpu_cbcs_head; host only, no key): a
+    CBCS_STREAM_RESULT record."""
+    raw = bytes(data)
+    res = np.zeros(1, dtype=CBCS_STREAM_RESULT)
+    check(lib().ohgpu_cbcs_head(raw, len(raw), res.ctypes.data_as(C.c_void_p)))
     return res[0]
 
 
@@ -1764,6 +1809,74 @@ class Context:
         pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
         ares, pres = np.zeros(m.size, dtype=ALAC_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET_RESULT)
         check(lib().ohgpu_cenc_alac_process_host(self._h, _ptr_or_none(m), _ptr_or_none(a), m.size, n_packets, n_runs, _ptr_or_none(src), src.nbytes, mid_bytes,
+                                                 _ptr_or_none(dst), dst.nbytes, _ptr_or_none(res), _ptr_or_none(runs), _ptr_or_none(pk), _ptr_or_none(sm), _ptr_or_none(ares),
+                                                 _ptr_or_none(pres)))
+        return res, runs, pk, sm, ares, pres
+
+    def cbcs_batch(self, descs, n_packets, n_runs, n_subsamples, src_arena_bytes, dst_arena_bytes):
+        d = _cbcs_descs(descs)
+        b = C.c_void_p()
+        check(lib().ohgpu_cbcs_batch_create(self._h, _ptr_or_none(d), d.size, n_packets, n_runs, n_subsamples, src_arena_bytes, dst_arena_bytes, C.byref(b)))
+        return b
+
+    def cbcs_run(self, batch, d_src, d_dst, stream=None):
+        """Walk and subsample chain, run sums, carries, expand, finish, decrypt-gather (ohgpu_cbcs_batch_run): queued on the stream."""
+        check(lib().ohgpu_cbcs_batch_run(self._h, batch, d_src, d_dst, stream))
+
+    def cbcs_results(self, batch, n, n_packets, n_runs):
+        """The last run's (CBCS_STREAM_RESULT per stream, the run table, the packet table, the sample table); waits for the run."""
+        res, runs = np.zeros(n, dtype=CBCS_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
+        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
+        check(lib().ohgpu_cbcs_batch_results(self._h, batch, _ptr_or_none(res), n))
+        check(lib().ohgpu_cbcs_batch_runs(self._h, batch, _ptr_or_none(runs), n_runs))
+        check(lib().ohgpu_cbcs_batch_packets(self._h, batch, _ptr_or_none(pk), n_packets))
+        check(lib().ohgpu_cbcs_batch_samples(self._h, batch, _ptr_or_none(sm), n_packets))
+        return res, runs, pk, sm
+
+    def cbcs_phase_ms(self, batch):
+        """(walk, run sums, carries, expand, finish, decrypt-gather) of the last run in milliseconds."""
+        ms = (C.c_float * 6)()
+        check(lib().ohgpu_cbcs_batch_phase_ms(self._h, batch, ms))
+        return tuple(float(v) for v in ms)
+
+    def cbcs_paths(self, batch):
+        """{route, tiles, wave_blocks: the persistent decrypt-gather launch's workgroups} of a batch of the family (ohgpu_cbcs_batch_paths)."""
+        route, tiles, blocks = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        check(lib().ohgpu_cbcs_batch_paths(batch, C.byref(route), C.byref(tiles), C.byref(blocks)))
+        return dict(route=int(route.value), tiles=int(tiles.value), wave_blocks=int(blocks.value))
+
+    def cbcs_process_host(self, descs, n_packets, n_runs, n_subsamples, src, dst):
+        """Host bytes in (ohgpu_cbcs_process_host), the clear runs into dst; returns (results, run table, packet table, sample table)."""
+        d = _cbcs_descs(descs)
+        res, runs = np.zeros(d.size, dtype=CBCS_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
+        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
+        check(lib().ohgpu_cbcs_process_host(self._h, _ptr_or_none(d), d.size, n_packets, n_runs, n_subsamples, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst), dst.nbytes,
+                                            _ptr_or_none(res), _ptr_or_none(runs), _ptr_or_none(pk), _ptr_or_none(sm)))
+        return res, runs, pk, sm
+
+    def cbcs_flac_process_host(self, descs, flac_descs, n_packets, n_runs, n_subsamples, src, mid_bytes, dst, frames_capacity=0):
+        """Protected fLaC from host buffers to PCM (ohgpu_cbcs_flac_process_host); returns (results, run table, packet table, sample table,
+        FLAC results, frames)."""
+        m, f = _cbcs_descs(descs), np.ascontiguousarray(flac_descs)
+        assert f.dtype == FLAC_STREAM_DESC and f.size == m.size
+        res, runs = np.zeros(m.size, dtype=CBCS_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
+        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
+        fres, frames = np.zeros(m.size, dtype=FLAC_STREAM_RESULT), np.zeros(frames_capacity, dtype=FLAC_FRAME)
+        n_frames = C.c_size_t(0)
+        check(lib().ohgpu_cbcs_flac_process_host(self._h, _ptr_or_none(m), _ptr_or_none(f), m.size, n_packets, n_runs, n_subsamples, _ptr_or_none(src), src.nbytes, mid_bytes,
+                                                 _ptr_or_none(dst), dst.nbytes, _ptr_or_none(res), _ptr_or_none(runs), _ptr_or_none(pk), _ptr_or_none(sm),
+                                                 _ptr_or_none(fres), _ptr_or_none(frames), frames_capacity, C.byref(n_frames)))
+        return res, runs, pk, sm, fres, frames[:min(int(n_frames.value), frames_capacity)]
+
+    def cbcs_alac_process_host(self, descs, alac_descs, n_packets, n_runs, n_subsamples, src, mid_bytes, dst):
+        """Protected alac from host buffers to PCM (ohgpu_cbcs_alac_process_host); returns (results, run table, packet table, sample table,
+        Apple Lossless stream results, packet results indexed as the tables are)."""
+        m, a = _cbcs_descs(descs), np.ascontiguousarray(alac_descs)
+        assert a.dtype == ALAC_STREAM_DESC and a.size == m.size
+        res, runs = np.zeros(m.size, dtype=CBCS_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
+        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
+        ares, pres = np.zeros(m.size, dtype=ALAC_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET_RESULT)
+        check(lib().ohgpu_cbcs_alac_process_host(self._h, _ptr_or_none(m), _ptr_or_none(a), m.size, n_packets, n_runs, n_subsamples, _ptr_or_none(src), src.nbytes, mid_bytes,
                                                  _ptr_or_none(dst), dst.nbytes, _ptr_or_none(res), _ptr_or_none(runs), _ptr_or_none(pk), _ptr_or_none(sm), _ptr_or_none(ares),
                                                  _ptr_or_none(pres)))
         return res, runs, pk, sm, ares, pres

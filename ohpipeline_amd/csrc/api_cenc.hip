@@ -188,65 +188,15 @@ int ohgpu_cenc_alac_process_host(ohgpu_ctx* ctx, const ohgpu_cenc_stream_desc* c
                                  ohgpu_cenc_stream_result* cenc_results, ohgpu_mp4f_run* runs, ohgpu_alac_packet* packets, ohgpu_mp4_sample* samples,
                                  ohgpu_alac_stream_result* alac_results, ohgpu_alac_packet_result* packet_results)
 {
-    const char* const who = "ohgpu_cenc_alac_process_host";
-    if (n && (!cenc_descs || !alac_descs)) return set_error(OHGPU_ERR_INVALID, "%s: null argument", who);
-    std::vector<ohgpu_cenc_stream_result> cres(n);
-    std::vector<ohgpu_alac_packet> table(n_packets), dense;
-    std::vector<ohgpu_alac_stream_desc> adescs(alac_descs, alac_descs + n);
-    std::vector<ohgpu_alac_stream_result> ares(n);
-    std::vector<ohgpu_alac_packet_result> pres;
-    std::vector<uint32_t> first_row(n, 0);
-    void* d_mid = nullptr;
-    const int err = decoder_process_host(ctx, who, src_host, src_bytes, dst_host, dst_bytes,
+    // the protected families' fused call (api_common.h has the one body): this family's batch writes the CLEAR packets into the middle arena
+    return frag_alac_process_host(ctx, "ohgpu_cenc_alac_process_host", cenc_descs, alac_descs, n, n_packets, src_host, src_bytes, mid_bytes, dst_host, dst_bytes, cenc_results,
+        packets, alac_results, packet_results,
         [&](ohgpu_batch** b) { return ohgpu_cenc_batch_create(ctx, cenc_descs, n, n_packets, n_runs, src_bytes, mid_bytes, b); },
-        [&](const ohgpu_batch* b, const void* d_src, void* d_dst) {
-            if (!n) return (int)OHGPU_OK;
-            OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &d_mid, mid_bytes ? mid_bytes : 1));      // the middle arena: the clear packets never leave the device
-            int e = ohgpu_cenc_batch_run(ctx, b, d_src, d_mid, nullptr);
-            if (e == OHGPU_OK) e = cenc_fetch_all(ctx, b, n, n_packets, n_runs, cres.data(), runs, table.data(), samples);   // the one small read between the layers
-            if (e != OHGPU_OK) return e;
-            // the Apple Lossless table has the streams' gathered rows one after the other without gaps: places in the middle arena
-            for (size_t i = 0; i < n; i++) {
-                ohgpu_alac_stream_desc& a = adescs[i];
-                const ohgpu_mp4f_stream_result& m = cres[i].mp4f;
-                const bool ok = m.status == OHGPU_MP4F_OK && m.codec == mp4box::fourcc('a', 'l', 'a', 'c') && m.bytes_gathered != 0u;
-                const uint32_t from = cenc_descs[i].gather_first_row, rows = ok ? m.samples_available - from : 0u;
-                // (a stream that brings no packets still stands in the Apple Lossless batch: see ohgpu_mp4_alac_process_host)
-                const ohgpu_alac_config none = {1, 0, 16, 0, 0, 1, 1, 0, 0, 0, 0};
-                a.config = ok ? m.config : none;
-                a.first_packet = (uint32_t)dense.size();
-                a.n_packets = rows;
-                first_row[i] = cenc_descs[i].packet_first + from;
-                if (!ok && !a.flags) a.dst_plane_stride = 0;
-                if (rows) dense.insert(dense.end(), table.begin() + first_row[i], table.begin() + first_row[i] + rows);
-            }
-            pres.resize(dense.size());
-            if (dense.empty()) return (int)OHGPU_OK;
-            ohgpu_batch* ab = nullptr;
-            e = ohgpu_alac_batch_create(ctx, adescs.data(), n, dense.data(), dense.size(), mid_bytes, dst_bytes, &ab);
-            if (e != OHGPU_OK) return e;
-            const BatchPtr own(ab, BatchDeleter{ctx});
-            e = ohgpu_alac_batch_run(ctx, ab, d_mid, d_dst, nullptr);
-            if (e == OHGPU_OK) e = ohgpu_alac_batch_results(ctx, ab, ares.data(), n, pres.data(), pres.size());
-            return e;
+        [&](const ohgpu_batch* b, const void* d_src, void* d_mid, ohgpu_cenc_stream_result* res, ohgpu_alac_packet* table) {
+            const int e = ohgpu_cenc_batch_run(ctx, b, d_src, d_mid, nullptr);
+            return e != OHGPU_OK ? e : cenc_fetch_all(ctx, b, n, n_packets, n_runs, res, runs, table, samples);
         },
-        [&] {   // only what was decoded comes back, as in ohgpu_alac_process_host
-            int e = OHGPU_OK;
-            for (size_t i = 0; i < n && e == OHGPU_OK; i++)
-                if (adescs[i].n_packets) e = alac_download_decoded(ctx, who, adescs[i], pres.data() + adescs[i].first_packet, dst_host);
-            return e;
-        });
-    if (d_mid) { (void)hipStreamSynchronize(ctx->stream); ctx_dev_free(ctx, d_mid); }
-    if (err != OHGPU_OK) return err;
-    if (cenc_results && n) memcpy(cenc_results, cres.data(), n * sizeof(cres[0]));
-    if (packets && n_packets) memcpy(packets, table.data(), n_packets * sizeof(table[0]));
-    if (alac_results && n) memcpy(alac_results, ares.data(), n * sizeof(ares[0]));
-    if (packet_results && n_packets) {
-        memset(packet_results, 0, n_packets * sizeof(*packet_results));
-        for (size_t i = 0; i < n; i++)
-            if (adescs[i].n_packets) memcpy(packet_results + first_row[i], pres.data() + adescs[i].first_packet, adescs[i].n_packets * sizeof(pres[0]));
-    }
-    return OHGPU_OK;
+        [](const ohgpu_cenc_stream_result& r) -> const ohgpu_mp4f_stream_result& { return r.mp4f; });
 }
 
 }  // extern "C"

@@ -328,5 +328,73 @@ int frag_flac_process_host(ohgpu_ctx* ctx, const char* who, const Desc* descs, c
     return err;
 }
 
+// The whole of a protected family's fused call to the Apple Lossless decoder (ohgpu_cenc_alac_process_host, ohgpu_cbcs_alac_process_host):
+// create(&batch) = the family's batch over a middle arena of mid_bytes that lives on the device only, run_fetch(batch, d_src, d_mid,
+// results, packet table) = the family's run and its results and tables home, an Apple Lossless batch over the rows the family wrote, and
+// of dst_host the samples that were decoded.  head(result) -> the result's ohgpu_mp4f_stream_result.
+template <typename Desc, typename Res, typename Create, typename RunFetch, typename Head>
+int frag_alac_process_host(ohgpu_ctx* ctx, const char* who, const Desc* descs, const ohgpu_alac_stream_desc* alac_descs, size_t n, size_t n_packets, const void* src_host,
+                           uint64_t src_bytes, uint64_t mid_bytes, void* dst_host, uint64_t dst_bytes, Res* results, ohgpu_alac_packet* packets,
+                           ohgpu_alac_stream_result* alac_results, ohgpu_alac_packet_result* packet_results, Create&& create, RunFetch&& run_fetch, Head&& head)
+{
+    if (n && (!descs || !alac_descs)) return set_error(OHGPU_ERR_INVALID, "%s: null argument", who);
+    std::vector<Res> cres(n);
+    std::vector<ohgpu_alac_packet> table(n_packets), dense;
+    std::vector<ohgpu_alac_stream_desc> adescs(alac_descs, alac_descs + n);
+    std::vector<ohgpu_alac_stream_result> ares(n);
+    std::vector<ohgpu_alac_packet_result> pres;
+    std::vector<uint32_t> first_row(n, 0);
+    void* d_mid = nullptr;
+    const int err = decoder_process_host(ctx, who, src_host, src_bytes, dst_host, dst_bytes,
+        create,
+        [&](const ohgpu_batch* b, const void* d_src, void* d_dst) {
+            if (!n) return (int)OHGPU_OK;
+            OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &d_mid, mid_bytes ? mid_bytes : 1));      // the middle arena: the clear packets never leave the device
+            int e = run_fetch(b, d_src, d_mid, cres.data(), table.data());                    // (with the one small read between the layers)
+            if (e != OHGPU_OK) return e;
+            // the Apple Lossless table has the streams' gathered rows one after the other without gaps: places in the middle arena
+            for (size_t i = 0; i < n; i++) {
+                ohgpu_alac_stream_desc& a = adescs[i];
+                const ohgpu_mp4f_stream_result& m = head(cres[i]);
+                const bool ok = m.status == OHGPU_MP4F_OK && m.codec == mp4box::fourcc('a', 'l', 'a', 'c') && m.bytes_gathered != 0u;
+                const uint32_t from = descs[i].gather_first_row, rows = ok ? m.samples_available - from : 0u;
+                // (a stream that brings no packets still stands in the Apple Lossless batch: see ohgpu_mp4_alac_process_host)
+                const ohgpu_alac_config none = {1, 0, 16, 0, 0, 1, 1, 0, 0, 0, 0};
+                a.config = ok ? m.config : none;
+                a.first_packet = (uint32_t)dense.size();
+                a.n_packets = rows;
+                first_row[i] = descs[i].packet_first + from;
+                if (!ok && !a.flags) a.dst_plane_stride = 0;
+                if (rows) dense.insert(dense.end(), table.begin() + first_row[i], table.begin() + first_row[i] + rows);
+            }
+            pres.resize(dense.size());
+            if (dense.empty()) return (int)OHGPU_OK;
+            ohgpu_batch* ab = nullptr;
+            e = ohgpu_alac_batch_create(ctx, adescs.data(), n, dense.data(), dense.size(), mid_bytes, dst_bytes, &ab);
+            if (e != OHGPU_OK) return e;
+            const BatchPtr own(ab, BatchDeleter{ctx});
+            e = ohgpu_alac_batch_run(ctx, ab, d_mid, d_dst, nullptr);
+            if (e == OHGPU_OK) e = ohgpu_alac_batch_results(ctx, ab, ares.data(), n, pres.data(), pres.size());
+            return e;
+        },
+        [&] {   // only what was decoded comes back, as in ohgpu_alac_process_host
+            int e = OHGPU_OK;
+            for (size_t i = 0; i < n && e == OHGPU_OK; i++)
+                if (adescs[i].n_packets) e = alac_download_decoded(ctx, who, adescs[i], pres.data() + adescs[i].first_packet, dst_host);
+            return e;
+        });
+    if (d_mid) { (void)hipStreamSynchronize(ctx->stream); ctx_dev_free(ctx, d_mid); }
+    if (err != OHGPU_OK) return err;
+    if (results && n) memcpy(results, cres.data(), n * sizeof(cres[0]));
+    if (packets && n_packets) memcpy(packets, table.data(), n_packets * sizeof(table[0]));
+    if (alac_results && n) memcpy(alac_results, ares.data(), n * sizeof(ares[0]));
+    if (packet_results && n_packets) {
+        memset(packet_results, 0, n_packets * sizeof(*packet_results));
+        for (size_t i = 0; i < n; i++)
+            if (adescs[i].n_packets) memcpy(packet_results + first_row[i], pres.data() + adescs[i].first_packet, adescs[i].n_packets * sizeof(pres[0]));
+    }
+    return OHGPU_OK;
+}
+
 }  // namespace ohgpu
 #pragma GCC visibility pop

@@ -162,8 +162,11 @@ CENC_HD void crypt_lane(const uint8_t* in, uint8_t* out, uint32_t size, uint32_t
             if (4u * k + b < n) out[at + 4u * k + b] = (uint8_t)(in[at + 4u * k + b] ^ (ks[k] >> (8u * b)));
 }
 
-// ---- the protection boxes: the policy of mp4frag::WalkT
-struct Protection {
+// ---- the protection boxes: the policy of mp4frag::WalkT.  What differs between the families that read them -- which schemes and
+// which `tenc` are served, and what a traf's `senc` must hold -- is the Rules': Whole, below, is this family's (`cenc`, whole samples,
+// an IV a sample); csrc/cbcs_core.h has the rules of ohgpu_cbcs_*.  Everything else is shared text.
+template <class Rules>
+struct ProtectionT : Rules {
     static constexpr bool kAdmits = true;
     // what the caller gives: the descriptor's key_flags and kid; head_only walks ask for no key
     uint32_t key_flags;
@@ -236,13 +239,8 @@ struct Protection {
         if (frma_len < 4u) return w.fail(kInvalid, frma_at);
         if (schm_len < 12u) return w.fail(kInvalid, schm_at);
         scheme = be32(p, schm_pay + 4);
-        if (scheme != fourcc('c', 'e', 'n', 'c')) return w.fail(kUnsupported, schm_at);
-        if (tenc_len < 24u) return w.fail(kInvalid, tenc_at);
-        if (p[tenc_pay] != 0u) return w.fail(kUnsupported, tenc_at);
-        const uint32_t prot = p[tenc_pay + 6], ivs = p[tenc_pay + 7];
-        if (prot > 1u) return w.fail(kInvalid, tenc_at);
-        if (prot == 1u && ivs != 8u && ivs != 16u) return w.fail(kUnsupported, tenc_at);
-        is_protected = (uint8_t)prot; iv_size = (uint8_t)(prot ? ivs : 0u);
+        const uint32_t judged = Rules::judge_entry(w, *this, schm_at, tenc_pay, tenc_len);      // the scheme and the tenc: is_protected, iv_size
+        if (judged != kOk) return judged;
         for (uint32_t k = 0; k < 16u; k++) kid[k] = p[tenc_pay + 8u + k];
         // the original format's own children, with the clear entry's rules
         w.codec = be32(p, frma_pay);
@@ -287,20 +285,44 @@ struct Protection {
     {
         if (have_seig) return w.fail(kUnsupported, seig_at);
         if (!is_protected) return kOk;
-        if (!have_senc) return n ? w.fail(kUnsupported, traf) : (uint32_t)kOk;
-        if (senc_len < 8u) return w.fail(kInvalid, senc_at);
-        const uint32_t head = be32(w.p, senc_pay), count = be32(w.p, senc_pay + 4);
-        if ((head >> 24) != 0u || (head & 3u)) return w.fail(kUnsupported, senc_at);
-        if (count > (senc_len - 8u) / iv_size || count != n) return w.fail(kInvalid, senc_at);
+        return Rules::judge_traf(w, *this, traf, run0, n);
+    }
+};
+
+// This family's rules: scheme `cenc`, tenc version 0, an IV of 8 or 16 bytes a sample, a senc of IVs alone.
+struct Whole {
+    template <class W, class G>
+    MP4B_HD uint32_t judge_entry(W& w, G& g, uint64_t schm_at, uint64_t tenc_pay, uint64_t tenc_len)
+    {
+        const uint8_t* const p = w.p;
+        if (g.scheme != fourcc('c', 'e', 'n', 'c')) return w.fail(kUnsupported, schm_at);
+        if (tenc_len < 24u) return w.fail(kInvalid, g.tenc_at);
+        if (p[tenc_pay] != 0u) return w.fail(kUnsupported, g.tenc_at);
+        const uint32_t prot = p[tenc_pay + 6], ivs = p[tenc_pay + 7];
+        if (prot > 1u) return w.fail(kInvalid, g.tenc_at);
+        if (prot == 1u && ivs != 8u && ivs != 16u) return w.fail(kUnsupported, g.tenc_at);
+        g.is_protected = (uint8_t)prot; g.iv_size = (uint8_t)(prot ? ivs : 0u);
+        return kOk;
+    }
+    // the end of a protected track's traf that has no seig grouping
+    template <class W, class G>
+    MP4B_HD uint32_t judge_traf(W& w, G& g, uint64_t traf, uint32_t run0, uint32_t n)
+    {
+        if (!g.have_senc) return n ? w.fail(kUnsupported, traf) : (uint32_t)kOk;
+        if (g.senc_len < 8u) return w.fail(kInvalid, g.senc_at);
+        const uint32_t head = be32(w.p, g.senc_pay), count = be32(w.p, g.senc_pay + 4);
+        if ((head >> 24) != 0u || (head & 3u)) return w.fail(kUnsupported, g.senc_at);
+        if (count > (g.senc_len - 8u) / g.iv_size || count != n) return w.fail(kInvalid, g.senc_at);
         uint64_t before = 0;
         for (uint32_t k = run0; k < w.n_runs && k < w.run_capacity; k++) {
             MP4B_STEP(1);
-            w.runs[k].iv_pos = (uint32_t)(senc_pay + 8u + before * iv_size);
+            w.runs[k].iv_pos = (uint32_t)(g.senc_pay + 8u + before * g.iv_size);
             before += w.runs[k].samples;
         }
         return kOk;
     }
 };
+using Protection = ProtectionT<Whole>;
 
 // One stream: mp4frag::walk_into under Protection, and what the protection boxes gave.
 CENC_HD void walk(const Stream& s, const uint8_t* base, bool head_only, mp4frag::Result* out, Extra* x, Rec* rec, RunRec* runs)

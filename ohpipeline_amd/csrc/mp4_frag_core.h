@@ -141,6 +141,7 @@ struct WalkT {
     RunRec*  runs;
     uint32_t run_capacity, n_runs, n_moofs;
     uint64_t samples, frames_beyond, first_moof;
+    uint32_t traf_def_size;   // at a traf's end, for the policy: the size of a sample whose trun entry has none (tfhd's, else trex's)
 
     MP4B_HD uint32_t fail(uint32_t status, uint64_t at) { err_at = at; return status; }
     MP4B_HD bool visit() { MP4B_STEP(0); return ++visited <= kMaxBoxes; }
@@ -367,6 +368,7 @@ struct WalkT {
         });
         if (st != kOk) return st;
         if (!have_tfhd) return fail(kInvalid, box);
+        traf_def_size = def_size;
         return mine ? prot.traf_end(*this, box, run0, (uint32_t)(samples - samples0)) : (uint32_t)kOk;
     }
 

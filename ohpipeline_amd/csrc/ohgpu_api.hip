@@ -319,8 +319,9 @@ static const struct { const char* noun; void (*release)(ohgpu_ctx*, ohgpu_batch*
     {"a transport stream", free_state<&ohgpu_batch::ts>, false},   // kBatchTs
     {"an ADTS", free_state<&ohgpu_batch::adts>, false},   // kBatchAdts
     {"a Vorbis", free_state<&ohgpu_batch::vorbis>, false},   // kBatchVorbis
+    {"a cbcs-protected MPEG-4", cbcs_free, false},   // kBatchCbcs
 };
-static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchVorbis + 1, "a row per BatchKind");
+static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchCbcs + 1, "a row per BatchKind");
 
 int run_guard(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, BatchKind kind, bool empty, bool null_src_ok,
               const void* src_base, const void* dst_base, bool needs_dst)

@@ -28,6 +28,7 @@
 #include "raop_rx_core.h"
 #include "raop_aes_core.h"
 #include "cenc_core.h"
+#include "cbcs_core.h"
 #include "ts_packet_core.h"
 #include "vorbis_core.h"
 
@@ -603,6 +604,27 @@ static_assert(sizeof(ohgpu_cenc_stream_desc) == 112 && sizeof(ohgpu_cenc_stream_
               offsetof(ohgpu_cenc_stream_result, blocks) == offsetof(cenc::Result, x) + offsetof(cenc::Extra, blocks) && mp4frag::kNoKey == OHGPU_CENC_NO_KEY &&
               cenc::kHaveKey == OHGPU_CENC_HAVE_KEY && mp4box::kMaxBoxes == OHGPU_MP4_MAX_BOXES, "protected MPEG-4 layouts");
 
+// ---- protected fragmented MPEG-4, the second family (csrc/cbcs_kernel.hip): a CencState (d_cstreams holds cbcs::Stream,
+// the schedules are cbcs::kKeyWords words a stream) with arrays of its own for the work units -- the sibling's d_rowrecs, d_tile_blocks and
+// d_nblocks stay null -- and what the subsample entries need.
+struct CbcsState : CencState {
+    size_t n_subsamples = 0;
+    void* d_unit_first = nullptr;                     // uint64[n_packets]: a row's work units in front of it in its tile
+    void* d_tile_units = nullptr;                     // uint64[n_tiles]: a tile's work units, then (the tile scan) those in front of it
+    void* d_nunits = nullptr;                         // uint64[n_streams]: the stream's work units
+    void* d_more = nullptr;                           // cbcs::More[n_streams]
+    void* d_subs = nullptr;                           // cbcs::SubRow[n_subsamples]
+    void* d_samprecs = nullptr;                       // cbcs::SampleRec[n_packets]
+    void* d_cipher_blocks = nullptr;                  // uint64[n_streams]: the cipher blocks of the gathered rows
+    void* d_sub_first = nullptr;                      // uint32[n_streams]: the stream's first row of the subsample table
+};
+static_assert(sizeof(ohgpu_cbcs_stream_desc) == 120 && sizeof(ohgpu_cbcs_stream_result) == 232 && sizeof(ohgpu_cbcs_stream_desc) == sizeof(cbcs::Stream) &&
+              sizeof(ohgpu_cbcs_stream_result) == sizeof(cbcs::Result) && offsetof(ohgpu_cbcs_stream_desc, subsample_first) == offsetof(cbcs::Stream, sub_first) &&
+              offsetof(ohgpu_cbcs_stream_desc, key) == offsetof(cbcs::Stream, c) + offsetof(cenc::Stream, key) &&
+              offsetof(ohgpu_cbcs_stream_result, crypt_blocks) == offsetof(cbcs::Result, m) && offsetof(ohgpu_cbcs_stream_result, constant_iv) == offsetof(cbcs::Result, m) + offsetof(cbcs::More, civ) &&
+              offsetof(ohgpu_cbcs_stream_result, subsamples) == offsetof(cbcs::Result, m) + offsetof(cbcs::More, subsamples) && cbcs::kSchemeCbcs == OHGPU_CBCS_SCHEME_CBCS &&
+              cbcs::kSchemeCenc == OHGPU_CBCS_SCHEME_CENC, "cbcs layouts");
+
 // ---- the two file layers: PCM files (csrc/iff_pcm_kernel.hip) and DSD files (csrc/dsd_file_kernel.hip, DESIGN.md
 // 5.18).  One state for both (api_file.h has the plan, the run and the C ABI's bodies over it): the descriptors, the list of the
 // conversion's workgroups, the walk's record of each stream's run and the results of the last run, each in the family's own layout
@@ -656,7 +678,7 @@ static_assert(sizeof(ohgpu_vorbis_stream_desc) == 64 && sizeof(ohgpu_vorbis_pack
               offsetof(ohgpu_vorbis_packet_result, reserved) == offsetof(vorbiscore::Rec, prev_block) && vorbiscore::kMaxCoupling == OHGPU_VORBIS_MAX_COUPLING_STEPS &&
               vorbiscore::kMaxImageBytes == OHGPU_VORBIS_MAX_IMAGE_BYTES && vorbiscore::kMaxClassBytes == OHGPU_VORBIS_MAX_CLASS_BYTES, "Vorbis layouts");
 
-enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11, kBatchOhmRx = 12, kBatchOgg = 13, kBatchMp4 = 14, kBatchIff = 15, kBatchDsdFile = 16, kBatchMp4f = 17, kBatchCenc = 18, kBatchRaopRx = 19, kBatchTs = 20, kBatchAdts = 21, kBatchVorbis = 22 };
+enum BatchKind { kBatchPcm = 1, kBatchSrc = 2, kBatchFmt = 3, kBatchFlywheel = 4, kBatchOhm = 5, kBatchSrcPull = 6, kBatchDsd = 7, kBatchFlac = 8, kBatchDsdPcm = 9, kBatchAlac = 10, kBatchRaop = 11, kBatchOhmRx = 12, kBatchOgg = 13, kBatchMp4 = 14, kBatchIff = 15, kBatchDsdFile = 16, kBatchMp4f = 17, kBatchCenc = 18, kBatchRaopRx = 19, kBatchTs = 20, kBatchAdts = 21, kBatchVorbis = 22, kBatchCbcs = 23 };
 
 }  // namespace ohgpu
 
@@ -773,6 +795,7 @@ struct ohgpu_batch {
     ohgpu::TsState* ts = nullptr;       // kBatchTs only
     ohgpu::AdtsState* adts = nullptr;   // kBatchAdts only
     ohgpu::VorbisState* vorbis = nullptr;   // kBatchVorbis only
+    ohgpu::CbcsState* cbcs = nullptr;   // kBatchCbcs only
     void*    d_pull_tiles = nullptr;   // kBatchSrcPull: PullTile[n_pull_tiles] on the device (d_descs holds the messages)
     uint32_t n_pull_tiles = 0;
     // kBatchSrc whose messages differ in layout: one uniform batch per layout (each with its own block-kernel plan), run one
@@ -895,6 +918,11 @@ uint32_t mp4f_wave_blocks(uint64_t slots, uint32_t cus);   // the persistent lau
 int  cenc_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const cenc::Stream* streams);
 int  cenc_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
 void cenc_free(ohgpu_ctx* ctx, ohgpu_batch* b);                       // clears the schedules, on the device and here, then state_free
+// csrc/cbcs_kernel.hip.  The sibling's launches over work units: the walk under cbcs::Protection (with the subsample chain), mp4f_tables,
+// the rows and their unit prefixes, the tiles' prefixes, and the persistent launch (a wave per chunk of 64 work units of a stream).
+int  cbcs_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const cbcs::Stream* streams);
+int  cbcs_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
+void cbcs_free(ohgpu_ctx* ctx, ohgpu_batch* b);                       // clears the schedules, on the device and here, then state_free
 // csrc/iff_pcm_kernel.hip.  No launch is persistent: a lane a stream (walk), a workgroup per kIffGroupPieces pieces of a run (convert).
 int  iff_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const iffchunk::Stream* streams);   // the descriptors and the workgroup list onto the device
 int  iff_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);

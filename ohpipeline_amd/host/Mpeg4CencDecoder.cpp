@@ -20,19 +20,25 @@ static Mpeg4CencKind KindOfHead(const ohgpu_cenc_stream_result& aHead)
     }
 }
 
-Mpeg4CencKind Mpeg4CencRecognise(const Brx& aBytes)
+Mpeg4CencKind Mpeg4CencRecognise(const Brx& aBytes, TBool aAllSchemes)
 {
     if (aBytes.Bytes() >= 8 && memcmp(aBytes.Ptr() + 4, "ftyp", 4) != 0) return Mpeg4CencKind::None;
+    if (aAllSchemes) {
+        ohgpu_cbcs_stream_result wide;
+        if (ohgpu_cbcs_head(aBytes.Ptr(), aBytes.Bytes(), &wide) != OHGPU_OK) return Mpeg4CencKind::None;
+        return KindOfHead(wide.cenc);
+    }
     ohgpu_cenc_stream_result head;
     if (ohgpu_cenc_head(aBytes.Ptr(), aBytes.Bytes(), &head) != OHGPU_OK) return Mpeg4CencKind::None;
     return KindOfHead(head);
 }
 
-Mpeg4CencBatchDecoder::Mpeg4CencBatchDecoder(ICencKeyProvider& aKeys)
-    : iKeys(aKeys), iHaveKey(false), iPeekAt(0), iWhole(0), iMoovEnd(0), iServed(0), iNextRow(0), iNextSample(0), iStuck(false), iHeadRead(false), iBad(false), iAnnounced(false), iConfigured(false),
+Mpeg4CencBatchDecoder::Mpeg4CencBatchDecoder(ICencKeyProvider& aKeys, TBool aAllSchemes)
+    : iKeys(aKeys), iAllSchemes(aAllSchemes), iHaveKey(false), iPeekAt(0), iWhole(0), iMoovEnd(0), iServed(0), iNextRow(0), iNextSample(0), iStuck(false), iHeadRead(false), iBad(false), iAnnounced(false), iConfigured(false),
       iKind(Mpeg4CencKind::NeedMore)
 {
     memset(&iHead, 0, sizeof(iHead));
+    memset(&iWideHead, 0, sizeof(iWideHead));
     memset(iKey, 0, sizeof(iKey));
 }
 
@@ -77,8 +83,9 @@ void Mpeg4CencBatchDecoder::Peek()
     }
     if (iStuck) iWhole = iFile.size();
     if (!iHeadRead && (iMoovEnd || iStuck)) {
-        const int err = ohgpu_cenc_head(iFile.data(), (size_t)iWhole, &iHead);
+        const int err = iAllSchemes ? ohgpu_cbcs_head(iFile.data(), (size_t)iWhole, &iWideHead) : ohgpu_cenc_head(iFile.data(), (size_t)iWhole, &iHead);
         ASSERT(err == OHGPU_OK);
+        if (iAllSchemes) iHead = iWideHead.cenc;
         iHeadRead = true;
         iKind = KindOfHead(iHead);
         if (iHead.mp4f.status == OHGPU_MP4F_OK && iHead.is_protected) {   // the key is asked for once, by the kid the head gives
@@ -132,160 +139,197 @@ void Mpeg4CencBatchDecoder::Flush(MsgFactory& aFactory, Lane* aLanes, size_t aCo
 {
     int firstBad = 0;                                                     // 1: corrupt, 2: unsupported
     auto refuse = [&](Mpeg4CencBatchDecoder& d, int bad) { d.iBad = true; if (!firstBad) firstBad = bad; };
-    std::vector<size_t> flacLanes, alacLanes;
-    for (size_t k = 0; k < aCount; k++) {
-        Mpeg4CencBatchDecoder& d = *aLanes[k].decoder;
-        if (!d.iHeadRead || d.iBad) continue;
-        if (d.iKind != Mpeg4CencKind::Flac && d.iKind != Mpeg4CencKind::Alac) {
-            const int bad = d.Judge(d.iHead, ~0u);
-            refuse(d, bad ? bad : 2);
-            continue;
+    // the second family's descriptors and results around the first's (ohgpu_cbcs_stream_desc begins with ohgpu_cenc_stream_desc, the result
+    // with the result): a lane's share of the subsample table is sized from its bytes, of which an entry costs six
+    auto widen = [](const std::vector<ohgpu_cenc_stream_desc>& aDescs, size_t* aSubsamples) {
+        std::vector<ohgpu_cbcs_stream_desc> wide(aDescs.size());
+        size_t rows = 0;
+        for (size_t i = 0; i < aDescs.size(); i++) {
+            memset(&wide[i], 0, sizeof(wide[i]));
+            memcpy(&wide[i], &aDescs[i], sizeof(aDescs[i]));
+            wide[i].subsample_first = (uint32_t)rows;
+            wide[i].subsample_capacity = aDescs[i].src_bytes / 6u;
+            rows += wide[i].subsample_capacity;
         }
-        if (d.iWhole <= d.iServed) continue;                             // nothing whole has arrived since the lane was served
-        (d.iKind == Mpeg4CencKind::Flac ? flacLanes : alacLanes).push_back(k);
-    }
-
-    // ---- fLaC: demultiplex, gather and decode in one call
-    if (!flacLanes.empty()) {
-        const size_t n = flacLanes.size();
-        std::vector<ohgpu_cenc_stream_desc> descs(n);
-        std::vector<ohgpu_flac_stream_desc> flac(n);
-        TUint64 srcTotal = 0, midTotal = 0, dstTotal = 0, rows = 0, runs = 0, framesMax = 0;
-        for (size_t i = 0; i < n; i++) {
-            const Mpeg4CencBatchDecoder& d = *aLanes[flacLanes[i]].decoder;
-            const ohgpu_flac_streaminfo_t& info = d.iHead.mp4f.flac;
-            d.Describe(descs[i], srcTotal, rows, runs);
-            descs[i].dst_offset = midTotal;
-            descs[i].dst_capacity = descs[i].src_bytes;
-            const TUint64 frames = d.iWhole / std::max<TUint64>(info.min_framesize, 7u + info.channels) + 1;
-            TUint64 samples = std::min<TUint64>(frames * std::max<TUint64>(info.max_blocksize, 16u), FlacBatchDecoder::kMaxSamplesPerTick);
-            if (info.total_samples != 0) samples = std::min<TUint64>(samples, info.total_samples - std::min<TUint64>(info.total_samples, d.iNextSample));
-            ohgpu_flac_stream_desc& s = flac[i];
-            memset(&s, 0, sizeof(s));
-            s.src_offset = midTotal;
-            s.dst_offset = dstTotal;
-            s.first_sample = d.iNextSample;
-            s.max_samples = (uint32_t)std::max<TUint64>(samples, info.max_blocksize);
-            s.sample_rate = info.sample_rate;
-            s.blocksize = info.min_blocksize == info.max_blocksize ? info.max_blocksize : 0;
-            s.max_blocksize = info.max_blocksize;
-            s.channels = info.channels;
-            s.bits = info.bits;
-            s.flags = OHGPU_FLAC_FLAG_AT_FRAME | OHGPU_FLAC_OUT_PACKED_BE;
-            srcTotal += MsgFactory::ArenaShare(descs[i].src_bytes);
-            midTotal += MsgFactory::ArenaShare(descs[i].src_bytes);
-            dstTotal += MsgFactory::ArenaShare((TUint64)s.max_samples * info.channels * (info.bits / 8));
-            rows += descs[i].packet_capacity;
-            runs += descs[i].run_capacity;
-            framesMax += descs[i].packet_capacity;
-        }
-        TByte* src = nullptr;
-        TByte* dst = nullptr;
-        aFactory.ReserveArena((size_t)srcTotal, (size_t)dstTotal, src, dst);
-        for (size_t i = 0; i < n; i++) memcpy(src + descs[i].src_offset, aLanes[flacLanes[i]].decoder->iFile.data(), descs[i].src_bytes);
-        std::vector<ohgpu_cenc_stream_result> demuxed(n);
-        std::vector<ohgpu_alac_packet> packets((size_t)rows);
-        std::vector<ohgpu_mp4_sample> samples((size_t)rows);
-        std::vector<ohgpu_flac_stream_result> results(n);
-        std::vector<ohgpu_flac_frame> frames((size_t)framesMax);
-        size_t nFrames = 0;
-        const int err = ohgpu_cenc_flac_process_host(aFactory.Gpu(), descs.data(), flac.data(), n, packets.size(), (size_t)runs, src, srcTotal, midTotal, dst, dstTotal,
-                                                     demuxed.data(), nullptr, packets.data(), samples.data(), results.data(), frames.data(), frames.size(), &nFrames);
-        ASSERT(err == OHGPU_OK && nFrames <= frames.size());
-        static const TByte kName[] = {'F', 'L', 'A', 'C'};
-        size_t at = 0;
-        for (size_t i = 0; i < n; i++) {
-            Lane& lane = aLanes[flacLanes[i]];
-            Mpeg4CencBatchDecoder& d = *lane.decoder;
-            const ohgpu_flac_streaminfo_t& info = d.iHead.mp4f.flac;
-            const TUint sampleBytes = (info.bits / 8u) * info.channels;
-            int bad = d.Judge(demuxed[i], descs[i].packet_capacity);
-            if (!bad && !d.iAnnounced) {
-                // Flac.cpp:427-441: bit rate = rate x depth x channels, lossless
-                lane.controller->OutputDecodedStream(info.sample_rate * info.bits * info.channels, info.bits, info.sample_rate, info.channels, Brn(kName, sizeof(kName)),
-                                                     info.total_samples * Jiffies::kPerSecond / info.sample_rate, 0, true);
-                d.iAnnounced = true;
+        *aSubsamples = rows;
+        return wide;
+    };
+    for (int family = 0; family < 2; family++) {                         // 0: ohgpu_cenc_*; 1: ohgpu_cbcs_* (the lanes made with aAllSchemes)
+        std::vector<size_t> flacLanes, alacLanes;
+        for (size_t k = 0; k < aCount; k++) {
+            Mpeg4CencBatchDecoder& d = *aLanes[k].decoder;
+            if (!d.iHeadRead || d.iBad || (d.iAllSchemes ? 1 : 0) != family) continue;
+            if (d.iKind != Mpeg4CencKind::Flac && d.iKind != Mpeg4CencKind::Alac) {
+                const int bad = d.Judge(d.iHead, ~0u);
+                refuse(d, bad ? bad : 2);
+                continue;
             }
-            for (; at < nFrames && frames[at].stream == i; at++) {
-                // Flac.cpp:379-417: a frame leaves in pieces of whole samples within kMaxPieceBytes, the count restarting with every frame
-                const TByte* audio = dst + flac[i].dst_offset + (frames[at].first_sample - flac[i].first_sample) * sampleBytes;
-                const TUint perPiece = FlacBatchDecoder::PieceSamples(info.channels, info.bits);
-                for (TUint done = 0; done < frames[at].blocksize; ) {
-                    const TUint m = std::min(perPiece, frames[at].blocksize - done);
-                    lane.trackOffset += lane.controller->OutputAudioPcm(Brn(audio + (size_t)done * sampleBytes, m * sampleBytes), info.channels, info.sample_rate, info.bits,
-                                                                        AudioDataEndian::Big, lane.trackOffset);
-                    done += m;
+            if (d.iWhole <= d.iServed) continue;                             // nothing whole has arrived since the lane was served
+            (d.iKind == Mpeg4CencKind::Flac ? flacLanes : alacLanes).push_back(k);
+        }
+
+        // ---- fLaC: demultiplex, gather and decode in one call
+        if (!flacLanes.empty()) {
+            const size_t n = flacLanes.size();
+            std::vector<ohgpu_cenc_stream_desc> descs(n);
+            std::vector<ohgpu_flac_stream_desc> flac(n);
+            TUint64 srcTotal = 0, midTotal = 0, dstTotal = 0, rows = 0, runs = 0, framesMax = 0;
+            for (size_t i = 0; i < n; i++) {
+                const Mpeg4CencBatchDecoder& d = *aLanes[flacLanes[i]].decoder;
+                const ohgpu_flac_streaminfo_t& info = d.iHead.mp4f.flac;
+                d.Describe(descs[i], srcTotal, rows, runs);
+                descs[i].dst_offset = midTotal;
+                descs[i].dst_capacity = descs[i].src_bytes;
+                const TUint64 frames = d.iWhole / std::max<TUint64>(info.min_framesize, 7u + info.channels) + 1;
+                TUint64 samples = std::min<TUint64>(frames * std::max<TUint64>(info.max_blocksize, 16u), FlacBatchDecoder::kMaxSamplesPerTick);
+                if (info.total_samples != 0) samples = std::min<TUint64>(samples, info.total_samples - std::min<TUint64>(info.total_samples, d.iNextSample));
+                ohgpu_flac_stream_desc& s = flac[i];
+                memset(&s, 0, sizeof(s));
+                s.src_offset = midTotal;
+                s.dst_offset = dstTotal;
+                s.first_sample = d.iNextSample;
+                s.max_samples = (uint32_t)std::max<TUint64>(samples, info.max_blocksize);
+                s.sample_rate = info.sample_rate;
+                s.blocksize = info.min_blocksize == info.max_blocksize ? info.max_blocksize : 0;
+                s.max_blocksize = info.max_blocksize;
+                s.channels = info.channels;
+                s.bits = info.bits;
+                s.flags = OHGPU_FLAC_FLAG_AT_FRAME | OHGPU_FLAC_OUT_PACKED_BE;
+                srcTotal += MsgFactory::ArenaShare(descs[i].src_bytes);
+                midTotal += MsgFactory::ArenaShare(descs[i].src_bytes);
+                dstTotal += MsgFactory::ArenaShare((TUint64)s.max_samples * info.channels * (info.bits / 8));
+                rows += descs[i].packet_capacity;
+                runs += descs[i].run_capacity;
+                framesMax += descs[i].packet_capacity;
+            }
+            TByte* src = nullptr;
+            TByte* dst = nullptr;
+            aFactory.ReserveArena((size_t)srcTotal, (size_t)dstTotal, src, dst);
+            for (size_t i = 0; i < n; i++) memcpy(src + descs[i].src_offset, aLanes[flacLanes[i]].decoder->iFile.data(), descs[i].src_bytes);
+            std::vector<ohgpu_cenc_stream_result> demuxed(n);
+            std::vector<ohgpu_alac_packet> packets((size_t)rows);
+            std::vector<ohgpu_mp4_sample> samples((size_t)rows);
+            std::vector<ohgpu_flac_stream_result> results(n);
+            std::vector<ohgpu_flac_frame> frames((size_t)framesMax);
+            size_t nFrames = 0;
+            int err;
+            if (family == 0) {
+                err = ohgpu_cenc_flac_process_host(aFactory.Gpu(), descs.data(), flac.data(), n, packets.size(), (size_t)runs, src, srcTotal, midTotal, dst, dstTotal,
+                                                   demuxed.data(), nullptr, packets.data(), samples.data(), results.data(), frames.data(), frames.size(), &nFrames);
+            } else {
+                size_t subsamples = 0;
+                const std::vector<ohgpu_cbcs_stream_desc> wide = widen(descs, &subsamples);
+                std::vector<ohgpu_cbcs_stream_result> wideResults(n);
+                err = ohgpu_cbcs_flac_process_host(aFactory.Gpu(), wide.data(), flac.data(), n, packets.size(), (size_t)runs, subsamples, src, srcTotal, midTotal, dst, dstTotal,
+                                                   wideResults.data(), nullptr, packets.data(), samples.data(), results.data(), frames.data(), frames.size(), &nFrames);
+                for (size_t i = 0; i < n; i++) demuxed[i] = wideResults[i].cenc;
+            }
+            ASSERT(err == OHGPU_OK && nFrames <= frames.size());
+            static const TByte kName[] = {'F', 'L', 'A', 'C'};
+            size_t at = 0;
+            for (size_t i = 0; i < n; i++) {
+                Lane& lane = aLanes[flacLanes[i]];
+                Mpeg4CencBatchDecoder& d = *lane.decoder;
+                const ohgpu_flac_streaminfo_t& info = d.iHead.mp4f.flac;
+                const TUint sampleBytes = (info.bits / 8u) * info.channels;
+                int bad = d.Judge(demuxed[i], descs[i].packet_capacity);
+                if (!bad && !d.iAnnounced) {
+                    // Flac.cpp:427-441: bit rate = rate x depth x channels, lossless
+                    lane.controller->OutputDecodedStream(info.sample_rate * info.bits * info.channels, info.bits, info.sample_rate, info.channels, Brn(kName, sizeof(kName)),
+                                                         info.total_samples * Jiffies::kPerSecond / info.sample_rate, 0, true);
+                    d.iAnnounced = true;
                 }
+                for (; at < nFrames && frames[at].stream == i; at++) {
+                    // Flac.cpp:379-417: a frame leaves in pieces of whole samples within kMaxPieceBytes, the count restarting with every frame
+                    const TByte* audio = dst + flac[i].dst_offset + (frames[at].first_sample - flac[i].first_sample) * sampleBytes;
+                    const TUint perPiece = FlacBatchDecoder::PieceSamples(info.channels, info.bits);
+                    for (TUint done = 0; done < frames[at].blocksize; ) {
+                        const TUint m = std::min(perPiece, frames[at].blocksize - done);
+                        lane.trackOffset += lane.controller->OutputAudioPcm(Brn(audio + (size_t)done * sampleBytes, m * sampleBytes), info.channels, info.sample_rate, info.bits,
+                                                                            AudioDataEndian::Big, lane.trackOffset);
+                        done += m;
+                    }
+                }
+                if (bad) { refuse(d, bad); continue; }
+                if (results[i].status == OHGPU_FLAC_CORRUPT) bad = 1;
+                if (results[i].status == OHGPU_FLAC_UNSUPPORTED) bad = 2;
+                // the rows whose bytes the FLAC phases consumed: a frame is a sample, so bytes_consumed ends a row
+                const ohgpu_alac_packet* mine = packets.data() + descs[i].packet_first;
+                TUint64 row = d.iNextRow, bytes = 0;
+                while (row < demuxed[i].mp4f.samples_available && bytes < results[i].bytes_consumed) bytes += mine[row++].bytes;
+                if (!bad && bytes != results[i].bytes_consumed) bad = 1;     // (these are no FLAC frames in samples)
+                const ohgpu_mp4_sample* rowsOf = samples.data() + descs[i].packet_first;
+                d.iSamples.assign(rowsOf, rowsOf + std::min<TUint64>(demuxed[i].mp4f.samples, descs[i].packet_capacity));
+                d.iNextRow = row;
+                d.iNextSample += results[i].samples;
+                if (row == demuxed[i].mp4f.samples_available) d.iServed = descs[i].src_bytes;      // (else this tick's arena was full: the next one goes on)
+                if (bad) refuse(d, bad);
             }
-            if (bad) { refuse(d, bad); continue; }
-            if (results[i].status == OHGPU_FLAC_CORRUPT) bad = 1;
-            if (results[i].status == OHGPU_FLAC_UNSUPPORTED) bad = 2;
-            // the rows whose bytes the FLAC phases consumed: a frame is a sample, so bytes_consumed ends a row
-            const ohgpu_alac_packet* mine = packets.data() + descs[i].packet_first;
-            TUint64 row = d.iNextRow, bytes = 0;
-            while (row < demuxed[i].mp4f.samples_available && bytes < results[i].bytes_consumed) bytes += mine[row++].bytes;
-            if (!bad && bytes != results[i].bytes_consumed) bad = 1;     // (these are no FLAC frames in samples)
-            const ohgpu_mp4_sample* rowsOf = samples.data() + descs[i].packet_first;
-            d.iSamples.assign(rowsOf, rowsOf + std::min<TUint64>(demuxed[i].mp4f.samples, descs[i].packet_capacity));
-            d.iNextRow = row;
-            d.iNextSample += results[i].samples;
-            if (row == demuxed[i].mp4f.samples_available) d.iServed = descs[i].src_bytes;      // (else this tick's arena was full: the next one goes on)
-            if (bad) refuse(d, bad);
         }
-    }
 
-    // ---- alac: demultiplex, then the packets that are new to the lane's packet decoder
-    if (!alacLanes.empty()) {
-        const size_t n = alacLanes.size();
-        std::vector<ohgpu_cenc_stream_desc> descs(n);
-        std::vector<TByte> src;
-        TUint64 rows = 0, runs = 0, dstTotal = 0;
-        for (size_t i = 0; i < n; i++) {
-            const Mpeg4CencBatchDecoder& d = *aLanes[alacLanes[i]].decoder;
-            d.Describe(descs[i], src.size(), rows, runs);
-            descs[i].dst_offset = dstTotal;                                   // the clear packets come home here
-            descs[i].dst_capacity = descs[i].src_bytes;
-            dstTotal += (descs[i].src_bytes + 15u) & ~15u;
-            src.insert(src.end(), d.iFile.begin(), d.iFile.begin() + (size_t)d.iWhole);
-            src.resize((src.size() + 15u) & ~(size_t)15u, 0);
-            rows += descs[i].packet_capacity;
-            runs += descs[i].run_capacity;
-        }
-        std::vector<ohgpu_cenc_stream_result> demuxed(n);
-        std::vector<ohgpu_alac_packet> packets((size_t)rows);
-        std::vector<ohgpu_mp4_sample> samples((size_t)rows);
-        std::vector<TByte> clear((size_t)dstTotal);
-        const int err = ohgpu_cenc_process_host(aFactory.Gpu(), descs.data(), n, packets.size(), (size_t)runs, src.data(), src.size(), clear.data(), clear.size(), demuxed.data(),
-                                                nullptr, packets.data(), samples.data());
-        ASSERT(err == OHGPU_OK);
-        for (size_t i = 0; i < n; i++) {
-            Mpeg4CencBatchDecoder& d = *aLanes[alacLanes[i]].decoder;
-            const ohgpu_mp4f_stream_result& r = demuxed[i].mp4f;
-            int bad = d.Judge(demuxed[i], descs[i].packet_capacity);
-            if (!bad && !d.iConfigured) {
-                const ohgpu_alac_config& c = r.config;
-                TByte cookie[24];
-                const uint32_t words[3] = {c.max_frame_bytes, c.avg_bit_rate, c.sample_rate};
-                for (int b = 0; b < 4; b++) cookie[b] = (TByte)(c.frame_length >> (24 - 8 * b));
-                cookie[4] = c.compatible_version; cookie[5] = c.bit_depth; cookie[6] = c.pb; cookie[7] = c.mb; cookie[8] = c.kb; cookie[9] = c.channels;
-                cookie[10] = (TByte)(c.max_run >> 8); cookie[11] = (TByte)c.max_run;
-                for (int w = 0; w < 3; w++) for (int b = 0; b < 4; b++) cookie[12 + 4 * w + b] = (TByte)(words[w] >> (24 - 8 * b));
-                try {
-                    d.iAlac.SetConfig(Brn(cookie, sizeof(cookie)), r.timescale, r.duration);      // AlacApple.cpp:160-185
-                    d.iConfigured = true;
-                } catch (CodecStreamFeatureUnsupported&) { bad = 2; } catch (CodecStreamCorrupt&) { bad = 1; }
+        // ---- alac: demultiplex, then the packets that are new to the lane's packet decoder
+        if (!alacLanes.empty()) {
+            const size_t n = alacLanes.size();
+            std::vector<ohgpu_cenc_stream_desc> descs(n);
+            std::vector<TByte> src;
+            TUint64 rows = 0, runs = 0, dstTotal = 0;
+            for (size_t i = 0; i < n; i++) {
+                const Mpeg4CencBatchDecoder& d = *aLanes[alacLanes[i]].decoder;
+                d.Describe(descs[i], src.size(), rows, runs);
+                descs[i].dst_offset = dstTotal;                                   // the clear packets come home here
+                descs[i].dst_capacity = descs[i].src_bytes;
+                dstTotal += (descs[i].src_bytes + 15u) & ~15u;
+                src.insert(src.end(), d.iFile.begin(), d.iFile.begin() + (size_t)d.iWhole);
+                src.resize((src.size() + 15u) & ~(size_t)15u, 0);
+                rows += descs[i].packet_capacity;
+                runs += descs[i].run_capacity;
             }
-            if (bad) { refuse(d, bad); continue; }
-            const ohgpu_alac_packet* mine = packets.data() + descs[i].packet_first;
-            // (rows [iNextRow, samples_available) were gathered: each row names its clear bytes in the destination buffer; a tick whose
-            // gather found no room or nothing new leaves the rows empty and the lane where it stands)
-            for (; r.bytes_gathered && d.iNextRow < r.samples_available; d.iNextRow++) {
-                const ohgpu_alac_packet& p = mine[(size_t)d.iNextRow];
-                d.iAlac.PushPacket(Brn(clear.data() + p.src_offset, p.bytes));
+            std::vector<ohgpu_cenc_stream_result> demuxed(n);
+            std::vector<ohgpu_alac_packet> packets((size_t)rows);
+            std::vector<ohgpu_mp4_sample> samples((size_t)rows);
+            std::vector<TByte> clear((size_t)dstTotal);
+            int err;
+            if (family == 0) {
+                err = ohgpu_cenc_process_host(aFactory.Gpu(), descs.data(), n, packets.size(), (size_t)runs, src.data(), src.size(), clear.data(), clear.size(), demuxed.data(),
+                                              nullptr, packets.data(), samples.data());
+            } else {
+                size_t subsamples = 0;
+                const std::vector<ohgpu_cbcs_stream_desc> wide = widen(descs, &subsamples);
+                std::vector<ohgpu_cbcs_stream_result> wideResults(n);
+                err = ohgpu_cbcs_process_host(aFactory.Gpu(), wide.data(), n, packets.size(), (size_t)runs, subsamples, src.data(), src.size(), clear.data(), clear.size(),
+                                              wideResults.data(), nullptr, packets.data(), samples.data());
+                for (size_t i = 0; i < n; i++) demuxed[i] = wideResults[i].cenc;
             }
-            const ohgpu_mp4_sample* rowsOf = samples.data() + descs[i].packet_first;
-            d.iSamples.assign(rowsOf, rowsOf + std::min<TUint64>(r.samples, descs[i].packet_capacity));
-            d.iServed = descs[i].src_bytes;
+            ASSERT(err == OHGPU_OK);
+            for (size_t i = 0; i < n; i++) {
+                Mpeg4CencBatchDecoder& d = *aLanes[alacLanes[i]].decoder;
+                const ohgpu_mp4f_stream_result& r = demuxed[i].mp4f;
+                int bad = d.Judge(demuxed[i], descs[i].packet_capacity);
+                if (!bad && !d.iConfigured) {
+                    const ohgpu_alac_config& c = r.config;
+                    TByte cookie[24];
+                    const uint32_t words[3] = {c.max_frame_bytes, c.avg_bit_rate, c.sample_rate};
+                    for (int b = 0; b < 4; b++) cookie[b] = (TByte)(c.frame_length >> (24 - 8 * b));
+                    cookie[4] = c.compatible_version; cookie[5] = c.bit_depth; cookie[6] = c.pb; cookie[7] = c.mb; cookie[8] = c.kb; cookie[9] = c.channels;
+                    cookie[10] = (TByte)(c.max_run >> 8); cookie[11] = (TByte)c.max_run;
+                    for (int w = 0; w < 3; w++) for (int b = 0; b < 4; b++) cookie[12 + 4 * w + b] = (TByte)(words[w] >> (24 - 8 * b));
+                    try {
+                        d.iAlac.SetConfig(Brn(cookie, sizeof(cookie)), r.timescale, r.duration);      // AlacApple.cpp:160-185
+                        d.iConfigured = true;
+                    } catch (CodecStreamFeatureUnsupported&) { bad = 2; } catch (CodecStreamCorrupt&) { bad = 1; }
+                }
+                if (bad) { refuse(d, bad); continue; }
+                const ohgpu_alac_packet* mine = packets.data() + descs[i].packet_first;
+                // (rows [iNextRow, samples_available) were gathered: each row names its clear bytes in the destination buffer; a tick whose
+                // gather found no room or nothing new leaves the rows empty and the lane where it stands)
+                for (; r.bytes_gathered && d.iNextRow < r.samples_available; d.iNextRow++) {
+                    const ohgpu_alac_packet& p = mine[(size_t)d.iNextRow];
+                    d.iAlac.PushPacket(Brn(clear.data() + p.src_offset, p.bytes));
+                }
+                const ohgpu_mp4_sample* rowsOf = samples.data() + descs[i].packet_first;
+                d.iSamples.assign(rowsOf, rowsOf + std::min<TUint64>(r.samples, descs[i].packet_capacity));
+                d.iServed = descs[i].src_bytes;
+            }
         }
     }
     // one decode for every alac lane, whether it was served this tick or not

@@ -35,11 +35,11 @@ enum class Mpeg4CencKind { None, NeedMore, Flac, Alac, Plain, Other };
 /** What the first bytes of a stream are: None (no "ftyp" at bytes 4..8), NeedMore (`moov` has not arrived whole), Flac / Alac (a
  *  fragmented stream with such a track: this element's), Plain (a file with sample tables: host/Mpeg4AlacDecoder.h's), Other (an MPEG-4
  *  stream this element refuses). */
-Mpeg4CencKind Mpeg4CencRecognise(const Brx& aBytes);
+Mpeg4CencKind Mpeg4CencRecognise(const Brx& aBytes, TBool aAllSchemes = false);
 
 class Mpeg4CencBatchDecoder {
 public:
-    explicit Mpeg4CencBatchDecoder(ICencKeyProvider& aKeys);
+    explicit Mpeg4CencBatchDecoder(ICencKeyProvider& aKeys, TBool aAllSchemes = false);
     /** Stream bytes as they come, from the first byte on.  Throws CodecStreamCorrupt at the eighth byte when they are no MPEG-4 stream. */
     void Push(const Brx& aBytes);
     TBool HeadRead() const { return iHeadRead; }            // `moov` has arrived whole and was read (on the host)
@@ -52,6 +52,8 @@ public:
     TBool Corrupt() const { return iBad; }
     TBool Protected() const { return iHeadRead && iHead.is_protected != 0; }
     TBool HaveKey() const { return iHaveKey; }                // the provider gave the key the head's kid names
+    TBool AllSchemes() const { return iAllSchemes; }          // served by ohgpu_cbcs_*
+    const ohgpu_cbcs_stream_result& WideHead() const { ASSERT(iHeadRead && iAllSchemes); return iWideHead; }
     AlacBatchDecoder& Alac() { return iAlac; }
     /** The sample that holds audio frame aFrame becomes the next one delivered; aFirstFrame is that sample's first frame.  False
      *  (nothing changes) before a Flush has read a fragment or when the frame lies behind the fragments read so far. */
@@ -72,6 +74,8 @@ private:
     void Describe(ohgpu_cenc_stream_desc& aDesc, TUint64 aSrcOffset, TUint64 aRow, TUint64 aRun) const;
 private:
     ICencKeyProvider& iKeys;
+    TBool iAllSchemes;
+    ohgpu_cbcs_stream_result iWideHead;
     TBool iHaveKey;
     TByte iKey[16];
     std::vector<TByte> iFile;
