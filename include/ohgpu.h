@@ -1263,8 +1263,8 @@ typedef struct ohgpu_mp4f_stream_result {   /* 168 bytes */
  * flags, a codecs mask of 0 or with unknown bits, src_bytes >= 2^31, row, run or gather ranges that overlap or (rows, runs) run past
  * their tables.  OHGPU_ERR_BOUNDS: a range outside its arena.  The empty batch is legal. */
 int ohgpu_mp4f_batch_check(const ohgpu_mp4f_stream_desc* descs, size_t n, size_t n_packets, size_t n_runs, uint64_t src_arena_bytes, uint64_t dst_arena_bytes);
-/* The descriptors go to the device; the tiles, the records, the three tables (every byte 0xa5 until a run writes it) and the results
- * are the batch's.  Created under ohgpu_set_kernel_variant(1) the batch takes the plain route: one launch, a lane per stream does
+/* The descriptors go to the device; the tiles, the records, the three tables (every byte 0xa5 that the LAST run did not write: a run
+ * begins by filling them, so no row of an earlier run shows) and the results are the batch's.  Created under ohgpu_set_kernel_variant(1) the batch takes the plain route: one launch, a lane per stream does
  * everything serially, the gather included (ohgpu_mp4f_batch_paths).  Both routes write the same bytes.  Freed with ohgpu_batch_destroy. */
 int ohgpu_mp4f_batch_create(ohgpu_ctx* ctx, const ohgpu_mp4f_stream_desc* descs, size_t n, size_t n_packets, size_t n_runs, uint64_t src_arena_bytes,
                             uint64_t dst_arena_bytes, ohgpu_batch** batch);

@@ -54,7 +54,8 @@ extern "C" {
  *
  * The delivered bytes are concatenated into [dst_offset, dst_offset + bytes_delivered), at any address; not one byte outside that range
  * is written.  A stream's records are [pes_first, pes_first + min(pes_packets, pes_capacity)) of the batch's table; the count goes on
- * past the capacity, as ohgpu_ogg_batch_packets documents. */
+ * past the capacity, as ohgpu_ogg_batch_packets documents.  Every other record of the table is zero after a run, whatever the run before
+ * it left there (the ADTS frame table likewise). */
 #define OHGPU_TS_PACKET_BYTES  188u
 #define OHGPU_TS_NONE          0xffffffffu            /* pat_packet, pmt_packet, corrupt_packet: there is none */
 #define OHGPU_TS_NO_PTS        0xffffffffffffffffull

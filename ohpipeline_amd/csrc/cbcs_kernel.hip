@@ -278,8 +278,6 @@ int cbcs_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const cbcs::Stream* streams)
     OHGPU_TRY(dev_array<uint64_t>(ctx, g, &g.d_nunits, n));
     OHGPU_TRY(dev_array<uint64_t>(ctx, g, &g.d_cipher_blocks, n));
     OHGPU_TRY(dev_array(ctx, g, &g.d_sub_first, n, sub_first.data()));
-    if (g.n_packets) OHGPU_HIP_TRY_ALLOC(hipMemset(g.d_rows, 0xa5, g.n_packets * sizeof(Row)));
-    OHGPU_HIP_TRY_ALLOC(hipStreamSynchronize(nullptr));                // (the fill is queued: a run on another stream must not meet it)
     return OHGPU_OK;
 }
 
@@ -311,6 +309,8 @@ int cbcs_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
     unsigned long long* const cipher_blocks = (unsigned long long*)g.d_cipher_blocks;
     const uint32_t* const keys = (const uint32_t*)g.d_keys;
     OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[0], s));
+    OHGPU_TRY(mp4f_fill(g, s));                                       // (no row of the run before stands in a table: csrc/mp4_frag_kernel.hip)
+    if (g.n_packets) OHGPU_HIP_TRY_ALLOC(hipMemsetAsync(g.d_rows, 0xa5, g.n_packets * sizeof(Row), s));
     if (g.plain) {
         hipLaunchKernelGGL(cbcs_plain_kernel, dim3(lane_blocks), dim3(64), 0, s, cstreams, ns, src, dst, results, extras, more, recs, runrecs, (Run*)g.d_runs, (Row*)g.d_packets,
                            (Row*)g.d_rows, (Sample*)g.d_samples, subs, samprecs, keys);

@@ -229,8 +229,6 @@ int cenc_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const cenc::Stream* streams)
     OHGPU_TRY(dev_array<uint64_t>(ctx, g, &g.d_tile_blocks, g.n_tiles));
     OHGPU_TRY(dev_array(ctx, g, &g.d_chunk_first, n + 1, chunk_first.data()));
     OHGPU_TRY(dev_array<uint64_t>(ctx, g, &g.d_nblocks, n));
-    if (g.n_packets) OHGPU_HIP_TRY_ALLOC(hipMemset(g.d_rows, 0xa5, g.n_packets * sizeof(Row)));
-    OHGPU_HIP_TRY_ALLOC(hipStreamSynchronize(nullptr));                // (the fill is queued: a run on another stream must not meet it)
     return OHGPU_OK;
 }
 
@@ -258,6 +256,8 @@ int cenc_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
     RunRec* const runrecs = (RunRec*)g.d_runrecs;
     const uint32_t* const keys = (const uint32_t*)g.d_keys;
     OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[0], s));
+    OHGPU_TRY(mp4f_fill(g, s));                                       // (no row of the run before stands in a table: csrc/mp4_frag_kernel.hip)
+    if (g.n_packets) OHGPU_HIP_TRY_ALLOC(hipMemsetAsync(g.d_rows, 0xa5, g.n_packets * sizeof(Row), s));
     if (g.plain) {
         hipLaunchKernelGGL(cenc_plain_kernel, dim3(lane_blocks), dim3(64), 0, s, cstreams, ns, src, dst, results, extras, recs, runrecs, (Run*)g.d_runs, (Row*)g.d_packets,
                            (Row*)g.d_rows, (Sample*)g.d_samples, keys);

@@ -265,10 +265,16 @@ int mp4f_plan(ohgpu_ctx* ctx, Mp4fState& g, const Stream* streams, const char* w
     OHGPU_TRY(dev_array<Run>(ctx, g, &g.d_runs, g.n_runs));
     OHGPU_TRY(dev_array<Row>(ctx, g, &g.d_packets, g.n_packets));
     OHGPU_TRY(dev_array<Sample>(ctx, g, &g.d_samples, g.n_packets));
-    if (g.n_runs) OHGPU_HIP_TRY_ALLOC(hipMemset(g.d_runs, 0xa5, g.n_runs * sizeof(Run)));
-    if (g.n_packets) OHGPU_HIP_TRY_ALLOC(hipMemset(g.d_packets, 0xa5, g.n_packets * sizeof(Row)));
-    if (g.n_packets) OHGPU_HIP_TRY_ALLOC(hipMemset(g.d_samples, 0xa5, g.n_packets * sizeof(Sample)));
-    OHGPU_HIP_TRY_ALLOC(hipStreamSynchronize(nullptr));                // (the fills are queued: a run on another stream must not meet them)
+    return OHGPU_OK;                                                  // (the tables are filled at the head of every run: mp4f_fill)
+}
+
+// The three public tables as a run finds them: 0xa5 in every row.  A run writes the rows its streams have and no others, so without this
+// a row of the run before -- of a stream that now has fewer samples or runs -- would stand in the table as if it were this run's.
+int mp4f_fill(const Mp4fState& g, hipStream_t s)
+{
+    if (g.n_runs) OHGPU_HIP_TRY_ALLOC(hipMemsetAsync(g.d_runs, 0xa5, g.n_runs * sizeof(Run), s));
+    if (g.n_packets) OHGPU_HIP_TRY_ALLOC(hipMemsetAsync(g.d_packets, 0xa5, g.n_packets * sizeof(Row), s));
+    if (g.n_packets) OHGPU_HIP_TRY_ALLOC(hipMemsetAsync(g.d_samples, 0xa5, g.n_packets * sizeof(Sample), s));
     return OHGPU_OK;
 }
 
@@ -314,6 +320,7 @@ int mp4f_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
     RunRec* const runrecs = (RunRec*)g.d_runrecs;
     const uint32_t* const slot_stream = (const uint32_t*)g.d_slot_stream;
     OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[0], s));
+    OHGPU_TRY(mp4f_fill(g, s));
     if (g.plain) {
         hipLaunchKernelGGL(mp4f_plain_kernel, dim3(lane_blocks), dim3(64), 0, s, streams, ns, src, dst, results, recs, runrecs, (Run*)g.d_runs, (Row*)g.d_packets, (Sample*)g.d_samples);
         OHGPU_HIP_TRY_ALLOC(hipGetLastError());

@@ -911,6 +911,7 @@ int  mp4_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, hipStream
 // lane a stream (walk, carries, finish) or a workgroup a tile (expand).
 int  mp4f_plan(ohgpu_ctx* ctx, Mp4fState& g, const mp4frag::Stream* streams, const char* who);   // the slot map, the tiles and the tables onto the device (g holds the counts)
 int  mp4f_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
+int  mp4f_fill(const Mp4fState& g, hipStream_t s);   // the head of a run of the three families: the run, packet and sample tables back to their fill, on the run's stream
 int  mp4f_tables(const Mp4fState& g, const uint8_t* src, hipStream_t s);   // behind a walk: ev[1], run sums, ev[2], carries, ev[3], expand, ev[4], finish, ev[5]
 uint32_t mp4f_wave_blocks(uint64_t slots, uint32_t cus);   // the persistent launches' size: the rule tests/test_gpu_mp4f_textbook.py restates
 // csrc/cenc_kernel.hip.  The walk under cenc::Protection, mp4f_tables, then the decrypt-gather: a workgroup a tile (the rows and their

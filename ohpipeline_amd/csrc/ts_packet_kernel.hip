@@ -227,9 +227,7 @@ int ts_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const tspkt::Stream* streams)
     OHGPU_TRY(dev_array<uint32_t>(ctx, g, &g.d_src_at, g.n_grid));
     OHGPU_TRY(dev_array(ctx, g, &g.d_tiles, g.n_tiles, tiles.data()));
     OHGPU_TRY(dev_array<tspkt::Pes>(ctx, g, &g.d_pes, g.n_pes));
-    if (g.n_pes) OHGPU_HIP_TRY_ALLOC(hipMemset(g.d_pes, 0, g.n_pes * sizeof(tspkt::Pes)));
-    OHGPU_HIP_TRY_ALLOC(hipStreamSynchronize(nullptr));                // (the fill is queued: a run on another stream must not meet it)
-    return OHGPU_OK;
+    return OHGPU_OK;                                                  // (the PES table is zeroed at the head of every run)
 }
 
 int ts_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s)
@@ -240,6 +238,9 @@ int ts_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* ds
     const tspkt::Stream* streams = (const tspkt::Stream*)g.d_streams;
     const uint64_t* first = (const uint64_t*)g.d_first;
     OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[0], s));
+    // a run writes the records its streams have and no others: a record of the run before, of a stream that now has fewer PES packets,
+    // must not stand in the table as if it were this run's
+    if (g.n_pes) OHGPU_HIP_TRY_ALLOC(hipMemsetAsync(g.d_pes, 0, g.n_pes * sizeof(tspkt::Pes), s));
     if (g.plain) {
         OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[1], s));
         OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[2], s));
@@ -374,9 +375,7 @@ int adts_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const adts::Stream* streams)
     OHGPU_TRY(dev_array(ctx, g, &g.d_tiles, g.n_tiles, tiles.data()));
     OHGPU_TRY(dev_array<uint8_t>(ctx, g, &g.d_bits, g.bits_bytes));
     OHGPU_TRY(dev_array<adts::Frame>(ctx, g, &g.d_frames, g.n_frames));
-    if (g.n_frames) OHGPU_HIP_TRY_ALLOC(hipMemset(g.d_frames, 0, g.n_frames * sizeof(adts::Frame)));
-    OHGPU_HIP_TRY_ALLOC(hipStreamSynchronize(nullptr));
-    return OHGPU_OK;
+    return OHGPU_OK;                                                  // (the frame table is zeroed at the head of every run)
 }
 
 int adts_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, hipStream_t s)
@@ -386,6 +385,7 @@ int adts_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, hipStream
     const uint32_t ns = (uint32_t)g.n_streams;
     const adts::Stream* streams = (const adts::Stream*)g.d_streams;
     OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[0], s));
+    if (g.n_frames) OHGPU_HIP_TRY_ALLOC(hipMemsetAsync(g.d_frames, 0, g.n_frames * sizeof(adts::Frame), s));      // (as ts_run zeroes its PES table)
     if (g.plain) {
         OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[1], s));
         hipLaunchKernelGGL(adts_plain_kernel, dim3((ns + 63u) / 64u), dim3(64), 0, s, streams, ns, src, (adts::Frame*)g.d_frames, (adts::Result*)g.d_results);

@@ -1,6 +1,6 @@
 """The batches of tests/test_gpu_stream_switch.py (on the device) and tests/test_stream_switch_cases.py (the tables and the models
-alone, on the CPU): for each of the eight families whose batch keeps per-run device records (flac, alac, raop, ohm_rx, ogg, mp4, iff,
-dsd_file)
+alone, on the CPU): for each of the fifteen families whose batch keeps per-run device records (flac, alac, raop, ohm_rx, ogg, mp4, iff,
+dsd_file; mp4f, cenc, cbcs, vorbis, ts, adts, raop_rx)
 ONE set of tables and TWO source arenas of equal size, X and Y, with what the family's textbook model says a run over each must leave:
 the whole destination arena (pre-filled, with guards), the results, the packet or sample tables.  A run of the batch over X and a run
 over Y on another stream share the batch's records; every stream's output differs between X and Y, so that a mix-up of the two runs
@@ -8,28 +8,38 @@ cannot produce the right bytes by accident.
 
 Every pair is made by the family's own case module (the writers, the Job, the comparison): X and Y are two Jobs over inputs of equal
 lengths, and the builder asserts that their tables came out byte for byte the same.  Two to four streams of a few hundred bytes to a
-few KiB (FLAC and MPEG-4 have one longer stream each; their builders say why), at least one of them busy in every phase.  Built once
-and kept.  TEST INFRASTRUCTURE ONLY."""
+few KiB (FLAC, MPEG-4 and fragmented MPEG-4 have one longer stream each; their builders say why), at least one of them busy in every
+phase.  Built once and kept.
+
+For the seven newer families Y is not X with other payload bytes alone: it changes what the per-run records HOLD -- fewer rows, runs,
+records or frames in one stream (what run X wrote there must be back at the table's fill), a refused sample, a lost key's worth of
+output, packets passed over -- and their models give the WHOLE tables, fill and guard rows included.  TEST INFRASTRUCTURE ONLY."""
 import functools
 
 import numpy as np
 
 from ohpipeline_amd import capi
 
-FAMILIES = ("flac", "alac", "raop", "ohm_rx", "ogg", "mp4", "iff", "dsd_file")
+FAMILIES = ("flac", "alac", "raop", "ohm_rx", "ogg", "mp4", "iff", "dsd_file", "mp4f", "cenc", "cbcs", "vorbis", "ts", "adts", "raop_rx")
+BOTH_ROUTES = ("mp4f", "cenc", "cbcs", "vorbis", "ts", "adts", "raop_rx")           # the families run on the plain route (kernel variant 1 at create) too
 
 
 class Pair:
     """family; src["X"], src["Y"]: the source arenas (uint8, equal sizes); dst0: the destination arena before a run (None: the
     family has none); want["X"], want["Y"]: the model's arena after a run (None likewise); ranges: (offset, bytes) of every stream's
     output in the destination arena; summary[which]: the model's results in a form that compares with ==; tables[which]: the model's
-    tables as bytes (MPEG-4, which has no arena).  check(): the library's own validation of the tables, without a device.
+    tables as bytes (a family without an arena has nothing else; the newer families with one give them too).  check(): the library's
+    own validation of the tables, without a device.
     create(ctx) -> batch; run(ctx, batch, d_src, d_dst, stream); verify(ctx, batch, which): the results and tables the batch holds
-    are the model's for `which` (waits for the last run)."""
+    are the model's for `which` (waits for the last run).  route(ctx, batch) -> 1 or 2, which kernels the batch was planned onto (None:
+    the family is run on the launches' route alone).  sample_types: None -- the arena is compared byte for byte -- or, for every range
+    in turn, the dtype of the samples it holds (Vorbis: the device rounds a float32 transform, the model a float64 one, and a sample
+    may come out 1 LSB apart); written[which]: then, the bytes of the arena the model writes in that run, as a mask."""
 
-    def __init__(self, family, src, dst0, want, ranges, summary, check, create, run, verify, tables=None):
+    def __init__(self, family, src, dst0, want, ranges, summary, check, create, run, verify, tables=None, route=None, sample_types=None, written=None):
         self.family, self.src, self.dst0, self.want, self.ranges, self.summary = family, src, dst0, want, ranges, summary
-        self.check, self.create, self.run, self.verify, self.tables = check, create, run, verify, tables
+        self.check, self.create, self.run, self.verify, self.tables, self.route = check, create, run, verify, tables, route
+        self.sample_types, self.written = sample_types, written
         assert src["X"].size == src["Y"].size and src["X"].dtype == src["Y"].dtype == np.uint8
         for a in list(src.values()) + [dst0] + list(want.values()):
             if a is not None:
@@ -363,7 +373,444 @@ def _dsd_file():
                 run=lambda ctx, b, s, d, stream: ctx.dsd_file_run(b, s, d, stream), verify=verify)
 
 
-_BUILDERS = {"flac": _flac, "alac": _alac, "raop": _raop, "ohm_rx": _ohm_rx, "ogg": _ogg, "mp4": _mp4, "iff": _iff, "dsd_file": _dsd_file}
+# ---------------------------------------------------------------- fragmented MPEG-4 (mp4f_cases), clear and protected (cenc_cases, cbcs_cases)
+def _other_bytes(samples, salt):
+    """samples of the same sizes with other bytes in them"""
+    return [bytes((b * 5 + 11 * k + 3 * j + salt) & 0xff for j, b in enumerate(s)) for k, s in enumerate(samples)]
+
+
+def _trun_size_at(m, nth, k):
+    """where sample k's size stands in the nth trun of a file whose truns carry a data offset, durations and sizes"""
+    return m.find("trun", nth)[1] + 12 + 8 * k + 4
+
+
+def _renamed(data, at, name=b"free"):
+    """the box whose header begins at `at` under another name: the walk steps over it"""
+    data = bytes(data)
+    return data[:at + 4] + name + data[at + 8:]
+
+
+def _frag_tables(family, jobs, check, create, run, results, route):
+    """What the three fragmented MPEG-4 families share: X and Y are two Jobs of one module (FC.Job, CC.Job, BC.Job) over files of equal
+    lengths and equal capacities; the run, packet and sample tables are compared whole, fill rows and guard rows included."""
+    import mp4f_cases as FC
+    x, y = jobs["X"], jobs["Y"]
+    assert (x.n_packets, x.n_runs, x.dst_bytes) == (y.n_packets, y.n_runs, y.dst_bytes)
+    _same_tables((x.descs, y.descs))
+    dst0 = np.full(x.dst_bytes, FC.FILL, dtype=np.uint8)
+    summary = {w: jobs[w].want_results.tobytes() for w in "XY"}
+    tables = {w: (jobs[w].want_runs.tobytes(), jobs[w].want_packets.tobytes(), jobs[w].want_samples.tobytes()) for w in "XY"}
+
+    def verify(ctx, b, which):
+        job = jobs[which]
+        res, runs, packets, samples = results(ctx, b, len(job.streams), job.n_packets, job.n_runs)
+        FC.assert_same(res, runs, packets, samples, job.want_dst, job, what=which)          # (the arena is the caller's to compare)
+
+    return Pair(family, {w: jobs[w].src.copy() for w in "XY"}, dst0, {w: jobs[w].want_dst.copy() for w in "XY"},
+                [(int(d["dst_offset"]), int(d["dst_capacity"])) for d in x.descs], summary,
+                check=lambda: check(x, x.src.size, dst0.size), create=lambda ctx: create(ctx, x, x.src.size, dst0.size), run=run, verify=verify,
+                tables=tables, route=route)
+
+
+FC_TILE = 1024           # mp4frag::kTile
+
+
+def _mp4f():
+    """Three gathered files, Y's samples of the same sizes with other bytes.  A file of 600 + 464 samples in two runs (two tiles of the
+    expansion: the second begins inside the second run); a file of three runs whose last moof is called `free` in Y (the walk steps over
+    it: X has a run and four rows more, which Y must leave as the batch's fill); an Apple Lossless file in which Y's fourth size stands
+    above the packet limit (refused, first_bad_sample, and every later sample of its run with it).  Capacities are X's, the larger."""
+    import mp4f_cases as FC
+
+    def files(w):
+        def made(counts, seed, codec=FC.FLAC):
+            fragments = []
+            for k, n in enumerate(counts):
+                samples = FC.pattern_samples(n, seed + k)
+                if w == "Y":
+                    samples = _other_bytes(samples, seed)
+                fragments.append(FC.fragment([FC.run(samples, [1 + (j * 5 + k) % 7 for j in range(n)])], sequence=k + 1))
+            return FC.mux(FC.init_segment(codec), fragments, codec=codec)
+        return [made([600, FC_TILE - 600 + 40], 11), made([5, 6, 4], 21), made([7, 8], 31, FC.ALAC)]
+
+    whole = {w: files(w) for w in "XY"}
+    assert [len(m.data) for m in whole["X"]] == [len(m.data) for m in whole["Y"]] and whole["X"][0].n > FC_TILE
+    y = whole["Y"]
+    data_y = [y[0].data, _renamed(y[1].data, y[1].find("moof", 2)[0]), FC.patched(y[2], _trun_size_at(y[2], 0, 3), 1 << 20)]
+    jobs = {"X": FC.Job([FC.stream(m) for m in whole["X"]]),
+            "Y": FC.Job([FC.stream(raw, capacity=m.n, run_capacity=len(m.runs), dst_capacity=len(m.data)) for raw, m in zip(data_y, whole["X"])])}
+    mx, my = jobs["X"].models, jobs["Y"].models
+    assert [m["status"] for m in mx + my] == [0] * 6
+    assert (mx[1]["runs"], mx[1]["samples"]) == (3, 15) and (my[1]["runs"], my[1]["samples"]) == (2, 11)
+    assert mx[2]["samples_refused"] == 0 and my[2]["samples_refused"] > 0 and my[2]["first_bad_sample"] == 3
+    return _frag_tables("mp4f", jobs, lambda j, s, d: capi.mp4f_batch_check(j.descs, j.n_packets, j.n_runs, s, d),
+                        lambda ctx, j, s, d: ctx.mp4f_batch(j.descs, j.n_packets, j.n_runs, s, d),
+                        lambda ctx, b, s, d, stream: ctx.mp4f_run(b, s, d, stream), lambda ctx, *a: ctx.mp4f_results(*a),
+                        lambda ctx, b: ctx.mp4f_paths(b)["route"])
+
+
+def _cut_to(longer, n):
+    """a file that goes on for longer than n bytes, cut there: inside its last fragment"""
+    assert len(longer.data) > n > longer.segment_ends[-2] if len(longer.segment_ends) > 1 else len(longer.data) > n > longer.init_bytes
+    return longer.data[:n]
+
+
+def _cenc():
+    """Four files under four keys, Y's with other plaintext of the same sizes under the same keys and IVs: FLAC with 8-byte IVs (Y: a
+    file that goes on for two samples more, cut where X's ends -- inside its last fragment's sample 8: refused, and first_bad_sample
+    says so); Apple Lossless with 16-byte IVs (Y: the tenc says is_protected = 0: X decrypts it, Y copies it); a file whose senc
+    stands in front of the truns; and a stream created WITHOUT its key in both runs -- X's file is protected (CENC_NO_KEY, nothing
+    gathered), Y's tenc says it is not (copied)."""
+    import cenc_cases as CC
+    import mp4f_cases as FC
+    sizes = [[40, 17, 0, 33, 100, 64, 16, 1, 90], [50, 64, 31, 7, 48, 80, 15], [16, 200, 5, 77, 32, 9, 60, 41], [30, 45, 12, 70, 8]]
+    counts = [[4, 5], [3, 4], [5, 3], [2, 3]]
+    how = [dict(codec=FC.FLAC, iv_size=8), dict(codec=FC.ALAC, iv_size=16), dict(codec=FC.FLAC, iv_size=8, senc="front"), dict(codec=FC.FLAC, iv_size=16)]
+    clear = dict(sinf_options=dict(is_protected=0, iv_size=16))
+
+    def made(k, seed, sizes_k=None, counts_k=None, **more):
+        return CC.simple(counts_k or counts[k], sizes=sizes_k or sizes[k], seed=seed, key=CC.key_of(k), kid=CC.kid_of(k), **how[k], **more)
+
+    x = [made(k, 40 + k) for k in range(4)]
+    y = [made(0, 50, sizes[0] + [70, 21], [4, 7]), made(1, 51, **clear), made(2, 52), made(3, 53, **clear)]
+    data_y = [_cut_to(y[0], len(x[0].data))] + [m.data for m in y[1:]]
+    assert [len(d) for d in data_y] == [len(m.data) for m in x]
+    jobs = {"X": CC.Job([CC.stream(m, have_key=k != 3) for k, m in enumerate(x)]),
+            "Y": CC.Job([CC.stream(raw, capacity=m.n, run_capacity=len(m.runs), dst_capacity=len(m.data), key=m.key, kid=m.kid, have_key=k != 3)
+                         for k, (raw, m) in enumerate(zip(data_y, x))])}
+    sx, sy = ([int(r["mp4f"]["status"]) for r in jobs[w].want_results] for w in "XY")
+    assert sx == [0, 0, 0, capi.CENC_NO_KEY] and sy == [0, 0, 0, 0], (sx, sy)
+    cut = jobs["Y"].want_results[0]["mp4f"]
+    assert (int(cut["samples"]), int(cut["samples_refused"]), int(cut["first_bad_sample"]), int(cut["samples_available"])) == (11, 1, 8, 8)     # (the cut falls in sample 8)
+    assert not jobs["X"].want_results["mp4f"]["samples_refused"].any()
+    assert [int(r["is_protected"]) for r in jobs["X"].want_results] == [1, 1, 1, 1] and [int(r["is_protected"]) for r in jobs["Y"].want_results][1:] == [0, 1, 0]
+    return _frag_tables("cenc", jobs, lambda j, s, d: capi.cenc_batch_check(j.descs, j.n_packets, j.n_runs, s, d),
+                        lambda ctx, j, s, d: ctx.cenc_batch(j.descs, j.n_packets, j.n_runs, s, d),
+                        lambda ctx, b, s, d, stream: ctx.cenc_run(b, s, d, stream), lambda ctx, *a: ctx.cenc_results(*a),
+                        lambda ctx, b: ctx.cenc_paths(b)["route"])
+
+
+def _cbcs():
+    """Four files under four keys, Y's with other plaintext: a `cbcs` stream with the 1:9 pattern and a constant IV (no senc); a
+    `cenc`-scheme stream with subsample entries (Y: a file that goes on for longer, cut where X's ends -- inside its last fragment:
+    a sample refused, six rows where X has seven);
+    a `cbcs` stream whose samples have three entries each in X and, from the third sample on, one in Y (the senc is shorter by what
+    the samples are longer: the subsample table of run Y is shorter, and nothing of run X's rows may show through); and a stream
+    created WITHOUT its key in both runs, protected in X (CENC_NO_KEY) and not in Y (copied)."""
+    import cbcs_cases as BC
+    three = [[(3, 32), (0, 17), (5, 48)], [(1, 16), (2, 40), (0, 0)], [(0, 64), (7, 9), (4, 16)], [(2, 33), (0, 80), (1, 1)], [(6, 16), (3, 3), (0, 32)], [(0, 48), (1, 20), (9, 16)]]
+    one = three[:2] + [[(sum(c + p for c, p in e) - 32 + 12, 32)] for e in three[2:]]                # (two entries of six bytes fewer, twelve bytes more)
+    subs = [[(4, 16 * k + 5), (0, 33)] for k in range(1, 8)]
+    size_of = lambda entries: [sum(c + p for c, p in e) for e in entries]
+    const = bytes(range(0x30, 0x40))
+
+    def files(w):
+        s = 60 if w == "X" else 70
+        a = BC.build([16 * 25 + 3, 7, 16 * 11, 160, 45], counts=[2, 3], constant_iv=const, pattern=(1, 9), senc=None, seed=s, key=BC.key_of(0), kid=BC.kid_of(0))
+        more = subs + [[(4, 50), (0, 33)]] * 2 if w == "Y" else subs
+        b = BC.build(size_of(more), counts=[3, len(more) - 3], scheme=BC.CENC, iv_size=8, layout=BC.split_layout(more), seed=s + 1, key=BC.key_of(1), kid=BC.kid_of(1))
+        parts = three if w == "X" else one
+        c = BC.build(size_of(parts), counts=[2, 4], iv_size=16, pattern=(1, 1), layout=BC.split_layout(parts), seed=s + 2, key=BC.key_of(2), kid=BC.kid_of(2))
+        d = BC.build([30, 45, 12, 70, 8], counts=[2, 3], iv_size=16, listed=False, seed=s + 3, key=BC.key_of(3), kid=BC.kid_of(3))
+        return [a, b, c, d]
+
+    x, y = files("X"), files("Y")
+    open_at = BC.at_of(y[3].data, b"tenc") + 8 + 6                                                     # (the tenc's is_protected byte)
+    assert y[3].data[open_at] == 1
+    data_y = [y[0].data, _cut_to(y[1], len(x[1].data)), y[2].data, y[3].data[:open_at] + b"\0" + y[3].data[open_at + 1:]]
+    assert [len(d) for d in data_y] == [len(m.data) for m in x]
+    jobs = {"X": BC.Job([BC.stream(m, have_key=k != 3) for k, m in enumerate(x)]),
+            "Y": BC.Job([BC.stream(raw, capacity=m.n, run_capacity=len(m.runs), dst_capacity=len(m.data), key=m.key, kid=m.kid, have_key=k != 3, sub_capacity=m.subsamples)
+                         for k, (raw, m) in enumerate(zip(data_y, x))])}
+    assert jobs["X"].n_subsamples == jobs["Y"].n_subsamples
+    sx, sy = ([int(r["cenc"]["mp4f"]["status"]) for r in jobs[w].want_results] for w in "XY")
+    assert sx == [0, 0, 0, capi.CENC_NO_KEY] and sy == [0, 0, 0, 0], (sx, sy)
+    cut = jobs["Y"].want_results[1]["cenc"]["mp4f"]
+    assert (int(cut["samples"]), int(cut["samples_refused"]), int(cut["samples_available"])) == (9, 1, 6) and not jobs["X"].want_results["cenc"]["mp4f"]["samples_refused"].any()
+    nx, ny = ([int(r["subsamples"]) for r in jobs[w].want_results] for w in "XY")
+    assert nx == [0, 14, 18, 0] and ny == [0, 14, 10, 0], (nx, ny)
+    return _frag_tables("cbcs", jobs, lambda j, s, d: capi.cbcs_batch_check(j.descs, j.n_packets, j.n_runs, j.n_subsamples, s, d),
+                        lambda ctx, j, s, d: ctx.cbcs_batch(j.descs, j.n_packets, j.n_runs, j.n_subsamples, s, d),
+                        lambda ctx, b, s, d, stream: ctx.cbcs_run(b, s, d, stream), lambda ctx, *a: ctx.cbcs_results(*a),
+                        lambda ctx, b: ctx.cbcs_paths(b)["route"])
+
+
+# ---------------------------------------------------------------- Ogg Vorbis packets (vorbis_cases, vorbis_frames.batch_tables)
+VORBIS_SPECTRA = 4       # the packets a stream whose spectra verify() compares with the model's, at the least
+
+
+def _vorbis():
+    """Three streams of tests/vorbis_cases.py, each with ONE setup image for both runs: mono_64_128 packets [0, 9) and [30, 39) packed
+    16-bit, six_128_512 [0, 6) and [8, 14) in 32-bit planes, stereo_256_2048 [0, 5) and [20, 25) packed 16-bit.  Every pair of packets
+    is padded with zeros to the longer one's length (the model decodes the padded bytes too: a packet that ends early reads zeros
+    either way).  In Y the mono stream's packet 3 is vorbis_cases.BAD_MODE and the six-channel stream's packet 2 a header packet,
+    both padded: packets that were OK in run X are passed over in run Y, and nothing of their floors, residues or spectra may show.
+    max_samples cuts the mono stream's last packet short in X.  The PCM is the one thing here that is not bit-exact against the model
+    (tests/test_gpu_vorbis_textbook.py): sample_types and written say where samples lie and which of them a run writes."""
+    import vorbis_cases as VC
+    import vorbis_frames as VF
+    import vorbis_textbook as TB
+    shapes = [("mono_64_128", (0, 30), 9), ("six_128_512", (0, 8), 6), ("stereo_256_2048", (0, 20), 5)]
+    planar = [False, True, False]
+    packets = {"X": [], "Y": []}
+    for k, (name, (a, b), n) in enumerate(shapes):
+        st = VC.stream(name)
+        xs, ys = list(st.packets[a:a + n]), list(st.packets[b:b + n])
+        if k == 0:
+            ys[3] = VC.BAD_MODE
+        if k == 1:
+            ys[2] = b"\x05vorbis"
+        xs, ys = _padded(xs, ys)
+        packets["X"].append(xs)
+        packets["Y"].append(ys)
+    streams = {w: [VF.Stream(VC.stream(name).ident, VC.stream(name).setup, p) for (name, _, _), p in zip(shapes, packets[w])] for w in "XY"}
+    uncut = [TB.decode_stream(s.model, s.packets) for s in streams["X"]]
+    whole = [pcm.shape[1] for _, _, pcm in uncut]
+    caps = [whole[0] - 7] + [n * s.model.bs[1] // 2 for (_, _, n), s in list(zip(shapes, streams["X"]))[1:]]
+    tables, dst_bytes = {}, 0
+    for w in "XY":
+        parts = [VF.batch_tables(capi, [s], planar=p, max_samples=[cap]) for s, p, cap in zip(streams[w], planar, caps)]
+        # one batch of the three: batch_tables lays streams of one output form, so the three are laid one behind the other here
+        blob, descs, rows, src, at = [], [], [], bytearray(), 0
+        for image, d, pk, s, n, _ in parts:
+            d, pk = d.copy(), pk.copy()
+            d["image_offset"], d["first_packet"], d["dst_offset"] = sum(im.size for im in blob), sum(r.size for r in rows), at + 8
+            pk["src_offset"] += len(src)
+            blob.append(image)
+            descs.append(d)
+            rows.append(pk)
+            src += s.tobytes()[:-4] + b"\xee" * (-(s.size - 4) % 4)
+            at += 8 + ((n + 3) & ~3)                                       # eight guard bytes in front of every stream's share
+        tables[w] = (np.concatenate(blob), np.concatenate(descs), np.concatenate(rows), _u8(bytes(src) + bytes(4)))
+        dst_bytes = at + 8
+    _same_tables(*[(tables["X"][k], tables["Y"][k]) for k in range(3)])
+    blob, descs, rows = tables["X"][:3]
+    src = {w: tables[w][3] for w in "XY"}
+    dst0 = np.full(dst_bytes, 0xA5, dtype=np.uint8)
+    models = {w: [TB.decode_stream(s.model, s.packets, cap) for s, cap in zip(streams[w], caps)] for w in "XY"}
+    want, written, ranges, sample_types = {}, {}, [], []
+    for w in "XY":
+        arena, mask = dst0.copy(), np.zeros(dst_bytes, dtype=bool)
+        for d, s, p, (recs, _, pcm) in zip(descs, streams[w], planar, models[w]):
+            at, ch, n = int(d["dst_offset"]), s.model.channels, pcm.shape[1]
+            if p:
+                stride = int(d["dst_plane_stride"])
+                for c in range(ch):
+                    arena[at + c * stride:at + c * stride + 4 * n] = np.frombuffer(pcm[c].astype("<i4").tobytes(), dtype=np.uint8)
+                    mask[at + c * stride:at + c * stride + 4 * n] = True
+            else:
+                arena[at:at + 2 * ch * n] = np.frombuffer(VC.pcm_s16be(pcm), dtype=np.uint8)
+                mask[at:at + 2 * ch * n] = True
+        want[w], written[w] = arena, mask
+    for d, s, p, cap in zip(descs, streams["X"], planar, caps):
+        ranges.append((int(d["dst_offset"]), cap * s.model.channels * (4 if p else 2)))
+        sample_types.append("<i4" if p else ">i2")
+    records = {w: [tuple(int(v) for v in r) for recs, _, _ in models[w] for r in recs] for w in "XY"}
+    summary = {}
+    for w in "XY":
+        rows_w = []
+        for recs, _, pcm in models[w]:
+            ok = next((k for k, r in enumerate(recs) if r[0] != TB.OK), len(recs))
+            rows_w.append((ok, recs[ok][0] if ok < len(recs) else 0, pcm.shape[1]))
+        summary[w] = rows_w
+    mx = models["X"]
+    assert [s[:2] for s in summary["X"]] == [(9, 0), (6, 0), (5, 0)] and [s[0] for s in summary["Y"]] == [3, 2, 5] and all(s[1] for s in summary["Y"][:2])
+    assert 0 < mx[0][0][-1][3] == uncut[0][0][-1][3] - 7 and sum(r[3] for r in mx[0][0]) == caps[0]      # (max_samples cut the mono stream's last packet)
+    first = np.concatenate([[0], np.cumsum([len(p) for p in packets["X"]])])
+
+    def verify(ctx, b, which):
+        res, pres = ctx.vorbis_results(b, len(descs), len(rows))
+        got = [(int(r["status"]), int(r["mode"]), int(r["blocksize"]), int(r["samples"]), int(r["position"])) for r in pres]
+        assert got == records[which] and not pres["reserved"].any(), (which, got, records[which])
+        got = [(int(r["packets_ok"]), int(r["first_bad_status"]), int(r["samples"])) for r in res]
+        assert got == summary[which] and not res["reserved"].any(), (which, got, summary[which])
+        for i, (recs, spectra, _) in enumerate(models[which]):
+            checked = 0
+            for k, spec in enumerate(spectra):
+                if spec is None:
+                    continue
+                for c in range(spec.shape[0]):
+                    mine = ctx.vorbis_spectrum(b, int(first[i]) + k, c, recs[k][2] // 2)
+                    assert mine.tobytes() == spec[c].tobytes(), (which, i, k, c)
+                checked += 1
+            assert checked >= VORBIS_SPECTRA, (which, i, checked)
+
+    return Pair("vorbis", src, dst0, want, ranges, summary,
+                check=lambda: capi.vorbis_batch_check(descs, rows, blob, src["X"].size, dst_bytes),
+                create=lambda ctx: ctx.vorbis_batch(descs, rows, blob, src["X"].size, dst_bytes),
+                run=lambda ctx, b, s, d, stream: ctx.vorbis_run(b, s, d, stream), verify=verify,
+                tables={w: (np.array(records[w], dtype="<i8").tobytes(),) for w in "XY"},
+                route=lambda ctx, b: ctx.vorbis_paths(b)["route"], sample_types=sample_types, written=written)
+
+
+# ---------------------------------------------------------------- MPEG transport streams and ADTS (ts_cases)
+def _ts():
+    """Three streams, Y's with other elementary bytes: three PES packets (Y: the counter of the fourth audio packet jumps); four PES
+    packets (Y: the sync byte of a packet in the middle is lost -- it is stepped over, and the counter jumps behind it); four PES
+    packets in X and three in Y in as many transport packets: the fourth record of that stream must be the table's fill in run Y."""
+    import ts_cases as TC
+
+    def packets(w):
+        rng = TC.Lcg(301 if w == "X" else 302)
+        a = TC.head_packets() + TC.audio_run(rng, n_pes=3)[0]
+        b = TC.head_packets() + TC.audio_run(rng, n_pes=4, es_bytes=(200, 500, 90, 333))[0]
+        c = TC.head_packets() + TC.audio_run(rng, n_pes=4 if w == "X" else 3, es_bytes=(300, 41, 700, 100) if w == "X" else (300, 900, 100))[0]
+        if w == "Y":
+            a[5] = a[5][:3] + bytes([a[5][3] & 0xF0 | (a[5][3] + 5) & 15]) + a[5][4:]
+            b[5] = b"\x48" + b[5][1:]
+        return [a, b, c]
+
+    data = {w: [b"".join(p) for p in packets(w)] for w in "XY"}
+    assert [len(d) for d in data["X"]] == [len(d) for d in data["Y"]]
+    caps = [max(len(TC.TX.demux(data[w][i], 0, 0, 0, 0)["pes"]) for w in "XY") for i in range(3)]
+    jobs = {w: TC.Job([TC.stream(d, pes_capacity=cap) for d, cap in zip(data[w], caps)]) for w in "XY"}
+    x, y = jobs["X"], jobs["Y"]
+    _same_tables((x.descs, y.descs), (x.dst0, y.dst0))
+    assert x.n_pes == y.n_pes and [len(m["pes"]) for m in x.models] == [3, 4, 4] and [len(m["pes"]) for m in y.models] == [3, 4, 3]
+    assert [m["cc_jumps"] for m in x.models] == [0, 0, 0] and y.models[0]["cc_jumps"] > 0 and (x.models[1]["bad_sync"], y.models[1]["bad_sync"]) == (0, 1)
+
+    def results_of(job):
+        res, pes = np.zeros(len(job.streams), dtype=capi.TS_STREAM_RESULT), np.zeros(job.n_pes, dtype=capi.TS_PES)       # (the table's fill is zeros)
+        for i, (d, m) in enumerate(zip(job.descs, job.models)):
+            for f in TC.RESULT_FIELDS:
+                res[i][f] = m[f]
+            res[i]["pes_packets"], res[i]["bytes_delivered"] = len(m["pes"]), len(m["run"])
+            for k, rec in enumerate(m["pes"][:int(d["pes_capacity"])]):
+                for f in TC.PES_FIELDS:
+                    pes[int(d["pes_first"]) + k][f] = rec[f]
+        return res, pes
+
+    want = {w: results_of(jobs[w]) for w in "XY"}
+
+    def verify(ctx, b, which):
+        res, pes = ctx.ts_results(b, len(x.streams), x.n_pes)
+        TC.assert_same(res, pes, jobs[which].want.tobytes(), jobs[which])                                                 # (the arena is the caller's to compare)
+        assert res.tobytes() == want[which][0].tobytes(), (which, res, want[which][0])
+        assert pes.tobytes() == want[which][1].tobytes(), (which, np.flatnonzero([a.tobytes() != b.tobytes() for a, b in zip(pes, want[which][1])]).tolist())
+
+    return Pair("ts", {w: jobs[w].src.copy() for w in "XY"}, x.dst0.copy(), {w: jobs[w].want.copy() for w in "XY"},
+                [(int(d["dst_offset"]), int(d["dst_capacity"])) for d in x.descs], {w: want[w][0].tobytes() for w in "XY"},
+                check=lambda: capi.ts_batch_check(x.descs, x.n_pes, x.src.size, x.dst0.size),
+                create=lambda ctx: ctx.ts_batch(x.descs, x.n_pes, x.src.size, x.dst0.size),
+                run=lambda ctx, b, s, d, stream: ctx.ts_run(b, s, d, stream), verify=verify, tables={w: (want[w][1].tobytes(),) for w in "XY"},
+                route=lambda ctx, b: ctx.ts_paths(b)["route"])
+
+
+def _adts():
+    """Three streams and no destination arena: the frame table and the results are what a run leaves.  Y has other payloads; junk between
+    two frames where X has a frame of that length (an interruption, skipped bytes); a header whose length field is wrong, so that the
+    chain loses its footing there and the table has fewer frames -- the surplus rows must be the table's fill; and a stream that is
+    recognised from its second frame on where X's begins at byte 0."""
+    import ts_cases as TC
+
+    def streams(w):
+        rng = TC.Lcg(77 if w == "X" else 78)
+        f = [TC.adts_frame(TC.clean(rng.bytes(n)), protection_absent=bool(k % 3)) for k, n in enumerate((40, 100, 33, 64, 2, 250, 90, 17))]
+        a, b, c = list(f[:5]), list(f[3:8]), list(f[1:6])
+        if w == "Y":
+            a[2] = TC.clean(rng.bytes(len(a[2])))
+            b[2] = TC.adts_frame(TC.clean(rng.bytes(len(b[2]) - 7)), length=len(b[2]) + 9)[:len(b[2])]
+            c[0] = TC.clean(rng.bytes(len(c[0])))
+        return [b"".join(a), b"".join(b), b"".join(c)]
+
+    data = {w: streams(w) for w in "XY"}
+    assert [len(d) for d in data["X"]] == [len(d) for d in data["Y"]]
+    caps = [max(len(TC.TX.adts_chain(data[w][i], 0)["frames"]) for w in "XY") for i in range(3)]
+    jobs = {w: TC.AdtsJob([TC.adts_stream(d, frame_capacity=cap) for d, cap in zip(data[w], caps)]) for w in "XY"}
+    x, y = jobs["X"], jobs["Y"]
+    _same_tables((x.descs, y.descs))
+    assert x.n_frames == y.n_frames and x.src.size == y.src.size
+    assert [len(m["frames"]) for m in x.models] == [5, 5, 5] and all(len(my["frames"]) < 5 for my in y.models)
+    assert [m["interruptions"] for m in x.models] == [0, 0, 0] and y.models[0]["interruptions"] == 1 and y.models[2]["first_frame_offset"] > 0
+
+    def results_of(job):
+        res, frames = np.zeros(len(job.streams), dtype=capi.ADTS_STREAM_RESULT), np.zeros(job.n_frames, dtype=capi.ADTS_FRAME)   # (the table's fill is zeros)
+        for i, (d, m) in enumerate(zip(job.descs, job.models)):
+            for f in TC.ADTS_RESULT_FIELDS:
+                res[i][f] = m[f]
+            res[i]["frames"] = len(m["frames"])
+            for k, rec in enumerate(m["frames"][:int(d["frame_capacity"])]):
+                for f in TC.FRAME_FIELDS:
+                    frames[int(d["frame_first"]) + k][f] = rec[f]
+        return res, frames
+
+    want = {w: results_of(jobs[w]) for w in "XY"}
+
+    def verify(ctx, b, which):
+        res, frames = ctx.adts_results(b, len(x.streams), x.n_frames)
+        TC.assert_same_adts(res, frames, jobs[which])
+        assert res.tobytes() == want[which][0].tobytes(), (which, res, want[which][0])
+        assert frames.tobytes() == want[which][1].tobytes(), (which, np.flatnonzero([a.tobytes() != b.tobytes() for a, b in zip(frames, want[which][1])]).tolist())
+
+    return Pair("adts", {w: jobs[w].src.copy() for w in "XY"}, None, {"X": None, "Y": None}, [], {w: want[w][0].tobytes() for w in "XY"},
+                check=lambda: capi.adts_batch_check(x.descs, x.n_frames, x.src.size),
+                create=lambda ctx: ctx.adts_batch(x.descs, x.n_frames, x.src.size),
+                run=lambda ctx, b, s, d, stream: ctx.adts_run(b, s, stream), verify=verify, tables={w: (want[w][1].tobytes(),) for w in "XY"},
+                route=lambda ctx, b: ctx.adts_paths(b)["route"])
+
+
+# ---------------------------------------------------------------- the RAOP receiver (raop_rx_cases.Job)
+def _raop_rx():
+    """Three streams and no destination arena: the records, the packet rows and the results are what a run leaves.  X: every frame in
+    order, some of them as resend responses on the control port.  Y: datagrams of the same lengths on the same ports with other
+    payloads -- a sync datagram where X has a resent frame, a frame missing (the frames behind it wait), the late resend that fills
+    the gap, a resend of a frame long out (a duplicate); a stream that ends inside a repair, with a duplicate of its first waiting
+    frame (a resend request: n_ranges, n_pending); and a stream that starts from a running state, with a sync datagram that changes
+    the delay and a late resend."""
+    import raop_rx_cases as RC
+    A, R, S = RC.A, RC.R, RC.S
+    sizes = [(9, 30, 4, 100, 7, 41, 250, 5, 12, 64), (16, 1, 80, 33, 200, 8), (4, 120, 6, 50, 77)]
+
+    def grams(w):
+        rng = RC.Lcg(61 if w == "X" else 67)
+        p = [[rng.bytes(n) for n in row] for row in sizes]
+        if w == "X":
+            a = [A(10), A(11), R(12), A(13), A(14), R(15), A(16), A(17), R(18), A(19)]
+            b = [A(100), A(101), A(102), A(103), A(104), A(105)]
+            c = [R(200), A(201), A(202), R(203), A(204)]
+        else:
+            a = [A(10), A(11), S(5000, 11025), A(13), A(14), R(12), A(15), A(16), R(14), A(17)]
+            b = [A(100), A(101), A(103), A(104), A(103), A(106)]
+            c = [S(7000, 11025 + 500), A(200), A(202), R(201), A(203)]
+        out = []
+        for made, payloads in zip((a, b, c), p):
+            row = []
+            for (gram, port), body in zip(made, payloads):
+                sync = port == RC.RX.CONTROL and gram[1] & 0x7f == 0x54
+                head = len(gram) - 4                                       # (the builders' own four payload bytes are replaced)
+                row.append((gram if sync else gram[:head] + body, port))
+            out.append(row)
+        return out
+
+    made = {w: grams(w) for w in "XY"}
+    states = [None, None, RC.running_state(199, latency=11025)]
+    jobs = {w: RC.Job([RC.stream(g, state, max_frames=5) for g, state in zip(made[w], states)]) for w in "XY"}
+    x, y = jobs["X"], jobs["Y"]
+    _same_tables((x.d_streams, y.d_streams), (x.d_grams, y.d_grams))
+    X = RC.RX
+    assert all(r["disposition"] == X.OUTPUT for recs in x.recs for r in recs) and all(not r["ranges"] and not r["n_pending"] for r in x.results)
+    assert [r["disposition"] for r in y.recs[0]] == [X.OUTPUT, X.OUTPUT, X.SYNC] + [X.OUTPUT] * 5 + [X.DUPLICATE, X.OUTPUT]
+    assert [r["order"] for r in y.recs[0]][3:6] == [3, 4, 2]                           # (the late resend goes out in front of the two that waited)
+    assert [r["disposition"] for r in y.recs[1]] == [X.OUTPUT, X.OUTPUT, X.PENDING, X.PENDING, X.DUPLICATE, X.PENDING]
+    assert y.results[1]["n_pending"] == 3 and y.results[1]["ranges"] == [(102, 102), (105, 105)]
+    assert [r["disposition"] for r in y.recs[2]] == [X.SYNC] + [X.OUTPUT] * 4 and y.recs[2][1]["events"] & X.DELAY and [r["order"] for r in y.recs[2]][1:] == [0, 2, 1, 3]
+    summary = {w: jobs[w].want_results.tobytes() for w in "XY"}
+    tables = {w: (jobs[w].want_records.tobytes(), jobs[w].want_rows.tobytes()) for w in "XY"}
+
+    def verify(ctx, b, which):
+        job = jobs[which]
+        sres, recs = ctx.raop_rx_results(b, len(job.streams), len(job.table))
+        RC.assert_same(sres, recs, ctx.raop_rx_packets(b, len(job.table)), job)
+
+    return Pair("raop_rx", {w: _u8(jobs[w].src) for w in "XY"}, None, {"X": None, "Y": None}, [], summary,
+                check=lambda: capi.raop_rx_batch_check(x.d_streams, x.d_grams, len(x.src)),
+                create=lambda ctx: ctx.raop_rx_batch(x.d_streams, x.d_grams, len(x.src)),
+                run=lambda ctx, b, s, d, stream: ctx.raop_rx_run(b, s, stream), verify=verify, tables=tables,
+                route=lambda ctx, b: ctx.batch_paths(b)["raop_rx_route"])
+
+
+_BUILDERS = {"flac": _flac, "alac": _alac, "raop": _raop, "ohm_rx": _ohm_rx, "ogg": _ogg, "mp4": _mp4, "iff": _iff, "dsd_file": _dsd_file,
+             "mp4f": _mp4f, "cenc": _cenc, "cbcs": _cbcs, "vorbis": _vorbis, "ts": _ts, "adts": _adts, "raop_rx": _raop_rx}
 
 
 @functools.lru_cache(maxsize=None)

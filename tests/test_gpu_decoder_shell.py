@@ -9,7 +9,13 @@ The batches are the smallest there are:
     flac   tests/golden/flac_decode/tiny_s16_stereo_44k1_b16.flac, one stream
     alac   tests/alac_cases.handmade: hand_stereo8 -- one stereo packet of eight samples, frame length 64, planes
     raop   two streams: that packet encrypted under a fixed key and IV, planes; and a PLAINTEXT stream of payloads of 20, 0 and 12
-           bytes (one block with a tail, nothing, a tail only)"""
+           bytes (one block with a tail, nothing, a tail only)
+
+The same three pins for the families that came behind the shared shell and keep three tables or a spectrum beside their results:
+
+    mp4f, cenc, cbcs   one gathered file of three samples in one run (tests/mp4f_cases.py, cenc_cases.py, cbcs_cases.py); the run, packet
+           and sample tables are each asked for before a run and with a wrong count
+    vorbis tests/vorbis_cases.py's mono_64_128, packets [0, 4); ohgpu_vorbis_batch_spectrum before a run and out of range"""
 import ctypes as C
 
 import numpy as np
@@ -17,14 +23,20 @@ import pytest
 
 import alac_cases as AC
 import alac_textbook as T
+import cbcs_cases as BC
+import cenc_cases as CC
 import flac_cases as FC
+import mp4f_cases as MF
 import raop_cases as RC
 import raop_textbook as R
+import vorbis_cases as VC
+import vorbis_frames as VF
 from ohpipeline_amd import capi
 
 pytestmark = pytest.mark.gpu
 
-FAMILIES = ("flac", "alac", "raop")
+FRAGMENTED = ("mp4f", "cenc", "cbcs")
+FAMILIES = ("flac", "alac", "raop") + FRAGMENTED + ("vorbis",)
 KEY, IV = bytes(range(16)), bytes(range(16, 32))
 KEY2, IV2 = bytes(range(32, 48)), bytes(range(48, 64))
 
@@ -37,8 +49,9 @@ class Case:
     """One batch: `head` = the arguments between the context and the source (create: the arena sizes), `counts` = (streams, packets)
     (FLAC: (streams,)), the source arena and the destination arena's size."""
 
-    def __init__(self, family, head, keep, counts, src, dst_bytes):
+    def __init__(self, family, head, keep, counts, src, dst_bytes, tables=()):
         self.family, self.head, self.keep, self.counts, self.src, self.dst_bytes = family, head, keep, counts, src, dst_bytes
+        self.tables = tables                    # the fragmented families: (the call's suffix, the row type, the batch's row count) of results, runs, packets, samples
 
 
 class Fixtures:
@@ -53,6 +66,14 @@ class Fixtures:
         descs, packets = RC.capi_tables(self.job)
         self.cases["raop"] = Case("raop", (_ptr(descs), descs.size, _ptr(packets), packets.size), [descs, packets], (descs.size, packets.size),
                                   np.frombuffer(self.job.src, dtype=np.uint8), len(self.job.dst0))
+
+        for family, job, result in (("mp4f", MF.Job([MF.stream(MF.simple([3]))]), capi.MP4F_STREAM_RESULT), ("cenc", CC.Job([CC.stream(CC.simple([3]))]), capi.CENC_STREAM_RESULT),
+                                    ("cbcs", BC.Job([BC.stream(BC.build([40, 50, 64], iv_size=16, listed=False))]), capi.CBCS_STREAM_RESULT)):
+            head = (_ptr(job.descs), 1, job.n_packets, job.n_runs) + ((job.n_subsamples,) if family == "cbcs" else ())
+            tables = (("results", result, 1), ("runs", capi.MP4F_RUN, job.n_runs), ("packets", capi.ALAC_PACKET, job.n_packets), ("samples", capi.MP4_SAMPLE, job.n_packets))
+            self.cases[family] = Case(family, head, [job.descs], (1, job.n_packets, job.n_runs), job.src, job.dst_bytes, tables)
+        blob, descs, packets, src, dst_bytes, _ = VF.batch_tables(capi, [VC.stream("mono_64_128")], ranges=[(0, 4)])
+        self.cases["vorbis"] = Case("vorbis", (_ptr(descs), 1, _ptr(packets), packets.size, _ptr(blob), blob.size), [descs, packets, blob], (1, packets.size), src, dst_bytes)
 
     def close(self):
         self.ctx.close()
@@ -82,8 +103,20 @@ class Fixtures:
         if family == "flac":
             res = np.zeros(counts[0], dtype=capi.FLAC_STREAM_RESULT)
             return capi.lib().ohgpu_flac_batch_results(self.ctx.handle, batch, _ptr(res), res.size)
-        sres, pres = np.zeros(counts[0], dtype=capi.ALAC_STREAM_RESULT), np.zeros(counts[1], dtype=capi.ALAC_PACKET_RESULT)
+        if family in FRAGMENTED:
+            return self.fetch(family, batch, "results", self.cases[family].tables[0][1], counts[0])
+        kinds = (capi.VORBIS_STREAM_RESULT, capi.VORBIS_PACKET_RESULT) if family == "vorbis" else (capi.ALAC_STREAM_RESULT, capi.ALAC_PACKET_RESULT)
+        sres, pres = np.zeros(counts[0], dtype=kinds[0]), np.zeros(counts[1], dtype=kinds[1])
         return getattr(capi.lib(), f"ohgpu_{family}_batch_results")(self.ctx.handle, batch, _ptr(sres), sres.size, _ptr(pres), pres.size)
+
+    def fetch(self, family, batch, suffix, kind, count):
+        """ohgpu_<family>_batch_<suffix> with room for `count` rows -> the library's code"""
+        rows = np.zeros(count, dtype=kind)
+        return getattr(capi.lib(), f"ohgpu_{family}_batch_{suffix}")(self.ctx.handle, batch, _ptr(rows), rows.size)
+
+    def spectrum(self, batch, packet, channel, n_values):
+        out = np.zeros(max(n_values, 1), dtype=np.float32)
+        return capi.lib().ohgpu_vorbis_batch_spectrum(self.ctx.handle, batch, packet, channel, _ptr(out), n_values)
 
 
 @pytest.fixture(scope="module")
@@ -99,9 +132,21 @@ def test_a_batch_that_has_not_run(fx, family):
     try:
         assert fx.results(family, b, case.counts) == capi.ERR_INVALID
         assert capi.last_error() == f"ohgpu_{family}_batch_results: the batch has not run"
-        ms = (C.c_float * 4)()
+        ms = (C.c_float * 8)()                                        # (the families have three to six phases)
         assert getattr(capi.lib(), f"ohgpu_{family}_batch_phase_ms")(fx.ctx.handle, b, ms) == capi.ERR_INVALID
         assert capi.last_error() == f"ohgpu_{family}_batch_phase_ms: the batch has not run"
+        for suffix, kind, count in case.tables:                       # every table of its own
+            assert count > 0 and fx.fetch(family, b, suffix, kind, count) == capi.ERR_INVALID
+            assert capi.last_error() == f"ohgpu_{family}_batch_{suffix}: the batch has not run"
+        if family == "vorbis":                                        # a mono stream of four packets, rows of 64 values
+            assert fx.spectrum(b, 0, 0, 32) == capi.ERR_INVALID
+            assert capi.last_error() == "ohgpu_vorbis_batch_spectrum: the batch has not run"
+            assert fx.spectrum(b, 4, 0, 32) == capi.ERR_INVALID
+            assert capi.last_error() == "ohgpu_vorbis_batch_spectrum: packet 4 of 4"
+            assert fx.spectrum(b, 0, 1, 32) == capi.ERR_INVALID
+            assert capi.last_error() == "ohgpu_vorbis_batch_spectrum: channel 1, 32 values (the stream has 1 channels and rows of 64)"
+            assert fx.spectrum(b, 0, 0, 65) == capi.ERR_INVALID
+            assert capi.last_error() == "ohgpu_vorbis_batch_spectrum: channel 0, 65 values (the stream has 1 channels and rows of 64)"
     finally:
         fx.ctx.batch_destroy(b)
 
@@ -112,6 +157,14 @@ def test_results_with_a_wrong_count(fx, family):
     try:
         assert fx.results(family, b, (case.counts[0] + 1,) + case.counts[1:]) == capi.ERR_INVALID
         assert "room for" in capi.last_error(), capi.last_error()
+        for suffix, kind, count in case.tables:                       # a row too many, a row too few: each table says what it has
+            for wrong in (count + 1, count - 1):
+                assert fx.fetch(family, b, suffix, kind, wrong) == capi.ERR_INVALID
+                noun = "results, the batch has 1 streams" if suffix == "results" else f"rows, the batch's table has {count}"
+                assert capi.last_error() == f"ohgpu_{family}_batch_{suffix}: room for {wrong} {noun}", capi.last_error()
+        if family == "vorbis":
+            assert fx.results(family, b, (case.counts[0], case.counts[1] - 1)) == capi.ERR_INVALID
+            assert capi.last_error() == "ohgpu_vorbis_batch_results: room for 3 packet results, the batch has 4 packets"
     finally:
         fx.ctx.batch_destroy(b)
 
@@ -120,7 +173,7 @@ def test_results_with_a_wrong_count(fx, family):
 def test_process_host_with_a_null_buffer(fx, family):
     case = fx.cases[family]
     dst = np.zeros(case.dst_bytes, dtype=np.uint8)
-    tail = (None, None, 0, None) if family == "flac" else (None, None)
+    tail = (None, None, 0, None) if family == "flac" else (None,) * 4 if family in FRAGMENTED else (None, None)
     before = fx.ctx.host_transfer_stats()
     code = getattr(capi.lib(), f"ohgpu_{family}_process_host")(fx.ctx.handle, *case.head, None, case.src.size, _ptr(dst), dst.size, *tail)
     assert case.src.size > 0 and code == capi.ERR_INVALID

@@ -1,12 +1,17 @@
-"""A decoder's or demultiplexer's batch on streams other than the context's own, for the seven families whose batch keeps per-run
-device records (flac, alac, raop, ohm_rx, ogg, mp4, iff: counters, candidate and piece lists, records, scratch rows).  Their runs never
+"""A decoder's or demultiplexer's batch on streams other than the context's own, for the fifteen families whose batch keeps per-run
+device records (flac, alac, raop, ohm_rx, ogg, mp4, iff, dsd_file; mp4f, cenc, cbcs, vorbis, ts, adts, raop_rx: counters, candidate and
+piece lists, records, row tables, scratch rows).  Their runs never
 refuse a stream: a run on another stream than the last one's first waits, on the host, for the batch's last run (run_begin,
 csrc/api_common.h) -- on the event that run recorded at its end, because the earlier stream may have been destroyed by then.
 
 One batch and two source arenas X and Y per family (tests/stream_switch_cases.py; tests/test_stream_switch_cases.py shows on the CPU
 that every stream's output differs between the two): a run that met the other run's records, or a wait that was left out, cannot give
-the model's bytes by accident.  The WHOLE destination arenas are compared with the models', the results and tables too.  Everything
-is exact."""
+the model's bytes by accident.  The WHOLE destination arenas are compared with the models', the results and tables too -- the whole
+tables of the seven newer families, so that a row run X wrote and run Y does not must be back at the table's fill.  Everything is exact
+but Vorbis's PCM, which tests/test_gpu_vorbis_textbook.py bounds at 1 LSB from the model: there every byte a run does not write is
+compared exactly, every sample within 1 LSB, the spectra bit for bit, and every later run over X with the first one byte for byte.
+The seven newer families run on both routes: the launches, and the plain route (kernel variant 1 at create), whose per-run state is
+its own."""
 import gc
 import time
 
@@ -39,16 +44,28 @@ def scratch(ctx):
 
 
 class Rig:
-    """One family's batch, both source arenas and a destination arena for each on the device, two streams of the caller's."""
+    """One family's batch, both source arenas and a destination arena for each on the device, two streams of the caller's.  variant:
+    None -- the batch is created as the context stands --, or the kernel variant it is created under (0: the launches, 1: the plain
+    route, which keeps per-run state of its own), asserted through the family's own paths call; the context is back at 0 afterwards."""
 
-    def __init__(self, ctx, family):
+    def __init__(self, ctx, family, variant=None):
         self.ctx, self.p = ctx, SC.pair(family)
         p = self.p
         p.check()
         self.d_src = {w: ctx.upload(p.src[w]) for w in "XY"}
         self.d_dst = {w: ctx.upload(p.dst0) if p.dst0 is not None else None for w in "XY"}
-        self.batch = p.create(ctx)
+        if variant is None:
+            self.batch = p.create(ctx)
+        else:
+            ctx.set_kernel_variant(variant)
+            try:
+                self.batch = p.create(ctx)
+            finally:
+                ctx.set_kernel_variant(0)
+            assert p.route(ctx, self.batch) == (2 if variant else 1)
         self.streams = {"A": ctx.stream_create(), "B": ctx.stream_create()}
+        self.label = family + {None: "", 0: " (launches)", 1: " (plain)"}[variant]
+        self.first_x = None                      # (Vorbis: the arena of the first checked run over X)
 
     def refill(self, which):
         if self.p.dst0 is not None:
@@ -61,17 +78,32 @@ class Rig:
     def arena_is_the_models(self, which):
         if self.p.dst0 is None:
             return
-        got, want = self.ctx.download(self.d_dst[which], self.p.dst0.size), self.p.want[which]
-        bad = np.flatnonzero(got != want)
-        assert bad.size == 0, f"arena {which}: {bad.size} of {want.size} bytes differ, the first at {bad[:8].tolist()}"
+        p = self.p
+        got, want = self.ctx.download(self.d_dst[which], p.dst0.size), p.want[which]
+        if p.sample_types is None:
+            bad = np.flatnonzero(got != want)
+            assert bad.size == 0, f"arena {which}: {bad.size} of {want.size} bytes differ, the first at {bad[:8].tolist()}"
+            return
+        # Vorbis: every byte the model does not write is the fill, exactly; inside a stream's range the samples lie within 1 LSB
+        bad = np.flatnonzero((got != want) & ~p.written[which])
+        assert bad.size == 0, f"arena {which}: {bad.size} bytes differ that the run does not write, the first at {bad[:8].tolist()}"
+        for (off, n), kind in zip(p.ranges, p.sample_types):
+            mine, model = (a[off:off + n].view(kind).astype(np.int64) for a in (got, want))
+            worst = int(np.abs(mine - model).max())
+            assert worst <= 1, f"arena {which}, the range at {off}: a sample {worst} LSB from the model's"
+        return got
 
     def checked(self, which, stream):
         """a run from a fresh arena, waited for and compared: the arena, the results, the tables"""
         self.refill(which)
         self.run(which, stream)
         self.ctx.sync(stream)
-        self.arena_is_the_models(which)
+        got = self.arena_is_the_models(which)
         self.p.verify(self.ctx, self.batch, which)
+        if got is not None and which == "X":     # (beside the model, not in its place: a run over X writes what the first one wrote)
+            if self.first_x is None:
+                self.first_x = got
+            assert np.array_equal(got, self.first_x), "a later run over X wrote other bytes than the first"
 
     def destroy_stream(self, name):
         self.ctx.stream_destroy(self.streams.pop(name))
@@ -88,12 +120,23 @@ class Rig:
 
 @pytest.fixture
 def rig(ctx, request):
-    r = Rig(ctx, request.param)
+    r = Rig(ctx, *request.param)
     yield r
     r.close()
 
 
-families = pytest.mark.parametrize("rig", SC.FAMILIES, indirect=True)
+def _cases():
+    """the first eight families as they were; the newer ones on both routes"""
+    out = []
+    for family in SC.FAMILIES:
+        if family in SC.BOTH_ROUTES:
+            out += [pytest.param((family, 0), id=f"{family}-launches"), pytest.param((family, 1), id=f"{family}-plain")]
+        else:
+            out.append(pytest.param((family, None), id=family))
+    return out
+
+
+families = pytest.mark.parametrize("rig", _cases(), indirect=True)
 
 
 @families
@@ -105,18 +148,27 @@ def test_a_run_on_another_stream_waits_for_the_last(ctx, scratch, rig):
 
     The fill proves nothing unless it outlasts the host's way to run Y: the interval on the device (an event in front of the fill,
     one behind run X) must be longer than the host's (from before the first event record to just before the call of run Y), or the
-    test fails.  MPEG-4 has no destination arena: its tables are read after each of the two waits, and are run Y's both times.
+    test fails.  MPEG-4, ADTS and the RAOP receiver have no destination arena: their tables are read after each of the two waits, and
+    are run Y's both times.
 
     The fill is four copies of 256 MiB from pinned memory, each a call of 5 us that keeps the stream busy for 4.7 ms.  A device fill
     (ohgpu_memset) does not do: measured on an MI355X, 1 GiB of it is over in 0.16 ms, while the host needs 0.65-0.8 ms to issue
     run X when the family's kernels have not run in the process yet (and a tenth of that when they have).  Measured once, in that
     cold state and with ONE copy of 256 MiB (host / device interval, ms): alac 0.65 / 5.47, raop 0.69 / 5.50, ohm_rx 0.67 / 4.74,
     ogg 0.68 / 4.75, mp4 0.81 / 4.78, iff 0.66 / 4.73 -- less than ten times, hence four copies; with the four, inside the whole
-    suite: alac 0.08 / 19.5, raop 0.09 / 19.6, ohm_rx 0.07 / 18.8, ogg 0.10 / 18.8, mp4 0.11 / 18.9, iff 0.06 / 18.8.  FLAC is
+    suite: alac 0.08 / 19.5, raop 0.09 / 19.6, ohm_rx 0.07 / 18.8, ogg 0.10 / 18.8, mp4 0.11 / 18.9, iff 0.06 / 18.8.  The seven newer
+    families, measured with the four copies, on the launches' route and then the plain one.  Cold (this file first in the process; the
+    plain route comes second, adts behind ts, whose code object it shares): mp4f 0.82 / 18.9 and 0.07 / 20.0, cenc 0.81 / 19.2 and
+    0.09 / 19.0, cbcs 0.89 / 19.1 and 0.08 / 19.3, vorbis 0.75 / 28.9 and 0.09 / 29.1, ts 0.77 / 18.8 and 0.07 / 18.9, adts 0.07 / 18.8
+    and 0.07 / 18.8, raop_rx 0.66 / 19.0 and 0.09 / 18.8 -- no host interval above a twentieth of the device's, so the four copies stay.
+    Inside the whole suite: mp4f 0.11 / 18.9 and 0.10 / 20.0, cenc 0.13 / 19.2 and 0.09 / 19.0, cbcs 0.13 / 19.1 and 0.09 / 19.3,
+    vorbis 0.13 / 30.4 and 0.12 / 29.4, ts 0.12 / 18.8 and 0.09 / 18.9, adts 0.11 / 18.8 and 0.09 / 18.8, raop_rx 0.10 / 18.8 and
+    0.10 / 18.8.  FLAC is
     another matter: its run waits on the host for the scan, so its host interval holds the fill whatever the fill's size (19.0 / 35.2;
     4.85 / 21.2 with one copy), and what is still running when run Y is issued is what run X queued behind that wait, the probe and
     restoration of frames of 4096 samples (tests/stream_switch_cases.py).  With run_begin's wait taken out of a scratch build, once,
-    the test failed for all seven families: FLAC's arena X came out wrong, the other six held run X's results at the end."""
+    the test failed for all seven families there were then: FLAC's arena X came out wrong, the other six held run X's results at
+    the end.  (No such build was run for the families added since: records that race can index out of bounds.)"""
     r, a, b = rig, rig.streams["A"], rig.streams["B"]
     e0, e1 = ctx.event(), ctx.event()
     r.refill("X")
@@ -142,7 +194,7 @@ def test_a_run_on_another_stream_waits_for_the_last(ctx, scratch, rig):
     host_ms, device_ms = (t1 - t0) * 1e3, ctx.elapsed_ms(e0, e1)
     ctx.event_destroy(e0)
     ctx.event_destroy(e1)
-    print(f"\n{r.p.family}: host interval {host_ms:.3f} ms, device interval {device_ms:.3f} ms")
+    print(f"\n{r.label}: host interval {host_ms:.3f} ms, device interval {device_ms:.3f} ms")
     r.arena_is_the_models("X")
     r.arena_is_the_models("Y")
     r.p.verify(ctx, r.batch, "Y")
