@@ -896,66 +896,79 @@ def _iff_descs(descs):
     return d
 
 
-def _mp4f_descs(descs):
+# The three fragmented MPEG-4 families behind one implementation (Context._frag_* has the device calls): a family's descriptor and
+# result records; `counts` is (n_packets, n_runs), with n_subsamples behind them for cbcs.
+_FRAG = {"mp4f": (MP4F_STREAM_DESC, MP4F_STREAM_RESULT), "cenc": (CENC_STREAM_DESC, CENC_STREAM_RESULT), "cbcs": (CBCS_STREAM_DESC, CBCS_STREAM_RESULT)}
+
+
+def _frag_call(fam, name, *args):
+    check(getattr(lib(), f"ohgpu_{fam}_{name}")(*args))
+
+
+def _frag_descs(fam, descs):
     d = np.ascontiguousarray(descs)
-    assert d.dtype == MP4F_STREAM_DESC
+    assert d.dtype == _FRAG[fam][0]
     return d
+
+
+def _frag_batch_check(fam, descs, counts, src_arena_bytes, dst_arena_bytes):
+    d = _frag_descs(fam, descs)
+    _frag_call(fam, "batch_check", _ptr_or_none(d), d.size, *counts, src_arena_bytes, dst_arena_bytes)
+
+
+def _frag_head(fam, data):
+    raw = bytes(data)
+    res = np.zeros(1, dtype=_FRAG[fam][1])
+    _frag_call(fam, "head", raw, len(raw), res.ctypes.data_as(C.c_void_p))
+    return res[0]
+
+
+def _frag_tables(fam, n, n_packets, n_runs):
+    return np.zeros(n, dtype=_FRAG[fam][1]), np.zeros(n_runs, dtype=MP4F_RUN), np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
+
+
+def _mp4f_descs(descs):
+    return _frag_descs("mp4f", descs)
 
 
 def mp4f_batch_check(descs, n_packets, n_runs, src_arena_bytes, dst_arena_bytes):
     """The validation of ctx.mp4f_batch without a device (ohgpu_mp4f_batch_check): OhGpuError on a bad descriptor."""
-    d = _mp4f_descs(descs)
-    check(lib().ohgpu_mp4f_batch_check(_ptr_or_none(d), d.size, n_packets, n_runs, src_arena_bytes, dst_arena_bytes))
+    _frag_batch_check("mp4f", descs, (n_packets, n_runs), src_arena_bytes, dst_arena_bytes)
 
 
 def mp4f_head(data):
     """The walk of a fragmented stream up to the end of moov (ohgpu_mp4f_head; host only): an MP4F_STREAM_RESULT record."""
-    raw = bytes(data)
-    res = np.zeros(1, dtype=MP4F_STREAM_RESULT)
-    check(lib().ohgpu_mp4f_head(raw, len(raw), res.ctypes.data_as(C.c_void_p)))
-    return res[0]
+    return _frag_head("mp4f", data)
 
 
 def _cenc_descs(descs):
-    d = np.ascontiguousarray(descs)
-    assert d.dtype == CENC_STREAM_DESC
-    return d
+    return _frag_descs("cenc", descs)
 
 
 def cenc_batch_check(descs, n_packets, n_runs, src_arena_bytes, dst_arena_bytes):
     """The validation of ctx.cenc_batch without a device (ohgpu_cenc_batch_check): OhGpuError on a bad descriptor."""
-    d = _cenc_descs(descs)
-    check(lib().ohgpu_cenc_batch_check(_ptr_or_none(d), d.size, n_packets, n_runs, src_arena_bytes, dst_arena_bytes))
+    _frag_batch_check("cenc", descs, (n_packets, n_runs), src_arena_bytes, dst_arena_bytes)
 
 
 def cenc_head(data):
     """The walk of a protected or clear fragmented stream up to the end of moov (ohgpu_cenc_head; host only, no key): a CENC_STREAM_RESULT
     record whose is_protected and kid say which key to ask for."""
-    raw = bytes(data)
-    res = np.zeros(1, dtype=CENC_STREAM_RESULT)
-    check(lib().ohgpu_cenc_head(raw, len(raw), res.ctypes.data_as(C.c_void_p)))
-    return res[0]
+    return _frag_head("cenc", data)
 
 
 def _cbcs_descs(descs):
-    d = np.ascontiguousarray(descs)
-    assert d.dtype == CBCS_STREAM_DESC
-    return d
+    return _frag_descs("cbcs", descs)
 
 
 def cbcs_batch_check(descs, n_packets, n_runs, n_subsamples, src_arena_bytes, dst_arena_bytes):
     """The validation of ctx.cbcs_batch without a device (ohgpu_cbcs_batch_check): OhGpuError on a bad descriptor."""
-    d = _cbcs_descs(descs)
-    check(lib().ohgpu_cbcs_batch_check(_ptr_or_none(d), d.size, n_packets, n_runs, n_subsamples, src_arena_bytes, dst_arena_bytes))
+    _frag_batch_check("cbcs", descs, (n_packets, n_runs, n_subsamples), src_arena_bytes, dst_arena_bytes)
 
 
 def cbcs_head(data):
     """The walk of a `cenc`- or `cbcs`-protected or clear fragmented stream up to the end of moov (ohgpu_cbcs_head; host only, no key): a
     CBCS_STREAM_RESULT record."""
-    raw = bytes(data)
-    res = np.zeros(1, dtype=CBCS_STREAM_RESULT)
-    check(lib().ohgpu_cbcs_head(raw, len(raw), res.ctypes.data_as(C.c_void_p)))
-    return res[0]
+    return _frag_head("cbcs", data)
 
 
 def iff_batch_check(descs, src_arena_bytes, dst_arena_bytes):
@@ -1678,11 +1691,57 @@ class Context:
                                                 _ptr_or_none(res), _ptr_or_none(pk), _ptr_or_none(sm), _ptr_or_none(ares), _ptr_or_none(pres)))
         return res, pk, sm, ares, pres
 
-    def mp4f_batch(self, descs, n_packets, n_runs, src_arena_bytes, dst_arena_bytes):
-        d = _mp4f_descs(descs)
+    # ---- the three fragmented MPEG-4 families: one implementation (counts: see _FRAG), then each family's names over it
+    def _frag_batch(self, fam, descs, counts, src_arena_bytes, dst_arena_bytes):
+        d = _frag_descs(fam, descs)
         b = C.c_void_p()
-        check(lib().ohgpu_mp4f_batch_create(self._h, _ptr_or_none(d), d.size, n_packets, n_runs, src_arena_bytes, dst_arena_bytes, C.byref(b)))
+        _frag_call(fam, "batch_create", self._h, _ptr_or_none(d), d.size, *counts, src_arena_bytes, dst_arena_bytes, C.byref(b))
         return b
+
+    def _frag_results(self, fam, batch, n, n_packets, n_runs):
+        out = _frag_tables(fam, n, n_packets, n_runs)
+        for name, table, rows in zip(("results", "runs", "packets", "samples"), out, (n, n_runs, n_packets, n_packets)):
+            _frag_call(fam, "batch_" + name, self._h, batch, _ptr_or_none(table), rows)
+        return out
+
+    def _frag_phase_ms(self, fam, batch):
+        ms = (C.c_float * 6)()
+        _frag_call(fam, "batch_phase_ms", self._h, batch, ms)
+        return tuple(float(v) for v in ms)
+
+    def _frag_paths(self, fam, batch):
+        route, tiles, blocks = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        _frag_call(fam, "batch_paths", batch, C.byref(route), C.byref(tiles), C.byref(blocks))
+        return dict(route=int(route.value), tiles=int(tiles.value), wave_blocks=int(blocks.value))
+
+    def _frag_process_host(self, fam, descs, counts, src, dst):
+        d = _frag_descs(fam, descs)
+        out = _frag_tables(fam, d.size, *counts[:2])
+        _frag_call(fam, "process_host", self._h, _ptr_or_none(d), d.size, *counts, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst), dst.nbytes, *map(_ptr_or_none, out))
+        return out
+
+    def _frag_flac_process_host(self, fam, descs, flac_descs, counts, src, mid_bytes, dst, frames_capacity):
+        m, f = _frag_descs(fam, descs), np.ascontiguousarray(flac_descs)
+        assert f.dtype == FLAC_STREAM_DESC and f.size == m.size
+        out = _frag_tables(fam, m.size, *counts[:2])
+        fres, frames = np.zeros(m.size, dtype=FLAC_STREAM_RESULT), np.zeros(frames_capacity, dtype=FLAC_FRAME)
+        n_frames = C.c_size_t(0)
+        _frag_call(fam, "flac_process_host", self._h, _ptr_or_none(m), _ptr_or_none(f), m.size, *counts, _ptr_or_none(src), src.nbytes, mid_bytes, _ptr_or_none(dst), dst.nbytes,
+                   *map(_ptr_or_none, out), _ptr_or_none(fres), _ptr_or_none(frames), frames_capacity, C.byref(n_frames))
+        return (*out, fres, frames[:min(int(n_frames.value), frames_capacity)])
+
+    def _frag_alac_process_host(self, fam, descs, alac_descs, counts, src, mid, dst):
+        """mid: (mid_bytes,) for a protected family, () for mp4f, whose packets are decoded where they lie"""
+        m, a = _frag_descs(fam, descs), np.ascontiguousarray(alac_descs)
+        assert a.dtype == ALAC_STREAM_DESC and a.size == m.size
+        out = _frag_tables(fam, m.size, *counts[:2])
+        ares, pres = np.zeros(m.size, dtype=ALAC_STREAM_RESULT), np.zeros(counts[0], dtype=ALAC_PACKET_RESULT)
+        _frag_call(fam, "alac_process_host", self._h, _ptr_or_none(m), _ptr_or_none(a), m.size, *counts, _ptr_or_none(src), src.nbytes, *mid, _ptr_or_none(dst), dst.nbytes,
+                   *map(_ptr_or_none, out), _ptr_or_none(ares), _ptr_or_none(pres))
+        return (*out, ares, pres)
+
+    def mp4f_batch(self, descs, n_packets, n_runs, src_arena_bytes, dst_arena_bytes):
+        return self._frag_batch("mp4f", descs, (n_packets, n_runs), src_arena_bytes, dst_arena_bytes)
 
     def mp4f_run(self, batch, d_src, d_dst, stream=None):
         """Walk, run sums, carries, expand, finish, gather (ohgpu_mp4f_batch_run): queued on the stream."""
@@ -1690,66 +1749,32 @@ class Context:
 
     def mp4f_results(self, batch, n, n_packets, n_runs):
         """The last run's (MP4F_STREAM_RESULT per stream, the run table, the packet table, the sample table); waits for the run."""
-        res, runs = np.zeros(n, dtype=MP4F_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
-        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
-        check(lib().ohgpu_mp4f_batch_results(self._h, batch, _ptr_or_none(res), n))
-        check(lib().ohgpu_mp4f_batch_runs(self._h, batch, _ptr_or_none(runs), n_runs))
-        check(lib().ohgpu_mp4f_batch_packets(self._h, batch, _ptr_or_none(pk), n_packets))
-        check(lib().ohgpu_mp4f_batch_samples(self._h, batch, _ptr_or_none(sm), n_packets))
-        return res, runs, pk, sm
+        return self._frag_results("mp4f", batch, n, n_packets, n_runs)
 
     def mp4f_phase_ms(self, batch):
         """(walk, run sums, carries, expand, finish, gather) of the last run in milliseconds."""
-        ms = (C.c_float * 6)()
-        check(lib().ohgpu_mp4f_batch_phase_ms(self._h, batch, ms))
-        return tuple(float(v) for v in ms)
+        return self._frag_phase_ms("mp4f", batch)
 
     def mp4f_paths(self, batch):
         """{route, tiles, wave_blocks} of a fragmented MPEG-4 batch (ohgpu_mp4f_batch_paths)."""
-        route, tiles, blocks = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
-        check(lib().ohgpu_mp4f_batch_paths(batch, C.byref(route), C.byref(tiles), C.byref(blocks)))
-        return dict(route=int(route.value), tiles=int(tiles.value), wave_blocks=int(blocks.value))
+        return self._frag_paths("mp4f", batch)
 
     def mp4f_process_host(self, descs, n_packets, n_runs, src, dst):
         """Host bytes in (ohgpu_mp4f_process_host), the gathered runs into dst; returns (results, run table, packet table, sample table)."""
-        d = _mp4f_descs(descs)
-        res, runs = np.zeros(d.size, dtype=MP4F_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
-        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
-        check(lib().ohgpu_mp4f_process_host(self._h, _ptr_or_none(d), d.size, n_packets, n_runs, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst), dst.nbytes,
-                                            _ptr_or_none(res), _ptr_or_none(runs), _ptr_or_none(pk), _ptr_or_none(sm)))
-        return res, runs, pk, sm
+        return self._frag_process_host("mp4f", descs, (n_packets, n_runs), src, dst)
 
     def mp4f_flac_process_host(self, mp4f_descs, flac_descs, n_packets, n_runs, src, mid_bytes, dst, frames_capacity=0):
         """Fragmented fLaC from host buffers to PCM (ohgpu_mp4f_flac_process_host); returns (results, run table, packet table, sample table,
         FLAC results, frames)."""
-        m, f = _mp4f_descs(mp4f_descs), np.ascontiguousarray(flac_descs)
-        assert f.dtype == FLAC_STREAM_DESC and f.size == m.size
-        res, runs = np.zeros(m.size, dtype=MP4F_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
-        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
-        fres, frames = np.zeros(m.size, dtype=FLAC_STREAM_RESULT), np.zeros(frames_capacity, dtype=FLAC_FRAME)
-        n_frames = C.c_size_t(0)
-        check(lib().ohgpu_mp4f_flac_process_host(self._h, _ptr_or_none(m), _ptr_or_none(f), m.size, n_packets, n_runs, _ptr_or_none(src), src.nbytes, mid_bytes,
-                                                 _ptr_or_none(dst), dst.nbytes, _ptr_or_none(res), _ptr_or_none(runs), _ptr_or_none(pk), _ptr_or_none(sm),
-                                                 _ptr_or_none(fres), _ptr_or_none(frames), frames_capacity, C.byref(n_frames)))
-        return res, runs, pk, sm, fres, frames[:min(int(n_frames.value), frames_capacity)]
+        return self._frag_flac_process_host("mp4f", mp4f_descs, flac_descs, (n_packets, n_runs), src, mid_bytes, dst, frames_capacity)
 
     def mp4f_alac_process_host(self, mp4f_descs, alac_descs, n_packets, n_runs, src, dst):
         """Fragmented alac from host buffers to PCM (ohgpu_mp4f_alac_process_host); returns (results, run table, packet table, sample table,
         Apple Lossless stream results, packet results indexed as the tables are)."""
-        m, a = _mp4f_descs(mp4f_descs), np.ascontiguousarray(alac_descs)
-        assert a.dtype == ALAC_STREAM_DESC and a.size == m.size
-        res, runs = np.zeros(m.size, dtype=MP4F_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
-        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
-        ares, pres = np.zeros(m.size, dtype=ALAC_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET_RESULT)
-        check(lib().ohgpu_mp4f_alac_process_host(self._h, _ptr_or_none(m), _ptr_or_none(a), m.size, n_packets, n_runs, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst),
-                                                 dst.nbytes, _ptr_or_none(res), _ptr_or_none(runs), _ptr_or_none(pk), _ptr_or_none(sm), _ptr_or_none(ares), _ptr_or_none(pres)))
-        return res, runs, pk, sm, ares, pres
+        return self._frag_alac_process_host("mp4f", mp4f_descs, alac_descs, (n_packets, n_runs), src, (), dst)
 
     def cenc_batch(self, descs, n_packets, n_runs, src_arena_bytes, dst_arena_bytes):
-        d = _cenc_descs(descs)
-        b = C.c_void_p()
-        check(lib().ohgpu_cenc_batch_create(self._h, _ptr_or_none(d), d.size, n_packets, n_runs, src_arena_bytes, dst_arena_bytes, C.byref(b)))
-        return b
+        return self._frag_batch("cenc", descs, (n_packets, n_runs), src_arena_bytes, dst_arena_bytes)
 
     def cenc_run(self, batch, d_src, d_dst, stream=None):
         """Walk, run sums, carries, expand, finish, decrypt-gather (ohgpu_cenc_batch_run): queued on the stream."""
@@ -1757,67 +1782,32 @@ class Context:
 
     def cenc_results(self, batch, n, n_packets, n_runs):
         """The last run's (CENC_STREAM_RESULT per stream, the run table, the packet table, the sample table); waits for the run."""
-        res, runs = np.zeros(n, dtype=CENC_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
-        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
-        check(lib().ohgpu_cenc_batch_results(self._h, batch, _ptr_or_none(res), n))
-        check(lib().ohgpu_cenc_batch_runs(self._h, batch, _ptr_or_none(runs), n_runs))
-        check(lib().ohgpu_cenc_batch_packets(self._h, batch, _ptr_or_none(pk), n_packets))
-        check(lib().ohgpu_cenc_batch_samples(self._h, batch, _ptr_or_none(sm), n_packets))
-        return res, runs, pk, sm
+        return self._frag_results("cenc", batch, n, n_packets, n_runs)
 
     def cenc_phase_ms(self, batch):
         """(walk, run sums, carries, expand, finish, decrypt-gather) of the last run in milliseconds."""
-        ms = (C.c_float * 6)()
-        check(lib().ohgpu_cenc_batch_phase_ms(self._h, batch, ms))
-        return tuple(float(v) for v in ms)
+        return self._frag_phase_ms("cenc", batch)
 
     def cenc_paths(self, batch):
         """{route, tiles, wave_blocks: the persistent decrypt-gather launch's workgroups} of a protected MPEG-4 batch (ohgpu_cenc_batch_paths)."""
-        route, tiles, blocks = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
-        check(lib().ohgpu_cenc_batch_paths(batch, C.byref(route), C.byref(tiles), C.byref(blocks)))
-        return dict(route=int(route.value), tiles=int(tiles.value), wave_blocks=int(blocks.value))
+        return self._frag_paths("cenc", batch)
 
     def cenc_process_host(self, descs, n_packets, n_runs, src, dst):
         """Host bytes in (ohgpu_cenc_process_host), the clear runs into dst; returns (results, run table, packet table, sample table)."""
-        d = _cenc_descs(descs)
-        res, runs = np.zeros(d.size, dtype=CENC_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
-        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
-        check(lib().ohgpu_cenc_process_host(self._h, _ptr_or_none(d), d.size, n_packets, n_runs, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst), dst.nbytes,
-                                            _ptr_or_none(res), _ptr_or_none(runs), _ptr_or_none(pk), _ptr_or_none(sm)))
-        return res, runs, pk, sm
+        return self._frag_process_host("cenc", descs, (n_packets, n_runs), src, dst)
 
     def cenc_flac_process_host(self, cenc_descs, flac_descs, n_packets, n_runs, src, mid_bytes, dst, frames_capacity=0):
         """Protected fLaC from host buffers to PCM (ohgpu_cenc_flac_process_host); returns (results, run table, packet table, sample table,
         FLAC results, frames)."""
-        m, f = _cenc_descs(cenc_descs), np.ascontiguousarray(flac_descs)
-        assert f.dtype == FLAC_STREAM_DESC and f.size == m.size
-        res, runs = np.zeros(m.size, dtype=CENC_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
-        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
-        fres, frames = np.zeros(m.size, dtype=FLAC_STREAM_RESULT), np.zeros(frames_capacity, dtype=FLAC_FRAME)
-        n_frames = C.c_size_t(0)
-        check(lib().ohgpu_cenc_flac_process_host(self._h, _ptr_or_none(m), _ptr_or_none(f), m.size, n_packets, n_runs, _ptr_or_none(src), src.nbytes, mid_bytes,
-                                                 _ptr_or_none(dst), dst.nbytes, _ptr_or_none(res), _ptr_or_none(runs), _ptr_or_none(pk), _ptr_or_none(sm),
-                                                 _ptr_or_none(fres), _ptr_or_none(frames), frames_capacity, C.byref(n_frames)))
-        return res, runs, pk, sm, fres, frames[:min(int(n_frames.value), frames_capacity)]
+        return self._frag_flac_process_host("cenc", cenc_descs, flac_descs, (n_packets, n_runs), src, mid_bytes, dst, frames_capacity)
 
     def cenc_alac_process_host(self, cenc_descs, alac_descs, n_packets, n_runs, src, mid_bytes, dst):
         """Protected alac from host buffers to PCM (ohgpu_cenc_alac_process_host); returns (results, run table, packet table, sample table,
         Apple Lossless stream results, packet results indexed as the tables are)."""
-        m, a = _cenc_descs(cenc_descs), np.ascontiguousarray(alac_descs)
-        assert a.dtype == ALAC_STREAM_DESC and a.size == m.size
-        res, runs = np.zeros(m.size, dtype=CENC_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
-        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
-        ares, pres = np.zeros(m.size, dtype=ALAC_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET_RESULT)
-        check(lib().ohgpu_cenc_alac_process_host(self._h, _ptr_or_none(m), _ptr_or_none(a), m.size, n_packets, n_runs, _ptr_or_none(src), src.nbytes, mid_bytes,
-                                                 _ptr_or_none(dst), dst.nbytes, _ptr_or_none(res), _ptr_or_none(runs), _ptr_or_none(pk), _ptr_or_none(sm), _ptr_or_none(ares),
-                                                 _ptr_or_none(pres)))
-        return res, runs, pk, sm, ares, pres
+        return self._frag_alac_process_host("cenc", cenc_descs, alac_descs, (n_packets, n_runs), src, (mid_bytes,), dst)
 
     def cbcs_batch(self, descs, n_packets, n_runs, n_subsamples, src_arena_bytes, dst_arena_bytes):
-        d = _cbcs_descs(descs)
-        b = C.c_void_p()
-        check(lib().ohgpu_cbcs_batch_create(self._h, _ptr_or_none(d), d.size, n_packets, n_runs, n_subsamples, src_arena_bytes, dst_arena_bytes, C.byref(b)))
-        return b
+        return self._frag_batch("cbcs", descs, (n_packets, n_runs, n_subsamples), src_arena_bytes, dst_arena_bytes)
 
     def cbcs_run(self, batch, d_src, d_dst, stream=None):
         """Walk and subsample chain, run sums, carries, expand, finish, decrypt-gather (ohgpu_cbcs_batch_run): queued on the stream."""
@@ -1825,61 +1815,29 @@ class Context:
 
     def cbcs_results(self, batch, n, n_packets, n_runs):
         """The last run's (CBCS_STREAM_RESULT per stream, the run table, the packet table, the sample table); waits for the run."""
-        res, runs = np.zeros(n, dtype=CBCS_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
-        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
-        check(lib().ohgpu_cbcs_batch_results(self._h, batch, _ptr_or_none(res), n))
-        check(lib().ohgpu_cbcs_batch_runs(self._h, batch, _ptr_or_none(runs), n_runs))
-        check(lib().ohgpu_cbcs_batch_packets(self._h, batch, _ptr_or_none(pk), n_packets))
-        check(lib().ohgpu_cbcs_batch_samples(self._h, batch, _ptr_or_none(sm), n_packets))
-        return res, runs, pk, sm
+        return self._frag_results("cbcs", batch, n, n_packets, n_runs)
 
     def cbcs_phase_ms(self, batch):
         """(walk, run sums, carries, expand, finish, decrypt-gather) of the last run in milliseconds."""
-        ms = (C.c_float * 6)()
-        check(lib().ohgpu_cbcs_batch_phase_ms(self._h, batch, ms))
-        return tuple(float(v) for v in ms)
+        return self._frag_phase_ms("cbcs", batch)
 
     def cbcs_paths(self, batch):
         """{route, tiles, wave_blocks: the persistent decrypt-gather launch's workgroups} of a batch of the family (ohgpu_cbcs_batch_paths)."""
-        route, tiles, blocks = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
-        check(lib().ohgpu_cbcs_batch_paths(batch, C.byref(route), C.byref(tiles), C.byref(blocks)))
-        return dict(route=int(route.value), tiles=int(tiles.value), wave_blocks=int(blocks.value))
+        return self._frag_paths("cbcs", batch)
 
     def cbcs_process_host(self, descs, n_packets, n_runs, n_subsamples, src, dst):
         """Host bytes in (ohgpu_cbcs_process_host), the clear runs into dst; returns (results, run table, packet table, sample table)."""
-        d = _cbcs_descs(descs)
-        res, runs = np.zeros(d.size, dtype=CBCS_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
-        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
-        check(lib().ohgpu_cbcs_process_host(self._h, _ptr_or_none(d), d.size, n_packets, n_runs, n_subsamples, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst), dst.nbytes,
-                                            _ptr_or_none(res), _ptr_or_none(runs), _ptr_or_none(pk), _ptr_or_none(sm)))
-        return res, runs, pk, sm
+        return self._frag_process_host("cbcs", descs, (n_packets, n_runs, n_subsamples), src, dst)
 
     def cbcs_flac_process_host(self, descs, flac_descs, n_packets, n_runs, n_subsamples, src, mid_bytes, dst, frames_capacity=0):
         """Protected fLaC from host buffers to PCM (ohgpu_cbcs_flac_process_host); returns (results, run table, packet table, sample table,
         FLAC results, frames)."""
-        m, f = _cbcs_descs(descs), np.ascontiguousarray(flac_descs)
-        assert f.dtype == FLAC_STREAM_DESC and f.size == m.size
-        res, runs = np.zeros(m.size, dtype=CBCS_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
-        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
-        fres, frames = np.zeros(m.size, dtype=FLAC_STREAM_RESULT), np.zeros(frames_capacity, dtype=FLAC_FRAME)
-        n_frames = C.c_size_t(0)
-        check(lib().ohgpu_cbcs_flac_process_host(self._h, _ptr_or_none(m), _ptr_or_none(f), m.size, n_packets, n_runs, n_subsamples, _ptr_or_none(src), src.nbytes, mid_bytes,
-                                                 _ptr_or_none(dst), dst.nbytes, _ptr_or_none(res), _ptr_or_none(runs), _ptr_or_none(pk), _ptr_or_none(sm),
-                                                 _ptr_or_none(fres), _ptr_or_none(frames), frames_capacity, C.byref(n_frames)))
-        return res, runs, pk, sm, fres, frames[:min(int(n_frames.value), frames_capacity)]
+        return self._frag_flac_process_host("cbcs", descs, flac_descs, (n_packets, n_runs, n_subsamples), src, mid_bytes, dst, frames_capacity)
 
     def cbcs_alac_process_host(self, descs, alac_descs, n_packets, n_runs, n_subsamples, src, mid_bytes, dst):
         """Protected alac from host buffers to PCM (ohgpu_cbcs_alac_process_host); returns (results, run table, packet table, sample table,
         Apple Lossless stream results, packet results indexed as the tables are)."""
-        m, a = _cbcs_descs(descs), np.ascontiguousarray(alac_descs)
-        assert a.dtype == ALAC_STREAM_DESC and a.size == m.size
-        res, runs = np.zeros(m.size, dtype=CBCS_STREAM_RESULT), np.zeros(n_runs, dtype=MP4F_RUN)
-        pk, sm = np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
-        ares, pres = np.zeros(m.size, dtype=ALAC_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET_RESULT)
-        check(lib().ohgpu_cbcs_alac_process_host(self._h, _ptr_or_none(m), _ptr_or_none(a), m.size, n_packets, n_runs, n_subsamples, _ptr_or_none(src), src.nbytes, mid_bytes,
-                                                 _ptr_or_none(dst), dst.nbytes, _ptr_or_none(res), _ptr_or_none(runs), _ptr_or_none(pk), _ptr_or_none(sm), _ptr_or_none(ares),
-                                                 _ptr_or_none(pres)))
-        return res, runs, pk, sm, ares, pres
+        return self._frag_alac_process_host("cbcs", descs, alac_descs, (n_packets, n_runs, n_subsamples), src, (mid_bytes,), dst)
 
     def iff_batch(self, descs, src_arena_bytes, dst_arena_bytes):
         d = _iff_descs(descs)

@@ -118,6 +118,18 @@ void state_free(ohgpu_ctx* ctx, S*& p)
     delete p;
     p = nullptr;
 }
+// ... of a family that holds key schedules (CencState, CbcsState).  They do not outlive the batch: the device block is cleared before it
+// goes back to the cache, the host copy too.
+template <class S>
+void protected_free(ohgpu_ctx* ctx, S*& p)
+{
+    if (p) {
+        (void)hipDeviceSynchronize();
+        if (p->d_keys) (void)hipMemset(p->d_keys, 0, p->keys_bytes);
+        for (uint32_t& w : p->keys) *(volatile uint32_t*)&w = 0;
+    }
+    state_free(ctx, p);
+}
 // The front of a results, table or phase call: the context, then "<who>: not <noun> batch" (the noun with its article: "an Ogg") unless
 // the batch is of `kind`.
 inline int state_guard(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, BatchKind kind, const char* noun)
@@ -279,121 +291,6 @@ int alac_process_host(ohgpu_ctx* ctx, const char* who, size_t n, size_t n_packet
     if (err == OHGPU_OK && stream_results && n) memcpy(stream_results, sres.data(), n * sizeof(sres[0]));
     if (err == OHGPU_OK && packet_results && n_packets) memcpy(packet_results, pres.data(), n_packets * sizeof(pres[0]));
     return err;
-}
-
-// The whole of a fragmented family's fused call to the FLAC decoder (ohgpu_mp4f_flac_process_host, ohgpu_cenc_flac_process_host): one
-// upload, create(&batch) = the family's batch over a middle arena of mid_bytes that lives on the device only, run_fetch(batch, d_src,
-// d_mid, results) = the family's run and its results and tables home, a FLAC batch over the runs the family wrote (a stream's src_bytes is
-// its bytes_gathered, 0 for a stream that is not fLaC), and of dst_host the samples that were decoded.  head(result) -> the result's
-// ohgpu_mp4f_stream_result.  flac_descs[i].src_offset must be descs[i].dst_offset.
-template <typename Desc, typename Res, typename Create, typename RunFetch, typename Head>
-int frag_flac_process_host(ohgpu_ctx* ctx, const char* who, const Desc* descs, const ohgpu_flac_stream_desc* flac_descs, size_t n, const void* src_host, uint64_t src_bytes,
-                           uint64_t mid_bytes, void* dst_host, uint64_t dst_bytes, Res* results, ohgpu_flac_stream_result* flac_results, ohgpu_flac_frame* frames,
-                           size_t frames_capacity, size_t* n_frames, Create&& create, RunFetch&& run_fetch, Head&& head)
-{
-    if (n && (!descs || !flac_descs)) return set_error(OHGPU_ERR_INVALID, "%s: null argument", who);
-    for (size_t i = 0; i < n; i++)
-        if (flac_descs[i].src_offset != descs[i].dst_offset)
-            return set_error(OHGPU_ERR_INVALID, "%s: stream %zu: the FLAC descriptor reads at %llu where the demultiplexer gathers at %llu", who, i,
-                             (unsigned long long)flac_descs[i].src_offset, (unsigned long long)descs[i].dst_offset);
-    if (n_frames) *n_frames = 0;
-    std::vector<Res> mres(n);
-    std::vector<ohgpu_flac_stream_result> fres(n);
-    std::vector<ohgpu_flac_stream_desc> fdescs(flac_descs, flac_descs + n);
-    void* d_mid = nullptr;
-    const int err = decoder_process_host(ctx, who, src_host, src_bytes, dst_host, dst_bytes, create,
-        [&](const ohgpu_batch* b, const void* d_src, void* d_dst) {
-            if (!n) return (int)OHGPU_OK;
-            OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &d_mid, mid_bytes ? mid_bytes : 1));      // the middle arena: the gathered bytes never leave the device
-            int e = run_fetch(b, d_src, d_mid, mres.data());
-            if (e != OHGPU_OK) return e;
-            for (size_t i = 0; i < n; i++) fdescs[i].src_bytes = head(mres[i]).codec == mp4box::fourcc('f', 'L', 'a', 'C') ? head(mres[i]).bytes_gathered : 0u;
-            ohgpu_batch* fb = nullptr;
-            e = ohgpu_flac_batch_create(ctx, fdescs.data(), n, mid_bytes, dst_bytes, &fb);
-            if (e != OHGPU_OK) return e;
-            const BatchPtr own(fb, BatchDeleter{ctx});
-            e = ohgpu_flac_batch_run(ctx, fb, d_mid, d_dst, nullptr);
-            if (e == OHGPU_OK) e = ohgpu_flac_batch_results(ctx, fb, fres.data(), n);
-            if (e == OHGPU_OK && (frames || n_frames)) e = ohgpu_flac_batch_frames(ctx, fb, frames, frames ? frames_capacity : 0, n_frames);
-            return e;
-        },
-        [&] {   // only what was decoded comes back, as in ohgpu_flac_process_host
-            int e = OHGPU_OK;
-            for (size_t i = 0; i < n && e == OHGPU_OK; i++) e = flac_download_decoded(ctx, who, fdescs[i], fres[i], dst_host);
-            return e;
-        });
-    if (d_mid) { (void)hipStreamSynchronize(ctx->stream); ctx_dev_free(ctx, d_mid); }
-    if (err == OHGPU_OK && results && n) memcpy(results, mres.data(), n * sizeof(mres[0]));
-    if (err == OHGPU_OK && flac_results && n) memcpy(flac_results, fres.data(), n * sizeof(fres[0]));
-    return err;
-}
-
-// The whole of a protected family's fused call to the Apple Lossless decoder (ohgpu_cenc_alac_process_host, ohgpu_cbcs_alac_process_host):
-// create(&batch) = the family's batch over a middle arena of mid_bytes that lives on the device only, run_fetch(batch, d_src, d_mid,
-// results, packet table) = the family's run and its results and tables home, an Apple Lossless batch over the rows the family wrote, and
-// of dst_host the samples that were decoded.  head(result) -> the result's ohgpu_mp4f_stream_result.
-template <typename Desc, typename Res, typename Create, typename RunFetch, typename Head>
-int frag_alac_process_host(ohgpu_ctx* ctx, const char* who, const Desc* descs, const ohgpu_alac_stream_desc* alac_descs, size_t n, size_t n_packets, const void* src_host,
-                           uint64_t src_bytes, uint64_t mid_bytes, void* dst_host, uint64_t dst_bytes, Res* results, ohgpu_alac_packet* packets,
-                           ohgpu_alac_stream_result* alac_results, ohgpu_alac_packet_result* packet_results, Create&& create, RunFetch&& run_fetch, Head&& head)
-{
-    if (n && (!descs || !alac_descs)) return set_error(OHGPU_ERR_INVALID, "%s: null argument", who);
-    std::vector<Res> cres(n);
-    std::vector<ohgpu_alac_packet> table(n_packets), dense;
-    std::vector<ohgpu_alac_stream_desc> adescs(alac_descs, alac_descs + n);
-    std::vector<ohgpu_alac_stream_result> ares(n);
-    std::vector<ohgpu_alac_packet_result> pres;
-    std::vector<uint32_t> first_row(n, 0);
-    void* d_mid = nullptr;
-    const int err = decoder_process_host(ctx, who, src_host, src_bytes, dst_host, dst_bytes,
-        create,
-        [&](const ohgpu_batch* b, const void* d_src, void* d_dst) {
-            if (!n) return (int)OHGPU_OK;
-            OHGPU_HIP_TRY_ALLOC(ctx_dev_alloc(ctx, &d_mid, mid_bytes ? mid_bytes : 1));      // the middle arena: the clear packets never leave the device
-            int e = run_fetch(b, d_src, d_mid, cres.data(), table.data());                    // (with the one small read between the layers)
-            if (e != OHGPU_OK) return e;
-            // the Apple Lossless table has the streams' gathered rows one after the other without gaps: places in the middle arena
-            for (size_t i = 0; i < n; i++) {
-                ohgpu_alac_stream_desc& a = adescs[i];
-                const ohgpu_mp4f_stream_result& m = head(cres[i]);
-                const bool ok = m.status == OHGPU_MP4F_OK && m.codec == mp4box::fourcc('a', 'l', 'a', 'c') && m.bytes_gathered != 0u;
-                const uint32_t from = descs[i].gather_first_row, rows = ok ? m.samples_available - from : 0u;
-                // (a stream that brings no packets still stands in the Apple Lossless batch: see ohgpu_mp4_alac_process_host)
-                const ohgpu_alac_config none = {1, 0, 16, 0, 0, 1, 1, 0, 0, 0, 0};
-                a.config = ok ? m.config : none;
-                a.first_packet = (uint32_t)dense.size();
-                a.n_packets = rows;
-                first_row[i] = descs[i].packet_first + from;
-                if (!ok && !a.flags) a.dst_plane_stride = 0;
-                if (rows) dense.insert(dense.end(), table.begin() + first_row[i], table.begin() + first_row[i] + rows);
-            }
-            pres.resize(dense.size());
-            if (dense.empty()) return (int)OHGPU_OK;
-            ohgpu_batch* ab = nullptr;
-            e = ohgpu_alac_batch_create(ctx, adescs.data(), n, dense.data(), dense.size(), mid_bytes, dst_bytes, &ab);
-            if (e != OHGPU_OK) return e;
-            const BatchPtr own(ab, BatchDeleter{ctx});
-            e = ohgpu_alac_batch_run(ctx, ab, d_mid, d_dst, nullptr);
-            if (e == OHGPU_OK) e = ohgpu_alac_batch_results(ctx, ab, ares.data(), n, pres.data(), pres.size());
-            return e;
-        },
-        [&] {   // only what was decoded comes back, as in ohgpu_alac_process_host
-            int e = OHGPU_OK;
-            for (size_t i = 0; i < n && e == OHGPU_OK; i++)
-                if (adescs[i].n_packets) e = alac_download_decoded(ctx, who, adescs[i], pres.data() + adescs[i].first_packet, dst_host);
-            return e;
-        });
-    if (d_mid) { (void)hipStreamSynchronize(ctx->stream); ctx_dev_free(ctx, d_mid); }
-    if (err != OHGPU_OK) return err;
-    if (results && n) memcpy(results, cres.data(), n * sizeof(cres[0]));
-    if (packets && n_packets) memcpy(packets, table.data(), n_packets * sizeof(table[0]));
-    if (alac_results && n) memcpy(alac_results, ares.data(), n * sizeof(ares[0]));
-    if (packet_results && n_packets) {
-        memset(packet_results, 0, n_packets * sizeof(*packet_results));
-        for (size_t i = 0; i < n; i++)
-            if (adescs[i].n_packets) memcpy(packet_results + first_row[i], pres.data() + adescs[i].first_packet, adescs[i].n_packets * sizeof(pres[0]));
-    }
-    return OHGPU_OK;
 }
 
 }  // namespace ohgpu

@@ -1,10 +1,8 @@
-// api_mp4f.hip -- the C ABI's fragmented MPEG-4 layer (ohgpu_mp4f_*): the validation of the descriptors, the batch's
-// life around csrc/mp4_frag_kernel.hip's launches, the results and the three tables, the host-buffer call, the head of a stream on the
-// host, and the two calls that put the FLAC and the Apple Lossless decoder behind it.
-#include <algorithm>
-#include <cstring>
-
-#include "api_common.h"
+// api_mp4f.hip -- the C ABI's fragmented MPEG-4 layer (ohgpu_mp4f_*): the validation of the descriptors, the results,
+// the head of a stream on the host, and the call that puts the Apple Lossless decoder behind it, which decodes the packets where they
+// lie.  The batch's life around csrc/mp4_frag_kernel.hip's launches, the three tables, the host-buffer call and the call in front of
+// the FLAC decoder are csrc/api_frag.h's bodies, shared with the two protected families, over the traits below.
+#include "api_frag.h"
 
 using namespace ohgpu;
 
@@ -25,25 +23,31 @@ int mp4f_check_desc(const ohgpu_mp4f_stream_desc& d, size_t i, size_t n_packets,
     return arena_span("mp4f desc", i, "gathers into", d.dst_offset, d.dst_capacity, dst_arena_bytes, "destination");
 }
 
-int mp4f_fetch(ohgpu_ctx* ctx, const char* who, const ohgpu_batch* batch, int table, void* out, size_t n_rows)
-{
-    OHGPU_TRY(state_guard(ctx, who, batch, kBatchMp4f, "a fragmented MPEG-4"));
-    const Mp4fState& g = *batch->mp4f;
-    return fetch_table(who, g, "rows, the batch's table has", "", n_rows, table == 0 ? g.n_runs : g.n_packets, g.n_streams, out,
-                       table == 0 ? g.d_runs : table == 1 ? g.d_packets : g.d_samples, table == 0 ? sizeof(ohgpu_mp4f_run) : 16u);
-}
-
-// what ohgpu_mp4f_process_host and the two decoder calls fetch after a run; any pointer may be null
-int mp4f_fetch_all(ohgpu_ctx* ctx, const ohgpu_batch* b, size_t n, size_t n_packets, size_t n_runs, ohgpu_mp4f_stream_result* results, ohgpu_mp4f_run* runs,
-                   ohgpu_alac_packet* packets, ohgpu_mp4_sample* samples)
-{
-    int e = OHGPU_OK;
-    if (results) e = ohgpu_mp4f_batch_results(ctx, b, n ? results : nullptr, n);
-    if (e == OHGPU_OK && runs) e = ohgpu_mp4f_batch_runs(ctx, b, n_runs ? runs : nullptr, n_runs);
-    if (e == OHGPU_OK && packets) e = ohgpu_mp4f_batch_packets(ctx, b, n_packets ? packets : nullptr, n_packets);
-    if (e == OHGPU_OK && samples) e = ohgpu_mp4f_batch_samples(ctx, b, n_packets ? samples : nullptr, n_packets);
-    return e;
-}
+struct Mp4fFamily : FragStateOf<Mp4fState, &ohgpu_batch::mp4f> {
+    using Desc = ohgpu_mp4f_stream_desc;
+    using Res = ohgpu_mp4f_stream_result;
+    static constexpr BatchKind kind = kBatchMp4f;
+    static constexpr const char* noun = "a fragmented MPEG-4";
+    static const ohgpu_mp4f_stream_result& head(const Res& r) { return r; }
+    static const void* packet_table(const State& g) { return g.d_packets; }
+    static uint32_t launch_blocks(const State& g) { return g.wave_blocks; }
+    static int check(const Desc* descs, const FragCounts& c, uint64_t src_arena_bytes, uint64_t dst_arena_bytes)
+    {
+        return ohgpu_mp4f_batch_check(descs, c.n, c.n_packets, c.n_runs, src_arena_bytes, dst_arena_bytes);
+    }
+    static void keys(State&, const Desc*, const FragCounts&) {}
+    static int plan(ohgpu_ctx* ctx, ohgpu_batch* b, const Desc* descs) { return mp4f_plan(ctx, *b->mp4f, (const mp4frag::Stream*)descs, "ohgpu_mp4f_batch_create"); }
+    static constexpr auto run = mp4f_run;
+    static int create(ohgpu_ctx* ctx, const Desc* descs, const FragCounts& c, uint64_t src_arena_bytes, uint64_t dst_arena_bytes, ohgpu_batch** out)
+    {
+        return ohgpu_mp4f_batch_create(ctx, descs, c.n, c.n_packets, c.n_runs, src_arena_bytes, dst_arena_bytes, out);
+    }
+    static constexpr auto run_c = ohgpu_mp4f_batch_run;
+    static constexpr auto results = ohgpu_mp4f_batch_results;
+    static constexpr auto runs = ohgpu_mp4f_batch_runs;
+    static constexpr auto packets = ohgpu_mp4f_batch_packets;
+    static constexpr auto samples = ohgpu_mp4f_batch_samples;
+};
 
 }  // namespace
 
@@ -70,30 +74,12 @@ int ohgpu_mp4f_batch_check(const ohgpu_mp4f_stream_desc* descs, size_t n, size_t
 int ohgpu_mp4f_batch_create(ohgpu_ctx* ctx, const ohgpu_mp4f_stream_desc* descs, size_t n, size_t n_packets, size_t n_runs, uint64_t src_arena_bytes,
                             uint64_t dst_arena_bytes, ohgpu_batch** out)
 {
-    CTX_GUARD("ohgpu_mp4f_batch_create");
-    BatchPtr b;
-    int err = batch_begin(ctx, "ohgpu_mp4f_batch_create", kBatchMp4f, n == 0 || descs, n, UINT64_MAX, src_arena_bytes, dst_arena_bytes, out, &b);
-    if (err == OHGPU_OK) err = ohgpu_mp4f_batch_check(descs, n, n_packets, n_runs, src_arena_bytes, dst_arena_bytes);
-    if (err != OHGPU_OK) return err;
-    b->mp4f = new (std::nothrow) Mp4fState();
-    if (!b->mp4f) return set_error(OHGPU_ERR_NOMEM, "ohgpu_mp4f_batch_create: out of host memory");
-    Mp4fState& g = *b->mp4f;
-    g.n_streams = n; g.n_packets = n_packets; g.n_runs = n_runs;
-    g.plain = ctx->variant == 1;
-    for (size_t i = 0; i < n; i++) {
-        b->src_bytes_touched += descs[i].src_bytes;
-        if ((descs[i].flags & OHGPU_MP4F_GATHER) && descs[i].dst_capacity) g.gathers = true;
-    }
-    err = mp4f_plan(ctx, g, (const mp4frag::Stream*)descs, "ohgpu_mp4f_batch_create");
-    return batch_done(err, b, out);
+    return frag_batch_create<Mp4fFamily>(ctx, "ohgpu_mp4f_batch_create", descs, {n, n_packets, n_runs, 0}, src_arena_bytes, dst_arena_bytes, out);
 }
 
 int ohgpu_mp4f_batch_run(ohgpu_ctx* ctx, const ohgpu_batch* batch, const void* src_base, void* dst_base, void* stream)
 {
-    const bool mine = batch && batch->kind == kBatchMp4f;
-    const int go = run_guard(ctx, "ohgpu_mp4f_batch_run", batch, kBatchMp4f, mine && batch->mp4f->n_streams == 0, true, src_base, dst_base, mine && batch->mp4f->gathers);
-    if (go <= 0) return go;
-    return mp4f_run(ctx, batch, (const uint8_t*)src_base, (uint8_t*)dst_base, pick_stream(ctx, stream));
+    return frag_batch_run<Mp4fFamily>(ctx, "ohgpu_mp4f_batch_run", batch, src_base, dst_base, stream);
 }
 
 int ohgpu_mp4f_batch_results(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_mp4f_stream_result* results, size_t n)
@@ -105,42 +91,32 @@ int ohgpu_mp4f_batch_results(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_mp4
 
 int ohgpu_mp4f_batch_runs(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_mp4f_run* runs, size_t n_runs)
 {
-    return mp4f_fetch(ctx, "ohgpu_mp4f_batch_runs", batch, 0, runs, n_runs);
+    return frag_fetch<Mp4fFamily>(ctx, "ohgpu_mp4f_batch_runs", batch, 0, runs, n_runs);
 }
 
 int ohgpu_mp4f_batch_packets(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_alac_packet* packets, size_t n_packets)
 {
-    return mp4f_fetch(ctx, "ohgpu_mp4f_batch_packets", batch, 1, packets, n_packets);
+    return frag_fetch<Mp4fFamily>(ctx, "ohgpu_mp4f_batch_packets", batch, 1, packets, n_packets);
 }
 
 int ohgpu_mp4f_batch_samples(ohgpu_ctx* ctx, const ohgpu_batch* batch, ohgpu_mp4_sample* samples, size_t n_packets)
 {
-    return mp4f_fetch(ctx, "ohgpu_mp4f_batch_samples", batch, 2, samples, n_packets);
+    return frag_fetch<Mp4fFamily>(ctx, "ohgpu_mp4f_batch_samples", batch, 2, samples, n_packets);
 }
 
 int ohgpu_mp4f_batch_phase_ms(ohgpu_ctx* ctx, const ohgpu_batch* batch, float ms[6])
 {
-    OHGPU_TRY(state_guard(ctx, "ohgpu_mp4f_batch_phase_ms", batch, kBatchMp4f, "a fragmented MPEG-4"));
-    if (!ms) return set_error(OHGPU_ERR_INVALID, "ohgpu_mp4f_batch_phase_ms: bad argument");
-    const Mp4fState& g = *batch->mp4f;
-    const int err = phase_ms("ohgpu_mp4f_batch_phase_ms", g.ran, g.ev, 6, ms);
-    if (err == OHGPU_OK && g.plain) ms[1] = ms[2] = ms[3] = ms[4] = ms[5] = 0.0f;      // (one launch: what lies between the later events is no phase)
-    return err;
+    return frag_batch_phase_ms<Mp4fFamily>(ctx, "ohgpu_mp4f_batch_phase_ms", batch, ms);
 }
 
 int ohgpu_mp4f_batch_paths(const ohgpu_batch* batch, uint32_t* route, uint32_t* tiles, uint32_t* wave_blocks)
 {
-    if (!batch || batch->kind != kBatchMp4f || !route) return set_error(OHGPU_ERR_INVALID, "ohgpu_mp4f_batch_paths: not a fragmented MPEG-4 batch, or a null argument");
-    *route = batch->mp4f->plain ? OHGPU_MP4F_ROUTE_PLAIN : OHGPU_MP4F_ROUTE_PHASES;
-    if (tiles) *tiles = batch->mp4f->n_tiles;
-    if (wave_blocks) *wave_blocks = batch->mp4f->plain ? 0u : batch->mp4f->wave_blocks;
-    return OHGPU_OK;
+    return frag_batch_paths<Mp4fFamily>("ohgpu_mp4f_batch_paths", batch, route, tiles, wave_blocks);
 }
 
 int ohgpu_mp4f_head(const void* bytes, size_t n, ohgpu_mp4f_stream_result* result)
 {
-    if ((n && !bytes) || !result) return set_error(OHGPU_ERR_INVALID, "ohgpu_mp4f_head: null argument");
-    if (n >= 0x80000000ull) return set_error(OHGPU_ERR_INVALID, "ohgpu_mp4f_head: %zu bytes are 2^31 or more", n);
+    OHGPU_TRY(frag_head_args("ohgpu_mp4f_head", bytes, n, result));
     mp4frag::Stream s = {};
     s.src_bytes = (uint32_t)n;
     s.codecs = OHGPU_MP4F_CODEC_ALAC | OHGPU_MP4F_CODEC_FLAC;
@@ -152,24 +128,8 @@ int ohgpu_mp4f_head(const void* bytes, size_t n, ohgpu_mp4f_stream_result* resul
 int ohgpu_mp4f_process_host(ohgpu_ctx* ctx, const ohgpu_mp4f_stream_desc* descs, size_t n, size_t n_packets, size_t n_runs, const void* src_host, uint64_t src_bytes,
                             void* dst_host, uint64_t dst_bytes, ohgpu_mp4f_stream_result* results, ohgpu_mp4f_run* runs, ohgpu_alac_packet* packets, ohgpu_mp4_sample* samples)
 {
-    const char* const who = "ohgpu_mp4f_process_host";
-    std::vector<ohgpu_mp4f_stream_result> res(n);
-    const int err = decoder_process_host(ctx, who, src_host, src_bytes, dst_host, dst_bytes,
-        [&](ohgpu_batch** b) { return ohgpu_mp4f_batch_create(ctx, descs, n, n_packets, n_runs, src_bytes, dst_bytes, b); },
-        [&](const ohgpu_batch* b, const void* d_src, void* d_dst) {
-            const int e = ohgpu_mp4f_batch_run(ctx, b, d_src, d_dst, nullptr);
-            return e != OHGPU_OK ? e : mp4f_fetch_all(ctx, b, n, n_packets, n_runs, res.data(), runs, packets, samples);
-        },
-        [&] {   // only what was gathered comes back
-            for (size_t i = 0; i < n; i++) {
-                if (!res[i].bytes_gathered) continue;
-                const int e = download_planes(ctx, who, dst_host, descs[i].dst_offset, 0, 1, 1, 0, res[i].bytes_gathered);
-                if (e != OHGPU_OK) return e;
-            }
-            return (int)OHGPU_OK;
-        });
-    if (err == OHGPU_OK && results && n) memcpy(results, res.data(), n * sizeof(res[0]));
-    return err;
+    return frag_process_host<Mp4fFamily>(ctx, "ohgpu_mp4f_process_host", descs, {n, n_packets, n_runs, 0}, src_host, src_bytes, dst_host, dst_bytes, results, runs, packets,
+                                         samples);
 }
 
 int ohgpu_mp4f_flac_process_host(ohgpu_ctx* ctx, const ohgpu_mp4f_stream_desc* mp4f_descs, const ohgpu_flac_stream_desc* flac_descs, size_t n, size_t n_packets, size_t n_runs,
@@ -177,14 +137,8 @@ int ohgpu_mp4f_flac_process_host(ohgpu_ctx* ctx, const ohgpu_mp4f_stream_desc* m
                                  ohgpu_mp4f_stream_result* mp4f_results, ohgpu_mp4f_run* runs, ohgpu_alac_packet* packets, ohgpu_mp4_sample* samples,
                                  ohgpu_flac_stream_result* flac_results, ohgpu_flac_frame* frames, size_t frames_capacity, size_t* n_frames)
 {
-    return frag_flac_process_host(ctx, "ohgpu_mp4f_flac_process_host", mp4f_descs, flac_descs, n, src_host, src_bytes, mid_bytes, dst_host, dst_bytes, mp4f_results, flac_results,
-        frames, frames_capacity, n_frames,
-        [&](ohgpu_batch** b) { return ohgpu_mp4f_batch_create(ctx, mp4f_descs, n, n_packets, n_runs, src_bytes, mid_bytes, b); },
-        [&](const ohgpu_batch* b, const void* d_src, void* d_mid, ohgpu_mp4f_stream_result* res) {
-            const int e = ohgpu_mp4f_batch_run(ctx, b, d_src, d_mid, nullptr);
-            return e != OHGPU_OK ? e : mp4f_fetch_all(ctx, b, n, n_packets, n_runs, res, runs, packets, samples);   // (the results: the one small read between the layers)
-        },
-        [](const ohgpu_mp4f_stream_result& r) -> const ohgpu_mp4f_stream_result& { return r; });
+    return frag_flac_process_host<Mp4fFamily>(ctx, "ohgpu_mp4f_flac_process_host", mp4f_descs, flac_descs, {n, n_packets, n_runs, 0}, src_host, src_bytes, mid_bytes, dst_host, dst_bytes,
+                                              mp4f_results, runs, packets, samples, flac_results, frames, frames_capacity, n_frames);
 }
 
 int ohgpu_mp4f_alac_process_host(ohgpu_ctx* ctx, const ohgpu_mp4f_stream_desc* mp4f_descs, const ohgpu_alac_stream_desc* alac_descs, size_t n, size_t n_packets, size_t n_runs,
@@ -205,8 +159,7 @@ int ohgpu_mp4f_alac_process_host(ohgpu_ctx* ctx, const ohgpu_mp4f_stream_desc* m
         [&](ohgpu_batch** b) { return ohgpu_mp4f_batch_create(ctx, mp4f_descs, n, n_packets, n_runs, src_bytes, 0, b); },
         [&](const ohgpu_batch* b, const void* d_src, void* d_dst) {
             if (!n) return (int)OHGPU_OK;
-            int e = ohgpu_mp4f_batch_run(ctx, b, d_src, nullptr, nullptr);
-            if (e == OHGPU_OK) e = mp4f_fetch_all(ctx, b, n, n_packets, n_runs, mres.data(), runs, table.data(), samples);   // the one small read between the layers
+            int e = frag_run_fetch<Mp4fFamily>(ctx, b, d_src, nullptr, {n, n_packets, n_runs, 0}, mres.data(), runs, table.data(), samples);   // the one small read between the layers
             if (e != OHGPU_OK) return e;
             // the Apple Lossless table has the streams' leading accepted rows one after the other without gaps
             for (size_t i = 0; i < n; i++) {

@@ -26,6 +26,7 @@
 #pragma once
 
 #include "cenc_core.h"
+#include "frag_units.h"
 
 #define CBCS_HD MP4B_HD
 
@@ -376,13 +377,7 @@ CBCS_HD void gather_serial(const Stream& cs, const uint8_t* src, uint8_t* dst, c
 // The entry of a sample that holds its unit u (n_sub != 0): the last whose unit_first is <= u.
 CBCS_HD uint32_t entry_of(const SubRow* subs, uint32_t n_sub, uint32_t u)
 {
-    uint32_t lo = 0, hi = n_sub;
-    while (hi - lo > 1u) {
-        MP4B_STEP(3);
-        const uint32_t mid = lo + (hi - lo) / 2u;
-        if (subs[mid].unit_first <= u) lo = mid; else hi = mid;
-    }
-    return lo;
+    return fragu::last_le(0u, n_sub, u, [subs](uint32_t k) { MP4B_STEP(3); return subs[k].unit_first; });
 }
 
 }  // namespace cbcs

@@ -1,5 +1,5 @@
 // cbcs_kernel.hip -- the second protected fragmented MPEG-4 family on the device (the text is csrc/cbcs_core.h over
-// csrc/cenc_core.h and csrc/mp4_frag_core.h).  The launches are csrc/cenc_kernel.hip's, re-stated over work units (a 16-byte piece of a
+// csrc/cenc_core.h and csrc/mp4_frag_core.h).  The launches have csrc/cenc_kernel.hip's shape, over work units (a 16-byte piece of a
 // part of a sample) where that file counts keystream blocks:
 //   walk            a lane per stream: mp4frag's walk under cbcs::Protection.  At every traf's end the lane follows the senc's entries --
 //                   a chain, serial inside a traf -- and writes the stream's subsample rows and a record a sample (cbcs_core.h says why
@@ -24,17 +24,11 @@
 // Loads: the walk's are mp4_frag_kernel.hip's, the chain's lie inside a senc that was held to its box entry by entry; an IV lies inside
 // that senc or inside the tenc; a sample is read only when emit() found it inside the stream, and a part only where the chain found its
 // parts to sum to its size.  Stores: the stream's rows, run slots and subsample rows, its own records, or [dst_offset, + bytes_gathered).
-#include <hip/hip_runtime.h>
-
-#include "api_common.h"
+// The scan, the tiles' prefix, the persistent loop and its searches, the plan of the slots and the run around the launches are
+// csrc/protected_shell.h's (over csrc/frag_units.h), shared with csrc/cenc_kernel.hip: this file has the kernels' own parts.
+#include "protected_shell.h"
 
 namespace ohgpu {
-
-using namespace mp4frag;
-
-constexpr uint32_t kCbcsThreads = 256, kCbcsWaves = kCbcsThreads / 64, kCbcsPerThread = kTile / kCbcsThreads;
-constexpr uint32_t kCbcsGroupsPerCu = 8;
-static_assert(kTile % kCbcsThreads == 0 && kCbcsThreads == 256, "a tile is a whole number of samples a thread; a thread stages one word of each table");
 
 constexpr cenc::Forward kCbcsHostForward = cenc::make_forward();
 constexpr raopcore::Tables kCbcsHostInverse = raopcore::make_tables();
@@ -56,13 +50,13 @@ __global__ __launch_bounds__(64) void cbcs_walk_kernel(const cbcs::Stream* __res
     cipher_blocks[i] = 0u;
 }
 
-__global__ __launch_bounds__(kCbcsThreads) void cbcs_rows_kernel(const Stream* __restrict__ streams, const Rec* __restrict__ recs, const RunRec* __restrict__ runrecs,
+__global__ __launch_bounds__(kProtThreads) void cbcs_rows_kernel(const Stream* __restrict__ streams, const Rec* __restrict__ recs, const RunRec* __restrict__ runrecs,
                                                                  const Mp4fTile* __restrict__ tiles, const Result* __restrict__ results, const cenc::Extra* __restrict__ extras,
                                                                  const cbcs::More* __restrict__ more, const cbcs::SampleRec* __restrict__ samprecs,
                                                                  const Row* __restrict__ src_rows, Row* __restrict__ rows, uint64_t* __restrict__ unit_first,
                                                                  uint64_t* __restrict__ tile_units, unsigned long long* __restrict__ cipher_blocks)
 {
-    __shared__ uint64_t part[kCbcsWaves];
+    __shared__ uint64_t part[kProtWaves];
     const Mp4fTile tile = tiles[blockIdx.x];
     const Rec rec = recs[tile.stream];
     if (tile.s0 >= rec.rows) return;                                  // (uniform over the workgroup)
@@ -71,64 +65,39 @@ __global__ __launch_bounds__(kCbcsThreads) void cbcs_rows_kernel(const Stream* _
     const RunRec* const runs = runrecs + st.run_first;
     const uint32_t kind = cbcs::kind_of(extras[tile.stream]);
     const cbcs::More m = more[tile.stream];
-    const uint32_t tid = threadIdx.x, lane = tid % 64u, wave = tid / 64u, first = tile.s0 + tid * kCbcsPerThread;
-    uint32_t n[kCbcsPerThread];
-    uint64_t mine = 0, blocks = 0;
-    for (uint32_t k = 0; k < kCbcsPerThread; k++) {
+    const uint32_t first = tile.s0 + threadIdx.x * kProtPerThread;
+    uint32_t n[kProtPerThread];
+    uint64_t blocks = 0;
+    for (uint32_t k = 0; k < kProtPerThread; k++) {
         const uint32_t s = first + k;
         n[k] = 0;
         if (s >= rec.rows) continue;
-        Row out;
-        out.src_offset = st.dst_offset; out.bytes = 0; out.reserved = 0;
-        if (cenc::gathered_row(st, res, s)) {
-            const uint32_t k_run = run_of(runs, rec.runs_written, s);
-            const Row from = src_rows[st.packet_first + s];
-            out.src_offset = cenc::row_place(st, rec, runs, k_run, from); out.bytes = from.bytes;
-            uint32_t b;
+        Row from;
+        uint32_t k_run, b;
+        if (public_row(st, rec, res, runs, src_rows, rows, s, &from, &k_run)) {
             cbcs::sample_work(kind, m, samprecs + st.packet_first, s, from.bytes, &n[k], &b);
             blocks += b;
         }
-        uint4 v;
-        __builtin_memcpy(&v, &out, 16);
-        *reinterpret_cast<uint4*>(&rows[st.packet_first + s]) = v;
-        mine += n[k];
-    }
-    uint64_t incl = mine;
-    for (uint32_t o = 1; o < 64u; o <<= 1) {
-        const uint64_t up = (uint64_t)__shfl_up((unsigned long long)incl, o);
-        if (lane >= o) incl += up;
     }
     for (uint32_t o = 32u; o; o >>= 1) blocks += (uint64_t)__shfl_down((unsigned long long)blocks, o);
-    if (lane == 0u && blocks) atomicAdd(&cipher_blocks[tile.stream], (unsigned long long)blocks);
-    if (lane == 63u) part[wave] = incl;
-    __syncthreads();
-    uint64_t before = incl - mine;
-    for (uint32_t w = 0; w < wave; w++) before += part[w];
-    for (uint32_t k = 0; k < kCbcsPerThread; k++) {
+    if (threadIdx.x % 64u == 0u && blocks) atomicAdd(&cipher_blocks[tile.stream], (unsigned long long)blocks);
+    uint64_t before, total;
+    tile_exclusive_scan(n, part, &before, &total);
+    for (uint32_t k = 0; k < kProtPerThread; k++) {
         const uint32_t s = first + k;
         if (s < rec.rows) unit_first[st.packet_first + s] = before;
         before += n[k];
     }
-    if (tid == kCbcsThreads - 1u) tile_units[blockIdx.x] = before;
+    if (threadIdx.x == kProtThreads - 1u) tile_units[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(64) void cbcs_tiles_kernel(uint32_t n, const Rec* __restrict__ recs, const uint32_t* __restrict__ tile_first, uint64_t* __restrict__ tile_units,
                                                         uint64_t* __restrict__ nunits, const unsigned long long* __restrict__ cipher_blocks, cenc::Extra* __restrict__ extras)
 {
-    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t t0 = tile_first[i], used = (recs[i].rows + kTile - 1u) / kTile;        // (rows <= packet_capacity: the stream has that many tiles)
-    uint64_t acc = 0;
-    for (uint32_t t = t0; t < t0 + used; t++) {
-        const uint64_t v = tile_units[t];
-        tile_units[t] = acc;
-        acc += v;
-    }
-    nunits[i] = acc;
-    extras[i].blocks = cipher_blocks[i];
+    tiles_body(n, recs, tile_first, tile_units, nunits, extras, [=](uint32_t i, uint64_t) { return (uint64_t)cipher_blocks[i]; });
 }
 
-__global__ __launch_bounds__(kCbcsThreads) void cbcs_crypt_kernel(const Stream* __restrict__ streams, uint32_t n_streams, const Rec* __restrict__ recs,
+__global__ __launch_bounds__(kProtThreads) void cbcs_crypt_kernel(const Stream* __restrict__ streams, uint32_t n_streams, const Rec* __restrict__ recs,
                                                                   const cenc::Extra* __restrict__ extras, const cbcs::More* __restrict__ more,
                                                                   const uint32_t* __restrict__ tile_first, const uint64_t* __restrict__ tile_units,
                                                                   const uint64_t* __restrict__ chunk_first, uint64_t n_chunks, const uint64_t* __restrict__ nunits,
@@ -150,57 +119,26 @@ __global__ __launch_bounds__(kCbcsThreads) void cbcs_crypt_kernel(const Stream* 
     __syncthreads();
     cbcs::Tables t;
     t.te0 = te0; t.td0 = td0; t.isbox = (const uint8_t*)isbox;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / 64u), lane = threadIdx.x % 64u;
-    const uint64_t stride = (uint64_t)gridDim.x * kCbcsWaves;
-    for (uint64_t g = (uint64_t)blockIdx.x * kCbcsWaves + wave; g < n_chunks;) {
-        uint32_t lo = 0, hi = n_streams;                              // the stream the slot lies in: the last whose first slot is <= g
-        while (hi - lo > 1u) {
-            const uint32_t mid = lo + (hi - lo) / 2u;
-            if (chunk_first[mid] <= g) lo = mid; else hi = mid;
-        }
-        const uint32_t i = __builtin_amdgcn_readfirstlane(lo);
-        const uint64_t total = nunits[i], u0 = (g - chunk_first[i]) * cbcs::kLaneUnits;
-        if (u0 >= total) {                                            // behind the stream's last unit: on to the next stream's slots
-            g += (chunk_first[i + 1u] - g + stride - 1u) / stride * stride;
-            continue;
-        }
-        g += stride;
-        const uint64_t u = u0 + lane;
-        if (u >= total) continue;
-        const Stream& st = streams[i];
-        const uint32_t t0 = tile_first[i], n_rows = recs[i].rows, used = (n_rows + kTile - 1u) / kTile;
-        uint32_t ta = 0, tb = used;                                   // the tile: the last whose first unit is <= u
-        while (tb - ta > 1u) {
-            const uint32_t mid = ta + (tb - ta) / 2u;
-            if (tile_units[t0 + mid] <= u) ta = mid; else tb = mid;
-        }
-        const uint64_t in_tile = u - tile_units[t0 + ta];
-        const uint32_t s0 = ta * kTile, s1 = s0 + kTile < n_rows ? s0 + kTile : n_rows;
-        const uint64_t* const uf = unit_first + st.packet_first;
-        uint32_t ra = s0, rb = s1;                                    // the row: the last of the tile whose first unit is <= in_tile
-        while (rb - ra > 1u) {
-            const uint32_t mid = ra + (rb - ra) / 2u;
-            if (uf[mid] <= in_tile) ra = mid; else rb = mid;
-        }
-        const uint32_t j = (uint32_t)(in_tile - uf[ra]);
-        const Row from = src_rows[st.packet_first + ra], to = rows[st.packet_first + ra];
-        const uint32_t kind = __builtin_amdgcn_readfirstlane(cbcs::kind_of(extras[i]));
-        const uint32_t pattern = __builtin_amdgcn_readfirstlane((uint32_t)more[i].crypt << 8 | more[i].skip);
-        const uint32_t iv_bytes = __builtin_amdgcn_readfirstlane(extras[i].iv_size ? (uint32_t)extras[i].iv_size : (uint32_t)more[i].civ_size);
-        cbcs::SubRow e = cbcs::whole_sample(kind, from.bytes);
-        uint32_t v = j;
-        cbcs::SampleIv iv = {};
-        if (kind != cbcs::kCopy) {
-            const cbcs::SampleRec sr = samprecs[st.packet_first + ra];
-            iv = cbcs::read_sample_iv(src + st.src_offset, sr.iv_pos, iv_bytes);
-            if (sr.n_sub) {
-                const cbcs::SubRow* const mine = subs + sub_first[i] + sr.sub_first;
-                e = mine[cbcs::entry_of(mine, sr.n_sub, j)];
-                v = j - e.unit_first;
+    unit_loop(streams, n_streams, recs, tile_first, tile_units, chunk_first, n_chunks, nunits, [=](uint32_t r) { return unit_first[r]; },
+        [=](uint32_t i, const Stream& st, uint32_t r, uint32_t j) {
+            const Row from = src_rows[r], to = rows[r];
+            const uint32_t kind = __builtin_amdgcn_readfirstlane(cbcs::kind_of(extras[i]));
+            const uint32_t pattern = __builtin_amdgcn_readfirstlane((uint32_t)more[i].crypt << 8 | more[i].skip);
+            const uint32_t iv_bytes = __builtin_amdgcn_readfirstlane(extras[i].iv_size ? (uint32_t)extras[i].iv_size : (uint32_t)more[i].civ_size);
+            cbcs::SubRow e = cbcs::whole_sample(kind, from.bytes);
+            uint32_t v = j;
+            cbcs::SampleIv iv = {};
+            if (kind != cbcs::kCopy) {
+                const cbcs::SampleRec sr = samprecs[r];
+                iv = cbcs::read_sample_iv(src + st.src_offset, sr.iv_pos, iv_bytes);
+                if (sr.n_sub) {
+                    const cbcs::SubRow* const mine = subs + sub_first[i] + sr.sub_first;
+                    e = mine[cbcs::entry_of(mine, sr.n_sub, j)];
+                    v = j - e.unit_first;
+                }
             }
-        }
-        cbcs::unit_lane(src + from.src_offset, dst + to.src_offset, e, v, kind, pattern >> 8, pattern & 0xffu, keys + (size_t)i * cbcs::kKeyWords, iv, t);
-    }
+            cbcs::unit_lane(src + from.src_offset, dst + to.src_offset, e, v, kind, pattern >> 8, pattern & 0xffu, keys + (size_t)i * cbcs::kKeyWords, iv, t);
+        });
 }
 
 __global__ __launch_bounds__(64) void cbcs_plain_kernel(const cbcs::Stream* __restrict__ streams, uint32_t n, const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
@@ -249,54 +187,19 @@ int cbcs_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const cbcs::Stream* streams)
         sub_first[i] = streams[i].sub_first;
         for (uint8_t& k : stripped[i].c.key) k = 0;
     }
-    OHGPU_TRY(mp4f_plan(ctx, g, plain.data(), "ohgpu_cbcs_batch_create"));
+    OHGPU_TRY(protected_plan<uint64_t>(ctx, g, plain, stripped, "ohgpu_cbcs_batch_create", [&](size_t i) { return streams[i].sub_capacity; }));
     if (!n) return OHGPU_OK;
-    g.tile_first.assign(n + 1, 0);
-    std::vector<uint64_t> chunk_first(n + 1, 0);
-    for (size_t i = 0; i < n; i++) {
-        const Stream& s = plain[i];
-        g.tile_first[i + 1] = g.tile_first[i] + (g.plain ? 0u : (uint32_t)(((uint64_t)s.packet_capacity + kTile - 1u) / kTile));
-        // a part of B bytes is at most B / 16 + 1 units (+ 2 under a keystream offset), a sample without entries at most size / 16 + 1
-        const uint64_t units = s.packet_capacity && s.dst_capacity ? s.dst_capacity / 16u + s.packet_capacity + 3ull * streams[i].sub_capacity : 0u;
-        chunk_first[i + 1] = chunk_first[i] + (g.plain ? 0u : (units + cbcs::kLaneUnits - 1u) / cbcs::kLaneUnits);
-    }
-    g.n_chunks = chunk_first[n];
-    const uint64_t want = (g.n_chunks + kCbcsWaves - 1u) / kCbcsWaves, cap = (uint64_t)(ctx->num_cus > 0 ? ctx->num_cus : 256) * kCbcsGroupsPerCu;
-    g.crypt_blocks = (uint32_t)(want < cap ? want : cap);
-    g.keys_bytes = g.keys.size() * sizeof(uint32_t);
-    OHGPU_TRY(dev_array(ctx, g, &g.d_cstreams, n, stripped.data()));
-    OHGPU_TRY(dev_array(ctx, g, &g.d_keys, g.keys.size(), g.keys.data()));
-    OHGPU_TRY(dev_array<cenc::Extra>(ctx, g, &g.d_extras, n));
     OHGPU_TRY(dev_array<cbcs::More>(ctx, g, &g.d_more, n));
-    OHGPU_TRY(dev_array<Row>(ctx, g, &g.d_rows, g.n_packets));
-    OHGPU_TRY(dev_array<uint64_t>(ctx, g, &g.d_unit_first, g.n_packets));
     OHGPU_TRY(dev_array<cbcs::SampleRec>(ctx, g, &g.d_samprecs, g.n_packets));
     OHGPU_TRY(dev_array<cbcs::SubRow>(ctx, g, &g.d_subs, g.n_subsamples));
-    OHGPU_TRY(dev_array(ctx, g, &g.d_tile_first, n + 1, g.tile_first.data()));
-    OHGPU_TRY(dev_array<uint64_t>(ctx, g, &g.d_tile_units, g.n_tiles));
-    OHGPU_TRY(dev_array(ctx, g, &g.d_chunk_first, n + 1, chunk_first.data()));
-    OHGPU_TRY(dev_array<uint64_t>(ctx, g, &g.d_nunits, n));
     OHGPU_TRY(dev_array<uint64_t>(ctx, g, &g.d_cipher_blocks, n));
     OHGPU_TRY(dev_array(ctx, g, &g.d_sub_first, n, sub_first.data()));
     return OHGPU_OK;
 }
 
-void cbcs_free(ohgpu_ctx* ctx, ohgpu_batch* b)
-{
-    if (b->cbcs) {
-        CbcsState& g = *b->cbcs;
-        (void)hipDeviceSynchronize();
-        // the schedules do not outlive the batch: the device block is cleared before it goes back to the cache, the host copy too
-        if (g.d_keys) (void)hipMemset(g.d_keys, 0, g.keys_bytes);
-        for (uint32_t& w : g.keys) *(volatile uint32_t*)&w = 0;
-    }
-    state_free(ctx, b->cbcs);
-}
-
 int cbcs_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s)
 {
     CbcsState& g = *b->cbcs;
-    OHGPU_TRY(run_begin(g, s));      // (the tables serve one run at a time)
     const uint32_t ns = (uint32_t)g.n_streams, lane_blocks = (ns + 63u) / 64u;
     const cbcs::Stream* const cstreams = (const cbcs::Stream*)g.d_cstreams;
     Result* const results = (Result*)g.d_results;
@@ -308,37 +211,34 @@ int cbcs_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
     cbcs::SampleRec* const samprecs = (cbcs::SampleRec*)g.d_samprecs;
     unsigned long long* const cipher_blocks = (unsigned long long*)g.d_cipher_blocks;
     const uint32_t* const keys = (const uint32_t*)g.d_keys;
-    OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[0], s));
-    OHGPU_TRY(mp4f_fill(g, s));                                       // (no row of the run before stands in a table: csrc/mp4_frag_kernel.hip)
-    if (g.n_packets) OHGPU_HIP_TRY_ALLOC(hipMemsetAsync(g.d_rows, 0xa5, g.n_packets * sizeof(Row), s));
-    if (g.plain) {
-        hipLaunchKernelGGL(cbcs_plain_kernel, dim3(lane_blocks), dim3(64), 0, s, cstreams, ns, src, dst, results, extras, more, recs, runrecs, (Run*)g.d_runs, (Row*)g.d_packets,
-                           (Row*)g.d_rows, (Sample*)g.d_samples, subs, samprecs, keys);
-        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-        for (int k = 1; k < 6; k++) OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[k], s));
-        return run_end(g, s);
-    }
-    hipLaunchKernelGGL(cbcs_walk_kernel, dim3(lane_blocks), dim3(64), 0, s, cstreams, ns, src, (Stream*)g.d_streams, results, extras, more, recs, runrecs, subs, samprecs,
-                       cipher_blocks);
-    OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-    OHGPU_TRY(mp4f_tables(g, src, s));
-    if (g.n_tiles) {
-        hipLaunchKernelGGL(cbcs_rows_kernel, dim3(g.n_tiles), dim3(kCbcsThreads), 0, s, (const Stream*)g.d_streams, (const Rec*)recs, (const RunRec*)runrecs,
-                           (const Mp4fTile*)g.d_tiles, (const Result*)results, (const cenc::Extra*)extras, (const cbcs::More*)more, (const cbcs::SampleRec*)samprecs,
-                           (const Row*)g.d_packets, (Row*)g.d_rows, (uint64_t*)g.d_unit_first, (uint64_t*)g.d_tile_units, cipher_blocks);
-        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-    }
-    hipLaunchKernelGGL(cbcs_tiles_kernel, dim3(lane_blocks), dim3(64), 0, s, ns, (const Rec*)recs, (const uint32_t*)g.d_tile_first, (uint64_t*)g.d_tile_units,
-                       (uint64_t*)g.d_nunits, (const unsigned long long*)cipher_blocks, extras);
-    OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-    if (g.n_tiles && g.crypt_blocks) {
-        hipLaunchKernelGGL(cbcs_crypt_kernel, dim3(g.crypt_blocks), dim3(kCbcsThreads), 0, s, (const Stream*)g.d_streams, ns, (const Rec*)recs, (const cenc::Extra*)extras,
-                           (const cbcs::More*)more, (const uint32_t*)g.d_tile_first, (const uint64_t*)g.d_tile_units, (const uint64_t*)g.d_chunk_first, g.n_chunks,
-                           (const uint64_t*)g.d_nunits, keys, (const Row*)g.d_packets, (const Row*)g.d_rows, (const uint64_t*)g.d_unit_first, (const cbcs::SampleRec*)samprecs,
-                           (const cbcs::SubRow*)subs, (const uint32_t*)g.d_sub_first, src, dst);
-        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-    }
-    return run_end(g, s);
+    return protected_run(g, src, s,
+        [&] {
+            hipLaunchKernelGGL(cbcs_plain_kernel, dim3(lane_blocks), dim3(64), 0, s, cstreams, ns, src, dst, results, extras, more, recs, runrecs, (Run*)g.d_runs,
+                               (Row*)g.d_packets, (Row*)g.d_rows, (Sample*)g.d_samples, subs, samprecs, keys);
+        },
+        [&] {
+            hipLaunchKernelGGL(cbcs_walk_kernel, dim3(lane_blocks), dim3(64), 0, s, cstreams, ns, src, (Stream*)g.d_streams, results, extras, more, recs, runrecs, subs, samprecs,
+                               cipher_blocks);
+        },
+        [&]() -> int {
+            if (g.n_tiles) {
+                hipLaunchKernelGGL(cbcs_rows_kernel, dim3(g.n_tiles), dim3(kProtThreads), 0, s, (const Stream*)g.d_streams, (const Rec*)recs, (const RunRec*)runrecs,
+                                   (const Mp4fTile*)g.d_tiles, (const Result*)results, (const cenc::Extra*)extras, (const cbcs::More*)more, (const cbcs::SampleRec*)samprecs,
+                                   (const Row*)g.d_packets, (Row*)g.d_rows, (uint64_t*)g.d_row_first, (uint64_t*)g.d_tile_units, cipher_blocks);
+                OHGPU_HIP_TRY_ALLOC(hipGetLastError());
+            }
+            // (with no tile too: the streams' units and blocks are this launch's to write)
+            hipLaunchKernelGGL(cbcs_tiles_kernel, dim3(lane_blocks), dim3(64), 0, s, ns, (const Rec*)recs, (const uint32_t*)g.d_tile_first, (uint64_t*)g.d_tile_units,
+                               (uint64_t*)g.d_nunits, (const unsigned long long*)cipher_blocks, extras);
+            OHGPU_HIP_TRY_ALLOC(hipGetLastError());
+            if (!g.n_tiles || !g.crypt_blocks) return OHGPU_OK;
+            hipLaunchKernelGGL(cbcs_crypt_kernel, dim3(g.crypt_blocks), dim3(kProtThreads), 0, s, (const Stream*)g.d_streams, ns, (const Rec*)recs, (const cenc::Extra*)extras,
+                               (const cbcs::More*)more, (const uint32_t*)g.d_tile_first, (const uint64_t*)g.d_tile_units, (const uint64_t*)g.d_chunk_first, g.n_chunks,
+                               (const uint64_t*)g.d_nunits, keys, (const Row*)g.d_packets, (const Row*)g.d_rows, (const uint64_t*)g.d_row_first,
+                               (const cbcs::SampleRec*)samprecs, (const cbcs::SubRow*)subs, (const uint32_t*)g.d_sub_first, src, dst);
+            OHGPU_HIP_TRY_ALLOC(hipGetLastError());
+            return OHGPU_OK;
+        });
 }
 
 }  // namespace ohgpu

@@ -22,17 +22,11 @@
 // Loads: the walk's are mp4_frag_kernel.hip's; an IV lies inside a senc that the walk held to its box; a sample is read only when
 // emit() found it inside the stream, in the aligned dwords that hold it.  Stores: the stream's rows and run slots, its own records, or
 // [dst_offset, + bytes_gathered <= dst_capacity).
-#include <hip/hip_runtime.h>
-
-#include "api_common.h"
+// The scan, the tiles' prefix, the persistent loop and its searches, the plan of the slots and the run around the launches are
+// csrc/protected_shell.h's (over csrc/frag_units.h), shared with csrc/cbcs_kernel.hip: this file has the kernels' own parts.
+#include "protected_shell.h"
 
 namespace ohgpu {
-
-using namespace mp4frag;
-
-constexpr uint32_t kCencThreads = 256, kCencWaves = kCencThreads / 64, kCencPerThread = kTile / kCencThreads;
-constexpr uint32_t kCencGroupsPerCu = 8;
-static_assert(kTile % kCencThreads == 0 && kCencThreads == 256, "a tile is a whole number of samples a thread; a thread stages one word of Te0");
 
 constexpr cenc::Forward kCencHostForward = cenc::make_forward();
 __constant__ const cenc::Forward kCencForward = kCencHostForward;
@@ -46,12 +40,12 @@ __global__ __launch_bounds__(64) void cenc_walk_kernel(const cenc::Stream* __res
     cenc::walk(s, src + s.s.src_offset, false, &results[i], &extras[i], &recs[i], runrecs + s.s.run_first);
 }
 
-__global__ __launch_bounds__(kCencThreads) void cenc_rows_kernel(const Stream* __restrict__ streams, const Rec* __restrict__ recs, const RunRec* __restrict__ runrecs,
+__global__ __launch_bounds__(kProtThreads) void cenc_rows_kernel(const Stream* __restrict__ streams, const Rec* __restrict__ recs, const RunRec* __restrict__ runrecs,
                                                                  const Mp4fTile* __restrict__ tiles, const Result* __restrict__ results, const cenc::Extra* __restrict__ extras,
                                                                  const Row* __restrict__ src_rows, Row* __restrict__ rows, cenc::RowRec* __restrict__ rowrecs,
                                                                  uint64_t* __restrict__ tile_blocks)
 {
-    __shared__ uint64_t part[kCencWaves];
+    __shared__ uint64_t part[kProtWaves];
     const Mp4fTile tile = tiles[blockIdx.x];
     const Rec rec = recs[tile.stream];
     if (tile.s0 >= rec.rows) return;                                  // (uniform over the workgroup)
@@ -60,37 +54,22 @@ __global__ __launch_bounds__(kCencThreads) void cenc_rows_kernel(const Stream* _
     const RunRec* const runs = runrecs + st.run_first;
     const bool prot = extras[tile.stream].is_protected != 0u;
     const uint32_t iv_size = extras[tile.stream].iv_size;
-    const uint32_t tid = threadIdx.x, lane = tid % 64u, wave = tid / 64u, first = tile.s0 + tid * kCencPerThread;
-    uint32_t n[kCencPerThread], iv_pos[kCencPerThread];
-    uint64_t mine = 0;
-    for (uint32_t k = 0; k < kCencPerThread; k++) {
+    const uint32_t first = tile.s0 + threadIdx.x * kProtPerThread;
+    uint32_t n[kProtPerThread], iv_pos[kProtPerThread];
+    for (uint32_t k = 0; k < kProtPerThread; k++) {
         const uint32_t s = first + k;
         n[k] = iv_pos[k] = 0;
         if (s >= rec.rows) continue;
-        Row out;
-        out.src_offset = st.dst_offset; out.bytes = 0; out.reserved = 0;
-        if (cenc::gathered_row(st, res, s)) {
-            const uint32_t k_run = run_of(runs, rec.runs_written, s);
-            const Row from = src_rows[st.packet_first + s];
-            out.src_offset = cenc::row_place(st, rec, runs, k_run, from); out.bytes = from.bytes;
+        Row from;
+        uint32_t k_run;
+        if (public_row(st, rec, res, runs, src_rows, rows, s, &from, &k_run)) {
             n[k] = cenc::blocks_of(from.bytes);
             if (prot) iv_pos[k] = runs[k_run].iv_pos + (s - runs[k_run].first_sample) * iv_size;
         }
-        uint4 v;
-        __builtin_memcpy(&v, &out, 16);
-        *reinterpret_cast<uint4*>(&rows[st.packet_first + s]) = v;
-        mine += n[k];
     }
-    uint64_t incl = mine;
-    for (uint32_t o = 1; o < 64u; o <<= 1) {
-        const uint64_t up = (uint64_t)__shfl_up((unsigned long long)incl, o);
-        if (lane >= o) incl += up;
-    }
-    if (lane == 63u) part[wave] = incl;
-    __syncthreads();
-    uint64_t before = incl - mine;
-    for (uint32_t w = 0; w < wave; w++) before += part[w];
-    for (uint32_t k = 0; k < kCencPerThread; k++) {
+    uint64_t before, total;
+    tile_exclusive_scan(n, part, &before, &total);
+    for (uint32_t k = 0; k < kProtPerThread; k++) {
         const uint32_t s = first + k;
         if (s < rec.rows) {
             cenc::RowRec r;
@@ -99,26 +78,16 @@ __global__ __launch_bounds__(kCencThreads) void cenc_rows_kernel(const Stream* _
         }
         before += n[k];
     }
-    if (tid == kCencThreads - 1u) tile_blocks[blockIdx.x] = before;
+    if (threadIdx.x == kProtThreads - 1u) tile_blocks[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(64) void cenc_tiles_kernel(uint32_t n, const Rec* __restrict__ recs, const uint32_t* __restrict__ tile_first, uint64_t* __restrict__ tile_blocks,
                                                         uint64_t* __restrict__ nblocks, cenc::Extra* __restrict__ extras)
 {
-    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t t0 = tile_first[i], used = (recs[i].rows + kTile - 1u) / kTile;        // (rows <= packet_capacity: the stream has that many tiles)
-    uint64_t acc = 0;
-    for (uint32_t t = t0; t < t0 + used; t++) {
-        const uint64_t v = tile_blocks[t];
-        tile_blocks[t] = acc;
-        acc += v;
-    }
-    nblocks[i] = acc;
-    extras[i].blocks = extras[i].is_protected ? acc : 0u;
+    tiles_body(n, recs, tile_first, tile_blocks, nblocks, extras, [=](uint32_t i, uint64_t blocks) { return extras[i].is_protected ? blocks : 0u; });
 }
 
-__global__ __launch_bounds__(kCencThreads) void cenc_crypt_kernel(const Stream* __restrict__ streams, uint32_t n_streams, const Rec* __restrict__ recs,
+__global__ __launch_bounds__(kProtThreads) void cenc_crypt_kernel(const Stream* __restrict__ streams, uint32_t n_streams, const Rec* __restrict__ recs,
                                                                   const cenc::Extra* __restrict__ extras, const uint32_t* __restrict__ tile_first,
                                                                   const uint64_t* __restrict__ tile_blocks, const uint64_t* __restrict__ chunk_first, uint64_t n_chunks,
                                                                   const uint64_t* __restrict__ nblocks, const uint32_t* __restrict__ keys, const Row* __restrict__ src_rows,
@@ -128,45 +97,15 @@ __global__ __launch_bounds__(kCencThreads) void cenc_crypt_kernel(const Stream* 
     __shared__ uint32_t te0[256];
     te0[threadIdx.x] = kCencForward.te0[threadIdx.x];
     __syncthreads();
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / 64u), lane = threadIdx.x % 64u;
-    const uint64_t stride = (uint64_t)gridDim.x * kCencWaves;
-    for (uint64_t g = (uint64_t)blockIdx.x * kCencWaves + wave; g < n_chunks;) {
-        uint32_t lo = 0, hi = n_streams;                              // the stream the slot lies in: the last whose first slot is <= g
-        while (hi - lo > 1u) {
-            const uint32_t mid = lo + (hi - lo) / 2u;
-            if (chunk_first[mid] <= g) lo = mid; else hi = mid;
-        }
-        const uint32_t i = __builtin_amdgcn_readfirstlane(lo);
-        const uint64_t total = nblocks[i], b0 = (g - chunk_first[i]) * cenc::kLaneBlocks;
-        if (b0 >= total) {                                            // behind the stream's last block: on to the next stream's slots
-            g += (chunk_first[i + 1u] - g + stride - 1u) / stride * stride;
-            continue;
-        }
-        g += stride;
-        const uint64_t b = b0 + lane;
-        if (b >= total) continue;
-        const Stream& st = streams[i];
-        const uint32_t t0 = tile_first[i], used = (recs[i].rows + kTile - 1u) / kTile;
-        uint32_t ta = 0, tb = used;                                   // the tile: the last whose first block is <= b
-        while (tb - ta > 1u) {
-            const uint32_t mid = ta + (tb - ta) / 2u;
-            if (tile_blocks[t0 + mid] <= b) ta = mid; else tb = mid;
-        }
-        const uint64_t in_tile = b - tile_blocks[t0 + ta];
-        const uint32_t s0 = ta * kTile, s1 = s0 + kTile < recs[i].rows ? s0 + kTile : recs[i].rows;
-        const cenc::RowRec* const rr = rowrecs + st.packet_first;
-        uint32_t ra = s0, rb = s1;                                    // the row: the last of the tile whose first block is <= in_tile
-        while (rb - ra > 1u) {
-            const uint32_t mid = ra + (rb - ra) / 2u;
-            if (rr[mid].block_first <= in_tile) ra = mid; else rb = mid;
-        }
-        const uint32_t j = (uint32_t)(in_tile - rr[ra].block_first);
-        const Row from = src_rows[st.packet_first + ra], to = rows[st.packet_first + ra];
-        const bool prot = extras[i].is_protected != 0u;
-        cenc::Iv iv = {};
-        if (prot) iv = cenc::read_iv(src + st.src_offset, rr[ra].iv_pos, extras[i].iv_size);
-        cenc::crypt_lane(src + from.src_offset, dst + to.src_offset, from.bytes, j, prot ? keys + (size_t)i * cenc::kScheduleWords : nullptr, iv, te0);
-    }
+    const uint32_t* const table = te0;
+    unit_loop(streams, n_streams, recs, tile_first, tile_blocks, chunk_first, n_chunks, nblocks, [=](uint32_t r) { return rowrecs[r].block_first; },
+        [=](uint32_t i, const Stream& st, uint32_t r, uint32_t j) {
+            const Row from = src_rows[r], to = rows[r];
+            const bool prot = extras[i].is_protected != 0u;
+            cenc::Iv iv = {};
+            if (prot) iv = cenc::read_iv(src + st.src_offset, rowrecs[r].iv_pos, extras[i].iv_size);
+            cenc::crypt_lane(src + from.src_offset, dst + to.src_offset, from.bytes, j, prot ? keys + (size_t)i * cenc::kScheduleWords : nullptr, iv, table);
+        });
 }
 
 __global__ __launch_bounds__(64) void cenc_plain_kernel(const cenc::Stream* __restrict__ streams, uint32_t n, const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
@@ -205,49 +144,12 @@ int cenc_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const cenc::Stream* streams)
         plain[i] = streams[i].s;
         for (uint8_t& k : stripped[i].key) k = 0;
     }
-    OHGPU_TRY(mp4f_plan(ctx, g, plain.data(), "ohgpu_cenc_batch_create"));
-    if (!n) return OHGPU_OK;
-    g.tile_first.assign(n + 1, 0);
-    std::vector<uint64_t> chunk_first(n + 1, 0);
-    for (size_t i = 0; i < n; i++) {
-        const Stream& s = plain[i];
-        g.tile_first[i + 1] = g.tile_first[i] + (g.plain ? 0u : (uint32_t)(((uint64_t)s.packet_capacity + kTile - 1u) / kTile));
-        // sum of ceil(size / 16) over rows that fit the room: at most dst_capacity / 16 + packet_capacity
-        const uint64_t blocks = s.packet_capacity && s.dst_capacity ? s.dst_capacity / 16u + s.packet_capacity : 0u;
-        chunk_first[i + 1] = chunk_first[i] + (g.plain ? 0u : (blocks + cenc::kLaneBlocks - 1u) / cenc::kLaneBlocks);
-    }
-    g.n_chunks = chunk_first[n];
-    const uint64_t want = (g.n_chunks + kCencWaves - 1u) / kCencWaves, cap = (uint64_t)(ctx->num_cus > 0 ? ctx->num_cus : 256) * kCencGroupsPerCu;
-    g.crypt_blocks = (uint32_t)(want < cap ? want : cap);
-    g.keys_bytes = g.keys.size() * sizeof(uint32_t);
-    OHGPU_TRY(dev_array(ctx, g, &g.d_cstreams, n, stripped.data()));
-    OHGPU_TRY(dev_array(ctx, g, &g.d_keys, g.keys.size(), g.keys.data()));
-    OHGPU_TRY(dev_array<cenc::Extra>(ctx, g, &g.d_extras, n));
-    OHGPU_TRY(dev_array<Row>(ctx, g, &g.d_rows, g.n_packets));
-    OHGPU_TRY(dev_array<cenc::RowRec>(ctx, g, &g.d_rowrecs, g.n_packets));
-    OHGPU_TRY(dev_array(ctx, g, &g.d_tile_first, n + 1, g.tile_first.data()));
-    OHGPU_TRY(dev_array<uint64_t>(ctx, g, &g.d_tile_blocks, g.n_tiles));
-    OHGPU_TRY(dev_array(ctx, g, &g.d_chunk_first, n + 1, chunk_first.data()));
-    OHGPU_TRY(dev_array<uint64_t>(ctx, g, &g.d_nblocks, n));
-    return OHGPU_OK;
-}
-
-void cenc_free(ohgpu_ctx* ctx, ohgpu_batch* b)
-{
-    if (b->cenc) {
-        CencState& g = *b->cenc;
-        (void)hipDeviceSynchronize();
-        // the schedules do not outlive the batch: the device block is cleared before it goes back to the cache, the host copy too
-        if (g.d_keys) (void)hipMemset(g.d_keys, 0, g.keys_bytes);
-        for (uint32_t& w : g.keys) *(volatile uint32_t*)&w = 0;
-    }
-    state_free(ctx, b->cenc);
+    return protected_plan<cenc::RowRec>(ctx, g, plain, stripped, "ohgpu_cenc_batch_create", [](size_t) { return 0u; });
 }
 
 int cenc_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s)
 {
     CencState& g = *b->cenc;
-    OHGPU_TRY(run_begin(g, s));      // (the tables serve one run at a time)
     const uint32_t ns = (uint32_t)g.n_streams, lane_blocks = (ns + 63u) / 64u;
     const cenc::Stream* const cstreams = (const cenc::Stream*)g.d_cstreams;
     Result* const results = (Result*)g.d_results;
@@ -255,35 +157,28 @@ int cenc_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* 
     Rec* const recs = (Rec*)g.d_recs;
     RunRec* const runrecs = (RunRec*)g.d_runrecs;
     const uint32_t* const keys = (const uint32_t*)g.d_keys;
-    OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[0], s));
-    OHGPU_TRY(mp4f_fill(g, s));                                       // (no row of the run before stands in a table: csrc/mp4_frag_kernel.hip)
-    if (g.n_packets) OHGPU_HIP_TRY_ALLOC(hipMemsetAsync(g.d_rows, 0xa5, g.n_packets * sizeof(Row), s));
-    if (g.plain) {
-        hipLaunchKernelGGL(cenc_plain_kernel, dim3(lane_blocks), dim3(64), 0, s, cstreams, ns, src, dst, results, extras, recs, runrecs, (Run*)g.d_runs, (Row*)g.d_packets,
-                           (Row*)g.d_rows, (Sample*)g.d_samples, keys);
-        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-        for (int k = 1; k < 6; k++) OHGPU_HIP_TRY_ALLOC(hipEventRecord(g.ev[k], s));
-        return run_end(g, s);
-    }
-    hipLaunchKernelGGL(cenc_walk_kernel, dim3(lane_blocks), dim3(64), 0, s, cstreams, ns, src, results, extras, recs, runrecs);
-    OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-    OHGPU_TRY(mp4f_tables(g, src, s));
-    if (g.n_tiles) {
-        hipLaunchKernelGGL(cenc_rows_kernel, dim3(g.n_tiles), dim3(kCencThreads), 0, s, (const Stream*)g.d_streams, (const Rec*)recs, (const RunRec*)runrecs,
-                           (const Mp4fTile*)g.d_tiles, (const Result*)results, (const cenc::Extra*)extras, (const Row*)g.d_packets, (Row*)g.d_rows,
-                           (cenc::RowRec*)g.d_rowrecs, (uint64_t*)g.d_tile_blocks);
-        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-        hipLaunchKernelGGL(cenc_tiles_kernel, dim3(lane_blocks), dim3(64), 0, s, ns, (const Rec*)recs, (const uint32_t*)g.d_tile_first, (uint64_t*)g.d_tile_blocks,
-                           (uint64_t*)g.d_nblocks, extras);
-        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-    }
-    if (g.n_tiles && g.crypt_blocks) {
-        hipLaunchKernelGGL(cenc_crypt_kernel, dim3(g.crypt_blocks), dim3(kCencThreads), 0, s, (const Stream*)g.d_streams, ns, (const Rec*)recs, (const cenc::Extra*)extras,
-                           (const uint32_t*)g.d_tile_first, (const uint64_t*)g.d_tile_blocks, (const uint64_t*)g.d_chunk_first, g.n_chunks, (const uint64_t*)g.d_nblocks, keys,
-                           (const Row*)g.d_packets, (const Row*)g.d_rows, (const cenc::RowRec*)g.d_rowrecs, src, dst);
-        OHGPU_HIP_TRY_ALLOC(hipGetLastError());
-    }
-    return run_end(g, s);
+    return protected_run(g, src, s,
+        [&] {
+            hipLaunchKernelGGL(cenc_plain_kernel, dim3(lane_blocks), dim3(64), 0, s, cstreams, ns, src, dst, results, extras, recs, runrecs, (Run*)g.d_runs, (Row*)g.d_packets,
+                               (Row*)g.d_rows, (Sample*)g.d_samples, keys);
+        },
+        [&] { hipLaunchKernelGGL(cenc_walk_kernel, dim3(lane_blocks), dim3(64), 0, s, cstreams, ns, src, results, extras, recs, runrecs); },
+        [&]() -> int {
+            if (!g.n_tiles) return OHGPU_OK;
+            hipLaunchKernelGGL(cenc_rows_kernel, dim3(g.n_tiles), dim3(kProtThreads), 0, s, (const Stream*)g.d_streams, (const Rec*)recs, (const RunRec*)runrecs,
+                               (const Mp4fTile*)g.d_tiles, (const Result*)results, (const cenc::Extra*)extras, (const Row*)g.d_packets, (Row*)g.d_rows,
+                               (cenc::RowRec*)g.d_row_first, (uint64_t*)g.d_tile_units);
+            OHGPU_HIP_TRY_ALLOC(hipGetLastError());
+            hipLaunchKernelGGL(cenc_tiles_kernel, dim3(lane_blocks), dim3(64), 0, s, ns, (const Rec*)recs, (const uint32_t*)g.d_tile_first, (uint64_t*)g.d_tile_units,
+                               (uint64_t*)g.d_nunits, extras);
+            OHGPU_HIP_TRY_ALLOC(hipGetLastError());
+            if (!g.crypt_blocks) return OHGPU_OK;
+            hipLaunchKernelGGL(cenc_crypt_kernel, dim3(g.crypt_blocks), dim3(kProtThreads), 0, s, (const Stream*)g.d_streams, ns, (const Rec*)recs, (const cenc::Extra*)extras,
+                               (const uint32_t*)g.d_tile_first, (const uint64_t*)g.d_tile_units, (const uint64_t*)g.d_chunk_first, g.n_chunks, (const uint64_t*)g.d_nunits, keys,
+                               (const Row*)g.d_packets, (const Row*)g.d_rows, (const cenc::RowRec*)g.d_row_first, src, dst);
+            OHGPU_HIP_TRY_ALLOC(hipGetLastError());
+            return OHGPU_OK;
+        });
 }
 
 }  // namespace ohgpu

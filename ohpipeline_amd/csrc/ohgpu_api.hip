@@ -293,6 +293,7 @@ int batch_begin(ohgpu_ctx* ctx, const char* who, BatchKind kind, bool args_ok, s
 // family is one row here, one api_*.hip, and a state that derives from RunState: its plan names each device block once (dev_array),
 // its release is free_state of the batch's pointer to it (state_free, api_common.h: state_release and a delete).
 template <auto State> static void free_state(ohgpu_ctx* ctx, ohgpu_batch* b) { state_free(ctx, b->*State); }
+template <auto State> static void free_protected(ohgpu_ctx* ctx, ohgpu_batch* b) { protected_free(ctx, b->*State); }   // (clears the key schedules first)
 static void free_fmt(ohgpu_ctx* ctx, ohgpu_batch* b) { free_fmt_line(ctx, b); free_pcm_line(ctx, b); }
 static void free_pull(ohgpu_ctx* ctx, ohgpu_batch* b) { if (b->d_pull_tiles) ctx_dev_free(ctx, b->d_pull_tiles); }
 static const struct { const char* noun; void (*release)(ohgpu_ctx*, ohgpu_batch*); bool drain; } kKinds[] = {
@@ -314,12 +315,12 @@ static const struct { const char* noun; void (*release)(ohgpu_ctx*, ohgpu_batch*
     {"a PCM file", free_state<&ohgpu_batch::file>, false},   // kBatchIff
     {"a DSD file", free_state<&ohgpu_batch::file>, false},   // kBatchDsdFile
     {"a fragmented MPEG-4", free_state<&ohgpu_batch::mp4f>, false},   // kBatchMp4f
-    {"a protected MPEG-4", cenc_free, false},   // kBatchCenc
+    {"a protected MPEG-4", free_protected<&ohgpu_batch::cenc>, false},   // kBatchCenc
     {"a RAOP receiver", free_state<&ohgpu_batch::raoprx>, false},   // kBatchRaopRx
     {"a transport stream", free_state<&ohgpu_batch::ts>, false},   // kBatchTs
     {"an ADTS", free_state<&ohgpu_batch::adts>, false},   // kBatchAdts
     {"a Vorbis", free_state<&ohgpu_batch::vorbis>, false},   // kBatchVorbis
-    {"a cbcs-protected MPEG-4", cbcs_free, false},   // kBatchCbcs
+    {"a cbcs-protected MPEG-4", free_protected<&ohgpu_batch::cbcs>, false},   // kBatchCbcs
 };
 static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == kBatchCbcs + 1, "a row per BatchKind");
 

@@ -581,21 +581,21 @@ static_assert(sizeof(ohgpu_mp4f_stream_desc) == sizeof(mp4frag::Stream) && sizeo
 
 // ---- protected fragmented MPEG-4 (csrc/cenc_kernel.hip): an Mp4fState whose packet table is the expansion's own (places
 // in the source arena), and what stands behind it -- the descriptors without their keys, the expanded keys, what the protection boxes gave,
-// the public packet table (places in the destination arena), and the block prefixes of the decrypt-gather.
+// the public packet table (places in the destination arena), and the unit prefixes of the decrypt-gather (csrc/protected_shell.h: a UNIT is a keystream block, or the second family's work unit).
 struct CencState : Mp4fState {
-    std::vector<uint32_t> keys;                       // cenc::kScheduleWords words per stream (cleared in cenc_free)
+    std::vector<uint32_t> keys;                       // the family's schedule words per stream (cleared in protected_free)
     std::vector<uint32_t> tile_first;                 // per stream: its first tile; n_streams + 1 entries
     uint32_t crypt_blocks = 0;                        // the size of the persistent decrypt-gather launch
-    uint64_t n_chunks = 0;                            // its slots: chunks of cenc::kLaneBlocks keystream blocks, from the capacities
-    void* d_cstreams = nullptr;                       // cenc::Stream[n_streams], the keys zero
-    void* d_keys = nullptr; size_t keys_bytes = 0;    // uint32[n_streams * kScheduleWords]
+    uint64_t n_chunks = 0;                            // its slots: chunks of fragu::kLanes units, from the capacities
+    void* d_cstreams = nullptr;                       // cenc::Stream[n_streams] (cbcs::Stream in the second family), the keys zero
+    void* d_keys = nullptr; size_t keys_bytes = 0;    // uint32[n_streams * the family's schedule words]
     void* d_extras = nullptr;                         // cenc::Extra[n_streams]
     void* d_rows = nullptr;                           // mp4box::Row[n_packets]: the public packet table
-    void* d_rowrecs = nullptr;                        // cenc::RowRec[n_packets]
+    void* d_row_first = nullptr;                      // [n_packets]: a row's units in front of it in its tile -- cenc::RowRec (with the IV's place), uint64 in the second family
     void* d_tile_first = nullptr;                     // uint32[n_streams + 1]
-    void* d_tile_blocks = nullptr;                    // uint64[n_tiles]: a tile's keystream blocks, then (the tile scan) those in front of it
+    void* d_tile_units = nullptr;                     // uint64[n_tiles]: a tile's units, then (the tile scan) those in front of it
     void* d_chunk_first = nullptr;                    // uint64[n_streams + 1]: the stream's first chunk slot
-    void* d_nblocks = nullptr;                        // uint64[n_streams]: the stream's keystream blocks
+    void* d_nunits = nullptr;                         // uint64[n_streams]: the stream's units
 };
 static_assert(sizeof(ohgpu_cenc_stream_desc) == 112 && sizeof(ohgpu_cenc_stream_result) == 208 && sizeof(ohgpu_cenc_stream_desc) == sizeof(cenc::Stream) &&
               sizeof(ohgpu_cenc_stream_result) == sizeof(cenc::Result) && offsetof(ohgpu_cenc_stream_desc, key_flags) == offsetof(cenc::Stream, key_flags) &&
@@ -605,13 +605,9 @@ static_assert(sizeof(ohgpu_cenc_stream_desc) == 112 && sizeof(ohgpu_cenc_stream_
               cenc::kHaveKey == OHGPU_CENC_HAVE_KEY && mp4box::kMaxBoxes == OHGPU_MP4_MAX_BOXES, "protected MPEG-4 layouts");
 
 // ---- protected fragmented MPEG-4, the second family (csrc/cbcs_kernel.hip): a CencState (d_cstreams holds cbcs::Stream,
-// the schedules are cbcs::kKeyWords words a stream) with arrays of its own for the work units -- the sibling's d_rowrecs, d_tile_blocks and
-// d_nblocks stay null -- and what the subsample entries need.
+// the schedules are cbcs::kKeyWords words a stream, the units are work units) and what the subsample entries need.
 struct CbcsState : CencState {
     size_t n_subsamples = 0;
-    void* d_unit_first = nullptr;                     // uint64[n_packets]: a row's work units in front of it in its tile
-    void* d_tile_units = nullptr;                     // uint64[n_tiles]: a tile's work units, then (the tile scan) those in front of it
-    void* d_nunits = nullptr;                         // uint64[n_streams]: the stream's work units
     void* d_more = nullptr;                           // cbcs::More[n_streams]
     void* d_subs = nullptr;                           // cbcs::SubRow[n_subsamples]
     void* d_samprecs = nullptr;                       // cbcs::SampleRec[n_packets]
@@ -914,16 +910,13 @@ int  mp4f_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t*
 int  mp4f_fill(const Mp4fState& g, hipStream_t s);   // the head of a run of the three families: the run, packet and sample tables back to their fill, on the run's stream
 int  mp4f_tables(const Mp4fState& g, const uint8_t* src, hipStream_t s);   // behind a walk: ev[1], run sums, ev[2], carries, ev[3], expand, ev[4], finish, ev[5]
 uint32_t mp4f_wave_blocks(uint64_t slots, uint32_t cus);   // the persistent launches' size: the rule tests/test_gpu_mp4f_textbook.py restates
-// csrc/cenc_kernel.hip.  The walk under cenc::Protection, mp4f_tables, then the decrypt-gather: a workgroup a tile (the rows and their
-// block prefixes), a lane a stream (the tiles' prefixes), and the persistent launch (a wave per chunk of 64 keystream blocks of a stream).
+// csrc/cenc_kernel.hip and csrc/cbcs_kernel.hip, over csrc/protected_shell.h.  The walk under the family's Protection (cbcs: with the
+// subsample chain), mp4f_tables, then the decrypt-gather: a workgroup a tile (the rows and their unit prefixes), a lane a stream (the
+// tiles' prefixes), and the persistent launch (a wave per chunk of 64 units of a stream: keystream blocks, or cbcs's work units).
 int  cenc_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const cenc::Stream* streams);
 int  cenc_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
-void cenc_free(ohgpu_ctx* ctx, ohgpu_batch* b);                       // clears the schedules, on the device and here, then state_free
-// csrc/cbcs_kernel.hip.  The sibling's launches over work units: the walk under cbcs::Protection (with the subsample chain), mp4f_tables,
-// the rows and their unit prefixes, the tiles' prefixes, and the persistent launch (a wave per chunk of 64 work units of a stream).
 int  cbcs_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const cbcs::Stream* streams);
 int  cbcs_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);
-void cbcs_free(ohgpu_ctx* ctx, ohgpu_batch* b);                       // clears the schedules, on the device and here, then state_free
 // csrc/iff_pcm_kernel.hip.  No launch is persistent: a lane a stream (walk), a workgroup per kIffGroupPieces pieces of a run (convert).
 int  iff_plan(ohgpu_ctx* ctx, ohgpu_batch* b, const iffchunk::Stream* streams);   // the descriptors and the workgroup list onto the device
 int  iff_run(ohgpu_ctx* ctx, const ohgpu_batch* b, const uint8_t* src, uint8_t* dst, hipStream_t s);

@@ -8,7 +8,7 @@ import cbcs_cases as BC
 import cbcs_textbook as BX
 import cenc_cases as CC
 
-TILE, SLOT_UNITS, CRYPT_WAVES, CRYPT_GROUPS_PER_CU = 1024, 64, 4, 8      # kTile, cbcs::kLaneUnits, kCbcsWaves, kCbcsGroupsPerCu
+TILE, SLOT_UNITS, CRYPT_WAVES, CRYPT_GROUPS_PER_CU = 1024, 64, 4, 8      # kTile, cbcs::kLaneUnits, kProtWaves, kProtGroupsPerCu (csrc/protected_shell.h)
 TRIPS = 5
 
 

@@ -561,7 +561,7 @@ def assert_reaches(name, job):
 
 # ---- more chunk slots than the persistent decrypt-gather launch has waves (cenc_crypt_kernel's loop over `g`)
 SLOT_BLOCKS = 64            # cenc::kLaneBlocks: the keystream blocks of a chunk slot, a lane each
-CRYPT_WAVES, CRYPT_GROUPS_PER_CU = 4, 8          # kCencWaves, kCencGroupsPerCu: the launch's cap today
+CRYPT_WAVES, CRYPT_GROUPS_PER_CU = 4, 8          # kProtWaves, kProtGroupsPerCu (csrc/protected_shell.h): the launch's cap today
 TRIP_SEED = 20264
 TRIPS = 5                   # the builder's target: 5 W + 67 slots (the condition is 3 W + 67; see trip_claims on why more)
 
