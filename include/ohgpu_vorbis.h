@@ -17,7 +17,11 @@
  *     stream by sending the last packet of the previous call again: the batch keeps nothing between runs.
  * V4  Only the first max_samples samples a channel of a stream are written; the packet records count what was written.
  * V5  sample = clamp(floor(x * 32768 + 0.5), -32768, 32767), written as interleaved big-endian 16-bit frames at dst_offset, or with
- *     OHGPU_VORBIS_OUT_PLANAR32 as 32-bit words, channel c at dst_offset + c * dst_plane_stride (what OHGPU_FLAG_SRC_PLANAR32 reads). */
+ *     OHGPU_VORBIS_OUT_PLANAR32 as 32-bit words, channel c at dst_offset + c * dst_plane_stride (what OHGPU_FLAG_SRC_PLANAR32 reads).
+ * V6  A setup whose codebooks hold a value vector entry that is not finite is OHGPU_ERR_INVALID, and a sample that is not a number is
+ *     stored as 0.  (The packed floats reach 2^256, so a header valid by its syntax can say infinity, and finite but huge entries can
+ *     still sum past float32 in the residue, the coupling or the transform: infinities clamp by V5, inf - inf is not a number.  No
+ *     float reaches an integer conversion unclamped.) */
 #ifndef OHGPU_VORBIS_H
 #define OHGPU_VORBIS_H
 
@@ -74,7 +78,7 @@ typedef struct ohgpu_vorbis_stream_result { /* 24 bytes */
 
 /* Host only, no device needed.  Reads the identification header packet and the setup header packet and writes the setup image: with
  * image == NULL or image_capacity too small only info is filled (info->image_bytes says how much room it takes) and, for a too small
- * capacity, OHGPU_ERR_BOUNDS is returned.  OHGPU_ERR_INVALID: a malformed header, an over-specified codebook tree, an index out of range.
+ * capacity, OHGPU_ERR_BOUNDS is returned.  OHGPU_ERR_INVALID: a malformed header, an over-specified codebook tree, an index out of range, a value that is not finite (V6).
  * OHGPU_ERR_UNSUPPORTED: floor type 0, more than 8 channels, more than OHGPU_VORBIS_MAX_COUPLING_STEPS coupling steps, an image or a
  * classification area beyond the caps above. */
 int ohgpu_vorbis_setup_parse(const void* id_packet, size_t id_bytes, const void* setup_packet, size_t setup_bytes,

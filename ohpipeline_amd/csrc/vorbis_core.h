@@ -1,4 +1,4 @@
-// vorbis_core.h -- Vorbis I, written from the specification's behaviour (the rules V1-V5 are include/ohgpu_vorbis.h's).
+// vorbis_core.h -- Vorbis I, written from the specification's behaviour (the rules V1-V6 are include/ohgpu_vorbis.h's).
 // The setup parse is host text; everything a packet needs is __host__ __device__: csrc/vorbis_kernel.hip runs it on the device,
 // tests/cpp/vorbis_core_driver.cpp runs the same text on the CPU under the sanitizers.
 //
@@ -404,10 +404,11 @@ VB_HD float overlap_at(const float* prev, uint32_t pn, const float* cur, uint32_
     return a + b;
 }
 
-// V5
+// V5, and V6: what is not a number is stored as 0 -- no float reaches the conversion unclamped
 VB_HD int32_t to_pcm16(float x)
 {
     const float v = floorf(x * 32768.0f + 0.5f);
+    if (v != v) return 0;
     return v < -32768.0f ? -32768 : v > 32767.0f ? 32767 : (int32_t)v;
 }
 
@@ -558,6 +559,7 @@ inline int parse_setup(const uint8_t* id, size_t id_bytes, const uint8_t* setup,
                     volatile float prod = (float)mult[(size_t)off] * delta;      // one float32 operation at a time
                     volatile float sum = prod + vmin;
                     const float v = sum + last;
+                    if (!std::isfinite(v)) VB_FAIL(kParseInvalid, "codebook value vector entry not finite");   // V6
                     if (seq) last = v;
                     uint32_t raw; memcpy(&raw, &v, 4);
                     w.push_back(raw);

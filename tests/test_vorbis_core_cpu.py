@@ -1,7 +1,9 @@
 """The Vorbis decoder without a device: the codeword assignment on the specification's own example, the setup parse's return codes, the ABI's
 sizes, the batch check's codes, csrc/vorbis_core.h stand-alone under ASan and UBSan against the model (records and spectrum exact, PCM
-within 1 LSB through the core's serial synthesis), the
+within 1 LSB through the core's serial synthesis) -- whole streams, the fixed-seed packet damage set, the setup header damage set and
+V6's huge finite values, the sets in one process each --, the
 model against the minimal encoder, and the premise of the GPU tests' 1 LSB: a float32 FFT transform of a full-scale block of 8192."""
+import collections
 import os
 import struct
 import subprocess
@@ -125,20 +127,46 @@ def driver(tmp_path_factory):
     return out
 
 
-def _case_files(tmp_path, st, packets, max_samples):
-    recs, spectra, pcm = TB.decode_stream(st.model, packets, max_samples)
+def _case_bytes(st, packets, model=None):
+    """(case, expect, pcm) as tests/cpp/vorbis_core_driver.cpp reads them; model: (records, spectra, pcm), None for headers the model refuses"""
     case = struct.pack("<I", len(st.ident)) + st.ident + struct.pack("<I", len(st.setup)) + st.setup + struct.pack("<I", len(packets))
     for p in packets:
         case += struct.pack("<I", len(p)) + p
+    if model is None:
+        return case, b"", b""
+    recs, spectra, pcm = model
     want = b""
     for (status, mode, block, samples, position), rows in zip(recs, spectra):
         want += struct.pack("<IIIIQ", status, mode, block, samples, position)
         if rows is not None:
             want += rows.astype("<f4").tobytes()
+    return case, want, pcm.T.astype("<i4").tobytes()
+
+
+def _case_files(tmp_path, st, packets, max_samples):
+    case, want, pcm = _case_bytes(st, packets, TB.decode_stream(st.model, packets, max_samples))
     (tmp_path / "case").write_bytes(case)
     (tmp_path / "expect").write_bytes(want)
-    (tmp_path / "pcm").write_bytes(pcm.T.astype("<i4").tobytes())
+    (tmp_path / "pcm").write_bytes(pcm)
     return str(tmp_path / "case"), str(tmp_path / "expect"), str(tmp_path / "pcm")
+
+
+PCM_MODEL, PCM_V6 = 1, 2
+
+
+def _run_many(driver, path, entries):
+    """The driver's --many mode over entries of (label, (case, expect, pcm), refused by the model, PCM_MODEL or PCM_V6), all with no
+    bound on the samples: the finished process, and {label: the core's parse code} of the cases whose headers it refused."""
+    with open(path, "wb") as f:
+        f.write(struct.pack("<I", len(entries)))
+        for label, (case, want, pcm), refused, pcm_mode in entries:
+            name = label.encode()
+            f.write(struct.pack("<I", len(name)) + name + struct.pack("<IIQ", int(refused), pcm_mode, 1 << 40))
+            for blob in (case, want, pcm):
+                f.write(struct.pack("<I", len(blob)) + blob)
+    r = subprocess.run([str(driver), "--many", str(path)], capture_output=True, text=True)
+    codes = {line.split()[1]: int(line.split()[2]) for line in r.stdout.splitlines() if line.startswith("PARSE ")}
+    return r, codes
 
 
 @pytest.mark.parametrize("name", sorted(VC.SHAPES))
@@ -158,6 +186,111 @@ def test_core_under_the_sanitizers_takes_damage(driver, tmp_path):
     assert r.returncode == 0 and r.stdout.startswith("OK"), r.stderr[-2000:]
     recs = TB.decode_stream(VC.stream(name).model, packets)[0]
     assert [recs[k][0] for k in (4, 7, 9)] == [TB.CORRUPT, TB.CORRUPT, TB.HEADER] and recs[2][0] == TB.OK
+
+
+def test_core_under_the_sanitizers_takes_every_mutation(driver, tmp_path):
+    """All 2 306 cases of tests/vorbis_cases.device_mutations -- a cut at every byte, the first 48 bits and 40 seeded ones flipped, a
+    splice, per mutated packet -- through the core's serial text in one process: records and spectrum exact, PCM within 1 LSB, the
+    sanitizers silent.  This is what lets the set onto the device (tests/test_gpu_vorbis_damage.py).  What the set is there for is
+    asserted from the model alone first."""
+    reach = VC.assert_mutations_reach()
+    cases, (models, seconds) = VC.device_mutations(), VC.mutation_models()
+    print("Vorbis damage set: %d cases, the model took %.1f s; %s" % (len(cases), seconds, dict(reach)))
+    entries = [(c.label, _case_bytes(VC.stream(c.shape), c.packets, m), False, PCM_MODEL) for c, m in zip(cases, models)]
+    r, codes = _run_many(driver, tmp_path / "mutations", entries)
+    assert r.returncode == 0 and r.stdout.strip().endswith("OK %d" % VC.N_MUTATIONS) and not codes, r.stderr[-4000:]
+
+
+UNSUPPORTED_BY_DESIGN = ("unsupported floor 0", "unsupported: more than 32 coupling steps", "unsupported: value vectors beyond the image's cap")
+
+
+def test_core_under_the_sanitizers_takes_setup_header_damage(driver, tmp_path):
+    """tests/vorbis_cases.setup_mutations -- every cut of a setup packet, 400 seeded flips of it, the hand-made configurations -- through
+    vorbiscore::parse_setup under the sanitizers, held to the model's parse: both accept or both refuse (ValueError is the model's
+    refusal; any other exception of the model's is the model's bug and fails here).  Accepted by both: the image passes
+    vorbiscore::image_valid, the intact stream's first five packets decode with records and spectrum exact, and the PCM within 1 LSB
+    where the model's spectra stay in V6's domain (finite, max|X| * N < 2^100; outside it the stored samples are held to V6 alone).
+    Refused by both: the core's code is INVALID, UNSUPPORTED only for what DESIGN.md 5.23 lists under that name."""
+    cases = VC.setup_mutations()
+    kinds = collections.Counter(c.label.split(":")[0] for c in cases)
+    assert kinds["cut"] == len(VC.setup_stream().setup) and 300 < kinds["flip"] <= VC.SETUP_FLIPS and kinds["made"] == len(VC.handmade_setups()) + 1 == 17, kinds
+    expected_made = {"made:" + name: accepted for name, _, accepted in VC.handmade_setups()}
+    expected_made["made:mode_past_count"] = True
+    entries, refusals = [], {}
+    for c in cases:
+        try:
+            model = TB.parse_headers(c.ident, c.setup)
+        except ValueError as e:
+            refusals[c.label] = str(e)
+            entries.append((c.label, _case_bytes(c, c.packets), True, PCM_MODEL))
+            continue
+        want = TB.decode_stream(model, c.packets)
+        entries.append((c.label, _case_bytes(c, c.packets, want), False, PCM_MODEL if VC.in_v6_domain(want[1]) else PCM_V6))
+    for label, accepted in expected_made.items():
+        assert (label not in refusals) == accepted, (label, refusals.get(label))
+    accepted = len(cases) - len(refusals)
+    print("Vorbis setup damage: %d cases (%s), the model accepts %d; outside V6's domain %d" % (len(cases), dict(kinds), accepted, sum(1 for e in entries if e[3] == PCM_V6)))
+    assert accepted > 100 and len(refusals) > 100                     # (the set reaches both answers many times over)
+    r, codes = _run_many(driver, tmp_path / "setups", entries)
+    assert r.returncode == 0 and r.stdout.strip().endswith("OK %d" % len(cases)), r.stderr[-4000:]
+    assert set(codes) == set(refusals)
+    for label, code in codes.items():
+        assert code == (capi.ERR_UNSUPPORTED if refusals[label] in UNSUPPORTED_BY_DESIGN else capi.ERR_INVALID), (label, code, refusals[label])
+
+
+def _headers_code(ident, setup):
+    """(the library's answer to the headers: 0 or its error code, the model's refusal or None)"""
+    try:
+        TB.parse_headers(ident, setup)
+        refusal = None
+    except ValueError as e:
+        refusal = str(e)
+    try:
+        capi.vorbis_setup_parse(ident, setup)
+        return 0, refusal
+    except capi.OhGpuError as e:
+        return e.code, refusal
+
+
+def test_setup_parse_refuses_values_that_are_not_finite():
+    """V6's first half, in three shapes.  The exponent field of min and delta at its top (2^235: every entry infinite): INVALID.  Every
+    entry finite and above 2^100: accepted.  A book of sequence_p whose entries are finite each and whose running sum is not: INVALID,
+    and accepted without sequence_p."""
+    cfg = VC.v6_cfg()
+    assert _headers_code(*VF.write_headers(cfg, 1023 - 788)) == (capi.ERR_INVALID, "invalid: a value vector entry is not finite (V6)")
+    st = VC.v6_stream()
+    assert _headers_code(st.ident, st.setup) == (0, None)
+    values = np.concatenate([np.abs(b.values).ravel() for b in st.model.books if b.values is not None])
+    assert np.isfinite(values).all() and values.max() >= 2.0 ** 127 and 2 * (values > 2.0 ** 100).sum() > values.size
+    for seq, want in ((1, (capi.ERR_INVALID, "invalid: a value vector entry is not finite (V6)")), (0, (0, None))):
+        cfg = VC.v6_cfg()
+        for b in cfg["books"]:
+            if b["lookup"]:                                           # every entry (1 * 1 - 1) * 2^123 = 0 ...
+                b.update(min_mant=1, delta_mant=1, vbits=4, seq=0, mult=[1] * len(b["mult"]))
+        b = cfg["books"][8]                                          # ... but this book's: 64 entries of dimension 8, each (15 * 2 - 1) * 2^123
+        assert b["dim"] == 8 and b["lookup"] == 1                    # = 2^127.86, finite; the second running sum is not
+        b.update(delta_mant=2, seq=seq, mult=[15] * len(b["mult"]))
+        assert _headers_code(*VF.write_headers(cfg, 123)) == want, seq
+
+
+def test_core_under_the_sanitizers_on_huge_finite_values(driver, tmp_path):
+    """V6's second half on the CPU.  tests/vorbis_cases.v6_stream: value vectors finite and up to 2^127, so that the residue's float32
+    sums reach infinity and the coupling inf - inf.  Records exact, spectrum bit-identical (two NaNs count as equal), and every stored
+    sample by V6: 0 where the overlap's sum is not a number, clamped where it is beyond 16 bits.
+
+    THE 1 LSB DOMAIN.  The model's PCM is the judge only where its spectrum satisfies max|X| * N < 2^100 (N = block / 2 values, all
+    finite): there a float32 transform cannot overflow (N terms of at most max|X|, far below 2^128) and its error is the relative one
+    the 1 LSB bound is derived from.  Outside it -- this stream -- the float32 transforms may overflow where the model's float64 direct
+    form does not; no route is wrong by a written rule, and only the properties above hold.  Every other stream of the tests lies
+    inside the domain, which is asserted here."""
+    for name in VC.SHAPES:
+        assert VC.in_v6_domain(VC.expected(name)[1]), name
+    st = VC.v6_stream()
+    want = VC.v6_expected()
+    assert not VC.in_v6_domain(want[1])
+    assert any(np.isnan(rows).any() for rows in want[1] if rows is not None) and any(np.isinf(rows).any() for rows in want[1] if rows is not None)
+    r, codes = _run_many(driver, tmp_path / "v6", [("v6", _case_bytes(st, st.packets, want), False, PCM_V6)])
+    assert r.returncode == 0 and r.stdout.strip().endswith("OK 1") and not codes, r.stderr[-4000:]
 
 
 def test_every_shape_covers_what_it_is_there_for():

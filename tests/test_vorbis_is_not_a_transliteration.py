@@ -17,7 +17,8 @@ pytestmark = pytest.mark.skipif(not os.path.isfile(os.path.join(REF, "OpenHome",
 
 MINE = ["include/ohgpu_vorbis.h", "ohpipeline_amd/csrc/vorbis_core.h", "ohpipeline_amd/csrc/vorbis_kernel.hip", "ohpipeline_amd/csrc/api_vorbis.hip",
         "tests/cpp/vorbis_core_driver.cpp", "tests/vorbis_textbook.py", "tests/vorbis_frames.py", "tests/vorbis_cases.py", "tests/test_vorbis_core_cpu.py",
-        "tests/test_gpu_vorbis_textbook.py", "tests/test_gpu_vorbis_far_offsets.py", "tests/test_vorbis_tremor.py", "tests/test_gpu_vorbis_ogg.py", "tests/test_vorbis_host_cpp.py", "tests/cpp/test_vorbis_decoder.cpp", "ohpipeline_amd/host/VorbisDecoder.h", "ohpipeline_amd/host/VorbisDecoder.cpp", "tests/test_vorbis_fixtures.py", "tests/golden/make_vorbis_fixtures.py", "tests/cpp/vorbis_tremor_driver.c", "tools/bench_vorbis.py", "tools/vorbis_host_cpu.cpp"]
+        "tests/test_gpu_vorbis_textbook.py", "tests/test_gpu_vorbis_far_offsets.py", "tests/test_vorbis_tremor.py", "tests/test_gpu_vorbis_ogg.py", "tests/test_vorbis_host_cpp.py", "tests/cpp/test_vorbis_decoder.cpp", "ohpipeline_amd/host/VorbisDecoder.h", "ohpipeline_amd/host/VorbisDecoder.cpp", "tests/test_vorbis_fixtures.py", "tests/golden/make_vorbis_fixtures.py", "tests/cpp/vorbis_tremor_driver.c", "tools/bench_vorbis.py", "tools/vorbis_host_cpu.cpp",
+        "tests/vorbis_device.py", "tests/test_gpu_vorbis_damage.py"]
 NAME = re.compile(r"vorbis", re.I)
 
 

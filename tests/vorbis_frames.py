@@ -136,7 +136,9 @@ def random_setup(rng, channels, e0, e1, coupling=0, submaps=1, one_entry=1, stri
 
 
 def write_headers(cfg, exponent):
-    """(identification packet, setup packet) of a configuration; the value books' floats are their mantissas times 2^exponent."""
+    """(identification packet, setup packet) of a configuration; the value books' floats are their mantissas times 2^exponent.
+    What a test overrides to write a header the random setups never are: cfg["floor_type"], cfg["framing"] (the last bit), and a book's
+    "overrun" (an ordered book whose first count is one more than its entries)."""
     w = Writer()
     for c in b"\x01vorbis":
         w.write(c, 8)
@@ -155,7 +157,7 @@ def write_headers(cfg, exponent):
             w.write(l[0] - 1, 5)
             cur, n = 0, l[0]
             while cur < len(l):
-                number = sum(1 for v in l if v == n)
+                number = len(l) + 1 if b.get("overrun") else sum(1 for v in l if v == n)
                 w.write(number, TB.ilog(len(l) - cur))
                 cur, n = cur + number, n + 1
         else:
@@ -217,7 +219,7 @@ def write_headers(cfg, exponent):
     w.write(len(cfg["modes"]) - 1, 6)
     for flag, mapping in cfg["modes"]:
         w.write(flag, 1), w.write(0, 16), w.write(0, 16), w.write(mapping, 8)
-    w.write(1, 1)
+    w.write(cfg.get("framing", 1), 1)
     return ident, w.bytes()
 
 
@@ -228,7 +230,8 @@ class Stream:
         self.model = TB.parse_headers(ident, setup)
 
 
-def random_stream(seed, channels, e0, e1, n_packets, coupling=0, submaps=1, peak=0.45, floor_cap=1.0, one_entry=1, strict=False):
+def random_stream(seed, channels, e0, e1, n_packets, coupling=0, submaps=1, peak=0.45, floor_cap=1.0, one_entry=1, strict=False, exponent=None):
+    """exponent: the value books' common exponent as it is, in place of the one that brings the PCM's peak to `peak`."""
     rng = np.random.default_rng(seed)
     cfg = random_setup(rng, channels, e0, e1, coupling, submaps, one_entry, strict)
     ident, setup = write_headers(cfg, -12)
@@ -246,6 +249,8 @@ def random_stream(seed, channels, e0, e1, n_packets, coupling=0, submaps=1, peak
         assert status == TB.OK and got_mode == mode
         TB.packet_spectrum(model, c, mode, n)
         packets.append(c.w.bytes())
+    if exponent is not None:
+        return Stream(*write_headers(cfg, exponent), packets)
     _, _, x = TB.decode_stream(model, packets, want_float=True)
     top = float(np.abs(x).max())
     shift = int(np.round(np.log2(peak / top))) if top > 0 else 0
@@ -308,19 +313,24 @@ def TB_pack(mant, exp, neg=False):
 
 
 # ---------------------------------------------------------------- the arenas of a batch
-def batch_tables(capi, streams, planar=False, max_samples=None, ranges=None):
+def batch_tables(capi, streams, planar=False, max_samples=None, ranges=None, pad=0, fill=0, share_images=False):
     """The images' blob, descriptors, packet table, source arena and destination size for streams laid one after the other; ranges[i] =
-    (first, count) takes a part of stream i's packets."""
-    images, descs, rows, src = [], np.zeros(len(streams), dtype=capi.VORBIS_STREAM_DESC), [], bytearray()
+    (first, count) takes a part of stream i's packets.  share_images: streams of the same headers name one image.  The packets lie back to back, a
+    packet's last byte followed at once by the next one's first, behind `pad` bytes of `fill`, which also ends the arena."""
+    images, descs, rows, src = {}, np.zeros(len(streams), dtype=capi.VORBIS_STREAM_DESC), [], bytearray([fill] * pad)
     infos = []
-    dst = 0
+    dst = blob_bytes = 0
     for i, st in enumerate(streams):
-        image, info = capi.vorbis_setup_parse(st.ident, st.setup)
+        key = (st.ident, st.setup) if share_images else i
+        if key not in images:
+            image, info = capi.vorbis_setup_parse(st.ident, st.setup)
+            images[key] = (blob_bytes, image, info)
+            blob_bytes += image.size
+        at, image, info = images[key]
         infos.append(info)
         first, count = ranges[i] if ranges else (0, len(st.packets))
         d = descs[i]
-        d["image_offset"], d["image_bytes"] = sum(im.size for im in images), image.size
-        images.append(image)
+        d["image_offset"], d["image_bytes"] = at, image.size
         d["first_packet"], d["n_packets"] = len(rows), count
         for p in st.packets[first:first + count]:
             rows.append((len(src), len(p), 0))
@@ -334,8 +344,8 @@ def batch_tables(capi, streams, planar=False, max_samples=None, ranges=None):
         else:
             dst += (cap * 2 * ch + 3) & ~3
     packets = np.array(rows, dtype=capi.ALAC_PACKET) if rows else np.zeros(0, dtype=capi.ALAC_PACKET)
-    blob = np.concatenate(images) if images else np.zeros(0, dtype=np.uint8)
-    return blob, descs, packets, np.frombuffer(bytes(src) + b"\0" * 4, dtype=np.uint8).copy(), max(dst, 4), infos
+    blob = np.concatenate([im for _, im, _ in images.values()]) if images else np.zeros(0, dtype=np.uint8)
+    return blob, descs, packets, np.frombuffer(bytes(src) + bytes([fill] * 4), dtype=np.uint8).copy(), max(dst, 4), infos
 
 
 # ---------------------------------------------------------------- Ogg around a stream

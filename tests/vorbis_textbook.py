@@ -1,7 +1,7 @@
-"""An independent model of the Vorbis I decoder (include/ohgpu_vorbis.h: V1-V5), in numpy, written from the specification: the header
+"""An independent model of the Vorbis I decoder (include/ohgpu_vorbis.h: V1-V6), in numpy, written from the specification: the header
 packets parsed here, codewords assigned here, floor 1, residues 0 / 1 / 2, coupling -- in float32 where the product is, one operation at a
 time, up to the spectrum -- and from there on float64: a direct-form DCT-IV unfolded into the IMDCT, the window from its closed form,
-overlap-add, and V5's rounding.  Nothing of the product's text is used.
+overlap-add, and V5's rounding with V6's rule for what is not a number.  Nothing of the product's text is used.
 
 The bit source is an object with read(n), choose(book) and eop: Bits reads a packet; tests/vorbis_frames.py passes one that invents the
 bits instead, which is how the random-valid streams are written."""
@@ -59,6 +59,8 @@ def assign_codewords(lengths):
     for e, n in enumerate(lengths):
         if n == 0:
             continue
+        if n > 32:
+            raise ValueError("codeword length beyond 32")
         if first:
             first = False
             out[e] = 0
@@ -80,7 +82,8 @@ def assign_codewords(lengths):
 
 def float32_unpack(x):
     mant, e = x & 0x1fffff, (x >> 21) & 0x3ff
-    return F32(math.ldexp(-mant if x & 0x80000000 else mant, e - 788))
+    with np.errstate(over="ignore"):                                 # (the packed float reaches 2^256: V6 refuses what is not finite)
+        return F32(math.ldexp(-mant if x & 0x80000000 else mant, e - 788))
 
 
 def lookup1_values(entries, dim):
@@ -98,8 +101,13 @@ class Setup:
     pass
 
 
-def parse_headers(id_packet, setup_packet):
-    """The identification and setup header packets -> Setup; ValueError("invalid ...") / ValueError("unsupported ...")."""
+class TooLarge(Exception):
+    """parse_headers met a codebook of more entries than its caller wants to wait for."""
+
+
+def parse_headers(id_packet, setup_packet, max_entries=None):
+    """The identification and setup header packets -> Setup; ValueError("invalid ...") / ValueError("unsupported ...").  max_entries:
+    TooLarge as soon as a codebook declares more (a damaged header can declare 2^24, and this is plain Python)."""
     b = Bits(id_packet)
 
     def magic(t):
@@ -123,6 +131,8 @@ def parse_headers(id_packet, setup_packet):
         if b.read(24) != 0x564342:
             raise ValueError("invalid codebook sync")
         k.dim, k.entries = b.read(16), b.read(24)
+        if max_entries is not None and k.entries > max_entries:
+            raise TooLarge(k.entries)
         lengths = [0] * k.entries
         if not b.read(1):
             sparse = b.read(1)
@@ -153,18 +163,30 @@ def parse_headers(id_packet, setup_packet):
         if k.lookup:
             vmin, delta = float32_unpack(b.read(32)), float32_unpack(b.read(32))
             vbits, seq = b.read(4) + 1, b.read(1)
+            if k.dim == 0:
+                raise ValueError("invalid: value vectors of dimension 0")
+            if k.entries * k.dim * 4 > 16 << 20:
+                raise ValueError("unsupported: value vectors beyond the image's cap")
             nmult = lookup1_values(k.entries, k.dim) if k.lookup == 1 else k.entries * k.dim
-            mult = [b.read(vbits) for _ in range(nmult)]
+            if nmult * vbits > 8 * len(setup_packet):
+                raise ValueError("invalid: header ends")
+            mult = np.array([b.read(vbits) for _ in range(nmult)], dtype=F32)
+            if b.eop:
+                raise ValueError("invalid: header ends")
+            # every entry's vector, one float32 operation at a time: (mult * delta + min) + last, a column of all entries per step
             k.values = np.zeros((k.entries, k.dim), dtype=F32)
-            for e in range(k.entries):
-                last, div = F32(0), 1
+            e = np.arange(k.entries, dtype=np.int64)
+            last, div = np.zeros(k.entries, dtype=F32), 1
+            with np.errstate(over="ignore", invalid="ignore"):
                 for d in range(k.dim):
                     off = (e // div) % nmult if k.lookup == 1 else e * k.dim + d
-                    v = F32(F32(F32(mult[off]) * delta) + vmin) + last
+                    v = (mult[off] * delta + vmin) + last          # (float32 arrays and scalars: each operation rounds to float32)
                     if seq:
                         last = v
-                    k.values[e, d] = v
-                    div *= nmult if k.lookup == 1 else 1
+                    k.values[:, d] = v
+                    div = div * nmult if k.lookup == 1 else 1        # (nmult ^ dim <= entries: it stays small)
+            if not np.isfinite(k.values).all():
+                raise ValueError("invalid: a value vector entry is not finite (V6)")
         s.books.append(k)
     for _ in range(b.read(6) + 1):
         if b.read(16) != 0:
@@ -172,9 +194,11 @@ def parse_headers(id_packet, setup_packet):
     s.floors = []
     for _ in range(b.read(6) + 1):
         t = b.read(16)
+        if b.eop:
+            raise ValueError("invalid: header ends")
         if t == 0:
             raise ValueError("unsupported floor 0")
-        if t != 1 or b.eop:
+        if t != 1:
             raise ValueError("invalid floor type")
         f = Setup()
         f.part_class = [b.read(4) for _ in range(b.read(5))]
@@ -184,6 +208,8 @@ def parse_headers(id_packet, setup_packet):
             c.dim, c.sub = b.read(3) + 1, b.read(2)
             c.master = b.read(8) if c.sub else None
             c.books = [b.read(8) - 1 for _ in range(1 << c.sub)]
+            if (c.sub and c.master >= len(s.books)) or max(c.books) >= len(s.books):
+                raise ValueError("invalid floor book")
             f.classes.append(c)
         f.mult, f.rangebits = b.read(2) + 1, b.read(4)
         f.x = [0, 1 << f.rangebits]
@@ -207,6 +233,10 @@ def parse_headers(id_packet, setup_packet):
             low = b.read(3)
             r.cascade.append((b.read(5) if b.read(1) else 0) * 8 + low)
         r.books = [[b.read(8) if (c >> j) & 1 else None for j in range(8)] for c in r.cascade]
+        if r.classbook >= len(s.books) or s.books[r.classbook].dim == 0:
+            raise ValueError("invalid residue class book")
+        if any(k is not None and (k >= len(s.books) or s.books[k].values is None) for row in r.books for k in row):
+            raise ValueError("invalid residue book: none, or one without value vectors")
         s.residues.append(r)
     s.mappings = []
     for _ in range(b.read(6) + 1):
@@ -218,6 +248,10 @@ def parse_headers(id_packet, setup_packet):
         if b.read(1):
             for _ in range(b.read(8) + 1):
                 m.coupling.append((b.read(ilog(ch - 1)), b.read(ilog(ch - 1))))
+            if len(m.coupling) > 32:
+                raise ValueError("unsupported: more than 32 coupling steps")
+            if any(mag == ang or mag >= ch or ang >= ch for mag, ang in m.coupling):
+                raise ValueError("invalid coupling channels")
         if b.read(2) != 0:
             raise ValueError("invalid mapping")
         m.mux = [b.read(4) for _ in range(ch)] if m.submaps > 1 else [0] * ch
@@ -225,6 +259,8 @@ def parse_headers(id_packet, setup_packet):
         for _ in range(m.submaps):
             b.read(8)
             m.sub.append((b.read(8), b.read(8)))
+        if max(m.mux) >= m.submaps or any(fl >= len(s.floors) or rs >= len(s.residues) for fl, rs in m.sub):
+            raise ValueError("invalid mapping: a mux, floor or residue number out of range")
         s.mappings.append(m)
     s.modes = []
     for _ in range(b.read(6) + 1):
@@ -232,6 +268,8 @@ def parse_headers(id_packet, setup_packet):
         if b.read(16) != 0 or b.read(16) != 0:
             raise ValueError("invalid mode")
         s.modes.append((flag, b.read(8)))
+        if s.modes[-1][1] >= len(s.mappings):
+            raise ValueError("invalid mode mapping")
     if b.read(1) != 1 or b.eop:
         raise ValueError("invalid framing")
     return s
@@ -460,21 +498,45 @@ def window(n, bs0, is_long, pf, nf):
     return np.concatenate([half(not is_long or pf), half(not is_long or nf)[::-1]])
 
 
-def decode_stream(s, packets, max_samples=None, want_float=False):
+def decode_packet(s, data):
+    """One packet by itself (nothing of a packet depends on another before the overlap): (status, mode, block, spectrum, windowed block),
+    the last two None unless OK."""
+    b = Bits(data)
+    status, mode, n, pf, nf = packet_head(s, b)
+    if status != OK:
+        return status, 0, 0, None, None
+    with np.errstate(over="ignore", invalid="ignore"):               # (V6: huge finite value vectors may sum past float32)
+        rows = packet_spectrum(s, b, mode, n)
+        block = np.stack([imdct(rows[c]) for c in range(s.channels)]) * window(n, s.bs[0], n == s.bs[1] and s.modes[mode][0], pf, nf)[None, :]
+    return status, mode, n, rows, block
+
+
+def to_pcm16(x):
+    """V5, and V6's second half: what is not a number is stored as 0."""
+    with np.errstate(invalid="ignore"):
+        v = np.clip(np.floor(x * 32768.0 + 0.5), -32768, 32767)
+    return np.where(np.isnan(v), 0.0, v).astype(np.int32)
+
+
+def decode_stream(s, packets, max_samples=None, want_float=False, cache=None):
     """A stream's packets (bytes each) -> (records, spectra, pcm): records as (status, mode, block, samples, position) per packet, spectra
-    float32 [channels][block / 2] per OK packet (else None), pcm int32 [channels][samples] by V3-V5 (or the float64 before rounding)."""
+    float32 [channels][block / 2] per OK packet (else None), pcm int32 [channels][samples] by V3-V6 (or the float64 before rounding).
+    cache: a dict of this setup's decode_packet results by the packet's bytes, for sets of streams that share most packets."""
     recs, spectra, out = [], [], []
     prev, pos = None, 0
     for data in packets:
-        b = Bits(data)
-        status, mode, n, pf, nf = packet_head(s, b)
+        data = bytes(data)
+        if cache is None:
+            status, mode, n, rows, block = decode_packet(s, data)
+        else:
+            if data not in cache:
+                cache[data] = decode_packet(s, data)
+            status, mode, n, rows, block = cache[data]
         if status != OK:
             recs.append((status, 0, 0, 0, pos))
             spectra.append(None)
             continue
-        rows = packet_spectrum(s, b, mode, n)
         spectra.append(rows)
-        block = np.stack([imdct(rows[c]) for c in range(s.channels)]) * window(n, s.bs[0], n == s.bs[1] and s.modes[mode][0], pf, nf)[None, :]
         d = 0
         if prev is not None:
             pn = prev.shape[1]
@@ -483,7 +545,8 @@ def decode_stream(s, packets, max_samples=None, want_float=False):
             piece[:, :min(pn // 2, d)] += prev[:, pn // 2:pn // 2 + min(pn // 2, d)]
             shift = n // 4 - pn // 4
             j0 = max(0, -shift)
-            piece[:, j0:] += block[:, j0 + shift:d + shift]
+            with np.errstate(invalid="ignore"):
+                piece[:, j0:] += block[:, j0 + shift:d + shift]
             out.append(piece)
         room = d if max_samples is None else max(0, min(d, max_samples - pos))
         recs.append((OK, mode, n, room, pos))
@@ -494,7 +557,7 @@ def decode_stream(s, packets, max_samples=None, want_float=False):
         x = x[:, :max_samples]
     if want_float:
         return recs, spectra, x
-    return recs, spectra, np.clip(np.floor(x * 32768.0 + 0.5), -32768, 32767).astype(np.int32)
+    return recs, spectra, to_pcm16(x)
 
 
 def mdct(x):
