@@ -1,4 +1,7 @@
-"""ctypes binding of libohgpu.so -- exactly the entry points include/ohgpu.h declares.
+"""ctypes binding of libohgpu.so -- exactly the entry points the headers under include/ declare.
+
+The record dtypes and constants come first, then the signature tables (ABI_TABLES: one per header), the private marshalling helpers
+(_typed, _ptr, _create, _fetch, _phase_ms, _paths, _process_host), and every family's named functions and Context methods over them.
 
 There is no CPU fallback: if the library is missing this module raises, and if there is no GPU
 ohgpu_init() returns OHGPU_ERR_NO_DEVICE which `Context` turns into an exception.
@@ -222,205 +225,8 @@ DSD_FILE_STREAM_RESULT = np.dtype([("status", "<u4"), ("kind", "<u4"), ("channel
                                    ("sample_count", "<u8"), ("chunks_total", "<u8"), ("chunks_available", "<u8"), ("chunks_written", "<u8"), ("bytes_written", "<u8"),
                                    ("data_offset", "<u8"), ("data_bytes", "<u8"), ("metadata_offset", "<u8"), ("error_offset", "<u8")], align=False)
 assert DSD_FILE_STREAM_DESC.itemsize == 64 and DSD_FILE_STREAM_RESULT.itemsize == 96
-
-# every symbol of include/ohgpu.h: name -> (restype, argtypes)
-_vp, _vpp = C.c_void_p, C.POINTER(C.c_void_p)
-_u64p = C.POINTER(C.c_uint64)
-SYMBOLS = {
-    "ohgpu_abi_version": (C.c_int, []),
-    "ohgpu_last_error": (C.c_char_p, []),
-    "ohgpu_device_count": (C.c_int, []),
-    "ohgpu_init": (C.c_int, [C.c_int, _vpp]),
-    "ohgpu_shutdown": (C.c_int, [_vp]),
-    "ohgpu_device_name": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
-    "ohgpu_device_pci_bus_id": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
-    "ohgpu_malloc": (C.c_int, [_vp, C.c_size_t, _vpp]),
-    "ohgpu_free": (C.c_int, [_vp, _vp]),
-    "ohgpu_malloc_host": (C.c_int, [_vp, C.c_size_t, _vpp]),
-    "ohgpu_free_host": (C.c_int, [_vp, _vp]),
-    "ohgpu_memcpy_h2d": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp]),
-    "ohgpu_memcpy_d2h": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp]),
-    "ohgpu_memset": (C.c_int, [_vp, _vp, C.c_int, C.c_size_t, _vp]),
-    "ohgpu_stream_create": (C.c_int, [_vp, _vpp]),
-    "ohgpu_stream_destroy": (C.c_int, [_vp, _vp]),
-    "ohgpu_stream_sync": (C.c_int, [_vp, _vp]),
-    "ohgpu_event_create": (C.c_int, [_vp, _vpp]),
-    "ohgpu_event_destroy": (C.c_int, [_vp, _vp]),
-    "ohgpu_event_record": (C.c_int, [_vp, _vp, _vp]),
-    "ohgpu_stream_wait_event": (C.c_int, [_vp, _vp, _vp]),
-    "ohgpu_event_elapsed_ms": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_float)]),
-    "ohgpu_ramp_table": (C.c_int, [C.POINTER(C.c_uint16)]),
-    "ohgpu_pcm_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
-    "ohgpu_pcm_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_batch_destroy": (C.c_int, [_vp, _vp]),
-    "ohgpu_batch_info": (C.c_int, [_vp, _u64p, _u64p, _u64p, _u64p, _u64p]),
-    "ohgpu_batch_paths_info": (C.c_int, [_vp, _vp]),
-    "ohgpu_pcm_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64]),
-    "ohgpu_fmt_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
-    "ohgpu_fmt_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_dsd_layout": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u64p, _u64p]),
-    "ohgpu_dsd_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
-    "ohgpu_dsd_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_dsd_batch_paths": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
-    "ohgpu_dsd_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64]),
-    "ohgpu_dsd_pcm_design": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double, _vp, C.c_size_t,
-                                       C.POINTER(C.c_uint32)]),
-    "ohgpu_dsd_pcm_create": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _vpp]),
-    "ohgpu_dsd_pcm_destroy": (C.c_int, [_vp, _vp]),
-    "ohgpu_dsd_pcm_window": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _u64p, _u64p]),
-    "ohgpu_dsd_pcm_batch_create": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
-    "ohgpu_dsd_pcm_batch_check": (C.c_int, [C.c_uint32, C.c_uint32, _vp, C.c_size_t, C.c_uint64, C.c_uint64]),
-    "ohgpu_dsd_pcm_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_dsd_pcm_batch_paths": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
-    "ohgpu_dsd_pcm_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64]),
-    "ohgpu_flac_streaminfo": (C.c_int, [_vp, C.c_size_t, _vp, _u64p]),
-    "ohgpu_flac_batch_check": (C.c_int, [_vp, C.c_size_t, C.c_uint64, C.c_uint64]),
-    "ohgpu_flac_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
-    "ohgpu_flac_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_flac_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_flac_batch_frames": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
-    "ohgpu_flac_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
-    "ohgpu_flac_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
-    "ohgpu_alac_config_parse": (C.c_int, [_vp, C.c_size_t, _vp]),
-    "ohgpu_alac_batch_check": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, C.c_uint64, C.c_uint64]),
-    "ohgpu_alac_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
-    "ohgpu_alac_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_alac_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t]),
-    "ohgpu_alac_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
-    "ohgpu_alac_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
-    "ohgpu_raop_fmtp_parse": (C.c_int, [C.c_char_p, C.c_size_t, _vp]),
-    "ohgpu_raop_batch_check": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, C.c_uint64, C.c_uint64]),
-    "ohgpu_raop_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
-    "ohgpu_raop_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_raop_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t]),
-    "ohgpu_raop_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
-    "ohgpu_raop_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
-    "ohgpu_ohm_rx_batch_check": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, C.c_uint64, C.c_uint64]),
-    "ohgpu_ohm_rx_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
-    "ohgpu_ohm_rx_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_ohm_rx_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t]),
-    "ohgpu_ohm_rx_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
-    "ohgpu_ohm_rx_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
-    "ohgpu_ogg_batch_check": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64]),
-    "ohgpu_ogg_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
-    "ohgpu_ogg_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_ogg_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_ogg_batch_packets": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_ogg_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
-    "ohgpu_ogg_process_host": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
-    "ohgpu_mp4_batch_check": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_uint64]),
-    "ohgpu_mp4_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_uint64, _vpp]),
-    "ohgpu_mp4_batch_run": (C.c_int, [_vp, _vp, _vp, _vp]),
-    "ohgpu_mp4_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_mp4_batch_packets": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_mp4_batch_samples": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_mp4_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
-    "ohgpu_mp4_process_host": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, _vp, _vp]),
-    "ohgpu_mp4_seek": (C.c_int, [_vp, C.c_size_t, C.c_uint64, _u64p, _u64p]),
-    "ohgpu_mp4_alac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_mp4f_batch_check": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64]),
-    "ohgpu_mp4f_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
-    "ohgpu_mp4f_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_mp4f_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_mp4f_batch_runs": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_mp4f_batch_packets": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_mp4f_batch_samples": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_mp4f_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
-    "ohgpu_mp4f_batch_paths": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
-    "ohgpu_mp4f_head": (C.c_int, [_vp, C.c_size_t, _vp]),
-    "ohgpu_mp4f_process_host": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
-    "ohgpu_mp4f_flac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp,
-                                               C.c_size_t, C.POINTER(C.c_size_t)]),
-    "ohgpu_mp4f_alac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_iff_batch_check": (C.c_int, [_vp, C.c_size_t, C.c_uint64, C.c_uint64]),
-    "ohgpu_iff_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
-    "ohgpu_iff_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_iff_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_iff_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
-    "ohgpu_iff_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),
-    "ohgpu_dsd_file_batch_check": (C.c_int, [_vp, C.c_size_t, C.c_uint64, C.c_uint64]),
-    "ohgpu_dsd_file_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
-    "ohgpu_dsd_file_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_dsd_file_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_dsd_file_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
-    "ohgpu_dsd_file_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),
-    "ohgpu_dsd_file_head": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp]),
-    "ohgpu_dsd_file_seek": (C.c_int, [C.c_uint32, C.c_uint64, _u64p, _u64p]),
-    "ohgpu_ogg_crc": (C.c_uint32, [_vp, C.c_size_t]),
-    "ohgpu_ogg_flac_head": (C.c_int, [_vp, C.c_size_t, _vp, C.POINTER(C.c_uint32), _u64p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
-    "ohgpu_ogg_flac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp,
-                                              C.c_size_t, C.POINTER(C.c_size_t)]),
-    "ohgpu_flywheel_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
-    "ohgpu_flywheel_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_flywheel_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64]),
-    "ohgpu_ohm_frame_layout": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
-    "ohgpu_ohm_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
-    "ohgpu_ohm_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_ohm_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64]),
-    "ohgpu_src_design": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, _vp, C.c_size_t,
-                                   C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
-    "ohgpu_src_create": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vpp]),
-    "ohgpu_src_destroy": (C.c_int, [_vp, _vp]),
-    "ohgpu_src_out_frames": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint64]),
-    "ohgpu_src_mfma_tables": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, C.c_size_t, _vp, C.c_size_t,
-                                        C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
-    "ohgpu_src_mfma_halfband_tables": (C.c_int, [_vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_uint32)]),
-    "ohgpu_src_batch_create": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
-    "ohgpu_src_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_src_batch_run_timed": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_src_batch_plan": (C.c_int, [_vp, _u64p, _u64p]),
-    "ohgpu_src_batch_units": (C.c_int, [_vp, _u64p, _u64p]),
-    "ohgpu_set_plan_threads": (C.c_int, [C.c_int]),
-    "ohgpu_src_batch_block": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
-    "ohgpu_src_batch_advance": (C.c_int, [_vp, _vp, C.c_uint64]),
-    "ohgpu_src_batch_set_ramps": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_src_plan_digest": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_size_t, C.c_uint64, C.c_uint64, C.c_int,
-                                        _vp, C.c_int, _u64p, _u64p, _u64p, C.POINTER(C.c_int)]),
-    "ohgpu_src_batch_kernel_name": (C.c_int, [_vp, _vp, C.c_char_p, C.c_size_t]),
-    "ohgpu_src_batch_occupancy": (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
-    "ohgpu_measure_shader_clock": (C.c_int, [_vp, _vp, C.POINTER(C.c_double)]),
-    "ohgpu_device_allocations": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
-    "ohgpu_src_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64]),
-    "ohgpu_host_transfer_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
-    "ohgpu_set_kernel_variant": (C.c_int, [_vp, C.c_int]),
-    "ohgpu_src_pull_design": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double, _vp, C.c_size_t]),
-    "ohgpu_src_pull_step": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _u64p]),
-    "ohgpu_src_pull_window": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _u64p, _u64p]),
-    "ohgpu_src_pull_create": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _vpp]),
-    "ohgpu_src_pull_destroy": (C.c_int, [_vp, _vp]),
-    "ohgpu_src_pull_batch_create": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
-    "ohgpu_src_pull_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_src_pull_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64]),
-}
-# include/ohgpu_cenc.h's, the part of the ABI that has a header of its own
-CENC_SYMBOLS = {
-    "ohgpu_cenc_batch_check": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64]),
-    "ohgpu_cenc_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
-    "ohgpu_cenc_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_cenc_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_cenc_batch_runs": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_cenc_batch_packets": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_cenc_batch_samples": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_cenc_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
-    "ohgpu_cenc_batch_paths": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
-    "ohgpu_cenc_head": (C.c_int, [_vp, C.c_size_t, _vp]),
-    "ohgpu_cenc_process_host": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
-    "ohgpu_cenc_flac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp,
-                                               C.c_size_t, C.POINTER(C.c_size_t)]),
-    "ohgpu_cenc_alac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
-}
-# include/ohgpu_raop_rx.h's: the RAOP receiver -- the datagram table, the stream table with the state carried between
+# the RAOP receiver (include/ohgpu_raop_rx.h): the datagram table, the stream table with the state carried between
 # batches, a record per datagram, a result per stream with the resend ranges
-RAOP_RX_SYMBOLS = {
-    "ohgpu_raop_rx_batch_check": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, C.c_uint64]),
-    "ohgpu_raop_rx_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_uint64, _vpp]),
-    "ohgpu_raop_rx_batch_run": (C.c_int, [_vp, _vp, _vp, _vp]),
-    "ohgpu_raop_rx_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t]),
-    "ohgpu_raop_rx_batch_packets": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_raop_rx_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
-    "ohgpu_raop_rx_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint64, _vp, _vp, _vp]),
-    "ohgpu_raop_rx_alac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
-}
 RAOP_RX_MAX_PACKET_BYTES, RAOP_RX_MAX_FRAMES, RAOP_RX_MAX_RANGES = 1472, 63, 31
 RAOP_RX_PORT_AUDIO, RAOP_RX_PORT_CONTROL = 0, 1
 RAOP_RX_OK, RAOP_RX_TRUNCATED, RAOP_RX_OVERSIZE, RAOP_RX_OTHER_TYPE = range(4)
@@ -440,31 +246,8 @@ RAOP_RX_RECORD = np.dtype([
 RAOP_RX_STREAM_RESULT = np.dtype(_RAOP_RX_STATE + [("n_output", "<u4"), ("n_pending", "<u4"), ("stop_reason", "<u4"), ("n_ranges", "<u4"),
                                                   ("ranges", "<u4", (31, 2))], align=False)
 assert RAOP_RX_DATAGRAM.itemsize == 16 and RAOP_RX_STREAM.itemsize == 48 and RAOP_RX_RECORD.itemsize == 48 and RAOP_RX_STREAM_RESULT.itemsize == 296
-# include/ohgpu_ts.h's: the MPEG transport stream demultiplexer and the ADTS frame table -- a descriptor and a result per
+# the MPEG transport stream demultiplexer and the ADTS frame table (include/ohgpu_ts.h): a descriptor and a result per
 # stream in both layers, a record per PES packet, a record per ADTS frame
-_u32p = C.POINTER(C.c_uint32)
-TS_SYMBOLS = {
-    "ohgpu_ts_batch_check": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64]),
-    "ohgpu_ts_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
-    "ohgpu_ts_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_ts_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_ts_batch_pes": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_ts_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
-    "ohgpu_ts_batch_paths": (C.c_int, [_vp, _u32p, _u32p, _u32p]),
-    "ohgpu_ts_process_host": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
-    "ohgpu_ts_crc": (C.c_uint32, [_vp, C.c_size_t]),
-    "ohgpu_adts_batch_check": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_uint64]),
-    "ohgpu_adts_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_uint64, _vpp]),
-    "ohgpu_adts_batch_run": (C.c_int, [_vp, _vp, _vp, _vp]),
-    "ohgpu_adts_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_adts_batch_frames": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_adts_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
-    "ohgpu_adts_batch_paths": (C.c_int, [_vp, _u32p, _u32p]),
-    "ohgpu_adts_process_host": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, _vp]),
-    "ohgpu_adts_header": (C.c_int, [_vp, C.c_size_t, _vp]),
-    "ohgpu_id3v2_skip": (C.c_uint64, [_vp, C.c_size_t]),
-    "ohgpu_ts_adts_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
-}
 TS_PACKET_BYTES, TS_NONE, TS_NO_PTS = 188, 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
 TS_OK, TS_NO_PAT, TS_NO_PMT, TS_NO_AUDIO, TS_CORRUPT = range(5)
 TS_PES_OPEN = 1
@@ -488,43 +271,7 @@ ADTS_FRAME = np.dtype([("offset", "<u8"), ("bytes", "<u4"), ("flags", "<u4"), ("
                        ("reserved", "<u4", (3,))], align=False)
 assert TS_STREAM_DESC.itemsize == 64 and TS_STREAM_RESULT.itemsize == 64 and TS_PES.itemsize == 32
 assert ADTS_STREAM_DESC.itemsize == 32 and ADTS_STREAM_RESULT.itemsize == 64 and ADTS_FRAME.itemsize == 32
-
-
-# include/ohgpu_cbcs.h's: ohgpu_cenc_*'s calls with a batch-wide n_subsamples behind n_runs
-CBCS_SYMBOLS = {
-    "ohgpu_cbcs_batch_check": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64]),
-    "ohgpu_cbcs_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64, _vpp]),
-    "ohgpu_cbcs_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_cbcs_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_cbcs_batch_runs": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_cbcs_batch_packets": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_cbcs_batch_samples": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
-    "ohgpu_cbcs_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
-    "ohgpu_cbcs_batch_paths": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
-    "ohgpu_cbcs_head": (C.c_int, [_vp, C.c_size_t, _vp]),
-    "ohgpu_cbcs_process_host": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
-    "ohgpu_cbcs_flac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp,
-                                               _vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
-    "ohgpu_cbcs_alac_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp,
-                                               _vp, _vp, _vp]),
-}
-# include/ohgpu_vorbis.h's: the Vorbis I decoder -- the setup image's parse, a descriptor per stream over rows of ALAC_PACKET
-VORBIS_SYMBOLS = {
-    "ohgpu_vorbis_setup_parse": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
-    "ohgpu_vorbis_codewords": (C.c_int, [_vp, C.c_size_t, _vp]),
-    "ohgpu_vorbis_batch_check": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint64, C.c_uint64, C.c_uint64]),
-    "ohgpu_vorbis_batch_create": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vpp]),
-    "ohgpu_vorbis_batch_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
-    "ohgpu_vorbis_batch_results": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t]),
-    "ohgpu_vorbis_batch_phase_ms": (C.c_int, [_vp, _vp, C.POINTER(C.c_float)]),
-    "ohgpu_vorbis_batch_paths": (C.c_int, [_vp, _u32p, _u32p]),
-    "ohgpu_vorbis_batch_spectrum": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, _vp, C.c_size_t]),
-    "ohgpu_vorbis_head": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, _vp, _u32p, C.POINTER(C.c_uint64), _u32p, _u32p]),
-    "ohgpu_ogg_vorbis_process_host": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
-    "ohgpu_vorbis_process_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
-    "ohgpu_ogg_vorbis_links_process_host": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp,
-                                                      _vp, C.c_size_t, C.POINTER(C.c_size_t), _vp]),
-}
+# the Vorbis I decoder (include/ohgpu_vorbis.h): the setup image's info, a descriptor per stream over rows of ALAC_PACKET
 VORBIS_OK, VORBIS_HEADER, VORBIS_CORRUPT = 0, 1, 2
 VORBIS_OUT_PLANAR32 = 1
 VORBIS_INFO = np.dtype([("channels", "<u4"), ("sample_rate", "<u4"), ("blocksize_short", "<u4"), ("blocksize_long", "<u4"), ("image_bytes", "<u4"),
@@ -540,6 +287,283 @@ VORBIS_LINK = np.dtype([("stream", "<u4"), ("serial", "<u4"), ("page_offset", "<
                         ("channels", "<u4"), ("sample_rate", "<u4"), ("blocksize_short", "<u4"), ("blocksize_long", "<u4"), ("reserved", "<u4"),
                         ("dst_offset", "<u8"), ("samples", "<u8")], align=False)
 assert VORBIS_LINK.itemsize == 64
+MF_STEP = np.dtype([("aoff", "<u4", (16,)), ("b0", "<u4", (16,)), ("b1", "<u4", (16,)), ("b2", "<i4", (16,)), ("kc", "<u4"), ("pad", "<u4", (7,))])
+assert MF_STEP.itemsize == 288
+
+# ---- the ABI's signatures: a table per header under include/, name -> (restype, argtypes), and ABI_TABLES over the six.  lib() binds
+# what ABI_TABLES lists; tests/test_capi_loads.py holds every entry to its header's prototype, argument by argument.  The shapes that
+# recur have a name each.
+_int, _u32, _u64, _sz, _dbl = C.c_int, C.c_uint32, C.c_uint64, C.c_size_t, C.c_double
+_vp, _vpp, _str = C.c_void_p, C.POINTER(C.c_void_p), C.c_char_p
+_u32p, _u64p, _szp, _intp = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_size_t), C.POINTER(C.c_int)
+_HANDLE = (_int, [_vp, _vp])                                           # (ctx, handle): a destroy, a free, a wait
+_CREATE = (_int, [_vp, _vp, _sz, _u64, _u64, _vpp])                    # (ctx, descs, n, src arena, dst arena, batch out)
+_CREATE_FILTER = (_int, [_vp, _vp, _vp, _sz, _u64, _u64, _vpp])        # ... with a filter in front of the descriptors
+_CREATE_PACKETS = (_int, [_vp, _vp, _sz, _vp, _sz, _u64, _u64, _vpp])  # ... with a second table behind them
+_CHECK = (_int, [_vp, _sz, _u64, _u64])                                # _CREATE without a device
+_CHECK_PACKETS = (_int, [_vp, _sz, _vp, _sz, _u64, _u64])              # _CREATE_PACKETS without a device
+_RUN = (_int, [_vp, _vp, _vp, _vp, _vp])                               # (ctx, batch, src, dst, stream)
+_RUN_SRC = (_int, [_vp, _vp, _vp, _vp])                                # (ctx, batch, src, stream): a batch with no destination arena
+_FETCH = (_int, [_vp, _vp, _vp, _sz])                                  # (ctx, batch, out, n): a table of the last run
+_FETCH_PAIR = (_int, [_vp, _vp, _vp, _sz, _vp, _sz])                   # ... two tables in one call
+_PHASE_MS = (_int, [_vp, _vp, C.POINTER(C.c_float)])                   # (ctx, batch, ms[K])
+_PATHS = (_int, [_vp, _u32p, _u32p, _u32p])                            # (batch, three words out)
+_PATHS_PAIR = (_int, [_vp, _u32p, _u32p])                              # (batch, two words out)
+_HEAD = (_int, [_vp, _sz, _vp])                                        # (bytes, n, one record out), host only
+_HOST = (_int, [_vp, _vp, _sz, _vp, _u64, _vp, _u64])                  # (ctx, descs, n, src, bytes, dst, bytes)
+_HOST_FILTER = (_int, [_vp, _vp, _vp, _sz, _vp, _u64, _vp, _u64])      # ... with a filter
+_HOST_RESULTS = (_int, [_vp, _vp, _sz, _vp, _u64, _vp, _u64, _vp])     # ... with the stream results out
+_HOST_PACKETS = (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _u64, _vp, _u64, _vp, _vp])   # two tables in, two out
+_FRAG_CHECK = (_int, [_vp, _sz, _sz, _sz, _u64, _u64])                 # the fragmented MPEG-4 families: descs, n, n_packets, n_runs
+_FRAG_CREATE = (_int, [_vp, _vp, _sz, _sz, _sz, _u64, _u64, _vpp])
+_FRAG_HOST = (_int, [_vp, _vp, _sz, _sz, _sz, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp])
+_FRAG_FLAC_HOST = (_int, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _szp])
+# include/ohgpu.h
+SYMBOLS = {
+    "ohgpu_abi_version": (_int, []),
+    "ohgpu_last_error": (_str, []),
+    "ohgpu_device_count": (_int, []),
+    "ohgpu_init": (_int, [_int, _vpp]),
+    "ohgpu_shutdown": (_int, [_vp]),
+    "ohgpu_device_name": (_int, [_vp, _str, _sz]),
+    "ohgpu_device_pci_bus_id": (_int, [_vp, _str, _sz]),
+    "ohgpu_malloc": (_int, [_vp, _sz, _vpp]),
+    "ohgpu_free": _HANDLE,
+    "ohgpu_malloc_host": (_int, [_vp, _sz, _vpp]),
+    "ohgpu_free_host": _HANDLE,
+    "ohgpu_memcpy_h2d": (_int, [_vp, _vp, _vp, _sz, _vp]),
+    "ohgpu_memcpy_d2h": (_int, [_vp, _vp, _vp, _sz, _vp]),
+    "ohgpu_memset": (_int, [_vp, _vp, _int, _sz, _vp]),
+    "ohgpu_stream_create": (_int, [_vp, _vpp]),
+    "ohgpu_stream_destroy": _HANDLE,
+    "ohgpu_stream_sync": _HANDLE,
+    "ohgpu_event_create": (_int, [_vp, _vpp]),
+    "ohgpu_event_destroy": _HANDLE,
+    "ohgpu_event_record": (_int, [_vp, _vp, _vp]),
+    "ohgpu_stream_wait_event": (_int, [_vp, _vp, _vp]),
+    "ohgpu_event_elapsed_ms": (_int, [_vp, _vp, _vp, C.POINTER(C.c_float)]),
+    "ohgpu_ramp_table": (_int, [C.POINTER(C.c_uint16)]),
+    "ohgpu_pcm_batch_create": _CREATE,
+    "ohgpu_pcm_batch_run": _RUN,
+    "ohgpu_batch_destroy": _HANDLE,
+    "ohgpu_batch_info": (_int, [_vp, _u64p, _u64p, _u64p, _u64p, _u64p]),
+    "ohgpu_batch_paths_info": (_int, [_vp, _vp]),
+    "ohgpu_pcm_process_host": _HOST,
+    "ohgpu_fmt_batch_create": _CREATE,
+    "ohgpu_fmt_batch_run": _RUN,
+    "ohgpu_dsd_layout": (_int, [_u32, _u32, _u32, _u32, _u64p, _u64p]),
+    "ohgpu_dsd_batch_create": _CREATE,
+    "ohgpu_dsd_batch_run": _RUN,
+    "ohgpu_dsd_batch_paths": _PATHS,
+    "ohgpu_dsd_process_host": _HOST,
+    "ohgpu_dsd_pcm_design": (_int, [_u32, _u32, _u32, _dbl, _dbl, _dbl, _vp, _sz, _u32p]),
+    "ohgpu_dsd_pcm_create": (_int, [_vp, _u32, _u32, _vp, _vpp]),
+    "ohgpu_dsd_pcm_destroy": _HANDLE,
+    "ohgpu_dsd_pcm_window": (_int, [_u64, _u32, _u32, _u32, _u64p, _u64p]),
+    "ohgpu_dsd_pcm_batch_create": _CREATE_FILTER,
+    "ohgpu_dsd_pcm_batch_check": (_int, [_u32, _u32, _vp, _sz, _u64, _u64]),
+    "ohgpu_dsd_pcm_batch_run": _RUN,
+    "ohgpu_dsd_pcm_batch_paths": _PATHS,
+    "ohgpu_dsd_pcm_process_host": _HOST_FILTER,
+    "ohgpu_flac_streaminfo": (_int, [_vp, _sz, _vp, _u64p]),
+    "ohgpu_flac_batch_check": _CHECK,
+    "ohgpu_flac_batch_create": _CREATE,
+    "ohgpu_flac_batch_run": _RUN,
+    "ohgpu_flac_batch_results": _FETCH,
+    "ohgpu_flac_batch_frames": (_int, [_vp, _vp, _vp, _sz, _szp]),
+    "ohgpu_flac_batch_phase_ms": _PHASE_MS,
+    "ohgpu_flac_process_host": (_int, [_vp, _vp, _sz, _vp, _u64, _vp, _u64, _vp, _vp, _sz, _szp]),
+    "ohgpu_alac_config_parse": _HEAD,
+    "ohgpu_alac_batch_check": _CHECK_PACKETS,
+    "ohgpu_alac_batch_create": _CREATE_PACKETS,
+    "ohgpu_alac_batch_run": _RUN,
+    "ohgpu_alac_batch_results": _FETCH_PAIR,
+    "ohgpu_alac_batch_phase_ms": _PHASE_MS,
+    "ohgpu_alac_process_host": _HOST_PACKETS,
+    "ohgpu_raop_fmtp_parse": (_int, [_str, _sz, _vp]),
+    "ohgpu_raop_batch_check": _CHECK_PACKETS,
+    "ohgpu_raop_batch_create": _CREATE_PACKETS,
+    "ohgpu_raop_batch_run": _RUN,
+    "ohgpu_raop_batch_results": _FETCH_PAIR,
+    "ohgpu_raop_batch_phase_ms": _PHASE_MS,
+    "ohgpu_raop_process_host": _HOST_PACKETS,
+    "ohgpu_ohm_rx_batch_check": _CHECK_PACKETS,
+    "ohgpu_ohm_rx_batch_create": _CREATE_PACKETS,
+    "ohgpu_ohm_rx_batch_run": _RUN,
+    "ohgpu_ohm_rx_batch_results": _FETCH_PAIR,
+    "ohgpu_ohm_rx_batch_phase_ms": _PHASE_MS,
+    "ohgpu_ohm_rx_process_host": _HOST_PACKETS,
+    "ohgpu_ogg_batch_check": (_int, [_vp, _sz, _sz, _u64, _u64]),
+    "ohgpu_ogg_batch_create": (_int, [_vp, _vp, _sz, _sz, _u64, _u64, _vpp]),
+    "ohgpu_ogg_batch_run": _RUN,
+    "ohgpu_ogg_batch_results": _FETCH,
+    "ohgpu_ogg_batch_packets": _FETCH,
+    "ohgpu_ogg_batch_phase_ms": _PHASE_MS,
+    "ohgpu_ogg_process_host": (_int, [_vp, _vp, _sz, _sz, _vp, _u64, _vp, _u64, _vp, _vp]),
+    "ohgpu_mp4_batch_check": (_int, [_vp, _sz, _sz, _u64]),
+    "ohgpu_mp4_batch_create": (_int, [_vp, _vp, _sz, _sz, _u64, _vpp]),
+    "ohgpu_mp4_batch_run": _RUN_SRC,
+    "ohgpu_mp4_batch_results": _FETCH,
+    "ohgpu_mp4_batch_packets": _FETCH,
+    "ohgpu_mp4_batch_samples": _FETCH,
+    "ohgpu_mp4_batch_phase_ms": _PHASE_MS,
+    "ohgpu_mp4_process_host": (_int, [_vp, _vp, _sz, _sz, _vp, _u64, _vp, _vp, _vp]),
+    "ohgpu_mp4_seek": (_int, [_vp, _sz, _u64, _u64p, _u64p]),
+    "ohgpu_mp4_alac_process_host": (_int, [_vp, _vp, _vp, _sz, _sz, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "ohgpu_mp4f_batch_check": _FRAG_CHECK,
+    "ohgpu_mp4f_batch_create": _FRAG_CREATE,
+    "ohgpu_mp4f_batch_run": _RUN,
+    "ohgpu_mp4f_batch_results": _FETCH,
+    "ohgpu_mp4f_batch_runs": _FETCH,
+    "ohgpu_mp4f_batch_packets": _FETCH,
+    "ohgpu_mp4f_batch_samples": _FETCH,
+    "ohgpu_mp4f_batch_phase_ms": _PHASE_MS,
+    "ohgpu_mp4f_batch_paths": _PATHS,
+    "ohgpu_mp4f_head": _HEAD,
+    "ohgpu_mp4f_process_host": _FRAG_HOST,
+    "ohgpu_mp4f_flac_process_host": _FRAG_FLAC_HOST,
+    "ohgpu_mp4f_alac_process_host": (_int, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ohgpu_iff_batch_check": _CHECK,
+    "ohgpu_iff_batch_create": _CREATE,
+    "ohgpu_iff_batch_run": _RUN,
+    "ohgpu_iff_batch_results": _FETCH,
+    "ohgpu_iff_batch_phase_ms": _PHASE_MS,
+    "ohgpu_iff_process_host": _HOST_RESULTS,
+    "ohgpu_dsd_file_batch_check": _CHECK,
+    "ohgpu_dsd_file_batch_create": _CREATE,
+    "ohgpu_dsd_file_batch_run": _RUN,
+    "ohgpu_dsd_file_batch_results": _FETCH,
+    "ohgpu_dsd_file_batch_phase_ms": _PHASE_MS,
+    "ohgpu_dsd_file_process_host": _HOST_RESULTS,
+    "ohgpu_dsd_file_head": (_int, [_vp, _u64, _u32, _u32, _vp]),
+    "ohgpu_dsd_file_seek": (_int, [_u32, _u64, _u64p, _u64p]),
+    "ohgpu_ogg_crc": (_u32, [_vp, _sz]),
+    "ohgpu_ogg_flac_head": (_int, [_vp, _sz, _vp, _u32p, _u64p, _u32p, _u32p]),
+    "ohgpu_ogg_flac_process_host": (_int, [_vp, _vp, _vp, _sz, _sz, _vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _sz, _szp]),
+    "ohgpu_flywheel_batch_create": _CREATE,
+    "ohgpu_flywheel_batch_run": _RUN,
+    "ohgpu_flywheel_process_host": _HOST,
+    "ohgpu_ohm_frame_layout": (_int, [_vp, _u32, _u32p, _u32p]),
+    "ohgpu_ohm_batch_create": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _u64, _u64, _vpp]),
+    "ohgpu_ohm_batch_run": _RUN,
+    "ohgpu_ohm_process_host": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _u64, _vp, _u64]),
+    "ohgpu_src_design": (_int, [_u32, _u32, _u32, _dbl, _dbl, _vp, _sz, _u32p, _u32p]),
+    "ohgpu_src_create": (_int, [_vp, _u32, _u32, _u32, _vp, _vpp]),
+    "ohgpu_src_destroy": _HANDLE,
+    "ohgpu_src_out_frames": (_u64, [_u32, _u32, _u64]),
+    "ohgpu_src_mfma_tables": (_int, [_u32, _u32, _u32, _vp, _u32, _vp, _sz, _vp, _sz, _szp, _szp, _u32p]),
+    "ohgpu_src_mfma_halfband_tables": (_int, [_vp, _vp, C.POINTER(C.c_int64), _u32p]),
+    "ohgpu_src_batch_create": _CREATE_FILTER,
+    "ohgpu_src_batch_run": _RUN,
+    "ohgpu_src_batch_run_timed": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ohgpu_src_batch_plan": (_int, [_vp, _u64p, _u64p]),
+    "ohgpu_src_batch_units": (_int, [_vp, _u64p, _u64p]),
+    "ohgpu_set_plan_threads": (_int, [_int]),
+    "ohgpu_src_batch_block": _PATHS_PAIR,
+    "ohgpu_src_batch_advance": (_int, [_vp, _vp, _u64]),
+    "ohgpu_src_batch_set_ramps": (_int, [_vp, _vp, _vp, _vp, _sz]),
+    "ohgpu_src_plan_digest": (_int, [_u32, _u32, _u32, _vp, _sz, _u64, _u64, _int, _vp, _int, _u64p, _u64p, _u64p, _intp]),
+    "ohgpu_src_batch_kernel_name": (_int, [_vp, _vp, _str, _sz]),
+    "ohgpu_src_batch_occupancy": (_int, [_vp, _vp, _intp, _intp, _u32p]),
+    "ohgpu_measure_shader_clock": (_int, [_vp, _vp, C.POINTER(C.c_double)]),
+    "ohgpu_device_allocations": (_int, [_vp, _u64p]),
+    "ohgpu_src_process_host": _HOST_FILTER,
+    "ohgpu_host_transfer_stats": (_int, [_vp, _u64p, _u64p, _u64p, _u64p]),
+    "ohgpu_set_kernel_variant": (_int, [_vp, _int]),
+    "ohgpu_src_pull_design": (_int, [_u32, _u32, _u32, _u32, _dbl, _dbl, _dbl, _vp, _sz]),
+    "ohgpu_src_pull_step": (_int, [_u32, _u32, _u32, _u64p]),
+    "ohgpu_src_pull_window": (_int, [_u64, _u32, _u64, _u32, _u32, _u64p, _u64p]),
+    "ohgpu_src_pull_create": (_int, [_vp, _u32, _u32, _vp, _vpp]),
+    "ohgpu_src_pull_destroy": _HANDLE,
+    "ohgpu_src_pull_batch_create": _CREATE_FILTER,
+    "ohgpu_src_pull_batch_run": _RUN,
+    "ohgpu_src_pull_process_host": _HOST_FILTER,
+}
+# include/ohgpu_cenc.h: protected fragmented MPEG-4, ohgpu_mp4f_*'s calls with a key in the descriptor
+CENC_SYMBOLS = {
+    "ohgpu_cenc_batch_check": _FRAG_CHECK,
+    "ohgpu_cenc_batch_create": _FRAG_CREATE,
+    "ohgpu_cenc_batch_run": _RUN,
+    "ohgpu_cenc_batch_results": _FETCH,
+    "ohgpu_cenc_batch_runs": _FETCH,
+    "ohgpu_cenc_batch_packets": _FETCH,
+    "ohgpu_cenc_batch_samples": _FETCH,
+    "ohgpu_cenc_batch_phase_ms": _PHASE_MS,
+    "ohgpu_cenc_batch_paths": _PATHS,
+    "ohgpu_cenc_head": _HEAD,
+    "ohgpu_cenc_process_host": _FRAG_HOST,
+    "ohgpu_cenc_flac_process_host": _FRAG_FLAC_HOST,
+    "ohgpu_cenc_alac_process_host": (_int, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+# include/ohgpu_cbcs.h: ohgpu_cenc_*'s calls with a batch-wide n_subsamples behind n_runs
+CBCS_SYMBOLS = {
+    "ohgpu_cbcs_batch_check": (_int, [_vp, _sz, _sz, _sz, _sz, _u64, _u64]),
+    "ohgpu_cbcs_batch_create": (_int, [_vp, _vp, _sz, _sz, _sz, _sz, _u64, _u64, _vpp]),
+    "ohgpu_cbcs_batch_run": _RUN,
+    "ohgpu_cbcs_batch_results": _FETCH,
+    "ohgpu_cbcs_batch_runs": _FETCH,
+    "ohgpu_cbcs_batch_packets": _FETCH,
+    "ohgpu_cbcs_batch_samples": _FETCH,
+    "ohgpu_cbcs_batch_phase_ms": _PHASE_MS,
+    "ohgpu_cbcs_batch_paths": _PATHS,
+    "ohgpu_cbcs_head": _HEAD,
+    "ohgpu_cbcs_process_host": (_int, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "ohgpu_cbcs_flac_process_host": (_int, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _szp]),
+    "ohgpu_cbcs_alac_process_host": (_int, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+# include/ohgpu_raop_rx.h
+RAOP_RX_SYMBOLS = {
+    "ohgpu_raop_rx_batch_check": (_int, [_vp, _sz, _vp, _sz, _u64]),
+    "ohgpu_raop_rx_batch_create": (_int, [_vp, _vp, _sz, _vp, _sz, _u64, _vpp]),
+    "ohgpu_raop_rx_batch_run": _RUN_SRC,
+    "ohgpu_raop_rx_batch_results": _FETCH_PAIR,
+    "ohgpu_raop_rx_batch_packets": _FETCH,
+    "ohgpu_raop_rx_batch_phase_ms": _PHASE_MS,
+    "ohgpu_raop_rx_process_host": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _u64, _vp, _vp, _vp]),
+    "ohgpu_raop_rx_alac_process_host": (_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+}
+# include/ohgpu_ts.h
+TS_SYMBOLS = {
+    "ohgpu_ts_batch_check": (_int, [_vp, _sz, _sz, _u64, _u64]),
+    "ohgpu_ts_batch_create": (_int, [_vp, _vp, _sz, _sz, _u64, _u64, _vpp]),
+    "ohgpu_ts_batch_run": _RUN,
+    "ohgpu_ts_batch_results": _FETCH,
+    "ohgpu_ts_batch_pes": _FETCH,
+    "ohgpu_ts_batch_phase_ms": _PHASE_MS,
+    "ohgpu_ts_batch_paths": _PATHS,
+    "ohgpu_ts_process_host": (_int, [_vp, _vp, _sz, _sz, _vp, _u64, _vp, _u64, _vp, _vp]),
+    "ohgpu_ts_crc": (_u32, [_vp, _sz]),
+    "ohgpu_adts_batch_check": (_int, [_vp, _sz, _sz, _u64]),
+    "ohgpu_adts_batch_create": (_int, [_vp, _vp, _sz, _sz, _u64, _vpp]),
+    "ohgpu_adts_batch_run": _RUN_SRC,
+    "ohgpu_adts_batch_results": _FETCH,
+    "ohgpu_adts_batch_frames": _FETCH,
+    "ohgpu_adts_batch_phase_ms": _PHASE_MS,
+    "ohgpu_adts_batch_paths": _PATHS_PAIR,
+    "ohgpu_adts_process_host": (_int, [_vp, _vp, _sz, _sz, _vp, _u64, _vp, _vp]),
+    "ohgpu_adts_header": _HEAD,
+    "ohgpu_id3v2_skip": (_u64, [_vp, _sz]),
+    "ohgpu_ts_adts_process_host": (_int, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
+}
+# include/ohgpu_vorbis.h
+VORBIS_SYMBOLS = {
+    "ohgpu_vorbis_setup_parse": (_int, [_vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "ohgpu_vorbis_codewords": _HEAD,
+    "ohgpu_vorbis_batch_check": (_int, [_vp, _sz, _vp, _sz, _vp, _u64, _u64, _u64]),
+    "ohgpu_vorbis_batch_create": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _u64, _u64, _u64, _vpp]),
+    "ohgpu_vorbis_batch_run": _RUN,
+    "ohgpu_vorbis_batch_results": _FETCH_PAIR,
+    "ohgpu_vorbis_batch_phase_ms": _PHASE_MS,
+    "ohgpu_vorbis_batch_paths": _PATHS_PAIR,
+    "ohgpu_vorbis_batch_spectrum": (_int, [_vp, _vp, _sz, _u32, _vp, _sz]),
+    "ohgpu_vorbis_head": (_int, [_vp, _sz, _vp, _sz, _vp, _u32p, _u64p, _u32p, _u32p]),
+    "ohgpu_ogg_vorbis_process_host": (_int, [_vp, _vp, _vp, _sz, _sz, _vp, _u64, _vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "ohgpu_vorbis_process_host": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp]),
+    "ohgpu_ogg_vorbis_links_process_host": (_int, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _u64, _vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _sz, _szp, _vp]),
+}
+# the registry: header file name -> its table.  A header that is not entered here fails tests/test_capi_loads.py.
+ABI_TABLES = {"ohgpu.h": SYMBOLS, "ohgpu_cenc.h": CENC_SYMBOLS, "ohgpu_cbcs.h": CBCS_SYMBOLS, "ohgpu_raop_rx.h": RAOP_RX_SYMBOLS,
+              "ohgpu_ts.h": TS_SYMBOLS, "ohgpu_vorbis.h": VORBIS_SYMBOLS}
 
 
 class OhGpuError(RuntimeError):
@@ -560,10 +584,11 @@ def lib():
         raise ImportError(f"{LIB_PATH} is missing: build the HIP extension first (python ohpipeline_amd/build.py); "
                           "there is no CPU fallback for the product path")
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(CENC_SYMBOLS.items()) + list(RAOP_RX_SYMBOLS.items()) + list(TS_SYMBOLS.items()) + list(VORBIS_SYMBOLS.items()) + list(CBCS_SYMBOLS.items()):
-        fn = getattr(L, name)          # AttributeError here = the library does not export what ohgpu.h declares
-        fn.restype = res
-        fn.argtypes = args
+    for table in ABI_TABLES.values():
+        for name, (res, args) in table.items():
+            fn = getattr(L, name)          # AttributeError here = the library does not export what its header declares
+            fn.restype = res
+            fn.argtypes = args
     _lib = L
     return L
 
@@ -578,6 +603,73 @@ def check(code):
     return code
 
 
+# ---- the marshalling layer: what every family's calls below are made of.  The *_run methods do not go through it: they are one direct
+# call each, because they sit inside timed loops.
+def _typed(a, dtype):
+    """A table as the library reads it: contiguous, and of the records the entry expects."""
+    a = np.ascontiguousarray(a)
+    assert a.dtype == dtype
+    return a
+
+
+def _ptr(a, keep=False):
+    """The address of a table or host buffer.  An empty one goes as a null pointer, which every entry takes with a zero count, except
+    the few that refuse a null whatever the count (a filter's coefficients, the ramps, ohgpu_flac_streaminfo's bytes): those `keep`
+    the array's own address."""
+    return a.ctypes.data_as(C.c_void_p) if keep or a.size else None
+
+
+def _create(fn, *args):
+    """An entry whose last parameter is the handle it makes (a batch, a filter, a stream, an event, memory): the handle."""
+    h = C.c_void_p()
+    check(fn(*args, C.byref(h)))
+    return h
+
+
+def _fetch(fn, ctx, batch, dtype, n):
+    """A table of a batch's last run (ctx, batch, out, n): n records of dtype."""
+    out = np.zeros(n, dtype=dtype)
+    check(fn(ctx, batch, _ptr(out), n))
+    return out
+
+
+def _fetch_pair(fn, ctx, batch, dtype, n, dtype2, n2):
+    """... of the entries that answer two tables in one call (ctx, batch, out, n, out2, n2)."""
+    out, out2 = np.zeros(n, dtype=dtype), np.zeros(n2, dtype=dtype2)
+    check(fn(ctx, batch, _ptr(out), n, _ptr(out2), n2))
+    return out, out2
+
+
+def _phase_ms(fn, ctx, batch, k):
+    """The k phase times of a batch's last run, in milliseconds."""
+    ms = (C.c_float * k)()
+    check(fn(ctx, batch, ms))
+    return tuple(float(v) for v in ms)
+
+
+def _paths(fn, batch, *keys):
+    """A *_batch_paths entry: a uint32 by reference per key, as a dict."""
+    v = [C.c_uint32(0) for _ in keys]
+    check(fn(batch, *map(C.byref, v)))
+    return {k: int(x.value) for k, x in zip(keys, v)}
+
+
+def _process_host(fn, ctx, args, src, dst, out, mid=(), tail=()):
+    """An ohgpu_*_process_host: `args` (the tables' pointers and the counts, in the entry's order), the source buffer, `mid` (the size
+    of a middle arena, where the entry has one), the destination buffer unless dst is None (a family that writes to no arena), the
+    result tables `out`, which it returns, and whatever the entry has behind them."""
+    bufs = (_ptr(src), src.nbytes, *mid) if dst is None else (_ptr(src), src.nbytes, *mid, _ptr(dst), dst.nbytes)
+    check(fn(ctx, *args, *bufs, *map(_ptr, out), *tail))
+    return out
+
+
+def _head(fn, data, dtype):
+    """A host-only parse of leading bytes into one record (bytes, n, record out)."""
+    raw, out = bytes(data), np.zeros(1, dtype=dtype)
+    check(fn(raw, len(raw), _ptr(out)))
+    return out[0]
+
+
 def ramp_table():
     out = (C.c_uint16 * 512)()
     check(lib().ohgpu_ramp_table(out))
@@ -588,10 +680,6 @@ def device_count():
     """GPUs visible to the process (ohgpu_device_count); 0 without one."""
     n = lib().ohgpu_device_count()
     return max(int(n), 0)
-
-
-MF_STEP = np.dtype([("aoff", "<u4", (16,)), ("b0", "<u4", (16,)), ("b1", "<u4", (16,)), ("b2", "<i4", (16,)), ("kc", "<u4"), ("pad", "<u4", (7,))])
-assert MF_STEP.itemsize == 288
 
 
 def set_plan_threads(threads):
@@ -605,8 +693,8 @@ def src_plan_digest(L, M, T, descs, src_arena_bytes, dst_arena_bytes, kernel_var
     d = np.ascontiguousarray(descs)
     coef = None if coef_q28 is None else np.ascontiguousarray(coef_q28, dtype=np.int32)
     h, u, p, k = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_int(0)
-    check(lib().ohgpu_src_plan_digest(L, M, T, d.ctypes.data_as(C.c_void_p), d.size, src_arena_bytes, dst_arena_bytes, kernel_variant,
-                                      None if coef is None else coef.ctypes.data_as(C.c_void_p), num_cus,
+    check(lib().ohgpu_src_plan_digest(L, M, T, _ptr(d), d.size, src_arena_bytes, dst_arena_bytes, kernel_variant,
+                                      None if coef is None else _ptr(coef, keep=True), num_cus,
                                       C.byref(h), C.byref(u), C.byref(p), C.byref(k)))
     return {"digest": int(h.value), "units": int(u.value), "generic_pieces": int(p.value), "kernel": int(k.value)}
 
@@ -615,10 +703,10 @@ def src_mfma_tables(L, M, T, coef_q28, max_blocks_per_row=8):
     """(digits [4][L][96] int8, steps MF_STEP[], outputs per block) -- the matrix-pipe resampler kernel's host tables (no device)."""
     coef = np.ascontiguousarray(coef_q28, dtype=np.int32)
     nb, ns, lb = C.c_size_t(0), C.c_size_t(0), C.c_uint32(0)
-    check(lib().ohgpu_src_mfma_tables(L, M, T, coef.ctypes.data, max_blocks_per_row, None, 0, None, 0, C.byref(nb), C.byref(ns), C.byref(lb)))
+    check(lib().ohgpu_src_mfma_tables(L, M, T, _ptr(coef, keep=True), max_blocks_per_row, None, 0, None, 0, C.byref(nb), C.byref(ns), C.byref(lb)))
     dig = np.zeros(nb.value, dtype=np.int8)
     steps = np.zeros(ns.value // MF_STEP.itemsize, dtype=MF_STEP)
-    check(lib().ohgpu_src_mfma_tables(L, M, T, coef.ctypes.data, max_blocks_per_row, dig.ctypes.data, dig.nbytes, steps.ctypes.data, steps.nbytes,
+    check(lib().ohgpu_src_mfma_tables(L, M, T, _ptr(coef, keep=True), max_blocks_per_row, _ptr(dig), dig.nbytes, _ptr(steps), steps.nbytes,
                                       C.byref(nb), C.byref(ns), C.byref(lb)))
     return dig.reshape(4, L, 96), steps, lb.value
 
@@ -628,7 +716,7 @@ def src_mfma_halfband_tables(coef_q28):
     coef = np.ascontiguousarray(coef_q28, dtype=np.int32)
     image = np.zeros(4096, dtype=np.int8)
     bias, lb = C.c_int64(0), C.c_uint32(0)
-    check(lib().ohgpu_src_mfma_halfband_tables(coef.ctypes.data, image.ctypes.data, C.byref(bias), C.byref(lb)))
+    check(lib().ohgpu_src_mfma_halfband_tables(_ptr(coef, keep=True), _ptr(image), C.byref(bias), C.byref(lb)))
     return image.reshape(4, 4, 16, 16), int(bias.value), int(lb.value)
 
 
@@ -637,8 +725,7 @@ def src_design(rate_in, rate_out, taps_per_phase=32, beta=9.0, f_pass=20000.0):
     L_, M_ = C.c_uint32(0), C.c_uint32(0)
     check(lib().ohgpu_src_design(rate_in, rate_out, taps_per_phase, beta, f_pass, None, 0, C.byref(L_), C.byref(M_)))
     coef = np.zeros(L_.value * taps_per_phase, dtype=np.int32)
-    check(lib().ohgpu_src_design(rate_in, rate_out, taps_per_phase, beta, f_pass, coef.ctypes.data_as(C.c_void_p),
-                                 coef.size, C.byref(L_), C.byref(M_)))
+    check(lib().ohgpu_src_design(rate_in, rate_out, taps_per_phase, beta, f_pass, _ptr(coef), coef.size, C.byref(L_), C.byref(M_)))
     return L_.value, M_.value, coef
 
 
@@ -646,8 +733,7 @@ def src_pull_design(rate_in, rate_out, taps_per_phase=32, phases_log2=8, beta=8.
     """The pulled resampler's Q28 table, shape (2^phases_log2 + 1, taps_per_phase) (ohgpu_src_pull_design; host only)."""
     rows = (1 << phases_log2) + 1 if 0 <= phases_log2 <= 16 else 1
     coef = np.zeros(rows * taps_per_phase, dtype=np.int32)
-    check(lib().ohgpu_src_pull_design(rate_in, rate_out, taps_per_phase, phases_log2, beta, f_pass, max_pull,
-                                      coef.ctypes.data_as(C.c_void_p), coef.size))
+    check(lib().ohgpu_src_pull_design(rate_in, rate_out, taps_per_phase, phases_log2, beta, f_pass, max_pull, _ptr(coef, keep=True), coef.size))
     return coef.reshape(rows, taps_per_phase)
 
 
@@ -677,8 +763,7 @@ def dsd_pcm_design(dsd_rate, pcm_rate, taps_per_output=16, beta=14.0, f_pass=200
     D = C.c_uint32(0)
     check(lib().ohgpu_dsd_pcm_design(dsd_rate, pcm_rate, taps_per_output, beta, f_pass, gain, None, 0, C.byref(D)))
     coef = np.zeros(D.value * taps_per_output, dtype=np.int32)
-    check(lib().ohgpu_dsd_pcm_design(dsd_rate, pcm_rate, taps_per_output, beta, f_pass, gain, coef.ctypes.data_as(C.c_void_p),
-                                     coef.size, C.byref(D)))
+    check(lib().ohgpu_dsd_pcm_design(dsd_rate, pcm_rate, taps_per_output, beta, f_pass, gain, _ptr(coef), coef.size, C.byref(D)))
     return D.value, coef
 
 
@@ -691,9 +776,8 @@ def dsd_pcm_window(out_frame0, n_frames, decimation, taps_per_output):
 
 def dsd_pcm_batch_check(decimation, taps_per_output, descs, src_arena_bytes, dst_arena_bytes):
     """The validation of ctx.dsd_pcm_batch without a device (ohgpu_dsd_pcm_batch_check): OhGpuError on a bad descriptor."""
-    d = np.ascontiguousarray(descs)
-    assert d.dtype == DSD_PCM_MSG_DESC
-    check(lib().ohgpu_dsd_pcm_batch_check(decimation, taps_per_output, d.ctypes.data_as(C.c_void_p), d.size, src_arena_bytes, dst_arena_bytes))
+    d = _typed(descs, DSD_PCM_MSG_DESC)
+    check(lib().ohgpu_dsd_pcm_batch_check(decimation, taps_per_output, _ptr(d), d.size, src_arena_bytes, dst_arena_bytes))
 
 
 def flac_streaminfo(stream):
@@ -701,81 +785,62 @@ def flac_streaminfo(stream):
     buf = np.frombuffer(bytes(stream), dtype=np.uint8)
     info = np.zeros(1, dtype=FLAC_STREAMINFO)
     off = C.c_uint64(0)
-    check(lib().ohgpu_flac_streaminfo(buf.ctypes.data_as(C.c_void_p), buf.size, info.ctypes.data_as(C.c_void_p), C.byref(off)))
+    check(lib().ohgpu_flac_streaminfo(_ptr(buf, keep=True), buf.size, _ptr(info), C.byref(off)))
     i = info[0]
     return ({k: int(i[k]) for k in ("min_blocksize", "max_blocksize", "sample_rate", "channels", "bits", "total_samples",
                                     "min_framesize", "max_framesize")} | {"md5": bytes(i["md5"])}, int(off.value))
+
+
+def flac_batch_check(descs, src_arena_bytes, dst_arena_bytes):
+    """The validation of ctx.flac_batch without a device (ohgpu_flac_batch_check): OhGpuError on a bad descriptor."""
+    d = _typed(descs, FLAC_STREAM_DESC)
+    check(lib().ohgpu_flac_batch_check(_ptr(d), d.size, src_arena_bytes, dst_arena_bytes))
 
 
 def alac_config_parse(cookie):
     """The stream configuration (ALAC_CONFIG, one record) of a magic cookie, atom wrappers and all (ohgpu_alac_config_parse; host only)."""
     buf = np.frombuffer(bytes(cookie), dtype=np.uint8)
     cfg = np.zeros(1, dtype=ALAC_CONFIG)
-    check(lib().ohgpu_alac_config_parse(buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size, cfg.ctypes.data_as(C.c_void_p)))
+    check(lib().ohgpu_alac_config_parse(_ptr(buf), buf.size, _ptr(cfg)))
     return cfg[0]
-
-
-def _alac_tables(descs, packets):
-    d, p = np.ascontiguousarray(descs), np.ascontiguousarray(packets)
-    assert d.dtype == ALAC_STREAM_DESC and p.dtype == ALAC_PACKET
-    return d, p
 
 
 def alac_batch_check(descs, packets, src_arena_bytes, dst_arena_bytes):
     """The validation of ctx.alac_batch without a device (ohgpu_alac_batch_check): OhGpuError on a bad descriptor."""
-    d, p = _alac_tables(descs, packets)
-    check(lib().ohgpu_alac_batch_check(d.ctypes.data_as(C.c_void_p), d.size, p.ctypes.data_as(C.c_void_p), p.size, src_arena_bytes, dst_arena_bytes))
+    d, p = _typed(descs, ALAC_STREAM_DESC), _typed(packets, ALAC_PACKET)
+    check(lib().ohgpu_alac_batch_check(_ptr(d), d.size, _ptr(p), p.size, src_arena_bytes, dst_arena_bytes))
 
 
 def raop_fmtp_parse(fmtp):
     """The stream configuration (ALAC_CONFIG, one record) of an SDP fmtp string (ohgpu_raop_fmtp_parse; host only)."""
-    raw = fmtp.encode("ascii") if isinstance(fmtp, str) else bytes(fmtp)
-    cfg = np.zeros(1, dtype=ALAC_CONFIG)
-    check(lib().ohgpu_raop_fmtp_parse(raw, len(raw), cfg.ctypes.data_as(C.c_void_p)))
-    return cfg[0]
+    return _head(lib().ohgpu_raop_fmtp_parse, fmtp.encode("ascii") if isinstance(fmtp, str) else fmtp, ALAC_CONFIG)
 
 
-def _ohm_rx_tables(streams, datagrams):
-    s, g = np.ascontiguousarray(streams), np.ascontiguousarray(datagrams)
-    assert s.dtype == OHM_RX_STREAM and g.dtype == OHM_RX_DATAGRAM
-    return s, g
-
-
-def _ptr_or_none(a):
-    return a.ctypes.data_as(C.c_void_p) if a.size else None
+def raop_batch_check(descs, packets, src_arena_bytes, dst_arena_bytes):
+    """The validation of ctx.raop_batch without a device (ohgpu_raop_batch_check): OhGpuError on a bad descriptor."""
+    d, p = _typed(descs, RAOP_STREAM_DESC), _typed(packets, ALAC_PACKET)
+    check(lib().ohgpu_raop_batch_check(_ptr(d), d.size, _ptr(p), p.size, src_arena_bytes, dst_arena_bytes))
 
 
 def ohm_rx_batch_check(streams, datagrams, src_arena_bytes, dst_arena_bytes):
     """The validation of ctx.ohm_rx_batch without a device (ohgpu_ohm_rx_batch_check): OhGpuError on a bad table."""
-    s, g = _ohm_rx_tables(streams, datagrams)
-    check(lib().ohgpu_ohm_rx_batch_check(_ptr_or_none(s), s.size, _ptr_or_none(g), g.size, src_arena_bytes, dst_arena_bytes))
-
-
-def _raop_rx_tables(streams, datagrams):
-    s, g = np.ascontiguousarray(streams), np.ascontiguousarray(datagrams)
-    assert s.dtype == RAOP_RX_STREAM and g.dtype == RAOP_RX_DATAGRAM
-    return s, g
+    s, g = _typed(streams, OHM_RX_STREAM), _typed(datagrams, OHM_RX_DATAGRAM)
+    check(lib().ohgpu_ohm_rx_batch_check(_ptr(s), s.size, _ptr(g), g.size, src_arena_bytes, dst_arena_bytes))
 
 
 def raop_rx_batch_check(streams, datagrams, src_arena_bytes):
     """The validation of ctx.raop_rx_batch without a device (ohgpu_raop_rx_batch_check): OhGpuError on a bad table."""
-    s, g = _raop_rx_tables(streams, datagrams)
-    check(lib().ohgpu_raop_rx_batch_check(_ptr_or_none(s), s.size, _ptr_or_none(g), g.size, src_arena_bytes))
-
-
-def _typed(descs, dtype):
-    d = np.ascontiguousarray(descs)
-    assert d.dtype == dtype
-    return d
+    s, g = _typed(streams, RAOP_RX_STREAM), _typed(datagrams, RAOP_RX_DATAGRAM)
+    check(lib().ohgpu_raop_rx_batch_check(_ptr(s), s.size, _ptr(g), g.size, src_arena_bytes))
 
 
 def vorbis_setup_parse(id_packet, setup_packet):
     """The setup image of a stream's identification and setup header packets (ohgpu_vorbis_setup_parse; host only): (image as uint8, info)."""
     a, b = bytes(id_packet), bytes(setup_packet)
     info = np.zeros(1, dtype=VORBIS_INFO)
-    check(lib().ohgpu_vorbis_setup_parse(a, len(a), b, len(b), None, 0, info.ctypes.data))
+    check(lib().ohgpu_vorbis_setup_parse(a, len(a), b, len(b), None, 0, _ptr(info)))
     image = np.zeros(int(info["image_bytes"][0]), dtype=np.uint8)
-    check(lib().ohgpu_vorbis_setup_parse(a, len(a), b, len(b), image.ctypes.data, image.size, info.ctypes.data))
+    check(lib().ohgpu_vorbis_setup_parse(a, len(a), b, len(b), _ptr(image), image.size, _ptr(info)))
     return image, info[0]
 
 
@@ -785,9 +850,9 @@ def vorbis_head(data):
     raw = bytes(data)
     info = np.zeros(1, dtype=VORBIS_INFO)
     serial, seg, seq, off = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
-    check(lib().ohgpu_vorbis_head(raw, len(raw), None, 0, info.ctypes.data, C.byref(serial), C.byref(off), C.byref(seg), C.byref(seq)))
+    check(lib().ohgpu_vorbis_head(raw, len(raw), None, 0, _ptr(info), C.byref(serial), C.byref(off), C.byref(seg), C.byref(seq)))
     image = np.zeros(int(info["image_bytes"][0]), dtype=np.uint8)
-    check(lib().ohgpu_vorbis_head(raw, len(raw), image.ctypes.data, image.size, info.ctypes.data, C.byref(serial), C.byref(off), C.byref(seg), C.byref(seq)))
+    check(lib().ohgpu_vorbis_head(raw, len(raw), _ptr(image), image.size, _ptr(info), C.byref(serial), C.byref(off), C.byref(seg), C.byref(seq)))
     return dict(image=image, info=info[0], serial=int(serial.value), page_offset=int(off.value), segment=int(seg.value), seq=int(seq.value))
 
 
@@ -795,32 +860,26 @@ def vorbis_codewords(lengths):
     """The codewords of a list of lengths, 0 for an unused entry (ohgpu_vorbis_codewords; host only)."""
     l = np.ascontiguousarray(lengths, dtype=np.uint8)
     out = np.zeros(l.size, dtype=np.uint32)
-    check(lib().ohgpu_vorbis_codewords(_ptr_or_none(l), l.size, _ptr_or_none(out)))
+    check(lib().ohgpu_vorbis_codewords(_ptr(l), l.size, _ptr(out)))
     return out
-
-
-def _vorbis_tables(descs, packets, images):
-    d, p, im = np.ascontiguousarray(descs), np.ascontiguousarray(packets), np.ascontiguousarray(images)
-    assert d.dtype == VORBIS_STREAM_DESC and p.dtype == ALAC_PACKET and im.dtype == np.uint8
-    return d, p, im
 
 
 def vorbis_batch_check(descs, packets, images, src_arena_bytes, dst_arena_bytes):
     """The validation of ctx.vorbis_batch without a device (ohgpu_vorbis_batch_check): OhGpuError on a bad descriptor."""
-    d, p, im = _vorbis_tables(descs, packets, images)
-    check(lib().ohgpu_vorbis_batch_check(_ptr_or_none(d), d.size, _ptr_or_none(p), p.size, _ptr_or_none(im), im.size, src_arena_bytes, dst_arena_bytes))
+    d, p, im = _typed(descs, VORBIS_STREAM_DESC), _typed(packets, ALAC_PACKET), _typed(images, np.uint8)
+    check(lib().ohgpu_vorbis_batch_check(_ptr(d), d.size, _ptr(p), p.size, _ptr(im), im.size, src_arena_bytes, dst_arena_bytes))
 
 
 def ts_batch_check(descs, n_pes, src_arena_bytes, dst_arena_bytes):
     """The validation of ctx.ts_batch without a device (ohgpu_ts_batch_check): OhGpuError on a bad descriptor."""
     d = _typed(descs, TS_STREAM_DESC)
-    check(lib().ohgpu_ts_batch_check(_ptr_or_none(d), d.size, n_pes, src_arena_bytes, dst_arena_bytes))
+    check(lib().ohgpu_ts_batch_check(_ptr(d), d.size, n_pes, src_arena_bytes, dst_arena_bytes))
 
 
 def adts_batch_check(descs, n_frames, src_arena_bytes):
     """The validation of ctx.adts_batch without a device (ohgpu_adts_batch_check)."""
     d = _typed(descs, ADTS_STREAM_DESC)
-    check(lib().ohgpu_adts_batch_check(_ptr_or_none(d), d.size, n_frames, src_arena_bytes))
+    check(lib().ohgpu_adts_batch_check(_ptr(d), d.size, n_frames, src_arena_bytes))
 
 
 def ts_crc(data):
@@ -832,7 +891,7 @@ def ts_crc(data):
 def adts_header(data):
     """One ADTS header (ohgpu_adts_header; host only): an ADTS_FRAME record, or None where the bytes begin with no valid header."""
     raw, out = bytes(data), np.zeros(1, dtype=ADTS_FRAME)
-    return out[0] if lib().ohgpu_adts_header(raw, len(raw), out.ctypes.data_as(C.c_void_p)) == OK else None
+    return out[0] if lib().ohgpu_adts_header(raw, len(raw), _ptr(out)) == OK else None
 
 
 def id3v2_skip(data):
@@ -841,16 +900,10 @@ def id3v2_skip(data):
     return int(lib().ohgpu_id3v2_skip(raw, len(raw)))
 
 
-def _ogg_descs(descs):
-    d = np.ascontiguousarray(descs)
-    assert d.dtype == OGG_STREAM_DESC
-    return d
-
-
 def ogg_batch_check(descs, n_packets, src_arena_bytes, dst_arena_bytes):
     """The validation of ctx.ogg_batch without a device (ohgpu_ogg_batch_check): OhGpuError on a bad descriptor."""
-    d = _ogg_descs(descs)
-    check(lib().ohgpu_ogg_batch_check(_ptr_or_none(d), d.size, n_packets, src_arena_bytes, dst_arena_bytes))
+    d = _typed(descs, OGG_STREAM_DESC)
+    check(lib().ohgpu_ogg_batch_check(_ptr(d), d.size, n_packets, src_arena_bytes, dst_arena_bytes))
 
 
 def ogg_crc(data):
@@ -865,35 +918,22 @@ def ogg_flac_head(data):
     raw = bytes(data)
     info = np.zeros(1, dtype=FLAC_STREAMINFO)
     serial, seg, seq, off = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
-    check(lib().ohgpu_ogg_flac_head(raw, len(raw), info.ctypes.data_as(C.c_void_p), C.byref(serial), C.byref(off), C.byref(seg), C.byref(seq)))
+    check(lib().ohgpu_ogg_flac_head(raw, len(raw), _ptr(info), C.byref(serial), C.byref(off), C.byref(seg), C.byref(seq)))
     return info[0], int(serial.value), int(off.value), int(seg.value), int(seq.value)
-
-
-def _mp4_descs(descs):
-    d = np.ascontiguousarray(descs)
-    assert d.dtype == MP4_STREAM_DESC
-    return d
 
 
 def mp4_batch_check(descs, n_packets, src_arena_bytes):
     """The validation of ctx.mp4_batch without a device (ohgpu_mp4_batch_check): OhGpuError on a bad descriptor."""
-    d = _mp4_descs(descs)
-    check(lib().ohgpu_mp4_batch_check(_ptr_or_none(d), d.size, n_packets, src_arena_bytes))
+    d = _typed(descs, MP4_STREAM_DESC)
+    check(lib().ohgpu_mp4_batch_check(_ptr(d), d.size, n_packets, src_arena_bytes))
 
 
 def mp4_seek(samples, frame):
     """The row of a sample table (MP4_SAMPLE) that holds audio frame `frame` (ohgpu_mp4_seek; host only): (index, its first frame)."""
-    t = np.ascontiguousarray(samples)
-    assert t.dtype == MP4_SAMPLE
+    t = _typed(samples, MP4_SAMPLE)
     index, first = C.c_uint64(0), C.c_uint64(0)
-    check(lib().ohgpu_mp4_seek(_ptr_or_none(t), t.size, frame, C.byref(index), C.byref(first)))
+    check(lib().ohgpu_mp4_seek(_ptr(t), t.size, frame, C.byref(index), C.byref(first)))
     return int(index.value), int(first.value)
-
-
-def _iff_descs(descs):
-    d = np.ascontiguousarray(descs)
-    assert d.dtype == IFF_STREAM_DESC
-    return d
 
 
 # The three fragmented MPEG-4 families behind one implementation (Context._frag_* has the device calls): a family's descriptor and
@@ -901,34 +941,17 @@ def _iff_descs(descs):
 _FRAG = {"mp4f": (MP4F_STREAM_DESC, MP4F_STREAM_RESULT), "cenc": (CENC_STREAM_DESC, CENC_STREAM_RESULT), "cbcs": (CBCS_STREAM_DESC, CBCS_STREAM_RESULT)}
 
 
-def _frag_call(fam, name, *args):
-    check(getattr(lib(), f"ohgpu_{fam}_{name}")(*args))
-
-
-def _frag_descs(fam, descs):
-    d = np.ascontiguousarray(descs)
-    assert d.dtype == _FRAG[fam][0]
-    return d
+def _frag_fn(fam, name):
+    return getattr(lib(), f"ohgpu_{fam}_{name}")
 
 
 def _frag_batch_check(fam, descs, counts, src_arena_bytes, dst_arena_bytes):
-    d = _frag_descs(fam, descs)
-    _frag_call(fam, "batch_check", _ptr_or_none(d), d.size, *counts, src_arena_bytes, dst_arena_bytes)
+    d = _typed(descs, _FRAG[fam][0])
+    check(_frag_fn(fam, "batch_check")(_ptr(d), d.size, *counts, src_arena_bytes, dst_arena_bytes))
 
 
-def _frag_head(fam, data):
-    raw = bytes(data)
-    res = np.zeros(1, dtype=_FRAG[fam][1])
-    _frag_call(fam, "head", raw, len(raw), res.ctypes.data_as(C.c_void_p))
-    return res[0]
-
-
-def _frag_tables(fam, n, n_packets, n_runs):
+def _frag_zeros(fam, n, n_packets, n_runs):
     return np.zeros(n, dtype=_FRAG[fam][1]), np.zeros(n_runs, dtype=MP4F_RUN), np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
-
-
-def _mp4f_descs(descs):
-    return _frag_descs("mp4f", descs)
 
 
 def mp4f_batch_check(descs, n_packets, n_runs, src_arena_bytes, dst_arena_bytes):
@@ -938,11 +961,7 @@ def mp4f_batch_check(descs, n_packets, n_runs, src_arena_bytes, dst_arena_bytes)
 
 def mp4f_head(data):
     """The walk of a fragmented stream up to the end of moov (ohgpu_mp4f_head; host only): an MP4F_STREAM_RESULT record."""
-    return _frag_head("mp4f", data)
-
-
-def _cenc_descs(descs):
-    return _frag_descs("cenc", descs)
+    return _head(lib().ohgpu_mp4f_head, data, MP4F_STREAM_RESULT)
 
 
 def cenc_batch_check(descs, n_packets, n_runs, src_arena_bytes, dst_arena_bytes):
@@ -953,11 +972,7 @@ def cenc_batch_check(descs, n_packets, n_runs, src_arena_bytes, dst_arena_bytes)
 def cenc_head(data):
     """The walk of a protected or clear fragmented stream up to the end of moov (ohgpu_cenc_head; host only, no key): a CENC_STREAM_RESULT
     record whose is_protected and kid say which key to ask for."""
-    return _frag_head("cenc", data)
-
-
-def _cbcs_descs(descs):
-    return _frag_descs("cbcs", descs)
+    return _head(lib().ohgpu_cenc_head, data, CENC_STREAM_RESULT)
 
 
 def cbcs_batch_check(descs, n_packets, n_runs, n_subsamples, src_arena_bytes, dst_arena_bytes):
@@ -968,32 +983,26 @@ def cbcs_batch_check(descs, n_packets, n_runs, n_subsamples, src_arena_bytes, ds
 def cbcs_head(data):
     """The walk of a `cenc`- or `cbcs`-protected or clear fragmented stream up to the end of moov (ohgpu_cbcs_head; host only, no key): a
     CBCS_STREAM_RESULT record."""
-    return _frag_head("cbcs", data)
+    return _head(lib().ohgpu_cbcs_head, data, CBCS_STREAM_RESULT)
 
 
 def iff_batch_check(descs, src_arena_bytes, dst_arena_bytes):
     """The validation of ctx.iff_batch without a device (ohgpu_iff_batch_check): OhGpuError on a bad descriptor."""
-    d = _iff_descs(descs)
-    check(lib().ohgpu_iff_batch_check(_ptr_or_none(d), d.size, src_arena_bytes, dst_arena_bytes))
-
-
-def _dsd_file_descs(descs):
-    d = np.ascontiguousarray(descs)
-    assert d.dtype == DSD_FILE_STREAM_DESC
-    return d
+    d = _typed(descs, IFF_STREAM_DESC)
+    check(lib().ohgpu_iff_batch_check(_ptr(d), d.size, src_arena_bytes, dst_arena_bytes))
 
 
 def dsd_file_batch_check(descs, src_arena_bytes, dst_arena_bytes):
     """The validation of ctx.dsd_file_batch without a device (ohgpu_dsd_file_batch_check): OhGpuError on a bad descriptor."""
-    d = _dsd_file_descs(descs)
-    check(lib().ohgpu_dsd_file_batch_check(_ptr_or_none(d), d.size, src_arena_bytes, dst_arena_bytes))
+    d = _typed(descs, DSD_FILE_STREAM_DESC)
+    check(lib().ohgpu_dsd_file_batch_check(_ptr(d), d.size, src_arena_bytes, dst_arena_bytes))
 
 
 def dsd_file_head(data, sample_block_words, pad_bytes_per_chunk):
     """The walk over a file's bytes on the host (ohgpu_dsd_file_head): one DSD_FILE_STREAM_RESULT record."""
     raw = np.frombuffer(bytes(data), dtype=np.uint8)
     res = np.zeros(1, dtype=DSD_FILE_STREAM_RESULT)
-    check(lib().ohgpu_dsd_file_head(_ptr_or_none(raw), raw.size, sample_block_words, pad_bytes_per_chunk, _ptr_or_none(res)))
+    check(lib().ohgpu_dsd_file_head(_ptr(raw), raw.size, sample_block_words, pad_bytes_per_chunk, _ptr(res)))
     return res[0]
 
 
@@ -1002,25 +1011,6 @@ def dsd_file_seek(kind, sample):
     first, rounded = C.c_uint64(0), C.c_uint64(0)
     check(lib().ohgpu_dsd_file_seek(kind, sample, C.byref(first), C.byref(rounded)))
     return int(first.value), int(rounded.value)
-
-
-def _raop_tables(descs, packets):
-    d, p = np.ascontiguousarray(descs), np.ascontiguousarray(packets)
-    assert d.dtype == RAOP_STREAM_DESC and p.dtype == ALAC_PACKET
-    return d, p
-
-
-def raop_batch_check(descs, packets, src_arena_bytes, dst_arena_bytes):
-    """The validation of ctx.raop_batch without a device (ohgpu_raop_batch_check): OhGpuError on a bad descriptor."""
-    d, p = _raop_tables(descs, packets)
-    check(lib().ohgpu_raop_batch_check(d.ctypes.data_as(C.c_void_p), d.size, p.ctypes.data_as(C.c_void_p), p.size, src_arena_bytes, dst_arena_bytes))
-
-
-def flac_batch_check(descs, src_arena_bytes, dst_arena_bytes):
-    """The validation of ctx.flac_batch without a device (ohgpu_flac_batch_check): OhGpuError on a bad descriptor."""
-    d = np.ascontiguousarray(descs)
-    assert d.dtype == FLAC_STREAM_DESC
-    check(lib().ohgpu_flac_batch_check(d.ctypes.data_as(C.c_void_p), d.size, src_arena_bytes, dst_arena_bytes))
 
 
 class Context:
@@ -1053,25 +1043,20 @@ class Context:
 
     # ---- memory
     def malloc(self, nbytes):
-        p = C.c_void_p()
-        check(lib().ohgpu_malloc(self._h, nbytes, C.byref(p)))
-        return p
+        return _create(lib().ohgpu_malloc, self._h, nbytes)
 
     def free(self, dptr):
         check(lib().ohgpu_free(self._h, dptr))
 
     def stream_create(self):
-        p = C.c_void_p()
-        check(lib().ohgpu_stream_create(self._h, C.byref(p)))
-        return p
+        return _create(lib().ohgpu_stream_create, self._h)
 
     def stream_destroy(self, stream):
         check(lib().ohgpu_stream_destroy(self._h, stream))
 
     def malloc_host(self, nbytes):
         """Pinned host memory as a uint8 array (free with free_host(array))."""
-        p = C.c_void_p()
-        check(lib().ohgpu_malloc_host(self._h, max(nbytes, 1), C.byref(p)))
+        p = _create(lib().ohgpu_malloc_host, self._h, max(nbytes, 1))
         a = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(max(nbytes, 1),))[:nbytes]
         return a
 
@@ -1079,21 +1064,21 @@ class Context:
         check(lib().ohgpu_free_host(self._h, C.c_void_p(array.ctypes.data)))
 
     def copy_h2d(self, dptr, array, stream=None):
-        check(lib().ohgpu_memcpy_h2d(self._h, dptr, array.ctypes.data_as(C.c_void_p), array.nbytes, stream))
+        check(lib().ohgpu_memcpy_h2d(self._h, dptr, _ptr(array), array.nbytes, stream))
 
     def copy_d2h(self, array, dptr, stream=None):
-        check(lib().ohgpu_memcpy_d2h(self._h, array.ctypes.data_as(C.c_void_p), dptr, array.nbytes, stream))
+        check(lib().ohgpu_memcpy_d2h(self._h, _ptr(array), dptr, array.nbytes, stream))
 
     def upload(self, array, stream=None):
         a = np.ascontiguousarray(array)
         p = self.malloc(max(a.nbytes, 1))
-        check(lib().ohgpu_memcpy_h2d(self._h, p, a.ctypes.data_as(C.c_void_p), a.nbytes, stream))
+        check(lib().ohgpu_memcpy_h2d(self._h, p, _ptr(a), a.nbytes, stream))
         self.sync(stream)
         return p
 
     def download(self, dptr, nbytes, stream=None):
         out = np.empty(nbytes, dtype=np.uint8)
-        check(lib().ohgpu_memcpy_d2h(self._h, out.ctypes.data_as(C.c_void_p), dptr, nbytes, stream))
+        check(lib().ohgpu_memcpy_d2h(self._h, _ptr(out), dptr, nbytes, stream))
         self.sync(stream)
         return out
 
@@ -1108,9 +1093,7 @@ class Context:
 
     # ---- events (HIP events on the launch stream)
     def event(self):
-        e = C.c_void_p()
-        check(lib().ohgpu_event_create(self._h, C.byref(e)))
-        return e
+        return _create(lib().ohgpu_event_create, self._h)
 
     def event_destroy(self, event):
         check(lib().ohgpu_event_destroy(self._h, event))
@@ -1128,12 +1111,8 @@ class Context:
 
     # ---- batches
     def pcm_batch(self, descs, src_arena_bytes, dst_arena_bytes):
-        d = np.ascontiguousarray(descs)
-        assert d.dtype == MSG_DESC
-        b = C.c_void_p()
-        check(lib().ohgpu_pcm_batch_create(self._h, d.ctypes.data_as(C.c_void_p), d.size, src_arena_bytes,
-                                           dst_arena_bytes, C.byref(b)))
-        return b
+        d = _typed(descs, MSG_DESC)
+        return _create(lib().ohgpu_pcm_batch_create, self._h, _ptr(d), d.size, src_arena_bytes, dst_arena_bytes)
 
     def pcm_run(self, batch, d_src, d_dst, stream=None):
         check(lib().ohgpu_pcm_batch_run(self._h, batch, d_src, d_dst, stream))
@@ -1150,7 +1129,7 @@ class Context:
     def batch_paths(self, batch):
         """Which kernels a pcm, Songcast frame or fmt batch was planned onto (ohgpu_batch_paths), as a dict of counts."""
         v = np.zeros(1, dtype=BATCH_PATHS)
-        check(lib().ohgpu_batch_paths_info(batch, v.ctypes.data_as(C.c_void_p)))
+        check(lib().ohgpu_batch_paths_info(batch, _ptr(v)))
         out = {k: int(v[k][0]) for k in BATCH_PATHS.names if k != "reserved"}
         out["alac_route"] = int(v["reserved"][0][0])        # (the header's union: the last word)
         out["mp4_route"] = out["alac_route"]                 # (the same word: a batch is of one kind)
@@ -1161,92 +1140,61 @@ class Context:
         return out
 
     def pcm_process_host(self, descs, src, dst):
-        d = np.ascontiguousarray(descs)
-        assert d.dtype == MSG_DESC
-        check(lib().ohgpu_pcm_process_host(self._h, d.ctypes.data_as(C.c_void_p), d.size,
-                                           src.ctypes.data_as(C.c_void_p), src.nbytes,
-                                           dst.ctypes.data_as(C.c_void_p), dst.nbytes))
+        d = _typed(descs, MSG_DESC)
+        _process_host(lib().ohgpu_pcm_process_host, self._h, (_ptr(d), d.size), src, dst, ())
         return dst
 
     def fmt_batch(self, descs, src_arena_bytes, dst_arena_bytes):
-        d = np.ascontiguousarray(descs)
-        assert d.dtype == FMT_DESC
-        b = C.c_void_p()
-        check(lib().ohgpu_fmt_batch_create(self._h, d.ctypes.data_as(C.c_void_p), d.size, src_arena_bytes,
-                                           dst_arena_bytes, C.byref(b)))
-        return b
+        d = _typed(descs, FMT_DESC)
+        return _create(lib().ohgpu_fmt_batch_create, self._h, _ptr(d), d.size, src_arena_bytes, dst_arena_bytes)
 
     def fmt_run(self, batch, d_src, d_dst, stream=None):
         check(lib().ohgpu_fmt_batch_run(self._h, batch, d_src, d_dst, stream))
 
     def dsd_batch(self, descs, src_arena_bytes, dst_arena_bytes):
-        d = np.ascontiguousarray(descs)
-        assert d.dtype == DSD_DESC
-        b = C.c_void_p()
-        check(lib().ohgpu_dsd_batch_create(self._h, d.ctypes.data_as(C.c_void_p), d.size, src_arena_bytes,
-                                           dst_arena_bytes, C.byref(b)))
-        return b
+        d = _typed(descs, DSD_DESC)
+        return _create(lib().ohgpu_dsd_batch_create, self._h, _ptr(d), d.size, src_arena_bytes, dst_arena_bytes)
 
     def dsd_run(self, batch, d_src, d_dst, stream=None):
         check(lib().ohgpu_dsd_batch_run(self._h, batch, d_src, d_dst, stream))
 
     def dsd_batch_paths(self, batch):
         """How a DSD batch was planned (ohgpu_dsd_batch_paths): descriptors on the wide path, on the byte path, launches."""
-        v = [C.c_uint32(0) for _ in range(3)]
-        check(lib().ohgpu_dsd_batch_paths(batch, *[C.byref(x) for x in v]))
-        return dict(zip(("wide_descs", "generic_descs", "launches"), (int(x.value) for x in v)))
+        return _paths(lib().ohgpu_dsd_batch_paths, batch, "wide_descs", "generic_descs", "launches")
 
     def dsd_process_host(self, descs, src, dst):
-        d = np.ascontiguousarray(descs)
-        assert d.dtype == DSD_DESC
-        check(lib().ohgpu_dsd_process_host(self._h, d.ctypes.data_as(C.c_void_p), d.size,
-                                           src.ctypes.data_as(C.c_void_p), src.nbytes,
-                                           dst.ctypes.data_as(C.c_void_p), dst.nbytes))
+        d = _typed(descs, DSD_DESC)
+        _process_host(lib().ohgpu_dsd_process_host, self._h, (_ptr(d), d.size), src, dst, ())
         return dst
 
     # ---- DSD -> PCM (DESIGN.md 4c)
     def dsd_pcm_create(self, decimation, taps_per_output, coef_q28):
         c = np.ascontiguousarray(coef_q28, dtype=np.int32)
         assert c.size == decimation * taps_per_output
-        f = C.c_void_p()
-        check(lib().ohgpu_dsd_pcm_create(self._h, decimation, taps_per_output, c.ctypes.data_as(C.c_void_p), C.byref(f)))
-        return f
+        return _create(lib().ohgpu_dsd_pcm_create, self._h, decimation, taps_per_output, _ptr(c, keep=True))
 
     def dsd_pcm_destroy(self, filt):
         check(lib().ohgpu_dsd_pcm_destroy(self._h, filt))
 
     def dsd_pcm_batch(self, filt, descs, src_arena_bytes, dst_arena_bytes):
-        d = np.ascontiguousarray(descs)
-        assert d.dtype == DSD_PCM_MSG_DESC
-        b = C.c_void_p()
-        check(lib().ohgpu_dsd_pcm_batch_create(self._h, filt, d.ctypes.data_as(C.c_void_p), d.size, src_arena_bytes,
-                                               dst_arena_bytes, C.byref(b)))
-        return b
+        d = _typed(descs, DSD_PCM_MSG_DESC)
+        return _create(lib().ohgpu_dsd_pcm_batch_create, self._h, filt, _ptr(d), d.size, src_arena_bytes, dst_arena_bytes)
 
     def dsd_pcm_run(self, batch, d_src, d_dst, stream=None):
         check(lib().ohgpu_dsd_pcm_batch_run(self._h, batch, d_src, d_dst, stream))
 
     def dsd_pcm_batch_paths(self, batch):
         """How a DSD -> PCM batch was planned (ohgpu_dsd_pcm_batch_paths): messages on the fast route, on the plain route, launches."""
-        v = [C.c_uint32(0) for _ in range(3)]
-        check(lib().ohgpu_dsd_pcm_batch_paths(batch, *[C.byref(x) for x in v]))
-        return dict(zip(("fast_descs", "plain_descs", "launches"), (int(x.value) for x in v)))
+        return _paths(lib().ohgpu_dsd_pcm_batch_paths, batch, "fast_descs", "plain_descs", "launches")
 
     def dsd_pcm_process_host(self, filt, descs, src, dst):
-        d = np.ascontiguousarray(descs)
-        assert d.dtype == DSD_PCM_MSG_DESC
-        check(lib().ohgpu_dsd_pcm_process_host(self._h, filt, d.ctypes.data_as(C.c_void_p), d.size,
-                                               src.ctypes.data_as(C.c_void_p), src.nbytes,
-                                               dst.ctypes.data_as(C.c_void_p), dst.nbytes))
+        d = _typed(descs, DSD_PCM_MSG_DESC)
+        _process_host(lib().ohgpu_dsd_pcm_process_host, self._h, (filt, _ptr(d), d.size), src, dst, ())
         return dst
 
     def flac_batch(self, descs, src_arena_bytes, dst_arena_bytes):
-        d = np.ascontiguousarray(descs)
-        assert d.dtype == FLAC_STREAM_DESC
-        b = C.c_void_p()
-        check(lib().ohgpu_flac_batch_create(self._h, d.ctypes.data_as(C.c_void_p), d.size, src_arena_bytes,
-                                            dst_arena_bytes, C.byref(b)))
-        return b
+        d = _typed(descs, FLAC_STREAM_DESC)
+        return _create(lib().ohgpu_flac_batch_create, self._h, _ptr(d), d.size, src_arena_bytes, dst_arena_bytes)
 
     def flac_run(self, batch, d_src, d_dst, stream=None):
         """Scan, probe, chain, restore (ohgpu_flac_batch_run): synchronises with the host once, after the scan."""
@@ -1254,40 +1202,29 @@ class Context:
 
     def flac_results(self, batch, n):
         """The last run's FLAC_STREAM_RESULT per stream (waits for the run)."""
-        res = np.zeros(n, dtype=FLAC_STREAM_RESULT)
-        check(lib().ohgpu_flac_batch_results(self._h, batch, res.ctypes.data_as(C.c_void_p), n))
-        return res
+        return _fetch(lib().ohgpu_flac_batch_results, self._h, batch, FLAC_STREAM_RESULT, n)
 
     def flac_frames(self, batch):
         """The last run's delivered frames (FLAC_FRAME), by stream and in stream order."""
         n = C.c_size_t(0)
         check(lib().ohgpu_flac_batch_frames(self._h, batch, None, 0, C.byref(n)))
         out = np.zeros(n.value, dtype=FLAC_FRAME)
-        check(lib().ohgpu_flac_batch_frames(self._h, batch, out.ctypes.data_as(C.c_void_p), out.size, C.byref(n)))
+        check(lib().ohgpu_flac_batch_frames(self._h, batch, _ptr(out), out.size, C.byref(n)))
         return out
 
     def flac_phase_ms(self, batch):
         """The last run's (scan, probe, chain, restore) in milliseconds, from device events."""
-        ms = (C.c_float * 4)()
-        check(lib().ohgpu_flac_batch_phase_ms(self._h, batch, ms))
-        return tuple(float(v) for v in ms)
+        return _phase_ms(lib().ohgpu_flac_batch_phase_ms, self._h, batch, 4)
 
     def flac_process_host(self, descs, src, dst):
         """Host buffers in and out (ohgpu_flac_process_host); returns the results.  Only decoded samples are written to dst."""
-        d = np.ascontiguousarray(descs)
-        assert d.dtype == FLAC_STREAM_DESC
+        d = _typed(descs, FLAC_STREAM_DESC)
         res = np.zeros(d.size, dtype=FLAC_STREAM_RESULT)
-        check(lib().ohgpu_flac_process_host(self._h, d.ctypes.data_as(C.c_void_p), d.size,
-                                            src.ctypes.data_as(C.c_void_p), src.nbytes,
-                                            dst.ctypes.data_as(C.c_void_p), dst.nbytes, res.ctypes.data_as(C.c_void_p), None, 0, None))
-        return res
+        return _process_host(lib().ohgpu_flac_process_host, self._h, (_ptr(d), d.size), src, dst, (res,), tail=(None, 0, None))[0]
 
     def alac_batch(self, descs, packets, src_arena_bytes, dst_arena_bytes):
-        d, p = _alac_tables(descs, packets)
-        b = C.c_void_p()
-        check(lib().ohgpu_alac_batch_create(self._h, d.ctypes.data_as(C.c_void_p), d.size, p.ctypes.data_as(C.c_void_p), p.size,
-                                            src_arena_bytes, dst_arena_bytes, C.byref(b)))
-        return b
+        d, p = _typed(descs, ALAC_STREAM_DESC), _typed(packets, ALAC_PACKET)
+        return _create(lib().ohgpu_alac_batch_create, self._h, _ptr(d), d.size, _ptr(p), p.size, src_arena_bytes, dst_arena_bytes)
 
     def alac_run(self, batch, d_src, d_dst, stream=None):
         """Entropy, predictor, matrix and store (ohgpu_alac_batch_run): queued on the stream, nothing waits for the host."""
@@ -1295,32 +1232,21 @@ class Context:
 
     def alac_results(self, batch, n, n_packets):
         """The last run's (ALAC_STREAM_RESULT per stream, ALAC_PACKET_RESULT per packet); waits for the run."""
-        sres, pres = np.zeros(n, dtype=ALAC_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET_RESULT)
-        check(lib().ohgpu_alac_batch_results(self._h, batch, sres.ctypes.data_as(C.c_void_p) if n else None, n,
-                                             pres.ctypes.data_as(C.c_void_p) if n_packets else None, n_packets))
-        return sres, pres
+        return _fetch_pair(lib().ohgpu_alac_batch_results, self._h, batch, ALAC_STREAM_RESULT, n, ALAC_PACKET_RESULT, n_packets)
 
     def alac_phase_ms(self, batch):
         """The last run's (entropy, predictor, matrix and store) in milliseconds, from device events."""
-        ms = (C.c_float * 3)()
-        check(lib().ohgpu_alac_batch_phase_ms(self._h, batch, ms))
-        return tuple(float(v) for v in ms)
+        return _phase_ms(lib().ohgpu_alac_batch_phase_ms, self._h, batch, 3)
 
     def alac_process_host(self, descs, packets, src, dst):
         """Host buffers in and out (ohgpu_alac_process_host); returns (stream results, packet results).  Only decoded samples are written to dst."""
-        d, p = _alac_tables(descs, packets)
-        sres, pres = np.zeros(d.size, dtype=ALAC_STREAM_RESULT), np.zeros(p.size, dtype=ALAC_PACKET_RESULT)
-        check(lib().ohgpu_alac_process_host(self._h, d.ctypes.data_as(C.c_void_p), d.size, p.ctypes.data_as(C.c_void_p), p.size,
-                                            src.ctypes.data_as(C.c_void_p), src.nbytes, dst.ctypes.data_as(C.c_void_p), dst.nbytes,
-                                            sres.ctypes.data_as(C.c_void_p), pres.ctypes.data_as(C.c_void_p)))
-        return sres, pres
+        d, p = _typed(descs, ALAC_STREAM_DESC), _typed(packets, ALAC_PACKET)
+        out = np.zeros(d.size, dtype=ALAC_STREAM_RESULT), np.zeros(p.size, dtype=ALAC_PACKET_RESULT)
+        return _process_host(lib().ohgpu_alac_process_host, self._h, (_ptr(d), d.size, _ptr(p), p.size), src, dst, out)
 
     def raop_batch(self, descs, packets, src_arena_bytes, dst_arena_bytes):
-        d, p = _raop_tables(descs, packets)
-        b = C.c_void_p()
-        check(lib().ohgpu_raop_batch_create(self._h, d.ctypes.data_as(C.c_void_p), d.size, p.ctypes.data_as(C.c_void_p), p.size,
-                                            src_arena_bytes, dst_arena_bytes, C.byref(b)))
-        return b
+        d, p = _typed(descs, RAOP_STREAM_DESC), _typed(packets, ALAC_PACKET)
+        return _create(lib().ohgpu_raop_batch_create, self._h, _ptr(d), d.size, _ptr(p), p.size, src_arena_bytes, dst_arena_bytes)
 
     def raop_run(self, batch, d_src, d_dst, stream=None):
         """Decrypt, then entropy, predictor, matrix and store (ohgpu_raop_batch_run): queued on the stream; both bases 4-byte aligned."""
@@ -1328,53 +1254,35 @@ class Context:
 
     def raop_results(self, batch, n, n_packets):
         """The last run's (ALAC_STREAM_RESULT per stream, ALAC_PACKET_RESULT per packet); waits for the run."""
-        sres, pres = np.zeros(n, dtype=ALAC_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET_RESULT)
-        check(lib().ohgpu_raop_batch_results(self._h, batch, sres.ctypes.data_as(C.c_void_p) if n else None, n,
-                                             pres.ctypes.data_as(C.c_void_p) if n_packets else None, n_packets))
-        return sres, pres
+        return _fetch_pair(lib().ohgpu_raop_batch_results, self._h, batch, ALAC_STREAM_RESULT, n, ALAC_PACKET_RESULT, n_packets)
 
     def raop_phase_ms(self, batch):
         """The last run's (decrypt, entropy, predictor, matrix and store) in milliseconds, from device events."""
-        ms = (C.c_float * 4)()
-        check(lib().ohgpu_raop_batch_phase_ms(self._h, batch, ms))
-        return tuple(float(v) for v in ms)
+        return _phase_ms(lib().ohgpu_raop_batch_phase_ms, self._h, batch, 4)
 
     def raop_process_host(self, descs, packets, src, dst):
         """Host buffers in and out (ohgpu_raop_process_host); returns (stream results, packet results)."""
-        d, p = _raop_tables(descs, packets)
-        sres, pres = np.zeros(d.size, dtype=ALAC_STREAM_RESULT), np.zeros(p.size, dtype=ALAC_PACKET_RESULT)
-        check(lib().ohgpu_raop_process_host(self._h, d.ctypes.data_as(C.c_void_p), d.size, p.ctypes.data_as(C.c_void_p), p.size,
-                                            src.ctypes.data_as(C.c_void_p), src.nbytes, dst.ctypes.data_as(C.c_void_p), dst.nbytes,
-                                            sres.ctypes.data_as(C.c_void_p), pres.ctypes.data_as(C.c_void_p)))
-        return sres, pres
+        d, p = _typed(descs, RAOP_STREAM_DESC), _typed(packets, ALAC_PACKET)
+        out = np.zeros(d.size, dtype=ALAC_STREAM_RESULT), np.zeros(p.size, dtype=ALAC_PACKET_RESULT)
+        return _process_host(lib().ohgpu_raop_process_host, self._h, (_ptr(d), d.size, _ptr(p), p.size), src, dst, out)
 
     def flywheel_batch(self, descs, src_arena_bytes, dst_arena_bytes):
-        d = np.ascontiguousarray(descs)
-        assert d.dtype == FLYWHEEL_DESC
-        b = C.c_void_p()
-        check(lib().ohgpu_flywheel_batch_create(self._h, d.ctypes.data_as(C.c_void_p), d.size, src_arena_bytes,
-                                                dst_arena_bytes, C.byref(b)))
-        return b
+        d = _typed(descs, FLYWHEEL_DESC)
+        return _create(lib().ohgpu_flywheel_batch_create, self._h, _ptr(d), d.size, src_arena_bytes, dst_arena_bytes)
 
     def flywheel_run(self, batch, d_src, d_dst, stream=None):
         check(lib().ohgpu_flywheel_batch_run(self._h, batch, d_src, d_dst, stream))
 
     def ohm_batch(self, streams, frames, fragments, src_arena_bytes, dst_arena_bytes):
-        st, fr, fg = np.ascontiguousarray(streams), np.ascontiguousarray(frames), np.ascontiguousarray(fragments)
-        assert st.dtype == OHM_STREAM and fr.dtype == OHM_FRAME_DESC and fg.dtype == OHM_FRAGMENT
-        b = C.c_void_p()
-        check(lib().ohgpu_ohm_batch_create(self._h, st.ctypes.data_as(C.c_void_p), st.size, fr.ctypes.data_as(C.c_void_p), fr.size,
-                                           fg.ctypes.data_as(C.c_void_p), fg.size, src_arena_bytes, dst_arena_bytes, C.byref(b)))
-        return b
+        st, fr, fg = _typed(streams, OHM_STREAM), _typed(frames, OHM_FRAME_DESC), _typed(fragments, OHM_FRAGMENT)
+        return _create(lib().ohgpu_ohm_batch_create, self._h, _ptr(st), st.size, _ptr(fr), fr.size, _ptr(fg), fg.size, src_arena_bytes, dst_arena_bytes)
 
     def ohm_run(self, batch, d_src, d_dst, stream=None):
         check(lib().ohgpu_ohm_batch_run(self._h, batch, d_src, d_dst, stream))
 
     def ohm_rx_batch(self, streams, datagrams, src_arena_bytes, dst_arena_bytes):
-        s, g = _ohm_rx_tables(streams, datagrams)
-        b = C.c_void_p()
-        check(lib().ohgpu_ohm_rx_batch_create(self._h, _ptr_or_none(s), s.size, _ptr_or_none(g), g.size, src_arena_bytes, dst_arena_bytes, C.byref(b)))
-        return b
+        s, g = _typed(streams, OHM_RX_STREAM), _typed(datagrams, OHM_RX_DATAGRAM)
+        return _create(lib().ohgpu_ohm_rx_batch_create, self._h, _ptr(s), s.size, _ptr(g), g.size, src_arena_bytes, dst_arena_bytes)
 
     def ohm_rx_run(self, batch, d_src, d_dst, stream=None):
         """Parse, sequence, gather (ohgpu_ohm_rx_batch_run): queued on the stream; d_src 4-byte aligned."""
@@ -1382,29 +1290,21 @@ class Context:
 
     def ohm_rx_results(self, batch, n, n_datagrams):
         """The last run's (OHM_RX_STREAM_RESULT per stream, OHM_RX_RECORD per datagram); waits for the run."""
-        sres, recs = np.zeros(n, dtype=OHM_RX_STREAM_RESULT), np.zeros(n_datagrams, dtype=OHM_RX_RECORD)
-        check(lib().ohgpu_ohm_rx_batch_results(self._h, batch, _ptr_or_none(sres), n, _ptr_or_none(recs), n_datagrams))
-        return sres, recs
+        return _fetch_pair(lib().ohgpu_ohm_rx_batch_results, self._h, batch, OHM_RX_STREAM_RESULT, n, OHM_RX_RECORD, n_datagrams)
 
     def ohm_rx_phase_ms(self, batch):
         """The last run's (parse, sequence, gather) in milliseconds, from device events."""
-        ms = (C.c_float * 3)()
-        check(lib().ohgpu_ohm_rx_batch_phase_ms(self._h, batch, ms))
-        return tuple(float(v) for v in ms)
+        return _phase_ms(lib().ohgpu_ohm_rx_batch_phase_ms, self._h, batch, 3)
 
     def ohm_rx_process_host(self, streams, datagrams, src, dst):
         """Host buffers in and out (ohgpu_ohm_rx_process_host); returns (stream results, records)."""
-        s, g = _ohm_rx_tables(streams, datagrams)
-        sres, recs = np.zeros(s.size, dtype=OHM_RX_STREAM_RESULT), np.zeros(g.size, dtype=OHM_RX_RECORD)
-        check(lib().ohgpu_ohm_rx_process_host(self._h, _ptr_or_none(s), s.size, _ptr_or_none(g), g.size, _ptr_or_none(src), src.nbytes,
-                                              _ptr_or_none(dst), dst.nbytes, _ptr_or_none(sres), _ptr_or_none(recs)))
-        return sres, recs
+        s, g = _typed(streams, OHM_RX_STREAM), _typed(datagrams, OHM_RX_DATAGRAM)
+        out = np.zeros(s.size, dtype=OHM_RX_STREAM_RESULT), np.zeros(g.size, dtype=OHM_RX_RECORD)
+        return _process_host(lib().ohgpu_ohm_rx_process_host, self._h, (_ptr(s), s.size, _ptr(g), g.size), src, dst, out)
 
     def raop_rx_batch(self, streams, datagrams, src_arena_bytes):
-        s, g = _raop_rx_tables(streams, datagrams)
-        b = C.c_void_p()
-        check(lib().ohgpu_raop_rx_batch_create(self._h, _ptr_or_none(s), s.size, _ptr_or_none(g), g.size, src_arena_bytes, C.byref(b)))
-        return b
+        s, g = _typed(streams, RAOP_RX_STREAM), _typed(datagrams, RAOP_RX_DATAGRAM)
+        return _create(lib().ohgpu_raop_rx_batch_create, self._h, _ptr(s), s.size, _ptr(g), g.size, src_arena_bytes)
 
     def raop_rx_run(self, batch, d_src, stream=None):
         """Parse, sequence, table (ohgpu_raop_rx_batch_run): queued on the stream; d_src 4-byte aligned."""
@@ -1412,48 +1312,34 @@ class Context:
 
     def raop_rx_results(self, batch, n, n_datagrams):
         """The last run's (RAOP_RX_STREAM_RESULT per stream, RAOP_RX_RECORD per datagram); waits for the run."""
-        sres, recs = np.zeros(n, dtype=RAOP_RX_STREAM_RESULT), np.zeros(n_datagrams, dtype=RAOP_RX_RECORD)
-        check(lib().ohgpu_raop_rx_batch_results(self._h, batch, _ptr_or_none(sres), n, _ptr_or_none(recs), n_datagrams))
-        return sres, recs
+        return _fetch_pair(lib().ohgpu_raop_rx_batch_results, self._h, batch, RAOP_RX_STREAM_RESULT, n, RAOP_RX_RECORD, n_datagrams)
 
     def raop_rx_packets(self, batch, n_datagrams):
         """The last run's packet table (ALAC_PACKET per datagram row); waits for the run."""
-        rows = np.zeros(n_datagrams, dtype=ALAC_PACKET)
-        check(lib().ohgpu_raop_rx_batch_packets(self._h, batch, _ptr_or_none(rows), n_datagrams))
-        return rows
+        return _fetch(lib().ohgpu_raop_rx_batch_packets, self._h, batch, ALAC_PACKET, n_datagrams)
 
     def raop_rx_phase_ms(self, batch):
         """The last run's (parse, sequence, table) in milliseconds, from device events."""
-        ms = (C.c_float * 3)()
-        check(lib().ohgpu_raop_rx_batch_phase_ms(self._h, batch, ms))
-        return tuple(float(v) for v in ms)
+        return _phase_ms(lib().ohgpu_raop_rx_batch_phase_ms, self._h, batch, 3)
 
     def raop_rx_process_host(self, streams, datagrams, src):
         """Host buffer in (ohgpu_raop_rx_process_host); returns (stream results, records, packet rows)."""
-        s, g = _raop_rx_tables(streams, datagrams)
-        sres, recs, rows = np.zeros(s.size, dtype=RAOP_RX_STREAM_RESULT), np.zeros(g.size, dtype=RAOP_RX_RECORD), np.zeros(g.size, dtype=ALAC_PACKET)
-        check(lib().ohgpu_raop_rx_process_host(self._h, _ptr_or_none(s), s.size, _ptr_or_none(g), g.size, _ptr_or_none(src), src.nbytes,
-                                               _ptr_or_none(sres), _ptr_or_none(recs), _ptr_or_none(rows)))
-        return sres, recs, rows
+        s, g = _typed(streams, RAOP_RX_STREAM), _typed(datagrams, RAOP_RX_DATAGRAM)
+        out = np.zeros(s.size, dtype=RAOP_RX_STREAM_RESULT), np.zeros(g.size, dtype=RAOP_RX_RECORD), np.zeros(g.size, dtype=ALAC_PACKET)
+        return _process_host(lib().ohgpu_raop_rx_process_host, self._h, (_ptr(s), s.size, _ptr(g), g.size), src, None, out)
 
     def raop_rx_alac_process_host(self, streams, descs, datagrams, src, dst):
         """Datagrams to PCM or plaintext (ohgpu_raop_rx_alac_process_host); returns (stream results, records, packet rows, Apple
         Lossless stream results, packet results by datagram row)."""
-        s, g = _raop_rx_tables(streams, datagrams)
-        d = np.ascontiguousarray(descs)
-        assert d.dtype == RAOP_STREAM_DESC and d.size == s.size
-        sres, recs, rows = np.zeros(s.size, dtype=RAOP_RX_STREAM_RESULT), np.zeros(g.size, dtype=RAOP_RX_RECORD), np.zeros(g.size, dtype=ALAC_PACKET)
-        ares, pres = np.zeros(s.size, dtype=ALAC_STREAM_RESULT), np.zeros(g.size, dtype=ALAC_PACKET_RESULT)
-        check(lib().ohgpu_raop_rx_alac_process_host(self._h, _ptr_or_none(s), _ptr_or_none(d), s.size, _ptr_or_none(g), g.size, _ptr_or_none(src), src.nbytes,
-                                                    _ptr_or_none(dst), dst.nbytes, _ptr_or_none(sres), _ptr_or_none(recs), _ptr_or_none(rows),
-                                                    _ptr_or_none(ares), _ptr_or_none(pres)))
-        return sres, recs, rows, ares, pres
+        s, g, d = _typed(streams, RAOP_RX_STREAM), _typed(datagrams, RAOP_RX_DATAGRAM), _typed(descs, RAOP_STREAM_DESC)
+        assert d.size == s.size
+        out = (np.zeros(s.size, dtype=RAOP_RX_STREAM_RESULT), np.zeros(g.size, dtype=RAOP_RX_RECORD), np.zeros(g.size, dtype=ALAC_PACKET),
+               np.zeros(s.size, dtype=ALAC_STREAM_RESULT), np.zeros(g.size, dtype=ALAC_PACKET_RESULT))
+        return _process_host(lib().ohgpu_raop_rx_alac_process_host, self._h, (_ptr(s), _ptr(d), s.size, _ptr(g), g.size), src, dst, out)
 
     def vorbis_batch(self, descs, packets, images, src_arena_bytes, dst_arena_bytes):
-        d, p, im = _vorbis_tables(descs, packets, images)
-        b = C.c_void_p()
-        check(lib().ohgpu_vorbis_batch_create(self._h, _ptr_or_none(d), d.size, _ptr_or_none(p), p.size, _ptr_or_none(im), im.size, src_arena_bytes, dst_arena_bytes, C.byref(b)))
-        return b
+        d, p, im = _typed(descs, VORBIS_STREAM_DESC), _typed(packets, ALAC_PACKET), _typed(images, np.uint8)
+        return _create(lib().ohgpu_vorbis_batch_create, self._h, _ptr(d), d.size, _ptr(p), p.size, _ptr(im), im.size, src_arena_bytes, dst_arena_bytes)
 
     def vorbis_run(self, batch, d_src, d_dst, stream=None):
         """Head, entropy, synthesis, store (ohgpu_vorbis_batch_run): queued on the stream."""
@@ -1461,71 +1347,56 @@ class Context:
 
     def vorbis_results(self, batch, n, n_packets):
         """The last run's (VORBIS_STREAM_RESULT per stream, VORBIS_PACKET_RESULT per packet); waits for the run."""
-        res, pres = np.zeros(n, dtype=VORBIS_STREAM_RESULT), np.zeros(n_packets, dtype=VORBIS_PACKET_RESULT)
-        check(lib().ohgpu_vorbis_batch_results(self._h, batch, _ptr_or_none(res), n, _ptr_or_none(pres), n_packets))
-        return res, pres
+        return _fetch_pair(lib().ohgpu_vorbis_batch_results, self._h, batch, VORBIS_STREAM_RESULT, n, VORBIS_PACKET_RESULT, n_packets)
 
     def vorbis_phase_ms(self, batch):
         """(head, entropy, synthesis, store) of the last run in milliseconds."""
-        ms = (C.c_float * 4)()
-        check(lib().ohgpu_vorbis_batch_phase_ms(self._h, batch, ms))
-        return tuple(float(v) for v in ms)
+        return _phase_ms(lib().ohgpu_vorbis_batch_phase_ms, self._h, batch, 4)
 
     def vorbis_paths(self, batch):
         """{route, blocks} of a Vorbis batch (ohgpu_vorbis_batch_paths)."""
-        route, blocks = C.c_uint32(0), C.c_uint32(0)
-        check(lib().ohgpu_vorbis_batch_paths(batch, C.byref(route), C.byref(blocks)))
-        return dict(route=int(route.value), blocks=int(blocks.value))
+        return _paths(lib().ohgpu_vorbis_batch_paths, batch, "route", "blocks")
 
     def vorbis_spectrum(self, batch, packet, channel, n_values):
         """The float32 spectrum the last run transformed for one packet and channel (ohgpu_vorbis_batch_spectrum)."""
         out = np.zeros(n_values, dtype=np.float32)
-        check(lib().ohgpu_vorbis_batch_spectrum(self._h, batch, packet, channel, _ptr_or_none(out), n_values))
+        check(lib().ohgpu_vorbis_batch_spectrum(self._h, batch, packet, channel, _ptr(out), n_values))
         return out
 
     def vorbis_process_host(self, descs, packets, images, src, dst):
         """Host buffers in and out (ohgpu_vorbis_process_host); returns (stream results, packet results)."""
-        d, p, im = _vorbis_tables(descs, packets, images)
-        res, pres = np.zeros(d.size, dtype=VORBIS_STREAM_RESULT), np.zeros(p.size, dtype=VORBIS_PACKET_RESULT)
-        check(lib().ohgpu_vorbis_process_host(self._h, _ptr_or_none(d), d.size, _ptr_or_none(p), p.size, _ptr_or_none(im), im.size, _ptr_or_none(src), src.nbytes,
-                                              _ptr_or_none(dst), dst.nbytes, _ptr_or_none(res), _ptr_or_none(pres)))
-        return res, pres
+        d, p, im = _typed(descs, VORBIS_STREAM_DESC), _typed(packets, ALAC_PACKET), _typed(images, np.uint8)
+        out = np.zeros(d.size, dtype=VORBIS_STREAM_RESULT), np.zeros(p.size, dtype=VORBIS_PACKET_RESULT)
+        return _process_host(lib().ohgpu_vorbis_process_host, self._h, (_ptr(d), d.size, _ptr(p), p.size, _ptr(im), im.size), src, dst, out)
 
     def ogg_vorbis_process_host(self, ogg_descs, vorbis_descs, n_packets, images, src, mid_bytes, dst):
         """Ogg bytes to PCM (ohgpu_ogg_vorbis_process_host); returns (Ogg results, Ogg packet table, Vorbis stream results, packet results
         indexed as the Ogg table)."""
-        o = _ogg_descs(ogg_descs)
-        v, im = np.ascontiguousarray(vorbis_descs), np.ascontiguousarray(images)
-        assert v.dtype == VORBIS_STREAM_DESC and v.size == o.size and im.dtype == np.uint8
-        ores, orecs = np.zeros(o.size, dtype=OGG_STREAM_RESULT), np.zeros(n_packets, dtype=OGG_PACKET)
-        sres, pres = np.zeros(o.size, dtype=VORBIS_STREAM_RESULT), np.zeros(n_packets, dtype=VORBIS_PACKET_RESULT)
-        check(lib().ohgpu_ogg_vorbis_process_host(self._h, _ptr_or_none(o), _ptr_or_none(v), o.size, n_packets, _ptr_or_none(im), im.size, _ptr_or_none(src), src.nbytes,
-                                                  mid_bytes, _ptr_or_none(dst), dst.nbytes, _ptr_or_none(ores), _ptr_or_none(orecs), _ptr_or_none(sres), _ptr_or_none(pres)))
-        return ores, orecs, sres, pres
+        o, v, im = _typed(ogg_descs, OGG_STREAM_DESC), _typed(vorbis_descs, VORBIS_STREAM_DESC), _typed(images, np.uint8)
+        assert v.size == o.size
+        out = (np.zeros(o.size, dtype=OGG_STREAM_RESULT), np.zeros(n_packets, dtype=OGG_PACKET),
+               np.zeros(o.size, dtype=VORBIS_STREAM_RESULT), np.zeros(n_packets, dtype=VORBIS_PACKET_RESULT))
+        return _process_host(lib().ohgpu_ogg_vorbis_process_host, self._h, (_ptr(o), _ptr(v), o.size, n_packets, _ptr(im), im.size), src, dst, out,
+                             mid=(mid_bytes,))
 
     def ogg_vorbis_links_process_host(self, ogg_descs, vorbis_descs, dst_capacity_bytes, n_packets, images, src, mid_bytes, dst, links_capacity=None):
         """Chained Ogg bytes to PCM (ohgpu_ogg_vorbis_links_process_host); returns (Ogg results, Ogg packet table, the link rows -- all of
         them unless links_capacity says how many there is room for, then (rows, true count) --, packet results indexed as the Ogg table)."""
-        o = _ogg_descs(ogg_descs)
-        v, im = np.ascontiguousarray(vorbis_descs), np.ascontiguousarray(images)
+        o, v, im = _typed(ogg_descs, OGG_STREAM_DESC), _typed(vorbis_descs, VORBIS_STREAM_DESC), _typed(images, np.uint8)
         caps = np.ascontiguousarray(dst_capacity_bytes, dtype="<u8")
-        assert v.dtype == VORBIS_STREAM_DESC and v.size == o.size == caps.size and im.dtype == np.uint8
-        ores, orecs = np.zeros(o.size, dtype=OGG_STREAM_RESULT), np.zeros(n_packets, dtype=OGG_PACKET)
-        pres = np.zeros(n_packets, dtype=VORBIS_PACKET_RESULT)
+        assert v.size == o.size == caps.size
         room = o.size + n_packets if links_capacity is None else links_capacity
-        links, count = np.zeros(room, dtype=VORBIS_LINK), C.c_size_t(0)
-        check(lib().ohgpu_ogg_vorbis_links_process_host(self._h, _ptr_or_none(o), _ptr_or_none(v), _ptr_or_none(caps), o.size, n_packets, _ptr_or_none(im), im.size,
-                                                        _ptr_or_none(src), src.nbytes, mid_bytes, _ptr_or_none(dst), dst.nbytes, _ptr_or_none(ores), _ptr_or_none(orecs),
-                                                        _ptr_or_none(links), room, C.byref(count), _ptr_or_none(pres)))
+        links, count, pres = np.zeros(room, dtype=VORBIS_LINK), C.c_size_t(0), np.zeros(n_packets, dtype=VORBIS_PACKET_RESULT)
+        ores, orecs, _ = _process_host(lib().ohgpu_ogg_vorbis_links_process_host, self._h, (_ptr(o), _ptr(v), _ptr(caps), o.size, n_packets, _ptr(im), im.size),
+                                       src, dst, (np.zeros(o.size, dtype=OGG_STREAM_RESULT), np.zeros(n_packets, dtype=OGG_PACKET), links), mid=(mid_bytes,),
+                                       tail=(room, C.byref(count), _ptr(pres)))
         if links_capacity is None:
             return ores, orecs, links[:count.value].copy(), pres
         return ores, orecs, (links, count.value), pres
 
     def ts_batch(self, descs, n_pes, src_arena_bytes, dst_arena_bytes):
         d = _typed(descs, TS_STREAM_DESC)
-        b = C.c_void_p()
-        check(lib().ohgpu_ts_batch_create(self._h, _ptr_or_none(d), d.size, n_pes, src_arena_bytes, dst_arena_bytes, C.byref(b)))
-        return b
+        return _create(lib().ohgpu_ts_batch_create, self._h, _ptr(d), d.size, n_pes, src_arena_bytes, dst_arena_bytes)
 
     def ts_run(self, batch, d_src, d_dst, stream=None):
         """Parse, tables and sums, gather (ohgpu_ts_batch_run): queued on the stream."""
@@ -1533,36 +1404,25 @@ class Context:
 
     def ts_results(self, batch, n, n_pes):
         """The last run's (TS_STREAM_RESULT per stream, the PES table as TS_PES); waits for the run."""
-        res, pes = np.zeros(n, dtype=TS_STREAM_RESULT), np.zeros(n_pes, dtype=TS_PES)
-        check(lib().ohgpu_ts_batch_results(self._h, batch, _ptr_or_none(res), n))
-        check(lib().ohgpu_ts_batch_pes(self._h, batch, _ptr_or_none(pes), n_pes))
-        return res, pes
+        return _fetch(lib().ohgpu_ts_batch_results, self._h, batch, TS_STREAM_RESULT, n), _fetch(lib().ohgpu_ts_batch_pes, self._h, batch, TS_PES, n_pes)
 
     def ts_phase_ms(self, batch):
         """(parse, tables and sums, gather) of the last run in milliseconds."""
-        ms = (C.c_float * 3)()
-        check(lib().ohgpu_ts_batch_phase_ms(self._h, batch, ms))
-        return tuple(float(v) for v in ms)
+        return _phase_ms(lib().ohgpu_ts_batch_phase_ms, self._h, batch, 3)
 
     def ts_paths(self, batch):
         """{route, tiles, wave_blocks} of a transport stream batch (ohgpu_ts_batch_paths)."""
-        route, tiles, blocks = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
-        check(lib().ohgpu_ts_batch_paths(batch, C.byref(route), C.byref(tiles), C.byref(blocks)))
-        return dict(route=int(route.value), tiles=int(tiles.value), wave_blocks=int(blocks.value))
+        return _paths(lib().ohgpu_ts_batch_paths, batch, "route", "tiles", "wave_blocks")
 
     def ts_process_host(self, descs, n_pes, src, dst):
         """Host buffers in and out (ohgpu_ts_process_host); returns (stream results, PES table)."""
         d = _typed(descs, TS_STREAM_DESC)
-        res, pes = np.zeros(d.size, dtype=TS_STREAM_RESULT), np.zeros(n_pes, dtype=TS_PES)
-        check(lib().ohgpu_ts_process_host(self._h, _ptr_or_none(d), d.size, n_pes, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst), dst.nbytes,
-                                          _ptr_or_none(res), _ptr_or_none(pes)))
-        return res, pes
+        out = np.zeros(d.size, dtype=TS_STREAM_RESULT), np.zeros(n_pes, dtype=TS_PES)
+        return _process_host(lib().ohgpu_ts_process_host, self._h, (_ptr(d), d.size, n_pes), src, dst, out)
 
     def adts_batch(self, descs, n_frames, src_arena_bytes):
         d = _typed(descs, ADTS_STREAM_DESC)
-        b = C.c_void_p()
-        check(lib().ohgpu_adts_batch_create(self._h, _ptr_or_none(d), d.size, n_frames, src_arena_bytes, C.byref(b)))
-        return b
+        return _create(lib().ohgpu_adts_batch_create, self._h, _ptr(d), d.size, n_frames, src_arena_bytes)
 
     def adts_run(self, batch, d_src, stream=None):
         """Map, chain (ohgpu_adts_batch_run): queued on the stream."""
@@ -1570,46 +1430,35 @@ class Context:
 
     def adts_results(self, batch, n, n_frames):
         """The last run's (ADTS_STREAM_RESULT per stream, the frame table as ADTS_FRAME); waits for the run."""
-        res, frames = np.zeros(n, dtype=ADTS_STREAM_RESULT), np.zeros(n_frames, dtype=ADTS_FRAME)
-        check(lib().ohgpu_adts_batch_results(self._h, batch, _ptr_or_none(res), n))
-        check(lib().ohgpu_adts_batch_frames(self._h, batch, _ptr_or_none(frames), n_frames))
-        return res, frames
+        return (_fetch(lib().ohgpu_adts_batch_results, self._h, batch, ADTS_STREAM_RESULT, n),
+                _fetch(lib().ohgpu_adts_batch_frames, self._h, batch, ADTS_FRAME, n_frames))
 
     def adts_phase_ms(self, batch):
         """(map, chain) of the last run in milliseconds."""
-        ms = (C.c_float * 2)()
-        check(lib().ohgpu_adts_batch_phase_ms(self._h, batch, ms))
-        return tuple(float(v) for v in ms)
+        return _phase_ms(lib().ohgpu_adts_batch_phase_ms, self._h, batch, 2)
 
     def adts_paths(self, batch):
         """{route, tiles} of an ADTS batch (ohgpu_adts_batch_paths)."""
-        route, tiles = C.c_uint32(0), C.c_uint32(0)
-        check(lib().ohgpu_adts_batch_paths(batch, C.byref(route), C.byref(tiles)))
-        return dict(route=int(route.value), tiles=int(tiles.value))
+        return _paths(lib().ohgpu_adts_batch_paths, batch, "route", "tiles")
 
     def adts_process_host(self, descs, n_frames, src):
         """Host bytes in (ohgpu_adts_process_host); returns (stream results, frame table)."""
         d = _typed(descs, ADTS_STREAM_DESC)
-        res, frames = np.zeros(d.size, dtype=ADTS_STREAM_RESULT), np.zeros(n_frames, dtype=ADTS_FRAME)
-        check(lib().ohgpu_adts_process_host(self._h, _ptr_or_none(d), d.size, n_frames, _ptr_or_none(src), src.nbytes, _ptr_or_none(res), _ptr_or_none(frames)))
-        return res, frames
+        out = np.zeros(d.size, dtype=ADTS_STREAM_RESULT), np.zeros(n_frames, dtype=ADTS_FRAME)
+        return _process_host(lib().ohgpu_adts_process_host, self._h, (_ptr(d), d.size, n_frames), src, None, out)
 
     def ts_adts_process_host(self, ts_descs, adts_descs, n_pes, n_frames, src, dst):
         """Transport bytes to the elementary run, the PES table and the frame table (ohgpu_ts_adts_process_host); returns (TS results, PES
         table, ADTS results, frame table)."""
         t, a = _typed(ts_descs, TS_STREAM_DESC), _typed(adts_descs, ADTS_STREAM_DESC)
         assert t.size == a.size
-        tres, pes = np.zeros(t.size, dtype=TS_STREAM_RESULT), np.zeros(n_pes, dtype=TS_PES)
-        ares, frames = np.zeros(t.size, dtype=ADTS_STREAM_RESULT), np.zeros(n_frames, dtype=ADTS_FRAME)
-        check(lib().ohgpu_ts_adts_process_host(self._h, _ptr_or_none(t), _ptr_or_none(a), t.size, n_pes, n_frames, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst),
-                                               dst.nbytes, _ptr_or_none(tres), _ptr_or_none(pes), _ptr_or_none(ares), _ptr_or_none(frames)))
-        return tres, pes, ares, frames
+        out = (np.zeros(t.size, dtype=TS_STREAM_RESULT), np.zeros(n_pes, dtype=TS_PES),
+               np.zeros(t.size, dtype=ADTS_STREAM_RESULT), np.zeros(n_frames, dtype=ADTS_FRAME))
+        return _process_host(lib().ohgpu_ts_adts_process_host, self._h, (_ptr(t), _ptr(a), t.size, n_pes, n_frames), src, dst, out)
 
     def ogg_batch(self, descs, n_packets, src_arena_bytes, dst_arena_bytes):
-        d = _ogg_descs(descs)
-        b = C.c_void_p()
-        check(lib().ohgpu_ogg_batch_create(self._h, _ptr_or_none(d), d.size, n_packets, src_arena_bytes, dst_arena_bytes, C.byref(b)))
-        return b
+        d = _typed(descs, OGG_STREAM_DESC)
+        return _create(lib().ohgpu_ogg_batch_create, self._h, _ptr(d), d.size, n_packets, src_arena_bytes, dst_arena_bytes)
 
     def ogg_run(self, batch, d_src, d_dst, stream=None):
         """Find, verify, chain, gather (ohgpu_ogg_batch_run): queued on the stream."""
@@ -1617,42 +1466,33 @@ class Context:
 
     def ogg_results(self, batch, n, n_packets):
         """The last run's (OGG_STREAM_RESULT per stream, the packet table as OGG_PACKET); waits for the run."""
-        res, pk = np.zeros(n, dtype=OGG_STREAM_RESULT), np.zeros(n_packets, dtype=OGG_PACKET)
-        check(lib().ohgpu_ogg_batch_results(self._h, batch, _ptr_or_none(res), n))
-        check(lib().ohgpu_ogg_batch_packets(self._h, batch, _ptr_or_none(pk), n_packets))
-        return res, pk
+        return (_fetch(lib().ohgpu_ogg_batch_results, self._h, batch, OGG_STREAM_RESULT, n),
+                _fetch(lib().ohgpu_ogg_batch_packets, self._h, batch, OGG_PACKET, n_packets))
 
     def ogg_phase_ms(self, batch):
         """The last run's (find, verify, chain, gather) in milliseconds, from device events."""
-        ms = (C.c_float * 4)()
-        check(lib().ohgpu_ogg_batch_phase_ms(self._h, batch, ms))
-        return tuple(float(v) for v in ms)
+        return _phase_ms(lib().ohgpu_ogg_batch_phase_ms, self._h, batch, 4)
 
     def ogg_process_host(self, descs, n_packets, src, dst):
         """Host buffers in and out (ohgpu_ogg_process_host); returns (stream results, packet table)."""
-        d = _ogg_descs(descs)
-        res, pk = np.zeros(d.size, dtype=OGG_STREAM_RESULT), np.zeros(n_packets, dtype=OGG_PACKET)
-        check(lib().ohgpu_ogg_process_host(self._h, _ptr_or_none(d), d.size, n_packets, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst), dst.nbytes,
-                                           _ptr_or_none(res), _ptr_or_none(pk)))
-        return res, pk
+        d = _typed(descs, OGG_STREAM_DESC)
+        out = np.zeros(d.size, dtype=OGG_STREAM_RESULT), np.zeros(n_packets, dtype=OGG_PACKET)
+        return _process_host(lib().ohgpu_ogg_process_host, self._h, (_ptr(d), d.size, n_packets), src, dst, out)
 
     def ogg_flac_process_host(self, ogg_descs, flac_descs, n_packets, src, mid_bytes, dst, frames_capacity=0):
         """Ogg FLAC from host buffers (ohgpu_ogg_flac_process_host); returns (Ogg results, packet table, FLAC results, frames)."""
-        o, f = _ogg_descs(ogg_descs), np.ascontiguousarray(flac_descs)
-        assert f.dtype == FLAC_STREAM_DESC and f.size == o.size
-        ores, pk = np.zeros(o.size, dtype=OGG_STREAM_RESULT), np.zeros(n_packets, dtype=OGG_PACKET)
-        fres, frames = np.zeros(o.size, dtype=FLAC_STREAM_RESULT), np.zeros(frames_capacity, dtype=FLAC_FRAME)
+        o, f = _typed(ogg_descs, OGG_STREAM_DESC), _typed(flac_descs, FLAC_STREAM_DESC)
+        assert f.size == o.size
+        out = (np.zeros(o.size, dtype=OGG_STREAM_RESULT), np.zeros(n_packets, dtype=OGG_PACKET),
+               np.zeros(o.size, dtype=FLAC_STREAM_RESULT), np.zeros(frames_capacity, dtype=FLAC_FRAME))
         n_frames = C.c_size_t(0)
-        check(lib().ohgpu_ogg_flac_process_host(self._h, _ptr_or_none(o), _ptr_or_none(f), o.size, n_packets, _ptr_or_none(src), src.nbytes, mid_bytes,
-                                                _ptr_or_none(dst), dst.nbytes, _ptr_or_none(ores), _ptr_or_none(pk), _ptr_or_none(fres),
-                                                _ptr_or_none(frames), frames_capacity, C.byref(n_frames)))
-        return ores, pk, fres, frames[:min(int(n_frames.value), frames_capacity)]
+        _process_host(lib().ohgpu_ogg_flac_process_host, self._h, (_ptr(o), _ptr(f), o.size, n_packets), src, dst, out, mid=(mid_bytes,),
+                      tail=(frames_capacity, C.byref(n_frames)))
+        return (*out[:3], out[3][:min(int(n_frames.value), frames_capacity)])
 
     def mp4_batch(self, descs, n_packets, src_arena_bytes):
-        d = _mp4_descs(descs)
-        b = C.c_void_p()
-        check(lib().ohgpu_mp4_batch_create(self._h, _ptr_or_none(d), d.size, n_packets, src_arena_bytes, C.byref(b)))
-        return b
+        d = _typed(descs, MP4_STREAM_DESC)
+        return _create(lib().ohgpu_mp4_batch_create, self._h, _ptr(d), d.size, n_packets, src_arena_bytes)
 
     def mp4_run(self, batch, d_src, stream=None):
         """Walk, tile sums, carries, expand (ohgpu_mp4_batch_run): queued on the stream."""
@@ -1660,85 +1500,57 @@ class Context:
 
     def mp4_results(self, batch, n, n_packets):
         """The last run's (MP4_STREAM_RESULT per stream, the packet table as ALAC_PACKET, the sample table as MP4_SAMPLE); waits for the run."""
-        res, pk, sm = np.zeros(n, dtype=MP4_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
-        check(lib().ohgpu_mp4_batch_results(self._h, batch, _ptr_or_none(res), n))
-        check(lib().ohgpu_mp4_batch_packets(self._h, batch, _ptr_or_none(pk), n_packets))
-        check(lib().ohgpu_mp4_batch_samples(self._h, batch, _ptr_or_none(sm), n_packets))
-        return res, pk, sm
+        return (_fetch(lib().ohgpu_mp4_batch_results, self._h, batch, MP4_STREAM_RESULT, n),
+                _fetch(lib().ohgpu_mp4_batch_packets, self._h, batch, ALAC_PACKET, n_packets),
+                _fetch(lib().ohgpu_mp4_batch_samples, self._h, batch, MP4_SAMPLE, n_packets))
 
     def mp4_phase_ms(self, batch):
         """The last run's (walk, tile sums, carries, expand) in milliseconds, from device events; the plain route: (all of it, 0, 0, 0)."""
-        ms = (C.c_float * 4)()
-        check(lib().ohgpu_mp4_batch_phase_ms(self._h, batch, ms))
-        return tuple(float(v) for v in ms)
+        return _phase_ms(lib().ohgpu_mp4_batch_phase_ms, self._h, batch, 4)
 
     def mp4_process_host(self, descs, n_packets, src):
         """Host bytes in (ohgpu_mp4_process_host); returns (stream results, packet table, sample table)."""
-        d = _mp4_descs(descs)
-        res, pk, sm = np.zeros(d.size, dtype=MP4_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
-        check(lib().ohgpu_mp4_process_host(self._h, _ptr_or_none(d), d.size, n_packets, _ptr_or_none(src), src.nbytes, _ptr_or_none(res), _ptr_or_none(pk),
-                                           _ptr_or_none(sm)))
-        return res, pk, sm
+        d = _typed(descs, MP4_STREAM_DESC)
+        out = np.zeros(d.size, dtype=MP4_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
+        return _process_host(lib().ohgpu_mp4_process_host, self._h, (_ptr(d), d.size, n_packets), src, None, out)
 
     def mp4_alac_process_host(self, mp4_descs, alac_descs, n_packets, src, dst):
         """.m4a bytes in, PCM out (ohgpu_mp4_alac_process_host); returns (MPEG-4 results, packet table, sample table, Apple Lossless stream
         results, packet results indexed as the tables are).  Of alac_descs only flags, dst_offset and dst_plane_stride are read."""
-        m, a = _mp4_descs(mp4_descs), np.ascontiguousarray(alac_descs)
-        assert a.dtype == ALAC_STREAM_DESC and a.size == m.size
-        res, pk, sm = np.zeros(m.size, dtype=MP4_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE)
-        ares, pres = np.zeros(m.size, dtype=ALAC_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET_RESULT)
-        check(lib().ohgpu_mp4_alac_process_host(self._h, _ptr_or_none(m), _ptr_or_none(a), m.size, n_packets, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst), dst.nbytes,
-                                                _ptr_or_none(res), _ptr_or_none(pk), _ptr_or_none(sm), _ptr_or_none(ares), _ptr_or_none(pres)))
-        return res, pk, sm, ares, pres
+        m, a = _typed(mp4_descs, MP4_STREAM_DESC), _typed(alac_descs, ALAC_STREAM_DESC)
+        assert a.size == m.size
+        out = (np.zeros(m.size, dtype=MP4_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET), np.zeros(n_packets, dtype=MP4_SAMPLE),
+               np.zeros(m.size, dtype=ALAC_STREAM_RESULT), np.zeros(n_packets, dtype=ALAC_PACKET_RESULT))
+        return _process_host(lib().ohgpu_mp4_alac_process_host, self._h, (_ptr(m), _ptr(a), m.size, n_packets), src, dst, out)
 
     # ---- the three fragmented MPEG-4 families: one implementation (counts: see _FRAG), then each family's names over it
     def _frag_batch(self, fam, descs, counts, src_arena_bytes, dst_arena_bytes):
-        d = _frag_descs(fam, descs)
-        b = C.c_void_p()
-        _frag_call(fam, "batch_create", self._h, _ptr_or_none(d), d.size, *counts, src_arena_bytes, dst_arena_bytes, C.byref(b))
-        return b
+        d = _typed(descs, _FRAG[fam][0])
+        return _create(_frag_fn(fam, "batch_create"), self._h, _ptr(d), d.size, *counts, src_arena_bytes, dst_arena_bytes)
 
     def _frag_results(self, fam, batch, n, n_packets, n_runs):
-        out = _frag_tables(fam, n, n_packets, n_runs)
-        for name, table, rows in zip(("results", "runs", "packets", "samples"), out, (n, n_runs, n_packets, n_packets)):
-            _frag_call(fam, "batch_" + name, self._h, batch, _ptr_or_none(table), rows)
-        return out
-
-    def _frag_phase_ms(self, fam, batch):
-        ms = (C.c_float * 6)()
-        _frag_call(fam, "batch_phase_ms", self._h, batch, ms)
-        return tuple(float(v) for v in ms)
-
-    def _frag_paths(self, fam, batch):
-        route, tiles, blocks = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
-        _frag_call(fam, "batch_paths", batch, C.byref(route), C.byref(tiles), C.byref(blocks))
-        return dict(route=int(route.value), tiles=int(tiles.value), wave_blocks=int(blocks.value))
+        return (_fetch(_frag_fn(fam, "batch_results"), self._h, batch, _FRAG[fam][1], n), _fetch(_frag_fn(fam, "batch_runs"), self._h, batch, MP4F_RUN, n_runs),
+                _fetch(_frag_fn(fam, "batch_packets"), self._h, batch, ALAC_PACKET, n_packets), _fetch(_frag_fn(fam, "batch_samples"), self._h, batch, MP4_SAMPLE, n_packets))
 
     def _frag_process_host(self, fam, descs, counts, src, dst):
-        d = _frag_descs(fam, descs)
-        out = _frag_tables(fam, d.size, *counts[:2])
-        _frag_call(fam, "process_host", self._h, _ptr_or_none(d), d.size, *counts, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst), dst.nbytes, *map(_ptr_or_none, out))
-        return out
+        d = _typed(descs, _FRAG[fam][0])
+        return _process_host(_frag_fn(fam, "process_host"), self._h, (_ptr(d), d.size, *counts), src, dst, _frag_zeros(fam, d.size, *counts[:2]))
 
     def _frag_flac_process_host(self, fam, descs, flac_descs, counts, src, mid_bytes, dst, frames_capacity):
-        m, f = _frag_descs(fam, descs), np.ascontiguousarray(flac_descs)
-        assert f.dtype == FLAC_STREAM_DESC and f.size == m.size
-        out = _frag_tables(fam, m.size, *counts[:2])
-        fres, frames = np.zeros(m.size, dtype=FLAC_STREAM_RESULT), np.zeros(frames_capacity, dtype=FLAC_FRAME)
+        m, f = _typed(descs, _FRAG[fam][0]), _typed(flac_descs, FLAC_STREAM_DESC)
+        assert f.size == m.size
+        out = (*_frag_zeros(fam, m.size, *counts[:2]), np.zeros(m.size, dtype=FLAC_STREAM_RESULT), np.zeros(frames_capacity, dtype=FLAC_FRAME))
         n_frames = C.c_size_t(0)
-        _frag_call(fam, "flac_process_host", self._h, _ptr_or_none(m), _ptr_or_none(f), m.size, *counts, _ptr_or_none(src), src.nbytes, mid_bytes, _ptr_or_none(dst), dst.nbytes,
-                   *map(_ptr_or_none, out), _ptr_or_none(fres), _ptr_or_none(frames), frames_capacity, C.byref(n_frames))
-        return (*out, fres, frames[:min(int(n_frames.value), frames_capacity)])
+        _process_host(_frag_fn(fam, "flac_process_host"), self._h, (_ptr(m), _ptr(f), m.size, *counts), src, dst, out, mid=(mid_bytes,),
+                      tail=(frames_capacity, C.byref(n_frames)))
+        return (*out[:5], out[5][:min(int(n_frames.value), frames_capacity)])
 
     def _frag_alac_process_host(self, fam, descs, alac_descs, counts, src, mid, dst):
         """mid: (mid_bytes,) for a protected family, () for mp4f, whose packets are decoded where they lie"""
-        m, a = _frag_descs(fam, descs), np.ascontiguousarray(alac_descs)
-        assert a.dtype == ALAC_STREAM_DESC and a.size == m.size
-        out = _frag_tables(fam, m.size, *counts[:2])
-        ares, pres = np.zeros(m.size, dtype=ALAC_STREAM_RESULT), np.zeros(counts[0], dtype=ALAC_PACKET_RESULT)
-        _frag_call(fam, "alac_process_host", self._h, _ptr_or_none(m), _ptr_or_none(a), m.size, *counts, _ptr_or_none(src), src.nbytes, *mid, _ptr_or_none(dst), dst.nbytes,
-                   *map(_ptr_or_none, out), _ptr_or_none(ares), _ptr_or_none(pres))
-        return (*out, ares, pres)
+        m, a = _typed(descs, _FRAG[fam][0]), _typed(alac_descs, ALAC_STREAM_DESC)
+        assert a.size == m.size
+        out = (*_frag_zeros(fam, m.size, *counts[:2]), np.zeros(m.size, dtype=ALAC_STREAM_RESULT), np.zeros(counts[0], dtype=ALAC_PACKET_RESULT))
+        return _process_host(_frag_fn(fam, "alac_process_host"), self._h, (_ptr(m), _ptr(a), m.size, *counts), src, dst, out, mid=mid)
 
     def mp4f_batch(self, descs, n_packets, n_runs, src_arena_bytes, dst_arena_bytes):
         return self._frag_batch("mp4f", descs, (n_packets, n_runs), src_arena_bytes, dst_arena_bytes)
@@ -1753,11 +1565,11 @@ class Context:
 
     def mp4f_phase_ms(self, batch):
         """(walk, run sums, carries, expand, finish, gather) of the last run in milliseconds."""
-        return self._frag_phase_ms("mp4f", batch)
+        return _phase_ms(lib().ohgpu_mp4f_batch_phase_ms, self._h, batch, 6)
 
     def mp4f_paths(self, batch):
         """{route, tiles, wave_blocks} of a fragmented MPEG-4 batch (ohgpu_mp4f_batch_paths)."""
-        return self._frag_paths("mp4f", batch)
+        return _paths(lib().ohgpu_mp4f_batch_paths, batch, "route", "tiles", "wave_blocks")
 
     def mp4f_process_host(self, descs, n_packets, n_runs, src, dst):
         """Host bytes in (ohgpu_mp4f_process_host), the gathered runs into dst; returns (results, run table, packet table, sample table)."""
@@ -1786,11 +1598,11 @@ class Context:
 
     def cenc_phase_ms(self, batch):
         """(walk, run sums, carries, expand, finish, decrypt-gather) of the last run in milliseconds."""
-        return self._frag_phase_ms("cenc", batch)
+        return _phase_ms(lib().ohgpu_cenc_batch_phase_ms, self._h, batch, 6)
 
     def cenc_paths(self, batch):
         """{route, tiles, wave_blocks: the persistent decrypt-gather launch's workgroups} of a protected MPEG-4 batch (ohgpu_cenc_batch_paths)."""
-        return self._frag_paths("cenc", batch)
+        return _paths(lib().ohgpu_cenc_batch_paths, batch, "route", "tiles", "wave_blocks")
 
     def cenc_process_host(self, descs, n_packets, n_runs, src, dst):
         """Host bytes in (ohgpu_cenc_process_host), the clear runs into dst; returns (results, run table, packet table, sample table)."""
@@ -1819,11 +1631,11 @@ class Context:
 
     def cbcs_phase_ms(self, batch):
         """(walk, run sums, carries, expand, finish, decrypt-gather) of the last run in milliseconds."""
-        return self._frag_phase_ms("cbcs", batch)
+        return _phase_ms(lib().ohgpu_cbcs_batch_phase_ms, self._h, batch, 6)
 
     def cbcs_paths(self, batch):
         """{route, tiles, wave_blocks: the persistent decrypt-gather launch's workgroups} of a batch of the family (ohgpu_cbcs_batch_paths)."""
-        return self._frag_paths("cbcs", batch)
+        return _paths(lib().ohgpu_cbcs_batch_paths, batch, "route", "tiles", "wave_blocks")
 
     def cbcs_process_host(self, descs, n_packets, n_runs, n_subsamples, src, dst):
         """Host bytes in (ohgpu_cbcs_process_host), the clear runs into dst; returns (results, run table, packet table, sample table)."""
@@ -1840,10 +1652,8 @@ class Context:
         return self._frag_alac_process_host("cbcs", descs, alac_descs, (n_packets, n_runs, n_subsamples), src, (mid_bytes,), dst)
 
     def iff_batch(self, descs, src_arena_bytes, dst_arena_bytes):
-        d = _iff_descs(descs)
-        b = C.c_void_p()
-        check(lib().ohgpu_iff_batch_create(self._h, _ptr_or_none(d), d.size, src_arena_bytes, dst_arena_bytes, C.byref(b)))
-        return b
+        d = _typed(descs, IFF_STREAM_DESC)
+        return _create(lib().ohgpu_iff_batch_create, self._h, _ptr(d), d.size, src_arena_bytes, dst_arena_bytes)
 
     def iff_run(self, batch, d_src, d_dst, stream=None):
         """Walk, convert (ohgpu_iff_batch_run): queued on the stream."""
@@ -1851,21 +1661,15 @@ class Context:
 
     def iff_results(self, batch, n):
         """The last run's IFF_STREAM_RESULT per stream; waits for the run."""
-        res = np.zeros(n, dtype=IFF_STREAM_RESULT)
-        check(lib().ohgpu_iff_batch_results(self._h, batch, _ptr_or_none(res), n))
-        return res
+        return _fetch(lib().ohgpu_iff_batch_results, self._h, batch, IFF_STREAM_RESULT, n)
 
     def iff_phase_ms(self, batch):
         """The last run's (walk, convert) in milliseconds, from device events; the plain route: (all of it, 0)."""
-        ms = (C.c_float * 2)()
-        check(lib().ohgpu_iff_batch_phase_ms(self._h, batch, ms))
-        return tuple(float(v) for v in ms)
+        return _phase_ms(lib().ohgpu_iff_batch_phase_ms, self._h, batch, 2)
 
     def dsd_file_batch(self, descs, src_arena_bytes, dst_arena_bytes):
-        d = _dsd_file_descs(descs)
-        b = C.c_void_p()
-        check(lib().ohgpu_dsd_file_batch_create(self._h, _ptr_or_none(d), d.size, src_arena_bytes, dst_arena_bytes, C.byref(b)))
-        return b
+        d = _typed(descs, DSD_FILE_STREAM_DESC)
+        return _create(lib().ohgpu_dsd_file_batch_create, self._h, _ptr(d), d.size, src_arena_bytes, dst_arena_bytes)
 
     def dsd_file_run(self, batch, d_src, d_dst, stream=None):
         """Walk, convert (ohgpu_dsd_file_batch_run): queued on the stream."""
@@ -1873,46 +1677,32 @@ class Context:
 
     def dsd_file_results(self, batch, n):
         """The last run's DSD_FILE_STREAM_RESULT per stream; waits for the run."""
-        res = np.zeros(n, dtype=DSD_FILE_STREAM_RESULT)
-        check(lib().ohgpu_dsd_file_batch_results(self._h, batch, _ptr_or_none(res), n))
-        return res
+        return _fetch(lib().ohgpu_dsd_file_batch_results, self._h, batch, DSD_FILE_STREAM_RESULT, n)
 
     def dsd_file_phase_ms(self, batch):
         """(walk, convert) of the last run in milliseconds; waits for the run."""
-        ms = (C.c_float * 2)()
-        check(lib().ohgpu_dsd_file_batch_phase_ms(self._h, batch, ms))
-        return [float(v) for v in ms]
+        return list(_phase_ms(lib().ohgpu_dsd_file_batch_phase_ms, self._h, batch, 2))     # (a list where its siblings answer a tuple)
 
     def dsd_file_process_host(self, descs, src, dst):
         """File bytes in, sample blocks of the pipeline's DSD format into dst (ohgpu_dsd_file_process_host); returns the stream results."""
-        d = _dsd_file_descs(descs)
-        res = np.zeros(d.size, dtype=DSD_FILE_STREAM_RESULT)
-        check(lib().ohgpu_dsd_file_process_host(self._h, _ptr_or_none(d), d.size, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst), dst.nbytes, _ptr_or_none(res)))
-        return res
+        d = _typed(descs, DSD_FILE_STREAM_DESC)
+        return _process_host(lib().ohgpu_dsd_file_process_host, self._h, (_ptr(d), d.size), src, dst, (np.zeros(d.size, dtype=DSD_FILE_STREAM_RESULT),))[0]
 
     def iff_process_host(self, descs, src, dst):
         """File bytes in, big-endian PCM into dst (ohgpu_iff_process_host); returns the stream results."""
-        d = _iff_descs(descs)
-        res = np.zeros(d.size, dtype=IFF_STREAM_RESULT)
-        check(lib().ohgpu_iff_process_host(self._h, _ptr_or_none(d), d.size, _ptr_or_none(src), src.nbytes, _ptr_or_none(dst), dst.nbytes, _ptr_or_none(res)))
-        return res
+        d = _typed(descs, IFF_STREAM_DESC)
+        return _process_host(lib().ohgpu_iff_process_host, self._h, (_ptr(d), d.size), src, dst, (np.zeros(d.size, dtype=IFF_STREAM_RESULT),))[0]
 
     def src_create(self, L, M, T, coef_q28):
         c = np.ascontiguousarray(coef_q28, dtype=np.int32)
-        s = C.c_void_p()
-        check(lib().ohgpu_src_create(self._h, L, M, T, c.ctypes.data_as(C.c_void_p), C.byref(s)))
-        return s
+        return _create(lib().ohgpu_src_create, self._h, L, M, T, _ptr(c, keep=True))
 
     def src_destroy(self, src):
         check(lib().ohgpu_src_destroy(self._h, src))
 
     def src_batch(self, src, descs, src_arena_bytes, dst_arena_bytes):
-        d = np.ascontiguousarray(descs)
-        assert d.dtype == SRC_MSG_DESC
-        b = C.c_void_p()
-        check(lib().ohgpu_src_batch_create(self._h, src, d.ctypes.data_as(C.c_void_p), d.size, src_arena_bytes,
-                                           dst_arena_bytes, C.byref(b)))
-        return b
+        d = _typed(descs, SRC_MSG_DESC)
+        return _create(lib().ohgpu_src_batch_create, self._h, src, _ptr(d), d.size, src_arena_bytes, dst_arena_bytes)
 
     def src_batch_block(self, batch):
         lo, mi = C.c_uint32(0), C.c_uint32(0)
@@ -1926,15 +1716,12 @@ class Context:
         a = np.ascontiguousarray(ramp_start, dtype=np.uint16)
         e = np.ascontiguousarray(ramp_end, dtype=np.uint16)
         assert a.size == e.size
-        check(lib().ohgpu_src_batch_set_ramps(self._h, batch, a.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p), a.size))
+        check(lib().ohgpu_src_batch_set_ramps(self._h, batch, _ptr(a, keep=True), _ptr(e, keep=True), a.size))
 
     def src_process_host(self, src, descs, src_bytes, dst_bytes_array):
         """ohgpu_src_process_host: host buffers in, host buffers out (validation, upload, launch, download, sync in one call)."""
-        d = np.ascontiguousarray(descs)
-        assert d.dtype == SRC_MSG_DESC
-        check(lib().ohgpu_src_process_host(self._h, src, d.ctypes.data_as(C.c_void_p), d.size,
-                                           src_bytes.ctypes.data_as(C.c_void_p), src_bytes.nbytes,
-                                           dst_bytes_array.ctypes.data_as(C.c_void_p), dst_bytes_array.nbytes))
+        d = _typed(descs, SRC_MSG_DESC)
+        _process_host(lib().ohgpu_src_process_host, self._h, (src, _ptr(d), d.size), src_bytes, dst_bytes_array, ())
         return dst_bytes_array
 
     def src_plan(self, batch):
@@ -1988,29 +1775,21 @@ class Context:
     # ---- the pulled resampler
     def src_pull_create(self, taps_per_phase, phases_log2, coef_q28):
         c = np.ascontiguousarray(coef_q28, dtype=np.int32)
-        s = C.c_void_p()
-        check(lib().ohgpu_src_pull_create(self._h, taps_per_phase, phases_log2, c.ctypes.data_as(C.c_void_p), C.byref(s)))
-        return s
+        return _create(lib().ohgpu_src_pull_create, self._h, taps_per_phase, phases_log2, _ptr(c, keep=True))
 
     def src_pull_destroy(self, src):
         check(lib().ohgpu_src_pull_destroy(self._h, src))
 
     def src_pull_batch(self, src, descs, src_arena_bytes, dst_arena_bytes):
-        d = np.ascontiguousarray(descs)
-        assert d.dtype == SRC_PULL_MSG_DESC
-        b = C.c_void_p()
-        check(lib().ohgpu_src_pull_batch_create(self._h, src, d.ctypes.data_as(C.c_void_p), d.size, src_arena_bytes,
-                                                dst_arena_bytes, C.byref(b)))
-        return b
+        d = _typed(descs, SRC_PULL_MSG_DESC)
+        return _create(lib().ohgpu_src_pull_batch_create, self._h, src, _ptr(d), d.size, src_arena_bytes, dst_arena_bytes)
 
     def src_pull_run(self, batch, d_src, d_dst, stream=None):
         check(lib().ohgpu_src_pull_batch_run(self._h, batch, d_src, d_dst, stream))
 
     def src_pull_process_host(self, src, descs, src_bytes, dst_bytes_array):
         """ohgpu_src_pull_process_host: host buffers in, host buffers out."""
-        d = np.ascontiguousarray(descs)
-        assert d.dtype == SRC_PULL_MSG_DESC
-        check(lib().ohgpu_src_pull_process_host(self._h, src, d.ctypes.data_as(C.c_void_p), d.size,
-                                                src_bytes.ctypes.data_as(C.c_void_p), src_bytes.nbytes,
-                                                dst_bytes_array.ctypes.data_as(C.c_void_p), dst_bytes_array.nbytes))
+        d = _typed(descs, SRC_PULL_MSG_DESC)
+        _process_host(lib().ohgpu_src_pull_process_host, self._h, (src, _ptr(d), d.size), src_bytes, dst_bytes_array, ())
         return dst_bytes_array
+

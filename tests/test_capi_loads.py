@@ -159,3 +159,83 @@ def test_the_shipped_library_is_not_a_diagnostic_build():
         for no, line in enumerate(text.splitlines(), 1):
             if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", line):
                 assert not switch.search(line), f"{name}:{no}: a compile-time switch: {line.strip()}"
+
+
+# ---- the signatures: every prototype of the six public headers against its symbol table's entry, class by class
+_INT64, _INT32 = {"uint64_t", "int64_t", "size_t"}, {"int", "unsigned", "uint32_t", "int32_t"}
+
+
+def _c_class(decl, named):
+    """The class of a C parameter (`named`: the last word is its name) or return type: ptr, i64, i32, f64, f32."""
+    if "*" in decl or "[" in decl:
+        return "ptr"
+    words = [w for w in decl.split() if w not in ("const", "struct")]
+    if named and len(words) > 1:
+        words = words[:-1]
+    assert len(words) == 1, f"cannot classify {decl!r}"
+    w = words[0]
+    if w in ("double", "float"):
+        return {"double": "f64", "float": "f32"}[w]
+    assert w in _INT64 | _INT32, f"cannot classify {decl!r}"
+    return "i64" if w in _INT64 else "i32"
+
+
+def header_prototypes(header):
+    """{name: (return class, [argument classes])} of every ohgpu_* function a header under include/ declares."""
+    text = open(os.path.join(ROOT, "include", header)).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*", " ", text, flags=re.M)            # preprocessor lines, continued ones too
+    text = re.sub(r'extern\s+"C"\s*\{', " ", text)
+    while True:                                                                      # struct, union and enum bodies, innermost first
+        text, n = re.subn(r"\{[^{}]*\}", " ", text)
+        if not n:
+            break
+    out = {}
+    for stmt in text.split(";"):                                                     # a prototype runs to its `;`, across lines
+        m = re.fullmatch(r"[\s}]*(?!typedef\b)([\w\s\*]+?)\b(ohgpu_[a-z0-9_]+)\s*\((.*)\)\s*", stmt, flags=re.S)
+        if not m:
+            assert "(" not in stmt, f"{header}: a statement with a parenthesis that is no ohgpu_* prototype: {stmt.strip()!r}"
+            continue
+        ret, name, params = m.groups()
+        assert "(" not in params and name not in out, f"{header}: {name}"
+        params = [p.strip() for p in params.split(",")] if params.strip() not in ("", "void") else []
+        out[name] = (_c_class(ret, named=False), [_c_class(p, named=True) for p in params])
+    return out
+
+
+def _ctypes_class(t):
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+        return "ptr"
+    if t in (C.c_double, C.c_float):
+        return "f64" if t is C.c_double else "f32"
+    assert t in (C.c_uint64, C.c_int64, C.c_size_t, C.c_int, C.c_uint32, C.c_int32), f"cannot classify {t!r}"
+    return {8: "i64", 4: "i32"}[C.sizeof(t)]
+
+
+def test_symbol_tables_match_the_headers_prototypes_argument_by_argument():
+    """Return class, argument count and each argument's class (pointer, 64-bit integer, 32-bit integer, double, float) of every
+    ohgpu_* prototype in the six headers against the entry of that header's table; each table holds exactly its header's functions."""
+    from ohpipeline_amd import build as product_build
+    public = sorted(os.path.basename(h) for h in product_build.HEADERS if os.path.dirname(h) == os.path.join(ROOT, "include"))
+    assert public == sorted(os.listdir(os.path.join(ROOT, "include")))
+    ABI_TABLES = capi.ABI_TABLES                                                     # the registry lib() binds: header file name -> table
+    assert sorted(ABI_TABLES) == public, "capi.ABI_TABLES must list exactly the headers the build lists under include/"
+    tables = (capi.SYMBOLS, capi.CENC_SYMBOLS, capi.CBCS_SYMBOLS, capi.RAOP_RX_SYMBOLS, capi.TS_SYMBOLS, capi.VORBIS_SYMBOLS)
+    assert sorted(map(id, ABI_TABLES.values())) == sorted(map(id, tables))
+    protos = {h: header_prototypes(h) for h in public}
+    assert {h: len(p) for h, p in protos.items()} == {"ohgpu.h": 158, "ohgpu_cenc.h": 13, "ohgpu_cbcs.h": 13, "ohgpu_raop_rx.h": 8,
+                                                      "ohgpu_ts.h": 20, "ohgpu_vorbis.h": 13}
+    found = [n for p in protos.values() for n in p]
+    entries = [n for t in ABI_TABLES.values() for n in t]
+    assert len(found) == len(set(found)) == 225 and len(entries) == len(set(entries))
+    assert set(entries) == set(found)
+    for h, table in ABI_TABLES.items():
+        assert set(table) == set(protos[h]), f"{h}: its table and its prototypes disagree"
+        for name, (res, args) in table.items():
+            want = protos[h][name]
+            got = (_ctypes_class(res), [_ctypes_class(a) for a in args])
+            assert len(got[1]) == len(want[1]), f"{name}: {len(got[1])} argtypes, the header has {len(want[1])} parameters"
+            assert got == want, f"{name}: capi has {got}, {h} declares {want}"
+            fn = getattr(capi.lib(), name)                                           # ... and lib() bound what the registry lists
+            assert fn.restype is res and list(fn.argtypes) == list(args), f"{name}: not bound as its table says"
